@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark: Mrays/s of the path-tracing hot path at 1920x1080, 8 spp (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline (`metric`, `value`, `unit`, `ms_per_step`, ...).
+--dump-outputs DIR writes what the timed path computed in its last step, the frame a caller of PTRenderPassTo receives, as
+DIR/frame.npy (float32, H x W x 4; above DUMP_BUDGET_BYTES a fixed, seeded sample of its pixels instead: frame_sample.npy +
+frame_sample_pixel.npy).  Inputs are seeded, so two builds given the same arguments can be compared output for output.
+--full adds everything else: the frame's CRC-32, the roofline (an untimed full-counter replay of the timed steps + the
+committed profiles), the latency leg, the secondary workloads and the CPU baseline.
 
 N > 1 under a launcher (WORLD_SIZE set, the driver's `python -m torch.distributed.run ... bench.py --gpus N`): this process is
 one rank.  N > 1 WITHOUT a launcher (`python bench.py --gpus 8`): bench.py starts `torch.distributed.run --nproc-per-node N`
@@ -19,7 +26,7 @@ tiles -- 1/N of the frame per rank -- to rank 0, which scatters them into the as
 float is added anywhere, so the frame is bit-identical for every N.  The total work is fixed as N grows ->
 "scaling": "strong".
 
-Rank 0 prints ONE JSON line.  `roofline` prices the render kernel against the 8 TB/s HBM peak with ALGORITHMIC
+Rank 0 prints ONE JSON line.  With --full, `roofline` prices the render kernel against the 8 TB/s HBM peak with ALGORITHMIC
 bytes (SURVEY.md 8d formula over the kernel's own node/triangle/attribute/material/texel counters) divided by the
 kernel's mean duration measured with HIP events on the stream it is launched on.  `cpu_baseline` times the
 reference's tinybvh CPU walkers (oracle/_ref, compiled from /root/reference) on a bounded sample of the very rays
@@ -50,6 +57,7 @@ from unity_webgpu_pathtracer_amd.pathtracer import PathTracer  # noqa: E402
 
 HBM_PEAK_GBPS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (spec)
 SEED0, SEED_STEP = 0x12345678, 0x9E3779B9
+DUMP_BUDGET_BYTES = 64_000_000  # --dump-outputs: at most this much in all (a 1080p frame is 33.2 MB)
 
 WORKLOADS = {
     # BASELINE.json configs[3]: the configuration the >= 1 Gray/s target is quoted on
@@ -63,6 +71,24 @@ WORKLOADS = {
 
 def seed_of(step):
     return (SEED0 + step * SEED_STEP) & 0xFFFFFFFF
+
+
+def write_outputs(dirname, frame, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: the (H, W, 4) float32 frame of the last timed step as frame.npy, or -- when it exceeds `budget` --
+    a fixed, seeded sample of its pixels (frame_sample.npy, (n, 4) float32, at the row-major pixel indices in
+    frame_sample_pixel.npy, float64, ascending).  Returns the names written."""
+    os.makedirs(dirname, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes <= budget:
+        np.save(os.path.join(dirname, "frame.npy"), frame)
+        return ["frame.npy"]
+    pixels = frame.reshape(-1, frame.shape[-1])
+    per_pixel = pixels.shape[1] * 4 + 8                    # float32 channels + one float64 index
+    n = min(pixels.shape[0], max(1, (budget - 4096) // per_pixel))
+    idx = np.sort(np.random.default_rng(0).choice(pixels.shape[0], size=n, replace=False))
+    np.save(os.path.join(dirname, "frame_sample.npy"), pixels[idx])
+    np.save(os.path.join(dirname, "frame_sample_pixel.npy"), idx.astype(np.float64))
+    return ["frame_sample.npy", "frame_sample_pixel.npy"]
 
 
 def cpu_baseline(scene, width, height, spp, pt, budget_rays=1_500_000):
@@ -170,7 +196,14 @@ def main():
                                                          "larger launches.  0 (default) = 1 on one GPU, min(N, 8) on N GPUs, where one rank's share of ONE pass is too small "
                                                          "a launch to fill an MI355X (1/8 of a 1080p pass: 2.92 ms alone, 2.28 ms per pass in batches of eight)")
     ap.add_argument("--master-port", type=int, default=29671, help="rendezvous port when bench.py launches its own ranks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the frame of the last timed step to DIR/*.npy (float32)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: frame CRC-32, roofline (untimed full-counter "
+                                                         "replay), latency leg, secondary workloads, CPU baseline")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.build_device:
+        args.full = True             # the device-built tree is reported against the counters of the full run
 
     # `python bench.py --gpus N` without a launcher: start the ranks ourselves, as a child, BEFORE this process touches HIP
     # (a process that has initialised the GPU must never exec another program; a child process is fine)
@@ -215,7 +248,7 @@ def main():
         args.batch = 1 if world == 1 else min(world, 8)
     args.batch = min(args.batch, 8)
 
-    def run_workload(name, steps, warmup, full, build_device=None):
+    def run_workload(name, steps, warmup, full, build_device=None, keep_frame=False):
         wl = WORKLOADS[name]
         scene = scenes.make_scene(wl["scene"], **wl["kw"])
         pt = PathTracer(scene, device=local_rank, width=W, height=H, samplesPerPass=SPP, maxRayBounces=args.bounces,
@@ -292,7 +325,8 @@ def main():
         tm = pt.timings()
         pt.set_profiling(False)
         final = assembled if distributed else frames[1 - cur]
-        crc = zlib.crc32(final.cpu().numpy().tobytes()) if (full and rank == 0) else 0   # identical for every N: owned tiles sum with zeros
+        final_np = final.cpu().numpy() if ((full or keep_frame) and rank == 0) else None   # before any replay below reuses the frames
+        crc = zlib.crc32(final_np.tobytes()) if (full and rank == 0) else 0   # identical for every N: owned tiles sum with zeros
         rays = torch.tensor([st.rays, st.closestHitRays, st.shadowRays, st.paths], dtype=torch.float64, device=device)
         el = torch.tensor([elapsed], dtype=torch.float64, device=device)
         if distributed:
@@ -308,7 +342,7 @@ def main():
             "msamples_per_s": float(rays[3].item()) / elapsed / 1e6,
             "kernel_ms": region_ms / steps,                        # device time per pass over the timed region (passes may overlap)
             "pass_span_ms": tm.kernelMsTotal / max(1, tm.passes),  # first-launch-to-resolve span of one pass
-            "tris": scene.tri_count, "frame_crc32": crc,
+            "tris": scene.tri_count, "frame_crc32": crc, "_frame": final_np if keep_frame else None,
         }
         if full and rank == 0 and not args.no_alg_replay:
             # algorithmic bytes: replay the same timed steps once, untimed, with the full-counter kernel variant
@@ -356,9 +390,25 @@ def main():
         res["_pt"], res["_scene"] = pt, scene
         return res
 
-    main_res = run_workload(args.workload, args.steps, args.warmup, full=True)
+    main_res = run_workload(args.workload, args.steps, args.warmup, full=args.full, keep_frame=args.dump_outputs is not None)
     out = None
     if rank == 0:
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, main_res["_frame"])
+        main_res["_frame"] = None
+        out = {
+            "metric": "Mrays/s at 1920x1080, 8 spp", "value": round(main_res["mrays_per_s"], 3), "unit": "Mrays/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(main_res["ms_per_step"], 4),
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"{args.workload}: {WORKLOADS[args.workload]['desc']}, {W}x{H}, {SPP} spp/pass, depth {args.bounces}, "
+                                   f"progressive passes (CurrentSample = 8k)",
+                       "tris": main_res["tris"], "rays_per_step": round(main_res["rays_per_step"]),
+                       "msamples_per_s": round(main_res["msamples_per_s"], 3), "schedule": main_res["schedule"],
+                       "passes_in_flight": main_res["passes_in_flight"], "passes_per_launch_sequence": max(1, args.batch),
+                       "sharding": "interleaved 16x16 blocks, one RCCL gather of owned tiles per frame" if distributed else "single GPU"},
+        }
+    if rank == 0 and args.full:
+        out["config"]["frame_crc32"] = main_res["frame_crc32"]
         kernel_s = main_res["kernel_ms"] / 1e3
         main_res.setdefault("alg_bytes_per_launch", 0.0)
         main_res.setdefault("counters_per_launch", {})
@@ -406,35 +456,23 @@ def main():
                            "lane_utilisation": {k: round(v, 3) for k, v in rec.get("pmc", {}).get("lane_utilisation", {}).items() if "trace" in k or "shade" in k}}
         except Exception:
             profile = None
-        out = {
-            "metric": "Mrays/s at 1920x1080, 8 spp", "value": round(main_res["mrays_per_s"], 3), "unit": "Mrays/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(main_res["ms_per_step"], 4),
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{args.workload}: {WORKLOADS[args.workload]['desc']}, {W}x{H}, {SPP} spp/pass, depth {args.bounces}, "
-                                   f"progressive passes (CurrentSample = 8k)",
-                       "tris": main_res["tris"], "rays_per_step": round(main_res["rays_per_step"]),
-                       "msamples_per_s": round(main_res["msamples_per_s"], 3), "schedule": main_res["schedule"],
-                       "passes_in_flight": main_res["passes_in_flight"], "passes_per_launch_sequence": max(1, args.batch),
-                       "frame_crc32": main_res["frame_crc32"],
-                       "sharding": "interleaved 16x16 blocks, one RCCL gather of owned tiles per frame" if distributed else "single GPU"},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic, "traffic_source": traffic_source,
-                         "kernel": {0: "pt_megakernel", 1: "pt_wf_trace_refill (main + tail) + pt_wf_shade (whole pass)", 2: "pt_wf_trace + pt_wf_shade (whole pass)",
-                                    3: "pt_wf_trace_persist + pt_wf_shade (whole pass)", 4: "pt_wf_fused (one persistent launch per pass)"}[main_res["schedule"]],
-                         "kernel_ms": round(main_res["kernel_ms"], 4), "pass_span_ms": round(main_res["pass_span_ms"], 4),
-                         "algorithmic_bytes_per_launch": round(main_res["alg_bytes_per_launch"]),
-                         "counters_per_launch": {k: round(v) for k, v in main_res["counters_per_launch"].items()},
-                         "max_stack_depth": main_res["max_stack_depth"],
-                         "valu_issue": valu,
-                         "binding_roof": ({"name": "valu_issue", "frac": valu["frac"],
-                                           "why": "the scene (148 MB) is Infinity-Cache resident, so the 8 TB/s HBM roof above is nominal (SURVEY.md 8d defines it); "
-                                                  "what the pass saturates first is VALU issue under divergence: wave instructions of a pass / measured issue peak"}
-                                          if valu else None),
-                         "profile": profile,
-                         "note": "rank-0 kernels; achieved = algorithmic bytes of a pass / its device time (HIP events on the context stream, passes overlap); "
-                                 "the scene is Infinity-Cache resident, so HBM is the nominal roof only: the pass is bound by VALU issue at 40-55 % lane "
-                                 "utilisation (valu_issue.frac), with the texture-data path ~70 % busy (DESIGN.md 5.4)"},
-        }
+        out["roofline"] = {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                           "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic, "traffic_source": traffic_source,
+                           "kernel": {0: "pt_megakernel", 1: "pt_wf_trace_refill (main + tail) + pt_wf_shade (whole pass)", 2: "pt_wf_trace + pt_wf_shade (whole pass)",
+                                      3: "pt_wf_trace_persist + pt_wf_shade (whole pass)", 4: "pt_wf_fused (one persistent launch per pass)"}[main_res["schedule"]],
+                           "kernel_ms": round(main_res["kernel_ms"], 4), "pass_span_ms": round(main_res["pass_span_ms"], 4),
+                           "algorithmic_bytes_per_launch": round(main_res["alg_bytes_per_launch"]),
+                           "counters_per_launch": {k: round(v) for k, v in main_res["counters_per_launch"].items()},
+                           "max_stack_depth": main_res["max_stack_depth"],
+                           "valu_issue": valu,
+                           "binding_roof": ({"name": "valu_issue", "frac": valu["frac"],
+                                             "why": "the scene (148 MB) is Infinity-Cache resident, so the 8 TB/s HBM roof above is nominal (SURVEY.md 8d defines it); "
+                                                    "what the pass saturates first is VALU issue under divergence: wave instructions of a pass / measured issue peak"}
+                                            if valu else None),
+                           "profile": profile,
+                           "note": "rank-0 kernels; achieved = algorithmic bytes of a pass / its device time (HIP events on the context stream, passes overlap); "
+                                   "the scene is Infinity-Cache resident, so HBM is the nominal roof only: the pass is bound by VALU issue at 40-55 % lane "
+                                   "utilisation (valu_issue.frac), with the texture-data path ~70 % busy (DESIGN.md 5.4)"}
     if out is not None and "latency_mode" in main_res:
         out["latency_mode"] = main_res["latency_mode"]
     if args.build_device and not distributed and out is not None:
@@ -453,7 +491,7 @@ def main():
             "nodes": int(r["_pt"]._bvhScene.bvh_nodes.nbytes // 80), "build_ms": r["_pt"]._bvhScene.build_ms,
             "what": "PTBuildBVHDevice tree (hit-equal, not byte-equal, to BuildBVH's): frames differ only where ties are broken differently"}
         r["_pt"].close()
-    if not args.no_extra and not distributed:
+    if args.full and not args.no_extra and not distributed:
         extra = {}
         for name in WORKLOADS:
             if name == args.workload:
@@ -464,7 +502,7 @@ def main():
                            "schedule": r["schedule"]}
         if out is not None:
             out["other_workloads"] = extra
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         wl = WORKLOADS[args.workload]
         scene = main_res.get("_scene")
         pt = main_res.get("_pt")

@@ -8,6 +8,11 @@
                 (oracle/ref_driver_cwbvh.cpp) -- the CPU twin of the shader's RayIntersectBvh.
   frame_*.npz   frames rendered by the CPU oracle (regression pin of the restatement itself; the reference's
                 shader cannot be executed here, so these are NOT reference outputs -- see DESIGN.md).
+  ref_builds.npz, ref_walker_sponza03.npz, ref_cwbvh_walker_sponza03.npz  what the reference plugin and its two walkers
+                return for the inputs of the *_live tests (tests/test_bvh_builder.py, tests/test_oracle.py), which use them
+                where oracle/_ref is not built: `--only live`.
+  helmet_geometry.npz  the reference snapshot's one real model, Assets/Examples/Models/DamagedHelmet.glb, as a .glb
+                with its images emptied (JSON chunk + geometry buffer views only): `--only helmet PATH_TO_GLB`.
 
 Fixtures are data only (inputs and expected outputs); no reference source text is stored.
 """
@@ -144,9 +149,62 @@ def main():
     print("present_cases, ingest_mesh_zoo written")
 
 
+def gen_live_pins():
+    """ref_builds.npz, ref_walker_sponza03.npz, ref_cwbvh_walker_sponza03.npz: the reference's outputs for the very inputs
+    of the *_live tests, which build them with their own helpers (imported from tests/)."""
+    import hashlib
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_bvh_builder
+    import test_oracle
+    sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()  # noqa: E731
+    cases, instances = test_bvh_builder._live_cases()
+    cw = [pyoracle.ref_build_cwbvh(v) for v in cases]
+    tl = [pyoracle.ref_build_tlas(inst) for inst in instances]
+    np.savez_compressed(os.path.join(HERE, "ref_builds.npz"), cwbvh_nodes=np.array([sha(n) for n, _ in cw]),
+                        cwbvh_tris=np.array([sha(t) for _, t in cw]), tlas_nodes=np.array([sha(n) for n, _ in tl]),
+                        tlas_indices=np.array([sha(i) for _, i in tl]))
+    s, raw = test_oracle._walker_live_case()
+    t, prim = test_oracle._ref_walker_trace(pyoracle.load_ref_tinybvh(), s, raw)
+    np.savez_compressed(os.path.join(HERE, "ref_walker_sponza03.npz"), t=t, prim=prim)
+    s, raw = test_oracle._cwbvh_walker_live_case()
+    records, nodes, tris = pyoracle.ref_cwbvh_trace(s.vertices, raw, threads=4)
+    np.savez_compressed(os.path.join(HERE, "ref_cwbvh_walker_sponza03.npz"), records=records, node_sha256=sha(nodes), tri_sha256=sha(tris))
+    print("ref_builds, ref_walker_sponza03, ref_cwbvh_walker_sponza03 written")
+
+
+def gen_helmet_geometry(src):
+    """helmet_geometry.npz: the .glb at `src` with every buffer view that no accessor reads (the embedded images) cut to zero
+    length; the JSON chunk (nodes, meshes, materials, textures, images) is kept, so load_glb(load_images=False) reads the
+    same meshes and materials from it as from the original."""
+    import json
+    import struct
+    from unity_webgpu_pathtracer_amd import ingest
+    doc, blob = ingest._glb_chunks(open(src, "rb").read())
+    used = {a["bufferView"] for a in doc["accessors"] if "bufferView" in a}
+    out = bytearray()
+    for i, bv in enumerate(doc["bufferViews"]):
+        start, length = bv.get("byteOffset", 0), bv["byteLength"]
+        if i in used:
+            out += bytes(-len(out) % 4)
+            bv["byteOffset"] = len(out)
+            out += blob[start:start + length]
+        else:
+            bv["byteOffset"], bv["byteLength"] = 0, 0
+    out += bytes(-len(out) % 4)
+    doc["buffers"] = [{"byteLength": len(out)}]
+    js = json.dumps(doc, separators=(",", ":")).encode()
+    js += b" " * (-len(js) % 4)
+    glb = struct.pack("<III", 0x46546C67, 2, 12 + 8 + len(js) + 8 + len(out)) + struct.pack("<II", len(js), 0x4E4F534A) + js \
+        + struct.pack("<II", len(out), 0x004E4942) + bytes(out)
+    np.savez_compressed(os.path.join(HERE, "helmet_geometry.npz"), glb=np.frombuffer(glb, np.uint8))
+    print(f"helmet_geometry written ({len(glb)} bytes of .glb)")
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 2 and sys.argv[1] == "--only":       # regenerate one family without touching the others
+    if len(sys.argv) > 3 and sys.argv[1:3] == ["--only", "helmet"]:
+        gen_helmet_geometry(sys.argv[3])
+    elif len(sys.argv) > 2 and sys.argv[1] == "--only":       # regenerate one family without touching the others
         pyoracle.build(ref=True)
-        {"trace_cwbvh": gen_trace_cwbvh}[sys.argv[2]]()
+        {"trace_cwbvh": gen_trace_cwbvh, "live": gen_live_pins}[sys.argv[2]]()
     else:
         main()

@@ -1,7 +1,9 @@
 """BuildBVH / BuildTLAS of the drop-in are byte-identical to the reference plugin's output:
 against committed golden dumps (made by tests/golden/make_golden.py from the reference compiled in place)
-and, when oracle/_ref is present, against the reference plugin itself on larger and degenerate inputs."""
+and against the reference plugin itself on larger and degenerate inputs (live when oracle/_ref is present, else through
+the digests of its outputs in tests/golden/ref_builds.npz)."""
 import glob
+import hashlib
 import os
 
 import numpy as np
@@ -46,9 +48,9 @@ def _soup(rng, n, spread, size):
     return out
 
 
-def test_against_reference_plugin_live(oracle):
-    if oracle.load_ref_plugin() is None:
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
+def _live_cases():
+    """The inputs of test_against_reference_plugin_live (also read by tests/golden/make_golden.py): vertex arrays for
+    BuildBVH, instance arrays for BuildTLAS."""
     rng = np.random.RandomState(5)
     cases = [scenes.material_zoo().vertices, scenes.sponza_atrium(tex_size=4, detail=0.2).vertices,
              scenes.bunny_box(frequency=12).vertices, _soup(rng, 5000, 10, 0.3), _soup(rng, 2, 1, 1), _soup(rng, 7, 1, 1)]
@@ -58,18 +60,41 @@ def test_against_reference_plugin_live(oracle):
     line = np.zeros((30, 4), np.float32)
     line[:, 0] = np.repeat(np.arange(10), 3) + np.tile([0, 0.5, 0.25], 10)   # degenerate: zero extent on two axes
     cases.append(line)
-    for v in cases:
-        rn, rt = oracle.ref_build_cwbvh(v)
-        mn, mt = plugin.build_cwbvh(v)
-        assert np.array_equal(rn, mn) and np.array_equal(rt, mt)
+    instances = []
     for n in (1, 3, 64, 257):
         inst = np.zeros(n, abi.BLAS_INSTANCE)
         c = rng.uniform(-20, 20, (n, 3))
         e = rng.uniform(0.0, 3, (n, 3))
         inst["aabbMin"], inst["aabbMax"] = c - e, c + e
-        rn, ri = oracle.ref_build_tlas(inst)
+        instances.append(inst)
+    return cases, instances
+
+
+def _sha256(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def test_against_reference_plugin_live(oracle):
+    """The reference plugin itself (oracle/_ref) on larger and degenerate inputs; where it is not built, its outputs for the
+    same inputs are pinned by their SHA-256 digests in tests/golden/ref_builds.npz (tests/golden/make_golden.py)."""
+    live = oracle.load_ref_plugin() is not None
+    g = np.load(os.path.join(GOLDEN, "ref_builds.npz"))
+    cases, instances = _live_cases()
+    assert len(g["cwbvh_nodes"]) == len(cases) and len(g["tlas_nodes"]) == len(instances)
+    for i, v in enumerate(cases):
+        mn, mt = plugin.build_cwbvh(v)
+        if live:
+            rn, rt = oracle.ref_build_cwbvh(v)
+            assert np.array_equal(rn, mn) and np.array_equal(rt, mt)
+        else:
+            assert _sha256(mn) == g["cwbvh_nodes"][i] and _sha256(mt) == g["cwbvh_tris"][i], i
+    for i, inst in enumerate(instances):
         mn, mi = plugin.build_tlas(inst)
-        assert np.array_equal(rn, mn) and np.array_equal(ri, mi)
+        if live:
+            rn, ri = oracle.ref_build_tlas(inst)
+            assert np.array_equal(rn, mn) and np.array_equal(ri, mi)
+        else:
+            assert _sha256(mn) == g["tlas_nodes"][i] and _sha256(mi) == g["tlas_indices"][i], i
 
 
 def test_benchmark_scene_sizes():

@@ -5,11 +5,13 @@ import json
 import os
 import subprocess
 import sys
+import zlib
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--workload", "cornell", "--width", "320", "--height", "200", "--steps", "3", "--warmup", "1", "--no-extra", "--no-cpu-baseline"]
+SMALL = ["--workload", "cornell", "--width", "320", "--height", "200", "--steps", "3", "--warmup", "1", "--no-extra", "--no-cpu-baseline", "--full"]
 
 
 def _last_json(out):
@@ -19,9 +21,9 @@ def _last_json(out):
 
 
 @pytest.mark.gpu
-def test_bench_contract_and_two_rank_rehearsal():
+def test_bench_contract_and_two_rank_rehearsal(tmp_path):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    one = _last_json(subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + SMALL,
+    one = _last_json(subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + SMALL + ["--dump-outputs", str(tmp_path / "one")],
                                              env=env, timeout=600, stderr=subprocess.STDOUT))
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline"):
@@ -29,6 +31,10 @@ def test_bench_contract_and_two_rank_rehearsal():
     assert one["n_gpus"] == 1 and one["steps"] == 3 and one["value"] > 0 and one["vs_baseline"] is None
     assert set(("bound", "achieved", "peak", "unit", "frac", "traffic")) <= set(one["roofline"])
     assert one["roofline"]["achieved"] > 0
+    # --dump-outputs: the frame of the last timed step, the very frame whose CRC-32 the full run reports
+    frame = np.load(tmp_path / "one" / "frame.npy")
+    assert frame.dtype == np.float32 and frame.shape == (200, 320, 4)
+    assert zlib.crc32(frame.tobytes()) == one["config"]["frame_crc32"] != 0
 
     two = _last_json(subprocess.check_output(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
@@ -129,3 +135,21 @@ def test_pack_unpack_kernels_match_the_numpy_mirror():
             assert np.array_equal(packed.cpu().numpy(), distributed.pack_tiles_numpy(frame.cpu().numpy(), rank, world))
             pt.close()
         assert torch.equal(out, frame)
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_only(tmp_path):
+    """Without --full: the headline and its timed steps only, and --dump-outputs writes the same frame as the full run."""
+    plain_args = [a for a in SMALL if a not in ("--no-extra", "--no-cpu-baseline", "--full")]
+    plain = _last_json(subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + plain_args
+                                               + ["--dump-outputs", str(tmp_path / "plain")], timeout=600, stderr=subprocess.STDOUT))
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "config"):
+        assert key in plain
+    assert plain["steps"] == 3 and plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["higher_is_better"] is True
+    for key in ("roofline", "latency_mode", "other_workloads", "cpu_baseline"):
+        assert key not in plain
+    full = _last_json(subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + SMALL
+                                              + ["--dump-outputs", str(tmp_path / "full")], timeout=600, stderr=subprocess.STDOUT))
+    a, b = np.load(tmp_path / "plain" / "frame.npy"), np.load(tmp_path / "full" / "frame.npy")
+    assert np.array_equal(a.view(np.uint32), b.view(np.uint32)) and zlib.crc32(a.tobytes()) == full["config"]["frame_crc32"]
+    assert plain["config"]["rays_per_step"] == full["config"]["rays_per_step"]

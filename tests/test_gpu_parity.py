@@ -515,7 +515,7 @@ def test_c4_benched_sponza_tex1024_windows_and_bench_crc(oracle):
     print(f"[parity] benched sponza frame after passes 0..2: crc32 = {crc}")
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--no-extra", "--no-cpu-baseline", "--no-alg-replay"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-extra", "--no-cpu-baseline", "--no-alg-replay"],
                          capture_output=True, text=True, cwd=root, timeout=600)
     line = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert line, out.stderr[-2000:]

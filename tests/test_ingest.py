@@ -8,6 +8,8 @@ import pytest
 
 from unity_webgpu_pathtracer_amd import abi, ingest, plugin, scenes
 
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
 
 def _trs():
     a, b = 0.7, -0.4
@@ -316,10 +318,12 @@ def test_glb_rejects_malformed_files(tmp_path):
         ingest.load_glb(path)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/Assets/Examples/Models/DamagedHelmet.glb"), reason="reference snapshot not present (GPU box)")
-def test_glb_reader_on_the_reference_helmet():
-    """The one real model in the reference snapshot, read as DATA (no reference code runs): geometry, transform, material."""
-    meshes, materials, images = ingest.load_glb("/root/reference/Assets/Examples/Models/DamagedHelmet.glb", load_images=False)
+def test_glb_reader_on_the_reference_helmet(tmp_path):
+    """The one real model in the reference snapshot, read as DATA (no reference code runs): geometry, transform, material.
+    tests/golden/helmet_geometry.npz holds the model's .glb with its images emptied (tests/golden/make_golden.py)."""
+    path = tmp_path / "DamagedHelmet.glb"
+    path.write_bytes(np.load(os.path.join(GOLDEN, "helmet_geometry.npz"))["glb"].tobytes())
+    meshes, materials, images = ingest.load_glb(str(path), load_images=False)
     assert len(meshes) == 1 and meshes[0].triangle_count == 15452 and meshes[0].positions.shape == (14556, 3)
     assert meshes[0].normals is not None and meshes[0].uvs is not None and meshes[0].indices.dtype == np.uint16
     assert np.isfinite(meshes[0].positions).all() and np.allclose(np.linalg.norm(meshes[0].normals, axis=1), 1.0, atol=1e-3)

@@ -50,12 +50,9 @@ def test_traversal_matches_reference_walker_golden(oracle):
     assert steps.max() < 200 and n == 4000
 
 
-def test_traversal_matches_reference_walker_live(oracle):
-    ref = oracle.load_ref_tinybvh()
-    if ref is None:
-        pytest.skip("oracle/_ref not built")
+def _walker_live_case():
+    """Scene and rays of test_traversal_matches_reference_walker_live (also read by tests/golden/make_golden.py)."""
     s = scenes.sponza_atrium(tex_size=4, detail=0.3)
-    b = _buffers(oracle, s)
     rng = np.random.RandomState(9)
     n = 20000
     raw = np.zeros((n, 8), np.float32)
@@ -65,12 +62,33 @@ def test_traversal_matches_reference_walker_live(oracle):
     d = rng.normal(0, 1, (n, 3))
     raw[:, 3:6] = d / np.linalg.norm(d, axis=1, keepdims=True)
     raw[:, 6] = 1e5
+    return s, raw
+
+
+def _ref_walker_trace(ref, s, raw):
+    """(t, prim) of the reference's BVH::Intersect / IsOccluded (oracle/_ref/libref_tinybvh.so) for every ray of raw."""
+    n = raw.shape[0]
     verts = np.ascontiguousarray(s.vertices, np.float32)
     h = ref.ref_bvh_build(verts.ctypes.data_as(C.c_void_p), s.tri_count, None)
     rt = np.zeros(n, np.float32)
     rp = np.zeros(n, np.uint32)
     ref.ref_bvh_trace(h, raw.ctypes.data_as(C.c_void_p), n, 4, rt.ctypes.data_as(C.c_void_p), rp.ctypes.data_as(C.c_void_p))
     ref.ref_bvh_destroy(h)
+    return rt, rp
+
+
+def test_traversal_matches_reference_walker_live(oracle):
+    """The reference's walker live when oracle/_ref is built, else its answers for the same rays as stored in
+    tests/golden/ref_walker_sponza03.npz (tests/golden/make_golden.py)."""
+    ref = oracle.load_ref_tinybvh()
+    s, raw = _walker_live_case()
+    b = _buffers(oracle, s)
+    if ref is not None:
+        rt, rp = _ref_walker_trace(ref, s, raw)
+    else:
+        g = np.load(os.path.join(GOLDEN, "ref_walker_sponza03.npz"))
+        rt, rp = g["t"], g["prim"]
+        assert rt.shape == rp.shape == (raw.shape[0],)
     t, prim, _ = oracle.trace(b, _rays(oracle, raw))
     hit = (rp != 0xFFFFFFFF) & (rt > 1e-3)
     assert ((prim != 0xFFFFFFFF) == (rp != 0xFFFFFFFF))[hit | (rp == 0xFFFFFFFF)].mean() > 0.999
@@ -112,9 +130,8 @@ def test_traversal_matches_reference_cwbvh_walker_golden(oracle, name, make):
     _check_against_cwbvh_walker(oracle, make(), g["rays"], g["records"], g["node_crc"], g["tri_crc"])
 
 
-def test_traversal_matches_reference_cwbvh_walker_live(oracle):
-    if oracle.load_ref_cwbvh() is None:
-        pytest.skip("oracle/_ref/libref_cwbvh.so not built")
+def _cwbvh_walker_live_case():
+    """Scene and rays of test_traversal_matches_reference_cwbvh_walker_live (also read by tests/golden/make_golden.py)."""
     s = scenes.sponza_atrium(tex_size=4, detail=0.3)
     rng = np.random.RandomState(77)
     n = 60000
@@ -123,10 +140,25 @@ def test_traversal_matches_reference_cwbvh_walker_live(oracle):
     d = rng.normal(0, 1, (n, 3))
     raw[:, 3:6] = d / np.linalg.norm(d, axis=1, keepdims=True)
     raw[:, 6] = 1e5
-    records, rn, rt = oracle.ref_cwbvh_trace(s.vertices, raw, threads=4)
+    return s, raw
+
+
+def test_traversal_matches_reference_cwbvh_walker_live(oracle):
+    """The reference's CWBVH walker live when oracle/_ref is built, else its records and the SHA-256 of the node and triangle
+    bytes it walked, as stored in tests/golden/ref_cwbvh_walker_sponza03.npz (tests/golden/make_golden.py)."""
+    import hashlib
+    s, raw = _cwbvh_walker_live_case()
     nodes, tris = plugin.build_cwbvh(s.vertices)
-    assert np.array_equal(rn, np.ascontiguousarray(nodes).view(np.uint8).ravel())       # scalar pipeline in the AVX TU == plugin bytes == ours
-    assert np.array_equal(rt, np.ascontiguousarray(tris).view(np.uint8).ravel())
+    if oracle.load_ref_cwbvh() is not None:
+        records, rn, rt = oracle.ref_cwbvh_trace(s.vertices, raw, threads=4)
+        assert np.array_equal(rn, np.ascontiguousarray(nodes).view(np.uint8).ravel())       # scalar pipeline in the AVX TU == plugin bytes == ours
+        assert np.array_equal(rt, np.ascontiguousarray(tris).view(np.uint8).ravel())
+    else:
+        g = np.load(os.path.join(GOLDEN, "ref_cwbvh_walker_sponza03.npz"))
+        records = g["records"]
+        assert records.shape == (raw.shape[0], 4)
+        assert hashlib.sha256(np.ascontiguousarray(nodes).tobytes()).hexdigest() == g["node_sha256"]      # the bytes the walker traversed
+        assert hashlib.sha256(np.ascontiguousarray(tris).tobytes()).hexdigest() == g["tri_sha256"]
     _check_against_cwbvh_walker(oracle, s, raw, records)
 
 

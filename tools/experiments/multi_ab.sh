@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: tools/experiments/multi_ab.sh [variants...]: main + bunny + Cornell (bench.py), the HAS_TLAS scene and schedule 4 (one pass in flight) per build
-one() { python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-alg-replay --latency-steps 0 2>/dev/null | python -c 'import sys, json
+one() { python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-alg-replay --latency-steps 0 2>/dev/null | python -c 'import sys, json
 for l in sys.stdin:
     if l.startswith("{"):
         j = json.loads(l); print("sponza", j["value"], "|", " | ".join(k + " " + str(v.get("mrays_per_s")) for k, v in j.get("other_workloads", {}).items()), end=" | ")'
