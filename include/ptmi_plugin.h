@@ -427,6 +427,66 @@ PT_API int PTTraceRays(PTContext* ctx, const PTRay* dRays, uint64_t count, uint3
 PT_API int PTTraceRaysHost(PTContext* ctx, const PTRay* rays, uint64_t count, uint32_t flags,
                            PTRayHit* hits, PTRaySurface* surface);
 
+/* =====================================================================================================================
+ * Part 4: guide buffers and denoising.  First-hit guides (albedo, normal, depth) rendered on the GPU with the render's own
+ * traversal, and an edge-avoiding a-trous filter (SVGF's spatial half) that runs between the Output frame and PTPresent.
+ *
+ * Guides (PTRenderGuides), for every pixel (x, y) of params' OutputWidth x OutputHeight, with S samples and n = sqrt(S):
+ *  - Sample (i, j), taken in the order j = 0..n-1, i = 0..n-1 (i fastest), is the pinhole ray through
+ *    (x + (i + 0.5) / n, y + (j + 0.5) / n): generate_camera_ray's arithmetic on CamInvProj / CamToWorld with the jitter
+ *    removed (every offset is exact in float32; for S = 1 it is the ray through the pixel centre).  Aperture, FocalLength,
+ *    the seeds and DispatchGroups are ignored: no thin lens.  Each sample is a closest-hit walk with tmax = PT_FAR_PLANE,
+ *    the same as PTTraceRays(PT_QUERY_CLOSEST | PT_QUERY_SURFACE).  Flat and HAS_TLAS scenes.
+ *  - Albedo guide: rgb = the material's base colour after texturing (GetBaseColorOpacity, as the render's material fetch
+ *    computes it), summed in float32 in sample order starting from 0, a missing sample contributing (1, 1, 1), then divided
+ *    by S.  w = (hitting samples) / S: the coverage mask, 0 = background.
+ *  - Normal + depth guide: xyz = the interpolated shading normal of the hitting samples (PTRaySurface.normal): with one
+ *    hitting sample that normal as it is, with more their float32 sum in sample order normalised with the device's
+ *    normalize3 (0 if the sum vanishes); 0 where nothing hit.  w = the mean hit distance over the hitting samples (their
+ *    sum in sample order divided by their count), 0 where nothing hit.
+ *  - The guides ignore opacity and alpha cutouts and do not see the visible analytic lights.
+ *  - Guides count nothing in PTStats and are not part of PTGetTimings.
+ *
+ * Filter (PTDenoise): DESIGN.md 5.9 gives the exact formula.  Pixels with coverage 0 pass through bit for bit and are never
+ * taps; iterations == 0 returns the input's bits; out.a is always the input's alpha.
+ *
+ * Memory: guide and filter buffers belong to the context, are allocated on first use, regrown when the size changes and
+ * freed by PTDestroy.  A context that never calls these functions allocates nothing for them.
+ * Errors: PT_ERR_INVALID_ARG for a NULL context or required pointer, samplesPerPixel not 1, 4 or 16, iterations outside
+ * 0..8, a sigma that is NaN or <= 0, an unknown flag bit, a structSize below sizeof(PTDenoiseParams) of this header, and
+ * PTDenoise without guides or with guides of another size than the frame; PT_ERR_NO_SCENE for PTRenderGuides before
+ * PTSetScene.  There is no CPU fallback.
+ * ===================================================================================================================== */
+#define PT_DENOISE_DEMODULATE_ALBEDO 0x1u   /* filter colour / max(albedo, 1e-3), multiply back afterwards */
+
+typedef struct PTDenoiseParams {  /* 24 bytes; versioned like PTFrameParams: min(structSize, sizeof) read, rest zero */
+    uint32_t structSize;          /* = sizeof(PTDenoiseParams) of the host's header */
+    int32_t  iterations;          /* a-trous levels 0..8 (steps 1, 2, 4, ...); suggested 5 */
+    float    sigmaLuminance;      /* suggested 4 */
+    float    sigmaNormal;         /* exponent of the normal weight; suggested 128 */
+    float    sigmaDepth;          /* suggested 1 */
+    uint32_t flags;               /* PT_DENOISE_DEMODULATE_ALBEDO; suggested on */
+} PTDenoiseParams;
+
+#ifdef __cplusplus
+static_assert(sizeof(PTDenoiseParams) == 24, "PTDenoiseParams is 24 bytes");
+#else
+_Static_assert(sizeof(PTDenoiseParams) == 24, "PTDenoiseParams is 24 bytes");
+#endif
+
+/* First-hit guides for the camera of `params` (its size, CamInvProj, CamToWorld); samplesPerPixel is 1, 4 or 16.
+ * Stream-ordered on the context's stream; returns before the guides are written. */
+PT_API int PTRenderGuides(PTContext* ctx, const PTFrameParams* params, int samplesPerPixel);
+/* dDst = denoise(dSrc), both DEVICE pointers to guide-size float4 frames; dSrc == NULL reads the current Output frame (which
+ * must then have the guides' size) and is never written unless it is dDst; dSrc == dDst is allowed.  Stream-ordered after
+ * every pass launched so far, the same as PTPresent. */
+PT_API int PTDenoise(PTContext* ctx, const PTDenoiseParams* params, const void* dSrc, void* dDst);
+/* Denoises the current Output frame into host memory (width*height float4); synchronous. */
+PT_API int PTDenoiseToHost(PTContext* ctx, const PTDenoiseParams* params, float* dstRGBA, uint64_t dstFloats);
+/* Device pointer of guide `which`: 0 albedo + coverage, 1 normal + depth (width*height float4 each); NULL before the first
+ * PTRenderGuides or for another `which`.  A host may write its own guides there before PTDenoise. */
+PT_API void* PTGetGuidePointer(PTContext* ctx, int which);
+
 /* Text of the last error on the calling thread ("" if none). */
 PT_API const char* PTGetLastError(void);
 /* Library/ABI version: (major << 16) | minor. */

@@ -1,0 +1,265 @@
+"""Guides and denoising (include/ptmi_plugin.h Part 4) without a GPU: exports, struct layout, argument checks, kernel resources,
+and the float64 numpy restatement of the a-trous filter with its own properties.  tests/test_gpu_denoise.py
+holds the GPU kernels to this restatement."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+from unity_webgpu_pathtracer_amd import abi, plugin
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "unity_webgpu_pathtracer_amd", "csrc")
+DENOISE_SYMBOLS = ["PTRenderGuides", "PTDenoise", "PTDenoiseToHost", "PTGetGuidePointer"]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the filter, restated in float64
+# ---------------------------------------------------------------------------------------------------------------------------
+H5 = np.array([1 / 16, 1 / 4, 3 / 8, 1 / 4, 1 / 16])
+K3 = np.array([1 / 4, 1 / 2, 1 / 4])
+
+
+def _lum(e):
+    return 0.2126 * e[..., 0] + 0.7152 * e[..., 1] + 0.0722 * e[..., 2]
+
+
+def _shift(a, dx, dy, fill=0.0):
+    """b[y, x] = a[y + dy, x + dx] where that lies in the image, else `fill`; and the mask of where it does."""
+    h, w = a.shape[:2]
+    b = np.full_like(a, fill)
+    m = np.zeros((h, w), bool)
+    ys, yd = (slice(dy, h), slice(0, h - dy)) if dy >= 0 else (slice(0, h + dy), slice(-dy, h))
+    xs, xd = (slice(dx, w), slice(0, w - dx)) if dx >= 0 else (slice(0, w + dx), slice(-dx, w))
+    if h - abs(dy) > 0 and w - abs(dx) > 0:
+        b[yd, xd] = a[ys, xs]
+        m[yd, xd] = True
+    return b, m
+
+
+def denoise_ref(color, albedo, normal_depth, iterations=5, sigma_l=4.0, sigma_n=128.0, sigma_z=1.0, demodulate=True):
+    """The a-trous filter of PTDenoise in float64.  color, albedo, normal_depth: (H, W, 4).  Returns (H, W, 4) float64."""
+    c = color.astype(np.float64)
+    if iterations == 0:
+        return c.copy()
+    a = albedo.astype(np.float64)
+    g = normal_depth.astype(np.float64)
+    cov = a[..., 3] > 0
+    amax = np.maximum(a[..., :3], 1e-3)
+    e = c[..., :3] / amax if demodulate else c[..., :3].copy()
+    l = _lum(e)
+    # prepass: luminance variance over the covered 3x3, depth gradient
+    lq = [(_shift(l, dx, dy)[0], _shift(cov, dx, dy, False)[0]) for dy in (-1, 0, 1) for dx in (-1, 0, 1)]
+    cnt = sum(m.astype(np.float64) for _, m in lq)
+    cnt = np.maximum(cnt, 1)
+    mean = sum(np.where(m, v, 0.0) for v, m in lq) / cnt
+    var = np.maximum(sum(np.where(m, (v - mean) ** 2, 0.0) for v, m in lq) / cnt, 0.0)
+    z = g[..., 3]
+    grad = []
+    for dx, dy in ((1, 0), (0, 1)):
+        zp, cp = _shift(z, dx, dy)[0], _shift(cov, dx, dy, False)[0]
+        zm, cm = _shift(z, -dx, -dy)[0], _shift(cov, -dx, -dy, False)[0]
+        grad.append(np.where(cm & cp, (zp - zm) * 0.5, np.where(cp, zp - z, np.where(cm, z - zm, 0.0))))
+    gx, gy = grad
+    n = g[..., :3]
+    v = var
+    for k in range(iterations):
+        s = 1 << k
+        vw = np.zeros_like(v)
+        vs = np.zeros_like(v)
+        for dy in (-1, 0, 1):
+            for dx in (-1, 0, 1):
+                vq, _ = _shift(v, dx, dy)
+                cq = _shift(cov, dx, dy, False)[0]
+                wk = K3[dx + 1] * K3[dy + 1] * cq
+                vw += wk
+                vs += wk * vq
+        gv = np.maximum(vs / np.maximum(vw, 1e-300), 0.0)
+        den_l = sigma_l * np.sqrt(gv) + 1e-6
+        sw = np.zeros_like(v)
+        sv = np.zeros_like(v)
+        se = np.zeros_like(e)
+        for dy in range(-2, 3):
+            for dx in range(-2, 3):
+                eq, _ = _shift(e, s * dx, s * dy)
+                vq, _ = _shift(v, s * dx, s * dy)
+                nq, _ = _shift(n, s * dx, s * dy)
+                zq, _ = _shift(z, s * dx, s * dy)
+                cq = _shift(cov, s * dx, s * dy, False)[0]
+                wl = np.exp(-np.abs(l - _lum(eq)) / den_l)
+                wn = np.maximum(0.0, np.sum(n * nq, axis=-1)) ** sigma_n
+                dz = np.abs(gx * (s * dx) + gy * (s * dy))
+                wz = np.exp(-np.abs(z - zq) / (sigma_z * dz + 1e-3 * z + 1e-6))
+                w = H5[dx + 2] * H5[dy + 2] * wl * wn * wz * cq
+                sw += w
+                sv += w * w * vq
+                se += w[..., None] * eq
+        ok = cov & (sw > 0)
+        swd = np.where(ok, sw, 1.0)
+        e = np.where(ok[..., None], se / swd[..., None], e)
+        v = np.where(ok, sv / (swd * swd), v)
+        l = _lum(e)
+    out = c.copy()
+    rgb = e * amax if demodulate else e
+    out[..., :3] = np.where(cov[..., None], rgb, c[..., :3])
+    return out
+
+
+def random_guides(h, w, rng, hole_fraction=0.15):
+    """Smooth-ish guides with background holes: albedo in [0.05, 1] (coverage 1 or 0.25..1), normals near a slowly turning
+    axis, depth a ramp plus noise; holes have coverage 0, normal 0 and depth 0."""
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+    albedo = np.ones((h, w, 4))
+    albedo[..., :3] = rng.uniform(0.05, 1.0, (h, w, 3))
+    albedo[..., 3] = rng.choice([1.0, 0.25, 0.5, 0.75], (h, w), p=[0.7, 0.1, 0.1, 0.1])
+    n = np.stack([np.sin(xx / w * 2), np.cos(yy / h * 2), np.ones_like(xx)], -1) + rng.normal(0, 0.05, (h, w, 3))
+    n /= np.linalg.norm(n, axis=-1, keepdims=True)
+    z = 2.0 + 3.0 * xx / w + yy / h + rng.uniform(0, 0.05, (h, w))
+    hole = rng.uniform(0, 1, (h, w)) < hole_fraction
+    hole[h // 3: h // 3 + 5, w // 4: w // 4 + 7] = True
+    albedo[hole] = (1.0, 1.0, 1.0, 0.0)
+    nd = np.concatenate([n, z[..., None]], -1)
+    nd[hole] = 0.0
+    return albedo.astype(np.float32), nd.astype(np.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the restatement's own properties
+# ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("iterations", [1, 3, 5])
+def test_constant_colour_is_a_fixed_point(iterations):
+    """Weights are normalised, so a constant filtered signal stays constant for any guides: the colour itself without
+    demodulation, and with demodulation whenever the albedo is constant too."""
+    rng = np.random.RandomState(1)
+    albedo, nd = random_guides(23, 31, rng)
+    color = np.zeros((23, 31, 4), np.float32)
+    color[...] = (0.3, 0.6, 0.9, 0.5)
+    out = denoise_ref(color, albedo, nd, iterations, demodulate=False)
+    assert np.allclose(out, color, rtol=1e-12, atol=1e-12)
+    albedo[albedo[..., 3] > 0, :3] = (0.2, 0.4, 0.8)
+    out = denoise_ref(color, albedo, nd, iterations, demodulate=True)
+    assert np.allclose(out, color, rtol=1e-12, atol=1e-12)
+
+
+def test_zero_iterations_is_the_identity():
+    rng = np.random.RandomState(2)
+    albedo, nd = random_guides(17, 13, rng)
+    color = rng.uniform(0, 4, (17, 13, 4)).astype(np.float32)
+    assert (denoise_ref(color, albedo, nd, 0) == color.astype(np.float64)).all()
+
+
+@pytest.mark.parametrize("demodulate", [True, False])
+def test_background_passes_through_and_is_no_tap(demodulate):
+    rng = np.random.RandomState(3)
+    albedo, nd = random_guides(29, 37, rng, hole_fraction=0.3)
+    color = rng.uniform(0, 4, (29, 37, 4)).astype(np.float32)
+    out = denoise_ref(color, albedo, nd, 4, demodulate=demodulate)
+    bg = albedo[..., 3] == 0
+    assert (out[bg] == color[bg].astype(np.float64)).all()
+    assert (out[..., 3] == color[..., 3]).all()                         # alpha is the input's everywhere
+    # changing what background pixels hold changes nothing on covered ones
+    color2 = color.copy()
+    color2[bg] = rng.uniform(100, 200, (int(bg.sum()), 4))
+    out2 = denoise_ref(color2, albedo, nd, 4, demodulate=demodulate)
+    assert (out2[~bg] == out[~bg]).all()
+    # and the filter does something on covered ones
+    assert np.abs(out[~bg] - color[~bg]).max() > 1e-3
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# ABI
+# ---------------------------------------------------------------------------------------------------------------------------
+def test_denoise_symbols_are_exported():
+    plugin.load_library()
+    out = subprocess.check_output(["nm", "-D", "--defined-only", plugin.LIB_PATH]).decode()
+    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
+    for name in DENOISE_SYMBOLS:
+        assert name in exported, name
+        assert name in plugin.EXPORTED_SYMBOLS, name
+    assert plugin.load_library().PTGetVersion() == (0 << 16) | 2
+
+
+def test_denoise_params_match_c_header():
+    fields = ["structSize", "iterations", "sigmaLuminance", "sigmaNormal", "sigmaDepth", "flags"]
+    lines = ['printf("size %zu\\n", sizeof(PTDenoiseParams));']
+    lines += [f'printf("{f} %zu\\n", offsetof(PTDenoiseParams, {f}));' for f in fields]
+    lines.append('printf("flag %u\\n", PT_DENOISE_DEMODULATE_ALBEDO);')
+    src = "#include <stdio.h>\n#include <stddef.h>\n#include \"ptmi_plugin.h\"\nint main(void) {\n" + "\n".join(lines) + "\nreturn 0; }\n"
+    with tempfile.TemporaryDirectory() as d:
+        c = os.path.join(d, "probe.c")
+        open(c, "w").write(src)
+        exe = os.path.join(d, "probe")
+        subprocess.check_call(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
+        got = dict(l.split(" ", 1) for l in subprocess.check_output([exe]).decode().splitlines())
+    assert int(got["size"]) == C.sizeof(abi.PTDenoiseParams) == 24
+    for f in fields:
+        assert int(got[f]) == getattr(abi.PTDenoiseParams, f).offset, f
+    assert int(got["flag"]) == abi.PT_DENOISE_DEMODULATE_ALBEDO
+    dp = abi.denoise_params()
+    assert (dp.structSize, dp.iterations, dp.sigmaLuminance, dp.sigmaNormal, dp.sigmaDepth, dp.flags) == (24, 5, 4.0, 128.0, 1.0, 1)
+
+
+def test_denoise_argument_errors_without_context():
+    lib = plugin.load_library()
+    dp = abi.denoise_params()
+    p = abi.PTFrameParams()
+    buf = (C.c_float * 16)()
+    assert lib.PTRenderGuides(None, C.byref(p), 1) == abi.PT_ERR_INVALID_ARG
+    assert b"ctx == NULL" in lib.PTGetLastError()
+    assert lib.PTDenoise(None, C.byref(dp), None, C.addressof(buf)) == abi.PT_ERR_INVALID_ARG
+    assert b"ctx == NULL" in lib.PTGetLastError()
+    assert lib.PTDenoiseToHost(None, C.byref(dp), C.addressof(buf), 16) == abi.PT_ERR_INVALID_ARG
+    assert b"ctx == NULL" in lib.PTGetLastError()
+    assert lib.PTGetGuidePointer(None, 0) is None
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# kernel resources (hipcc -Rpass-analysis=kernel-resource-usage, as tests/test_kernel_resources.py reads them)
+# ---------------------------------------------------------------------------------------------------------------------------
+def _device_flags():
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    flags = re.search(r"^FLAGS\s*:=\s*(.*)$", mk, re.M).group(1).split()
+    hip = re.search(r"^HIPFLAGS\s*:=\s*(.*)$", mk, re.M).group(1)
+    extra = hip.replace("$(FLAGS)", "").replace("--offload-arch=$(ARCH)", "").split()
+    return [f for f in flags if f != "-Wall"] + extra
+
+
+def _resources(src, defines=()):
+    out = subprocess.run(["hipcc", "--offload-arch=gfx950", "--cuda-device-only", "-c", src, "-o", os.devnull,
+                          "-Rpass-analysis=kernel-resource-usage"] + _device_flags() + list(defines),
+                         cwd=CSRC, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    res, cur = {}, None
+    for line in out.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            cur = res.setdefault(m.group(1), {})
+            continue
+        for key, name in (("VGPRs:", "vgprs"), ("ScratchSize", "scratch"), ("Occupancy", "occupancy"), ("VGPRs Spill", "vgpr_spill"), ("LDS Size", "lds")):
+            m = re.search(re.escape(key) + r"[^0-9]*(\d+)", line)
+            if m and cur is not None and key in line:
+                cur[name] = int(m.group(1))
+    return res
+
+
+# LDS bytes per workgroup and waves per SIMD of the filter kernels
+FILTER_KERNELS = {"pt_denoise_prepass": (0, 8), "pt_denoise_atrous_s1": (12800, 8), "pt_denoise_atrous_s2": (18432, 8),
+                  "pt_denoise_atrous_s4": (32768, 5), "pt_denoise_atrous": (0, 8), "pt_denoise_remodulate": (0, 8)}
+
+
+@pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not installed")
+@pytest.mark.parametrize("defines", [(), ("-DPT_Q_LDS_STACK=1",)], ids=["default", "stress"])
+def test_denoise_kernel_resources(defines):
+    res = _resources("pt_denoise.hip", defines)
+    g = res["pt_guides"]                                                # CWBVH stack in LDS + the HBM slab: no scratch
+    assert g["scratch"] == 0 and g["vgpr_spill"] == 0, g
+    assert res["pt_guides_tlas"]["vgpr_spill"] == 0, res["pt_guides_tlas"]
+    for name, (lds, occ) in FILTER_KERNELS.items():
+        r = res[name]
+        assert r["scratch"] == 0 and r["vgpr_spill"] == 0, (name, r)
+        assert (r["lds"], r["occupancy"]) == (lds, occ), (name, r)

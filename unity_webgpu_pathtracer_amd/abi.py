@@ -198,6 +198,27 @@ class PTRaySurface(C.Structure):
 assert C.sizeof(PTRay) == 32 and C.sizeof(PTRayHit) == 16 and C.sizeof(PTRaySurface) == 48
 
 
+# ---------------------------------------------------------------------------------------
+# Part 4: guide buffers and denoising (PTRenderGuides / PTDenoise)
+# ---------------------------------------------------------------------------------------
+PT_DENOISE_DEMODULATE_ALBEDO = 0x1
+
+
+class PTDenoiseParams(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("iterations", C.c_int32), ("sigmaLuminance", C.c_float),
+                ("sigmaNormal", C.c_float), ("sigmaDepth", C.c_float), ("flags", C.c_uint32)]
+
+
+assert C.sizeof(PTDenoiseParams) == 24
+
+
+def denoise_params(iterations: int = 5, sigma_luminance: float = 4.0, sigma_normal: float = 128.0, sigma_depth: float = 1.0,
+                   demodulate: bool = True) -> PTDenoiseParams:
+    """PTDenoiseParams with the header's suggested values (5 levels, sigmas 4 / 128 / 1, albedo demodulation on)."""
+    return PTDenoiseParams(C.sizeof(PTDenoiseParams), iterations, sigma_luminance, sigma_normal, sigma_depth,
+                           PT_DENOISE_DEMODULATE_ALBEDO if demodulate else 0)
+
+
 def as_void_p(arr):
     """Borrowed host pointer of a C-contiguous numpy array (None -> NULL)."""
     if arr is None:

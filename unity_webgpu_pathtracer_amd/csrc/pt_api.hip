@@ -126,6 +126,16 @@ struct PTContext {
     uint32_t queryCapMax = 0;
     void* querySlab = nullptr;
     DeviceBuffer qRays, qHits, qSurface;        // PTTraceRaysHost staging, grown on demand
+    // guides and denoising (PTRenderGuides / PTDenoise): allocated on first use, regrown on a size change
+    uint32_t guideCaps[2] = {};
+    void* guideSlab = nullptr;
+    float4* guides[2] = {nullptr, nullptr};     // albedo + coverage, normal + depth
+    uint32_t guideW = 0, guideH = 0;
+    float4* dnState[2] = {nullptr, nullptr};    // filter state ping-pong (e.rgb, v)
+    float2* dnGradZ = nullptr;
+    uint32_t dnW = 0, dnH = 0;
+    void* dnHost = nullptr;                     // PTDenoiseToHost staging frame
+    size_t dnHostBytes = 0;
 };
 
 namespace {
@@ -543,6 +553,8 @@ PT_API int PTDestroy(PTContext* c)
     if (c->batchScratch) hipFree(c->batchScratch);
     for (auto* b : {&c->qRays, &c->qHits, &c->qSurface}) if (b->ptr) hipFree(b->ptr);
     if (c->querySlab) hipFree(c->querySlab);
+    for (void* p : {(void*)c->guideSlab, (void*)c->guides[0], (void*)c->guides[1], (void*)c->dnState[0], (void*)c->dnState[1],
+                    (void*)c->dnGradZ, c->dnHost}) if (p) hipFree(p);
     for (auto& set : c->sets) {
         if (set.stream) { hipStreamSynchronize(set.stream); hipStreamDestroy(set.stream); }
         if (set.arena) hipFree(set.arena);
@@ -875,6 +887,154 @@ PT_API int PTTraceRaysHost(PTContext* c, const PTRay* rays, uint64_t count, uint
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     return PT_OK;
+}
+
+} // extern "C"
+namespace {
+// Guides and denoising (include/ptmi_plugin.h Part 4).  Everything runs on c->stream; buffers are regrown only after that
+// stream has drained, so no launch still reads a buffer that is freed.
+int free_and_sync(PTContext* c, void** ptrs, int count)
+{
+    bool any = false;
+    for (int k = 0; k < count; ++k) any = any || ptrs[k];
+    if (!any) return PT_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < count; ++k) if (ptrs[k]) { hipFree(ptrs[k]); ptrs[k] = nullptr; }
+    return PT_OK;
+}
+
+int ensure_guides(PTContext* c, uint32_t w, uint32_t h)
+{
+    if (!c->guideSlab) {
+        HIP_TRY(pt_guide_grid_caps(c->device, c->guideCaps));
+        const uint32_t cap = c->guideCaps[0] > c->guideCaps[1] ? c->guideCaps[0] : c->guideCaps[1];
+        HIP_TRY(hipMalloc(&c->guideSlab, (size_t)cap * pt_guide_slab_bytes_per_wave()));
+    }
+    if (c->guides[0] && c->guideW == w && c->guideH == h) return PT_OK;
+    void* old[2] = {c->guides[0], c->guides[1]};
+    int rc = free_and_sync(c, old, 2);
+    if (rc) return rc;
+    c->guides[0] = c->guides[1] = nullptr;
+    c->guideW = c->guideH = 0;
+    const size_t bytes = (size_t)w * h * sizeof(float4);
+    HIP_TRY(hipMalloc((void**)&c->guides[0], bytes));
+    HIP_TRY(hipMalloc((void**)&c->guides[1], bytes));
+    c->guideW = w;
+    c->guideH = h;
+    return PT_OK;
+}
+
+int ensure_filter(PTContext* c, uint32_t w, uint32_t h)
+{
+    if (c->dnState[0] && c->dnW == w && c->dnH == h) return PT_OK;
+    void* old[3] = {c->dnState[0], c->dnState[1], c->dnGradZ};
+    int rc = free_and_sync(c, old, 3);
+    if (rc) return rc;
+    c->dnState[0] = c->dnState[1] = nullptr;
+    c->dnGradZ = nullptr;
+    c->dnW = c->dnH = 0;
+    const size_t n = (size_t)w * h;
+    HIP_TRY(hipMalloc((void**)&c->dnState[0], n * sizeof(float4)));
+    HIP_TRY(hipMalloc((void**)&c->dnState[1], n * sizeof(float4)));
+    HIP_TRY(hipMalloc((void**)&c->dnGradZ, n * sizeof(float2)));
+    c->dnW = w;
+    c->dnH = h;
+    return PT_OK;
+}
+
+int import_denoise_params(const PTDenoiseParams* in, PTDenoiseParams& p)
+{
+    if (!in) return fail(PT_ERR_INVALID_ARG, "PTDenoise: params == NULL");
+    if (in->structSize < sizeof(PTDenoiseParams) || in->structSize > 4096u)
+        return fail(PT_ERR_INVALID_ARG, "PTDenoiseParams.structSize is not set (must be sizeof(PTDenoiseParams) of the host's header)");
+    memset(&p, 0, sizeof(p));
+    memcpy(&p, in, in->structSize < sizeof(p) ? in->structSize : sizeof(p));
+    p.structSize = (uint32_t)sizeof(p);
+    if (p.iterations < 0 || p.iterations > 8) return fail(PT_ERR_INVALID_ARG, "PTDenoise: iterations " + std::to_string(p.iterations) + " outside 0..8");
+    // !(x > 0): NaN and <= 0
+    if (!(p.sigmaLuminance > 0.0f) || !(p.sigmaNormal > 0.0f) || !(p.sigmaDepth > 0.0f))
+        return fail(PT_ERR_INVALID_ARG, "PTDenoise: sigmaLuminance / sigmaNormal / sigmaDepth must be > 0 (and not NaN)");
+    if (p.flags & ~PT_DENOISE_DEMODULATE_ALBEDO) return fail(PT_ERR_INVALID_ARG, "PTDenoise: unknown flag bits " + std::to_string(p.flags));
+    return PT_OK;
+}
+} // namespace
+extern "C" {
+
+PT_API int PTRenderGuides(PTContext* c, const PTFrameParams* hostParams, int samplesPerPixel)
+{
+    if (!c) return fail(PT_ERR_INVALID_ARG, "PTRenderGuides: ctx == NULL");
+    PTFrameParams p;
+    int rc = import_params(hostParams, p);
+    if (rc) return rc;
+    if ((rc = validate_params(&p))) return rc;
+    if (samplesPerPixel != 1 && samplesPerPixel != 4 && samplesPerPixel != 16)
+        return fail(PT_ERR_INVALID_ARG, "PTRenderGuides: samplesPerPixel " + std::to_string(samplesPerPixel) + " is not 1, 4 or 16");
+    if (!c->hasScene) return fail(PT_ERR_NO_SCENE, "PTSetScene has not been called");
+    HIP_TRY(hipSetDevice(c->device));
+    RoctxRange range("PT guides (enqueue)");
+    if ((rc = ensure_guides(c, p.OutputWidth, p.OutputHeight))) return rc;
+    const uint32_t n = samplesPerPixel == 1 ? 1u : samplesPerPixel == 4 ? 2u : 4u;
+    HIP_TRY(pt_launch_guides(c->scene, p, n, c->guides[0], c->guides[1], (uint2*)c->guideSlab, c->guideCaps[c->scene.hasTlas ? 1 : 0], c->stream));
+    return PT_OK;
+}
+
+PT_API int PTDenoise(PTContext* c, const PTDenoiseParams* params, const void* dSrc, void* dDst)
+{
+    if (!c) return fail(PT_ERR_INVALID_ARG, "PTDenoise: ctx == NULL");
+    PTDenoiseParams p;
+    int rc = import_denoise_params(params, p);
+    if (rc) return rc;
+    if (!dDst) return fail(PT_ERR_INVALID_ARG, "PTDenoise: dst == NULL");
+    if (!c->guides[0]) return fail(PT_ERR_INVALID_ARG, "PTDenoise: no guides (call PTRenderGuides first)");
+    if (!dSrc) {
+        if (!c->frames[0]) return fail(PT_ERR_INVALID_ARG, "PTDenoise: no frame rendered yet");
+        if (c->frameW != c->guideW || c->frameH != c->guideH)
+            return fail(PT_ERR_INVALID_ARG, "PTDenoise: the guides are " + std::to_string(c->guideW) + "x" + std::to_string(c->guideH) +
+                                                ", the Output frame " + std::to_string(c->frameW) + "x" + std::to_string(c->frameH));
+        dSrc = c->frames[c->cur];
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    RoctxRange range("PT denoise (enqueue)");
+    const size_t bytes = (size_t)c->guideW * c->guideH * sizeof(float4);
+    if (p.iterations == 0) {
+        if (dSrc != dDst) HIP_TRY(hipMemcpyAsync(dDst, dSrc, bytes, hipMemcpyDeviceToDevice, c->stream));
+        return PT_OK;
+    }
+    if ((rc = ensure_filter(c, c->guideW, c->guideH))) return rc;
+    PTDenoiseArgs A = {c->guideW, c->guideH, p.sigmaLuminance, p.sigmaNormal, p.sigmaDepth, p.flags};
+    HIP_TRY(pt_launch_denoise(A, p.iterations, (const float4*)dSrc, (float4*)dDst, c->guides[0], c->guides[1], c->dnState[0], c->dnState[1],
+                              c->dnGradZ, c->stream));
+    return PT_OK;
+}
+
+PT_API int PTDenoiseToHost(PTContext* c, const PTDenoiseParams* params, float* dst, uint64_t dstFloats)
+{
+    if (!c) return fail(PT_ERR_INVALID_ARG, "PTDenoiseToHost: ctx == NULL");
+    if (!params || !dst) return fail(PT_ERR_INVALID_ARG, "PTDenoiseToHost: params/dst == NULL");
+    if (!c->guides[0]) return fail(PT_ERR_INVALID_ARG, "PTDenoise: no guides (call PTRenderGuides first)");
+    const uint64_t need = (uint64_t)c->guideW * c->guideH * 4;
+    if (dstFloats < need) return fail(PT_ERR_INVALID_ARG, "destination too small");
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->dnHostBytes < need * sizeof(float)) {
+        void* old[1] = {c->dnHost};
+        int rc = free_and_sync(c, old, 1);
+        if (rc) return rc;
+        c->dnHost = nullptr;
+        c->dnHostBytes = 0;
+        HIP_TRY(hipMalloc(&c->dnHost, need * sizeof(float)));
+        c->dnHostBytes = need * sizeof(float);
+    }
+    int rc = PTDenoise(c, params, nullptr, c->dnHost);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(dst, c->dnHost, need * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+PT_API void* PTGetGuidePointer(PTContext* c, int which)
+{
+    if (!c || which < 0 || which > 1) return nullptr;
+    return c->guides[which];
 }
 
 PT_API int PTSynchronize(PTContext* c)
@@ -1399,6 +1559,6 @@ PT_API int PTGroupResetStats(PTGroup* g)
 }
 
 PT_API const char* PTGetLastError(void) { return g_lastError.c_str(); }
-PT_API int PTGetVersion(void) { return (0 << 16) | 1; }
+PT_API int PTGetVersion(void) { return (0 << 16) | 2; }
 
 } // extern "C"

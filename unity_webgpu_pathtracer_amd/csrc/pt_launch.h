@@ -70,6 +70,22 @@ size_t pt_query_slab_bytes_per_wave();
 hipError_t pt_launch_query(const DScene& S, const float4* rays, uint32_t count, uint32_t mode, bool stats, float4* hits,
                            float4* surface, uint2* slab, uint32_t gridCap, unsigned long long* gstats, hipStream_t stream);
 
+// ---- guides and denoising (pt_denoise.hip) ----
+// resident one-wave workgroups per device of the two guide kernels (flat, HAS_TLAS): the grid cap, and the slab waves it needs
+hipError_t pt_guide_grid_caps(int device, uint32_t caps[2]);
+size_t pt_guide_slab_bytes_per_wave();
+// n x n sub-pixel samples per pixel of P's OutputWidth x OutputHeight; albedo / normalDepth: one float4 per pixel each
+hipError_t pt_launch_guides(const DScene& S, const PTFrameParams& P, uint32_t n, float4* albedo, float4* normalDepth, uint2* slab,
+                            uint32_t gridCap, hipStream_t stream);
+struct PTDenoiseArgs {
+    uint32_t width, height;
+    float sigmaL, sigmaN, sigmaZ;
+    uint32_t flags;
+};
+// iterations >= 1 levels: prepass, one launch per level, remodulation (iterations + 2 launches); every buffer width*height
+hipError_t pt_launch_denoise(const PTDenoiseArgs& A, int iterations, const float4* src, float4* dst, const float4* albedo,
+                             const float4* normalDepth, float4* state0, float4* state1, float2* gradz, hipStream_t stream);
+
 // ---- schedule 1 (wavefront): slot-indexed path state in HBM (see pt_wavefront.hip) ----
 // float4 arrays of a state set, in carving order.  PT_F4_RAY0/1/2 are the RAY RECORDS of the three ray kinds a slot can have in
 // flight (bounce ray, environment NEE, light NEE): 32 bytes per slot and kind, {origin.xyz, w0, direction.xyz, w1} at

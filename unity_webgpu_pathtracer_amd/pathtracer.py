@@ -134,6 +134,7 @@ class PathTracer:
         ctx = C.c_void_p()
         plugin.check(self.lib.PTCreate(device, C.byref(ctx)))
         self.ctx = ctx
+        self.device = device
         self._bvhScene = BVHScene(scene, build_device=build_device)
         self._bvhScene.PrepareShader(self.ctx)
         if world_size > 1:
@@ -362,6 +363,49 @@ class PathTracer:
         d = self.camera_ray(x, y, params)[3:6].astype(np.float64)
         return float(hit["distance"] * np.dot(d, self.camera_forward(params)))
 
+    # ---- guides and denoising (include/ptmi_plugin.h Part 4)
+    def render_guides(self, samples: int = 1, params: abi.PTFrameParams = None):
+        """PTRenderGuides: first-hit albedo / normal / depth guides for the camera of `params` (default: this tracer's),
+        `samples` = 1, 4 or 16 sub-pixel rays per pixel.  Stream-ordered; guides() reads them back."""
+        p = params or self.params(seed=0)
+        plugin.check(self.lib.PTRenderGuides(self.ctx, C.byref(p), samples))
+        self._guide_size = (p.OutputHeight, p.OutputWidth)
+
+    def guide_pointer(self, which: int) -> int:
+        """Device pointer of guide 0 (albedo + coverage) or 1 (normal + depth); 0 before render_guides."""
+        return self.lib.PTGetGuidePointer(self.ctx, which) or 0
+
+    def guides(self):
+        """The guides as numpy arrays: albedo (H, W, 4) = base colour rgb + coverage, normal+depth (H, W, 4)."""
+        h, w = self._guide_size
+        self.synchronize()
+        out = []
+        for which in (0, 1):
+            ptr = self.guide_pointer(which)
+            if not ptr:
+                raise RuntimeError("render_guides() has not been called")
+            out.append(_device_to_numpy(ptr, (h, w, 4)))
+        return out[0], out[1]
+
+    def denoise(self, dp: abi.PTDenoiseParams = None, d_src: int = 0, d_dst: int = 0):
+        """PTDenoise with `dp` (default abi.denoise_params()).  d_src = 0 reads the current Output frame.  With d_dst = 0 the
+        result comes back as (H, W, 4) float32 numpy (PTDenoiseToHost when d_src is 0 too); else it is written to d_dst."""
+        dp = dp or abi.denoise_params()
+        if d_dst:
+            plugin.check(self.lib.PTDenoise(self.ctx, C.byref(dp), C.c_void_p(d_src) if d_src else None, C.c_void_p(d_dst)))
+            return None
+        h, w = self._guide_size
+        out = np.empty((h, w, 4), dtype=np.float32)
+        if not d_src:
+            plugin.check(self.lib.PTDenoiseToHost(self.ctx, C.byref(dp), out.ctypes.data_as(C.c_void_p), out.size))
+            return out
+        import torch
+        dst = torch.empty((h, w, 4), dtype=torch.float32, device=f"cuda:{self.device}")
+        torch.cuda.synchronize(dst.device)
+        plugin.check(self.lib.PTDenoise(self.ctx, C.byref(dp), C.c_void_p(d_src), C.c_void_p(dst.data_ptr())))
+        self.synchronize()
+        return dst.cpu().numpy()
+
     def close(self):
         if self.ctx:
             self.lib.PTDestroy(self.ctx)
@@ -372,3 +416,10 @@ class PathTracer:
             self.close()
         except Exception:
             pass
+
+
+def _device_to_numpy(ptr: int, shape) -> np.ndarray:
+    """Copy float32 device memory at `ptr` into a new numpy array of `shape` (the HIP runtime's hipMemcpy, synchronous)."""
+    out = np.empty(shape, dtype=np.float32)
+    plugin.hip_memcpy(out.ctypes.data, ptr, out.nbytes, plugin.HIP_MEMCPY_D2H)
+    return out

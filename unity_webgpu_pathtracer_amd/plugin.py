@@ -84,6 +84,11 @@ def load_library():
         # Part 3 (ray queries)
         "PTTraceRays": (i32, [vp, vp, C.c_uint64, C.c_uint32, vp, vp]),
         "PTTraceRaysHost": (i32, [vp, vp, C.c_uint64, C.c_uint32, vp, vp]),
+        # Part 4 (guides and denoising)
+        "PTRenderGuides": (i32, [vp, C.POINTER(abi.PTFrameParams), i32]),
+        "PTDenoise": (i32, [vp, C.POINTER(abi.PTDenoiseParams), vp, vp]),
+        "PTDenoiseToHost": (i32, [vp, C.POINTER(abi.PTDenoiseParams), vp, C.c_uint64]),
+        "PTGetGuidePointer": (vp, [vp, i32]),
         "PTGetLastError": (C.c_char_p, []), "PTGetVersion": (i32, []),
     }
     for name, (res, args) in sig.items():
@@ -105,6 +110,7 @@ EXPORTED_SYMBOLS = [
     "PTGroupSetScene", "PTGroupRenderPass", "PTGroupFlipFrames", "PTGroupResetFrames", "PTGroupSynchronize", "PTGroupReadback",
     "PTGroupGetAssembledFrame", "PTGroupGetStats", "PTGroupResetStats",
     "PTTraceRays", "PTTraceRaysHost",
+    "PTRenderGuides", "PTDenoise", "PTDenoiseToHost", "PTGetGuidePointer",
     "PTGetLastError", "PTGetVersion",
 ]
 
@@ -119,6 +125,28 @@ def check(rc):
     if rc != abi.PT_OK:
         raise PluginError(rc, load_library().PTGetLastError().decode())
     return rc
+
+
+HIP_MEMCPY_H2D, HIP_MEMCPY_D2H = 1, 2          # hipMemcpyKind
+_hip = None
+
+
+def hip_memcpy(dst: int, src: int, nbytes: int, kind: int):
+    """hipMemcpy through the HIP runtime the plugin itself linked (found among the process's mapped files): synchronous
+    copies to or from device pointers the plugin hands out (PTGetGuidePointer, PTGetFramePointer)."""
+    global _hip
+    if _hip is None:
+        load_library()
+        with open("/proc/self/maps") as f:
+            paths = {l.split()[-1] for l in f if "libamdhip64.so" in l}
+        if not paths:
+            raise RuntimeError("the HIP runtime is not loaded")
+        _hip = C.CDLL(sorted(paths)[0])
+        _hip.hipMemcpy.restype = C.c_int
+        _hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    rc = _hip.hipMemcpy(C.c_void_p(dst), C.c_void_p(src), nbytes, kind)
+    if rc != 0:
+        raise RuntimeError(f"hipMemcpy failed: {rc}")
 
 
 class TinyBVH:
