@@ -487,6 +487,37 @@ PT_API int PTDenoiseToHost(PTContext* ctx, const PTDenoiseParams* params, float*
  * PTRenderGuides or for another `which`.  A host may write its own guides there before PTDenoise. */
 PT_API void* PTGetGuidePointer(PTContext* ctx, int which);
 
+/* =====================================================================================================================
+ * Part 5: scene updates.  Move instances, lights and materials of the scene PTSetScene uploaded, without setting it again
+ * (the reference's BVHScene.UpdateTLAS, PathTracer.UpdateLights / UpdateMaterialData).
+ *
+ * Instances: `count` PTBlasInstance records (the 192-byte input of BuildTLAS); count must equal the scene's instanceCount.
+ * localToWorld, worldToLocal, aabbMin and aabbMax are read; blasIndex is ignored as in BuildTLAS; the BLAS offsets and
+ * materialIndex stay as PTSetScene set them.  The TLAS is rebuilt on the GPU, byte-identical to BuildTLAS of the same
+ * records (PTReadTLAS returns it), and the frames, ray queries and guides equal those of a fresh PTSetScene.  The host
+ * variant refuses non-finite AABBs and matrices; the device variant does not look at the data: such input gives an
+ * unspecified tree that is still memory-safe.
+ * Lights: 1..lightCount (of PTSetScene) PTLight records, 64 bytes; the scene must have HAS_LIGHTS.
+ * Materials: materialCount PTMaterialData records, 128 bytes; a texture slot is negative (none) or names a texture that
+ * PTSetScene validated.
+ * Ordering: passes, queries and guides enqueued before an update see the old scene, everything enqueued after sees the new
+ * one.  Updates never block the host for the GPU; the host variants copy the caller's array before they return (they may
+ * wait for their own staging buffer).  PTUpdateInstancesDevice reads dInstances in the context stream's order.
+ * The library does not reset accumulation: call PTResetFrames / start again at CurrentSample = 0.
+ * Memory: allocated on the first update of each kind (two generations of what changes); PTSetScene discards the update
+ * state and PTDestroy frees it.
+ * Errors: PT_ERR_INVALID_ARG for a NULL context or array, a count mismatch, a refused record; PT_ERR_NO_SCENE before
+ * PTSetScene; PT_ERR_UNSUPPORTED for instance updates without HAS_TLAS and light updates without HAS_LIGHTS.
+ * ===================================================================================================================== */
+PT_API int PTUpdateInstances(PTContext* ctx, const PTBlasInstance* instances, uint32_t count);          /* host array, copied before return */
+PT_API int PTUpdateInstancesDevice(PTContext* ctx, const PTBlasInstance* dInstances, uint32_t count);   /* device array, read in stream order */
+PT_API int PTUpdateLights(PTContext* ctx, const void* lights, uint32_t count);                          /* PTLight records, 64 B */
+PT_API int PTUpdateMaterials(PTContext* ctx, const void* materials, uint32_t count);                    /* PTMaterialData records, 128 B */
+/* The current TLAS in BuildTLAS's layout: *outNodeCount nodes (64 bytes each) into dstNodes and instanceCount indices into
+ * dstIndices.  Synchronising.  Before any instance update it returns what PTSetScene was given. */
+PT_API int PTReadTLAS(PTContext* ctx, void* dstNodes, uint64_t dstNodeBytes, uint32_t* dstIndices, uint64_t dstIndexCount,
+                      uint32_t* outNodeCount);
+
 /* Text of the last error on the calling thread ("" if none). */
 PT_API const char* PTGetLastError(void);
 /* Library/ABI version: (major << 16) | minor. */

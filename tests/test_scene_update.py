@@ -1,0 +1,126 @@
+"""Scene updates (include/ptmi_plugin.h Part 5) without a GPU: exports, prototypes, argument checks that need no context,
+the cooperative partition's placement rule against the host builder's swap loop, and the TLAS kernels' resources.
+tests/test_gpu_scene_update.py holds the GPU build to BuildTLAS's bytes and updated scenes to fresh PTSetScene renders."""
+import ctypes as C
+import os
+import shutil
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+from test_denoise import _resources
+from unity_webgpu_pathtracer_amd import abi, plugin, scenes
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+UPDATE_SYMBOLS = ["PTUpdateInstances", "PTUpdateInstancesDevice", "PTUpdateLights", "PTUpdateMaterials", "PTReadTLAS"]
+
+
+def test_update_symbols_are_exported():
+    plugin.load_library()
+    out = subprocess.check_output(["nm", "-D", "--defined-only", plugin.LIB_PATH]).decode()
+    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
+    for name in UPDATE_SYMBOLS:
+        assert name in exported, name
+        assert name in plugin.EXPORTED_SYMBOLS, name
+    assert plugin.load_library().PTGetVersion() == (0 << 16) | 2         # hosts detect the feature by symbol
+
+
+def test_update_prototypes_match_c_header():
+    src = """#include <stdint.h>
+#include "ptmi_plugin.h"
+int (*a)(PTContext*, const PTBlasInstance*, uint32_t) = PTUpdateInstances;
+int (*b)(PTContext*, const PTBlasInstance*, uint32_t) = PTUpdateInstancesDevice;
+int (*c)(PTContext*, const void*, uint32_t) = PTUpdateLights;
+int (*d)(PTContext*, const void*, uint32_t) = PTUpdateMaterials;
+int (*e)(PTContext*, void*, uint64_t, uint32_t*, uint64_t, uint32_t*) = PTReadTLAS;
+"""
+    with tempfile.TemporaryDirectory() as d:
+        f = os.path.join(d, "probe.c")
+        open(f, "w").write(src)
+        subprocess.check_call(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", f, "-o", os.path.join(d, "probe.o")])
+
+
+def test_null_context_is_refused():
+    lib = plugin.load_library()
+    buf = (C.c_uint8 * 256)()
+    n = C.c_uint32()
+    assert lib.PTUpdateInstances(None, C.addressof(buf), 1) == abi.PT_ERR_INVALID_ARG
+    assert lib.PTUpdateInstancesDevice(None, C.addressof(buf), 1) == abi.PT_ERR_INVALID_ARG
+    assert lib.PTUpdateLights(None, C.addressof(buf), 1) == abi.PT_ERR_INVALID_ARG
+    assert lib.PTUpdateMaterials(None, C.addressof(buf), 1) == abi.PT_ERR_INVALID_ARG
+    assert lib.PTReadTLAS(None, C.addressof(buf), 256, C.addressof(buf), 1, C.byref(n)) == abi.PT_ERR_INVALID_ARG
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the cooperative partition (pt_tlas.hip build_node_coop) against bvh_builder.cpp's swap loop
+# ---------------------------------------------------------------------------------------------------------------------------
+def swap_partition(right):
+    """Bvh2::build's in-place partition, element ids 0..m-1 in place of primitive indices."""
+    m = len(right)
+    a = list(range(m))
+    j, src = m, 0
+    for _ in range(m):
+        if not right[a[src]]:
+            src += 1
+        else:
+            j -= 1
+            a[src], a[j] = a[j], a[src]
+    return a, src
+
+
+def placement_partition(right):
+    """The placement rule the kernel evaluates with prefix counts, written out sequentially."""
+    m = len(right)
+    R, c = [0] * m, 0
+    for i in range(m):
+        R[i] = c
+        c += right[i]
+    tot = c
+    L = m - tot
+    s = L if (L == m or not right[L]) else L + 1
+    rf, lb = {}, {}
+    for i in range(m):
+        if i < s and right[i]:
+            rf[R[i]] = i
+        if i >= s and not right[i]:
+            lb[(m - 1 - i) - (tot - R[i] - right[i])] = i
+    out = [None] * m
+    for i in range(m):
+        f = right[i]
+        if i < s:
+            o = i if not f else (m - 1 if R[i] == 0 else lb[R[i] - 1] - 1)
+        else:
+            o = i - 1 if f else rf[(m - 1 - i) - (tot - R[i] - f)]
+        out[o] = i
+    return out, L
+
+
+def test_partition_placement_rule_matches_swap_loop():
+    rng = np.random.RandomState(1234)
+    for _ in range(20000):
+        m = int(rng.randint(1, 48))
+        f = (rng.uniform(size=m) < rng.uniform()).astype(int).tolist()
+        assert placement_partition(f) == swap_partition(f), f
+
+
+def test_bounce_transforms_follow_bounce_cs():
+    s = scenes.instanced_scene(count=3, detail=4)
+    t = 0.7
+    T = scenes.bounce_transforms(s, t)
+    assert np.array_equal(T[0], s.instances[0][1])                       # the floor does not move
+    for k in range(1, 4):
+        y0 = np.float32(s.instances[k][1][1, 3])
+        want = y0 + (y0 + np.float32(np.sin(np.float32(t) * np.float32(2))) * np.float32(2))
+        assert np.float32(T[k][1, 3]) == want
+        assert np.array_equal(T[k][:, :3], s.instances[k][1][:, :3]) and T[k][0, 3] == s.instances[k][1][0, 3]
+
+
+@pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not installed")
+def test_tlas_kernel_resources():
+    res = _resources("pt_tlas.hip")
+    names = {k: v for k, v in res.items() if "pt_tlas_" in k}
+    assert len(names) == 3, list(res)
+    for k, r in names.items():
+        assert r["scratch"] == 0 and r["vgpr_spill"] == 0, (k, r)

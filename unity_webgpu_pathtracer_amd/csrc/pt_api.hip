@@ -5,6 +5,7 @@
 // (PathTracer.cs:226-252) and the ping-pong frame bookkeeping (PathTracer.cs:246-247, 268-272).
 // There is NO CPU fallback: without a HIP device PTCreate fails with PT_ERR_NO_DEVICE.
 #include "pt_launch.h"
+#include "pt_tlas.h"
 hipError_t pt_launch_wavefront_b(const DScene& S, const PTFrameParams& P, const PTBatch& batch, const float4* accumulated, float4* output,
                                  const PTTileMap& tm, const PTWfBuffers& B, unsigned long long* gstats, bool fullStats,
                                  hipStream_t stream, hipEvent_t orderAfter, bool zeroOutputFirst,
@@ -14,7 +15,9 @@ hipError_t pt_launch_wavefront_b(const DScene& S, const PTFrameParams& P, const 
 
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <thread>
@@ -136,6 +139,26 @@ struct PTContext {
     uint32_t dnW = 0, dnH = 0;
     void* dnHost = nullptr;                     // PTDenoiseToHost staging frame
     size_t dnHostBytes = 0;
+    // scene updates (PTUpdateInstances / Lights / Materials): two generations of what an update rewrites, allocated on the first
+    // update of each kind and discarded by PTSetScene.  cur = -1 while PTSetScene's own buffers are current.
+    struct UpdGroup {
+        void* gen[2] = {nullptr, nullptr};
+        int cur = -1;
+        hipEvent_t freeEv[2] = {nullptr, nullptr};      // recorded on the context stream when the generation stops being current
+        bool freeRecorded[2] = {false, false};
+        void* staging[2] = {nullptr, nullptr};          // pinned host copies of the host variants' arrays
+        size_t stagingBytes = 0;
+        hipEvent_t stagedEv[2] = {nullptr, nullptr};
+        bool stagedRecorded[2] = {false, false};
+    } updInst, updLights, updMats;
+    hipStream_t updStream = nullptr;
+    hipEvent_t updDone = nullptr;                       // the last update's completion
+    hipEvent_t updInput = nullptr;                      // PTUpdateInstancesDevice: the context stream up to the call
+    bool updPending = false;                            // an update since PTSetScene: every pass waits for updDone first
+    void* tlasWork = nullptr;
+    PTTlasWork tlasW = {};
+    uint32_t instanceCount = 0, sceneLightCount = 0, origTlasNodes = 0;
+    std::vector<uint32_t> validTextures;                // texture indices PTSetScene validated (sorted)
 };
 
 namespace {
@@ -479,6 +502,7 @@ int render_to(PTContext* c, const PTFrameParams* hostParams, float4* dOut, const
             // the launch chain runs on the set's own stream; only its resolve (which reads `accumulated` and writes `output`)
             // is ordered after what the caller has enqueued on the context stream so far, the previous pass included
             HIP_TRY(hipEventRecord(set.callEv, c->stream));
+            if (c->updPending) HIP_TRY(hipStreamWaitEvent(set.stream, c->updDone, 0));     // the trace reads the scene before the resolve's wait
             if (c->profiling && j == 0u) HIP_TRY(hipEventRecord(ep.start, set.stream));
             uint32_t n = 0;
             // the default schedule's kernels (refill trace + shade) come from the translation unit built without the post-RA scheduler,
@@ -510,6 +534,31 @@ int render_to(PTContext* c, const PTFrameParams* hostParams, float4* dOut, const
         c->pending.push_back(ep);
     }
     return PT_OK;
+}
+
+// PTSetScene / PTDestroy: drop the update generations (the scene's own buffers become current again)
+void discard_updates(PTContext* c, bool destroy)
+{
+    if (c->updStream) hipStreamSynchronize(c->updStream);
+    for (PTContext::UpdGroup* g : {&c->updInst, &c->updLights, &c->updMats}) {
+        for (int k = 0; k < 2; ++k) {
+            if (g->gen[k]) hipFree(g->gen[k]);
+            if (g->staging[k]) hipHostFree(g->staging[k]);
+            if (g->freeEv[k]) hipEventDestroy(g->freeEv[k]);
+            if (g->stagedEv[k]) hipEventDestroy(g->stagedEv[k]);
+        }
+        *g = PTContext::UpdGroup();
+    }
+    if (c->tlasWork) { hipFree(c->tlasWork); c->tlasWork = nullptr; }
+    c->tlasW = {};
+    c->updPending = false;
+    if (destroy) {
+        if (c->updDone) hipEventDestroy(c->updDone);
+        if (c->updInput) hipEventDestroy(c->updInput);
+        if (c->updStream) hipStreamDestroy(c->updStream);
+        c->updDone = c->updInput = nullptr;
+        c->updStream = nullptr;
+    }
 }
 
 } // namespace
@@ -546,6 +595,7 @@ PT_API int PTDestroy(PTContext* c)
     if (!c) return PT_OK;
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
+    discard_updates(c, true);
     for (auto* b : {&c->nodes, &c->tris, &c->attrs, &c->materials, &c->lights, &c->lightConst, &c->tex, &c->tlas, &c->tlasBfs, &c->instances, &c->instByLeaf, &c->envTex, &c->envCdf}) if (b->ptr) hipFree(b->ptr);
     for (int i = 0; i < 2; i++) if (c->frames[i]) hipFree(c->frames[i]);
     if (c->dStats) hipFree(c->dStats);
@@ -604,6 +654,7 @@ int set_scene(PTContext* c, const PTSceneDesc* hostScene, bool validate)
     HIP_TRY(hipSetDevice(c->device));
     for (auto& set : c->sets) if (set.stream) HIP_TRY(hipStreamSynchronize(set.stream));   // no pass may still read the old scene
     HIP_TRY(hipStreamSynchronize(c->stream));
+    discard_updates(c, false);
     int rc;
     if ((rc = upload(c, c->nodes, s->bvhNodes, s->bvhNodesBytes))) return rc;
     if ((rc = upload(c, c->tris, s->bvhTris, s->bvhTrisBytes))) return rc;
@@ -695,6 +746,25 @@ int set_scene(PTContext* c, const PTSceneDesc* hostScene, bool validate)
     c->scene.envCdfSum = cdfSum;
     c->scene.hasEnvTex = envOn ? 1u : 0u;
     c->scene.lightConst = lights ? (const float4*)c->lightConst.ptr : nullptr;
+    c->instanceCount = tlasOn ? s->instanceCount : 0u;
+    c->sceneLightCount = lights ? s->lightCount : 0u;
+    c->origTlasNodes = tlasOn ? s->tlasIndexOffset / 16u : 0u;
+    c->validTextures.clear();
+    if (textures) {                                // what PTUpdateMaterials may name: the textures this scene's materials named
+        const float* mats = (const float*)s->materials;
+        for (uint32_t m = 0; m < s->materialCount; ++m)
+            for (int k : {22, 23, 25, 26}) {
+                const float f = mats[(size_t)m * 32 + k];
+                if (!(f >= 0.0f && f < 1.0e9f)) continue;
+                const uint64_t t = (uint64_t)f;
+                if (4 * t + 3 >= s->textureDataUints) continue;
+                const uint32_t* d = s->textureData + 4 * t;
+                if (d[0] == 0 || d[1] == 0 || (uint64_t)d[2] + (uint64_t)d[0] * d[1] > s->textureDataUints) continue;
+                c->validTextures.push_back((uint32_t)t);
+            }
+        std::sort(c->validTextures.begin(), c->validTextures.end());
+        c->validTextures.erase(std::unique(c->validTextures.begin(), c->validTextures.end()), c->validTextures.end());
+    }
     if (lights) {
         HIP_TRY(pt_launch_derive_lights(c->scene, (float4*)c->lightConst.ptr, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1555,6 +1625,242 @@ PT_API int PTGroupResetStats(PTGroup* g)
 {
     if (!g) return fail(PT_ERR_INVALID_ARG, "group == NULL");
     for (PTContext* c : g->ctx) { int rc = PTResetStats(c); if (rc) return rc; }
+    return PT_OK;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// Part 5: scene updates
+// ------------------------------------------------------------------------------------------
+namespace {
+
+size_t al256(size_t b) { return (b + 255) / 256 * 256; }
+// one instance generation: raw TLAS ((2n - 1) nodes, then n indices), breadth-first copy, PTGpuInstance records, instByLeaf
+size_t inst_raw_bytes(uint32_t n) { return al256(((size_t)2 * n - 1) * 64 + (size_t)n * 4); }
+size_t inst_gen_bytes(uint32_t n) { return inst_raw_bytes(n) + al256(((size_t)2 * n - 1) * 64) + al256((size_t)n * 144) + al256((size_t)n * 96); }
+struct InstGen { float* raw; float* bfs; float* inst; float* byLeaf; };
+InstGen inst_gen(void* base, uint32_t n)
+{
+    char* p = (char*)base;
+    InstGen g;
+    g.raw = (float*)p; p += inst_raw_bytes(n);
+    g.bfs = (float*)p; p += al256(((size_t)2 * n - 1) * 64);
+    g.inst = (float*)p; p += al256((size_t)n * 144);
+    g.byLeaf = (float*)p;
+    return g;
+}
+
+int ensure_update_stream(PTContext* c)
+{
+    if (c->updStream) return PT_OK;
+    HIP_TRY(hipStreamCreateWithFlags(&c->updStream, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&c->updDone, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&c->updInput, hipEventDisableTiming));
+    return PT_OK;
+}
+
+int ensure_group(PTContext::UpdGroup& g, size_t genBytes, size_t stagingBytes)
+{
+    for (int k = 0; k < 2; ++k) {
+        if (!g.gen[k]) HIP_TRY(hipMalloc(&g.gen[k], genBytes));
+        if (!g.freeEv[k]) HIP_TRY(hipEventCreateWithFlags(&g.freeEv[k], hipEventDisableTiming));
+        if (!g.stagedEv[k]) HIP_TRY(hipEventCreateWithFlags(&g.stagedEv[k], hipEventDisableTiming));
+        if (stagingBytes && !g.staging[k]) HIP_TRY(hipHostMalloc(&g.staging[k], stagingBytes, hipHostMallocDefault));
+    }
+    g.stagingBytes = stagingBytes;
+    return PT_OK;
+}
+
+// The generation an update writes: not the current one; the update stream first waits until every piece of work that read
+// it (enqueued before it stopped being current) has finished.
+int begin_update(PTContext* c, PTContext::UpdGroup& g, int& target)
+{
+    target = g.cur == 0 ? 1 : 0;
+    if (g.freeRecorded[target]) HIP_TRY(hipStreamWaitEvent(c->updStream, g.freeEv[target], 0));
+    return PT_OK;
+}
+
+// host array -> pinned staging of `target` -> device, on the update stream; waits only for that staging buffer's last copy
+int stage_host(PTContext* c, PTContext::UpdGroup& g, int target, const void* src, size_t bytes, void* dst)
+{
+    if (g.stagedRecorded[target]) HIP_TRY(hipEventSynchronize(g.stagedEv[target]));
+    memcpy(g.staging[target], src, bytes);
+    HIP_TRY(hipMemcpyAsync(dst, g.staging[target], bytes, hipMemcpyHostToDevice, c->updStream));
+    HIP_TRY(hipEventRecord(g.stagedEv[target], c->updStream));
+    g.stagedRecorded[target] = true;
+    return PT_OK;
+}
+
+// the written generation becomes current: work enqueued from now on (passes on their set streams, the context stream's
+// queries, guides and resolves) waits for the update; the previous generation is free once the context stream reaches here
+int end_update(PTContext* c, PTContext::UpdGroup& g, int target)
+{
+    if (g.cur >= 0) {
+        HIP_TRY(hipEventRecord(g.freeEv[g.cur], c->stream));
+        g.freeRecorded[g.cur] = true;
+    }
+    g.cur = target;
+    HIP_TRY(hipEventRecord(c->updDone, c->updStream));
+    HIP_TRY(hipStreamWaitEvent(c->stream, c->updDone, 0));
+    c->updPending = true;
+    return PT_OK;
+}
+
+bool finite_record(const PTBlasInstance& r)
+{
+    for (float v : r.localToWorld) if (!std::isfinite(v)) return false;
+    for (float v : r.worldToLocal) if (!std::isfinite(v)) return false;
+    for (int k = 0; k < 3; ++k) if (!std::isfinite(r.aabbMin[k]) || !std::isfinite(r.aabbMax[k])) return false;
+    return true;
+}
+
+int update_instances(PTContext* c, const PTBlasInstance* src, uint32_t count, bool onDevice)
+{
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx == NULL");
+    if (!src) return fail(PT_ERR_INVALID_ARG, "instances == NULL");
+    if (!c->hasScene) return fail(PT_ERR_NO_SCENE, "PTSetScene has not been called");
+    if (!c->scene.hasTlas) return fail(PT_ERR_UNSUPPORTED, "instance updates need a HAS_TLAS scene");
+    const uint32_t n = c->instanceCount;
+    if (count != n) return fail(PT_ERR_INVALID_ARG, "count (" + std::to_string(count) + ") != the scene's instanceCount (" + std::to_string(n) + ")");
+    if (!onDevice)
+        for (uint32_t i = 0; i < n; ++i)
+            if (!finite_record(src[i])) return fail(PT_ERR_INVALID_ARG, "instance " + std::to_string(i) + ": non-finite matrix or AABB");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure_update_stream(c))) return rc;
+    PTContext::UpdGroup& g = c->updInst;
+    const bool fresh = g.gen[0] == nullptr;
+    if ((rc = ensure_group(g, inst_gen_bytes(n), onDevice ? 0 : (size_t)n * sizeof(PTBlasInstance)))) return rc;
+    if (!onDevice && !g.staging[0]) if ((rc = ensure_group(g, inst_gen_bytes(n), (size_t)n * sizeof(PTBlasInstance)))) return rc;
+    if (!c->tlasWork) {
+        HIP_TRY(hipMalloc(&c->tlasWork, pt_tlas_work_bytes(n)));
+        c->tlasW = pt_tlas_carve(c->tlasWork, n);
+    }
+    if (fresh)                                      // the offsets rows of both generations: PTSetScene's records
+        for (int k = 0; k < 2; ++k)
+            HIP_TRY(hipMemcpyAsync(inst_gen(g.gen[k], n).inst, c->instances.ptr, (size_t)n * 144, hipMemcpyDeviceToDevice, c->updStream));
+    int target;
+    if ((rc = begin_update(c, g, target))) return rc;
+    const size_t inBytes = (size_t)n * sizeof(PTBlasInstance);
+    if (onDevice) {
+        HIP_TRY(hipEventRecord(c->updInput, c->stream));
+        HIP_TRY(hipStreamWaitEvent(c->updStream, c->updInput, 0));
+        HIP_TRY(hipMemcpyAsync(c->tlasW.input, src, inBytes, hipMemcpyDeviceToDevice, c->updStream));
+    } else if ((rc = stage_host(c, g, target, src, inBytes, c->tlasW.input))) {
+        return rc;
+    }
+    const InstGen G = inst_gen(g.gen[target], n);
+    HIP_TRY(pt_launch_tlas_update(c->tlasW, c->tlasW.input, G.raw, G.bfs, G.byLeaf, G.inst, c->updStream));
+    if ((rc = end_update(c, g, target))) return rc;
+    c->scene.tlas = G.raw;
+    c->scene.tlasBfs = G.bfs;
+    c->scene.instances = (const float4*)G.inst;
+    c->scene.instByLeaf = (const float4*)G.byLeaf;
+    c->scene.tlasNodeCount = 2u * n - 1u;           // unreachable padding past the tree: the kernels only read reachable nodes
+    c->scene.tlasIndexOffset = (2u * n - 1u) * 16u;
+    return PT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+PT_API int PTUpdateInstances(PTContext* c, const PTBlasInstance* instances, uint32_t count)
+{
+    return update_instances(c, instances, count, false);
+}
+
+PT_API int PTUpdateInstancesDevice(PTContext* c, const PTBlasInstance* dInstances, uint32_t count)
+{
+    return update_instances(c, dInstances, count, true);
+}
+
+PT_API int PTUpdateLights(PTContext* c, const void* lights, uint32_t count)
+{
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx == NULL");
+    if (!lights) return fail(PT_ERR_INVALID_ARG, "lights == NULL");
+    if (!c->hasScene) return fail(PT_ERR_NO_SCENE, "PTSetScene has not been called");
+    if (!c->scene.hasLights) return fail(PT_ERR_UNSUPPORTED, "light updates need a scene set with HAS_LIGHTS");
+    if (count == 0 || count > c->sceneLightCount)
+        return fail(PT_ERR_INVALID_ARG, "count must be 1.." + std::to_string(c->sceneLightCount) + " (the lightCount given to PTSetScene)");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure_update_stream(c))) return rc;
+    PTContext::UpdGroup& g = c->updLights;
+    const size_t cap = (size_t)c->sceneLightCount * 64;
+    if ((rc = ensure_group(g, 2 * cap, cap))) return rc;
+    int target;
+    if ((rc = begin_update(c, g, target))) return rc;
+    float4* dl = (float4*)g.gen[target];
+    float4* dc = (float4*)((char*)g.gen[target] + cap);
+    if ((rc = stage_host(c, g, target, lights, (size_t)count * 64, dl))) return rc;
+    DScene S = c->scene;
+    S.lights = dl;
+    S.lightCount = (int32_t)count;
+    HIP_TRY(pt_launch_derive_lights(S, dc, c->updStream));
+    if ((rc = end_update(c, g, target))) return rc;
+    c->scene.lights = dl;
+    c->scene.lightConst = dc;
+    c->scene.lightCount = (int32_t)count;
+    return PT_OK;
+}
+
+PT_API int PTUpdateMaterials(PTContext* c, const void* materials, uint32_t count)
+{
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx == NULL");
+    if (!materials) return fail(PT_ERR_INVALID_ARG, "materials == NULL");
+    if (!c->hasScene) return fail(PT_ERR_NO_SCENE, "PTSetScene has not been called");
+    if (count != c->scene.materialCount)
+        return fail(PT_ERR_INVALID_ARG, "count (" + std::to_string(count) + ") != the scene's materialCount (" + std::to_string(c->scene.materialCount) + ")");
+    // the texture slots validate_scene checks: negative = none, otherwise a texture PTSetScene validated (the texture data
+    // itself was only borrowed for that call)
+    const float* mats = (const float*)materials;
+    if (c->scene.hasTextures)
+        for (uint32_t m = 0; m < count; ++m)
+            for (int k : {22, 23, 25, 26}) {
+                const float f = mats[(size_t)m * 32 + k];
+                if (f < 0.0f) continue;
+                const bool ok = f < 1.0e9f && std::binary_search(c->validTextures.begin(), c->validTextures.end(), (uint32_t)(uint64_t)f);
+                if (!ok) return fail(PT_ERR_INVALID_ARG, "material " + std::to_string(m) + ": texture index is not a texture PTSetScene validated");
+            }
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure_update_stream(c))) return rc;
+    PTContext::UpdGroup& g = c->updMats;
+    const size_t bytes = (size_t)count * 128;
+    if ((rc = ensure_group(g, bytes, bytes))) return rc;
+    int target;
+    if ((rc = begin_update(c, g, target))) return rc;
+    if ((rc = stage_host(c, g, target, materials, bytes, g.gen[target]))) return rc;
+    if ((rc = end_update(c, g, target))) return rc;
+    c->scene.materials = (const float4*)g.gen[target];
+    return PT_OK;
+}
+
+PT_API int PTReadTLAS(PTContext* c, void* dstNodes, uint64_t dstNodeBytes, uint32_t* dstIndices, uint64_t dstIndexCount, uint32_t* outNodeCount)
+{
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx == NULL");
+    if (!dstNodes || !dstIndices || !outNodeCount) return fail(PT_ERR_INVALID_ARG, "dstNodes / dstIndices / outNodeCount == NULL");
+    if (!c->hasScene) return fail(PT_ERR_NO_SCENE, "PTSetScene has not been called");
+    if (!c->scene.hasTlas) return fail(PT_ERR_UNSUPPORTED, "the scene has no TLAS");
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->updStream) HIP_TRY(hipStreamSynchronize(c->updStream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const uint32_t n = c->instanceCount;
+    uint32_t nodes = c->origTlasNodes;
+    const char* base = (const char*)c->tlas.ptr;
+    if (c->updInst.cur >= 0) {
+        HIP_TRY(hipMemcpy(&nodes, c->tlasW.ctrl, 4, hipMemcpyDeviceToHost));
+        if (nodes > 2u * n - 1u) return fail(PT_ERR_HIP, "internal: TLAS node count out of range");
+        base = (const char*)inst_gen(c->updInst.gen[c->updInst.cur], n).raw;
+    }
+    const size_t idxOff = c->updInst.cur >= 0 ? ((size_t)2 * n - 1) * 64 : (size_t)c->origTlasNodes * 64;
+    if (dstNodeBytes < (uint64_t)nodes * 64 || dstIndexCount < n)
+        return fail(PT_ERR_INVALID_ARG, "destination too small: " + std::to_string(nodes) + " nodes and " + std::to_string(n) + " indices");
+    HIP_TRY(hipMemcpy(dstNodes, base, (size_t)nodes * 64, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(dstIndices, base + idxOff, (size_t)n * 4, hipMemcpyDeviceToHost));
+    *outNodeCount = nodes;
     return PT_OK;
 }
 

@@ -102,6 +102,32 @@ class BVHScene:
             d.envHeight, d.envWidth = self.env_texture.shape[:2]
         return d
 
+    def UpdateTLAS(self, ctx, local_to_world) -> bool:
+        """BVHScene.UpdateTLAS (BVHScene.cs:769-841): for every instance whose localToWorld changed, recompute worldToLocal and
+        the world bounds as _build_two_level does, rewrite its BLASInstance / GPUInstance records, then rebuild the TLAS --
+        on the GPU, through PTUpdateInstances.  local_to_world: one 4x4 per instance.  Returns whether anything changed."""
+        from .scenes import instance_world_bounds
+        assert self.gpu_instances is not None, "UpdateTLAS needs a HAS_TLAS scene"
+        assert len(local_to_world) == self.gpu_instances.shape[0]
+        dirty = False
+        for k, l2w in enumerate(local_to_world):
+            l2w = np.asarray(l2w, np.float64)
+            packed = l2w.T.reshape(16).astype(np.float32)
+            if np.array_equal(packed.view(np.uint32), self.gpu_instances[k]["localToWorld"].view(np.uint32)):
+                continue
+            dirty = True
+            mesh = self.scene.instances[k][0]
+            w2l = np.linalg.inv(l2w)
+            t0, n = self.scene.mesh_ranges[mesh]
+            lo, hi = instance_world_bounds(self.scene.vertices[t0 * 3:(t0 + n) * 3], l2w)
+            for rec in (self.gpu_instances[k], self.blas_instances[k]):
+                rec["localToWorld"] = packed
+                rec["worldToLocal"] = w2l.T.reshape(16).astype(np.float32)
+            self.blas_instances[k]["aabbMin"], self.blas_instances[k]["aabbMax"] = lo, hi
+        if dirty:
+            plugin.check(plugin.load_library().PTUpdateInstances(ctx, self.blas_instances.ctypes.data, self.blas_instances.shape[0]))
+        return dirty
+
     def PrepareShader(self, ctx):
         """BVHScene.PrepareShader (BVHScene.cs:140-167): bind the buffers to the kernel."""
         plugin.check(plugin.load_library().PTSetScene(ctx, C.byref(self.desc())))
@@ -405,6 +431,48 @@ class PathTracer:
         plugin.check(self.lib.PTDenoise(self.ctx, C.byref(dp), C.c_void_p(d_src), C.c_void_p(dst.data_ptr())))
         self.synchronize()
         return dst.cpu().numpy()
+
+    # ---- scene updates (include/ptmi_plugin.h Part 5)
+    def set_instance_transforms(self, local_to_world) -> bool:
+        """Move the instances (one 4x4 localToWorld each): BVHScene.UpdateTLAS, then Reset() when anything changed, as the
+        reference's frame loop does (PathTracer.cs:169-183).  Returns whether anything changed."""
+        changed = self._bvhScene.UpdateTLAS(self.ctx, local_to_world)
+        if changed:
+            self.Reset()
+        return changed
+
+    def update_instances_device(self, records):
+        """PTUpdateInstancesDevice from a torch tensor on this context's device holding instanceCount PTBlasInstance records
+        (192 bytes each, e.g. uint8 (n, 192) or float32 (n, 48)).  Ordered after torch's current stream; torch's later work
+        is ordered after the update.  Does not reset accumulation."""
+        import torch
+        assert records.is_contiguous() and records.numel() * records.element_size() % 192 == 0
+        n = records.numel() * records.element_size() // 192
+        dev = records.device
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
+        ext.wait_stream(cur)
+        plugin.check(self.lib.PTUpdateInstancesDevice(self.ctx, records.data_ptr(), n))
+        cur.wait_stream(ext)
+
+    def update_lights(self, lights: np.ndarray):
+        """PTUpdateLights: (k, 16) float32 PTLight records, 1 <= k <= the scene's light count."""
+        L = np.ascontiguousarray(lights, dtype=np.float32).reshape(-1, 16)
+        plugin.check(self.lib.PTUpdateLights(self.ctx, L.ctypes.data, L.shape[0]))
+
+    def update_materials(self, materials: np.ndarray):
+        """PTUpdateMaterials: (materialCount, 32) float32 PTMaterialData records."""
+        M = np.ascontiguousarray(materials, dtype=np.float32).reshape(-1, 32)
+        plugin.check(self.lib.PTUpdateMaterials(self.ctx, M.ctypes.data, M.shape[0]))
+
+    def read_tlas(self):
+        """PTReadTLAS: the current TLAS as plugin.build_tlas returns it -> (node bytes uint8[], indices uint32[])."""
+        n = self._bvhScene.gpu_instances.shape[0]
+        nodes = np.empty((2 * n - 1) * 64, np.uint8)
+        idx = np.empty(n, np.uint32)
+        count = C.c_uint32()
+        plugin.check(self.lib.PTReadTLAS(self.ctx, nodes.ctypes.data, nodes.nbytes, idx.ctypes.data, n, C.byref(count)))
+        return nodes[:count.value * 64].copy(), idx
 
     def close(self):
         if self.ctx:

@@ -89,6 +89,10 @@ def load_library():
         "PTDenoise": (i32, [vp, C.POINTER(abi.PTDenoiseParams), vp, vp]),
         "PTDenoiseToHost": (i32, [vp, C.POINTER(abi.PTDenoiseParams), vp, C.c_uint64]),
         "PTGetGuidePointer": (vp, [vp, i32]),
+        # Part 5 (scene updates)
+        "PTUpdateInstances": (i32, [vp, vp, C.c_uint32]), "PTUpdateInstancesDevice": (i32, [vp, vp, C.c_uint32]),
+        "PTUpdateLights": (i32, [vp, vp, C.c_uint32]), "PTUpdateMaterials": (i32, [vp, vp, C.c_uint32]),
+        "PTReadTLAS": (i32, [vp, vp, C.c_uint64, vp, C.c_uint64, u32p]),
         "PTGetLastError": (C.c_char_p, []), "PTGetVersion": (i32, []),
     }
     for name, (res, args) in sig.items():
@@ -111,6 +115,7 @@ EXPORTED_SYMBOLS = [
     "PTGroupGetAssembledFrame", "PTGroupGetStats", "PTGroupResetStats",
     "PTTraceRays", "PTTraceRaysHost",
     "PTRenderGuides", "PTDenoise", "PTDenoiseToHost", "PTGetGuidePointer",
+    "PTUpdateInstances", "PTUpdateInstancesDevice", "PTUpdateLights", "PTUpdateMaterials", "PTReadTLAS",
     "PTGetLastError", "PTGetVersion",
 ]
 

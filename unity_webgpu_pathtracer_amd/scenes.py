@@ -18,7 +18,7 @@ The scenes are the configs of BASELINE.json: cornell (C1/C2), bunny (C3, "bunny-
 icosphere in the Cornell box), sponza (C4/C5, "Sponza-class" procedural atrium), plus `zoo`, a small
 scene that exercises every material lobe, light type, alpha mode, texture slot and the thin lens.
 """
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import numpy as np
 
@@ -846,6 +846,30 @@ def instance_world_bounds(local_verts, local_to_world):
     corners = np.array([[x, y, z, 1.0] for x in (lo[0], hi[0]) for y in (lo[1], hi[1]) for z in (lo[2], hi[2])])
     w = (local_to_world @ corners.T).T[:, :3]
     return w.min(axis=0).astype(F32), w.max(axis=0).astype(F32)
+
+
+def with_transforms(scene: Scene, local_to_world) -> Scene:
+    """The same HAS_TLAS scene with instance k placed by local_to_world[k] (4x4)."""
+    inst = [(mesh, np.asarray(m, np.float64), material) for (mesh, _, material), m in zip(scene.instances, local_to_world)]
+    assert len(inst) == len(scene.instances)
+    return replace(scene, instances=inst)
+
+
+def bounce_transforms(scene: Scene, t: float, movers=None):
+    """The motion of the reference's Assets/Examples/Scripts/Bounce.cs at Time.time = t: a moving instance's position is
+    startPosition + (0, startPosition.y + sin(2 t) * 2, 0) (as written there, startPosition.y counts twice).  `movers` lists the
+    instances that carry the script; default every instance but the first (the floor of instanced_scene).
+    Returns one float64 4x4 localToWorld per instance."""
+    out = []
+    movers = range(1, len(scene.instances)) if movers is None else movers
+    movers = set(movers)
+    for k, (_, l2w, _) in enumerate(scene.instances):
+        m = np.array(l2w, np.float64)
+        if k in movers:
+            y0 = float(np.float32(m[1, 3]))
+            m[1, 3] = float(np.float32(y0 + np.float32(y0 + np.float32(np.sin(np.float32(t) * np.float32(2.0))) * np.float32(2.0))))
+        out.append(m)
+    return out
 
 
 def bake_instances(scene: Scene) -> Scene:
