@@ -1,5 +1,5 @@
 #!/bin/bash
-# usage: tools/experiments/build_variant.sh NAME "-DPT_WF_FLAT=0 ..."   -> tools/experiments/variants/NAME.so
+# usage: tools/experiments/build_variant.sh NAME "-DPT_WF_TRI_PARK=8u ..."   -> tools/experiments/variants/NAME.so
 # Rebuilds only the translation units the -D flags can change (pt_wavefront.hip, pt_kernels.hip) and links them with the
 # default objects; tools/experiments/variants.py then benches every variant through PT_PLUGIN.
 set -e

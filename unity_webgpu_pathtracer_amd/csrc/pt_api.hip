@@ -122,8 +122,6 @@ struct PTContext {
     uint32_t subFrames = 1;                     // launch chains a pass is cut into (PTSetSubFrames)
     uint32_t numSets = 0;                       // passes in flight = state sets in use (PTSetPassesInFlight); carved on first use
     uint32_t wfIterations = 0;                  // 0 = automatic
-    uint32_t shadeSorted = PT_WF_SHADE_SORTED;  // PT_WF_SHADE_SORTED in the environment overrides (experiments)
-    uint32_t tailCut = PT_WF_TAIL_CUT;          // wavefront tail cut (pt_wavefront.hip tail_cut); PT_WF_TAIL_CUT in the environment overrides (experiments)
     // ray queries (PTTraceRays): grid caps per query kernel (read once), the CWBVH stack slab sized for the largest, host staging
     uint32_t queryCaps[PT_QUERY_KERNELS] = {};
     uint32_t queryCapMax = 0;
@@ -199,10 +197,7 @@ int ensure_wavefront(PTContext* c, PTContext::WfSet& set, uint32_t numSlots, uin
         HIP_TRY(hipEventCreateWithFlags(&set.done, hipEventDisableTiming));
     }
     const bool needTlas = c->scene.hasTlas != 0u;
-    set.wf.tailCut = c->tailCut;
-    set.wf.shadeSorted = c->shadeSorted;
-    const bool needRec = c->shadeSorted == 2u;
-    if (set.wf.flags && set.wf.numSlots == numSlots && set.wf.maxIterations >= maxIterations && (!needTlas || set.wf.tlasSpill) && (!needRec || set.wf.recPlanes)) return PT_OK;
+    if (set.wf.flags && set.wf.numSlots == numSlots && set.wf.maxIterations >= maxIterations && (!needTlas || set.wf.tlasSpill)) return PT_OK;
     const size_t n = numSlots;
     const uint32_t numRows = 4u * (numSlots >> 6);
     auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -218,8 +213,8 @@ int ensure_wavefront(PTContext* c, PTContext::WfSet& set, uint32_t numSlots, uin
     const size_t spillBytes = traceWaves * 64u * (size_t)(needTlas ? PT_WF_SPILL_ROW_ENTRIES : PT_BVH_STACK_SIZE - PT_WF_LDS_STACK) * sizeof(uint2);
     const size_t suspBytes = traceWaves * (size_t)(PT_WF_SUSPEND ? PT_WF_SUSPEND : 1u) * 6 * sizeof(uint4);
     const size_t tlasSpillBytes = needTlas ? traceWaves * 64u * (size_t)PT_BVH_STACK_SIZE * sizeof(uint32_t) : 0;
-    size_t total = align(n * 4) * 2 + align(n * 16) * PT_F4_COUNT + align(n * 2) + align((size_t)maxIterations * 4 * PT_WF_ALIVE_SHARDS) +
-                   align((size_t)numRows * 16 * 8) + align(8 * 32 * 4) + (needRec ? align(n * 16) * 10 + align(n * 4) + align(64) : 0) + align(spillBytes) + align(suspBytes) + align(traceWaves * 4) + align(tlasSpillBytes);
+    size_t total = align(n * 4) * 2 + align(n * 16) * PT_F4_COUNT + align(n * 2) + align((size_t)numRows * 16 * 8) + align(8 * 32 * 4) +
+                   align(spillBytes) + align(suspBytes) + align(traceWaves * 4) + align(tlasSpillBytes);
     // The arena only ever grows: a different slot count (another batch size, another frame size) that fits is a new carving of
     // the same memory -- launches already enqueued on the set's stream keep the pointers they were given and finish first
     // (stream order), so neither a synchronisation nor an allocation lands in a caller's timed region.
@@ -242,22 +237,13 @@ int ensure_wavefront(PTContext* c, PTContext::WfSet& set, uint32_t numSlots, uin
     B.f4base = B.ray[0];
     B.f4stride = (uint32_t)(align(n * 16) / 16);
     B.occl = (uint8_t*)carve(n * 2);
-    B.aliveFlags = (uint32_t*)carve((size_t)maxIterations * 4 * PT_WF_ALIVE_SHARDS);
     B.statRows = (unsigned long long*)carve((size_t)numRows * 16 * 8);
     B.chunkHeads = (uint32_t*)carve(8 * 32 * 4);
     B.stackSpill = (uint2*)carve(spillBytes);
     B.susp = (uint4*)carve(suspBytes);
     B.suspCount = (uint32_t*)carve(traceWaves * 4);
-    B.recPlanes = nullptr; B.recDest = nullptr; B.recCount = nullptr;
-    if (needRec) {
-        B.recPlanes = (float4*)carve(n * 16);
-        for (int k = 1; k < 10; ++k) carve(n * 16);
-        B.recDest = (uint32_t*)carve(n * 4);
-        B.recCount = (uint32_t*)carve(64);
-    }
     B.tlasSpill = needTlas ? (uint32_t*)carve(tlasSpillBytes) : nullptr;
     B.residentWaves = residentWaves;
-    B.tailCut = c->tailCut;
     B.numSlots = numSlots;
     B.numStatRows = numRows;
     B.maxIterations = maxIterations;
@@ -579,8 +565,6 @@ PT_API int PTCreate(int deviceIndex, PTContext** outCtx)
     PTContext* c = new PTContext();
     c->device = deviceIndex;
     c->numSets = default_passes_in_flight();
-    if (const char* e = getenv("PT_WF_SHADE_SORTED")) c->shadeSorted = (uint32_t)strtoul(e, nullptr, 10);
-    if (const char* e = getenv("PT_WF_TAIL_CUT")) c->tailCut = (uint32_t)strtoul(e, nullptr, 10);
     hipError_t se = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (se != hipSuccess) { delete c; return fail(PT_ERR_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(se)); }
     se = hipMalloc((void**)&c->dStats, 16 * sizeof(unsigned long long));

@@ -619,10 +619,6 @@ PT_DEV void derive_light_rows(const DLight& light, float4 rows[4])
 // identical lane requests on the vector-memory path -- which costs a broadcast as much as a gather (~55 CU-cycles per instruction,
 // tools/microbench/gather16.hip) and parks the result in VGPRs.  Round 3: the light loop of intersect_lights issued ~5 such loads per
 // light and shading step, ~6 x 10^8 lane requests per Sponza-class pass, a tenth of all vector-memory requests.
-#ifndef PT_UNIFORM_LIGHTS
-#define PT_UNIFORM_LIGHTS 0          // scenes with at most this many lights read all of them per wave (scalar loads) in nee_prepare_light.
-                                     // Measured with 4 on the two-light Sponza-class scene: 5,088 against 5,102 Mrays/s with 0 (the per-lane gather): off
-#endif
 typedef float pt_vec4 __attribute__((ext_vector_type(4)));
 PT_DEV float4 pt_uniform_load(const float4* p, size_t index)          // p + index must be the same address in every lane of the wave
 {
@@ -715,11 +711,8 @@ PT_DEV v4 sample_texture(const DScene& S, int32_t textureIndex, v2 uv, Counters&
 }
 
 // The four texture lookups of a material (base colour, emission, metallic-roughness, occlusion) as TWO memory round trips for
-// all of them -- every wanted descriptor, then every texel -- instead of two per texture one after the other (PT_TEX_BATCH).
+// all of them -- every wanted descriptor, then every texel -- instead of two per texture one after the other.
 // Same arithmetic per texture as sample_texture (same counters), only the order of the requests differs.
-#ifndef PT_TEX_BATCH
-#define PT_TEX_BATCH 1
-#endif
 template <bool STATS>
 PT_DEV void sample_textures4(const DScene& S, const bool want[4], const int32_t index[4], const v2 uvs[4], v4 out[4], Counters& cn)
 {
@@ -779,20 +772,13 @@ PT_DEV Material get_material(const DScene& S, int32_t materialIndex, v3 rayDir, 
     const bool T = S.hasTextures != 0u;
     v2 uv = hit.uv;
     v4 bco = {d1.x, d1.y, d1.z, d1.w};
-#if PT_TEX_BATCH
     const bool want[4] = {T && !(d6t1.z < 0.0f), T && !(t2.y < 0.0f), T && !(d6t1.w < 0.0f), T && !(t2.z < 0.0f)};
     const int32_t tindex[4] = {pt_f2i(d6t1.z), pt_f2i(t2.y), pt_f2i(d6t1.w), pt_f2i(t2.z)};
     const v2 uvs[4] = {{uv.x * tr.x + tr.z, uv.y * tr.y + tr.w}, uv, uv, uv};
     v4 texel[4];
     if (T) sample_textures4<STATS>(S, want, tindex, uvs, texel, cn);
-#endif
     if (T && !(d6t1.z < 0.0f)) {                                          // GetBaseColorOpacity :56-69
-#if PT_TEX_BATCH
         v4 px = texel[0];
-#else
-        v2 tuv = {uv.x * tr.x + tr.z, uv.y * tr.y + tr.w};
-        v4 px = sample_texture<STATS>(S, pt_f2i(d6t1.z), tuv, cn);
-#endif
         bco = px * bco;
     }
     Material m;
@@ -802,20 +788,12 @@ PT_DEV Material get_material(const DScene& S, int32_t materialIndex, v3 rayDir, 
     m.alphaCutoff = d2.w;
     m.emission = mk3(d2.x, d2.y, d2.z);
     if (T && !(t2.y < 0.0f)) {                                            // GetEmission :8-21
-#if PT_TEX_BATCH
         v4 px = texel[1];
-#else
-        v4 px = sample_texture<STATS>(S, pt_f2i(t2.y), uv, cn);
-#endif
         m.emission = mk3(px.x, px.y, px.z);
     }
     float metallic = d3.x, rough = d3.y;
     if (T && !(d6t1.w < 0.0f)) {                                          // GetMetallicRoughness :40-54
-#if PT_TEX_BATCH
         v4 px = texel[2];
-#else
-        v4 px = sample_texture<STATS>(S, pt_f2i(d6t1.w), uv, cn);
-#endif
         metallic = px.z;
         rough = px.y * px.y;
     }
@@ -832,11 +810,7 @@ PT_DEV Material get_material(const DScene& S, int32_t materialIndex, v3 rayDir, 
     m.anisotropic = pt_clamp(d4.y, -0.9f, 0.9f);
     m.occlusion = 1.0f;
     if (T && !(t2.z < 0.0f)) {                                            // GetOcclusion :71-82
-#if PT_TEX_BATCH
         float px = texel[3].x;
-#else
-        float px = sample_texture<STATS>(S, pt_f2i(t2.z), uv, cn).x;
-#endif
         m.occlusion = 1.0f + (px - 1.0f);
     }
     float aspect = pt_sqrt(1.0f - m.anisotropic * 0.9f);
@@ -1328,25 +1302,12 @@ PT_DEV void nee_prepare_light(const DScene& S, v3 rayDir, const SurfHit& hit, co
     if (!S.hasLights) return;
     int32_t lightIndex = pt_f2i(rnd(rng) * (float)S.lightCount);
     if (lightIndex > S.lightCount - 1) lightIndex = S.lightCount - 1;
-    // The picked light differs from lane to lane, but with a handful of lights it is cheaper to read EVERY light once per wave
-    // through the scalar path (pt_uniform_load) and keep the lane's own than to gather six rows per lane: no vector-memory
-    // requests, no dependent round trip in front of the BSDF evaluation.  Same records, same values.
-    DLight light;
-    float4 lcN, lcNN;
-    if (S.lightCount <= PT_UNIFORM_LIGHTS) {
-        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a, c = a, d = a;
-        lcN = a; lcNN = a;
-        for (int i = 0; i < S.lightCount; ++i) {
-            const float4 ua = pt_uniform_load(S.lights, (size_t)i * 4), ub = pt_uniform_load(S.lights, (size_t)i * 4 + 1),
-                         uc = pt_uniform_load(S.lights, (size_t)i * 4 + 2), ud = pt_uniform_load(S.lights, (size_t)i * 4 + 3),
-                         un = pt_uniform_load(S.lightConst, (size_t)i * 4), unn = pt_uniform_load(S.lightConst, (size_t)i * 4 + 3);
-            if (lightIndex == i) { a = ua; b = ub; c = uc; d = ud; lcN = un; lcNN = unn; }
-        }
-        light.position = mk3(a.x, a.y, a.z); light.type = pt_asuint(a.w);
-        light.emission = mk3(b.x, b.y, b.z); light.range = b.w;
-        light.u = mk3(c.x, c.y, c.z); light.area = c.w;
-        light.v = mk3(d.x, d.y, d.z);
-    } else {
+    // the picked light differs from lane to lane: a per-lane gather (reading every light through the scalar path and keeping
+    // the lane's own was measured no faster).  hasLights implies lightCount >= 1 (PTSetScene, PTUpdateLights), so
+    // the guard never fails; without it the megakernel and the fused kernel spill more.
+    DLight light = {};
+    float4 lcN = make_float4(0.0f, 0.0f, 0.0f, 0.0f), lcNN = lcN;
+    if (S.lightCount > 0) {
         light = load_light(S, lightIndex);
         lcN = S.lightConst[(size_t)lightIndex * 4]; lcNN = S.lightConst[(size_t)lightIndex * 4 + 3];
     }
@@ -1546,18 +1507,6 @@ PT_DEV void path_apply_pending(PathRegs& r, bool occEnv, bool occLight)
 // ---- (2) shade the closest hit                           (util/pathtrace.hlsl:27-127).  Precondition: r.state == PS_TRACE.
 // Reads r.ro, rd, radiance, throughput, scatterPdf, maxRoughness, rng, depth; writes those plus state, hasPending, green,
 // env, light, neeOrigin, pendThroughput.
-// -DPT_SHADE_TIME (diagnostics build, STATS instantiations only; tools/experiments/shade_time.py): clock ticks >> 4 a WAVE spends in the
-// sections of the shading step, through the work counters: attrFetches = hit attributes + light intersection, pixelsRead = miss / light-hit
-// branch, materialFetches = material + textures, texelFetches = environment NEE, lightFetches = light NEE, texDescFetches = BSDF sampling + the
-// rest, tlasNodeVisits = the whole step, instanceVisits = wave executions of the step
-#ifdef PT_SHADE_TIME
-#define PT_ST_BEGIN() const unsigned long long _st0 = __builtin_readcyclecounter()
-#define PT_ST_MARK(var) unsigned long long var = __builtin_readcyclecounter()
-#define PT_ST_ADD(field, a, b) do { if (STATS && (int)(threadIdx.x & 63u) == __ffsll((long long)__ballot(true)) - 1) cn.field += (uint32_t)(((b) - (a)) >> 4); } while (0)
-#else
-#define PT_ST_MARK(var) do { } while (0)
-#define PT_ST_ADD(field, a, b) do { } while (0)
-#endif
 template <bool STATS, class NeeSink = NoNeeSink>
 PT_DEV void path_shade_hit(const DScene& S, const PTFrameParams& P, PathRegs& r, const HitRecord& rec, Counters& cn, NeeSink neeSink = NeeSink())
 {
@@ -1570,17 +1519,11 @@ PT_DEV void path_shade_hit(const DScene& S, const PTFrameParams& P, PathRegs& r,
         hit.materialIndex = 0;
         hit.position = mk3(0.0f); hit.normal = mk3(0.0f); hit.ffnormal = mk3(0.0f);
         hit.uv = {0.0f, 0.0f};
-        PT_ST_MARK(st0);
         if (rec.h.t < PT_FAR_PLANE) {
             if (S.hasTlas) fetch_hit_attributes_tlas(S, r.rd, rec, hit);
             else fetch_hit_attributes<STATS>(S, r.ro, r.rd, rec.h, hit, cn);
         }
         intersect_lights<STATS>(S, r.ro, r.rd, hit, cn);
-        PT_ST_MARK(st1);
-        PT_ST_ADD(attrFetches, st0, st1);
-#ifdef PT_SHADE_TIME
-        if (STATS && (int)(threadIdx.x & 63u) == __ffsll((long long)__ballot(true)) - 1) cn.instanceVisits++;
-#endif
 
         if (!(hit.distance < PT_FAR_PLANE)) {
             v4 sky = sample_sky_radiance(S, P, r.rd, r.depth);
@@ -1588,20 +1531,13 @@ PT_DEV void path_shade_hit(const DScene& S, const PTFrameParams& P, PathRegs& r,
             if (r.depth > 0u) misWeight = power_heuristic(r.scatterPdf, sky.w);
             if (misWeight > 0.0f) r.radiance = r.radiance + misWeight * mk3(sky.x, sky.y, sky.z) * r.throughput;
             r.state = PS_ENDING;
-            PT_ST_MARK(st2);
-            PT_ST_ADD(pixelsRead, st1, st2);
         } else if (S.hasLights && hit.isLight) {
             DLight light = load_light(S, (int)hit.triIndex);
-#ifndef PT_SHADE_TIME
             if (STATS) cn.lightFetches++;
-#endif
             r.radiance = r.radiance + light.emission * r.throughput;
             r.state = PS_ENDING;
         } else {
-            PT_ST_MARK(st3);
             Material material = get_material<STATS>(S, hit.materialIndex, r.rd, hit, cn);
-            PT_ST_MARK(st4);
-            PT_ST_ADD(materialFetches, st3, st4);
             r.maxRoughness = pt_max(r.maxRoughness, material.roughness);
             material.roughness = r.maxRoughness;
             r.radiance = r.radiance + material.emission * r.throughput;
@@ -1624,13 +1560,8 @@ PT_DEV void path_shade_hit(const DScene& S, const PTFrameParams& P, PathRegs& r,
                     BsdfShared sh;
                     tint_colors(material, material.eta, sh.F0, sh.Csheen, sh.Cspec0);
                     const Onb ffOnb = make_onb(hit.ffnormal);
-                    PT_ST_MARK(st5);
                     nee_prepare_environment(S, P, r.rd, hit, material, r.rng, r.env, sh, ffOnb);
-                    PT_ST_MARK(st6);
-                    PT_ST_ADD(texelFetches, st5, st6);
                     nee_prepare_light<STATS>(S, r.rd, hit, material, r.neeOrigin, r.rng, r.light, cn, sh, ffOnb);
-                    PT_ST_MARK(st7);
-                    PT_ST_ADD(lightFetches, st6, st7);
                     r.pendThroughput = r.throughput;
                     r.hasPending = true;
                     neeSink(r);
@@ -1648,8 +1579,6 @@ PT_DEV void path_shade_hit(const DScene& S, const PTFrameParams& P, PathRegs& r,
                         advance = false;
                     }
                     if (advance) r.depth++;
-                    PT_ST_MARK(st8);
-                    PT_ST_ADD(texDescFetches, st7, st8);
                 }
                 if (advance) {
                     r.rd = scatterL;
@@ -1764,25 +1693,16 @@ PT_DEV bool ray_begin(RayState& r, v3 o, v3 d, bool anyHit)
 }
 
 // one outer iteration; returns true when the traversal is complete
-#ifdef PT_TRACE_DIAG
-#define PT_DIAG_WAVE_COUNT(field) do { if ((int)(threadIdx.x & 63u) == __ffsll((long long)__ballot(true)) - 1) cn.field++; } while (0)
-#else
-#define PT_DIAG_WAVE_COUNT(field) do { } while (0)
-#endif
-
 template <bool STATS, class ST>
 PT_DEV bool ray_step(const DScene& S, RayState& r, ST& st, Counters& cn)
 {
-    PT_DIAG_WAVE_COUNT(attrFetches);          // wave-level outer iterations
     if (r.ng.y > 0x00FFFFFFu) {
-        PT_DIAG_WAVE_COUNT(materialFetches);  // wave-level node-block executions
         cwbvh_visit_node<STATS>(S.nodes, 0u, r.o, r.invDir, r.octinv4, r.hit.t, r.ng, r.tg, r.sp, r.overflow, st, cn);
     } else {
         r.tg = r.ng;
         r.ng = make_uint2(0u, 0u);
     }
     while (r.tg.y != 0u) {
-        PT_DIAG_WAVE_COUNT(lightFetches);     // wave-level triangle-block executions
         uint32_t triangleIndex = 31u - (uint32_t)__clz((int)r.tg.y);
         uint32_t triAddr = r.tg.x + triangleIndex * 3u;
         intersect_triangle(S.tris, triAddr, r.o, r.d, r.hit);
@@ -1800,62 +1720,8 @@ PT_DEV bool ray_step(const DScene& S, RayState& r, ST& st, Counters& cn)
     return false;
 }
 
-// ray_unistep: the same traversal in finer steps, with ONE memory round trip per wave iteration.  Every lane first decides what it does next
-// -- test the next triangle of its group, or (pop and) visit the next node -- and only computes an ADDRESS; then all lanes
-// request their rows together (3 rows for a triangle, 5 for a node), and after that single wait the node block and the
-// triangle block run one after the other under their lane masks.  With the nested loops of ray_step a wave iteration paid a
-// node round trip and then one more round trip per triangle of its slowest lane (2.1 on average, at 8 % lane utilisation in
-// the triangle block); here a lane with triangles pending simply stays in "triangle mode" for as many iterations as it has
-// triangles while its neighbours keep visiting nodes.  The per-ray sequence of operations is that of traverse_cwbvh.
-template <bool STATS, class ST>
-PT_DEV bool ray_unistep(const DScene& S, RayState& r, ST& st, Counters& cn)
-{
-    bool finished = false;
-    const bool isTri = r.tg.y != 0u;
-    bool isNode = false;
-    uint32_t triangleIndex = 0u;
-    const uint4* p = S.nodes;
-    if (isTri) {
-        triangleIndex = 31u - (uint32_t)__clz((int)r.tg.y);
-        p = (const uint4*)S.tris + (size_t)(r.tg.x + triangleIndex * 3u);
-    } else {
-        if (r.ng.y <= 0x00FFFFFFu) {
-            if (r.sp > 0u) { --r.sp; r.ng = stack_pop(st, r.sp); }
-            else finished = true;
-        }
-        if (!finished) {
-            if (r.ng.y > 0x00FFFFFFu) {
-                isNode = true;
-                p = S.nodes + (size_t)cwbvh_pick_child<STATS>(r.ng, r.octinv4, r.sp, r.overflow, st, cn) * 5;
-            } else {
-                r.tg = r.ng;                                   // a triangle group came off the stack (util/bvh.hlsl:172-176)
-                r.ng = make_uint2(0u, 0u);
-            }
-        }
-    }
-    uint4 q0 = make_uint4(0u, 0u, 0u, 0u), q1 = q0, q2 = q0, q3 = q0, q4 = q0;
-    if (isTri || isNode) {
-        q0 = p[0]; q1 = p[1]; q2 = p[2];
-        if (isNode) { q3 = p[3]; q4 = p[4]; }
-    }
-    asm volatile("" : "+v"(q0.x), "+v"(q1.x), "+v"(q2.x), "+v"(q3.x), "+v"(q4.x));      // all rows requested before the first use
-    if (isNode) {
-        cwbvh_apply_node<STATS>(r.o, r.invDir, r.octinv4, r.hit.t, q0, q1, q2, q3, q4, r.ng, r.tg, cn);
-    } else if (isTri) {
-        const float4 t0 = make_float4(pt_asfloat(q0.x), pt_asfloat(q0.y), pt_asfloat(q0.z), pt_asfloat(q0.w));
-        const float4 t1 = make_float4(pt_asfloat(q1.x), pt_asfloat(q1.y), pt_asfloat(q1.z), pt_asfloat(q1.w));
-        const float4 t2 = make_float4(pt_asfloat(q2.x), pt_asfloat(q2.y), pt_asfloat(q2.z), pt_asfloat(q2.w));
-        intersect_triangle_rows<false>(t0, t1, t2, 0u, r.o, r.d, r.hit);
-        if (STATS) cn.triTests++;
-        r.tg.y -= 1u << triangleIndex;
-        if (r.anyHit && r.hit.t < PT_FAR_PLANE) finished = true;
-    }
-    if (finished && STATS && r.overflow) cn.overflows++;
-    return finished;
-}
-
-// The two halves of ray_unistep as separate phases, so that a wave can decide per iteration WHICH phase to run: the triangle
-// block costs ~100 VALU instructions per execution whatever the number of lanes in it, so lanes whose node visit produced
+// The traversal of ray_step in finer steps -- ONE triangle test, or (pop and) visit ONE node -- as separate phases, so that a wave
+// can decide per iteration WHICH phase to run: the triangle block costs ~100 VALU instructions per execution whatever the number of lanes in it, so lanes whose node visit produced
 // triangles PARK until enough of them have accumulated (pt_wavefront.hip, PT_WF_TRI_PARK).  A lane's own sequence of operations
 // -- hence every result and counter -- is unchanged: it only waits.
 template <bool STATS>

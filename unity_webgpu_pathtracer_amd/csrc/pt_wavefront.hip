@@ -71,20 +71,6 @@ PT_DEV void store_path(const PTWfBuffers& B, uint32_t slot, const PathRegs& r, b
     }
 }
 
-// Tail cut: B.aliveFlags[i] = number of slots still alive after shade launch i (zeroed at the start of a pass).  Once that
-// drops below B.tailCut, every later trace / shade launch of the pass returns at its first instruction and pt_wf_cleanup runs
-// the stragglers to completion: the last ~20 of the 52 iterations of a pass used to cost ~170 us each (the latency of the
-// longest surviving ray, three launches per iteration) for a handful of rays.  Wave-uniform, no host synchronisation.
-// The count is kept in PT_WF_ALIVE_SHARDS words per iteration (a wave adds to word blockIdx % SHARDS): 32,000 atomics per
-// launch on ONE word serialise in one L2 channel and doubled the time of a pass.
-PT_DEV bool tail_cut(const PTWfBuffers& B, uint32_t iteration)
-{
-    if (iteration == 0u || B.tailCut == 0u) return false;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t part = lane < PT_WF_ALIVE_SHARDS ? B.aliveFlags[(iteration - 1u) * PT_WF_ALIVE_SHARDS + lane] : 0u;
-    return wave_sum_u32(part) < B.tailCut;
-}
-
 // per-wave counter rows: one wave owns a row, so a plain read-modify-write is race-free across launches of one stream
 template <bool STATS>
 PT_DEV void flush_counters(const Counters& cn, unsigned long long* rows, uint32_t row, uint32_t lane)
@@ -147,7 +133,6 @@ template <bool STATS, bool TLAS>
 __global__ __launch_bounds__(256, 4) void pt_wf_trace(DScene S, PTWfBuffers B, uint32_t iteration)
 {
     __shared__ uint2 s_stack[PT_LDS_STACK][256];
-    if (tail_cut(B, iteration)) return;
     const uint32_t nb = B.numSlots >> 8;
     const uint32_t vb = blockIdx.x;
     const uint32_t kind = vb / nb;
@@ -199,25 +184,9 @@ static_assert(PT_WF_RANGE >= 64u && (PT_WF_RANGE & (PT_WF_RANGE - 1u)) == 0u,
 #ifndef PT_WF_REFILL
 #define PT_WF_REFILL 16u        // refill when at least this many lanes are idle
 #endif
-#ifndef PT_WF_FLAT
-#define PT_WF_FLAT 0            // 0: ray_step (node visit + all its triangles per wave iteration), 2: ray_unistep (one triangle OR one node visit, one memory round trip)
-#endif
 #ifndef PT_WF_TRI_PARK
-#define PT_WF_TRI_PARK 4u       // > 0: two-phase wave iteration (ray_tri_one / ray_node_one); lanes with triangles pending wait until
-                                // that many lanes do.  0: ray_step's nested loops.  2 ... 12 measure the same (+6 %), 16: +3 %, 24: -2 %
-#endif
-#ifndef PT_WF_ROOT_SCALAR
-#define PT_WF_ROOT_SCALAR 0     // 1: main refill launch reads the root node once per wave through the scalar path and visits it when a ray is taken.
-                                // Measured: 4,918 / 4,938 against 5,090 / 5,063 Mrays/s -- 4.5e8 lane requests and one dependent fetch per ray saved, but the
-                                // node test then runs in the refill block at 25-50 % of the lanes (round 2's LDS copy of the root lost the same way)
-#endif
-#ifndef PT_WF_HIT_REGS
-#define PT_WF_HIT_REGS 1        // main refill launch (with PT_WF_TRI_PARK): the hit's (u, v, triIndex) stay in registers until the ray ends
-#endif
-#if PT_WF_FLAT == 2
-#define PT_WF_STEP ray_unistep
-#else
-#define PT_WF_STEP ray_step
+#define PT_WF_TRI_PARK 4u       // two-phase wave iteration (ray_tri_one / ray_node_one): lanes with triangles pending wait until that many lanes
+                                // do.  2 ... 12 measure the same (+6 % over ray_step's nested loops), 16: +3 %, 24: -2 %
 #endif
 
 // LDS words the lanes of a wave exchange through, as LDS-address-space pointers: through a generic `volatile uint32_t*` every
@@ -289,7 +258,6 @@ template <bool STATS, bool TAIL, uint32_t RANGE>
 __global__ __launch_bounds__(64, PT_WF_TRACE_MIN_WAVES) void pt_wf_trace_refill(DScene S, PTWfBuffers B, uint32_t iteration)
 {
     __shared__ uint2 s_stack[PT_WF_LDS_STACK][64];
-    if (tail_cut(B, iteration)) return;                               // main and tail launch of an iteration decide alike
     __shared__ uint32_t s_xchg[TAIL ? PT_WF_TAIL_GROUP * (PT_WF_SUSPEND ? PT_WF_SUSPEND : 1u) : 64u];
     // the wave's counter row is parked in LDS until the end: kept in a register it is the one value the compiler spilled to
     // scratch, and ANY scratch costs this kernel its occupancy (see TravStackT)
@@ -329,18 +297,6 @@ __global__ __launch_bounds__(64, PT_WF_TRACE_MIN_WAVES) void pt_wf_trace_refill(
     st.stride = 64u;
     st.gbase = B.stackSpill;
     st.gwave = PT_LDS_WORD(s_gw);                                                 // slab row = wave * 64 + lane < numSlots
-#if PT_WF_ROOT_SCALAR
-    uint4 root0 = make_uint4(0u, 0u, 0u, 0u), root1 = root0, root2 = root0, root3 = root0, root4 = root0;
-    if (!TAIL) {
-        const float4 r0 = pt_uniform_load((const float4*)S.nodes, 0), r1 = pt_uniform_load((const float4*)S.nodes, 1), r2 = pt_uniform_load((const float4*)S.nodes, 2),
-                     r3 = pt_uniform_load((const float4*)S.nodes, 3), r4 = pt_uniform_load((const float4*)S.nodes, 4);
-        root0 = make_uint4(pt_asuint(r0.x), pt_asuint(r0.y), pt_asuint(r0.z), pt_asuint(r0.w));
-        root1 = make_uint4(pt_asuint(r1.x), pt_asuint(r1.y), pt_asuint(r1.z), pt_asuint(r1.w));
-        root2 = make_uint4(pt_asuint(r2.x), pt_asuint(r2.y), pt_asuint(r2.z), pt_asuint(r2.w));
-        root3 = make_uint4(pt_asuint(r3.x), pt_asuint(r3.y), pt_asuint(r3.z), pt_asuint(r3.w));
-        root4 = make_uint4(pt_asuint(r4.x), pt_asuint(r4.y), pt_asuint(r4.z), pt_asuint(r4.w));
-    }
-#endif
     RayState rs;
     rs.sp = 0u; rs.anyHit = false; rs.overflow = false;
     bool have = false;
@@ -378,18 +334,7 @@ __global__ __launch_bounds__(64, PT_WF_TRACE_MIN_WAVES) void pt_wf_trace_refill(
                         // NaN ray: certain miss
                         if (myKind == 0u) store_miss(B, mySlot);
                         else store_occlusion(B, myKind, mySlot, false);
-                    } else {
-                        have = true;
-#if PT_WF_ROOT_SCALAR
-                        // Every ray's first node visit is the ROOT (ray_begin leaves the node group (0, bit 31): child 0 of base 0): the
-                        // same five rows for every lane.  They are read once per wave through the scalar path (root0..root4) and the
-                        // visit happens here, at refill time: ~9 x 10^7 rays x 5 rows per pass leave the vector-memory path and every
-                        // ray's chain of dependent fetches is one shorter.  Same operations per ray: cwbvh_pick_child (nothing to push:
-                        // the group holds one child) + cwbvh_apply_node.
-                        rs.ng.y = 0u;                                                       // the root taken off its node group
-                        cwbvh_apply_node<STATS>(rs.o, rs.invDir, rs.octinv4, rs.hit.t, root0, root1, root2, root3, root4, rs.ng, rs.tg, cn);
-#endif
-                    }
+                    } else have = true;
                 }
                 __builtin_amdgcn_wave_barrier();
                 cursor += consumed;
@@ -429,61 +374,31 @@ __global__ __launch_bounds__(64, PT_WF_TRACE_MIN_WAVES) void pt_wf_trace_refill(
         const bool exhausted = cursor >= nItems;
         const uint32_t stopAt = !exhausted ? PT_WF_REFILL : ((!TAIL && PT_WF_SUSPEND > 0u) ? 64u - PT_WF_SUSPEND : 64u);
         while (nIdle < stopAt) {
-#ifdef PT_TRACE_HIST
-            // diagnostics build: histogram of active lanes per wave iteration, reported through the shading counters
-            // (attrFetches: 1-8 lanes, materialFetches: 9-16, lightFetches: 17-32, texelFetches: 33-48, texDescFetches: 49-64;
-            //  tlasNodeVisits: iterations after the wave's candidates were exhausted)
-            {
-                const uint32_t nAct = (uint32_t)__popcll(__ballot(have));
-                if (lane == 0u) {
-                    if (nAct <= 8u) cn.attrFetches++; else if (nAct <= 16u) cn.materialFetches++; else if (nAct <= 32u) cn.lightFetches++;
-                    else if (nAct <= 48u) cn.texelFetches++; else cn.texDescFetches++;
-                    if (exhausted) cn.tlasNodeVisits++;
-                }
-            }
-#endif
-#if PT_WF_TRI_PARK > 0
             // Two phases per wave iteration instead of ray_step's nested loops: (1) every lane with a triangle pending tests ONE
             // (the block runs when PT_WF_TRI_PARK lanes want it, or when nobody can do anything else), (2) every lane without a
             // triangle pending -- including those that have just tested their last one -- pops and visits its next node.  A lane
             // with k triangles spends k - 1 extra iterations in phase 1 while its neighbours keep visiting nodes; the triangle
             // block runs once per iteration at ~3x the lane utilisation of the nested loop (2.1 executions at 8 %).
-            {
-                const bool wantTri = have && rs.tg.y != 0u;
-                const uint32_t nT = (uint32_t)__popcll(__ballot(wantTri));
-                const uint32_t nN = (uint32_t)__popcll(__ballot(have && !wantTri));
-                bool fin = false;
-                if ((nT >= PT_WF_TRI_PARK || nN == 0u) && wantTri) {
-                    const float tBefore = rs.hit.t;
-                    fin = ray_tri_one<STATS>(S, rs, cn);
-                    // TAIL: the hit record goes to memory when a test improved it (a resumed ray has only t in registers).
-                    // main launch (PT_WF_HIT_REGS): (u, v, triIndex) stay in registers and are written once, when the ray finishes or is suspended
-                    if ((TAIL || !PT_WF_HIT_REGS) && myKind == 0u && rs.hit.t < tBefore) f4_array(B, PT_F4_HIT)[mySlot] = make_float4(rs.hit.t, rs.hit.u, rs.hit.v, pt_asfloat(rs.hit.triIndex));
-                }
-                if (have && !fin && rs.tg.y == 0u) fin = ray_node_one<STATS>(S, rs, st, cn);
-                if (fin) {
-                    if (myKind == 0u) {
-                        if (!(rs.hit.t < PT_FAR_PLANE)) store_miss(B, mySlot);
-                        else if (!TAIL && PT_WF_HIT_REGS) f4_array(B, PT_F4_HIT)[mySlot] = make_float4(rs.hit.t, rs.hit.u, rs.hit.v, pt_asfloat(rs.hit.triIndex));
-                    }
-                    else store_occlusion(B, myKind, mySlot, rs.hit.t < PT_FAR_PLANE);
-                    have = false;
-                }
-            }
-#else
-            if (have) {
-                // the hit record goes to memory whenever a step improved it, so (u, v, triIndex) need no registers across
-                // iterations (64 VGPRs without a spill = no scratch, see TravStackT); a ray that never hits writes the miss
+            const bool wantTri = have && rs.tg.y != 0u;
+            const uint32_t nT = (uint32_t)__popcll(__ballot(wantTri));
+            const uint32_t nN = (uint32_t)__popcll(__ballot(have && !wantTri));
+            bool fin = false;
+            if ((nT >= PT_WF_TRI_PARK || nN == 0u) && wantTri) {
                 const float tBefore = rs.hit.t;
-                const bool fin = PT_WF_STEP<STATS>(S, rs, st, cn);
-                if (myKind == 0u && rs.hit.t < tBefore) f4_array(B, PT_F4_HIT)[mySlot] = make_float4(rs.hit.t, rs.hit.u, rs.hit.v, pt_asfloat(rs.hit.triIndex));
-                if (fin) {
-                    if (myKind == 0u) { if (!(rs.hit.t < PT_FAR_PLANE)) store_miss(B, mySlot); }
-                    else store_occlusion(B, myKind, mySlot, rs.hit.t < PT_FAR_PLANE);
-                    have = false;
-                }
+                fin = ray_tri_one<STATS>(S, rs, cn);
+                // TAIL: the hit record goes to memory when a test improved it (a resumed ray has only t in registers).
+                // main launch: (u, v, triIndex) stay in registers and are written once, when the ray finishes or is suspended
+                if (TAIL && myKind == 0u && rs.hit.t < tBefore) f4_array(B, PT_F4_HIT)[mySlot] = make_float4(rs.hit.t, rs.hit.u, rs.hit.v, pt_asfloat(rs.hit.triIndex));
             }
-#endif
+            if (have && !fin && rs.tg.y == 0u) fin = ray_node_one<STATS>(S, rs, st, cn);
+            if (fin) {
+                if (myKind == 0u) {
+                    if (!(rs.hit.t < PT_FAR_PLANE)) store_miss(B, mySlot);
+                    else if (!TAIL) f4_array(B, PT_F4_HIT)[mySlot] = make_float4(rs.hit.t, rs.hit.u, rs.hit.v, pt_asfloat(rs.hit.triIndex));
+                }
+                else store_occlusion(B, myKind, mySlot, rs.hit.t < PT_FAR_PLANE);
+                have = false;
+            }
             nIdle = (uint32_t)__popcll(__ballot(!have));
         }
         if (!TAIL && PT_WF_SUSPEND > 0u && exhausted && nIdle < 64u) {
@@ -491,18 +406,12 @@ __global__ __launch_bounds__(64, PT_WF_TRACE_MIN_WAVES) void pt_wf_trace_refill(
             if (__ballot(have && rs.sp > PT_WF_LDS_STACK) != 0ull) {
                 while (__ballot(have && rs.sp > PT_WF_LDS_STACK) != 0ull) {
                     if (have) {
-                        const float tBefore = rs.hit.t;
-#if PT_WF_TRI_PARK > 0
                         // a lane may arrive with triangles pending: one triangle OR one node visit, whichever is next for it
                         const bool fin = rs.tg.y != 0u ? ray_tri_one<STATS>(S, rs, cn) : ray_node_one<STATS>(S, rs, st, cn);
-#else
-                        const bool fin = PT_WF_STEP<STATS>(S, rs, st, cn);
-#endif
-                        if ((TAIL || !PT_WF_HIT_REGS || PT_WF_TRI_PARK == 0u) && myKind == 0u && rs.hit.t < tBefore) f4_array(B, PT_F4_HIT)[mySlot] = make_float4(rs.hit.t, rs.hit.u, rs.hit.v, pt_asfloat(rs.hit.triIndex));
                         if (fin) {
                             if (myKind == 0u) {
                                 if (!(rs.hit.t < PT_FAR_PLANE)) store_miss(B, mySlot);
-                                else if (!TAIL && PT_WF_HIT_REGS && PT_WF_TRI_PARK > 0u) f4_array(B, PT_F4_HIT)[mySlot] = make_float4(rs.hit.t, rs.hit.u, rs.hit.v, pt_asfloat(rs.hit.triIndex));
+                                else f4_array(B, PT_F4_HIT)[mySlot] = make_float4(rs.hit.t, rs.hit.u, rs.hit.v, pt_asfloat(rs.hit.triIndex));
                             } else store_occlusion(B, myKind, mySlot, rs.hit.t < PT_FAR_PLANE);
                             have = false;
                         }
@@ -511,7 +420,7 @@ __global__ __launch_bounds__(64, PT_WF_TRACE_MIN_WAVES) void pt_wf_trace_refill(
             }
             const unsigned long long act = __ballot(have);
             // a suspended bounce ray leaves its best hit so far in the hit array (the tail launch writes there only when it improves it)
-            if (PT_WF_HIT_REGS && PT_WF_TRI_PARK > 0u && have && myKind == 0u && rs.hit.t < PT_FAR_PLANE)
+            if (have && myKind == 0u && rs.hit.t < PT_FAR_PLANE)
                 f4_array(B, PT_F4_HIT)[mySlot] = make_float4(rs.hit.t, rs.hit.u, rs.hit.v, pt_asfloat(rs.hit.triIndex));
             if (have) suspend_ray(B, *PT_LDS_WORD(s_gw) * PT_WF_SUSPEND + rank_below(act), mySlot, myKind, rs, st);
             have = false;
@@ -537,16 +446,9 @@ __global__ __launch_bounds__(64, PT_WF_TRACE_MIN_WAVES) void pt_wf_trace_refill(
 #define PT_WF_TLAS_LDS_STACK 8u
 #endif
 
-#ifndef PT_WF_TLAS_STEPS
-#define PT_WF_TLAS_STEPS 0xFFFFFFFFu // TLAS-walk steps a lane between instances takes per wave iteration (0xFFFFFFFF: until it is inside the next instance).
-                                     // 200-instance scene, 1080p / 8 spp: unbounded 2,076 Mrays/s, 1 step 1,971, 2 steps 1,889 (round 3)
-#endif
 #ifndef PT_WF_TLAS_CONT
 #define PT_WF_TLAS_CONT 16u          // > 1: a lane keeps walking the TLAS within one wave iteration only while at least this many lanes walk with it
                                      // (0 / 4 / 8 / 16 / 24 / 32: 2,070 / 2,091 / 2,124 / 2,130 / 2,097 / 2,049 Mrays/s on the 200-instance scene)
-#endif
-#ifndef PT_WF_TLAS_QUORUM
-#define PT_WF_TLAS_QUORUM 0u         // > 0: the TLAS-walk block runs when that many lanes want it, or when no lane is inside an instance (8: 1,920, 16: 1,892)
 #endif
 #ifndef PT_WF_TLAS_MIN_WAVES
 #define PT_WF_TLAS_MIN_WAVES 6      // 80 VGPRs, no scratch (without the SLP vectorizer); 5 waves: -3 %
@@ -568,7 +470,6 @@ __global__ __launch_bounds__(64 * WAVES, PT_WF_TLAS_MIN_WAVES) void pt_wf_trace_
     constexpr uint32_t kBlasLds = kCached ? (uint32_t)PT_WF_TLAS_BLAS_LDS_STACK : (uint32_t)PT_WF_LDS_STACK;
     typedef typename std::conditional<kCached, uint16_t, uint32_t>::type tentry_t;
     __shared__ uint2 s_stack[WAVES][kBlasLds][64];
-    if (tail_cut(B, iteration)) return;
     __shared__ tentry_t s_tstack[WAVES][PT_WF_TLAS_LDS_STACK][64];
     __shared__ uint32_t s_xchg[WAVES][64];
     __shared__ uint32_t s_gw[WAVES];
@@ -682,37 +583,17 @@ __global__ __launch_bounds__(64 * WAVES, PT_WF_TLAS_MIN_WAVES) void pt_wf_trace_
         if (nIdle == 64u) break;
         const uint32_t stopAt = (kCached ? more : cursor < nItems) ? PT_WF_REFILL : 64u;
         do {
-#ifdef PT_TLAS_DIAG
-            // diagnostics builds (tools/experiments/tlas_diag.sh): wave-level event counts / clock ticks through the two pixel counters
-            const bool dl0 = lane == (uint32_t)(__ffsll((long long)__ballot(true)) - 1);
-            if (PT_TLAS_DIAG == 1 && dl0) cn.pixelsWritten++;                                   // outer wave iterations
-            const unsigned long long dT0 = __builtin_readcyclecounter();
-#endif
             // ---- a lane that is between instances (its instance epilogue is done) walks the TLAS to the next instance whose box it hits.
             //      Per ray of the 200-instance scene: 13.0 TLAS nodes + 5.9 instance entries + 9.6 BLAS nodes + 3.0 triangles = 37
-            //      steps against 18.6 for the same geometry baked flat.  Measured with the -DPT_TLAS_DIAG builds (tools/experiments/
-            //      tlas_diag.py): this block is 57 % of the loop's time; it runs in 45 % of the wave iterations, 11 inner steps per
-            //      execution (until its slowest lane is inside an instance) at 15.5 of 64 lanes, 80.8 M wave-steps per pass against 16.2 M
-            //      executions of the CWBVH step below (37.8 lanes).  Neither the chain's length (one fetch per instance entry instead
-            //      of two, instByLeaf: no change) nor its scheduling (one TLAS step per wave iteration, a quorum for entering the block,
-            //      triangle parking: all slower) is the lever; letting the last few walkers wait for company (PT_WF_TLAS_CONT) is
-            //      worth 3 %.  What is left is the work itself: 19 TLAS steps per ray at a quarter of the lanes.
-#ifndef PT_WF_TLAS_SPLIT_ENTRY
-#define PT_WF_TLAS_SPLIT_ENTRY 1     // 1: the walk loop only visits TLAS nodes; lanes that reached a leaf (or still have instances of their leaf left) enter
-                                     // their instance together in ONE block after it.  0 (round 2): the ~130-instruction entry path sits inside the walk loop and runs
-                                     // in most of its ~11 steps per execution for one or two lanes each
-#endif
-            const bool walkT = have && !inBlas && (!PT_WF_TLAS_SPLIT_ENTRY || instLeft == 0u);
-#if PT_WF_TLAS_QUORUM > 0
-            const uint32_t nWalk = (uint32_t)__popcll(__ballot(walkT)), nIn = (uint32_t)__popcll(__ballot(have && inBlas));
-            const bool runWalk = nWalk >= PT_WF_TLAS_QUORUM || nIn == 0u;
-#else
-            const bool runWalk = true;
-#endif
-#ifdef PT_TLAS_DIAG
-            if (PT_TLAS_DIAG == 1 && dl0 && __ballot(walkT && runWalk) != 0ull) cn.pixelsRead++;      // executions of the TLAS-walk block
-            if (PT_TLAS_DIAG == 3 && walkT) cn.pixelsRead++;                                        // lanes entering the walk block
-#endif
+            //      steps against 18.6 for the same geometry baked flat.  Measured: this block is 57 % of the loop's
+            //      time; it runs in 45 % of the wave iterations, 11 inner steps per execution (until its slowest lane is inside an
+            //      instance) at 15.5 of 64 lanes, 80.8 M wave-steps per pass against 16.2 M executions of the CWBVH step below (37.8
+            //      lanes).  Neither the chain's length (one fetch per instance entry instead of two, instByLeaf: no change) nor its
+            //      scheduling (one TLAS step per wave iteration, a quorum for entering the block, triangle parking: all slower) is the
+            //      lever; letting the last few walkers wait for company (PT_WF_TLAS_CONT) is worth 3 %.  What is left is the work
+            //      itself: 19 TLAS steps per ray at a quarter of the lanes.
+            //      The walk loop only visits TLAS nodes: lanes that reached a leaf (or still have instances of their leaf left) enter
+            //      their instance together in ONE block after it.
             // enter the next instance of the current TLAS leaf (tlas.hlsl:129-147)
             // ONE fetch: the record PTSetScene laid out per TLAS index slot (worldToLocal, offsets, instance index) instead of
             // TLASData[TLASIndexOffset + k] -> instance record (two dependent fetches; same values)
@@ -732,16 +613,12 @@ __global__ __launch_bounds__(64 * WAVES, PT_WF_TLAS_MIN_WAVES) void pt_wf_trace_
                 hitFound = false;
                 inBlas = true;
             };
-            if (walkT && runWalk) {
+            if (have && !inBlas && instLeft == 0u) {
                 bool finished = false;
-                for (uint32_t stepT = 0; stepT < PT_WF_TLAS_STEPS; ++stepT) {
+                for (uint32_t stepT = 0;; ++stepT) {                  // no step bound: until inside the next instance
                     // the lanes still walking are the wave's active lanes here; when only a few are left they wait for company (the
                     // lanes whose instance ends in this wave iteration) instead of stepping through the TLAS at 1-2 lanes per instruction
                     if (PT_WF_TLAS_CONT > 1u && stepT > 0u && (uint32_t)__popcll(__ballot(true)) < PT_WF_TLAS_CONT) break;
-#ifdef PT_TLAS_DIAG
-                    if (PT_TLAS_DIAG == 2) { cn.pixelsRead++; if (lane == (uint32_t)(__ffsll((long long)__ballot(true)) - 1)) cn.pixelsWritten++; }   // lane-steps / wave-steps inside the walk block
-#endif
-                    if (!PT_WF_TLAS_SPLIT_ENTRY && instLeft > 0u) { enter_instance(); break; }
                     if (needPop) {
                         if (tsp == 0u) { finished = true; break; }
                         nodeIndex = tpop();
@@ -785,7 +662,7 @@ __global__ __launch_bounds__(64 * WAVES, PT_WF_TLAS_MIN_WAVES) void pt_wf_trace_
                         nextInst = pt_asuint(e.w);
                         instLeft = instanceCount;
                         needPop = true;                                    // after the leaf's instances
-                        if (PT_WF_TLAS_SPLIT_ENTRY) break;                 // to the entry block below
+                        break;                                             // to the entry block below
                     }
                 }
                 if (finished) {
@@ -794,11 +671,7 @@ __global__ __launch_bounds__(64 * WAVES, PT_WF_TLAS_MIN_WAVES) void pt_wf_trace_
                     have = false;
                 }
             }
-            if (PT_WF_TLAS_SPLIT_ENTRY && have && !inBlas && instLeft > 0u) enter_instance();
-#ifdef PT_TLAS_DIAG
-            const unsigned long long dT1 = __builtin_readcyclecounter();
-            if (PT_TLAS_DIAG == 3 && have && inBlas) cn.pixelsWritten++;                             // lanes in the CWBVH step
-#endif
+            if (have && !inBlas && instLeft > 0u) enter_instance();
             // ---- the hot step: one CWBVH iteration inside the current instance
             if (have && inBlas) {
                 const float tBefore = rs.hit.t;
@@ -844,9 +717,6 @@ __global__ __launch_bounds__(64 * WAVES, PT_WF_TLAS_MIN_WAVES) void pt_wf_trace_
                     }
                 }
             }
-#ifdef PT_TLAS_DIAG
-            if (PT_TLAS_DIAG == 4 && dl0) { const unsigned long long dT2 = __builtin_readcyclecounter(); cn.pixelsRead += (uint32_t)((dT1 - dT0) >> 4); cn.pixelsWritten += (uint32_t)((dT2 - dT1) >> 4); }
-#endif
             nIdle = (uint32_t)__popcll(__ballot(!have));
         } while (nIdle < stopAt);
     }
@@ -885,7 +755,6 @@ template <bool STATS>
 __global__ __launch_bounds__(64, PT_WF_TRACE_MIN_WAVES) void pt_wf_trace_persist(DScene S, PTWfBuffers B, uint32_t iteration)
 {
     __shared__ uint2 s_stack[PT_WF_LDS_STACK][64];
-    if (tail_cut(B, iteration)) return;
     __shared__ uint32_t s_xchg[64];
     const uint32_t lane = threadIdx.x;
     const uint32_t numChunks = (B.numSlots + PT_WF_CHUNK - 1u) / PT_WF_CHUNK;
@@ -954,7 +823,7 @@ __global__ __launch_bounds__(64, PT_WF_TRACE_MIN_WAVES) void pt_wf_trace_persist
         do {
             if (have) {
                 const float tBefore = rs.hit.t;
-                const bool fin = PT_WF_STEP<STATS>(S, rs, st, cn);
+                const bool fin = ray_step<STATS>(S, rs, st, cn);
                 if (myKind == 0u && rs.hit.t < tBefore) f4_array(B, PT_F4_HIT)[mySlot] = make_float4(rs.hit.t, rs.hit.u, rs.hit.v, pt_asfloat(rs.hit.triIndex));
                 if (fin) {
                     if (myKind == 0u) { if (!(rs.hit.t < PT_FAR_PLANE)) store_miss(B, mySlot); }
@@ -1080,9 +949,7 @@ PT_DEV bool shade_slot(const DScene& S, const PTFrameParams& P, const PTTileMap&
     return r.state != PS_DONE;
 }
 
-// one lane per slot, in screen order.  (Walking a compacted or class-sorted list of live slots instead was built twice and is
-// slower -- round 2: shade VALU -41 %, throughput -20 % -- because path state is then read and written through gathers;
-// DESIGN.md 5.1.)
+// one lane per slot, in screen order: every regrouping of the slots that shade a hit was measured slower
 #ifndef PT_WF_SHADE_BLOCK
 #define PT_WF_SHADE_BLOCK 64u          // one wave per workgroup: a finished wave frees its 128 VGPRs at once (256 -> 64: +4 %)
 #endif
@@ -1093,21 +960,9 @@ __global__ __launch_bounds__(PT_WF_SHADE_BLOCK, PT_WF_SHADE_MIN_WAVES) void pt_w
     const uint32_t vb = blockIdx.x;
     const uint32_t slot = vb * PT_WF_SHADE_BLOCK + threadIdx.x;
     if (vb == 0u && threadIdx.x < PT_WF_SHARDS) B.chunkHeads[threadIdx.x * 32u] = 0u;   // for the next trace launch (schedule 3)
-    if (tail_cut(B, iteration)) return;                               // (aliveFlags[iteration] stays 0: the later launches return too)
     const uint32_t f = B.flags[slot];
     Counters cn = {};
-    bool alive = false;
-#ifdef PT_SHADE_DIAG
-    // diagnostics build: wave-level executions of the shade body and lanes active in them (reported in the TLAS counters)
-    if (__any(fl_state(f) != PS_DONE) && (threadIdx.x & 63u) == 0u) cn.tlasNodeVisits++;
-    if (fl_state(f) != PS_DONE) cn.instanceVisits++;
-#endif
-    if (fl_state(f) != PS_DONE) alive = shade_slot<STATS>(S, P, tm, B, slot, slot, f, cn);
-    {
-        const uint32_t nAlive = (uint32_t)__popcll(__ballot(alive));
-        if (B.tailCut != 0u && nAlive && (threadIdx.x & 63u) == 0u)
-            atomicAdd(&B.aliveFlags[iteration * PT_WF_ALIVE_SHARDS + (blockIdx.x & (PT_WF_ALIVE_SHARDS - 1u))], nAlive);   // one atomic per wave that still has paths
-    }
+    if (fl_state(f) != PS_DONE) shade_slot<STATS>(S, P, tm, B, slot, slot, f, cn);
     flush_counters<STATS>(cn, B.statRows, vb * (PT_WF_SHADE_BLOCK / 64u) + (threadIdx.x >> 6), threadIdx.x & 63u);
 }
 
@@ -1189,18 +1044,6 @@ __global__ __launch_bounds__(64, PT_WF_FUSED_WAVES) void pt_wf_fused(DScene S, P
     __builtin_amdgcn_wave_barrier();
     uint32_t nSusp = 0u, pb = 0u;
     bool more = true;
-#ifdef PT_FUSED_DIAG
-    // diagnostics build: wave time per phase (s_memtime ticks), rounds, reported through the shading counters of the FULL-stats variant:
-    // attrFetches = refill ticks / 1024, materialFetches = trace ticks / 1024, lightFetches = shade ticks / 1024, texDescFetches = rounds
-    unsigned long long tRefill = 0ull, tTrace = 0ull, tShade = 0ull, tMark = __builtin_readcyclecounter();
-    uint32_t rounds = 0u, dIter = 0u, dScan = 0u, dTri = 0u;
-    unsigned long long tScan = 0ull;
-#define PT_DIAG_INC(x) do { x++; } while (0)
-#define PT_DIAG_LAP(acc) do { const unsigned long long now_ = __builtin_readcyclecounter(); acc += now_ - tMark; tMark = now_; } while (0)
-#else
-#define PT_DIAG_LAP(acc) do { } while (0)
-#define PT_DIAG_INC(x) do { } while (0)
-#endif
 
     while (true) {
         // ---- (0) refill: a context without a pixel takes the next pixel of the frame and starts its first sample
@@ -1238,7 +1081,6 @@ __global__ __launch_bounds__(64, PT_WF_FUSED_WAVES) void pt_wf_fused(DScene S, P
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         __builtin_amdgcn_wave_barrier();
-        PT_DIAG_LAP(tRefill);
 
         // ---- (1) trace: resume what was parked, then scan the contexts' flag words kind-major and keep 64 traversals in flight
         {
@@ -1301,7 +1143,6 @@ __global__ __launch_bounds__(64, PT_WF_FUSED_WAVES) void pt_wf_fused(DScene S, P
             while (true) {
                 uint32_t nIdle = (uint32_t)__popcll(__ballot(!have));
                 while (cursor < nItems && (nIdle >= PT_WF_REFILL || nIdle == 64u)) {
-                    PT_DIAG_INC(dScan);
                     const unsigned long long idle = __ballot(!have);
                     const uint32_t rankI = rank_below(idle);
                     const uint32_t item = cursor + lane;
@@ -1344,12 +1185,11 @@ __global__ __launch_bounds__(64, PT_WF_FUSED_WAVES) void pt_wf_fused(DScene S, P
                 const bool mayPark = PT_WF_SUSPEND > 0u && exhausted && startedNew;
                 const uint32_t stopAt = !exhausted ? PT_WF_REFILL : (mayPark ? 64u - PT_WF_SUSPEND : 64u);
                 while (nIdle < stopAt) {
-                    PT_DIAG_INC(dIter);
                     const bool wantTri = have && rs.tg.y != 0u;
                     const uint32_t nT = (uint32_t)__popcll(__ballot(wantTri));
                     const uint32_t nN = (uint32_t)__popcll(__ballot(have && !wantTri));
                     bool fin = false;
-                    if ((nT >= PT_WF_TRI_PARK || nN == 0u) && wantTri) { PT_DIAG_INC(dTri); fin = ray_tri_one<STATS>(S, rs, cn); }
+                    if ((nT >= PT_WF_TRI_PARK || nN == 0u) && wantTri) fin = ray_tri_one<STATS>(S, rs, cn);
                     if (have && !fin && rs.tg.y == 0u) fin = ray_node_one<STATS>(S, rs, st, cn);
                     if (fin) finish();
                     nIdle = (uint32_t)__popcll(__ballot(!have));
@@ -1389,7 +1229,6 @@ __global__ __launch_bounds__(64, PT_WF_FUSED_WAVES) void pt_wf_fused(DScene S, P
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         __builtin_amdgcn_wave_barrier();
-        PT_DIAG_LAP(tTrace);
 
         // ---- (2) shade: every context whose rays have all returned
 #pragma unroll 1
@@ -1408,16 +1247,7 @@ __global__ __launch_bounds__(64, PT_WF_FUSED_WAVES) void pt_wf_fused(DScene S, P
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         __builtin_amdgcn_wave_barrier();
-        PT_DIAG_LAP(tShade);
-#ifdef PT_FUSED_DIAG
-        rounds++;
-#endif
     }
-#ifdef PT_FUSED_DIAG
-    if (lane == 0u) { cnt[5] = (uint32_t)(tRefill >> 10); cnt[6] = (uint32_t)(tTrace >> 10); cnt[7] = (uint32_t)(tShade >> 10); cnt[9] = rounds;
-                      cnt[8] = dIter; cnt[14] = dScan; cnt[15] = dTri; }
-    __builtin_amdgcn_wave_barrier();
-#endif
     // the wave's totals -> its counter row (a wave owns row blockIdx.x for the whole launch)
     __builtin_amdgcn_wave_barrier();
     if (lane < PT_NUM_COUNTERS) {
@@ -1425,395 +1255,6 @@ __global__ __launch_bounds__(64, PT_WF_FUSED_WAVES) void pt_wf_fused(DScene S, P
         const unsigned long long v = cnt[lane];
         if (lane == 12u) { if (v > *p) *p = v; } else if (v) *p += v;
     }
-}
-
-// ------------------------------------------------------------------------------------------
-// shade, regrouped through LDS (round 3).  path_step() is three stages: (1) add the pending NEE of the last bounce, (2) shade the
-// closest hit that came back -- attributes, lights, material + textures, two NEE evaluations, BSDF sampling, roulette: ~90 % of the
-// kernel's instructions -- and (3) end-of-sample bookkeeping / next camera ray.  In slot order a wave runs stage 2 with whatever
-// lanes happen to need it: 75 % of the slots are alive, about 60 % of those have a surface hit, and the wave still issues every
-// instruction of every branch any lane takes (38 % VALU lane utilisation, profiles/r03_pmc.json).  Sorting the slot LIST fixed
-// that and lost to the state gathers it caused (round 2: shade VALU -41 %, throughput -20 %).
-//
-// Here loads and stores stay coalesced in slot order (the HOME lane of a slot runs stages 1 and 3 and does all global state
-// traffic), and only stage 2 is regrouped: inside a 256-slot workgroup the slots that need it are ranked -- surface hits first,
-// then misses / light candidates, stable in slot order -- their stage-2 inputs (20 words) go to LDS record [rank], lane i of the
-// workgroup shades record i, writes the 31 words of results back in place, and the home lanes pick them up.  Waves of the workgroup
-// are therefore full surface-hit waves, at most one mixed wave, and waves with nothing to shade, which skip stage 2 altogether.
-// The values a path sees are those of path_step() in the same order: frames and counters are bit-identical.
-// LDS: 35 fields x 256 x 4 B = 35 KB per workgroup, SoA (one ds_*_b32 per field and lane, conflict-free) -> 4 workgroups per CU.
-//
-// MEASURED (round 3, Sponza-class 1080p / 8 spp; tools/experiments/sorted_pmc.sh): SQ_INSTS_VALU of the shade launches 4.46e9 ->
-// 3.35e9 per pass (-25 %), lanes per VALU instruction 38 % -> 54 %, bit-identical frames and counters (the parity suite runs it) --
-// and the launches take 9.8 instead of 7.7 ms per pass, the pipelined bench 4,390 instead of 5,030 Mrays/s.  The shade step is a
-// chain of dependent fetches (state -> attributes -> material -> texels -> lights) that needs many waves in flight to hide; after
-// the regrouping a workgroup's surface hits sit in ~2 of its 4 waves and the other two WAIT at the barriers holding their
-// registers and the workgroup's LDS: per CU, 6-7 waves do stage 2 where 16 one-wave workgroups did before.  Fewer instructions,
-// fewer waves to overlap their latency -- the second effect wins.  Kept as a variant (PT_WF_SHADE_SORTED=1 in the environment
-// selects it); what would cash the instruction saving in is a regrouping that does not park waves: stage 2 as its own launch
-// over compacted records.
-// ------------------------------------------------------------------------------------------
-#define PT_SH_FIELDS 31u
-#define PT_SH_HOME 4u
-template <bool STATS>
-__global__ __launch_bounds__(256, PT_WF_SHADE_MIN_WAVES) void pt_wf_shade_sorted(DScene S, PTFrameParams P, PTTileMap tm, PTWfBuffers B, uint32_t iteration)
-{
-    __shared__ uint32_t s_rec[PT_SH_FIELDS][256];      // stage-2 records, field-major
-    __shared__ uint32_t s_home[PT_SH_HOME][256];       // what a home lane parks across stage 2: throughput before the bounce (or radiance / rng of a slot that skips stage 2)
-    __shared__ uint32_t s_cnt[2][4];                   // per wave: slots of class 0 (surface hit), class 1 (miss)
-    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
-    const uint32_t slot = blockIdx.x * 256u + tid;
-    if (blockIdx.x == 0u && tid < PT_WF_SHARDS) B.chunkHeads[tid * 32u] = 0u;   // for the next trace launch (schedule 3)
-    if (tail_cut(B, iteration)) return;
-    Counters cn = {};
-    const uint32_t f = B.flags[slot];
-    const bool live = fl_state(f) != PS_DONE;
-    auto put = [&](uint32_t field, uint32_t idx, uint32_t v) { s_rec[field][idx] = v; };
-    auto putf = [&](uint32_t field, uint32_t idx, float v) { s_rec[field][idx] = pt_asuint(v); };
-    auto get = [&](uint32_t field, uint32_t idx) -> uint32_t { return s_rec[field][idx]; };
-    auto getf = [&](uint32_t field, uint32_t idx) -> float { return pt_asfloat(s_rec[field][idx]); };
-
-    // ---- stage 1 at home: the slot's state (one batch of coalesced loads), pending NEE applied
-    uint32_t key = 2u;                                              // 0: surface hit to shade, 1: miss (sky / analytic light), 2: no stage 2
-    {
-        uint32_t rng = B.rng[slot];
-        float4 qro = B.ray[0][2u * slot], qrd = B.ray[0][2u * slot + 1u], qrad = B.rad[slot], qthr = B.thr[slot];
-        float4 qenvC = B.envC[slot], qlightC = B.lightC[slot], qpthr = B.pthr[slot], qhit = B.hit[slot];
-        uint32_t o0 = B.occl[slot], o1 = B.occl[(size_t)B.numSlots + slot];
-        float4 qhit2 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (S.hasTlas) qhit2 = B.hit2[slot];
-        asm volatile("" : "+v"(rng), "+v"(qro.x), "+v"(qrd.x), "+v"(qrad.x), "+v"(qthr.x), "+v"(qenvC.x), "+v"(qlightC.x), "+v"(qpthr.x), "+v"(qhit.x), "+v"(o0), "+v"(o1), "+v"(qhit2.x));
-        if (live) {
-            PathRegs r;
-            r.state = fl_state(f);
-            r.hasPending = fl_pending(f);
-            r.env.valid = fl_env(f);
-            r.light.valid = fl_light(f);
-            r.green = (f >> 6) & 1u;
-            r.radiance = xyz(qrad);
-            r.env.contribution = r.hasPending ? xyz(qenvC) : mk3(0.0f);
-            r.light.contribution = r.hasPending ? xyz(qlightC) : mk3(0.0f);
-            r.pendThroughput = r.hasPending ? xyz(qpthr) : mk3(0.0f);
-            const bool occEnv = r.hasPending && o0 != 0u, occLight = r.hasPending && o1 != 0u;
-            path_apply_pending(r, occEnv, occLight);
-            if (r.state == PS_TRACE) key = qhit.x < PT_FAR_PLANE ? 0u : 1u;
-            qrad = f4(r.radiance, 0.0f);
-        }
-        // ---- rank the slots that need stage 2 (stable partition of the workgroup's 256 slots: class 0, then class 1)
-        const unsigned long long m0 = __ballot(key == 0u), m1 = __ballot(key == 1u);
-        if (lane == 0u) { s_cnt[0][wave] = (uint32_t)__popcll(m0); s_cnt[1][wave] = (uint32_t)__popcll(m1); }
-        __syncthreads();
-        uint32_t base0 = 0u, base1 = 0u, total0 = 0u, total1 = 0u;
-#pragma unroll
-        for (uint32_t w = 0; w < 4u; ++w) {
-            const uint32_t c0 = s_cnt[0][w], c1 = s_cnt[1][w];
-            if (w < wave) { base0 += c0; base1 += c1; }
-            total0 += c0; total1 += c1;
-        }
-        const uint32_t dest = key == 0u ? base0 + rank_below(m0) : (key == 1u ? total0 + base1 + rank_below(m1) : 0xFFFFu);
-        key |= dest << 2;                                            // the lane's own ticket, kept across stage 2 in ONE register
-        key |= (total0 + total1) << 20;
-        if (dest != 0xFFFFu) {
-            putf(0, dest, qro.x); putf(1, dest, qro.y); putf(2, dest, qro.z);
-            putf(3, dest, qrd.x); putf(4, dest, qrd.y); putf(5, dest, qrd.z);
-            put(6, dest, rng); put(7, dest, f >> 19);               // depth
-            putf(8, dest, qro.w); putf(9, dest, qrd.w);             // scatterPdf, maxRoughness
-            putf(10, dest, qthr.x); putf(11, dest, qthr.y); putf(12, dest, qthr.z);
-            putf(13, dest, qrad.x); putf(14, dest, qrad.y); putf(15, dest, qrad.z);
-            putf(16, dest, qhit.x); putf(17, dest, qhit.y); putf(18, dest, qhit.z); putf(19, dest, qhit.w);
-            if (S.hasTlas) { putf(20, dest, qhit2.x); putf(21, dest, qhit2.y); putf(22, dest, qhit2.z); putf(23, dest, qhit2.w); }
-            s_home[0][tid] = pt_asuint(qthr.x); s_home[1][tid] = pt_asuint(qthr.y); s_home[2][tid] = pt_asuint(qthr.z);    // the throughput the NEE of this bounce applies to
-        } else {
-            s_home[0][tid] = pt_asuint(qrad.x); s_home[1][tid] = pt_asuint(qrad.y); s_home[2][tid] = pt_asuint(qrad.z);
-            s_home[3][tid] = rng;
-        }
-    }
-    __syncthreads();
-
-    // ---- stage 2: lane i shades record i (waves beyond the last record skip it)
-    const uint32_t nWork = key >> 20;
-    if (tid < nWork) {
-        PathRegs w;
-        w.ro = mk3(getf(0, tid), getf(1, tid), getf(2, tid));
-        w.rd = mk3(getf(3, tid), getf(4, tid), getf(5, tid));
-        w.rng = get(6, tid); w.depth = get(7, tid);
-        w.scatterPdf = getf(8, tid); w.maxRoughness = getf(9, tid);
-        w.throughput = mk3(getf(10, tid), getf(11, tid), getf(12, tid));
-        w.radiance = mk3(getf(13, tid), getf(14, tid), getf(15, tid));
-        HitRecord ch;
-        ch.h.t = getf(16, tid); ch.h.u = getf(17, tid); ch.h.v = getf(18, tid); ch.h.triIndex = get(19, tid);
-        ch.pos = mk3(0.0f); ch.inst = 0u;
-        if (S.hasTlas) { ch.pos = mk3(getf(20, tid), getf(21, tid), getf(22, tid)); ch.inst = get(23, tid); }
-        w.state = PS_TRACE; w.hasPending = false; w.green = false; w.sampleIdx = 0u;
-        w.color = mk3(0.0f);
-        w.env.valid = 0u; w.light.valid = 0u;
-        w.env.dir = mk3(0.0f); w.light.dir = mk3(0.0f); w.neeOrigin = mk3(0.0f);
-        w.env.contribution = mk3(0.0f); w.light.contribution = mk3(0.0f); w.pendThroughput = mk3(0.0f);
-        // the NEE rays of the bounce go to the record as soon as they are final: their 15 registers are free while the BSDF is sampled
-        struct Sink {
-            uint32_t (*rec)[256]; uint32_t i;
-            PT_DEV void operator()(PathRegs& q) const {
-                rec[16][i] = pt_asuint(q.neeOrigin.x); rec[17][i] = pt_asuint(q.neeOrigin.y); rec[18][i] = pt_asuint(q.neeOrigin.z);
-                rec[19][i] = pt_asuint(q.env.dir.x); rec[20][i] = pt_asuint(q.env.dir.y); rec[21][i] = pt_asuint(q.env.dir.z);
-                rec[22][i] = pt_asuint(q.light.dir.x); rec[23][i] = pt_asuint(q.light.dir.y); rec[24][i] = pt_asuint(q.light.dir.z);
-                rec[25][i] = pt_asuint(q.env.contribution.x); rec[26][i] = pt_asuint(q.env.contribution.y); rec[27][i] = pt_asuint(q.env.contribution.z);
-                rec[28][i] = pt_asuint(q.light.contribution.x); rec[29][i] = pt_asuint(q.light.contribution.y); rec[30][i] = pt_asuint(q.light.contribution.z);
-            }
-        };
-        path_shade_hit<STATS, Sink>(S, P, w, ch, cn, Sink{s_rec, tid});
-        putf(0, tid, w.ro.x); putf(1, tid, w.ro.y); putf(2, tid, w.ro.z);
-        putf(3, tid, w.rd.x); putf(4, tid, w.rd.y); putf(5, tid, w.rd.z);
-        put(6, tid, w.rng);
-        put(7, tid, (w.state & 3u) | ((w.hasPending ? 1u : 0u) << 2) | ((w.env.valid & 3u) << 3) | ((w.light.valid & 1u) << 5) | ((w.green ? 1u : 0u) << 6) | ((w.depth & 0x1FFFu) << 19));
-        putf(8, tid, w.scatterPdf); putf(9, tid, w.maxRoughness);
-        putf(10, tid, w.throughput.x); putf(11, tid, w.throughput.y); putf(12, tid, w.throughput.z);
-        putf(13, tid, w.radiance.x); putf(14, tid, w.radiance.y); putf(15, tid, w.radiance.z);
-    }
-    __syncthreads();
-
-    // ---- stage 3 at home: results of stage 2 (if any), end of the sample, coalesced stores
-    bool alive = false;
-    if (live) {
-        uint32_t px, py, pass;
-        pt_slot_to_pixel(tm, pixel_slot_of(B, slot, pass), px, py);
-        const uint32_t dest = (key >> 2) & 0xFFFFu;
-        PathRegs r;
-        r.sampleIdx = (f >> 7) & 0xFFFu;
-        r.color = xyz(B.color[slot]);
-        r.env.dir = mk3(0.0f); r.light.dir = mk3(0.0f); r.neeOrigin = mk3(0.0f);
-        r.env.contribution = mk3(0.0f); r.light.contribution = mk3(0.0f); r.pendThroughput = mk3(0.0f);
-        r.env.valid = 0u; r.light.valid = 0u;
-        bool writeNee = false;
-        if (dest != 0xFFFFu) {
-            const uint32_t m = get(7, dest);
-            r.state = m & 3u; r.hasPending = (m >> 2) & 1u; r.env.valid = (m >> 3) & 3u; r.light.valid = (m >> 5) & 1u; r.green = (m >> 6) & 1u;
-            r.depth = m >> 19;
-            r.ro = mk3(getf(0, dest), getf(1, dest), getf(2, dest));
-            r.rd = mk3(getf(3, dest), getf(4, dest), getf(5, dest));
-            r.rng = get(6, dest);
-            r.scatterPdf = getf(8, dest); r.maxRoughness = getf(9, dest);
-            r.throughput = mk3(getf(10, dest), getf(11, dest), getf(12, dest));
-            r.radiance = mk3(getf(13, dest), getf(14, dest), getf(15, dest));
-            if (r.hasPending) {
-                writeNee = true;
-                r.neeOrigin = mk3(getf(16, dest), getf(17, dest), getf(18, dest));
-                r.env.dir = mk3(getf(19, dest), getf(20, dest), getf(21, dest));
-                r.light.dir = mk3(getf(22, dest), getf(23, dest), getf(24, dest));
-                r.env.contribution = mk3(getf(25, dest), getf(26, dest), getf(27, dest));
-                r.light.contribution = mk3(getf(28, dest), getf(29, dest), getf(30, dest));
-                r.pendThroughput = mk3(pt_asfloat(s_home[0][tid]), pt_asfloat(s_home[1][tid]), pt_asfloat(s_home[2][tid]));
-            }
-        } else {
-            // no closest hit to shade: the path was waiting for its last NEE (state ENDING)
-            r.state = fl_state(f); r.hasPending = false; r.green = false;
-            r.depth = f >> 19;
-            r.radiance = mk3(pt_asfloat(s_home[0][tid]), pt_asfloat(s_home[1][tid]), pt_asfloat(s_home[2][tid]));
-            r.rng = s_home[3][tid];
-            const float4 qro = B.ray[0][2u * slot], qrd = B.ray[0][2u * slot + 1u], qthr = B.thr[slot];
-            r.ro = xyz(qro); r.scatterPdf = qro.w;
-            r.rd = xyz(qrd); r.maxRoughness = qrd.w;
-            r.throughput = xyz(qthr);
-        }
-        path_end_sample<false>(P, r, px, py, py * P.OutputWidth + px, nullptr, nullptr, cn);
-        store_path(B, slot, r, writeNee);
-        alive = r.state != PS_DONE;
-    }
-    {
-        const uint32_t nAlive = (uint32_t)__popcll(__ballot(alive));
-        if (B.tailCut != 0u && nAlive && lane == 0u)
-            atomicAdd(&B.aliveFlags[iteration * PT_WF_ALIVE_SHARDS + (blockIdx.x & (PT_WF_ALIVE_SHARDS - 1u))], nAlive);
-    }
-    flush_counters<STATS>(cn, B.statRows, blockIdx.x * 4u + wave, lane);
-}
-
-// ------------------------------------------------------------------------------------------
-// shade, split into three launches (round 3, PTWfBuffers.shadeSorted == 2): the regrouping of pt_wf_shade_sorted without its
-// parked waves.  pre: every slot's HOME lane adds the pending NEE (stage 1), and a slot with a closest hit to shade gets a RECORD:
-// rank within the workgroup by ballot + one atomic per workgroup and class for the base (surface hits fill the record array
-// from the front, misses from the back), inputs written as five coalesced float4 planes.  hit: one lane per record, one wave per
-// workgroup -- full waves of surface hits, full waves of misses, nothing idle -- runs path_shade_hit() and writes nine planes of
-// results.  post: the home lanes pick the results up (rank order = slot order inside a workgroup: near-contiguous reads), finish the
-// sample (stage 3) and store the state coalesced.  Which record a slot gets depends on timing; what is computed for it does not.
-// ------------------------------------------------------------------------------------------
-#define PT_SP_PLANES 10u        // float4 planes of the record array (PTWfBuffers.recPlanes, stride numSlots)
-PT_DEV float4* rec_plane(const PTWfBuffers& B, uint32_t k) { return B.recPlanes + (size_t)k * B.numSlots; }
-
-__global__ __launch_bounds__(256) void pt_wf_shade_pre(DScene S, PTWfBuffers B, uint32_t iteration)
-{
-    __shared__ uint32_t s_cnt[2][4];
-    __shared__ uint32_t s_base[2];
-    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
-    const uint32_t slot = blockIdx.x * 256u + tid;
-    if (blockIdx.x == 0u && tid < PT_WF_SHARDS) B.chunkHeads[tid * 32u] = 0u;   // for the next trace launch (schedule 3)
-    if (tail_cut(B, iteration)) return;
-    const uint32_t f = B.flags[slot];
-    const bool live = fl_state(f) != PS_DONE;
-    uint32_t key = 2u;
-    uint32_t rng = 0u;
-    float4 qro = make_float4(0, 0, 0, 0), qrd = qro, qrad = qro, qthr = qro, qhit = qro, qhit2 = qro;
-    if (live) {
-        const bool pending = fl_pending(f);
-        qrad = B.rad[slot];
-        qhit = B.hit[slot];
-        if (pending) {
-            const float4 qenvC = B.envC[slot], qlightC = B.lightC[slot], qpthr = B.pthr[slot];
-            const uint32_t o0 = B.occl[slot], o1 = B.occl[(size_t)B.numSlots + slot];
-            PathRegs r;
-            r.hasPending = true;
-            r.env.valid = fl_env(f); r.light.valid = fl_light(f);
-            r.green = (f >> 6) & 1u;
-            r.radiance = xyz(qrad);
-            r.env.contribution = xyz(qenvC); r.light.contribution = xyz(qlightC); r.pendThroughput = xyz(qpthr);
-            path_apply_pending(r, o0 != 0u, o1 != 0u);
-            qrad = f4(r.radiance, 0.0f);
-            B.rad[slot] = qrad;                                       // stage 3 (and a slot that skips stage 2) reads it back
-        }
-        if (fl_state(f) == PS_TRACE) {
-            key = qhit.x < PT_FAR_PLANE ? 0u : 1u;
-            rng = B.rng[slot];
-            qro = B.ray[0][2u * slot]; qrd = B.ray[0][2u * slot + 1u]; qthr = B.thr[slot];
-            if (S.hasTlas) qhit2 = B.hit2[slot];
-        }
-    }
-    const unsigned long long m0 = __ballot(key == 0u), m1 = __ballot(key == 1u);
-    if (lane == 0u) { s_cnt[0][wave] = (uint32_t)__popcll(m0); s_cnt[1][wave] = (uint32_t)__popcll(m1); }
-    __syncthreads();
-    uint32_t base0 = 0u, base1 = 0u, total0 = 0u, total1 = 0u;
-#pragma unroll
-    for (uint32_t w = 0; w < 4u; ++w) {
-        const uint32_t c0 = s_cnt[0][w], c1 = s_cnt[1][w];
-        if (w < wave) { base0 += c0; base1 += c1; }
-        total0 += c0; total1 += c1;
-    }
-    if (tid == 0u) {
-        s_base[0] = total0 ? atomicAdd(&B.recCount[0], total0) : 0u;
-        s_base[1] = total1 ? atomicAdd(&B.recCount[1], total1) : 0u;
-    }
-    __syncthreads();
-    uint32_t dest = 0xFFFFFFFFu;
-    if (key == 0u) dest = s_base[0] + base0 + rank_below(m0);
-    else if (key == 1u) dest = B.numSlots - 1u - (s_base[1] + base1 + rank_below(m1));      // misses fill the array from the back
-    if (live) B.recDest[slot] = dest;
-    if (dest != 0xFFFFFFFFu) {
-        rec_plane(B, 0)[dest] = qro;                                  // origin, scatterPdf
-        rec_plane(B, 1)[dest] = qrd;                                  // direction, maxRoughness
-        rec_plane(B, 2)[dest] = make_float4(qthr.x, qthr.y, qthr.z, pt_asfloat(rng));
-        rec_plane(B, 3)[dest] = make_float4(qrad.x, qrad.y, qrad.z, pt_asfloat(f >> 19));     // radiance, depth
-        rec_plane(B, 4)[dest] = qhit;
-        if (S.hasTlas) rec_plane(B, 5)[dest] = qhit2;
-        B.pthr[slot] = qthr;                                          // the throughput the NEE of this bounce applies to (if it produces one)
-    }
-}
-
-template <bool STATS>
-__global__ __launch_bounds__(64, PT_WF_SHADE_MIN_WAVES) void pt_wf_shade_hit(DScene S, PTFrameParams P, PTWfBuffers B, uint32_t iteration)
-{
-    if (tail_cut(B, iteration)) return;
-    const uint32_t idx = blockIdx.x * 64u + threadIdx.x;
-    const uint32_t c0 = B.recCount[0], c1 = B.recCount[1];
-    const bool mine = idx < c0 || idx >= B.numSlots - c1;
-    Counters cn = {};
-    if (mine) {
-        const float4 p0 = rec_plane(B, 0)[idx], p1 = rec_plane(B, 1)[idx], p2 = rec_plane(B, 2)[idx], p3 = rec_plane(B, 3)[idx], p4 = rec_plane(B, 4)[idx];
-        PathRegs w;
-        w.ro = xyz(p0); w.scatterPdf = p0.w;
-        w.rd = xyz(p1); w.maxRoughness = p1.w;
-        w.throughput = xyz(p2); w.rng = pt_asuint(p2.w);
-        w.radiance = xyz(p3); w.depth = pt_asuint(p3.w);
-        HitRecord ch;
-        ch.h.t = p4.x; ch.h.u = p4.y; ch.h.v = p4.z; ch.h.triIndex = pt_asuint(p4.w);
-        ch.pos = mk3(0.0f); ch.inst = 0u;
-        if (S.hasTlas) { const float4 p5 = rec_plane(B, 5)[idx]; ch.pos = xyz(p5); ch.inst = pt_asuint(p5.w); }
-        w.state = PS_TRACE; w.hasPending = false; w.green = false; w.sampleIdx = 0u;
-        w.color = mk3(0.0f);
-        w.env.valid = 0u; w.light.valid = 0u;
-        w.env.dir = mk3(0.0f); w.light.dir = mk3(0.0f); w.neeOrigin = mk3(0.0f);
-        w.env.contribution = mk3(0.0f); w.light.contribution = mk3(0.0f); w.pendThroughput = mk3(0.0f);
-        struct Sink {                                                // the NEE rays of the bounce leave for their planes as soon as they are final
-            const PTWfBuffers& B; uint32_t i;
-            PT_DEV void operator()(PathRegs& q) const {
-                uint32_t j = i;
-                asm volatile("" : "+v"(j));
-                rec_plane(B, 5)[j] = f4(q.neeOrigin, 0.0f);
-                rec_plane(B, 6)[j] = f4(q.env.dir, 0.0f);
-                rec_plane(B, 7)[j] = f4(q.light.dir, 0.0f);
-                rec_plane(B, 8)[j] = f4(q.env.contribution, 0.0f);
-                rec_plane(B, 9)[j] = f4(q.light.contribution, 0.0f);
-            }
-        };
-        path_shade_hit<STATS, Sink>(S, P, w, ch, cn, Sink{B, idx});
-        uint32_t j = idx;
-        asm volatile("" : "+v"(j));
-        rec_plane(B, 0)[j] = f4(w.ro, w.scatterPdf);
-        rec_plane(B, 1)[j] = f4(w.rd, w.maxRoughness);
-        rec_plane(B, 2)[j] = make_float4(w.throughput.x, w.throughput.y, w.throughput.z, pt_asfloat(w.rng));
-        rec_plane(B, 3)[j] = make_float4(w.radiance.x, w.radiance.y, w.radiance.z,
-                                         pt_asfloat((w.state & 3u) | ((w.hasPending ? 1u : 0u) << 2) | ((w.env.valid & 3u) << 3) | ((w.light.valid & 1u) << 5) |
-                                                    ((w.green ? 1u : 0u) << 6) | ((w.depth & 0x1FFFu) << 19)));
-    }
-    flush_counters<STATS>(cn, B.statRows, blockIdx.x, threadIdx.x);
-}
-
-template <bool STATS>
-__global__ __launch_bounds__(256) void pt_wf_shade_post(PTFrameParams P, PTTileMap tm, PTWfBuffers B, uint32_t iteration)
-{
-    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
-    const uint32_t slot = blockIdx.x * 256u + tid;
-    if (blockIdx.x == 0u && tid < 2u) B.recCount[tid] = 0u;           // for the next iteration's pre launch (this launch does not read them)
-    if (tail_cut(B, iteration)) return;
-    Counters cn = {};
-    const uint32_t f = B.flags[slot];
-    bool alive = false;
-    if (fl_state(f) != PS_DONE) {
-        uint32_t px, py, pass;
-        pt_slot_to_pixel(tm, pixel_slot_of(B, slot, pass), px, py);
-        const uint32_t dest = B.recDest[slot];
-        PathRegs r;
-        r.sampleIdx = (f >> 7) & 0xFFFu;
-        r.color = xyz(B.color[slot]);
-        r.env.dir = mk3(0.0f); r.light.dir = mk3(0.0f); r.neeOrigin = mk3(0.0f);
-        r.env.contribution = mk3(0.0f); r.light.contribution = mk3(0.0f); r.pendThroughput = mk3(0.0f);
-        r.env.valid = 0u; r.light.valid = 0u;
-        bool writeNee = false;
-        if (dest != 0xFFFFFFFFu) {
-            const float4 q0 = rec_plane(B, 0)[dest], q1 = rec_plane(B, 1)[dest], q2 = rec_plane(B, 2)[dest], q3 = rec_plane(B, 3)[dest];
-            const uint32_t m = pt_asuint(q3.w);
-            r.state = m & 3u; r.hasPending = (m >> 2) & 1u; r.env.valid = (m >> 3) & 3u; r.light.valid = (m >> 5) & 1u; r.green = (m >> 6) & 1u;
-            r.depth = m >> 19;
-            r.ro = xyz(q0); r.scatterPdf = q0.w;
-            r.rd = xyz(q1); r.maxRoughness = q1.w;
-            r.throughput = xyz(q2); r.rng = pt_asuint(q2.w);
-            r.radiance = xyz(q3);
-            if (r.hasPending) {
-                writeNee = true;
-                r.neeOrigin = xyz(rec_plane(B, 5)[dest]);
-                r.env.dir = xyz(rec_plane(B, 6)[dest]);
-                r.light.dir = xyz(rec_plane(B, 7)[dest]);
-                r.env.contribution = xyz(rec_plane(B, 8)[dest]);
-                r.light.contribution = xyz(rec_plane(B, 9)[dest]);
-                r.pendThroughput = xyz(B.pthr[slot]);
-            }
-        } else {
-            // no closest hit to shade: the path was waiting for its last NEE (state ENDING, radiance updated by the pre launch)
-            r.state = fl_state(f); r.hasPending = false; r.green = false;
-            r.depth = f >> 19;
-            r.radiance = xyz(B.rad[slot]);
-            r.rng = B.rng[slot];
-            const float4 qro = B.ray[0][2u * slot], qrd = B.ray[0][2u * slot + 1u], qthr = B.thr[slot];
-            r.ro = xyz(qro); r.scatterPdf = qro.w;
-            r.rd = xyz(qrd); r.maxRoughness = qrd.w;
-            r.throughput = xyz(qthr);
-        }
-        path_end_sample<false>(P, r, px, py, py * P.OutputWidth + px, nullptr, nullptr, cn);
-        store_path(B, slot, r, writeNee);
-        alive = r.state != PS_DONE;
-    }
-    {
-        const uint32_t nAlive = (uint32_t)__popcll(__ballot(alive));
-        if (B.tailCut != 0u && nAlive && lane == 0u)
-            atomicAdd(&B.aliveFlags[iteration * PT_WF_ALIVE_SHARDS + (blockIdx.x & (PT_WF_ALIVE_SHARDS - 1u))], nAlive);
-    }
-    flush_counters<STATS>(cn, B.statRows, blockIdx.x * 4u + wave, lane);
 }
 
 // cleanup: pixels still alive after the fixed number of iterations are run to completion here, one lane per slot with
@@ -1971,8 +1412,6 @@ hipError_t pt_launch_wavefront(const DScene& S, const PTFrameParams& P, const PT
         if (launchesOut) *launchesOut = 3u;
         return hipGetLastError();
     }
-    if ((e = hipMemsetAsync(B.aliveFlags, 0, sizeof(uint32_t) * B.maxIterations * PT_WF_ALIVE_SHARDS, stream)) != hipSuccess) return e;
-    if (B.shadeSorted == 2u && (e = hipMemsetAsync(B.recCount, 0, 2 * sizeof(uint32_t), stream)) != hipSuccess) return e;
     hipLaunchKernelGGL(pt_wf_init, dim3(nb), dim3(256), 0, stream, P, batch, tm, B);
     launches++;
     const uint32_t spp = P.SamplesPerPass > 1 ? (uint32_t)P.SamplesPerPass : 1u;
@@ -2025,23 +1464,8 @@ hipError_t pt_launch_wavefront(const DScene& S, const PTFrameParams& P, const PT
             if (fullStats) hipLaunchKernelGGL((pt_wf_trace<true, false>), dim3(nb * 3u), dim3(256), 0, stream, S, B, it);
             else hipLaunchKernelGGL((pt_wf_trace<false, false>), dim3(nb * 3u), dim3(256), 0, stream, S, B, it);
         }
-        if (B.shadeSorted == 2u) {
-            hipLaunchKernelGGL(pt_wf_shade_pre, dim3(nb), dim3(256), 0, stream, S, B, it);
-            if (fullStats) {
-                hipLaunchKernelGGL(pt_wf_shade_hit<true>, dim3(B.numSlots / 64u), dim3(64), 0, stream, S, P, B, it);
-                hipLaunchKernelGGL(pt_wf_shade_post<true>, dim3(nb), dim3(256), 0, stream, P, tm, B, it);
-            } else {
-                hipLaunchKernelGGL(pt_wf_shade_hit<false>, dim3(B.numSlots / 64u), dim3(64), 0, stream, S, P, B, it);
-                hipLaunchKernelGGL(pt_wf_shade_post<false>, dim3(nb), dim3(256), 0, stream, P, tm, B, it);
-            }
-            launches += 2;
-        } else if (B.shadeSorted) {
-            if (fullStats) hipLaunchKernelGGL(pt_wf_shade_sorted<true>, dim3(nb), dim3(256), 0, stream, S, P, tm, B, it);
-            else hipLaunchKernelGGL(pt_wf_shade_sorted<false>, dim3(nb), dim3(256), 0, stream, S, P, tm, B, it);
-        } else {
-            if (fullStats) hipLaunchKernelGGL(pt_wf_shade<true>, dim3(B.numSlots / PT_WF_SHADE_BLOCK), dim3(PT_WF_SHADE_BLOCK), 0, stream, S, P, tm, B, it);
-            else hipLaunchKernelGGL(pt_wf_shade<false>, dim3(B.numSlots / PT_WF_SHADE_BLOCK), dim3(PT_WF_SHADE_BLOCK), 0, stream, S, P, tm, B, it);
-        }
+        if (fullStats) hipLaunchKernelGGL(pt_wf_shade<true>, dim3(B.numSlots / PT_WF_SHADE_BLOCK), dim3(PT_WF_SHADE_BLOCK), 0, stream, S, P, tm, B, it);
+        else hipLaunchKernelGGL(pt_wf_shade<false>, dim3(B.numSlots / PT_WF_SHADE_BLOCK), dim3(PT_WF_SHADE_BLOCK), 0, stream, S, P, tm, B, it);
         launches += 2;
     }
     const uint32_t cleanupBlocks = nb < 1024u ? nb : 1024u;          // 256 CUs x 4 workgroups; each strides over the slot blocks
