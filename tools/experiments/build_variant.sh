@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: tools/experiments/build_variant.sh NAME "-DPT_WF_TRI_PARK=8u ..."   -> tools/experiments/variants/NAME.so
-# Rebuilds only the translation units the -D flags can change (pt_wavefront.hip, pt_kernels.hip) and links them with the
-# default objects; tools/experiments/variants.py then benches every variant through PT_PLUGIN.
+# Rebuilds only the translation units the -D flags can change (pt_wavefront.hip, pt_kernels.hip, and the host API files
+# pt_api_*.hip, which see -DPT_WF_SETS= through pt_context.h) and links them with the default objects; tools/experiments/variants.py then benches every variant through PT_PLUGIN.
 set -e
 NAME=$1; shift
 DEFS="$*"
@@ -15,7 +15,7 @@ STRAT="-mllvm -amdgpu-sched-strategy=${STRATEGY:-max-memory-clause}"
 [ "$STRATEGY" = "none" ] && STRAT=""
 FLAGS="-O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-slp-vectorize -fvisibility=hidden -I../../include -Wno-unused-function -Wno-unused-value $STRAT ${BASE_EXTRA--mllvm -amdgpu-use-amdgpu-trackers=1} $EXTRA_FLAGS"
 OUT=../../tools/experiments/variants/_obj_$NAME
-for f in pt_kernels pt_api; do
+for f in pt_kernels $(basename -s .hip pt_api_*.hip); do
   hipcc --offload-arch=gfx950 $FLAGS $DEFS -c $f.hip -o $OUT/$f.o &
 done
 hipcc --offload-arch=gfx950 $FLAGS $DEFS -DPT_WF_TU_B -c pt_wavefront.hip -o $OUT/pt_wavefront.o &

@@ -1,0 +1,265 @@
+// pt_api_render.hip — passes, batches, the ping-pong frames, presentation and readback (include/ptmi_plugin.h Part 2).
+#include "pt_context.h"
+
+namespace {
+
+int ensure_frames(PTContext* c, uint32_t w, uint32_t h)
+{
+    if (c->frames.w == w && c->frames.h == h) return PT_OK;
+    int rc = c->frames.resize(w, h, {sizeof(float4), sizeof(float4)}, nullptr);    // no drain of ours: freeing device memory waits for the device
+    if (rc) return rc;
+    for (int i = 0; i < 2; i++) HIP_TRY(hipMemsetAsync(c->frames.f4(i), 0, c->frames.buf[i].used, c->stream));
+    c->cur = 0;                         // PrepareRenderTexture re-created the targets -> Reset() (PathTracer.cs:211-215)
+    return PT_OK;
+}
+
+// one arena for all slot-indexed arrays of a wavefront state set (pt_wf_arena_bytes / pt_wf_arena_carve, pt_wavefront.hip);
+// re-carved when the slot count changes
+int ensure_wavefront(PTContext* c, PTContext::WfSet& set, uint32_t numSlots, uint32_t maxIterations)
+{
+    int rc;
+    if ((rc = create(set.stream)) || (rc = create(set.callEv)) || (rc = create(set.done))) return rc;
+    const bool needTlas = c->scene.hasTlas != 0u;
+    if (set.wf.flags && set.wf.numSlots == numSlots && set.wf.maxIterations >= maxIterations && (!needTlas || set.wf.tlasSpill)) return PT_OK;
+    if (c->residentWaves == 0u) {
+        hipDeviceProp_t prop;
+        HIP_TRY(hipGetDeviceProperties(&prop, c->device));
+        c->residentWaves = (uint32_t)prop.multiProcessorCount * 4u * 8u;
+    }
+    // The arena only ever grows: a different slot count (another batch size, another frame size) that fits is a new carving of
+    // the same memory -- launches already enqueued on the set's stream keep the pointers they were given and finish first
+    // (stream order), so neither a synchronisation nor an allocation lands in a caller's timed region.
+    if ((rc = set.arena.reserve(pt_wf_arena_bytes(numSlots, c->residentWaves, needTlas, maxIterations), set.stream))) {
+        set.wf = PTWfBuffers{};
+        return rc;
+    }
+    set.wf = pt_wf_arena_carve(set.arena.ptr, numSlots, c->residentWaves, needTlas, maxIterations);
+    HIP_TRY(hipMemsetAsync(set.wf.statRows, 0, (size_t)set.wf.numStatRows * 16 * 8, set.stream));
+    return PT_OK;
+}
+
+// p: imported and validated (import_frame_params).
+// `batch`: the passes a launch sequence renders together (count >= 1; batch.seedRoot[0] / currentSample[0] = those of p)
+int render_to(PTContext* c, const PTFrameParams& params, float4* dOut, const float4* dAcc, const PTBatch* hostBatch = nullptr)
+{
+    RoctxRange range("PT pass (enqueue)");
+    const PTFrameParams* p = &params;
+    int rc;
+    PTBatch batch = {};
+    if (hostBatch) batch = *hostBatch;
+    else { batch.count = 1u; batch.seedRoot[0] = p->RngSeedRoot; batch.currentSample[0] = p->CurrentSample; }
+    if (!c->hasScene) return fail(PT_ERR_NO_SCENE, "PTSetScene has not been called");
+    if (!dOut) return fail(PT_ERR_INVALID_ARG, "output buffer == NULL");
+    if (p->CurrentSample > 0 && !dAcc) return fail(PT_ERR_INVALID_ARG, "CurrentSample > 0 needs an accumulated frame");
+    HIP_TRY(hipSetDevice(c->device));
+
+    const PTTileMap tm = pt_make_tile_map(*p, c->rank, c->world);
+
+    EventPair ep;
+    if (c->profiling) {
+        if (c->pending.size() >= 4096) { rc = drain_events(c); if (rc) return rc; }
+        if (!c->freeEvents.empty()) { ep = std::move(c->freeEvents.back()); c->freeEvents.pop_back(); }
+        else if ((rc = create(ep.start, hipEventDefault)) || (rc = create(ep.stop, hipEventDefault))) return rc;
+    }
+    uint32_t launches = 0;
+    const int schedule = effective_schedule(c);
+    switch (schedule) {
+    case 1:
+    case 2:
+    case 3:
+    case 4: {
+        const uint32_t spp = p->SamplesPerPass > 1 ? (uint32_t)p->SamplesPerPass : 1u;
+        const uint32_t bounces = p->MaxRayBounces > 1u ? p->MaxRayBounces : 1u;
+        if (spp > 4095u || bounces > 8191u) return fail(PT_ERR_UNSUPPORTED, "wavefront schedules pack SamplesPerPass <= 4095 and MaxRayBounces <= 8191");
+        const uint64_t maxIt = (uint64_t)spp * (bounces + 2u) + 4u;
+        // A pass may be cut into SUB-FRAMES (PTSetSubFrames): interleaved subsets of the context's 16x16 blocks, each with its own
+        // launch sequence on its own state set and stream, all writing the same output frame.  To the kernels a sub-frame is
+        // tile ownership (rank + world * j of world * S); to the machine it is what a second pass in flight is -- other kernels to
+        // fill the ramp-up and drain of every launch -- without the host having to run ahead of the frame it shows.
+        uint32_t S = c->subFrames < 1u ? 1u : c->subFrames;
+        if (S > c->numSets) S = c->numSets;
+        const bool zeroOnce = c->world > 1 && S > 1u;
+        if (zeroOnce) HIP_TRY(hipMemsetAsync(dOut, 0, (size_t)p->OutputWidth * p->OutputHeight * sizeof(float4), c->stream));
+        for (uint32_t j = 0; j < S; ++j) {
+            const PTTileMap tmj = S == 1u ? tm : pt_make_tile_map(*p, c->rank + c->world * (int)j, c->world * (int)S);
+            if (c->nextSet >= c->numSets) c->nextSet = 0u;
+            PTContext::WfSet& set = c->sets[c->nextSet];
+            c->nextSet = (c->nextSet + 1u) % c->numSets;
+            // every set IN USE is carved on the FIRST pass of a frame size (a no-op afterwards): a caller that times passes after a
+            // short warm-up must not find the allocation of sets it has not reached yet inside its timed region.  Sets beyond
+            // PTSetPassesInFlight are never allocated (0.6 GB each at 1080p).
+            const uint32_t slotsPerPass = pt_num_slots(tmj);
+            if ((uint64_t)slotsPerPass * batch.count > 0x3FFFFFFFull) return fail(PT_ERR_UNSUPPORTED, "batch too large: passes x owned pixels exceeds 2^30 slots");
+            if (j == 0u)
+                for (uint32_t k = 0; k < c->numSets; ++k) {
+                    if ((rc = ensure_wavefront(c, c->sets[k], slotsPerPass * batch.count, (uint32_t)(maxIt > 65536u ? 65536u : maxIt)))) return rc;
+                    c->sets[k].wf.slotsPerPass = slotsPerPass;
+                }
+            // the launch chain runs on the set's own stream; only its resolve (which reads `accumulated` and writes `output`)
+            // is ordered after what the caller has enqueued on the context stream so far, the previous pass included
+            HIP_TRY(hipEventRecord(set.callEv, c->stream));
+            if (c->update.pending) HIP_TRY(hipStreamWaitEvent(set.stream, c->update.done, 0));     // the trace reads the scene before the resolve's wait
+            if (c->profiling && j == 0u) HIP_TRY(hipEventRecord(ep.start, set.stream));
+            uint32_t n = 0;
+            // the default schedule's kernels (refill trace + shade) come from the translation unit built without the post-RA scheduler,
+            // HAS_TLAS, the fused persistent kernel and the other schedules from the one built with it (csrc/Makefile)
+            const bool tuA = schedule == 1 && c->scene.hasTlas == 0u;
+            HIP_TRY((tuA ? pt_launch_wavefront : pt_launch_wavefront_b)(c->scene, *p, batch, dAcc, dOut, tmj, set.wf, (unsigned long long*)c->dStats.ptr, c->statsLevel > 0, set.stream, set.callEv,
+                                        c->world > 1 && !zeroOnce, &n, trace_variant(schedule), c->wfIterations));
+            launches += n;
+            if (c->profiling && j + 1u == S) HIP_TRY(hipEventRecord(ep.stop, set.stream));
+            HIP_TRY(hipEventRecord(set.done, set.stream));
+            HIP_TRY(hipStreamWaitEvent(c->stream, set.done, 0));          // consumers of the context stream see the finished frame
+        }
+        break;
+    }
+    case 0:
+    default:
+        if (batch.count != 1u) return fail(PT_ERR_UNSUPPORTED, "internal: the megakernel renders one pass per launch");
+        // pixels this context does not own must read as exact zeros (sum over ranks == single-GPU frame)
+        if (c->world > 1)
+            HIP_TRY(hipMemsetAsync(dOut, 0, (size_t)p->OutputWidth * p->OutputHeight * sizeof(float4), c->stream));
+        if (c->profiling) HIP_TRY(hipEventRecord(ep.start, c->stream));
+        HIP_TRY(pt_launch_megakernel(c->scene, *p, dAcc, dOut, tm, (unsigned long long*)c->dStats.ptr, c->statsLevel > 0, c->stream));
+        if (c->profiling) HIP_TRY(hipEventRecord(ep.stop, c->stream));
+        launches = 1;
+        break;
+    }
+    if (c->profiling) {
+        ep.launches = launches;
+        c->pending.push_back(std::move(ep));
+    }
+    return PT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+PT_API int PTRenderPass(PTContext* c, const PTFrameParams* hostParams)
+{
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx == NULL");
+    PTFrameParams p;
+    int rc = import_frame_params(hostParams, p);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = ensure_frames(c, p.OutputWidth, p.OutputHeight))) return rc;
+    return render_to(c, p, c->frames.f4(c->cur), c->frames.f4(1 - c->cur));
+}
+
+PT_API int PTFlipFrames(PTContext* c) { if (!c) return fail(PT_ERR_INVALID_ARG, "ctx == NULL"); c->cur = 1 - c->cur; return PT_OK; }
+PT_API int PTResetFrames(PTContext* c) { if (!c) return fail(PT_ERR_INVALID_ARG, "ctx == NULL"); c->cur = 0; return PT_OK; }
+
+PT_API int PTRenderPassTo(PTContext* c, const PTFrameParams* hostParams, void* dOutput, const void* dAccumulated)
+{
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx == NULL");
+    PTFrameParams p;
+    int rc = import_frame_params(hostParams, p);
+    if (rc) return rc;
+    return render_to(c, p, (float4*)dOutput, (const float4*)dAccumulated);
+}
+
+PT_API int PTRenderPassBatchTo(PTContext* c, const PTFrameParams* hostParams, int count, void* dOutput, const void* dAccumulated)
+{
+    if (!c || !hostParams) return fail(PT_ERR_INVALID_ARG, "ctx/params == NULL");
+    if (count < 1 || count > PT_MAX_BATCH) return fail(PT_ERR_INVALID_ARG, "count outside 1.." + std::to_string(PT_MAX_BATCH));
+    // the host's array has the stride of ITS header (structSize of the first element)
+    const uint32_t stride = hostParams->structSize;
+    if (stride < PT_FRAME_PARAMS_MIN_SIZE || stride > 4096u) return fail(PT_ERR_INVALID_ARG, "PTFrameParams.structSize is not set");
+    PTFrameParams first, other;
+    int rc = import_struct(hostParams, first, PT_FRAME_PARAMS_MIN_SIZE, "PTFrameParams", "params == NULL");
+    if (rc) return rc;
+    PTBatch batch = {};
+    batch.count = (uint32_t)count;
+    for (int j = 0; j < count; ++j) {
+        const PTFrameParams* hp = (const PTFrameParams*)((const char*)hostParams + (size_t)j * stride);
+        if (hp->structSize != stride) return fail(PT_ERR_INVALID_ARG, "every PTFrameParams of a batch must carry the same structSize");
+        if ((rc = import_struct(hp, other, PT_FRAME_PARAMS_MIN_SIZE, "PTFrameParams", "params == NULL"))) return rc;
+        batch.seedRoot[j] = other.RngSeedRoot;
+        batch.currentSample[j] = other.CurrentSample;
+        other.RngSeedRoot = first.RngSeedRoot;
+        other.CurrentSample = first.CurrentSample;
+        if (memcmp(&other, &first, sizeof(first)) != 0)
+            return fail(PT_ERR_INVALID_ARG, "the passes of a batch may differ in RngSeedRoot and CurrentSample only (pass " + std::to_string(j) + " differs elsewhere)");
+    }
+    if ((rc = validate_params(first))) return rc;
+    if (count == 1) return render_to(c, first, (float4*)dOutput, (const float4*)dAccumulated);
+    if (effective_schedule(c) == 0) {
+        // the megakernel writes pixels itself: run the passes one by one, ping-ponging between dOutput and a scratch frame so that the
+        // last pass lands in dOutput
+        HIP_TRY(hipSetDevice(c->device));
+        if ((rc = c->batchScratch.reserve((size_t)first.OutputWidth * first.OutputHeight * sizeof(float4), c->stream))) return rc;
+        const float4* acc = (const float4*)dAccumulated;
+        for (int j = 0; j < count; ++j) {
+            PTFrameParams pj = first;
+            pj.RngSeedRoot = batch.seedRoot[j];
+            pj.CurrentSample = batch.currentSample[j];
+            float4* out = ((count - 1 - j) & 1) ? (float4*)c->batchScratch.ptr : (float4*)dOutput;
+            if ((rc = render_to(c, pj, out, acc))) return rc;
+            acc = out;
+        }
+        return PT_OK;
+    }
+    return render_to(c, first, (float4*)dOutput, (const float4*)dAccumulated, &batch);
+}
+
+PT_API int PTRenderPassBatch(PTContext* c, const PTFrameParams* hostParams, int count)
+{
+    if (!c || !hostParams) return fail(PT_ERR_INVALID_ARG, "ctx/params == NULL");
+    PTFrameParams p;
+    int rc = import_frame_params(hostParams, p);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = ensure_frames(c, p.OutputWidth, p.OutputHeight))) return rc;
+    return PTRenderPassBatchTo(c, hostParams, count, c->frames.f4(c->cur), c->frames.f4(1 - c->cur));
+}
+
+PT_API int PTReadback(PTContext* c, float* dst, uint64_t dstFloats)
+{
+    if (!c || !dst) return fail(PT_ERR_INVALID_ARG, "ctx/dst == NULL");
+    if (!c->frames.w) return fail(PT_ERR_INVALID_ARG, "no frame rendered yet");
+    uint64_t need = (uint64_t)c->frames.w * c->frames.h * 4;
+    if (dstFloats < need) return fail(PT_ERR_INVALID_ARG, "destination too small");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(dst, c->frames.f4(c->cur), need * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+PT_API int PTPresent(PTContext* c, const PTPresentParams* q, const void* dSrc, void* dDst)
+{
+    if (!c || !q || !dDst) return fail(PT_ERR_INVALID_ARG, "ctx/params/dst == NULL");
+    if (q->OutputWidth == 0 || q->OutputHeight == 0 || (uint64_t)q->OutputWidth * q->OutputHeight > 0x7FFFFFFFull / 4)
+        return fail(PT_ERR_INVALID_ARG, "bad presentation size");
+    if (!dSrc) {
+        if (!c->frames.w) return fail(PT_ERR_INVALID_ARG, "no frame rendered yet");
+        if (q->OutputWidth != c->frames.w || q->OutputHeight != c->frames.h) return fail(PT_ERR_INVALID_ARG, "presentation size differs from the rendered frame");
+        dSrc = c->frames.f4(c->cur);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(pt_launch_present(*q, (const float4*)dSrc, (float4*)dDst, c->stream));
+    return PT_OK;
+}
+
+PT_API int PTPresentToHost(PTContext* c, const PTPresentParams* q, float* dst, uint64_t dstFloats)
+{
+    if (!c || !q || !dst) return fail(PT_ERR_INVALID_ARG, "ctx/params/dst == NULL");
+    const uint64_t need = (uint64_t)q->OutputWidth * q->OutputHeight * 4;
+    if (dstFloats < need) return fail(PT_ERR_INVALID_ARG, "destination too small");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = c->present.reserve(need * sizeof(float));      // every use of it ends in the synchronise below
+    if (rc) return rc;
+    if ((rc = PTPresent(c, q, nullptr, c->present.ptr))) return rc;
+    HIP_TRY(hipMemcpyAsync(dst, c->present.ptr, need * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+PT_API void* PTGetFramePointer(PTContext* c, int which)
+{
+    if (!c) return nullptr;
+    if (which < 0) return c->frames.f4(c->cur);
+    return which < 2 ? c->frames.f4(which) : nullptr;
+}
+
+} // extern "C"

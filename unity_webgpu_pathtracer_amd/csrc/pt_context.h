@@ -1,0 +1,238 @@
+// pt_context.h — internal to the pt_api_*.hip files (the PT* entry points of include/ptmi_plugin.h, one file per part of that
+// header): the context and the group, the types that own their HIP resources, and the error / import helpers every part uses.
+#pragma once
+#include "pt_launch.h"
+#include "pt_tlas.h"
+
+#include <cstring>
+#include <initializer_list>
+#include <string>
+#include <utility>
+#include <vector>
+
+extern thread_local std::string g_lastError;        // one for the whole library (pt_api_context.hip)
+
+inline int fail(int code, const std::string& msg)
+{
+    g_lastError = msg;
+    return code;
+}
+
+#define HIP_TRY(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t _e = (expr);                                                                    \
+        if (_e != hipSuccess)                                                                      \
+            return fail(PT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));            \
+    } while (0)
+
+// roctx ranges around every pass / scene upload (rocprofv3 --marker-trace shows them; the reference wraps its dispatch in
+// _cmd.BeginSample / EndSample("Path Tracer"), PathTracer.cs:226,252)
+struct RoctxRange {
+    explicit RoctxRange(const char* name);
+    ~RoctxRange();
+};
+
+// ---- owners: whatever a context or a group holds is released by its destructor; movable, not copyable ----
+template <class T, hipError_t (*Destroy)(T)>
+struct Owned {
+    T h = nullptr;
+    Owned() = default;
+    Owned(Owned&& o) noexcept : h(o.h) { o.h = nullptr; }
+    Owned& operator=(Owned&& o) noexcept { std::swap(h, o.h); return *this; }      // o's destructor releases what we held
+    ~Owned() { if (h) Destroy(h); }
+    operator T() const { return h; }
+};
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+// created on first use
+inline int create(Stream& s) { if (!s.h) HIP_TRY(hipStreamCreateWithFlags(&s.h, hipStreamNonBlocking)); return PT_OK; }
+inline int create(Event& e, unsigned flags = hipEventDisableTiming) { if (!e.h) HIP_TRY(hipEventCreateWithFlags(&e.h, flags)); return PT_OK; }
+
+// One device allocation (Pinned: one page-locked host allocation).
+template <bool Pinned>
+struct Buffer {
+    void* ptr = nullptr;
+    size_t bytes = 0;           // allocation capacity (a smaller request re-uses it)
+    size_t used = 0;            // bytes of the last request
+    Buffer() = default;
+    Buffer(Buffer&& o) noexcept : ptr(o.ptr), bytes(o.bytes), used(o.used) { o.ptr = nullptr; o.bytes = o.used = 0; }
+    Buffer& operator=(Buffer&& o) noexcept { std::swap(ptr, o.ptr); std::swap(bytes, o.bytes); std::swap(used, o.used); return *this; }
+    ~Buffer() { release(); }
+    void release()
+    {
+        if (ptr) (void)(Pinned ? hipHostFree(ptr) : hipFree(ptr));
+        ptr = nullptr;
+        bytes = used = 0;
+    }
+    // Keeps an allocation that is large enough.  Otherwise frees it and allocates `need` bytes; work that may still use the old
+    // memory must have finished by then: pass the stream it was enqueued on (drained here, only when there is something to free), or
+    // say at the call which synchronisation covers it.
+    int reserve(size_t need, hipStream_t drain = nullptr)
+    {
+        used = need;
+        if (need <= bytes) return PT_OK;
+        if (ptr && drain) HIP_TRY(hipStreamSynchronize(drain));
+        release();
+        HIP_TRY(Pinned ? hipHostMalloc(&ptr, need, hipHostMallocDefault) : hipMalloc(&ptr, need));
+        bytes = used = need;
+        return PT_OK;
+    }
+};
+using DeviceBuffer = Buffer<false>;
+using PinnedBuffer = Buffer<true>;
+
+// N per-pixel device buffers that are resized together: afterwards all N hold w x h elements, or the set is empty (w = h = 0).
+template <int N>
+struct FrameSet {
+    DeviceBuffer buf[N];
+    uint32_t w = 0, h = 0;
+    float4* f4(int k) const { return (float4*)buf[k].ptr; }
+    void clear()
+    {
+        for (DeviceBuffer& b : buf) b.release();
+        w = h = 0;
+    }
+    // elemBytes: bytes per pixel of each buffer; drain: as for Buffer::reserve
+    int resize(uint32_t W, uint32_t H, std::initializer_list<size_t> elemBytes, hipStream_t drain)
+    {
+        if (w == W && h == H) return PT_OK;
+        if (w && drain) HIP_TRY(hipStreamSynchronize(drain));
+        clear();
+        int k = 0;
+        for (size_t e : elemBytes)
+            if (int rc = buf[k++].reserve((size_t)W * H * e)) { clear(); return rc; }
+        w = W; h = H;
+        return PT_OK;
+    }
+};
+
+struct EventPair { Event start, stop; uint32_t launches = 0; };
+
+struct PTContext {
+    int device = 0;
+    Stream stream;
+    DeviceBuffer nodes, tris, attrs, materials, lights, lightConst, tex, tlas, tlasBfs, instances, instByLeaf, envTex, envCdf;
+    DeviceBuffer batchScratch;                  // PTRenderPassBatchTo under the megakernel: the frame the odd passes of a batch write
+    DeviceBuffer present;                       // PTPresentToHost staging frame
+    DScene scene = {};
+    bool hasScene = false;
+    FrameSet<2> frames;
+    int cur = 0;
+    int rank = 0, world = 1;
+    int statsLevel = 0;
+    int schedule = -1;                          // -1 auto (default), 0 megakernel, 1 wavefront + refill trace, 2, 3: see PTSetSchedule
+    DeviceBuffer dStats;                        // 16 counters, PTStats order
+    bool profiling = false;
+    std::vector<EventPair> pending;             // recorded, not yet read
+    std::vector<EventPair> freeEvents;
+    PTTimings timings = {};
+    // wavefront schedules: PT_WF_SETS path-state sets, each with its own stream, so consecutive passes overlap
+    struct WfSet {
+        PTWfBuffers wf = {};
+        DeviceBuffer arena;
+        Stream stream;
+        Event callEv, done;
+    } sets[PT_WF_SETS];
+    uint32_t nextSet = 0;
+    uint32_t residentWaves = 0;                 // CUs x 4 SIMDs x 8 waves (device property, read once)
+    uint32_t subFrames = 1;                     // launch chains a pass is cut into (PTSetSubFrames)
+    uint32_t numSets = 0;                       // passes in flight = state sets in use (PTSetPassesInFlight); carved on first use
+    uint32_t wfIterations = 0;                  // 0 = automatic
+    // ray queries (PTTraceRays): grid caps per query kernel (read once), the CWBVH stack slab sized for the largest, host staging
+    struct Query {
+        uint32_t caps[PT_QUERY_KERNELS] = {};
+        uint32_t capMax = 0;
+        DeviceBuffer slab;
+        DeviceBuffer rays, hits, surface;       // PTTraceRaysHost staging, grown on demand
+    } query;
+    // guides (PTRenderGuides): allocated on first use, regrown on a size change
+    struct Guide {
+        uint32_t caps[2] = {};
+        DeviceBuffer slab;
+        FrameSet<2> frames;                     // albedo + coverage, normal + depth
+    } guide;
+    // denoising (PTDenoise): likewise
+    struct Denoise {
+        FrameSet<3> state;                      // filter state ping-pong (e.rgb, v) x 2, then the float2 depth gradient
+        DeviceBuffer host;                      // PTDenoiseToHost staging frame
+    } denoise;
+    // scene updates (PTUpdateInstances / Lights / Materials): two generations of what an update rewrites, allocated on the first
+    // update of each kind and discarded by PTSetScene.  cur = -1 while PTSetScene's own buffers are current.
+    struct UpdGroup {
+        DeviceBuffer gen[2];
+        int cur = -1;
+        Event freeEv[2];                                // recorded on the context stream when the generation stops being current
+        bool freeRecorded[2] = {false, false};
+        PinnedBuffer staging[2];                        // pinned host copies of the host variants' arrays
+        Event stagedEv[2];
+        bool stagedRecorded[2] = {false, false};
+    };
+    struct Update {
+        UpdGroup inst, lights, mats;
+        Stream stream;
+        Event done;                                     // the last update's completion
+        Event input;                                    // PTUpdateInstancesDevice: the context stream up to the call
+        bool pending = false;                           // an update since PTSetScene: every pass waits for `done` first
+        DeviceBuffer tlasWork;
+        PTTlasWork tlasW = {};
+        uint32_t instanceCount = 0, sceneLightCount = 0, origTlasNodes = 0;
+        std::vector<uint32_t> validTextures;            // texture indices PTSetScene validated (sorted)
+    } update;
+};
+
+struct PTGroup {
+    struct Dev {
+        PTContext* ctx = nullptr;
+        DeviceBuffer packed;            // on device i: its owned tiles, dense
+        DeviceBuffer staged;            // on the root device: the same, after the peer copy (unused for the root: it unpacks `packed`)
+        Event arrived;                  // recorded on ctx->stream after the peer copy
+        Event unpacked;                 // recorded on the root's stream after the tiles were scattered into the assembled frame
+        bool unpackedValid = false;
+        float4* tiles() const { return (float4*)(staged.ptr ? staged.ptr : packed.ptr); }     // what the root unpacks
+    };
+    std::vector<Dev> dev;               // dev[0] is the root
+    FrameSet<1> assembled;
+};
+
+// "Versioning" (include/ptmi_plugin.h): copy min(structSize, sizeof) bytes of the host's struct into a zeroed one of ours
+template <class T>
+int import_struct(const T* in, T& out, size_t minSize, const char* typeName, const char* nullMsg)
+{
+    if (!in) return fail(PT_ERR_INVALID_ARG, nullMsg);
+    if (in->structSize < minSize || in->structSize > 4096u)
+        return fail(PT_ERR_INVALID_ARG, std::string(typeName) + ".structSize is not set (must be sizeof(" + typeName + ") of the host's header)");
+    memset(&out, 0, sizeof(out));
+    memcpy(&out, in, in->structSize < sizeof(out) ? in->structSize : sizeof(out));
+    out.structSize = (uint32_t)sizeof(out);
+    return PT_OK;
+}
+
+inline int validate_params(const PTFrameParams& p)
+{
+    if (p.OutputWidth == 0 || p.OutputHeight == 0) return fail(PT_ERR_INVALID_ARG, "OutputWidth/OutputHeight == 0");
+    if ((uint64_t)p.OutputWidth * p.OutputHeight > 0x7FFFFFFFull / 4) return fail(PT_ERR_INVALID_ARG, "frame too large");
+    return PT_OK;
+}
+
+// what opens every entry point that takes frame parameters
+inline int import_frame_params(const PTFrameParams* in, PTFrameParams& p)
+{
+    const int rc = import_struct(in, p, PT_FRAME_PARAMS_MIN_SIZE, "PTFrameParams", "params == NULL");
+    return rc ? rc : validate_params(p);
+}
+
+// auto (-1): scenes whose whole BVH is a handful of nodes (Cornell box: 1 node) have no traversal to speak of; the
+// wavefront's per-iteration path-state traffic then costs more than it buys (measured 8.7 vs 10.5 Grays/s)
+inline int effective_schedule(const PTContext* c)
+{
+    if (c->schedule >= 0) return c->schedule;
+    return (c->nodes.used <= 80u * 16u && !c->scene.hasTlas) ? 0 : 1;
+}
+// pt_launch_wavefront's traceVariant of a wavefront schedule: 1 -> 2 (refill), 2 -> 1 (one ray per lane), 3 -> 0 (persistent), 4 -> 4 (fused)
+inline int trace_variant(int schedule) { return schedule == 4 ? 4 : (schedule == 1 ? 2 : (schedule == 2 ? 1 : 0)); }
+
+// the material slots that name a texture: baseColor, metallicRoughness, emission, occlusion (normal map is unused)
+constexpr int kTextureSlots[4] = {22, 23, 25, 26};
+
+int set_scene(PTContext* c, const PTSceneDesc* hostScene, bool validate);      // pt_api_context.hip; PTGroupSetScene validates once
+int drain_events(PTContext* c);                                                 // pt_api_context.hip

@@ -1,4 +1,4 @@
-// pt_launch.h — host-visible launcher declarations shared by pt_kernels.hip and pt_api.hip.
+// pt_launch.h — host-visible launcher declarations shared by the kernel files and the host API (pt_context.h, pt_api_*.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "pt_device.h"
@@ -143,9 +143,15 @@ struct PTWfBuffers {
     uint32_t residentWaves;     // waves the device holds at the trace kernel's occupancy (CUs x 4 SIMDs x 8)
 };
 
+// The arena of a state set: every array of PTWfBuffers carved from one allocation of pt_wf_arena_bytes() bytes.  Both are defined
+// in pt_wavefront.hip, by the one of its two compilations that every library links (-DPT_WF_TU_B), so the layout is by
+// construction the one its kernels index.  needTlas: the scene is HAS_TLAS (tlasSpill); slotsPerPass is left to the caller.
+size_t pt_wf_arena_bytes(uint32_t numSlots, uint32_t residentWaves, bool needTlas, uint32_t maxIterations);
+PTWfBuffers pt_wf_arena_carve(void* base, uint32_t numSlots, uint32_t residentWaves, bool needTlas, uint32_t maxIterations);
+
 // Refill trace launches: 128 slots per wave while that still gives a quarter of the device's wave slots a wave (1080p: 16,320
 // waves for 8,192 slots, +2.4 %; half and quarter frames: +2 %), 64 for smaller launches.  Shared by the launcher and by the
-// arena sizing of pt_api.hip (a trace wave addresses 64 slab rows and PT_WF_SUSPEND records).
+// arena sizing (a trace wave addresses 64 slab rows and PT_WF_SUSPEND records).
 #ifndef PT_WF_WIDE_DIV
 #define PT_WF_WIDE_DIV 4u       // with 12 sets in flight: 1/4 of a 1080p frame 5.09 vs 5.21 ms, 1/8 equal either way
 #endif
@@ -176,21 +182,19 @@ __host__ __device__ inline void pt_batch_pick(const PTBatch& b, uint32_t j, uint
 }
 
 // pt_wavefront.hip is compiled twice with different scheduler flags (csrc/Makefile): the translation unit built with -DPT_WF_TU_B
-// exports the same launcher under the name pt_launch_wavefront_b
-#ifdef PT_WF_TU_B
-#define pt_launch_wavefront pt_launch_wavefront_b
-#endif
-hipError_t pt_launch_wavefront(const DScene& S, const PTFrameParams& P, const PTBatch& batch, const float4* accumulated, float4* output,
-                               const PTTileMap& tm, const PTWfBuffers& B, unsigned long long* gstats, bool fullStats,
-                               hipStream_t stream, hipEvent_t orderAfter, bool zeroOutputFirst,
-                               uint32_t* launchesOut, int traceVariant, uint32_t iterationsOverride);
+// defines the same launcher under the name pt_launch_wavefront_b
+typedef hipError_t PTWfLauncher(const DScene& S, const PTFrameParams& P, const PTBatch& batch, const float4* accumulated, float4* output,
+                                const PTTileMap& tm, const PTWfBuffers& B, unsigned long long* gstats, bool fullStats,
+                                hipStream_t stream, hipEvent_t orderAfter, bool zeroOutputFirst,
+                                uint32_t* launchesOut, int traceVariant, uint32_t iterationsOverride);
+PTWfLauncher pt_launch_wavefront, pt_launch_wavefront_b;
 #ifndef PT_WF_FUSED_GROUPS
 #define PT_WF_FUSED_GROUPS 2u   // schedule 4: groups of 64 path contexts a persistent wave owns (power of two <= 4: numSlots is a multiple of 256).
                                 // Sponza-class 1080p / 8 spp, one pass in flight: 1: 29.9 ms, 2: 25.2, 4: 27.9, 8: 31.4
 #endif
 #ifndef PT_WF_SUSPEND
 #define PT_WF_SUSPEND 16u       // refill trace kernel: a wave whose range is exhausted stops when this many rays or fewer are left, and leaves them
-                                // as records for the tail launch (pt_wavefront.hip); 0 = off.  Also the record slots per trace wave (pt_api.hip)
+                                // as records for the tail launch (pt_wavefront.hip); 0 = off.  Also the record slots per trace wave (pt_wf_arena_bytes)
 #endif
 #ifndef PT_WF_SETS
 #define PT_WF_SETS 12            // path-state sets = passes that can be in flight at once, each on its own stream (3 -> 6 sets with 8 hardware queues: +12 %;

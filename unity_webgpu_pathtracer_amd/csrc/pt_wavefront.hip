@@ -179,8 +179,9 @@ __global__ __launch_bounds__(256, 4) void pt_wf_trace(DScene S, PTWfBuffers B, u
 #define PT_WF_RANGE 128u        // largest slots-per-wave the launcher may pick (power of two): two 8x8 tiles x 3 kinds = 384 candidate rays.
                                 // Full 1080p frame, 64 / 128 / 256: 4,590 / 4,700 / 4,690 Mrays/s; small launches use 64 (pt_launch_wavefront)
 #endif
-static_assert(PT_WF_RANGE >= 64u && (PT_WF_RANGE & (PT_WF_RANGE - 1u)) == 0u,
-              "one counter row per trace wave: pt_api.hip sizes statRows for 4 x numSlots/64 rows; the main trace launch uses rows numSlots/64 + wave, the tail launch rows 2 x numSlots/64 + wave");
+#define PT_WF_STAT_ROW_SETS 4u   // statRows holds this many x numSlots/64 counter rows (pt_wf_arena_layout)
+static_assert(PT_WF_RANGE >= 64u && (PT_WF_RANGE & (PT_WF_RANGE - 1u)) == 0u && PT_WF_STAT_ROW_SETS >= 3u,
+              "one counter row per trace wave: the main trace launch uses rows numSlots/64 + wave, the tail launch rows 2 x numSlots/64 + wave");
 #ifndef PT_WF_REFILL
 #define PT_WF_REFILL 16u        // refill when at least this many lanes are idle
 #endif
@@ -236,7 +237,8 @@ PT_DEV bool ray_exists(uint32_t f, uint32_t kind)
 #endif
 #define PT_WF_SUSP_STACK_ROWS ((PT_WF_LDS_STACK + 1u) / 2u)       // two stack entries per uint4 row
 #define PT_WF_SUSP_ROWS (2u + PT_WF_SUSP_STACK_ROWS)             // uint4 rows per record (6 = 96 bytes with the default 8-entry LDS stack)
-static_assert(PT_WF_SUSP_ROWS <= 6u, "pt_api.hip sizes the record array for 6 rows per record");
+#define PT_WF_SUSP_RECORD_ROWS 6u                                // uint4 rows a record has room for (pt_wf_arena_layout)
+static_assert(PT_WF_SUSP_ROWS <= PT_WF_SUSP_RECORD_ROWS, "a suspended ray's record does not fit its slot of the record array");
 
 // A record holds the LDS part of the stack; a ray whose stack reaches into the HBM slab is not suspended (it is finished first).
 template <class ST>
@@ -1376,8 +1378,57 @@ __global__ __launch_bounds__(256) void pt_wf_fold_rows(unsigned long long* rows,
     }
 }
 
+// Walks the arena of a state set in carving order and returns its size; with a base, fills B with the pointers.
+size_t pt_wf_arena_layout(char* base, uint32_t numSlots, uint32_t residentWaves, bool needTlas, uint32_t maxIterations, PTWfBuffers& B)
+{
+    const size_t n = numSlots;
+    const uint32_t numRows = PT_WF_STAT_ROW_SETS * (numSlots >> 6);
+    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    // trace waves own 64 or 128 consecutive slots (pt_wf_wide_ranges); a wave addresses 64 slab rows and PT_WF_SUSPEND records.
+    // The HAS_TLAS refill kernel always uses PT_WF_RANGE = 128 slots per wave; the plain one 64 or 128.
+    const size_t traceWaves = pt_wf_max_trace_waves(numSlots, residentWaves);
+    const size_t spillBytes = traceWaves * 64u * (size_t)(needTlas ? PT_WF_SPILL_ROW_ENTRIES : PT_BVH_STACK_SIZE - PT_WF_LDS_STACK) * sizeof(uint2);
+    const size_t suspBytes = traceWaves * (size_t)(PT_WF_SUSPEND ? PT_WF_SUSPEND : 1u) * PT_WF_SUSP_RECORD_ROWS * sizeof(uint4);
+    const size_t tlasSpillBytes = needTlas ? traceWaves * 64u * (size_t)PT_BVH_STACK_SIZE * sizeof(uint32_t) : 0;
+    size_t total = 0;
+    auto carve = [&](size_t bytes) { char* q = base ? base + total : nullptr; total += align(bytes); return q; };
+    B.flags = (uint32_t*)carve(n * 4);
+    B.rng = (uint32_t*)carve(n * 4);
+    float4* dummy = nullptr;
+    float4** arrs[PT_F4_COUNT] = {&B.ray[0], &dummy, &B.ray[1], &dummy, &B.ray[2], &dummy, &B.rad, &B.thr, &B.color, &B.envC, &B.lightC, &B.pthr, &B.hit, &B.hit2, &B.pixsum};   // PT_F4_* order; a ray-record array spans two strides
+    for (auto a : arrs) *a = (float4*)carve(n * 16);
+    B.f4base = B.ray[0];
+    B.f4stride = (uint32_t)(align(n * 16) / 16);
+    B.occl = (uint8_t*)carve(n * 2);
+    B.statRows = (unsigned long long*)carve((size_t)numRows * 16 * 8);
+    B.chunkHeads = (uint32_t*)carve(PT_WF_SHARDS * 32 * 4);
+    B.stackSpill = (uint2*)carve(spillBytes);
+    B.susp = (uint4*)carve(suspBytes);
+    B.suspCount = (uint32_t*)carve(traceWaves * 4);
+    B.tlasSpill = needTlas ? (uint32_t*)carve(tlasSpillBytes) : nullptr;
+    B.residentWaves = residentWaves;
+    B.numSlots = numSlots;
+    B.numStatRows = numRows;
+    B.maxIterations = maxIterations;
+    return total;
+}
+
 } // namespace
 
+#ifdef PT_WF_TU_B
+size_t pt_wf_arena_bytes(uint32_t numSlots, uint32_t residentWaves, bool needTlas, uint32_t maxIterations)
+{
+    PTWfBuffers B = {};
+    return pt_wf_arena_layout(nullptr, numSlots, residentWaves, needTlas, maxIterations, B);
+}
+PTWfBuffers pt_wf_arena_carve(void* base, uint32_t numSlots, uint32_t residentWaves, bool needTlas, uint32_t maxIterations)
+{
+    PTWfBuffers B = {};
+    pt_wf_arena_layout((char*)base, numSlots, residentWaves, needTlas, maxIterations, B);
+    return B;
+}
+#define pt_launch_wavefront pt_launch_wavefront_b
+#endif
 
 // One pass = a fixed sequence of launches on `stream`, no host synchronisation (see the file header).
 // `orderAfter` (may be null) is the event of the previous pass's resolve: this pass's resolve reads that pass's output as

@@ -19,6 +19,61 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libunity-webgpu-pathtracer-plugin.so"      # Plugin/CMakeLists.txt:3 / TinyBVH.cs:8-12
 LIB_PATH = os.environ.get("PT_PLUGIN") or os.path.join(_HERE, "lib", LIB_NAME)   # PT_PLUGIN: explicit build to load
 
+# every export of include/ptmi_plugin.h: name -> (restype, argtypes)
+vp, i32, u32p = C.c_void_p, C.c_int, C.POINTER(C.c_uint32)
+sig = {
+    # Part 1 (TinyBVH.cs)
+    "BuildBVH": (i32, [vp, i32]), "DestroyBVH": (None, [i32]), "IsBVHReady": (i32, [i32]),
+    "GetBVHPtr": (vp, [i32]), "GetBVH": (vp, [i32]),
+    "GetCWBVHNodesSize": (i32, [i32]), "GetCWBVHTrisSize": (i32, [i32]),
+    "GetCWBVHData": (i32, [i32, C.POINTER(vp), C.POINTER(vp)]),
+    "PTBuildBVHDevice": (i32, [i32, vp, i32]), "PTGetBVHBuildError": (C.c_char_p, []), "PTGetBVHBuildMs": (C.c_double, [i32]),
+    "BuildTLAS": (i32, [vp, i32]), "DestroyTLAS": (None, [i32]), "IsTLASReady": (i32, [i32]),
+    "GetTLASNodesSize": (i32, [i32]), "GetTLASData": (i32, [i32, C.POINTER(vp), C.POINTER(vp)]),
+    # Part 2 (render)
+    "PTCreate": (i32, [i32, C.POINTER(vp)]), "PTDestroy": (i32, [vp]),
+    "PTSetScene": (i32, [vp, C.POINTER(abi.PTSceneDesc)]),
+    "PTSetTileOwnership": (i32, [vp, i32, i32]),
+    "PTRenderPass": (i32, [vp, C.POINTER(abi.PTFrameParams)]),
+    "PTFlipFrames": (i32, [vp]), "PTResetFrames": (i32, [vp]),
+    "PTRenderPassTo": (i32, [vp, C.POINTER(abi.PTFrameParams), vp, vp]),
+    "PTRenderPassBatchTo": (i32, [vp, C.POINTER(abi.PTFrameParams), i32, vp, vp]),
+    "PTRenderPassBatch": (i32, [vp, C.POINTER(abi.PTFrameParams), i32]),
+    "PTGroupRenderPassBatch": (i32, [vp, C.POINTER(abi.PTFrameParams), i32]),
+    "PTSynchronize": (i32, [vp]), "PTReadback": (i32, [vp, vp, C.c_uint64]),
+    "PTGetFramePointer": (vp, [vp, i32]), "PTGetStream": (vp, [vp]),
+    "PTSetStatsLevel": (i32, [vp, i32]), "PTGetStats": (i32, [vp, C.POINTER(abi.PTStats)]), "PTResetStats": (i32, [vp]),
+    "PTSetProfiling": (i32, [vp, i32]), "PTGetTimings": (i32, [vp, C.POINTER(abi.PTTimings)]), "PTResetTimings": (i32, [vp]),
+    "PTProcessMeshes": (i32, [vp, C.POINTER(abi.PTMeshDesc), C.c_uint32, C.c_uint32, vp, vp]),
+    "PTCopyTextureData": (i32, [vp, C.POINTER(abi.PTTextureDesc), C.c_uint32, vp, C.c_uint64]),
+    "PTPresent": (i32, [vp, C.POINTER(abi.PTPresentParams), vp, vp]),
+    "PTPresentToHost": (i32, [vp, C.POINTER(abi.PTPresentParams), vp, C.c_uint64]),
+    "PTSetSchedule": (i32, [vp, i32]), "PTGetSchedule": (i32, [vp]), "PTSetWavefrontIterations": (i32, [vp, i32]),
+    "PTSetPassesInFlight": (i32, [vp, i32]), "PTGetPassesInFlight": (i32, [vp]), "PTSetSubFrames": (i32, [vp, i32]),
+    "PTGetOwnedTileSlots": (i32, [vp, C.POINTER(abi.PTFrameParams), C.POINTER(C.c_uint64)]),
+    "PTPackOwnedTiles": (i32, [vp, C.POINTER(abi.PTFrameParams), vp, vp]),
+    "PTUnpackTiles": (i32, [vp, C.POINTER(abi.PTFrameParams), i32, i32, vp, vp]),
+    "PTCreateMulti": (i32, [C.POINTER(i32), i32, C.POINTER(vp)]), "PTGroupDestroy": (i32, [vp]), "PTGroupSize": (i32, [vp]),
+    "PTGroupGetContext": (vp, [vp, i32]), "PTGroupSetScene": (i32, [vp, C.POINTER(abi.PTSceneDesc)]),
+    "PTGroupRenderPass": (i32, [vp, C.POINTER(abi.PTFrameParams)]), "PTGroupFlipFrames": (i32, [vp]), "PTGroupResetFrames": (i32, [vp]),
+    "PTGroupSynchronize": (i32, [vp]), "PTGroupReadback": (i32, [vp, vp, C.c_uint64]), "PTGroupGetAssembledFrame": (vp, [vp]),
+    "PTGroupGetStats": (i32, [vp, C.POINTER(abi.PTStats)]), "PTGroupResetStats": (i32, [vp]),
+    # Part 3 (ray queries)
+    "PTTraceRays": (i32, [vp, vp, C.c_uint64, C.c_uint32, vp, vp]),
+    "PTTraceRaysHost": (i32, [vp, vp, C.c_uint64, C.c_uint32, vp, vp]),
+    # Part 4 (guides and denoising)
+    "PTRenderGuides": (i32, [vp, C.POINTER(abi.PTFrameParams), i32]),
+    "PTDenoise": (i32, [vp, C.POINTER(abi.PTDenoiseParams), vp, vp]),
+    "PTDenoiseToHost": (i32, [vp, C.POINTER(abi.PTDenoiseParams), vp, C.c_uint64]),
+    "PTGetGuidePointer": (vp, [vp, i32]),
+    # Part 5 (scene updates)
+    "PTUpdateInstances": (i32, [vp, vp, C.c_uint32]), "PTUpdateInstancesDevice": (i32, [vp, vp, C.c_uint32]),
+    "PTUpdateLights": (i32, [vp, vp, C.c_uint32]), "PTUpdateMaterials": (i32, [vp, vp, C.c_uint32]),
+    "PTReadTLAS": (i32, [vp, vp, C.c_uint64, vp, C.c_uint64, u32p]),
+    "PTGetLastError": (C.c_char_p, []), "PTGetVersion": (i32, []),
+}
+EXPORTED_SYMBOLS = list(sig)
+
 _lib = None
 
 
@@ -43,58 +98,6 @@ def load_library():
     except ImportError:
         pass
     lib = C.CDLL(LIB_PATH)
-    vp, i32, u32p = C.c_void_p, C.c_int, C.POINTER(C.c_uint32)
-    sig = {
-        # Part 1 (TinyBVH.cs)
-        "BuildBVH": (i32, [vp, i32]), "DestroyBVH": (None, [i32]), "IsBVHReady": (i32, [i32]),
-        "GetBVHPtr": (vp, [i32]), "GetBVH": (vp, [i32]),
-        "GetCWBVHNodesSize": (i32, [i32]), "GetCWBVHTrisSize": (i32, [i32]),
-        "GetCWBVHData": (i32, [i32, C.POINTER(vp), C.POINTER(vp)]),
-        "PTBuildBVHDevice": (i32, [i32, vp, i32]), "PTGetBVHBuildError": (C.c_char_p, []), "PTGetBVHBuildMs": (C.c_double, [i32]),
-        "BuildTLAS": (i32, [vp, i32]), "DestroyTLAS": (None, [i32]), "IsTLASReady": (i32, [i32]),
-        "GetTLASNodesSize": (i32, [i32]), "GetTLASData": (i32, [i32, C.POINTER(vp), C.POINTER(vp)]),
-        # Part 2 (render)
-        "PTCreate": (i32, [i32, C.POINTER(vp)]), "PTDestroy": (i32, [vp]),
-        "PTSetScene": (i32, [vp, C.POINTER(abi.PTSceneDesc)]),
-        "PTSetTileOwnership": (i32, [vp, i32, i32]),
-        "PTRenderPass": (i32, [vp, C.POINTER(abi.PTFrameParams)]),
-        "PTFlipFrames": (i32, [vp]), "PTResetFrames": (i32, [vp]),
-        "PTRenderPassTo": (i32, [vp, C.POINTER(abi.PTFrameParams), vp, vp]),
-        "PTRenderPassBatchTo": (i32, [vp, C.POINTER(abi.PTFrameParams), i32, vp, vp]),
-        "PTRenderPassBatch": (i32, [vp, C.POINTER(abi.PTFrameParams), i32]),
-        "PTGroupRenderPassBatch": (i32, [vp, C.POINTER(abi.PTFrameParams), i32]),
-        "PTSynchronize": (i32, [vp]), "PTReadback": (i32, [vp, vp, C.c_uint64]),
-        "PTGetFramePointer": (vp, [vp, i32]), "PTGetStream": (vp, [vp]),
-        "PTSetStatsLevel": (i32, [vp, i32]), "PTGetStats": (i32, [vp, C.POINTER(abi.PTStats)]), "PTResetStats": (i32, [vp]),
-        "PTSetProfiling": (i32, [vp, i32]), "PTGetTimings": (i32, [vp, C.POINTER(abi.PTTimings)]), "PTResetTimings": (i32, [vp]),
-        "PTProcessMeshes": (i32, [vp, C.POINTER(abi.PTMeshDesc), C.c_uint32, C.c_uint32, vp, vp]),
-        "PTCopyTextureData": (i32, [vp, C.POINTER(abi.PTTextureDesc), C.c_uint32, vp, C.c_uint64]),
-        "PTPresent": (i32, [vp, C.POINTER(abi.PTPresentParams), vp, vp]),
-        "PTPresentToHost": (i32, [vp, C.POINTER(abi.PTPresentParams), vp, C.c_uint64]),
-        "PTSetSchedule": (i32, [vp, i32]), "PTGetSchedule": (i32, [vp]), "PTSetWavefrontIterations": (i32, [vp, i32]),
-        "PTSetPassesInFlight": (i32, [vp, i32]), "PTGetPassesInFlight": (i32, [vp]), "PTSetSubFrames": (i32, [vp, i32]),
-        "PTGetOwnedTileSlots": (i32, [vp, C.POINTER(abi.PTFrameParams), C.POINTER(C.c_uint64)]),
-        "PTPackOwnedTiles": (i32, [vp, C.POINTER(abi.PTFrameParams), vp, vp]),
-        "PTUnpackTiles": (i32, [vp, C.POINTER(abi.PTFrameParams), i32, i32, vp, vp]),
-        "PTCreateMulti": (i32, [C.POINTER(i32), i32, C.POINTER(vp)]), "PTGroupDestroy": (i32, [vp]), "PTGroupSize": (i32, [vp]),
-        "PTGroupGetContext": (vp, [vp, i32]), "PTGroupSetScene": (i32, [vp, C.POINTER(abi.PTSceneDesc)]),
-        "PTGroupRenderPass": (i32, [vp, C.POINTER(abi.PTFrameParams)]), "PTGroupFlipFrames": (i32, [vp]), "PTGroupResetFrames": (i32, [vp]),
-        "PTGroupSynchronize": (i32, [vp]), "PTGroupReadback": (i32, [vp, vp, C.c_uint64]), "PTGroupGetAssembledFrame": (vp, [vp]),
-        "PTGroupGetStats": (i32, [vp, C.POINTER(abi.PTStats)]), "PTGroupResetStats": (i32, [vp]),
-        # Part 3 (ray queries)
-        "PTTraceRays": (i32, [vp, vp, C.c_uint64, C.c_uint32, vp, vp]),
-        "PTTraceRaysHost": (i32, [vp, vp, C.c_uint64, C.c_uint32, vp, vp]),
-        # Part 4 (guides and denoising)
-        "PTRenderGuides": (i32, [vp, C.POINTER(abi.PTFrameParams), i32]),
-        "PTDenoise": (i32, [vp, C.POINTER(abi.PTDenoiseParams), vp, vp]),
-        "PTDenoiseToHost": (i32, [vp, C.POINTER(abi.PTDenoiseParams), vp, C.c_uint64]),
-        "PTGetGuidePointer": (vp, [vp, i32]),
-        # Part 5 (scene updates)
-        "PTUpdateInstances": (i32, [vp, vp, C.c_uint32]), "PTUpdateInstancesDevice": (i32, [vp, vp, C.c_uint32]),
-        "PTUpdateLights": (i32, [vp, vp, C.c_uint32]), "PTUpdateMaterials": (i32, [vp, vp, C.c_uint32]),
-        "PTReadTLAS": (i32, [vp, vp, C.c_uint64, vp, C.c_uint64, u32p]),
-        "PTGetLastError": (C.c_char_p, []), "PTGetVersion": (i32, []),
-    }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = the library does not export what the header declares
         fn.restype = res
@@ -103,21 +106,6 @@ def load_library():
     return lib
 
 
-EXPORTED_SYMBOLS = [
-    "BuildBVH", "DestroyBVH", "IsBVHReady", "GetBVHPtr", "GetBVH", "GetCWBVHNodesSize", "GetCWBVHTrisSize", "GetCWBVHData",
-    "PTBuildBVHDevice", "PTGetBVHBuildError", "PTGetBVHBuildMs",
-    "BuildTLAS", "DestroyTLAS", "IsTLASReady", "GetTLASNodesSize", "GetTLASData",
-    "PTCreate", "PTDestroy", "PTSetScene", "PTSetTileOwnership", "PTRenderPass", "PTFlipFrames", "PTResetFrames",
-    "PTRenderPassTo", "PTRenderPassBatchTo", "PTRenderPassBatch", "PTGroupRenderPassBatch", "PTSynchronize", "PTReadback", "PTGetFramePointer", "PTGetStream", "PTSetStatsLevel", "PTGetStats",
-    "PTResetStats", "PTSetProfiling", "PTGetTimings", "PTResetTimings", "PTProcessMeshes", "PTCopyTextureData", "PTPresent", "PTPresentToHost", "PTSetSchedule", "PTGetSchedule", "PTSetWavefrontIterations", "PTSetPassesInFlight", "PTGetPassesInFlight", "PTSetSubFrames",
-    "PTGetOwnedTileSlots", "PTPackOwnedTiles", "PTUnpackTiles", "PTCreateMulti", "PTGroupDestroy", "PTGroupSize", "PTGroupGetContext",
-    "PTGroupSetScene", "PTGroupRenderPass", "PTGroupFlipFrames", "PTGroupResetFrames", "PTGroupSynchronize", "PTGroupReadback",
-    "PTGroupGetAssembledFrame", "PTGroupGetStats", "PTGroupResetStats",
-    "PTTraceRays", "PTTraceRaysHost",
-    "PTRenderGuides", "PTDenoise", "PTDenoiseToHost", "PTGetGuidePointer",
-    "PTUpdateInstances", "PTUpdateInstancesDevice", "PTUpdateLights", "PTUpdateMaterials", "PTReadTLAS",
-    "PTGetLastError", "PTGetVersion",
-]
 
 
 class PluginError(RuntimeError):
