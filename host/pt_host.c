@@ -8,6 +8,9 @@
  *   usage: pt_host [width height spp passes out.f32 [abi_dump.bin]]
  *          PT_HOST_DEVICES=0,1,2,3 (environment): render on those devices through PTCreateMulti / PTGroup* -- one process, N
  *          GPUs, frame assembled in the library from every device's tiles; the same device may be listed twice.
+ *          PT_HOST_NOISE_TARGET=<eps> (environment, one device): every pass is recorded in the per-pixel moments
+ *          (PTAccumulateMoments) and the loop stops early once the 95th percentile of the relative error (PTMeasureNoise) is
+ *          below eps; the samples used are printed.  Unset: nothing of this is called and the output is unchanged.
  *          out.f32: width*height float4, linear radiance, row 0 = bottom.
  *          abi_dump.bin: everything this host handed across the C-ABI, byte for byte -- the BuildBVH input, the attribute,
  *          material and light arrays, the CWBVH the library returned, and the PTFrameParams of every pass -- so that a
@@ -80,6 +83,16 @@ int main(int argc, char** argv)
     LOAD(PTGetStats) LOAD(PTGetLastError) LOAD(PTSynchronize)
     LOAD(PTCreateMulti) LOAD(PTGroupDestroy) LOAD(PTGroupSetScene) LOAD(PTGroupRenderPass) LOAD(PTGroupFlipFrames) LOAD(PTGroupReadback)
     LOAD(PTGroupGetStats)
+    /* optional: stop once the frame is converged to PT_HOST_NOISE_TARGET (looked up only then: older libraries still load) */
+    const char* noiseEnv = getenv("PT_HOST_NOISE_TARGET");
+    const float noiseTarget = noiseEnv && *noiseEnv ? (float)atof(noiseEnv) : 0.0f;
+    __typeof__(&PTAccumulateMoments) p_PTAccumulateMoments = NULL;
+    __typeof__(&PTMeasureNoise) p_PTMeasureNoise = NULL;
+    if (noiseTarget > 0.0f) {
+        p_PTAccumulateMoments = (__typeof__(&PTAccumulateMoments))dlsym(lib, "PTAccumulateMoments");
+        p_PTMeasureNoise = (__typeof__(&PTMeasureNoise))dlsym(lib, "PTMeasureNoise");
+        if (!p_PTAccumulateMoments || !p_PTMeasureNoise) { fprintf(stderr, "PT_HOST_NOISE_TARGET needs PTAccumulateMoments / PTMeasureNoise\n"); return 2; }
+    }
     int devices[64], nDevices = 0;
     const char* devList = getenv("PT_HOST_DEVICES");
     if (devList && *devList) {
@@ -162,6 +175,22 @@ int main(int argc, char** argv)
         if (rc) { fprintf(stderr, "PTRenderPass: %d %s\n", rc, p_PTGetLastError()); return 1; }
         currentSample += spp > 1 ? spp : 1;
         flipped = 0;
+        if (noiseTarget > 0.0f && !group) {         /* after the pass, before the flip */
+            rc = p_PTAccumulateMoments(ctx, &p, 1);
+            if (rc) { fprintf(stderr, "PTAccumulateMoments: %d %s\n", rc, p_PTGetLastError()); return 1; }
+            if (k >= 1) {
+                PTNoiseParams np = {(uint32_t)sizeof(PTNoiseParams), 0.01f, noiseTarget, 0.95f};
+                PTNoiseStats ns;
+                ns.structSize = (uint32_t)sizeof(ns);
+                rc = p_PTMeasureNoise(ctx, &np, NULL, &ns);
+                if (rc) { fprintf(stderr, "PTMeasureNoise: %d %s\n", rc, p_PTGetLastError()); return 1; }
+                if (ns.percentileError < noiseTarget || k + 1 == passes)
+                    printf("pt_host: noise target %g %s after %d samples (95th percentile of the relative error <= %g, mean %g)\n",
+                           (double)noiseTarget, ns.percentileError < noiseTarget ? "reached" : "not reached", currentSample,
+                           (double)ns.percentileError, (double)ns.meanError);
+                if (ns.percentileError < noiseTarget) break;
+            }
+        }
         if (currentSample < maxSamples && k + 1 < passes) { if (group) p_PTGroupFlipFrames(group); else p_PTFlipFrames(ctx); flipped = 1; }
     }
     (void)flipped;

@@ -518,6 +518,95 @@ PT_API int PTUpdateMaterials(PTContext* ctx, const void* materials, uint32_t cou
 PT_API int PTReadTLAS(PTContext* ctx, void* dstNodes, uint64_t dstNodeBytes, uint32_t* dstIndices, uint64_t dstIndexCount,
                       uint32_t* outNodeCount);
 
+/* =====================================================================================================================
+ * Part 6: per-pixel variance across passes.  How far is the running mean from converged?  The accumulation already carries
+ * the answer: after a pass Output and AccumulatedOutput are the running mean after and before m new samples, and by Welford's
+ * update identity their difference is the term that advances the per-pixel sum of squared deviations.  No render kernel is
+ * touched; the view is static; the only history is the running mean the reference itself keeps.
+ *
+ * Moments (PTAccumulateMoments[To]): one call records ONE observation -- the `count` passes (1..8) that PTRenderPass[To] or
+ * PTRenderPassBatch[To] just enqueued with these params (a batch is one observation: its intermediate frames do not exist).
+ * n = params[0].CurrentSample, m = count * max(1, SamplesPerPass).
+ *  - n == 0: both planes are written with zeros, Acc is not read; observations = 1, samples = m.
+ *  - n > 0: n must equal the stored sample count and the size the stored size.  Per pixel, in float32, every operation one
+ *    IEEE operation in this order (no contraction):
+ *        f  = (float)((double)n * (double)(n + m) / (double)m)                     (host)
+ *        d  = Out.rgb - Acc.rgb;  dl = 0.2126f*d.r + 0.7152f*d.g + 0.0722f*d.b
+ *        plane0 += ((d.r*d.r)*f, (d.g*d.g)*f, (d.b*d.b)*f, (dl*dl)*f)               Srr Sgg Sbb Sll
+ *        plane1 += ((d.r*d.g)*f, (d.r*d.b)*f, (d.g*d.b)*f, 0)                       Srg Srb Sgb
+ *    then observations += 1, samples = n + m, and Out becomes "the frame last accumulated".
+ *  With k observations of W samples in all, S / ((k - 1) * W) estimates the variance of the running mean (invDof below).
+ *  Ordering: enqueued on the context stream -- after the resolve of the passes it describes, before the resolve of any later
+ *  pass (which overwrites Acc's buffer); the trace chains of passes in flight do not wait for it.  Call it after the pass and
+ *  before PTFlipFrames.
+ *
+ * Noise (PTMeasureNoise; needs observations k >= 2), per pixel of the blocks this context owns (PTSetTileOwnership), float32:
+ *        invDof = (float)(1.0 / ((double)(k - 1) * (double)W))                     (host)
+ *        l   = 0.2126f*r + 0.7152f*g + 0.0722f*b                                    of dFrame.rgb
+ *        eps = sqrtf(Sll * invDof) / (l + relFloor)          relative standard error of the mean; NaN or negative -> +inf
+ *        bin = clamp((int)(bits(eps) >> 20) - ((127 - 24) << 3), 0, 255)            eighth-octave bins from 2^-24 to 2^8
+ *  pixels = pixels counted, pixelsBelow = those with eps <= threshold, maxError / meanError = maximum / mean of eps,
+ *  percentileError = the upper edge of the first bin at which the cumulative count reaches ceil(percentile * pixels)
+ *  (+inf for bin 255; 0 when pixels == 0).  The tile map holds the mean eps of every 16x16 block, 0 for blocks of other
+ *  ranks; a multi-rank host adds the integer fields of its ranks.  Two calls on the same data return the same bytes (integer
+ *  atomics and ordered sums only).
+ *
+ * Denoising led by that variance (PTDenoiseMoments): PTDenoise with one change -- the prepass's v at a covered pixel is the
+ * variance of the mean of the filter luminance instead of the 3x3 spatial variance:
+ *        not demodulated:  v = Sll * invDof
+ *        demodulated:      q_c = w_c / max(albedo_c, 1e-3), w = (0.2126, 0.7152, 0.0722),
+ *                          v = max(0, (q_r^2 Srr + q_g^2 Sgg + q_b^2 Sbb + 2 (q_r q_g Srg + q_r q_b Srb + q_g q_b Sgb)) * invDof)
+ *  so a converged frame is left alone.  Needs guides of the moments' size and observations >= 2.
+ *
+ * Memory: allocated on first use, regrown on a size change, freed by PTDestroy; a context that never calls these functions
+ * allocates nothing for them.
+ * Errors: PT_ERR_INVALID_ARG for a NULL context or required pointer, count outside 1..8, n != the stored sample count or
+ * another size (the message names both numbers), relFloor or threshold not > 0, percentile outside (0, 1], fewer than 2
+ * observations, a short structSize.  There is no CPU fallback.
+ * ===================================================================================================================== */
+typedef struct PTNoiseParams {    /* 16 bytes */
+    uint32_t structSize;          /* = sizeof(PTNoiseParams) of the host's header */
+    float    relFloor;            /* added to the luminance in the denominator; suggested 0.01 */
+    float    threshold;           /* pixelsBelow counts eps <= threshold; suggested 0.02 */
+    float    percentile;          /* in (0, 1]; suggested 0.95 */
+} PTNoiseParams;
+
+typedef struct PTNoiseStats {     /* 1072 bytes */
+    uint32_t structSize;          /* in: sizeof(PTNoiseStats) of the host's header */
+    uint32_t observations;
+    uint64_t samples;
+    uint64_t pixels;
+    uint64_t pixelsBelow;
+    float    meanError, maxError, percentileError;
+    uint32_t _pad;
+    uint32_t histogram[256];
+} PTNoiseStats;
+
+#ifdef __cplusplus
+static_assert(sizeof(PTNoiseParams) == 16, "PTNoiseParams is 16 bytes");
+static_assert(sizeof(PTNoiseStats) == 1072, "PTNoiseStats is 1072 bytes");
+#else
+_Static_assert(sizeof(PTNoiseParams) == 16, "PTNoiseParams is 16 bytes");
+_Static_assert(sizeof(PTNoiseStats) == 1072, "PTNoiseStats is 1072 bytes");
+#endif
+
+/* Out = frame[cur], Acc = frame[1 - cur] of the context's own frames: call after the pass, before PTFlipFrames. */
+PT_API int PTAccumulateMoments(PTContext* ctx, const PTFrameParams* params, int count);
+/* The same over caller-owned DEVICE frames (dAccumulated may be NULL when CurrentSample == 0). */
+PT_API int PTAccumulateMomentsTo(PTContext* ctx, const PTFrameParams* params, int count, const void* dOutput, const void* dAccumulated);
+/* Any of the four outputs may be NULL.  Before the first accumulation everything is 0. */
+PT_API int PTGetMomentsInfo(PTContext* ctx, uint32_t* observations, uint64_t* samples, uint32_t* width, uint32_t* height);
+/* Device pointer of plane 0 (Srr Sgg Sbb Sll) or 1 (Srg Srb Sgb 0): width*height float4 each; NULL before first use. */
+PT_API void* PTGetMomentsPointer(PTContext* ctx, int which);
+/* dFrame: DEVICE pointer to the frame whose luminance is the denominator; NULL = the frame last accumulated.  Synchronous. */
+PT_API int PTMeasureNoise(PTContext* ctx, const PTNoiseParams* params, const void* dFrame, PTNoiseStats* out);
+/* ceil(W/16) * ceil(H/16) floats, row-major: the mean eps of each 16x16 block after PTMeasureNoise; NULL before. */
+PT_API void* PTGetNoiseTilePointer(PTContext* ctx);
+/* PTDenoise with the moments' variance; dSrc == NULL reads the frame last accumulated. */
+PT_API int PTDenoiseMoments(PTContext* ctx, const PTDenoiseParams* params, const void* dSrc, void* dDst);
+/* Denoises the frame last accumulated into host memory (width*height float4); synchronous. */
+PT_API int PTDenoiseMomentsToHost(PTContext* ctx, const PTDenoiseParams* params, float* dstRGBA, uint64_t dstFloats);
+
 /* Text of the last error on the calling thread ("" if none). */
 PT_API const char* PTGetLastError(void);
 /* Library/ABI version: (major << 16) | minor. */

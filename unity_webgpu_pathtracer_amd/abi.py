@@ -219,6 +219,34 @@ def denoise_params(iterations: int = 5, sigma_luminance: float = 4.0, sigma_norm
                            PT_DENOISE_DEMODULATE_ALBEDO if demodulate else 0)
 
 
+# ---------------------------------------------------------------------------------------
+# Part 6: per-pixel variance across passes (PTAccumulateMoments / PTMeasureNoise / PTDenoiseMoments)
+# ---------------------------------------------------------------------------------------
+class PTNoiseParams(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("relFloor", C.c_float), ("threshold", C.c_float), ("percentile", C.c_float)]
+
+
+class PTNoiseStats(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("observations", C.c_uint32), ("samples", C.c_uint64), ("pixels", C.c_uint64),
+                ("pixelsBelow", C.c_uint64), ("meanError", C.c_float), ("maxError", C.c_float), ("percentileError", C.c_float),
+                ("_pad", C.c_uint32), ("histogram", C.c_uint32 * 256)]
+
+
+assert C.sizeof(PTNoiseParams) == 16 and C.sizeof(PTNoiseStats) == 1072
+
+
+def noise_params(rel_floor: float = 0.01, threshold: float = 0.02, percentile: float = 0.95) -> PTNoiseParams:
+    """PTNoiseParams with the header's suggested values (floor 0.01, threshold 2 %, 95th percentile)."""
+    return PTNoiseParams(C.sizeof(PTNoiseParams), rel_floor, threshold, percentile)
+
+
+def noise_stats() -> PTNoiseStats:
+    """An empty PTNoiseStats with structSize set, for PTMeasureNoise to fill."""
+    st = PTNoiseStats()
+    st.structSize = C.sizeof(PTNoiseStats)
+    return st
+
+
 def as_void_p(arr):
     """Borrowed host pointer of a C-contiguous numpy array (None -> NULL)."""
     if arr is None:

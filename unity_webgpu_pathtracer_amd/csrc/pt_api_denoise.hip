@@ -50,6 +50,13 @@ PT_API int PTRenderGuides(PTContext* c, const PTFrameParams* hostParams, int sam
 PT_API int PTDenoise(PTContext* c, const PTDenoiseParams* params, const void* dSrc, void* dDst)
 {
     if (!c) return fail(PT_ERR_INVALID_ARG, "PTDenoise: ctx == NULL");
+    return denoise_frame(c, params, dSrc, dDst, nullptr);
+}
+
+} // extern "C"
+
+int denoise_frame(PTContext* c, const PTDenoiseParams* params, const void* dSrc, void* dDst, const PTDenoiseVariance* variance)
+{
     PTDenoiseParams p;
     int rc = import_denoise_params(params, p);
     if (rc) return rc;
@@ -74,9 +81,11 @@ PT_API int PTDenoise(PTContext* c, const PTDenoiseParams* params, const void* dS
     if ((rc = state.resize(guides.w, guides.h, {sizeof(float4), sizeof(float4), sizeof(float2)}, c->stream))) return rc;
     PTDenoiseArgs A = {guides.w, guides.h, p.sigmaLuminance, p.sigmaNormal, p.sigmaDepth, p.flags};
     HIP_TRY(pt_launch_denoise(A, p.iterations, (const float4*)dSrc, (float4*)dDst, guides.f4(0), guides.f4(1), state.f4(0), state.f4(1),
-                              (float2*)state.buf[2].ptr, c->stream));
+                              (float2*)state.buf[2].ptr, variance, c->stream));
     return PT_OK;
 }
+
+extern "C" {
 
 PT_API int PTDenoiseToHost(PTContext* c, const PTDenoiseParams* params, float* dst, uint64_t dstFloats)
 {

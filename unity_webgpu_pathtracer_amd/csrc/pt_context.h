@@ -156,6 +156,16 @@ struct PTContext {
         FrameSet<3> state;                      // filter state ping-pong (e.rgb, v) x 2, then the float2 depth gradient
         DeviceBuffer host;                      // PTDenoiseToHost staging frame
     } denoise;
+    // moments across passes (PTAccumulateMoments / PTMeasureNoise / PTDenoiseMoments): likewise
+    struct Moments {
+        FrameSet<2> planes;                     // Srr Sgg Sbb Sll | Srg Srb Sgb 0
+        uint32_t observations = 0;
+        uint64_t samples = 0;
+        // the frame last accumulated: one of the context's own frames (by index: they may be re-created) or a caller's pointer
+        int lastOwn = -1;
+        const void* lastPtr = nullptr;
+        DeviceBuffer stats, blockSums, tiles;   // PTMeasureNoise: PT_NOISE_WORDS words, one float per 16x16 block each
+    } moments;
     // scene updates (PTUpdateInstances / Lights / Materials): two generations of what an update rewrites, allocated on the first
     // update of each kind and discarded by PTSetScene.  cur = -1 while PTSetScene's own buffers are current.
     struct UpdGroup {
@@ -234,5 +244,7 @@ inline int trace_variant(int schedule) { return schedule == 4 ? 4 : (schedule ==
 // the material slots that name a texture: baseColor, metallicRoughness, emission, occlusion (normal map is unused)
 constexpr int kTextureSlots[4] = {22, 23, 25, 26};
 
+// pt_api_denoise.hip: PTDenoise's body; variance != nullptr is PTDenoiseMoments (dSrc then is never NULL)
+int denoise_frame(PTContext* c, const PTDenoiseParams* params, const void* dSrc, void* dDst, const PTDenoiseVariance* variance);
 int set_scene(PTContext* c, const PTSceneDesc* hostScene, bool validate);      // pt_api_context.hip; PTGroupSetScene validates once
 int drain_events(PTContext* c);                                                 // pt_api_context.hip

@@ -243,6 +243,54 @@ extern "C" __global__ __launch_bounds__(256) void pt_denoise_prepass(PTDenoiseAr
     gradz[p] = make_float2(g[0], g[1]);
 }
 
+// The prepass of PTDenoiseMoments: the same state and depth gradient, but v at a covered pixel is the variance of the MEAN of the
+// filter luminance, from the moment planes of PTAccumulateMoments (include/ptmi_plugin.h Part 6).  The demodulated luminance is
+// sum_c (w_c / max(albedo_c, 1e-3)) e_c, linear in rgb with per-pixel constants, so its variance is the quadratic form of the
+// rgb covariance.  Only the four axis neighbours' coverage is read (for the gradient).
+extern "C" __global__ __launch_bounds__(256) void pt_denoise_prepass_moments(PTDenoiseArgs A, PTDenoiseVariance V,
+                                                                             const float4* __restrict__ src,
+                                                                             const float4* __restrict__ albedo,
+                                                                             const float4* __restrict__ normalDepth,
+                                                                             float4* __restrict__ state, float2* __restrict__ gradz)
+{
+    const int W = (int)A.width, H = (int)A.height;
+    const int x = (int)(blockIdx.x * PT_DN_TILE + threadIdx.x % PT_DN_TILE), y = (int)(blockIdx.y * PT_DN_TILE + threadIdx.x / PT_DN_TILE);
+    if (x >= W || y >= H) return;
+    const size_t p = (size_t)y * W + x;
+    const float4 a = albedo[p];
+    if (!(a.w > 0.0f)) {
+        state[p] = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+        gradz[p] = make_float2(0.0f, 0.0f);
+        return;
+    }
+    const bool demod = (A.flags & PT_DENOISE_DEMODULATE_ALBEDO) != 0u;
+    const float4 s0 = V.plane0[p];
+    float var;
+    if (demod) {
+        const float4 s1 = V.plane1[p];
+        const float qr = 0.2126f / pt_max(a.x, 1e-3f), qg = 0.7152f / pt_max(a.y, 1e-3f), qb = 0.0722f / pt_max(a.z, 1e-3f);
+        const float diag = (qr * qr) * s0.x + (qg * qg) * s0.y + (qb * qb) * s0.z;
+        const float cross = (qr * qg) * s1.x + (qr * qb) * s1.y + (qg * qb) * s1.z;
+        var = pt_max((diag + 2.0f * cross) * V.invDof, 0.0f);
+    } else {
+        var = pt_max(s0.w * V.invDof, 0.0f);
+    }
+    const float4 e = dn_demod(src[p], a, demod);
+    state[p] = make_float4(e.x, e.y, e.z, var);
+    // central difference on covered neighbours, one-sided where one is uncovered, 0 where both are (pt_denoise_prepass's rule)
+    const float zc = normalDepth[p].w;
+    float g[2];
+#pragma unroll
+    for (int axis = 0; axis < 2; ++axis) {
+        const bool im = axis == 0 ? x > 0 : y > 0, ip = axis == 0 ? x + 1 < W : y + 1 < H;
+        const size_t qm = axis == 0 ? p - 1 : p - (size_t)W, qp = axis == 0 ? p + 1 : p + (size_t)W;
+        const bool cm = im && albedo[qm].w > 0.0f, cp = ip && albedo[qp].w > 0.0f;
+        const float zm = cm ? normalDepth[qm].w : 0.0f, zq = cp ? normalDepth[qp].w : 0.0f;
+        g[axis] = cm && cp ? (zq - zm) * 0.5f : cp ? zq - zc : cm ? zc - zm : 0.0f;
+    }
+    gradz[p] = make_float2(g[0], g[1]);
+}
+
 // One a-trous level.  STEP > 0: the tile and its 2 * STEP halo staged in LDS; STEP == 0: step `step`, taps read from memory.
 template <int STEP>
 PT_DEV void atrous_level(const PTDenoiseArgs& A, int step, const float4* __restrict__ stateIn, const float4* __restrict__ normalDepth,
@@ -361,10 +409,12 @@ hipError_t pt_launch_guides(const DScene& S, const PTFrameParams& P, uint32_t n,
 }
 
 hipError_t pt_launch_denoise(const PTDenoiseArgs& A, int iterations, const float4* src, float4* dst, const float4* albedo,
-                             const float4* normalDepth, float4* state0, float4* state1, float2* gradz, hipStream_t stream)
+                             const float4* normalDepth, float4* state0, float4* state1, float2* gradz,
+                             const PTDenoiseVariance* variance, hipStream_t stream)
 {
     const dim3 grid((A.width + PT_DN_TILE - 1u) / PT_DN_TILE, (A.height + PT_DN_TILE - 1u) / PT_DN_TILE), block(PT_DN_TILE * PT_DN_TILE);
-    hipLaunchKernelGGL(pt_denoise_prepass, grid, block, 0, stream, A, src, albedo, normalDepth, state0, gradz);
+    if (variance) hipLaunchKernelGGL(pt_denoise_prepass_moments, grid, block, 0, stream, A, *variance, src, albedo, normalDepth, state0, gradz);
+    else hipLaunchKernelGGL(pt_denoise_prepass, grid, block, 0, stream, A, src, albedo, normalDepth, state0, gradz);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     float4* in = state0;

@@ -82,9 +82,32 @@ struct PTDenoiseArgs {
     float sigmaL, sigmaN, sigmaZ;
     uint32_t flags;
 };
-// iterations >= 1 levels: prepass, one launch per level, remodulation (iterations + 2 launches); every buffer width*height
+// where the prepass takes v from: the moment planes of PTAccumulateMoments (Srr Sgg Sbb Sll | Srg Srb Sgb 0) and 1 / ((k - 1) W)
+struct PTDenoiseVariance {
+    const float4* plane0;
+    const float4* plane1;
+    float invDof;
+};
+// iterations >= 1 levels: prepass, one launch per level, remodulation (iterations + 2 launches); every buffer width*height.
+// variance == nullptr: the 3x3 spatial variance of PTDenoise; else the variance of the mean from the moments (PTDenoiseMoments)
 hipError_t pt_launch_denoise(const PTDenoiseArgs& A, int iterations, const float4* src, float4* dst, const float4* albedo,
-                             const float4* normalDepth, float4* state0, float4* state1, float2* gradz, hipStream_t stream);
+                             const float4* normalDepth, float4* state0, float4* state1, float2* gradz,
+                             const PTDenoiseVariance* variance, hipStream_t stream);
+
+// ---- per-pixel moments across passes and the noise metric (pt_moments.hip) ----
+// plane0 / plane1 += the Welford term of (out - acc) times f, per pixel (include/ptmi_plugin.h Part 6)
+hipError_t pt_launch_moments_accumulate(uint32_t pixels, float f, const float4* out, const float4* acc, float4* plane0,
+                                        float4* plane1, hipStream_t stream);
+// words of the statistics buffer: 256 histogram bins, then the maximum's bits, pixelsBelow, the sum of eps (float bits)
+enum : uint32_t { PT_NOISE_MAX = 256, PT_NOISE_BELOW, PT_NOISE_SUM, PT_NOISE_WORDS };
+struct PTNoiseArgs {
+    uint32_t width, height;
+    uint32_t rank, world;           // block (bx, by) is counted when (bx + by) % world == rank
+    float invDof, relFloor, threshold;
+};
+// stats: PT_NOISE_WORDS zeroed words; blockSums / tiles: ceil(width/16) * ceil(height/16) floats each
+hipError_t pt_launch_noise(const PTNoiseArgs& A, const float4* frame, const float4* plane0, uint32_t* stats, float* blockSums,
+                           float* tiles, hipStream_t stream);
 
 // ---- schedule 1 (wavefront): slot-indexed path state in HBM (see pt_wavefront.hip) ----
 // float4 arrays of a state set, in carving order.  PT_F4_RAY0/1/2 are the RAY RECORDS of the three ray kinds a slot can have in

@@ -140,8 +140,9 @@ class PathTracer:
                  samplesPerPass: int = 1, maxSamples: int = 100000, maxRayBounces: int = 4,
                  useRussianRoulette: bool = True, fireflyFilter: bool = False, maxFireflyLuminance: float = 10.0,
                  rank: int = 0, world_size: int = 1, reference_dispatch: bool = False, schedule: int = None,
-                 build_device: int = None):
+                 build_device: int = None, track_noise: bool = False):
         self.lib = plugin.load_library()
+        self.track_noise = track_noise          # OnRenderImage records every pass in the moments (PTAccumulateMoments)
         self.scene = scene
         self.width, self.height = width, height
         # inspector fields (PathTracer.cs:24-50)
@@ -190,6 +191,8 @@ class PathTracer:
         if self._currentSample < self.maxSamples:
             p = self.params(seed)
             plugin.check(self.lib.PTRenderPass(self.ctx, C.byref(p)))
+            if self.track_noise:
+                plugin.check(self.lib.PTAccumulateMoments(self.ctx, C.byref(p), 1))       # after the pass, before the flip
         if self._currentSample < self.maxSamples:
             self._currentSample += max(1, self.samplesPerPass)
         if self._currentSample < self.maxSamples:
@@ -413,24 +416,95 @@ class PathTracer:
             out.append(_device_to_numpy(ptr, (h, w, 4)))
         return out[0], out[1]
 
-    def denoise(self, dp: abi.PTDenoiseParams = None, d_src: int = 0, d_dst: int = 0):
+    def denoise(self, dp: abi.PTDenoiseParams = None, d_src: int = 0, d_dst: int = 0, variance: str = "spatial"):
         """PTDenoise with `dp` (default abi.denoise_params()).  d_src = 0 reads the current Output frame.  With d_dst = 0 the
-        result comes back as (H, W, 4) float32 numpy (PTDenoiseToHost when d_src is 0 too); else it is written to d_dst."""
+        result comes back as (H, W, 4) float32 numpy (PTDenoiseToHost when d_src is 0 too); else it is written to d_dst.
+        variance: "spatial" = PTDenoise (the 3x3 luminance variance); "moments" = PTDenoiseMoments (the variance of the mean
+        from the tracked passes; d_src = 0 then reads the frame last accumulated); "auto" = the moments from 4 observations
+        on, else spatial (SVGF's fallback rule)."""
+        if variance not in ("spatial", "moments", "auto"):
+            raise ValueError(f"variance = {variance!r}")
+        if variance == "auto":
+            variance = "moments" if self.moments_info()[0] >= 4 else "spatial"
+        fn, fn_host = ((self.lib.PTDenoiseMoments, self.lib.PTDenoiseMomentsToHost) if variance == "moments"
+                       else (self.lib.PTDenoise, self.lib.PTDenoiseToHost))
         dp = dp or abi.denoise_params()
         if d_dst:
-            plugin.check(self.lib.PTDenoise(self.ctx, C.byref(dp), C.c_void_p(d_src) if d_src else None, C.c_void_p(d_dst)))
+            plugin.check(fn(self.ctx, C.byref(dp), C.c_void_p(d_src) if d_src else None, C.c_void_p(d_dst)))
             return None
         h, w = self._guide_size
         out = np.empty((h, w, 4), dtype=np.float32)
         if not d_src:
-            plugin.check(self.lib.PTDenoiseToHost(self.ctx, C.byref(dp), out.ctypes.data_as(C.c_void_p), out.size))
+            plugin.check(fn_host(self.ctx, C.byref(dp), out.ctypes.data_as(C.c_void_p), out.size))
             return out
         import torch
         dst = torch.empty((h, w, 4), dtype=torch.float32, device=f"cuda:{self.device}")
         torch.cuda.synchronize(dst.device)
-        plugin.check(self.lib.PTDenoise(self.ctx, C.byref(dp), C.c_void_p(d_src), C.c_void_p(dst.data_ptr())))
+        plugin.check(fn(self.ctx, C.byref(dp), C.c_void_p(d_src), C.c_void_p(dst.data_ptr())))
         self.synchronize()
         return dst.cpu().numpy()
+
+    # ---- variance across passes (include/ptmi_plugin.h Part 6)
+    def accumulate_moments(self, p: abi.PTFrameParams, count: int = 1, d_output: int = 0, d_accumulated: int = 0):
+        """PTAccumulateMoments: record the `count` passes just enqueued with `p` as one observation -- over the internal frames
+        (call it before flip()), or over caller-owned device frames when d_output is given (PTAccumulateMomentsTo)."""
+        if d_output:
+            plugin.check(self.lib.PTAccumulateMomentsTo(self.ctx, C.byref(p), count, C.c_void_p(d_output), C.c_void_p(d_accumulated or None)))
+        else:
+            plugin.check(self.lib.PTAccumulateMoments(self.ctx, C.byref(p), count))
+
+    def moments_info(self):
+        """(observations, samples, width, height) of the moments; zeros before the first accumulation."""
+        k, w, h, n = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint64()
+        plugin.check(self.lib.PTGetMomentsInfo(self.ctx, C.byref(k), C.byref(n), C.byref(w), C.byref(h)))
+        return k.value, n.value, w.value, h.value
+
+    def moments_pointer(self, which: int) -> int:
+        return self.lib.PTGetMomentsPointer(self.ctx, which) or 0
+
+    def moments(self):
+        """The two moment planes as (H, W, 4) float32 numpy arrays: (Srr, Sgg, Sbb, Sll) and (Srg, Srb, Sgb, 0)."""
+        _, _, w, h = self.moments_info()
+        if not w:
+            raise RuntimeError("nothing accumulated yet")
+        self.synchronize()
+        return tuple(_device_to_numpy(self.moments_pointer(k), (h, w, 4)) for k in (0, 1))
+
+    def noise(self, threshold: float = 0.02, percentile: float = 0.95, rel_floor: float = 0.01, d_frame: int = 0) -> abi.PTNoiseStats:
+        """PTMeasureNoise over the frame last accumulated (or d_frame): the statistics of the per-pixel relative standard
+        error of the mean.  Synchronous."""
+        st = abi.noise_stats()
+        q = abi.noise_params(rel_floor, threshold, percentile)
+        plugin.check(self.lib.PTMeasureNoise(self.ctx, C.byref(q), C.c_void_p(d_frame) if d_frame else None, C.byref(st)))
+        return st
+
+    def noise_tiles(self) -> np.ndarray:
+        """The mean error of every 16x16 block after noise(): (ceil(H/16), ceil(W/16)) float32, 0 for other ranks' blocks."""
+        ptr = self.lib.PTGetNoiseTilePointer(self.ctx)
+        if not ptr:
+            raise RuntimeError("noise() has not been called")
+        _, _, w, h = self.moments_info()
+        return _device_to_numpy(ptr, ((h + 15) // 16, (w + 15) // 16))
+
+    def render_until(self, noise: float, percentile: float = 0.95, max_samples: int = None, seed0: int = 0, check_every: int = 4):
+        """Reset(), then OnRenderImage(seed0 + k) with every pass tracked, until a check -- every `check_every` passes -- finds
+        the `percentile` of the relative error below `noise`, or `max_samples` (default maxSamples) are reached.  The frame is
+        the one the same number of plain OnRenderImage calls gives.  Returns (passes rendered, the last PTNoiseStats or None)."""
+        limit = min(self.maxSamples, max_samples if max_samples is not None else self.maxSamples)
+        was, self.track_noise = self.track_noise, True
+        st, k = None, 0
+        try:
+            self.Reset()
+            while self._currentSample < limit:
+                self.OnRenderImage(seed0 + k)
+                k += 1
+                if k >= 2 and k % max(1, check_every) == 0:
+                    st = self.noise(threshold=noise, percentile=percentile)
+                    if st.percentileError < noise:
+                        break
+        finally:
+            self.track_noise = was
+        return k, st
 
     # ---- scene updates (include/ptmi_plugin.h Part 5)
     def set_instance_transforms(self, local_to_world) -> bool:

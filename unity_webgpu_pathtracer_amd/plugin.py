@@ -70,6 +70,15 @@ sig = {
     "PTUpdateInstances": (i32, [vp, vp, C.c_uint32]), "PTUpdateInstancesDevice": (i32, [vp, vp, C.c_uint32]),
     "PTUpdateLights": (i32, [vp, vp, C.c_uint32]), "PTUpdateMaterials": (i32, [vp, vp, C.c_uint32]),
     "PTReadTLAS": (i32, [vp, vp, C.c_uint64, vp, C.c_uint64, u32p]),
+    # Part 6 (variance across passes)
+    "PTAccumulateMoments": (i32, [vp, C.POINTER(abi.PTFrameParams), i32]),
+    "PTAccumulateMomentsTo": (i32, [vp, C.POINTER(abi.PTFrameParams), i32, vp, vp]),
+    "PTGetMomentsInfo": (i32, [vp, u32p, C.POINTER(C.c_uint64), u32p, u32p]),
+    "PTGetMomentsPointer": (vp, [vp, i32]),
+    "PTMeasureNoise": (i32, [vp, C.POINTER(abi.PTNoiseParams), vp, C.POINTER(abi.PTNoiseStats)]),
+    "PTGetNoiseTilePointer": (vp, [vp]),
+    "PTDenoiseMoments": (i32, [vp, C.POINTER(abi.PTDenoiseParams), vp, vp]),
+    "PTDenoiseMomentsToHost": (i32, [vp, C.POINTER(abi.PTDenoiseParams), vp, C.c_uint64]),
     "PTGetLastError": (C.c_char_p, []), "PTGetVersion": (i32, []),
 }
 EXPORTED_SYMBOLS = list(sig)
