@@ -607,6 +607,76 @@ PT_API int PTDenoiseMoments(PTContext* ctx, const PTDenoiseParams* params, const
 /* Denoises the frame last accumulated into host memory (width*height float4); synchronous. */
 PT_API int PTDenoiseMomentsToHost(PTContext* ctx, const PTDenoiseParams* params, float* dstRGBA, uint64_t dstFloats);
 
+/* =====================================================================================================================
+ * Part 7: adaptive sampling.  Passes over the ACTIVE 16x16 blocks of the frame only, every block with its own sample count.
+ * The stop criterion of Part 6 is global: the host pays for every pixel until the worst ones are good enough.  Here the
+ * blocks that still are noisy (the tile map of PTMeasureNoise) -- or any explicit list: a region of interest -- are
+ * rendered on, the rest of the frame moves on unchanged.
+ *
+ * A block is a 16x16 tile of the frame; its id is by * ceil(W/16) + bx, the indexing of the noise tile map.  The adaptive
+ * state holds one sample count n_b per block, on the host side of the context (allocated by PTAdaptiveBegin, dropped by
+ * PTAdaptiveEnd and PTDestroy; a context that never calls this part allocates nothing).
+ *
+ * The contract (bit-exact): PTRenderPassActive[To] renders `count` passes (1..8) of spp = max(1, SamplesPerPass) samples
+ * over the active blocks.  For an active block b and pass j, cs = n_b + j * spp, and every pixel of b is computed exactly as
+ * PTRenderPassTo computes it with CurrentSample = cs and RngSeedRoot = params[j].RngSeedRoot (the seed of a pixel is
+ * pixelIndex * (cs + 1) + seedRoot; the running mean (color + acc * cs) / (cs + spp), or color / spp when cs == 0), the
+ * passes applied in order, the intermediate frames never stored.  params[j].CurrentSample is not read.  Afterwards
+ * n_b += count * spp.  Every pixel that is not in an active block, not in a block this context owns (PTSetTileOwnership) or
+ * outside the dispatch coverage gets Output = Accumulated, bit for bit -- so ping-pong and PTFlipFrames work as before.
+ *  (a) every block active and all n_b equal: the frame of PTRenderPassBatch on the same params, bit for bit;
+ *  (b) in general: a per-block composite of the frames PTRenderPassTo gives for each distinct cs.
+ * Ordering and PTStats as for PTRenderPassBatchTo (one launch sequence on the next state set; passes in flight overlap):
+ * paths = active covered pixels x spp x count; the copy of the inactive pixels is not counted.  Sub-frames are not applied.
+ * An empty list enqueues only the copy.  dOutput == dAccumulated is refused; dAccumulated may be NULL only when every block is
+ * active and every n_b is 0.  Schedules 1, 2 and 3 (flat and HAS_TLAS); schedules 0 and 4 return PT_ERR_UNSUPPORTED.
+ *
+ * Moments: when PTAdaptiveBegin finds moments (Part 6) of the frame's size with samples == currentSample, every block
+ * starts with the global (k, W) and PTAccumulateMomentsActive[To] records ONE observation of the adaptive call just
+ * enqueued: the update of PTAccumulateMoments over that call's blocks, with f_b = (float)((double)n_b * (double)(n_b + m)
+ * / (double)m) per block (n_b before the call, m = count * spp), then k_b += 1, W_b += m.  An inactive pixel has
+ * Out - Acc == 0, so skipping it is exact.  While such state is live PTMeasureNoise, PTDenoiseMoments and
+ * PTDenoiseMomentsToHost use invDof_b = (float)(1.0 / ((double)(k_b - 1) * (double)W_b)) per block, PTNoiseStats.observations
+ * / samples (and PTGetMomentsInfo) report the minimum over the blocks this context owns, and PTAccumulateMoments (the global
+ * one) is refused.  Without moments at PTAdaptiveBegin the render calls work and the moments calls fail.
+ *
+ * Errors: PT_ERR_INVALID_ARG, with the offending numbers in PTGetLastError, for a call without PTAdaptiveBegin, params of
+ * another frame size, ids not strictly ascending or out of range, count outside 1..8, n_b + m past 2^32,
+ * PTAccumulateMoments while adaptive state is live, a short structSize.  Invalid input is refused before any launch.
+ * ===================================================================================================================== */
+typedef struct PTAdaptiveSelect {   /* 20 bytes */
+    uint32_t structSize;            /* = sizeof(PTAdaptiveSelect) of the host's header */
+    float    threshold;             /* a block is selected when its tile mean eps > threshold ... */
+    uint32_t maxSamples;            /* ... and n_b + addSamples <= maxSamples */
+    uint32_t addSamples;            /* what the next adaptive call will add per block (count * spp) */
+    uint32_t dilate;                /* 0 or 1: also the up to eight neighbours of a selected block that meet the sample limit */
+} PTAdaptiveSelect;
+
+#ifdef __cplusplus
+static_assert(sizeof(PTAdaptiveSelect) == 20, "PTAdaptiveSelect is 20 bytes");
+#else
+_Static_assert(sizeof(PTAdaptiveSelect) == 20, "PTAdaptiveSelect is 20 bytes");
+#endif
+
+/* Every block of the OutputWidth x OutputHeight frame of `params` holds currentSample samples; every block active. */
+PT_API int PTAdaptiveBegin(PTContext* ctx, const PTFrameParams* params, uint32_t currentSample);
+PT_API int PTAdaptiveEnd(PTContext* ctx);
+/* Strictly ascending block ids; NULL with count 0 = every block (a non-NULL pointer with count 0 = none).  Blocks of other
+ * ranks and blocks without a covered pixel are dropped silently; *kept (may be NULL) = how many remain. */
+PT_API int PTSetActiveBlocks(PTContext* ctx, const uint32_t* blocks, uint32_t count, uint32_t* kept);
+/* Selects on the host from the tile map of the last PTMeasureNoise (read back: synchronous) and the sample counts. */
+PT_API int PTSelectActiveBlocks(PTContext* ctx, const PTAdaptiveSelect* select, uint32_t* kept);
+/* The blocks the next adaptive call renders, ascending; dst may be NULL to ask for *count only. */
+PT_API int PTGetActiveBlocks(PTContext* ctx, uint32_t* dst, uint32_t capacity, uint32_t* count);
+/* n_b of every block of the frame, row-major: ceil(W/16) * ceil(H/16) values. */
+PT_API int PTGetBlockSamples(PTContext* ctx, uint32_t* dst, uint64_t capacity);
+/* params: an array of `count` PTFrameParams as for PTRenderPassBatchTo (may differ in RngSeedRoot only; CurrentSample ignored). */
+PT_API int PTRenderPassActive(PTContext* ctx, const PTFrameParams* params, int count);
+PT_API int PTRenderPassActiveTo(PTContext* ctx, const PTFrameParams* params, int count, void* dOutput, const void* dAccumulated);
+/* One observation for the blocks of the adaptive call just enqueued (same params[0] and count); before PTFlipFrames. */
+PT_API int PTAccumulateMomentsActive(PTContext* ctx, const PTFrameParams* params, int count);
+PT_API int PTAccumulateMomentsActiveTo(PTContext* ctx, const PTFrameParams* params, int count, const void* dOutput, const void* dAccumulated);
+
 /* Text of the last error on the calling thread ("" if none). */
 PT_API const char* PTGetLastError(void);
 /* Library/ABI version: (major << 16) | minor. */

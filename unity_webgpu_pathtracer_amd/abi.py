@@ -247,6 +247,21 @@ def noise_stats() -> PTNoiseStats:
     return st
 
 
+# ---------------------------------------------------------------------------------------
+# Part 7: adaptive sampling (PTAdaptiveBegin / PTSetActiveBlocks / PTRenderPassActive)
+# ---------------------------------------------------------------------------------------
+class PTAdaptiveSelect(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("threshold", C.c_float), ("maxSamples", C.c_uint32), ("addSamples", C.c_uint32),
+                ("dilate", C.c_uint32)]
+
+
+assert C.sizeof(PTAdaptiveSelect) == 20
+
+
+def adaptive_select(threshold: float, max_samples: int, add_samples: int, dilate: bool = True) -> PTAdaptiveSelect:
+    return PTAdaptiveSelect(C.sizeof(PTAdaptiveSelect), threshold, max_samples, add_samples, 1 if dilate else 0)
+
+
 def as_void_p(arr):
     """Borrowed host pointer of a C-contiguous numpy array (None -> NULL)."""
     if arr is None:

@@ -14,6 +14,8 @@ std::string dims(uint32_t w, uint32_t h) { return std::to_string(w) + "x" + std:
 int accumulate(PTContext* c, const PTFrameParams& p, int count, const void* dOut, const void* dAcc, int ownIndex, const char* who)
 {
     PTContext::Moments& M = c->moments;
+    if (c->adaptive.live)
+        return fail(PT_ERR_INVALID_ARG, std::string(who) + ": adaptive state is live, its blocks hold different sample counts (use PTAccumulateMomentsActive, or PTAdaptiveEnd first)");
     if (count < 1 || count > PT_MAX_BATCH)
         return fail(PT_ERR_INVALID_ARG, std::string(who) + ": count " + std::to_string(count) + " outside 1.." + std::to_string(PT_MAX_BATCH));
     if (!dOut) return fail(PT_ERR_INVALID_ARG, std::string(who) + ": output frame == NULL");
@@ -129,8 +131,13 @@ PT_API int PTMeasureNoise(PTContext* c, const PTNoiseParams* params, const void*
         (rc = M.tiles.reserve(blocks * sizeof(float), c->stream)))
         return rc;
     HIP_TRY(hipMemsetAsync(M.stats.ptr, 0, PT_NOISE_WORDS * sizeof(uint32_t), c->stream));
+    // adaptive state of this size: one 1 / ((k_b - 1) W_b) per block, and the statistics name the least converged owned block
+    const float* blockInvDof;
+    uint32_t observations;
+    uint64_t samples;
+    if ((rc = adaptive_inv_dof(c, &blockInvDof, &observations, &samples))) return rc;
     const PTNoiseArgs A = {W, H, (uint32_t)c->rank, (uint32_t)(c->world > 1 ? c->world : 1), inv_dof(c), params->relFloor, params->threshold};
-    HIP_TRY(pt_launch_noise(A, (const float4*)dFrame, M.planes.f4(0), (uint32_t*)M.stats.ptr, (float*)M.blockSums.ptr, (float*)M.tiles.ptr, c->stream));
+    HIP_TRY(pt_launch_noise(A, (const float4*)dFrame, M.planes.f4(0), (uint32_t*)M.stats.ptr, (float*)M.blockSums.ptr, (float*)M.tiles.ptr, c->stream, blockInvDof));
     uint32_t words[PT_NOISE_WORDS];
     HIP_TRY(hipMemcpyAsync(words, M.stats.ptr, sizeof(words), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -138,8 +145,8 @@ PT_API int PTMeasureNoise(PTContext* c, const PTNoiseParams* params, const void*
     PTNoiseStats s;
     memset(&s, 0, sizeof(s));
     s.structSize = (uint32_t)sizeof(s);
-    s.observations = M.observations;
-    s.samples = M.samples;
+    s.observations = observations;
+    s.samples = samples;
     for (int b = 0; b < 256; ++b) { s.histogram[b] = words[b]; s.pixels += words[b]; }
     s.pixelsBelow = words[PT_NOISE_BELOW];
     float sum;
@@ -176,7 +183,10 @@ PT_API int PTDenoiseMoments(PTContext* c, const PTDenoiseParams* params, const v
     if (guides.w != M.planes.w || guides.h != M.planes.h)
         return fail(PT_ERR_INVALID_ARG, "PTDenoiseMoments: the guides are " + dims(guides.w, guides.h) + ", the moments " + dims(M.planes.w, M.planes.h));
     if (!dSrc && !(dSrc = last_frame(c, "PTDenoiseMoments"))) return PT_ERR_INVALID_ARG;
-    const PTDenoiseVariance V = {M.planes.f4(0), M.planes.f4(1), inv_dof(c)};
+    PTDenoiseVariance V = {M.planes.f4(0), M.planes.f4(1), inv_dof(c)};
+    uint32_t observations;
+    uint64_t samples;
+    if (int rc = adaptive_inv_dof(c, &V.blockInvDof, &observations, &samples)) return rc;
     return denoise_frame(c, params, dSrc, dDst, &V);
 }
 

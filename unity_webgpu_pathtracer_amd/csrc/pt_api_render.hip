@@ -1,8 +1,6 @@
 // pt_api_render.hip — passes, batches, the ping-pong frames, presentation and readback (include/ptmi_plugin.h Part 2).
 #include "pt_context.h"
 
-namespace {
-
 int ensure_frames(PTContext* c, uint32_t w, uint32_t h)
 {
     if (c->frames.w == w && c->frames.h == h) return PT_OK;
@@ -38,6 +36,8 @@ int ensure_wavefront(PTContext* c, PTContext::WfSet& set, uint32_t numSlots, uin
     return PT_OK;
 }
 
+namespace {
+
 // p: imported and validated (import_frame_params).
 // `batch`: the passes a launch sequence renders together (count >= 1; batch.seedRoot[0] / currentSample[0] = those of p)
 int render_to(PTContext* c, const PTFrameParams& params, float4* dOut, const float4* dAcc, const PTBatch* hostBatch = nullptr)
@@ -56,11 +56,7 @@ int render_to(PTContext* c, const PTFrameParams& params, float4* dOut, const flo
     const PTTileMap tm = pt_make_tile_map(*p, c->rank, c->world);
 
     EventPair ep;
-    if (c->profiling) {
-        if (c->pending.size() >= 4096) { rc = drain_events(c); if (rc) return rc; }
-        if (!c->freeEvents.empty()) { ep = std::move(c->freeEvents.back()); c->freeEvents.pop_back(); }
-        else if ((rc = create(ep.start, hipEventDefault)) || (rc = create(ep.stop, hipEventDefault))) return rc;
-    }
+    if (c->profiling && (rc = take_event_pair(c, ep))) return rc;
     uint32_t launches = 0;
     const int schedule = effective_schedule(c);
     switch (schedule) {
@@ -159,17 +155,20 @@ PT_API int PTRenderPassTo(PTContext* c, const PTFrameParams* hostParams, void* d
     return render_to(c, p, (float4*)dOutput, (const float4*)dAccumulated);
 }
 
-PT_API int PTRenderPassBatchTo(PTContext* c, const PTFrameParams* hostParams, int count, void* dOutput, const void* dAccumulated)
+} // extern "C"
+
+// The params array of a batch (PTRenderPassBatchTo, PTRenderPassActiveTo): `first` = pass 0 imported and validated, batch = every
+// pass's RngSeedRoot and CurrentSample; the passes may differ in nothing else.
+int import_batch(const PTFrameParams* hostParams, int count, PTFrameParams& first, PTBatch& batch)
 {
-    if (!c || !hostParams) return fail(PT_ERR_INVALID_ARG, "ctx/params == NULL");
     if (count < 1 || count > PT_MAX_BATCH) return fail(PT_ERR_INVALID_ARG, "count outside 1.." + std::to_string(PT_MAX_BATCH));
     // the host's array has the stride of ITS header (structSize of the first element)
     const uint32_t stride = hostParams->structSize;
     if (stride < PT_FRAME_PARAMS_MIN_SIZE || stride > 4096u) return fail(PT_ERR_INVALID_ARG, "PTFrameParams.structSize is not set");
-    PTFrameParams first, other;
+    PTFrameParams other;
     int rc = import_struct(hostParams, first, PT_FRAME_PARAMS_MIN_SIZE, "PTFrameParams", "params == NULL");
     if (rc) return rc;
-    PTBatch batch = {};
+    batch = PTBatch{};
     batch.count = (uint32_t)count;
     for (int j = 0; j < count; ++j) {
         const PTFrameParams* hp = (const PTFrameParams*)((const char*)hostParams + (size_t)j * stride);
@@ -182,7 +181,27 @@ PT_API int PTRenderPassBatchTo(PTContext* c, const PTFrameParams* hostParams, in
         if (memcmp(&other, &first, sizeof(first)) != 0)
             return fail(PT_ERR_INVALID_ARG, "the passes of a batch may differ in RngSeedRoot and CurrentSample only (pass " + std::to_string(j) + " differs elsewhere)");
     }
-    if ((rc = validate_params(first))) return rc;
+    return validate_params(first);
+}
+
+int take_event_pair(PTContext* c, EventPair& ep)
+{
+    int rc;
+    if (c->pending.size() >= 4096) { rc = drain_events(c); if (rc) return rc; }
+    if (!c->freeEvents.empty()) { ep = std::move(c->freeEvents.back()); c->freeEvents.pop_back(); }
+    else if ((rc = create(ep.start, hipEventDefault)) || (rc = create(ep.stop, hipEventDefault))) return rc;
+    return PT_OK;
+}
+
+extern "C" {
+
+PT_API int PTRenderPassBatchTo(PTContext* c, const PTFrameParams* hostParams, int count, void* dOutput, const void* dAccumulated)
+{
+    if (!c || !hostParams) return fail(PT_ERR_INVALID_ARG, "ctx/params == NULL");
+    PTFrameParams first;
+    PTBatch batch = {};
+    int rc = import_batch(hostParams, count, first, batch);
+    if (rc) return rc;
     if (count == 1) return render_to(c, first, (float4*)dOutput, (const float4*)dAccumulated);
     if (effective_schedule(c) == 0) {
         // the megakernel writes pixels itself: run the passes one by one, ping-ponging between dOutput and a scratch frame so that the

@@ -106,6 +106,33 @@ struct FrameSet {
     }
 };
 
+// A small table the host rewrites per call and kernels read in stream order: a ring of pinned staging buffers and one device
+// copy.  send() only waits for the upload made kRing sends ago to have left its staging buffer (an event recorded right behind
+// that copy), never for kernels -- on a stream that sits behind the resolves of passes in flight a single buffer would make
+// the host wait for the previous pass.
+struct UploadTable {
+    static constexpr int kRing = 4;
+    DeviceBuffer dev;
+    PinnedBuffer host[kRing];
+    Event copied[kRing];
+    bool recorded[kRing] = {};
+    int next = 0;
+    int send(const void* src, size_t bytes, hipStream_t stream)
+    {
+        const int k = next;
+        next = (next + 1) % kRing;
+        if (int rc = create(copied[k])) return rc;
+        if (recorded[k]) HIP_TRY(hipEventSynchronize(copied[k]));
+        if (int rc = host[k].reserve(bytes)) return rc;
+        if (int rc = dev.reserve(bytes, stream)) return rc;         // growing: kernels that read the old copy ran on this stream
+        memcpy(host[k].ptr, src, bytes);
+        HIP_TRY(hipMemcpyAsync(dev.ptr, host[k].ptr, bytes, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipEventRecord(copied[k], stream));
+        recorded[k] = true;
+        return PT_OK;
+    }
+};
+
 struct EventPair { Event start, stop; uint32_t launches = 0; };
 
 struct PTContext {
@@ -132,6 +159,7 @@ struct PTContext {
         DeviceBuffer arena;
         Stream stream;
         Event callEv, done;
+        UploadTable blockTable;                 // PTRenderPassActive: the call's {block id, sample count} snapshot (pt_launch.h PTListMap)
     } sets[PT_WF_SETS];
     uint32_t nextSet = 0;
     uint32_t residentWaves = 0;                 // CUs x 4 SIMDs x 8 waves (device property, read once)
@@ -166,6 +194,23 @@ struct PTContext {
         const void* lastPtr = nullptr;
         DeviceBuffer stats, blockSums, tiles;   // PTMeasureNoise: PT_NOISE_WORDS words, one float per 16x16 block each
     } moments;
+    // adaptive sampling (include/ptmi_plugin.h Part 7): per-block sample counts and the active list, on the host; empty until PTAdaptiveBegin
+    struct Adaptive {
+        bool live = false;
+        uint32_t w = 0, h = 0, blocksX = 0, blocksY = 0;
+        uint32_t coverW = 0, coverH = 0;        // dispatch coverage of PTAdaptiveBegin's params (pt_make_tile_map)
+        std::vector<uint32_t> samples;          // n_b, one per block of the frame
+        bool allActive = true;                  // PTSetActiveBlocks(NULL, 0): every block (the state after PTAdaptiveBegin)
+        std::vector<uint32_t> active;           // as given to PTSetActiveBlocks (ascending), when !allActive
+        // moments per block (PTAccumulateMomentsActive); tracked only when PTAdaptiveBegin found moments that match
+        bool moments = false;
+        std::vector<uint32_t> obs;              // k_b
+        std::vector<uint64_t> wsum;             // W_b
+        // the adaptive call last enqueued: what PTAccumulateMomentsActive describes
+        std::vector<uint2> lastTable;           // {block id, n_b at the start of the call}
+        uint32_t lastM = 0;                     // samples the call added per block; 0 = none pending
+        UploadTable momentsTable, invDof;       // on the context stream
+    } adaptive;
     // scene updates (PTUpdateInstances / Lights / Materials): two generations of what an update rewrites, allocated on the first
     // update of each kind and discarded by PTSetScene.  cur = -1 while PTSetScene's own buffers are current.
     struct UpdGroup {
@@ -248,3 +293,11 @@ constexpr int kTextureSlots[4] = {22, 23, 25, 26};
 int denoise_frame(PTContext* c, const PTDenoiseParams* params, const void* dSrc, void* dDst, const PTDenoiseVariance* variance);
 int set_scene(PTContext* c, const PTSceneDesc* hostScene, bool validate);      // pt_api_context.hip; PTGroupSetScene validates once
 int drain_events(PTContext* c);                                                 // pt_api_context.hip
+int ensure_frames(PTContext* c, uint32_t w, uint32_t h);                        // pt_api_render.hip
+int import_batch(const PTFrameParams* hostParams, int count, PTFrameParams& first, PTBatch& batch);      // pt_api_render.hip
+int take_event_pair(PTContext* c, EventPair& ep);                               // pt_api_render.hip: a start / stop pair for a profiled pass
+int ensure_wavefront(PTContext* c, PTContext::WfSet& set, uint32_t numSlots, uint32_t maxIterations);      // pt_api_render.hip
+// pt_api_adaptive.hip: the per-block 1 / ((k_b - 1) W_b) table on the device while adaptive state of the moments' size tracks
+// moments, else NULL (rc != PT_OK on a failed upload); minObs / minSamples: the minimum over the blocks this context owns
+// table == NULL: only the minima, nothing is uploaded
+int adaptive_inv_dof(PTContext* c, const float** table, uint32_t* minObs, uint64_t* minSamples);

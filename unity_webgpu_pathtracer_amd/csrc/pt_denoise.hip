@@ -265,15 +265,17 @@ extern "C" __global__ __launch_bounds__(256) void pt_denoise_prepass_moments(PTD
     }
     const bool demod = (A.flags & PT_DENOISE_DEMODULATE_ALBEDO) != 0u;
     const float4 s0 = V.plane0[p];
+    // adaptive sampling: every 16x16 block has its own observation and sample counts
+    const float invDof = V.blockInvDof ? V.blockInvDof[(size_t)(y >> 4) * (size_t)((W + 15) >> 4) + (size_t)(x >> 4)] : V.invDof;
     float var;
     if (demod) {
         const float4 s1 = V.plane1[p];
         const float qr = 0.2126f / pt_max(a.x, 1e-3f), qg = 0.7152f / pt_max(a.y, 1e-3f), qb = 0.0722f / pt_max(a.z, 1e-3f);
         const float diag = (qr * qr) * s0.x + (qg * qg) * s0.y + (qb * qb) * s0.z;
         const float cross = (qr * qg) * s1.x + (qr * qb) * s1.y + (qg * qb) * s1.z;
-        var = pt_max((diag + 2.0f * cross) * V.invDof, 0.0f);
+        var = pt_max((diag + 2.0f * cross) * invDof, 0.0f);
     } else {
-        var = pt_max(s0.w * V.invDof, 0.0f);
+        var = pt_max(s0.w * invDof, 0.0f);
     }
     const float4 e = dn_demod(src[p], a, demod);
     state[p] = make_float4(e.x, e.y, e.z, var);

@@ -87,6 +87,7 @@ struct PTDenoiseVariance {
     const float4* plane0;
     const float4* plane1;
     float invDof;
+    const float* blockInvDof = nullptr;      // NULL = invDof everywhere; else one value per 16x16 block (row-major, ceil(width/16) per row)
 };
 // iterations >= 1 levels: prepass, one launch per level, remodulation (iterations + 2 launches); every buffer width*height.
 // variance == nullptr: the 3x3 spatial variance of PTDenoise; else the variance of the mean from the moments (PTDenoiseMoments)
@@ -98,6 +99,9 @@ hipError_t pt_launch_denoise(const PTDenoiseArgs& A, int iterations, const float
 // plane0 / plane1 += the Welford term of (out - acc) times f, per pixel (include/ptmi_plugin.h Part 6)
 hipError_t pt_launch_moments_accumulate(uint32_t pixels, float f, const float4* out, const float4* acc, float4* plane0,
                                         float4* plane1, hipStream_t stream);
+// the same update over the listed 16x16 blocks only: entry e = {block id = by * ceil(width/16) + bx, the bits of the block's f}
+hipError_t pt_launch_moments_accumulate_blocks(uint32_t entries, const uint2* table, uint32_t width, uint32_t height, const float4* out,
+                                               const float4* acc, float4* plane0, float4* plane1, hipStream_t stream);
 // words of the statistics buffer: 256 histogram bins, then the maximum's bits, pixelsBelow, the sum of eps (float bits)
 enum : uint32_t { PT_NOISE_MAX = 256, PT_NOISE_BELOW, PT_NOISE_SUM, PT_NOISE_WORDS };
 struct PTNoiseArgs {
@@ -105,9 +109,10 @@ struct PTNoiseArgs {
     uint32_t rank, world;           // block (bx, by) is counted when (bx + by) % world == rank
     float invDof, relFloor, threshold;
 };
-// stats: PT_NOISE_WORDS zeroed words; blockSums / tiles: ceil(width/16) * ceil(height/16) floats each
+// stats: PT_NOISE_WORDS zeroed words; blockSums / tiles: ceil(width/16) * ceil(height/16) floats each.
+// blockInvDof: NULL = A.invDof everywhere; else one value per 16x16 block of the tile map (adaptive sampling)
 hipError_t pt_launch_noise(const PTNoiseArgs& A, const float4* frame, const float4* plane0, uint32_t* stats, float* blockSums,
-                           float* tiles, hipStream_t stream);
+                           float* tiles, hipStream_t stream, const float* blockInvDof = nullptr);
 
 // ---- schedule 1 (wavefront): slot-indexed path state in HBM (see pt_wavefront.hip) ----
 // float4 arrays of a state set, in carving order.  PT_F4_RAY0/1/2 are the RAY RECORDS of the three ray kinds a slot can have in
@@ -211,6 +216,33 @@ typedef hipError_t PTWfLauncher(const DScene& S, const PTFrameParams& P, const P
                                 hipStream_t stream, hipEvent_t orderAfter, bool zeroOutputFirst,
                                 uint32_t* launchesOut, int traceVariant, uint32_t iterationsOverride);
 PTWfLauncher pt_launch_wavefront, pt_launch_wavefront_b;
+
+// ---- adaptive passes (include/ptmi_plugin.h Part 7): a pass over a LIST of 16x16 blocks, each with its own sample count ----
+// Slot s of pass j is j * slotsPerPass + e * 256 + tid with slotsPerPass = entries * 256; entry e of the per-call table is
+// {block id = by * frameBlocksX + bx, the block's sample count at the start of the call}.  Inside a block the lanes are laid
+// out as by pt_slot_to_pixel (four 8x8 waves).  The kernels of one call read only this snapshot (uploaded on the set's stream
+// before the init kernel): a later call's init may run while this call's resolve is still pending.
+struct PTListMap {
+    uint32_t frameBlocksX;         // ceil(OutputWidth / 16)
+    uint32_t coverW, coverH;       // pixels with x < coverW && y < coverH are rendered (pt_make_tile_map)
+    const uint2* table;
+};
+__host__ __device__ inline bool pt_list_slot_to_pixel(uint32_t frameBlocksX, uint32_t coverW, uint32_t coverH, uint32_t blockId, uint32_t tid,
+                                                      uint32_t& px, uint32_t& py)
+{
+    const uint32_t by = blockId / frameBlocksX, bx = blockId - by * frameBlocksX;
+    const uint32_t wave = tid >> 6, lane = tid & 63u;
+    px = bx * 16u + (wave & 1u) * 8u + (lane & 7u);
+    py = by * 16u + (wave >> 1) * 8u + (lane >> 3);
+    return px < coverW && py < coverH;
+}
+// The launch sequence of pt_launch_wavefront over the list: batch.currentSample is not read (pass j of entry e renders with
+// CurrentSample = table[e].y + j * spp), the whole frame is copied from `accumulated` to `output` before the resolve (when
+// accumulated != NULL), schedule 4 (traceVariant 4) is not available.
+typedef hipError_t PTWfListLauncher(const DScene& S, const PTFrameParams& P, const PTBatch& batch, const float4* accumulated, float4* output,
+                                    const PTListMap& lm, const PTWfBuffers& B, unsigned long long* gstats, bool fullStats,
+                                    hipStream_t stream, hipEvent_t orderAfter, uint32_t* launchesOut, int traceVariant, uint32_t iterationsOverride);
+PTWfListLauncher pt_launch_wavefront_list, pt_launch_wavefront_list_b;
 #ifndef PT_WF_FUSED_GROUPS
 #define PT_WF_FUSED_GROUPS 2u   // schedule 4: groups of 64 path contexts a persistent wave owns (power of two <= 4: numSlots is a multiple of 256).
                                 // Sponza-class 1080p / 8 spp, one pass in flight: 1: 29.9 ms, 2: 25.2, 4: 27.9, 8: 31.4

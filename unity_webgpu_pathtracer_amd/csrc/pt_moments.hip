@@ -33,9 +33,33 @@ extern "C" __global__ __launch_bounds__(256) void pt_moments_accumulate(uint32_t
     plane1[p] = make_float4(s1.x, s1.y, s1.z, 0.0f);
 }
 
+// The same update over a list of 16x16 blocks (PTAccumulateMomentsActive): workgroup e takes table entry e = {block id, bits of the
+// block's f}; a pixel outside the list has Out == Acc, so skipping it is exact and the traffic follows the listed area.
+extern "C" __global__ __launch_bounds__(256) void pt_moments_accumulate_blocks(const uint2* __restrict__ table, uint32_t width, uint32_t height,
+                                                                               const float4* __restrict__ out, const float4* __restrict__ acc,
+                                                                               float4* __restrict__ plane0, float4* __restrict__ plane1)
+{
+    const uint2 entry = table[blockIdx.x];
+    const uint32_t blocksX = (width + 15u) / 16u;
+    const uint32_t by = entry.x / blocksX, bx = entry.x - by * blocksX;
+    const uint32_t x = bx * 16u + (threadIdx.x & 15u), y = by * 16u + (threadIdx.x >> 4);
+    if (x >= width || y >= height) return;
+    const float f = __uint_as_float(entry.y);
+    const size_t p = (size_t)y * width + x;
+    const float4 o = out[p], a = acc[p];
+    const float dr = o.x - a.x, dg = o.y - a.y, db = o.z - a.z;
+    const float dl = mo_lum(dr, dg, db);
+    float4 s0 = plane0[p], s1 = plane1[p];
+    s0.x += (dr * dr) * f; s0.y += (dg * dg) * f; s0.z += (db * db) * f; s0.w += (dl * dl) * f;
+    s1.x += (dr * dg) * f; s1.y += (dr * db) * f; s1.z += (dg * db) * f;
+    plane0[p] = s0;
+    plane1[p] = make_float4(s1.x, s1.y, s1.z, 0.0f);
+}
+
 extern "C" __global__ __launch_bounds__(256) void pt_noise_blocks(PTNoiseArgs A, const float4* __restrict__ frame,
                                                                   const float4* __restrict__ plane0, uint32_t* __restrict__ stats,
-                                                                  float* __restrict__ blockSums, float* __restrict__ tiles)
+                                                                  float* __restrict__ blockSums, float* __restrict__ tiles,
+                                                                  const float* __restrict__ blockInvDof)
 {
     __shared__ uint32_t s_hist[256];
     __shared__ float s_part[4];
@@ -51,13 +75,14 @@ extern "C" __global__ __launch_bounds__(256) void pt_noise_blocks(PTNoiseArgs A,
     __syncthreads();
     const uint32_t x = blockIdx.x * 16u + (t & 15u), y = blockIdx.y * 16u + (t >> 4);
     const bool inside = x < A.width && y < A.height;
+    const float invDof = blockInvDof ? blockInvDof[block] : A.invDof;      // one workgroup is one block: uniform
     float eps = 0.0f;
     if (inside) {
         const size_t p = (size_t)y * A.width + x;
         const float4 c = frame[p];
         const float sll = plane0[p].w;
         const float l = mo_lum(c.x, c.y, c.z);
-        eps = __builtin_sqrtf(sll * A.invDof) / (l + A.relFloor);
+        eps = __builtin_sqrtf(sll * invDof) / (l + A.relFloor);
         if (!(eps >= 0.0f)) eps = __builtin_inff();                 // NaN or negative
         const uint32_t bits = __float_as_uint(eps) & 0x7FFFFFFFu;   // -0 counts as 0
         eps = __uint_as_float(bits);
@@ -114,11 +139,19 @@ hipError_t pt_launch_moments_accumulate(uint32_t pixels, float f, const float4* 
     return hipGetLastError();
 }
 
+hipError_t pt_launch_moments_accumulate_blocks(uint32_t entries, const uint2* table, uint32_t width, uint32_t height, const float4* out,
+                                               const float4* acc, float4* plane0, float4* plane1, hipStream_t stream)
+{
+    if (entries == 0u) return hipSuccess;
+    hipLaunchKernelGGL(pt_moments_accumulate_blocks, dim3(entries), dim3(256), 0, stream, table, width, height, out, acc, plane0, plane1);
+    return hipGetLastError();
+}
+
 hipError_t pt_launch_noise(const PTNoiseArgs& A, const float4* frame, const float4* plane0, uint32_t* stats, float* blockSums,
-                           float* tiles, hipStream_t stream)
+                           float* tiles, hipStream_t stream, const float* blockInvDof)
 {
     const dim3 grid((A.width + 15u) / 16u, (A.height + 15u) / 16u);
-    hipLaunchKernelGGL(pt_noise_blocks, grid, dim3(256), 0, stream, A, frame, plane0, stats, blockSums, tiles);
+    hipLaunchKernelGGL(pt_noise_blocks, grid, dim3(256), 0, stream, A, frame, plane0, stats, blockSums, tiles, blockInvDof);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(pt_noise_finish, dim3(1), dim3(256), 0, stream, grid.x * grid.y, blockSums, stats);

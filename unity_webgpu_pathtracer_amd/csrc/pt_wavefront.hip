@@ -103,18 +103,39 @@ PT_DEV uint32_t pixel_slot_of(const PTWfBuffers& B, uint32_t slot, uint32_t& pas
     return slot;
 }
 
-__global__ __launch_bounds__(256) void pt_wf_init(PTFrameParams P, PTBatch batch, PTTileMap tm, PTWfBuffers B)
+// The pixel and the pass of a slot under the two mappings a kernel can be instantiated with (MAP): PTTileMap, the frame's owned
+// blocks in their fixed order (every PTRenderPass* path), and PTListMap, the blocks of a per-call table (PTRenderPassActive).
+// wgSlot is the first slot of the lane's workgroup -- formed from blockIdx, hence wave-uniform: under the list mapping the
+// table entry is ONE scalar load per wave (SGPRs, not VGPRs; the shade kernel sits on its 128-VGPR line).  A workgroup never
+// straddles two entries or two passes (64 or 256 slots, entries of 256).  base = the block's sample count when the call began.
+PT_DEV bool wf_pixel(const PTTileMap& tm, const PTWfBuffers& B, uint32_t slot, uint32_t wgSlot, uint32_t& px, uint32_t& py, uint32_t& pass, uint32_t& base)
+{
+    base = 0u;
+    return pt_slot_to_pixel(tm, pixel_slot_of(B, slot, pass), px, py);
+}
+PT_DEV bool wf_pixel(const PTListMap& lm, const PTWfBuffers& B, uint32_t slot, uint32_t wgSlot, uint32_t& px, uint32_t& py, uint32_t& pass, uint32_t& base)
+{
+    pass = wgSlot / B.slotsPerPass;
+    const uint2 entry = lm.table[(wgSlot - pass * B.slotsPerPass) >> 8];
+    base = entry.y;
+    return pt_list_slot_to_pixel(lm.frameBlocksX, lm.coverW, lm.coverH, entry.x, slot & 255u, px, py);
+}
+template <class MAP> constexpr bool kListMap = std::is_same<MAP, PTListMap>::value;
+
+template <class MAP = PTTileMap>
+__global__ __launch_bounds__(256) void pt_wf_init(PTFrameParams P, PTBatch batch, MAP tm, PTWfBuffers B)
 {
     const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
     if (blockIdx.x == 0u && threadIdx.x < PT_WF_SHARDS) B.chunkHeads[threadIdx.x * 32u] = 0u;
     if (slot >= B.numSlots) return;
-    uint32_t px, py, pass;
+    uint32_t px, py, pass, base;
     Counters cn = {};
-    if (!pt_slot_to_pixel(tm, pixel_slot_of(B, slot, pass), px, py)) B.flags[slot] = PS_DONE;
+    if (!wf_pixel(tm, B, slot, blockIdx.x * 256u, px, py, pass, base)) B.flags[slot] = PS_DONE;
     else {
         PathRegs r;
         uint32_t seedRoot, currentSample;
         pt_batch_pick(batch, pass, seedRoot, currentSample);
+        if (kListMap<MAP>) currentSample = base + pass * (P.SamplesPerPass > 1 ? (uint32_t)P.SamplesPerPass : 1u);
         path_init(P, seedRoot, currentSample, px, py, py * P.OutputWidth + px, r, cn);
         store_path(B, slot, r, false);
     }
@@ -881,12 +902,13 @@ PT_DEV void load_path(const PTWfBuffers& B, uint32_t slot, uint32_t f, PathRegs&
 // `slot` indexes the path-state arrays; `pixelSlot` is the pixel the state belongs to (the same number in schedules 1-3, where
 // every pixel has its own slot; a context's current pixel in schedule 4, which also wants the finished pixel's sample sum in
 // B.pixsum[pixelSlot]: PIXSUM).
-template <bool STATS, bool PIXSUM = false>
-PT_DEV bool shade_slot(const DScene& S, const PTFrameParams& P, const PTTileMap& tm, const PTWfBuffers& B, uint32_t slot, uint32_t pixelSlot,
-                       uint32_t f, Counters& cn)
+// wgSlot: see wf_pixel (only read under the list mapping).
+template <bool STATS, bool PIXSUM = false, class MAP = PTTileMap>
+PT_DEV bool shade_slot(const DScene& S, const PTFrameParams& P, const MAP& tm, const PTWfBuffers& B, uint32_t slot, uint32_t pixelSlot,
+                       uint32_t f, Counters& cn, uint32_t wgSlot = 0u)
 {
-    uint32_t px, py, pass;
-    pt_slot_to_pixel(tm, pixel_slot_of(B, pixelSlot, pass), px, py);
+    uint32_t px, py, pass, base;
+    wf_pixel(tm, B, pixelSlot, wgSlot, px, py, pass, base);
     uint32_t rng = B.rng[slot];
     float4 qro = B.ray[0][2u * slot], qrd = B.ray[0][2u * slot + 1u], qrad = B.rad[slot], qthr = B.thr[slot], qcol = B.color[slot];
     float4 qenvC = B.envC[slot], qlightC = B.lightC[slot], qpthr = B.pthr[slot], qhit = B.hit[slot];
@@ -955,8 +977,8 @@ PT_DEV bool shade_slot(const DScene& S, const PTFrameParams& P, const PTTileMap&
 #ifndef PT_WF_SHADE_BLOCK
 #define PT_WF_SHADE_BLOCK 64u          // one wave per workgroup: a finished wave frees its 128 VGPRs at once (256 -> 64: +4 %)
 #endif
-template <bool STATS>
-__global__ __launch_bounds__(PT_WF_SHADE_BLOCK, PT_WF_SHADE_MIN_WAVES) void pt_wf_shade(DScene S, PTFrameParams P, PTTileMap tm, PTWfBuffers B,
+template <bool STATS, class MAP = PTTileMap>
+__global__ __launch_bounds__(PT_WF_SHADE_BLOCK, PT_WF_SHADE_MIN_WAVES) void pt_wf_shade(DScene S, PTFrameParams P, MAP tm, PTWfBuffers B,
                                                                          uint32_t iteration)
 {
     const uint32_t vb = blockIdx.x;
@@ -964,7 +986,7 @@ __global__ __launch_bounds__(PT_WF_SHADE_BLOCK, PT_WF_SHADE_MIN_WAVES) void pt_w
     if (vb == 0u && threadIdx.x < PT_WF_SHARDS) B.chunkHeads[threadIdx.x * 32u] = 0u;   // for the next trace launch (schedule 3)
     const uint32_t f = B.flags[slot];
     Counters cn = {};
-    if (fl_state(f) != PS_DONE) shade_slot<STATS>(S, P, tm, B, slot, slot, f, cn);
+    if (fl_state(f) != PS_DONE) shade_slot<STATS, false, MAP>(S, P, tm, B, slot, slot, f, cn, vb * PT_WF_SHADE_BLOCK);
     flush_counters<STATS>(cn, B.statRows, vb * (PT_WF_SHADE_BLOCK / 64u) + (threadIdx.x >> 6), threadIdx.x & 63u);
 }
 
@@ -1261,8 +1283,8 @@ __global__ __launch_bounds__(64, PT_WF_FUSED_WAVES) void pt_wf_fused(DScene S, P
 
 // cleanup: pixels still alive after the fixed number of iterations are run to completion here, one lane per slot with
 // the megakernel's loop (trace <= 3 rays, path_step, repeat).  Normally a handful of lanes; correctness for any path length.
-template <bool STATS, bool TLAS>
-__global__ __launch_bounds__(256, 2) void pt_wf_cleanup(DScene S, PTFrameParams P, PTTileMap tm, PTWfBuffers B)
+template <bool STATS, bool TLAS, class MAP = PTTileMap>
+__global__ __launch_bounds__(256, 2) void pt_wf_cleanup(DScene S, PTFrameParams P, MAP tm, PTWfBuffers B)
 {
     __shared__ uint2 s_stack[PT_LDS_STACK][256];
     Counters cn = {};
@@ -1273,8 +1295,8 @@ __global__ __launch_bounds__(256, 2) void pt_wf_cleanup(DScene S, PTFrameParams 
     const uint32_t f = B.flags[slot];
     if (__any(fl_state(f) != PS_DONE)) {
         if (fl_state(f) != PS_DONE) {
-            uint32_t px, py, pass;
-            pt_slot_to_pixel(tm, pixel_slot_of(B, slot, pass), px, py);
+            uint32_t px, py, pass, base;
+            wf_pixel(tm, B, slot, blk * 256u, px, py, pass, base);
             PathRegs r;
             load_path(B, slot, f, r);
             if (r.hasPending) {
@@ -1335,6 +1357,42 @@ __global__ __launch_bounds__(256) void pt_wf_resolve(PTFrameParams P, PTBatch ba
             uint32_t seedRoot, currentSample;
             pt_batch_pick(batch, j, seedRoot, currentSample);
             const v3 color = xyz(sums[(size_t)j * B.slotsPerPass + slot]);      // per-pixel sample sum: B.color (schedules 1-3) or B.pixsum (schedule 4)
+            if (currentSample > 0u) {
+                if (j == 0u) {
+                    const float4 a = accumulated[pixelIndex];
+                    acc = mk3(a.x, a.y, a.z);
+                }
+                cn.pixelsRead++;
+                const float cs = (float)currentSample;
+                acc = (color + acc * cs) / (cs + fSamples);
+            } else {
+                acc = color / fSamples;
+            }
+            cn.pixelsWritten++;
+        }
+        output[pixelIndex] = make_float4(acc.x, acc.y, acc.z, 1.0f);
+    }
+    flush_counters<false>(cn, B.statRows, blockIdx.x * 4u + (threadIdx.x >> 6), threadIdx.x & 63u);
+}
+
+// resolve of a pass over a block list: workgroup e writes the covered pixels of table entry e with the block's own sample count
+// (the same chain of fp32 operations as pt_wf_resolve with CurrentSample = n_b + j * spp).  Every other pixel of `output` was
+// copied from `accumulated` by the launcher.
+__global__ __launch_bounds__(256) void pt_wf_resolve_list(PTFrameParams P, PTBatch batch, PTListMap lm, PTWfBuffers B, const float4* __restrict__ sums,
+                                                          const float4* __restrict__ accumulated, float4* __restrict__ output)
+{
+    const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
+    uint32_t px, py;
+    Counters cn = {};
+    const uint2 entry = lm.table[blockIdx.x];
+    if (pt_list_slot_to_pixel(lm.frameBlocksX, lm.coverW, lm.coverH, entry.x, threadIdx.x, px, py)) {
+        const uint32_t pixelIndex = py * P.OutputWidth + px;
+        const uint32_t numSamples = P.SamplesPerPass > 1 ? (uint32_t)P.SamplesPerPass : 1u;
+        const float fSamples = (float)numSamples;
+        v3 acc = mk3(0.0f);
+        for (uint32_t j = 0; j < batch.count; ++j) {
+            const uint32_t currentSample = entry.y + j * numSamples;
+            const v3 color = xyz(sums[(size_t)j * B.slotsPerPass + slot]);
             if (currentSample > 0u) {
                 if (j == 0u) {
                     const float4 a = accumulated[pixelIndex];
@@ -1428,16 +1486,21 @@ PTWfBuffers pt_wf_arena_carve(void* base, uint32_t numSlots, uint32_t residentWa
     return B;
 }
 #define pt_launch_wavefront pt_launch_wavefront_b
+#define pt_launch_wavefront_list pt_launch_wavefront_list_b
 #endif
 
 // One pass = a fixed sequence of launches on `stream`, no host synchronisation (see the file header).
 // `orderAfter` (may be null) is the event of the previous pass's resolve: this pass's resolve reads that pass's output as
 // AccumulatedOutput and, with ping-pong frames, overwrites the frame that resolve was still reading.
-hipError_t pt_launch_wavefront(const DScene& S, const PTFrameParams& P, const PTBatch& batch, const float4* accumulated, float4* output,
-                               const PTTileMap& tm, const PTWfBuffers& B, unsigned long long* gstats, bool fullStats,
-                               hipStream_t stream, hipEvent_t orderAfter, bool zeroOutputFirst,
-                               uint32_t* launchesOut, int traceVariant, uint32_t iterationsOverride)
+// MAP = PTListMap: the pass over a block list (pt_launch_wavefront_list); zeroOutputFirst then is false and the frame is copied instead.
+namespace {
+template <class MAP>
+hipError_t launch_wavefront(const DScene& S, const PTFrameParams& P, const PTBatch& batch, const float4* accumulated, float4* output,
+                            const MAP& tm, const PTWfBuffers& B, unsigned long long* gstats, bool fullStats,
+                            hipStream_t stream, hipEvent_t orderAfter, bool zeroOutputFirst,
+                            uint32_t* launchesOut, int traceVariant, uint32_t iterationsOverride)
 {
+    constexpr bool kList = kListMap<MAP>;
     const uint32_t nb = B.numSlots >> 8, nbPass = B.slotsPerPass >> 8;
     uint32_t launches = 0;
     hipError_t e;
@@ -1445,7 +1508,7 @@ hipError_t pt_launch_wavefront(const DScene& S, const PTFrameParams& P, const PT
     if (tlas && traceVariant == 4) traceVariant = 2;      // schedule 4 with HAS_TLAS: the two-level walk runs through schedule 1's refill kernel
     const bool tlasRefill = tlas && traceVariant == 2;    // schedule 1: two-level traversal through the refill scheduler
     if (tlas) traceVariant = 1;          // schedules 2, 3: the one-ray-per-lane trace kernel
-    if (traceVariant == 4 && !tlas) {
+    if constexpr (!kList) if (traceVariant == 4 && !tlas) {
         // schedule 4: one persistent launch renders the whole pass (pt_wf_fused); then the ordered pixel write and the counter fold
         if ((e = hipMemsetAsync(B.chunkHeads, 0, sizeof(uint32_t), stream)) != hipSuccess) return e;
         const uint32_t maxWaves = B.numSlots / (64u * PT_WF_FUSED_GROUPS);           // contexts never outnumber the frame's slots (array sizes)
@@ -1463,7 +1526,7 @@ hipError_t pt_launch_wavefront(const DScene& S, const PTFrameParams& P, const PT
         if (launchesOut) *launchesOut = 3u;
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(pt_wf_init, dim3(nb), dim3(256), 0, stream, P, batch, tm, B);
+    hipLaunchKernelGGL(pt_wf_init<MAP>, dim3(nb), dim3(256), 0, stream, P, batch, tm, B);
     launches++;
     const uint32_t spp = P.SamplesPerPass > 1 ? (uint32_t)P.SamplesPerPass : 1u;
     const uint32_t bounces = P.MaxRayBounces > 1u ? P.MaxRayBounces : 1u;
@@ -1515,24 +1578,48 @@ hipError_t pt_launch_wavefront(const DScene& S, const PTFrameParams& P, const PT
             if (fullStats) hipLaunchKernelGGL((pt_wf_trace<true, false>), dim3(nb * 3u), dim3(256), 0, stream, S, B, it);
             else hipLaunchKernelGGL((pt_wf_trace<false, false>), dim3(nb * 3u), dim3(256), 0, stream, S, B, it);
         }
-        if (fullStats) hipLaunchKernelGGL(pt_wf_shade<true>, dim3(B.numSlots / PT_WF_SHADE_BLOCK), dim3(PT_WF_SHADE_BLOCK), 0, stream, S, P, tm, B, it);
-        else hipLaunchKernelGGL(pt_wf_shade<false>, dim3(B.numSlots / PT_WF_SHADE_BLOCK), dim3(PT_WF_SHADE_BLOCK), 0, stream, S, P, tm, B, it);
+        if (fullStats) hipLaunchKernelGGL((pt_wf_shade<true, MAP>), dim3(B.numSlots / PT_WF_SHADE_BLOCK), dim3(PT_WF_SHADE_BLOCK), 0, stream, S, P, tm, B, it);
+        else hipLaunchKernelGGL((pt_wf_shade<false, MAP>), dim3(B.numSlots / PT_WF_SHADE_BLOCK), dim3(PT_WF_SHADE_BLOCK), 0, stream, S, P, tm, B, it);
         launches += 2;
     }
     const uint32_t cleanupBlocks = nb < 1024u ? nb : 1024u;          // 256 CUs x 4 workgroups; each strides over the slot blocks
     if (tlas) {
-        if (fullStats) hipLaunchKernelGGL((pt_wf_cleanup<true, true>), dim3(cleanupBlocks), dim3(256), 0, stream, S, P, tm, B);
-        else hipLaunchKernelGGL((pt_wf_cleanup<false, true>), dim3(cleanupBlocks), dim3(256), 0, stream, S, P, tm, B);
+        if (fullStats) hipLaunchKernelGGL((pt_wf_cleanup<true, true, MAP>), dim3(cleanupBlocks), dim3(256), 0, stream, S, P, tm, B);
+        else hipLaunchKernelGGL((pt_wf_cleanup<false, true, MAP>), dim3(cleanupBlocks), dim3(256), 0, stream, S, P, tm, B);
     } else {
-        if (fullStats) hipLaunchKernelGGL((pt_wf_cleanup<true, false>), dim3(cleanupBlocks), dim3(256), 0, stream, S, P, tm, B);
-        else hipLaunchKernelGGL((pt_wf_cleanup<false, false>), dim3(cleanupBlocks), dim3(256), 0, stream, S, P, tm, B);
+        if (fullStats) hipLaunchKernelGGL((pt_wf_cleanup<true, false, MAP>), dim3(cleanupBlocks), dim3(256), 0, stream, S, P, tm, B);
+        else hipLaunchKernelGGL((pt_wf_cleanup<false, false, MAP>), dim3(cleanupBlocks), dim3(256), 0, stream, S, P, tm, B);
     }
     if (orderAfter && (e = hipStreamWaitEvent(stream, orderAfter, 0)) != hipSuccess) return e;
     if (zeroOutputFirst &&
         (e = hipMemsetAsync(output, 0, (size_t)P.OutputWidth * P.OutputHeight * sizeof(float4), stream)) != hipSuccess) return e;
-    hipLaunchKernelGGL(pt_wf_resolve, dim3(nbPass), dim3(256), 0, stream, P, batch, tm, B, (const float4*)B.color, accumulated, output);
+    if constexpr (kList) {
+        // pixels outside the list keep Accumulated, bit for bit: one copy of the frame, then the resolve overwrites the listed blocks
+        if (accumulated &&
+            (e = hipMemcpyAsync(output, accumulated, (size_t)P.OutputWidth * P.OutputHeight * sizeof(float4), hipMemcpyDeviceToDevice, stream)) != hipSuccess) return e;
+        hipLaunchKernelGGL(pt_wf_resolve_list, dim3(nbPass), dim3(256), 0, stream, P, batch, tm, B, (const float4*)B.color, accumulated, output);
+    } else {
+        hipLaunchKernelGGL(pt_wf_resolve, dim3(nbPass), dim3(256), 0, stream, P, batch, tm, B, (const float4*)B.color, accumulated, output);
+    }
     hipLaunchKernelGGL(pt_wf_fold_rows, dim3(256), dim3(256), 0, stream, B.statRows, B.numStatRows, gstats);
     launches += 3;
     if (launchesOut) *launchesOut = launches;
     return hipGetLastError();
+}
+} // namespace
+
+hipError_t pt_launch_wavefront(const DScene& S, const PTFrameParams& P, const PTBatch& batch, const float4* accumulated, float4* output,
+                               const PTTileMap& tm, const PTWfBuffers& B, unsigned long long* gstats, bool fullStats,
+                               hipStream_t stream, hipEvent_t orderAfter, bool zeroOutputFirst,
+                               uint32_t* launchesOut, int traceVariant, uint32_t iterationsOverride)
+{
+    return launch_wavefront(S, P, batch, accumulated, output, tm, B, gstats, fullStats, stream, orderAfter, zeroOutputFirst, launchesOut, traceVariant, iterationsOverride);
+}
+
+hipError_t pt_launch_wavefront_list(const DScene& S, const PTFrameParams& P, const PTBatch& batch, const float4* accumulated, float4* output,
+                                    const PTListMap& lm, const PTWfBuffers& B, unsigned long long* gstats, bool fullStats,
+                                    hipStream_t stream, hipEvent_t orderAfter, uint32_t* launchesOut, int traceVariant, uint32_t iterationsOverride)
+{
+    if (traceVariant == 4) return hipErrorNotSupported;
+    return launch_wavefront(S, P, batch, accumulated, output, lm, B, gstats, fullStats, stream, orderAfter, false, launchesOut, traceVariant, iterationsOverride);
 }

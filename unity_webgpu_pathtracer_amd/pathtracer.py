@@ -506,6 +506,118 @@ class PathTracer:
             self.track_noise = was
         return k, st
 
+    # ---- adaptive sampling (include/ptmi_plugin.h Part 7)
+    def block_grid(self):
+        """(rows, columns) of the frame's 16x16 blocks; block id = row * columns + column."""
+        return (self.height + 15) // 16, (self.width + 15) // 16
+
+    def adaptive_begin(self, current_sample: int = None):
+        """PTAdaptiveBegin: every block holds `current_sample` samples (default: what OnRenderImage has accumulated); all active."""
+        n = self._currentSample if current_sample is None else current_sample
+        p = self.params(seed=0)
+        plugin.check(self.lib.PTAdaptiveBegin(self.ctx, C.byref(p), n))
+
+    def adaptive_end(self):
+        plugin.check(self.lib.PTAdaptiveEnd(self.ctx))
+
+    def set_active_blocks(self, ids=None) -> int:
+        """PTSetActiveBlocks: strictly ascending block ids (None = every block, an empty sequence = none).  Returns how many
+        this context keeps (its own blocks with a covered pixel)."""
+        kept = C.c_uint32()
+        if ids is None:
+            plugin.check(self.lib.PTSetActiveBlocks(self.ctx, None, 0, C.byref(kept)))
+        else:
+            a = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+            buf = (C.c_uint32 * max(1, a.size))(*a.tolist())
+            plugin.check(self.lib.PTSetActiveBlocks(self.ctx, buf, a.size, C.byref(kept)))
+        return kept.value
+
+    def select_active_blocks(self, threshold: float, max_samples: int, add_samples: int, dilate: bool = True) -> int:
+        """PTSelectActiveBlocks after noise(): the blocks whose mean error exceeds `threshold` and that may still take
+        `add_samples` within `max_samples` (with dilate: and their neighbours).  Returns how many are active."""
+        kept = C.c_uint32()
+        sel = abi.adaptive_select(threshold, max_samples, add_samples, dilate)
+        plugin.check(self.lib.PTSelectActiveBlocks(self.ctx, C.byref(sel), C.byref(kept)))
+        return kept.value
+
+    def active_blocks(self) -> np.ndarray:
+        """The block ids the next render_active renders, ascending (uint32)."""
+        n = C.c_uint32()
+        plugin.check(self.lib.PTGetActiveBlocks(self.ctx, None, 0, C.byref(n)))
+        buf = (C.c_uint32 * max(1, n.value))()
+        plugin.check(self.lib.PTGetActiveBlocks(self.ctx, buf, n.value, C.byref(n)))
+        return np.array(buf[:n.value], dtype=np.uint32)
+
+    def block_samples(self) -> np.ndarray:
+        """PTGetBlockSamples: the sample count of every block, (ceil(H/16), ceil(W/16)) uint32."""
+        rows, cols = self.block_grid()
+        out = np.empty((rows, cols), np.uint32)
+        plugin.check(self.lib.PTGetBlockSamples(self.ctx, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size))
+        return out
+
+    def _active_params(self, seeds):
+        ps = []
+        for s in seeds:
+            p = self.params(seed=s)
+            p.CurrentSample = 0          # not read: every block renders with its own count
+            ps.append(p)
+        return (abi.PTFrameParams * len(ps))(*ps)
+
+    def render_active(self, seeds, d_output: int = 0, d_accumulated: int = 0):
+        """PTRenderPassActive: len(seeds) passes (1..8, RngSeedRoot = seeds[j]) over the active blocks, into the internal
+        ping-pong frames, or into caller-owned device frames when d_output is given (PTRenderPassActiveTo)."""
+        arr = self._active_params(seeds)
+        if d_output:
+            plugin.check(self.lib.PTRenderPassActiveTo(self.ctx, arr, len(arr), C.c_void_p(d_output), C.c_void_p(d_accumulated or None)))
+        else:
+            plugin.check(self.lib.PTRenderPassActive(self.ctx, arr, len(arr)))
+
+    def accumulate_moments_active(self, count: int, d_output: int = 0, d_accumulated: int = 0):
+        """PTAccumulateMomentsActive: one observation for the blocks of the render_active call just enqueued (count = its
+        number of passes); call it before flip()."""
+        p = self._active_params([0])[0]
+        if d_output:
+            plugin.check(self.lib.PTAccumulateMomentsActiveTo(self.ctx, C.byref(p), count, C.c_void_p(d_output), C.c_void_p(d_accumulated or None)))
+        else:
+            plugin.check(self.lib.PTAccumulateMomentsActive(self.ctx, C.byref(p), count))
+
+    def render_adaptive(self, noise: float, min_samples: int, max_samples: int, seed0: int = 0, passes_per_round: int = 4,
+                        dilate: bool = True, history: list = None):
+        """Reset(); tracked OnRenderImage(seed0 + k) until at least 4 observations and `min_samples`; then rounds of: noise(),
+        select the blocks whose mean error exceeds `noise` (and that stay within `max_samples`), one render_active batch of
+        `passes_per_round` passes with the next seeds, accumulate_moments_active, flip -- until nothing is selected.
+        Afterwards readback() returns the frame (the last output, already flipped) and denoise(variance="moments") works on it.
+        history (optional list) receives ("uniform", seed) and ("active", ids, seeds) records in order.
+        Returns (block_samples, the last PTNoiseStats)."""
+        spp = max(1, self.samplesPerPass)
+        was, self.track_noise = self.track_noise, True
+        try:
+            self.adaptive_end()
+            self.Reset()
+            k = 0
+            while k < 4 or self._currentSample < min_samples:
+                self.OnRenderImage(seed0 + k)
+                if history is not None:
+                    history.append(("uniform", seed0 + k))
+                k += 1
+        finally:
+            self.track_noise = was
+        self.adaptive_begin()
+        add = spp * passes_per_round
+        while True:
+            st = self.noise(threshold=noise)
+            if self.select_active_blocks(noise, max_samples, add, dilate) == 0:
+                break
+            seeds = [seed0 + k + j for j in range(passes_per_round)]
+            k += passes_per_round
+            if history is not None:
+                history.append(("active", self.active_blocks(), seeds))
+            self.render_active(seeds)
+            self.accumulate_moments_active(passes_per_round)
+            self.flip()
+            self._flipped = True
+        return self.block_samples(), st
+
     # ---- scene updates (include/ptmi_plugin.h Part 5)
     def set_instance_transforms(self, local_to_world) -> bool:
         """Move the instances (one 4x4 localToWorld each): BVHScene.UpdateTLAS, then Reset() when anything changed, as the
@@ -558,6 +670,36 @@ class PathTracer:
             self.close()
         except Exception:
             pass
+
+
+def select_blocks(tiles, samples, threshold: float, max_samples: int, add_samples: int, dilate: bool) -> np.ndarray:
+    """PTSelectActiveBlocks restated: tiles / samples are the (rows, columns) tile map and block sample counts.  A block is
+    selected when its tile value > threshold and samples + add_samples <= max_samples; with dilate also the up to eight
+    neighbours of such a block that meet the sample limit.  Returns the ascending block ids (uint32)."""
+    tiles = np.asarray(tiles, np.float32)
+    samples = np.asarray(samples, np.uint64)
+    within = samples + np.uint64(add_samples) <= np.uint64(max_samples)
+    core = (tiles > np.float32(threshold)) & within
+    pick = core.copy()
+    if dilate:
+        rows, cols = core.shape
+        for by, bx in zip(*np.nonzero(core)):
+            y0, y1, x0, x1 = max(by - 1, 0), min(by + 2, rows), max(bx - 1, 0), min(bx + 2, cols)
+            pick[y0:y1, x0:x1] |= within[y0:y1, x0:x1]
+    return np.flatnonzero(pick.reshape(-1)).astype(np.uint32)
+
+
+def list_slot_to_pixel(width: int, height: int, ids, cover=None):
+    """The slot -> pixel mapping of a pass over a block list (pt_launch.h PTListMap), restated: slot e * 256 + tid of entry e =
+    block ids[e], four 8x8 waves per block.  Returns (px, py, valid) arrays of len(ids) * 256 entries."""
+    cw, ch = cover or (width, height)
+    cols = (width + 15) // 16
+    ids = np.asarray(ids, np.int64)
+    tid = np.arange(256)
+    wave, lane = tid >> 6, tid & 63
+    px = ((ids % cols) * 16)[:, None] + ((wave & 1) * 8 + (lane & 7))[None, :]
+    py = ((ids // cols) * 16)[:, None] + ((wave >> 1) * 8 + (lane >> 3))[None, :]
+    return px.reshape(-1), py.reshape(-1), ((px < cw) & (py < ch)).reshape(-1)
 
 
 def _device_to_numpy(ptr: int, shape) -> np.ndarray:

@@ -79,6 +79,15 @@ sig = {
     "PTGetNoiseTilePointer": (vp, [vp]),
     "PTDenoiseMoments": (i32, [vp, C.POINTER(abi.PTDenoiseParams), vp, vp]),
     "PTDenoiseMomentsToHost": (i32, [vp, C.POINTER(abi.PTDenoiseParams), vp, C.c_uint64]),
+    # Part 7 (adaptive sampling)
+    "PTAdaptiveBegin": (i32, [vp, C.POINTER(abi.PTFrameParams), C.c_uint32]), "PTAdaptiveEnd": (i32, [vp]),
+    "PTSetActiveBlocks": (i32, [vp, u32p, C.c_uint32, u32p]),
+    "PTSelectActiveBlocks": (i32, [vp, C.POINTER(abi.PTAdaptiveSelect), u32p]),
+    "PTGetActiveBlocks": (i32, [vp, u32p, C.c_uint32, u32p]), "PTGetBlockSamples": (i32, [vp, u32p, C.c_uint64]),
+    "PTRenderPassActive": (i32, [vp, C.POINTER(abi.PTFrameParams), i32]),
+    "PTRenderPassActiveTo": (i32, [vp, C.POINTER(abi.PTFrameParams), i32, vp, vp]),
+    "PTAccumulateMomentsActive": (i32, [vp, C.POINTER(abi.PTFrameParams), i32]),
+    "PTAccumulateMomentsActiveTo": (i32, [vp, C.POINTER(abi.PTFrameParams), i32, vp, vp]),
     "PTGetLastError": (C.c_char_p, []), "PTGetVersion": (i32, []),
 }
 EXPORTED_SYMBOLS = list(sig)
