@@ -677,6 +677,79 @@ PT_API int PTRenderPassActiveTo(PTContext* ctx, const PTFrameParams* params, int
 PT_API int PTAccumulateMomentsActive(PTContext* ctx, const PTFrameParams* params, int count);
 PT_API int PTAccumulateMomentsActiveTo(PTContext* ctx, const PTFrameParams* params, int count, const void* dOutput, const void* dAccumulated);
 
+/* =====================================================================================================================
+ * Part 8: radiance queries.  How much light arrives along a ray?  Part 3 says what a ray hits; radiance so far exists only for
+ * the pixels of one camera (PTRenderPass*).  Here the host hands the path tracer a LIST of rays -- light and reflection
+ * probes, lightmap texels with host-made gather directions, sensor simulation, scattered pixels, ray batches across many
+ * cameras -- and gets the path-traced radiance of each, computed by the render's own code.  The reference has nothing like
+ * it: an addition beside its ABI, like Parts 3 to 7.
+ *
+ * The contract of PTTraceRadiance (bit-exact):
+ *  - Entry i runs n = max(SamplesPerPass, 1) samples.  Sample 0 starts in the state the render's path_init leaves --
+ *    sample index 0, colour 0, no pending NEE -- with RNG state rays[i].rng and the entry's origin and direction as the
+ *    first ray; the direction is used as given, never re-normalised.  Every later sample restarts from the SAME ray with the
+ *    RNG continuing where the previous sample left it (what the render does at the end of a sample, with the camera drawing
+ *    nothing).  Everything from there on is the render's code in the render's order: the path step, the firefly filter,
+ *    Russian roulette and MaxRayBounces of `params`, the environment mode, lights, textures, HAS_TLAS.
+ *  - out[i].rgb = colour / (float)n, the expression of the render's pixel write for CurrentSample == 0 (one fp32 division
+ *    per channel); out[i].rng = the RNG state after the last draw.  Feeding it back as rays[i].rng continues the chain:
+ *    one call with n samples equals n calls with one sample each, their colours summed in order and divided by (float)n.
+ *  - Results are in the caller's order; nothing past `count` is written.
+ *  - Not read from PTFrameParams: CamInvProj, CamToWorld, OutputWidth, OutputHeight, CurrentSample, RngSeedRoot, Aperture,
+ *    FocalLength, DispatchGroupsX / Y.  The struct is still validated as for a pass (structSize, a non-empty frame size).
+ *  - A NaN in an origin or direction behaves as in the render: no walk, the sky.  A direction that is not of unit length is
+ *    the caller's error: some finite or NaN colour, never an out-of-bounds access.
+ *  - Stream-ordered on the context's stream, like PTTraceRays: the call returns before anything is traced, dRays is read
+ *    after everything enqueued on that stream so far, and must stay valid until the call has run (samples after the first
+ *    re-read it).  dRays and dOut are 16-byte aligned.  Calls take the context's state sets round-robin exactly as passes do
+ *    (PTSetPassesInFlight); each call's output is its own (no ordering between resolves).
+ *  - A list of more than 2^21 entries is cut into chunks of 2^21, each a launch sequence on the next state set: a state set
+ *    never grows beyond what a 1080p frame needs, and the chunks of one call overlap like passes in flight.  Two calls do not
+ *    overlap (the second one's rays are ordered after the first one's results): one long list beats many short ones.
+ *  - PTStats (at the level set): paths = count x n; every ray, node, triangle, fetch and TLAS counter by the render's
+ *    definitions; pixelsWritten and pixelsRead do not move.  With profiling on, every chunk is one entry of PTGetTimings.
+ *  - Schedules 1, 2 and 3, flat and HAS_TLAS scenes; schedules 0 and 4 return PT_ERR_UNSUPPORTED (PTSetSchedule; note that
+ *    the automatic schedule of a scene with a handful of BVH nodes is 0).  PT_ERR_UNSUPPORTED also for SamplesPerPass > 4095
+ *    or MaxRayBounces > 8191.  count == 0 returns PT_OK and launches nothing.  PT_ERR_INVALID_ARG for a NULL context or
+ *    pointer, a misaligned pointer and (PTTraceRadianceHost) a nonzero `reserved` word; PT_ERR_NO_SCENE before PTSetScene.
+ *    There is no CPU fallback.
+ *
+ * The contract of PTCameraRays: for pixel index k = py * OutputWidth + px the entry is what the render's path_init makes of
+ * that pixel: the RNG is seeded with k * (CurrentSample + 1) + RngSeedRoot, the camera ray is generated (two draws; four with
+ * Aperture > 0 and FocalLength > 0), and the entry holds that ray's origin and direction and the RNG state AFTER the draws.
+ * dPixelIndices == NULL: entry i is pixel i, and count > OutputWidth * OutputHeight is PT_ERR_INVALID_ARG.  In a device list
+ * an index >= OutputWidth * OutputHeight yields an entry with a NaN direction and rng = 0 (never an out-of-range read).
+ * Stream-ordered on the context's stream; needs no scene.
+ *
+ * Together: PTCameraRays followed by PTTraceRadiance with SamplesPerPass = 1 gives, bit for bit, the rgb PTRenderPassTo
+ * writes for those pixels with SamplesPerPass = 1 and CurrentSample = 0.
+ * ===================================================================================================================== */
+typedef struct PTRadianceRay {    /* 32 bytes */
+    float    origin[3];
+    float    direction[3];        /* unit length; used as given, never re-normalised */
+    uint32_t rng;                 /* RNG state the path starts with */
+    uint32_t reserved;            /* must be 0 (PTTraceRadianceHost checks it; the device path ignores it) */
+} PTRadianceRay;
+
+typedef struct PTRadiance {       /* 16 bytes */
+    float    rgb[3];              /* mean over the samples: sum / (float)n */
+    uint32_t rng;                 /* RNG state after the last sample */
+} PTRadiance;
+
+#ifdef __cplusplus
+static_assert(sizeof(PTRadianceRay) == 32, "PTRadianceRay is 32 bytes");
+static_assert(sizeof(PTRadiance) == 16, "PTRadiance is 16 bytes");
+#else
+_Static_assert(sizeof(PTRadianceRay) == 32, "PTRadianceRay is 32 bytes");
+_Static_assert(sizeof(PTRadiance) == 16, "PTRadiance is 16 bytes");
+#endif
+
+/* Device pointers, stream-ordered on the context's stream; dPixelIndices == NULL = every pixel in index order. */
+PT_API int PTCameraRays(PTContext* ctx, const PTFrameParams* params, const uint32_t* dPixelIndices, uint64_t count, PTRadianceRay* dRays);
+PT_API int PTTraceRadiance(PTContext* ctx, const PTFrameParams* params, const PTRadianceRay* dRays, uint64_t count, PTRadiance* dOut);
+/* Host arrays: staged through device buffers the context keeps and grows; synchronous. */
+PT_API int PTTraceRadianceHost(PTContext* ctx, const PTFrameParams* params, const PTRadianceRay* rays, uint64_t count, PTRadiance* out);
+
 /* Text of the last error on the calling thread ("" if none). */
 PT_API const char* PTGetLastError(void);
 /* Library/ABI version: (major << 16) | minor. */

@@ -1,0 +1,88 @@
+"""Radiance queries (include/ptmi_plugin.h Part 8) without a GPU: exports, struct layout, argument checks and the compile-time
+resources of the ray-mapped kernels.  tests/test_gpu_radiance.py holds the kernels to the contract."""
+import ctypes as C
+import os
+import shutil
+import subprocess
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
+
+import pytest
+
+from unity_webgpu_pathtracer_amd import abi, plugin
+from test_kernel_resources import _resources
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RADIANCE_SYMBOLS = ["PTCameraRays", "PTTraceRadiance", "PTTraceRadianceHost"]
+
+
+def test_radiance_symbols_are_exported():
+    lib = plugin.load_library()
+    out = subprocess.check_output(["nm", "-D", "--defined-only", plugin.LIB_PATH]).decode()
+    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
+    header = open(os.path.join(ROOT, "include", "ptmi_plugin.h")).read()
+    for name in RADIANCE_SYMBOLS:
+        assert name in exported, name
+        assert name in plugin.EXPORTED_SYMBOLS, name
+        assert f" {name}(" in header, name
+        assert getattr(lib, name).restype is C.c_int
+
+
+def test_radiance_structs_match_c_header():
+    fields = {"PTRadianceRay": ["origin", "direction", "rng", "reserved"], "PTRadiance": ["rgb", "rng"]}
+    lines = []
+    for s, fs in fields.items():
+        lines.append(f'printf("{s} %zu\\n", sizeof({s}));')
+        lines += [f'printf("{s}.{f} %zu\\n", offsetof({s}, {f}));' for f in fs]
+    src = "#include <stdio.h>\n#include <stddef.h>\n#include \"ptmi_plugin.h\"\nint main(void) {\n" + "\n".join(lines) + "\nreturn 0; }\n"
+    with tempfile.TemporaryDirectory() as d:
+        c = os.path.join(d, "probe.c")
+        open(c, "w").write(src)
+        exe = os.path.join(d, "probe")
+        subprocess.check_call(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
+        got = dict(l.split(" ", 1) for l in subprocess.check_output([exe]).decode().splitlines())
+    assert int(got["PTRadianceRay"]) == C.sizeof(abi.PTRadianceRay) == 32
+    assert int(got["PTRadiance"]) == C.sizeof(abi.PTRadiance) == 16
+    for s, fs in fields.items():
+        for f in fs:
+            assert int(got[f"{s}.{f}"]) == getattr(getattr(abi, s), f).offset, (s, f)
+    assert [abi.PTRadianceRay.origin.offset, abi.PTRadianceRay.direction.offset, abi.PTRadianceRay.rng.offset,
+            abi.PTRadianceRay.reserved.offset] == [0, 12, 24, 28]
+    assert [abi.PTRadiance.rgb.offset, abi.PTRadiance.rng.offset] == [0, 12]
+
+
+def test_radiance_argument_errors_without_context():
+    lib = plugin.load_library()
+    p = abi.PTFrameParams()
+    p.OutputWidth, p.OutputHeight = 4, 4
+    buf = (C.c_float * 64)()
+    for rc in (lib.PTCameraRays(None, C.byref(p), None, 4, C.addressof(buf)),
+               lib.PTTraceRadiance(None, C.byref(p), C.addressof(buf), 4, C.addressof(buf)),
+               lib.PTTraceRadianceHost(None, C.byref(p), C.addressof(buf), 4, C.addressof(buf))):
+        assert rc == abi.PT_ERR_INVALID_ARG
+        assert b"ctx" in lib.PTGetLastError() and b"NULL" in lib.PTGetLastError()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# kernel resources: the ray-mapped shade kernel stays on the frame-mapped one's line (test_kernel_resources.py)
+# ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not installed")
+def test_ray_mapped_kernels_keep_the_register_budget():
+    with ThreadPoolExecutor(2) as ex:
+        fa = ex.submit(_resources, "pt_wavefront.hip", True)
+        fb = ex.submit(_resources, "pt_wavefront.hip", False)
+        res_a, res_b = fa.result(), fb.result()
+    for unit, res in (("a", res_a), ("b", res_b)):
+        shade = {k: v for k, v in res.items() if "pt_wf_shadeILb0E" in k and "PTRayMap" in k}
+        assert len(shade) == 1, sorted(res)
+        for k, r in shade.items():
+            print(f"[resources] unit {unit} {k}: {r}")
+            assert r["scratch"] == 0 and r["vgprs"] <= 128 and r["occupancy"] >= 4, (unit, r)
+        init = [v for k, v in res.items() if "pt_wf_initI" in k and "PTRayMap" in k]
+        resolve = [v for k, v in res.items() if "pt_wf_resolve_rays" in k]
+        assert len(init) == 1 and len(resolve) == 1, sorted(res)
+        for r in init + resolve:
+            print(f"[resources] unit {unit}: {r}")
+            assert r["scratch"] == 0 and r["occupancy"] == 8, (unit, r)
+        # the cleanup kernel is compiled for two waves per SIMD like the frame-mapped one: no spill beyond what that has
+        assert [k for k in res if "pt_wf_cleanup" in k and "PTRayMap" in k], sorted(res)

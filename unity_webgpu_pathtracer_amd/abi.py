@@ -262,6 +262,18 @@ def adaptive_select(threshold: float, max_samples: int, add_samples: int, dilate
     return PTAdaptiveSelect(C.sizeof(PTAdaptiveSelect), threshold, max_samples, add_samples, 1 if dilate else 0)
 
 
+# ---- radiance queries (include/ptmi_plugin.h Part 8)
+class PTRadianceRay(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("direction", C.c_float * 3), ("rng", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PTRadiance(C.Structure):
+    _fields_ = [("rgb", C.c_float * 3), ("rng", C.c_uint32)]
+
+
+assert C.sizeof(PTRadianceRay) == 32 and C.sizeof(PTRadiance) == 16
+
+
 def as_void_p(arr):
     """Borrowed host pointer of a C-contiguous numpy array (None -> NULL)."""
     if arr is None:

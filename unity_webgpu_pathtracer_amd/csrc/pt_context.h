@@ -211,6 +211,10 @@ struct PTContext {
         uint32_t lastM = 0;                     // samples the call added per block; 0 = none pending
         UploadTable momentsTable, invDof;       // on the context stream
     } adaptive;
+    // radiance queries (PTTraceRadianceHost): host staging, grown on demand
+    struct Radiance {
+        DeviceBuffer rays, out;
+    } radiance;
     // scene updates (PTUpdateInstances / Lights / Materials): two generations of what an update rewrites, allocated on the first
     // update of each kind and discarded by PTSetScene.  cur = -1 while PTSetScene's own buffers are current.
     struct UpdGroup {

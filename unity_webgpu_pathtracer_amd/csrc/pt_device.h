@@ -1489,6 +1489,11 @@ PT_DEV void path_init(const PTFrameParams& P, uint32_t seedRoot, uint32_t curren
 // to), BEFORE the BSDF is sampled.  The wavefront shade kernel writes them to the slot arrays there, so that their 15
 // registers are free while sample_brdf runs (pt_wavefront.hip); the other schedules keep them in registers and pass nothing.
 struct NoNeeSink { PT_DEV void operator()(PathRegs&) const {} };
+// Source: how a sample starts.  The camera's (the default; every render) draws its jitter and lens numbers from the path's RNG;
+// a radiance query restarts from the caller's ray and draws nothing (pt_wavefront.hip RaySample).
+struct CameraSample {
+    PT_DEV void operator()(const PTFrameParams& P, uint32_t pixelX, uint32_t pixelY, PathRegs& r, Counters& cn) const { path_start_sample(P, pixelX, pixelY, r, cn); }
+};
 
 // ---- (1) radiance += DirectLight(...) * throughput      (util/pathtrace.hlsl:93, deferred until the shadow rays are in)
 PT_DEV void path_apply_pending(PathRegs& r, bool occEnv, bool occLight)
@@ -1595,9 +1600,9 @@ PT_DEV void path_shade_hit(const DScene& S, const PTFrameParams& P, PathRegs& r,
 }
 
 // ---- (3) end of a sample                                 (PathTracer.compute:77-98)
-template <bool INLINE_RESOLVE>
+template <bool INLINE_RESOLVE, class Source = CameraSample>
 PT_DEV void path_end_sample(const PTFrameParams& P, PathRegs& r, uint32_t pixelX, uint32_t pixelY, uint32_t pixelIndex,
-                            const float4* __restrict__ accumulated, float4* __restrict__ output, Counters& cn)
+                            const float4* __restrict__ accumulated, float4* __restrict__ output, Counters& cn, Source source = Source())
 {
     if (r.state == PS_ENDING && !r.hasPending) {
         if (P.UseFireflyFilter) {
@@ -1608,7 +1613,7 @@ PT_DEV void path_end_sample(const PTFrameParams& P, PathRegs& r, uint32_t pixelX
         r.sampleIdx++;
         const uint32_t numSamples = P.SamplesPerPass > 1 ? (uint32_t)P.SamplesPerPass : 1u;
         if (r.sampleIdx < numSamples) {
-            path_start_sample(P, pixelX, pixelY, r, cn);
+            source(P, pixelX, pixelY, r, cn);
         } else if (!INLINE_RESOLVE) {
             r.state = PS_DONE;
         } else {
@@ -1631,14 +1636,15 @@ PT_DEV void path_end_sample(const PTFrameParams& P, PathRegs& r, uint32_t pixelX
     }
 }
 
-template <bool STATS, bool INLINE_RESOLVE = true, class NeeSink = NoNeeSink>
+template <bool STATS, bool INLINE_RESOLVE = true, class NeeSink = NoNeeSink, class Source = CameraSample>
 PT_DEV void path_step(const DScene& S, const PTFrameParams& P, PathRegs& r, const HitRecord& rec, bool occEnv, bool occLight,
                       uint32_t pixelX, uint32_t pixelY, uint32_t pixelIndex,
-                      const float4* __restrict__ accumulated, float4* __restrict__ output, Counters& cn, NeeSink neeSink = NeeSink())
+                      const float4* __restrict__ accumulated, float4* __restrict__ output, Counters& cn, NeeSink neeSink = NeeSink(),
+                      Source source = Source())
 {
     path_apply_pending(r, occEnv, occLight);
     if (r.state == PS_TRACE) path_shade_hit<STATS, NeeSink>(S, P, r, rec, cn, neeSink);
-    path_end_sample<INLINE_RESOLVE>(P, r, pixelX, pixelY, pixelIndex, accumulated, output, cn);
+    path_end_sample<INLINE_RESOLVE, Source>(P, r, pixelX, pixelY, pixelIndex, accumulated, output, cn, source);
 }
 
 // Wave-level helpers (wave64).

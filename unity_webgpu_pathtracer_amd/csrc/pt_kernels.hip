@@ -103,7 +103,37 @@ __global__ void pt_derive_lights(DScene S, float4* lightConst)
     for (int k = 0; k < 4; ++k) lightConst[(size_t)i * 4 + k] = rows[k];
 }
 
+// PTCameraRays: what path_init makes of a pixel -- seed, camera ray, the RNG state after the camera's draws -- as a list entry
+__global__ __launch_bounds__(256) void pt_camera_rays(PTFrameParams P, const uint32_t* __restrict__ indices, uint32_t count, PTRadianceRay* __restrict__ rays)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= count) return;
+    const uint32_t k = indices ? indices[i] : i;
+    float4 a, b;
+    if (k < P.OutputWidth * P.OutputHeight) {
+        PathRegs r;
+        Counters cn = {};
+        path_init(P, P.RngSeedRoot, P.CurrentSample, k % P.OutputWidth, k / P.OutputWidth, k, r, cn);
+        a = make_float4(r.ro.x, r.ro.y, r.ro.z, r.rd.x);
+        b = make_float4(r.rd.y, r.rd.z, pt_asfloat(r.rng), pt_asfloat(0u));
+    } else {
+        const float nan = pt_asfloat(0x7FC00000u);
+        a = make_float4(0.0f, 0.0f, 0.0f, nan);
+        b = make_float4(nan, nan, pt_asfloat(0u), pt_asfloat(0u));
+    }
+    float4* e = (float4*)(rays + i);
+    e[0] = a;
+    e[1] = b;
+}
+
 } // namespace
+
+hipError_t pt_launch_camera_rays(const PTFrameParams& P, const uint32_t* indices, uint32_t count, PTRadianceRay* rays, hipStream_t stream)
+{
+    if (count == 0u) return hipSuccess;
+    hipLaunchKernelGGL(pt_camera_rays, dim3((count + 255u) / 256u), dim3(256), 0, stream, P, indices, count, rays);
+    return hipGetLastError();
+}
 
 hipError_t pt_launch_derive_lights(const DScene& S, float4* lightConst, hipStream_t stream)
 {

@@ -243,6 +243,23 @@ typedef hipError_t PTWfListLauncher(const DScene& S, const PTFrameParams& P, con
                                     const PTListMap& lm, const PTWfBuffers& B, unsigned long long* gstats, bool fullStats,
                                     hipStream_t stream, hipEvent_t orderAfter, uint32_t* launchesOut, int traceVariant, uint32_t iterationsOverride);
 PTWfListLauncher pt_launch_wavefront_list, pt_launch_wavefront_list_b;
+// ---- radiance queries (include/ptmi_plugin.h Part 8): a launch sequence over a caller's LIST OF RAYS ----
+// Slot s is entry s of the list (one pass, slotsPerPass = numSlots = count rounded up to 256; the slots past count start as
+// finished).  A path depends on its "pixel" only through how a sample starts: here sample 0 is the entry's ray and RNG state, and
+// every later sample reloads the entry's ray (a 32-byte vector load by slot) and draws nothing.  px, py and pixelIndex carry nothing.
+struct PTRayMap {
+    const PTRadianceRay* rays;     // 16-byte aligned
+    uint32_t count;
+};
+#define PT_RADIANCE_CHUNK (1u << 21)      // most entries of one launch sequence (a state set no larger than a 1080p frame's); <= 2^23
+// The launch sequence of pt_launch_wavefront over the list; the resolve writes out[s] = {colour / (float)spp, rng} for s < count and
+// depends on nothing but this sequence.  Schedule 4 (traceVariant 4) is not available.
+typedef hipError_t PTWfRaysLauncher(const DScene& S, const PTFrameParams& P, const PTRayMap& rm, PTRadiance* out, const PTWfBuffers& B,
+                                    unsigned long long* gstats, bool fullStats, hipStream_t stream, uint32_t* launchesOut, int traceVariant,
+                                    uint32_t iterationsOverride);
+PTWfRaysLauncher pt_launch_wavefront_rays, pt_launch_wavefront_rays_b;
+// PTCameraRays (pt_kernels.hip): entry i = path_init's ray and RNG state of pixel indices[i] (NULL: pixel i); count <= 2^31
+hipError_t pt_launch_camera_rays(const PTFrameParams& P, const uint32_t* indices, uint32_t count, PTRadianceRay* rays, hipStream_t stream);
 #ifndef PT_WF_FUSED_GROUPS
 #define PT_WF_FUSED_GROUPS 2u   // schedule 4: groups of 64 path contexts a persistent wave owns (power of two <= 4: numSlots is a multiple of 256).
                                 // Sponza-class 1080p / 8 spp, one pass in flight: 1: 29.9 ms, 2: 25.2, 4: 27.9, 8: 31.4

@@ -122,6 +122,47 @@ PT_DEV bool wf_pixel(const PTListMap& lm, const PTWfBuffers& B, uint32_t slot, u
 }
 template <class MAP> constexpr bool kListMap = std::is_same<MAP, PTListMap>::value;
 
+// PTRayMap (radiance queries, pt_launch.h): slot s is entry s of the caller's ray list; there is no pixel, one pass, no base.
+PT_DEV bool wf_pixel(const PTRayMap& rm, const PTWfBuffers& B, uint32_t slot, uint32_t wgSlot, uint32_t& px, uint32_t& py, uint32_t& pass, uint32_t& base)
+{
+    px = 0u; py = 0u; pass = 0u; base = 0u;
+    return slot < rm.count;
+}
+template <class MAP> constexpr bool kRayMap = std::is_same<MAP, PTRayMap>::value;
+// How a sample of a list entry starts (the Source of path_step): path_start_sample with the entry's ray in place of the camera's,
+// and no RNG draw.  The entry is two 16-byte vector loads by slot: {origin.xyz, direction.x} {direction.yz, rng, reserved}.
+struct RaySample {
+    const PTRadianceRay* rays; uint32_t slot;
+    PT_DEV void operator()(const PTFrameParams&, uint32_t, uint32_t, PathRegs& r, Counters& cn) const { start(r, cn); }
+    PT_DEV void start(PathRegs& r, Counters& cn) const
+    {
+        const float4* e = (const float4*)(rays + slot);
+        const float4 a = e[0], b = e[1];
+        cn.paths++;
+        r.radiance = mk3(0.0f);
+        r.throughput = mk3(1.0f);
+        r.depth = 0u;
+        r.scatterPdf = 0.0f;
+        r.maxRoughness = 0.0f;
+        r.ro = mk3(a.x, a.y, a.z);
+        r.rd = mk3(a.w, b.x, b.y);
+        r.state = PS_TRACE;
+    }
+};
+// path_init for a list entry: the state path_init leaves, with the entry's RNG state and ray
+PT_DEV void ray_path_init(const PTRayMap& rm, uint32_t slot, PathRegs& r, Counters& cn)
+{
+    r.rng = rm.rays[slot].rng;
+    r.sampleIdx = 0u;
+    r.color = mk3(0.0f);
+    r.env.valid = 0u; r.light.valid = 0u;
+    r.env.dir = mk3(0.0f); r.light.dir = mk3(0.0f);
+    r.env.contribution = mk3(0.0f); r.light.contribution = mk3(0.0f);
+    r.neeOrigin = mk3(0.0f); r.pendThroughput = mk3(0.0f);
+    r.hasPending = false; r.green = false;
+    RaySample{rm.rays, slot}.start(r, cn);
+}
+
 template <class MAP = PTTileMap>
 __global__ __launch_bounds__(256) void pt_wf_init(PTFrameParams P, PTBatch batch, MAP tm, PTWfBuffers B)
 {
@@ -133,10 +174,13 @@ __global__ __launch_bounds__(256) void pt_wf_init(PTFrameParams P, PTBatch batch
     if (!wf_pixel(tm, B, slot, blockIdx.x * 256u, px, py, pass, base)) B.flags[slot] = PS_DONE;
     else {
         PathRegs r;
-        uint32_t seedRoot, currentSample;
-        pt_batch_pick(batch, pass, seedRoot, currentSample);
-        if (kListMap<MAP>) currentSample = base + pass * (P.SamplesPerPass > 1 ? (uint32_t)P.SamplesPerPass : 1u);
-        path_init(P, seedRoot, currentSample, px, py, py * P.OutputWidth + px, r, cn);
+        if constexpr (kRayMap<MAP>) ray_path_init(tm, slot, r, cn);
+        else {
+            uint32_t seedRoot, currentSample;
+            pt_batch_pick(batch, pass, seedRoot, currentSample);
+            if (kListMap<MAP>) currentSample = base + pass * (P.SamplesPerPass > 1 ? (uint32_t)P.SamplesPerPass : 1u);
+            path_init(P, seedRoot, currentSample, px, py, py * P.OutputWidth + px, r, cn);
+        }
         store_path(B, slot, r, false);
     }
     // every lane of the wave takes part in the reduction (a lane that had returned would be read as garbage)
@@ -959,7 +1003,10 @@ PT_DEV bool shade_slot(const DScene& S, const PTFrameParams& P, const MAP& tm, c
             B.pthr[s2] = f4(q.pendThroughput, 0.0f);
         }
     };
-    path_step<STATS, false, Sink>(S, P, r, ch, occEnv, occLight, px, py, py * P.OutputWidth + px, nullptr, nullptr, cn, Sink{B, slot});
+    if constexpr (kRayMap<MAP>)
+        path_step<STATS, false, Sink, RaySample>(S, P, r, ch, occEnv, occLight, 0u, 0u, 0u, nullptr, nullptr, cn, Sink{B, slot}, RaySample{tm.rays, pixelSlot});
+    else
+        path_step<STATS, false, Sink>(S, P, r, ch, occEnv, occLight, px, py, py * P.OutputWidth + px, nullptr, nullptr, cn, Sink{B, slot});
     // the store addresses are formed HERE from a slot the compiler cannot connect with the one the loads used: otherwise the
     // thirteen 64-bit load addresses stay in registers across the whole step to be reused by these stores
     uint32_t storeSlot = slot;
@@ -1329,10 +1376,14 @@ __global__ __launch_bounds__(256, 2) void pt_wf_cleanup(DScene S, PTFrameParams 
                     else traverse_cwbvh<STATS>(S, r.ro, r.rd, false, ch.h, st, cn);
                     cn.closestRays++;
                 }
-                path_step<STATS, false>(S, P, r, ch, occEnv, occLight, px, py, py * P.OutputWidth + px, nullptr, nullptr, cn);
+                if constexpr (kRayMap<MAP>)
+                    path_step<STATS, false, NoNeeSink, RaySample>(S, P, r, ch, occEnv, occLight, 0u, 0u, 0u, nullptr, nullptr, cn, NoNeeSink(), RaySample{tm.rays, slot});
+                else
+                    path_step<STATS, false>(S, P, r, ch, occEnv, occLight, px, py, py * P.OutputWidth + px, nullptr, nullptr, cn);
             }
             B.flags[slot] = pack_flags(r);
             B.color[slot] = f4(r.color, 0.0f);
+            if constexpr (kRayMap<MAP>) B.rng[slot] = r.rng;           // a query returns the RNG state; a frame's resolve never reads it
         }
     }
     }
@@ -1411,6 +1462,18 @@ __global__ __launch_bounds__(256) void pt_wf_resolve_list(PTFrameParams P, PTBat
     flush_counters<false>(cn, B.statRows, blockIdx.x * 4u + (threadIdx.x >> 6), threadIdx.x & 63u);
 }
 
+// resolve of a radiance query: entry s gets the mean of its samples -- the expression of pt_wf_resolve's CurrentSample == 0 branch --
+// and the RNG state its path ended with.  Writes nothing past count; counts nothing (no pixel is written).
+__global__ __launch_bounds__(256) void pt_wf_resolve_rays(PTFrameParams P, PTRayMap rm, PTWfBuffers B, PTRadiance* __restrict__ out)
+{
+    const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
+    if (slot >= rm.count) return;
+    const uint32_t numSamples = P.SamplesPerPass > 1 ? (uint32_t)P.SamplesPerPass : 1u;
+    const float fSamples = (float)numSamples;
+    const v3 acc = xyz(B.color[slot]) / fSamples;
+    ((float4*)out)[slot] = make_float4(acc.x, acc.y, acc.z, pt_asfloat(B.rng[slot]));
+}
+
 // fold the per-wave rows into the context's 16 counters (PTStats order) and clear them
 __global__ __launch_bounds__(256) void pt_wf_fold_rows(unsigned long long* rows, uint32_t numRows, unsigned long long* gstats)
 {
@@ -1487,12 +1550,14 @@ PTWfBuffers pt_wf_arena_carve(void* base, uint32_t numSlots, uint32_t residentWa
 }
 #define pt_launch_wavefront pt_launch_wavefront_b
 #define pt_launch_wavefront_list pt_launch_wavefront_list_b
+#define pt_launch_wavefront_rays pt_launch_wavefront_rays_b
 #endif
 
 // One pass = a fixed sequence of launches on `stream`, no host synchronisation (see the file header).
 // `orderAfter` (may be null) is the event of the previous pass's resolve: this pass's resolve reads that pass's output as
 // AccumulatedOutput and, with ping-pong frames, overwrites the frame that resolve was still reading.
 // MAP = PTListMap: the pass over a block list (pt_launch_wavefront_list); zeroOutputFirst then is false and the frame is copied instead.
+// MAP = PTRayMap: a radiance query (pt_launch_wavefront_rays): `output` is the PTRadiance array, nothing is ordered, zeroed or copied.
 namespace {
 template <class MAP>
 hipError_t launch_wavefront(const DScene& S, const PTFrameParams& P, const PTBatch& batch, const float4* accumulated, float4* output,
@@ -1500,7 +1565,7 @@ hipError_t launch_wavefront(const DScene& S, const PTFrameParams& P, const PTBat
                             hipStream_t stream, hipEvent_t orderAfter, bool zeroOutputFirst,
                             uint32_t* launchesOut, int traceVariant, uint32_t iterationsOverride)
 {
-    constexpr bool kList = kListMap<MAP>;
+    constexpr bool kList = kListMap<MAP>, kRays = kRayMap<MAP>;
     const uint32_t nb = B.numSlots >> 8, nbPass = B.slotsPerPass >> 8;
     uint32_t launches = 0;
     hipError_t e;
@@ -1508,7 +1573,7 @@ hipError_t launch_wavefront(const DScene& S, const PTFrameParams& P, const PTBat
     if (tlas && traceVariant == 4) traceVariant = 2;      // schedule 4 with HAS_TLAS: the two-level walk runs through schedule 1's refill kernel
     const bool tlasRefill = tlas && traceVariant == 2;    // schedule 1: two-level traversal through the refill scheduler
     if (tlas) traceVariant = 1;          // schedules 2, 3: the one-ray-per-lane trace kernel
-    if constexpr (!kList) if (traceVariant == 4 && !tlas) {
+    if constexpr (!kList && !kRays) if (traceVariant == 4 && !tlas) {
         // schedule 4: one persistent launch renders the whole pass (pt_wf_fused); then the ordered pixel write and the counter fold
         if ((e = hipMemsetAsync(B.chunkHeads, 0, sizeof(uint32_t), stream)) != hipSuccess) return e;
         const uint32_t maxWaves = B.numSlots / (64u * PT_WF_FUSED_GROUPS);           // contexts never outnumber the frame's slots (array sizes)
@@ -1593,7 +1658,9 @@ hipError_t launch_wavefront(const DScene& S, const PTFrameParams& P, const PTBat
     if (orderAfter && (e = hipStreamWaitEvent(stream, orderAfter, 0)) != hipSuccess) return e;
     if (zeroOutputFirst &&
         (e = hipMemsetAsync(output, 0, (size_t)P.OutputWidth * P.OutputHeight * sizeof(float4), stream)) != hipSuccess) return e;
-    if constexpr (kList) {
+    if constexpr (kRays) {
+        hipLaunchKernelGGL(pt_wf_resolve_rays, dim3(nbPass), dim3(256), 0, stream, P, tm, B, (PTRadiance*)output);
+    } else if constexpr (kList) {
         // pixels outside the list keep Accumulated, bit for bit: one copy of the frame, then the resolve overwrites the listed blocks
         if (accumulated &&
             (e = hipMemcpyAsync(output, accumulated, (size_t)P.OutputWidth * P.OutputHeight * sizeof(float4), hipMemcpyDeviceToDevice, stream)) != hipSuccess) return e;
@@ -1622,4 +1689,14 @@ hipError_t pt_launch_wavefront_list(const DScene& S, const PTFrameParams& P, con
 {
     if (traceVariant == 4) return hipErrorNotSupported;
     return launch_wavefront(S, P, batch, accumulated, output, lm, B, gstats, fullStats, stream, orderAfter, false, launchesOut, traceVariant, iterationsOverride);
+}
+
+hipError_t pt_launch_wavefront_rays(const DScene& S, const PTFrameParams& P, const PTRayMap& rm, PTRadiance* out, const PTWfBuffers& B,
+                                    unsigned long long* gstats, bool fullStats, hipStream_t stream, uint32_t* launchesOut, int traceVariant,
+                                    uint32_t iterationsOverride)
+{
+    if (traceVariant == 4) return hipErrorNotSupported;
+    PTBatch batch = {};
+    batch.count = 1u;
+    return launch_wavefront(S, P, batch, nullptr, (float4*)out, rm, B, gstats, fullStats, stream, nullptr, false, launchesOut, traceVariant, iterationsOverride);
 }

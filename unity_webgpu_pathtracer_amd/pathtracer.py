@@ -340,6 +340,74 @@ class PathTracer:
         cur.wait_stream(ext)                   # torch's later work sees the results -- and any reuse of these buffers comes after
         return (hits, surf) if surface else hits
 
+    # ---- radiance queries (include/ptmi_plugin.h Part 8)
+    def _radiance_params(self, params, seed=0, current_sample=0, spp=None):
+        p = abi.PTFrameParams()
+        C.memmove(C.byref(p), C.byref(params or self.params(seed=seed)), C.sizeof(p))
+        if params is None:
+            p.RngSeedRoot, p.CurrentSample = seed & 0xFFFFFFFF, current_sample
+        if spp is not None:
+            p.SamplesPerPass = spp
+        return p
+
+    def camera_rays(self, pixels=None, seed: int = 0, current_sample: int = 0, params: abi.PTFrameParams = None):
+        """PTCameraRays: the rays the render starts the first sample of its pixels with, as radiance() takes them.
+
+        pixels: None = every pixel in index order (k = y * width + x); else pixel indices (uint32), as a numpy array or as a torch
+          tensor on this context's device (int32 or uint32 storage).  An index outside the frame gives a NaN direction and rng 0.
+        The camera, frame size, seed and CurrentSample are those of `params` when given, else of this tracer with `seed` and
+        `current_sample`.  Returns (n, 8) float32 rows -- origin xyz, direction xyz, RNG state bits, 0 -- as a device tensor when
+        `pixels` is a tensor, else as numpy."""
+        import torch
+        p = self._radiance_params(params, seed, current_sample)
+        dev = torch.device(f"cuda:{self.device}")
+        as_numpy = not isinstance(pixels, torch.Tensor)
+        if pixels is None:
+            idx, n = None, p.OutputWidth * p.OutputHeight
+        elif as_numpy:
+            idx = torch.from_numpy(np.ascontiguousarray(pixels, dtype=np.uint32).reshape(-1).view(np.int32)).to(dev)
+            n = idx.numel()
+        else:
+            assert pixels.device == dev and pixels.dim() == 1 and pixels.is_contiguous() and pixels.element_size() == 4, (pixels.device, pixels.shape, pixels.dtype)
+            idx, n = pixels, pixels.numel()
+        rays = torch.empty((n, 8), dtype=torch.float32, device=dev)
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
+        ext.wait_stream(cur)
+        plugin.check(self.lib.PTCameraRays(self.ctx, C.byref(p), idx.data_ptr() if idx is not None and n else None, n, rays.data_ptr()))
+        cur.wait_stream(ext)
+        return rays.cpu().numpy() if as_numpy else rays
+
+    def radiance(self, rays, spp: int = 1, params: abi.PTFrameParams = None):
+        """Path-trace the radiance arriving along a batch of rays on the GPU, with the render's own code and settings.
+
+        rays: (n, 8) float32 -- origin xyz, unit direction xyz, RNG state, reserved (0) per row (PTRadianceRay; columns 6 and 7
+          are uint32 bits).  `spp` samples per ray; bounces, roulette, firefly filter from `params` (default: this tracer's).
+          numpy array  -> PTTraceRadianceHost, returns numpy;
+          torch tensor on this context's device -> PTTraceRadiance zero-copy, ordered against torch's current stream both ways
+          (no host synchronisation), returns a device tensor.
+        Returns (n, 4) float32 = mean rgb, RNG state after the last sample (view column 3 as uint32); feeding that state back in
+        column 6 continues the chain."""
+        p = self._radiance_params(params, spp=spp)
+        if isinstance(rays, np.ndarray):
+            r = np.ascontiguousarray(rays, dtype=np.float32)
+            assert r.ndim == 2 and r.shape[1] == 8, r.shape
+            n = r.shape[0]
+            out = np.empty((n, 4), np.float32)
+            plugin.check(self.lib.PTTraceRadianceHost(self.ctx, C.byref(p), r.ctypes.data, n, out.ctypes.data))
+            return out
+        import torch
+        assert rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 8 and rays.is_contiguous(), (rays.dtype, rays.shape)
+        dev = rays.device
+        n = rays.shape[0]
+        out = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
+        ext.wait_stream(cur)                   # the rays and the fresh output are ready before the query runs
+        plugin.check(self.lib.PTTraceRadiance(self.ctx, C.byref(p), rays.data_ptr(), n, out.data_ptr()))
+        cur.wait_stream(ext)                   # torch's later work sees the results -- and any reuse of these buffers comes after
+        return out
+
     def camera_ray(self, x: float, y: float, params: abi.PTFrameParams = None) -> np.ndarray:
         """The pinhole ray through the centre of pixel (x, y): util/camera.hlsl:13-42 without jitter and lens, in float32 with
         the device's operation order.  Returns one (8,) float32 ray row with tmax = PT_FAR_PLANE."""

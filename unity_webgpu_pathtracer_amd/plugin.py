@@ -88,6 +88,10 @@ sig = {
     "PTRenderPassActiveTo": (i32, [vp, C.POINTER(abi.PTFrameParams), i32, vp, vp]),
     "PTAccumulateMomentsActive": (i32, [vp, C.POINTER(abi.PTFrameParams), i32]),
     "PTAccumulateMomentsActiveTo": (i32, [vp, C.POINTER(abi.PTFrameParams), i32, vp, vp]),
+    # Part 8 (radiance queries)
+    "PTCameraRays": (i32, [vp, C.POINTER(abi.PTFrameParams), vp, C.c_uint64, vp]),
+    "PTTraceRadiance": (i32, [vp, C.POINTER(abi.PTFrameParams), vp, C.c_uint64, vp]),
+    "PTTraceRadianceHost": (i32, [vp, C.POINTER(abi.PTFrameParams), vp, C.c_uint64, vp]),
     "PTGetLastError": (C.c_char_p, []), "PTGetVersion": (i32, []),
 }
 EXPORTED_SYMBOLS = list(sig)
