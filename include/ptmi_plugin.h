@@ -168,7 +168,7 @@ typedef struct PTStats {
     uint64_t pixelsWritten;        /* Output texels written (16 B each)                    */
     uint64_t pixelsRead;           /* AccumulatedOutput texels read (16 B each)            */
     uint64_t maxStackDepth;        /* deepest traversal stack seen (reference limit is 32) */
-    uint64_t stackOverflows;       /* rays that would have exceeded BVH_STACK_SIZE         */
+    uint64_t stackOverflows;       /* walks that dropped a stack entry (Part 3: the overflow rule) */
     uint64_t tlasNodeVisits;       /* HAS_TLAS: TLAS nodes read (64 B each)                */
     uint64_t instanceVisits;       /* HAS_TLAS: BLAS instances entered (144 B each)        */
 } PTStats;
@@ -365,8 +365,14 @@ PT_API int PTSetSubFrames(PTContext* ctx, int subFrames);
  * Semantics (the shader's rules, util/bvh.hlsl and util/tlas.hlsl, not new ones):
  *  - Flat scene: hits are accepted for 1e-4 < t < tmax (util/bvh.hlsl:47).  The direction is NOT normalised: t is the ray
  *    parameter (origin + t * direction).  PT_QUERY_CLOSEST returns, bit for bit, the record of the render's closest-hit walk
- *    started at distance tmax (and of the CPU oracle's oracle_trace_uv).  The 32-entry traversal stack and its overflow rule
- *    (entries beyond 32 are dropped) are the shader's.
+ *    started at distance tmax (and of the CPU oracle's oracle_trace_uv).
+ *  - The overflow rule of the traversal stacks, for the render and for every query alike.  Both stacks -- the CWBVH stack of a
+ *    flat scene or of one instance, and the TLAS stack -- hold 32 entries.  A push at index >= 32 stores nothing but still
+ *    advances the stack pointer.  A pop from an index >= 32 yields nothing and the walk pops again.  The walk ends when the
+ *    pointer reaches 0 without having yielded an entry.  A ray whose TLAS walk dropped at least one entry adds 1 to
+ *    PTStats.stackOverflows, once per ray, in addition to the 1 that each of its CWBVH walks (one per instance entered) adds
+ *    when it dropped an entry.  What hung on a dropped entry is not visited: such a ray may miss geometry that it crosses.
+ *    (The reference shader writes past a local array there, so there is no behaviour of its own to keep.)
  *  - HAS_TLAS scene (util/tlas.hlsl): the direction is normalised for the TLAS walk, triangles accept LOCAL parameters
  *    t > 0 (not 1e-4), and a closest hit's t is the WORLD-space distance length(position - origin); later instances compare
  *    their local parameters against it (the reference's quirk).  For a parametric t, pass unit directions.  An any-hit

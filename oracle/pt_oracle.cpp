@@ -476,6 +476,15 @@ bool RayIntersectTLAS(Ctx& c, const Ray& ray, RayHit& hit, bool isShadowRay)
     bool hitFound = false;
     uint32_t stack[PT_BVH_STACK_SIZE];
     uint32_t nodeIndex = 0, stackPtr = 0;
+    bool overflowed = false;
+    // The pop of the overflow rule (ptmi_plugin.h, Part 3): entries at index >= 32 were never stored, yield nothing and popping
+    // goes on -- so the next entry that can be yielded is the one below min(stackPtr, 32).  false: nothing left, the walk is over.
+    auto pop = [&]() -> bool {
+        stackPtr = stackPtr < PT_BVH_STACK_SIZE ? stackPtr : PT_BVH_STACK_SIZE;
+        if (stackPtr == 0) return false;
+        nodeIndex = stack[--stackPtr];
+        return true;
+    };
     const float* T = S.tlas;
     while (true) {
         uint32_t no = nodeIndex * 16u;
@@ -502,12 +511,12 @@ bool RayIntersectTLAS(Ctx& c, const Ray& ray, RayHit& hit, bool isShadowRay)
                 uint32_t t = left; left = right; right = t;
             }
             if (dist1 == PT_FAR_PLANE) {
-                if (stackPtr > 0) nodeIndex = stack[--stackPtr];
-                else break;
+                if (!pop()) break;
             } else {
                 nodeIndex = left;
                 if (dist2 != PT_FAR_PLANE) {
                     if (stackPtr < PT_BVH_STACK_SIZE) stack[stackPtr] = right;
+                    else overflowed = true;
                     stackPtr++;
                 }
             }
@@ -518,12 +527,12 @@ bool RayIntersectTLAS(Ctx& c, const Ray& ray, RayHit& hit, bool isShadowRay)
                 uint32_t instanceIndex = pt_asuint(T[S.tlasIndexOffset + firstInstance + i]);
                 bool stopNow = false;
                 hitFound = RayIntersectBvhInstance(c, ray, S.instances[instanceIndex], isShadowRay, hit, stopNow) | hitFound;
-                if (stopNow) return true;
+                if (stopNow) { if (overflowed) c.st.stackOverflows++; return true; }
             }
-            if (stackPtr > 0) nodeIndex = stack[--stackPtr];
-            else break;
+            if (!pop()) break;
         }
     }
+    if (overflowed) c.st.stackOverflows++;
     return hitFound;
 }
 
@@ -1545,6 +1554,42 @@ int oracle_trace_uv(const PTSceneDesc* scene, const OracleRay* rays, uint64_t n,
     }
     if (outNodeVisits) *outNodeVisits = c.st.nodeVisits;
     if (outTriTests) *outTriTests = c.st.triTests;
+    return 0;
+}
+
+// The ray queries of include/ptmi_plugin.h Part 3 (PTTraceRays) restated: the scene's own walk -- RayIntersectTLAS for a HAS_TLAS
+// scene, RayIntersectBvh otherwise -- with the record and the counters of the GPU query kernels (see pt_oracle.h).
+int oracle_trace_rays(const PTSceneDesc* scene, const OracleRay* rays, uint64_t n, float* out4, PTStats* stats)
+{
+    if (!scene || !rays || !out4) return -1;
+    SceneView S = MakeView(scene);
+    PTFrameParams P;
+    memset(&P, 0, sizeof(P));
+    Ctx c;
+    c.S = &S; c.P = &P; memset(&c.st, 0, sizeof(PTStats)); c.shadowAnyHit = false; c.nanRayEarlyOut = true; c.opt = nullptr;
+    for (uint64_t i = 0; i < n; i++) {
+        Ray r = {V3(rays[i].origin[0], rays[i].origin[1], rays[i].origin[2]),
+                 V3(rays[i].direction[0], rays[i].direction[1], rays[i].direction[2])};
+        const float tmax = rays[i].tmax;
+        const bool anyHit = rays[i].kind != 0.0f;
+        RayHit hit;
+        memset(&hit, 0, sizeof(hit));
+        hit.distance = tmax;
+        hit.triIndex = 0xFFFFFFFFu;
+        if (anyHit) c.st.shadowRays++; else c.st.closestHitRays++;
+        bool found = false;
+        if (tmax > 0.0f) {                                  // NaN, 0, negative: a miss by definition, no walk
+            c.shadowAnyHit = anyHit;
+            if (S.hasTlas) found = RayIntersectTLAS(c, r, hit, anyHit);       // closest: with the instance epilogue (world-space distance)
+            else { RayIntersectBvh(c, r, hit, true); found = hit.distance < tmax; }      // the shadow path = the loop without the attribute fetch
+        }
+        const uint32_t prim = found ? hit.triIndex : 0xFFFFFFFFu;
+        out4[i * 4 + 0] = hit.distance;
+        out4[i * 4 + 1] = found ? hit.barycentric.x : 0.0f;
+        out4[i * 4 + 2] = found ? hit.barycentric.y : 0.0f;
+        memcpy(&out4[i * 4 + 3], &prim, 4);
+    }
+    if (stats) *stats = c.st;
     return 0;
 }
 

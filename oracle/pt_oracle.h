@@ -70,6 +70,13 @@ int oracle_trace(const PTSceneDesc* scene, const OracleRay* rays, uint64_t n, fl
  * (BVH8_CWBVH::Intersect, tiny_bvh.h:7006-7114; oracle/ref_driver_cwbvh.cpp) by tests/test_oracle.py. */
 int oracle_trace_uv(const PTSceneDesc* scene, const OracleRay* rays, uint64_t n, float* out4, uint64_t* outNodeVisits, uint64_t* outTriTests);
 
+/* Explicit rays as the GPU ray queries (include/ptmi_plugin.h Part 3) answer them: through RayIntersectTLAS when the scene has
+ * HAS_TLAS, through RayIntersectBvh otherwise.  rays[i].kind 0 = closest hit, otherwise any hit (the walk stops at the first accepted
+ * triangle; give such rays tmax = PT_FAR_PLANE).  out4[i] = {t, u, v, primitive bits}, {tmax, 0, 0, 0xFFFFFFFF} on a miss; t is the
+ * world-space distance for a HAS_TLAS closest hit.  stats (optional): the counters of the batch as the query kernels count them
+ * (rays, nodeVisits, triTests, attrFetches, maxStackDepth, stackOverflows, tlasNodeVisits, instanceVisits). */
+int oracle_trace_rays(const PTSceneDesc* scene, const OracleRay* rays, uint64_t n, float* out4, PTStats* stats);
+
 /* Scalar entry points for unit tests. */
 float    oracle_random_float(uint32_t* state);                       /* util/random.hlsl:12-16 */
 float    oracle_math(int fn, float x, float y);                      /* ptmi_math.h: 0 sin 1 cos 2 log 3 log2 4 exp2 5 pow 6 acos 7 asin 8 sqrt 9 rcp 10 atan2(x = y-arg, y = x-arg) 11 fmod 12 wrap01 (closed form) 13 wrap01 (literal loops) */

@@ -66,6 +66,8 @@ def load_oracle():
         lib.oracle_trace.argtypes = [C.POINTER(abi.PTSceneDesc), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.oracle_trace_uv.restype = C.c_int
         lib.oracle_trace_uv.argtypes = [C.POINTER(abi.PTSceneDesc), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        lib.oracle_trace_rays.restype = C.c_int
+        lib.oracle_trace_rays.argtypes = [C.POINTER(abi.PTSceneDesc), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(abi.PTStats)]
         lib.oracle_random_float.restype = C.c_float
         lib.oracle_random_float.argtypes = [C.POINTER(C.c_uint32)]
         lib.oracle_math.restype = C.c_float
@@ -313,6 +315,19 @@ def trace_uv(buffers: SceneBuffers, rays: np.ndarray):
     rc = lib.oracle_trace_uv(C.byref(buffers.desc), rays.ctypes.data, n, out.ctypes.data, C.byref(nv), C.byref(tt))
     assert rc == 0
     return out, nv.value, tt.value
+
+
+def trace_rays(buffers: SceneBuffers, rays: np.ndarray):
+    """The ray queries restated (oracle_trace_rays): the scene's own walk, two-level when it has a TLAS, over explicit rays
+    (kind 0 closest hit, otherwise any hit) -> (out[n,4] = t, u, v, prim bits; PTStats of the batch)."""
+    lib = load_oracle()
+    rays = np.ascontiguousarray(rays, dtype=ORACLE_RAY_DTYPE)
+    n = rays.shape[0]
+    out = np.zeros((n, 4), dtype=np.float32)
+    st = abi.PTStats()
+    rc = lib.oracle_trace_rays(C.byref(buffers.desc), rays.ctypes.data, n, out.ctypes.data, C.byref(st))
+    assert rc == 0
+    return out, st
 
 
 def env_probe(buffers: SceneBuffers, params, what: int, values: np.ndarray):

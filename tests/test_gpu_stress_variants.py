@@ -27,6 +27,26 @@ for name, s, w, h, spp, sched in (("zoo", scenes.material_zoo(), 128, 80, 3, 1),
     st = pt.stats().as_dict()
     out[name + "_stats"] = np.array([st[k] for k in sorted(st)], dtype=np.uint64)
     pt.close()
+# more than 32 pending entries (tests/stack_cases.py): 31 of the 32 stack entries live in the slab, the rest is dropped by the overflow rule
+sys.path.insert(0, sys.argv[1] + "/tests")
+import stack_cases as sc
+for case in (sc.deep_cwbvh(40), sc.deep_tlas(48, floor=True)):
+    pt = case.tracer(48, 32, samplesPerPass=2, schedule=1)
+    pt.set_stats_level(1)
+    pt.render_pass(pt.params(seed=0x57E55))
+    out[case.name] = pt.readback()
+    st = pt.stats().as_dict()
+    out[case.name + "_stats"] = np.array([st[k] for k in sorted(st)], dtype=np.uint64)
+    pt.close()
+for case in (sc.deep_cwbvh(40), sc.deep_tlas(48)):
+    pt = case.tracer()
+    pt.set_stats_level(1)
+    for fam, f in case.families.items():
+        out[case.name + "_" + fam] = pt.trace_rays(sc.pad128(f["rays"]))
+        out[case.name + "_" + fam + "_any"] = pt.trace_rays(sc.pad128(f["rays"]), any_hit=True)
+    st = pt.stats().as_dict()
+    out[case.name + "_query_stats"] = np.array([st[k] for k in sorted(st)], dtype=np.uint64)
+    pt.close()
 np.savez(sys.argv[2], **out)
 '''
 
@@ -50,3 +70,29 @@ def test_small_stack_build_is_bit_exact(tmp_path, oracle):
         d = st.as_dict()
         assert np.array_equal(got[name + "_stats"], np.array([d[k] for k in sorted(d)], dtype=np.uint64)), name
         assert d["maxStackDepth"] >= 2                              # deeper than the stress build's LDS part: the slab was used
+    # the deep-stack cases: a frame each (schedule 1) against the oracle, and the query batches against the closed-form records
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import stack_cases as sc
+    for case in (sc.deep_cwbvh(40), sc.deep_tlas(48, floor=True)):
+        p = scenes.frame_params(case.scene, 48, 32, spp=2, seed=0x57E55)
+        ref, st = oracle.render(case.buffers(oracle), p, shadow_any_hit=True)
+        assert np.array_equal(got[case.name].view(np.uint32), ref.view(np.uint32)), case.name
+        d = st.as_dict()
+        assert np.array_equal(got[case.name + "_stats"], np.array([d[k] for k in sorted(d)], dtype=np.uint64)), case.name
+        assert d["stackOverflows"] > 0
+    for case in (sc.deep_cwbvh(40), sc.deep_tlas(48)):
+        buffers = case.buffers(oracle)
+        total = {}
+        for fam, f in case.families.items():
+            n = len(f["rays"])
+            row = np.arange(128) % n
+            assert np.array_equal(got[case.name + "_" + fam].view(np.uint32), f["expected"][row].view(np.uint32)), (case.name, fam)
+            assert np.array_equal(got[case.name + "_" + fam + "_any"][:, 3].view(np.uint32) != sc.MISS, f["hit"][row]), (case.name, fam)
+            for kind in (0.0, 1.0):
+                rays = sc.pad128(f["rays"])
+                rays[:, 7] = kind
+                _, st = oracle.trace_rays(buffers, rays.view(oracle.ORACLE_RAY_DTYPE).reshape(-1))
+                for k, v in st.as_dict().items():
+                    total[k] = max(total.get(k, 0), v) if k == "maxStackDepth" else total.get(k, 0) + v
+        assert np.array_equal(got[case.name + "_query_stats"], np.array([total[k] for k in sorted(total)], dtype=np.uint64)), case.name
+        assert total["stackOverflows"] == 2 * 128

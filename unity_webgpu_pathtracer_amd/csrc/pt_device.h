@@ -456,6 +456,17 @@ PT_DEV bool traverse_instance(const DScene& S, v3 wo, v3 wd, uint32_t instIndex,
     return rec.h.t < PT_FAR_PLANE;
 }
 
+// The pop of the overflow rule (ptmi_plugin.h, Part 3) for the TLAS stack: entries at index >= 32 were never stored, yield nothing
+// and popping goes on -- so the next entry that can be yielded is the one below min(sp, 32).  false: nothing left, the walk is over.
+// No index >= PT_BVH_STACK_SIZE is formed.
+PT_DEV bool tlas_stack_pop(const uint32_t (&stack)[PT_BVH_STACK_SIZE], uint32_t& sp, uint32_t& nodeIndex)
+{
+    sp = sp < PT_BVH_STACK_SIZE ? sp : PT_BVH_STACK_SIZE;
+    if (sp == 0u) return false;
+    nodeIndex = stack[--sp];
+    return true;
+}
+
 // tlas.hlsl:236-332
 template <bool STATS, class ST>
 PT_DEV bool traverse_tlas(const DScene& S, v3 O, v3 dir, bool isShadow, HitRecord& rec, ST& st, Counters& cn)
@@ -463,7 +474,7 @@ PT_DEV bool traverse_tlas(const DScene& S, v3 O, v3 dir, bool isShadow, HitRecor
     if (pt_isnan(O.x) || pt_isnan(O.y) || pt_isnan(O.z) || pt_isnan(dir.x) || pt_isnan(dir.y) || pt_isnan(dir.z)) return false;
     const v3 D = normalize3(dir);
     const v3 rD = mk3(1.0f / D.x, 1.0f / D.y, 1.0f / D.z);
-    bool hitFound = false;
+    bool hitFound = false, overflow = false;
     uint32_t stack[PT_BVH_STACK_SIZE];
     uint32_t nodeIndex = 0u, sp = 0u;
     const float* T = S.tlas;
@@ -487,12 +498,12 @@ PT_DEV bool traverse_tlas(const DScene& S, v3 O, v3 dir, bool isShadow, HitRecor
                 uint32_t t = left; left = right; right = t;
             }
             if (dist1 == PT_FAR_PLANE) {
-                if (sp > 0u) nodeIndex = stack[--sp];
-                else break;
+                if (!tlas_stack_pop(stack, sp, nodeIndex)) break;
             } else {
                 nodeIndex = left;
                 if (dist2 != PT_FAR_PLANE) {
                     if (sp < PT_BVH_STACK_SIZE) stack[sp] = right;
+                    else if (STATS) overflow = true;
                     sp++;
                 }
             }
@@ -503,12 +514,15 @@ PT_DEV bool traverse_tlas(const DScene& S, v3 O, v3 dir, bool isShadow, HitRecor
                 const uint32_t instanceIndex = pt_asuint(T[S.tlasIndexOffset + firstInstance + i]);
                 bool stopNow = false;
                 hitFound = traverse_instance<STATS>(S, O, dir, instanceIndex, isShadow, rec, st, cn, stopNow) | hitFound;
-                if (stopNow) return true;
+                if (stopNow) {
+                    if (STATS && overflow) cn.overflows++;
+                    return true;
+                }
             }
-            if (sp > 0u) nodeIndex = stack[--sp];
-            else break;
+            if (!tlas_stack_pop(stack, sp, nodeIndex)) break;
         }
     }
+    if (STATS && overflow) cn.overflows++;
     return hitFound;
 }
 

@@ -575,6 +575,7 @@ __global__ __launch_bounds__(64 * WAVES, PT_WF_TLAS_MIN_WAVES) void pt_wf_trace_
     RayState rs;
     rs.sp = 0u; rs.anyHit = false; rs.overflow = false;
     bool have = false, inBlas = false, needPop = false, hitFound = false;
+    bool toverflow = false;                                                   // STATS: the ray's TLAS walk dropped an entry
     uint32_t mySlot = 0u, myKind = 0u, cursor = kCached ? nItems : 0u;       // WAVES > 1: no chunk yet
     bool more = kCached;                                                      // chunks may remain (WAVES > 1)
     v3 O = mk3(0.0f), rD = mk3(0.0f);
@@ -588,13 +589,19 @@ __global__ __launch_bounds__(64 * WAVES, PT_WF_TLAS_MIN_WAVES) void pt_wf_trace_
     auto tpush = [&](uint32_t v) {
         if (tsp < PT_WF_TLAS_LDS_STACK) { tlds[tsp * 64u] = (tentry_t)v; asm volatile("" ::: "memory"); }
         else if (tsp < PT_BVH_STACK_SIZE) B.tlasSpill[spill_row(PT_LDS_WORD(s_gw[wv])) * PT_BVH_STACK_SIZE + tsp] = v;
+        else if (STATS) toverflow = true;
         tsp++;
     };
-    auto tpop = [&]() -> uint32_t {
+    // The pop of the overflow rule (ptmi_plugin.h, Part 3; tlas_stack_pop in pt_device.h): entries at index >= 32 were never stored,
+    // yield nothing and popping goes on, so the entry yielded is the one below min(tsp, 32).  false: nothing left, the ray is done.
+    // The clamp sits on the slab branch: a pointer below PT_WF_TLAS_LDS_STACK needs none.
+    auto tpop = [&]() -> bool {
+        if (tsp == 0u) return false;
         --tsp;
-        if (tsp < PT_WF_TLAS_LDS_STACK) { uint32_t v = tlds[tsp * 64u]; asm volatile("" : "+v"(v)); return v; }
-        if (tsp < PT_BVH_STACK_SIZE) return B.tlasSpill[spill_row(PT_LDS_WORD(s_gw[wv])) * PT_BVH_STACK_SIZE + tsp];
-        return 0u;
+        if (tsp < PT_WF_TLAS_LDS_STACK) { uint32_t v = tlds[tsp * 64u]; asm volatile("" : "+v"(v)); nodeIndex = v; return true; }
+        tsp = tsp < PT_BVH_STACK_SIZE ? tsp : PT_BVH_STACK_SIZE - 1u;
+        nodeIndex = B.tlasSpill[spill_row(PT_LDS_WORD(s_gw[wv])) * PT_BVH_STACK_SIZE + tsp];
+        return true;
     };
 
     while (true) {
@@ -639,7 +646,7 @@ __global__ __launch_bounds__(64 * WAVES, PT_WF_TLAS_MIN_WAVES) void pt_wf_trace_
                     rD = mk3(1.0f / D.x, 1.0f / D.y, 1.0f / D.z);
                     rs.hit.t = PT_FAR_PLANE;
                     rs.anyHit = myKind != 0u;
-                    nodeIndex = 0u; tsp = 0u; instLeft = 0u; needPop = false; inBlas = false;
+                    nodeIndex = 0u; tsp = 0u; instLeft = 0u; needPop = false; inBlas = false; toverflow = false;
                     have = true;
                 }
             }
@@ -687,8 +694,7 @@ __global__ __launch_bounds__(64 * WAVES, PT_WF_TLAS_MIN_WAVES) void pt_wf_trace_
                     // lanes whose instance ends in this wave iteration) instead of stepping through the TLAS at 1-2 lanes per instruction
                     if (PT_WF_TLAS_CONT > 1u && stepT > 0u && (uint32_t)__popcll(__ballot(true)) < PT_WF_TLAS_CONT) break;
                     if (needPop) {
-                        if (tsp == 0u) { finished = true; break; }
-                        nodeIndex = tpop();
+                        if (!tpop()) { finished = true; break; }
                         needPop = false;
                     }
                     // visit TLAS node nodeIndex (tlas.hlsl:246-331)
@@ -735,6 +741,7 @@ __global__ __launch_bounds__(64 * WAVES, PT_WF_TLAS_MIN_WAVES) void pt_wf_trace_
                 if (finished) {
                     if (myKind == 0u) { if (!(rs.hit.t < PT_FAR_PLANE)) store_miss(B, mySlot); }
                     else store_occlusion(B, myKind, mySlot, false);
+                    if (STATS && toverflow) cn.overflows++;
                     have = false;
                 }
             }
@@ -769,7 +776,11 @@ __global__ __launch_bounds__(64 * WAVES, PT_WF_TLAS_MIN_WAVES) void pt_wf_trace_
                     if (STATS && rs.overflow) cn.overflows++;
                     inBlas = false;
                     if (rs.anyHit) {
-                        if (hitFound) { store_occlusion(B, myKind, mySlot, true); have = false; }       // stopNow (tlas.hlsl:196-200)
+                        if (hitFound) {                                                                  // stopNow (tlas.hlsl:196-200)
+                            store_occlusion(B, myKind, mySlot, true);
+                            if (STATS && toverflow) cn.overflows++;
+                            have = false;
+                        }
                     } else if (hitFound) {
                         // tlas.hlsl:208-229: world-space hit position and distance of the instance that improved the hit
                         if (STATS) cn.attrFetches++;
