@@ -13,8 +13,7 @@ import pytest
 
 from unity_webgpu_pathtracer_amd import abi, plugin
 from unity_webgpu_pathtracer_amd.pathtracer import list_slot_to_pixel, select_blocks
-from test_denoise import _resources as _resources_plain
-from test_kernel_resources import _resources as _resources_wavefront
+from kernel_resources import resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ADAPTIVE_SYMBOLS = ["PTAdaptiveBegin", "PTAdaptiveEnd", "PTSetActiveBlocks", "PTSelectActiveBlocks", "PTGetActiveBlocks",
@@ -153,9 +152,9 @@ def test_list_mapping_with_all_blocks_is_the_frame_mapping():
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not installed")
 def test_list_mapped_kernels_keep_the_register_budget():
     with ThreadPoolExecutor(3) as ex:
-        fa = ex.submit(_resources_wavefront, "pt_wavefront.hip", True)
-        fb = ex.submit(_resources_wavefront, "pt_wavefront.hip", False)
-        fm = ex.submit(_resources_plain, "pt_moments.hip")
+        fa = ex.submit(resources, "pt_wavefront.hip", "a")
+        fb = ex.submit(resources, "pt_wavefront.hip", "b")
+        fm = ex.submit(resources, "pt_moments.hip")
         res_a, res_b, res_m = fa.result(), fb.result(), fm.result()
     for unit, res in (("a", res_a), ("b", res_b)):
         shade = {k: v for k, v in res.items() if "pt_wf_shadeILb0E" in k and "PTListMap" in k}

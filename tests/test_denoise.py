@@ -3,7 +3,6 @@ and the float64 numpy restatement of the a-trous filter with its
 holds the GPU kernels to this restatement."""
 import ctypes as C
 import os
-import re
 import shutil
 import subprocess
 import tempfile
@@ -11,6 +10,7 @@ import tempfile
 import numpy as np
 import pytest
 
+from kernel_resources import resources
 from unity_webgpu_pathtracer_amd import abi, plugin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -221,32 +221,6 @@ def test_denoise_argument_errors_without_context():
 # ---------------------------------------------------------------------------------------------------------------------------
 # kernel resources (hipcc -Rpass-analysis=kernel-resource-usage, as tests/test_kernel_resources.py reads them)
 # ---------------------------------------------------------------------------------------------------------------------------
-def _device_flags():
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    flags = re.search(r"^FLAGS\s*:=\s*(.*)$", mk, re.M).group(1).split()
-    hip = re.search(r"^HIPFLAGS\s*:=\s*(.*)$", mk, re.M).group(1)
-    extra = hip.replace("$(FLAGS)", "").replace("--offload-arch=$(ARCH)", "").split()
-    return [f for f in flags if f != "-Wall"] + extra
-
-
-def _resources(src, defines=()):
-    out = subprocess.run(["hipcc", "--offload-arch=gfx950", "--cuda-device-only", "-c", src, "-o", os.devnull,
-                          "-Rpass-analysis=kernel-resource-usage"] + _device_flags() + list(defines),
-                         cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    res, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = res.setdefault(m.group(1), {})
-            continue
-        for key, name in (("VGPRs:", "vgprs"), ("ScratchSize", "scratch"), ("Occupancy", "occupancy"), ("VGPRs Spill", "vgpr_spill"), ("LDS Size", "lds")):
-            m = re.search(re.escape(key) + r"[^0-9]*(\d+)", line)
-            if m and cur is not None and key in line:
-                cur[name] = int(m.group(1))
-    return res
-
-
 # LDS bytes per workgroup and waves per SIMD of the filter kernels
 FILTER_KERNELS = {"pt_denoise_prepass": (0, 8), "pt_denoise_atrous_s1": (12800, 8), "pt_denoise_atrous_s2": (18432, 8),
                   "pt_denoise_atrous_s4": (32768, 5), "pt_denoise_atrous": (0, 8), "pt_denoise_remodulate": (0, 8)}
@@ -255,7 +229,7 @@ FILTER_KERNELS = {"pt_denoise_prepass": (0, 8), "pt_denoise_atrous_s1": (12800, 
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not installed")
 @pytest.mark.parametrize("defines", [(), ("-DPT_Q_LDS_STACK=1",)], ids=["default", "stress"])
 def test_denoise_kernel_resources(defines):
-    res = _resources("pt_denoise.hip", defines)
+    res = resources("pt_denoise.hip", defines=defines)
     g = res["pt_guides"]                                                # CWBVH stack in LDS + the HBM slab: no scratch
     assert g["scratch"] == 0 and g["vgpr_spill"] == 0, g
     assert res["pt_guides_tlas"]["vgpr_spill"] == 0, res["pt_guides_tlas"]

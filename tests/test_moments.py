@@ -14,7 +14,8 @@ import pytest
 
 from unity_webgpu_pathtracer_amd import abi, plugin, scenes
 import test_denoise
-from test_denoise import H5, K3, _lum, _shift, _resources, random_guides
+from kernel_resources import resources
+from test_denoise import H5, K3, _lum, _shift, random_guides
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MOMENTS_SYMBOLS = ["PTAccumulateMoments", "PTAccumulateMomentsTo", "PTGetMomentsInfo", "PTGetMomentsPointer", "PTMeasureNoise",
@@ -345,13 +346,13 @@ def test_filter_restatement_with_no_variance_is_test_denoise():
 # ---------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not installed")
 def test_moments_kernel_resources():
-    res = _resources("pt_moments.hip")
+    res = resources("pt_moments.hip")
     for name in ("pt_moments_accumulate", "pt_noise_blocks", "pt_noise_finish"):
         r = res[name]
         print(f"[resources] {name}: {r}")
         assert r["scratch"] == 0 and r["vgpr_spill"] == 0, (name, r)
     assert res["pt_noise_blocks"]["lds"] <= 2048, res["pt_noise_blocks"]
     assert res["pt_moments_accumulate"]["lds"] == 0
-    r = _resources("pt_denoise.hip")["pt_denoise_prepass_moments"]
+    r = resources("pt_denoise.hip")["pt_denoise_prepass_moments"]
     print(f"[resources] pt_denoise_prepass_moments: {r}")
     assert r["scratch"] == 0 and r["vgpr_spill"] == 0 and r["lds"] == 0, r

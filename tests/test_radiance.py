@@ -10,7 +10,7 @@ from concurrent.futures import ThreadPoolExecutor
 import pytest
 
 from unity_webgpu_pathtracer_amd import abi, plugin
-from test_kernel_resources import _resources
+from kernel_resources import resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RADIANCE_SYMBOLS = ["PTCameraRays", "PTTraceRadiance", "PTTraceRadianceHost"]
@@ -69,8 +69,8 @@ def test_radiance_argument_errors_without_context():
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not installed")
 def test_ray_mapped_kernels_keep_the_register_budget():
     with ThreadPoolExecutor(2) as ex:
-        fa = ex.submit(_resources, "pt_wavefront.hip", True)
-        fb = ex.submit(_resources, "pt_wavefront.hip", False)
+        fa = ex.submit(resources, "pt_wavefront.hip", "a")
+        fb = ex.submit(resources, "pt_wavefront.hip", "b")
         res_a, res_b = fa.result(), fb.result()
     for unit, res in (("a", res_a), ("b", res_b)):
         shade = {k: v for k, v in res.items() if "pt_wf_shadeILb0E" in k and "PTRayMap" in k}

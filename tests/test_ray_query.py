@@ -1,13 +1,13 @@
 """Ray queries (include/ptmi_plugin.h Part 3) without a GPU: exports, struct layouts, argument checks, kernel resources."""
 import ctypes as C
 import os
-import re
 import shutil
 import subprocess
 import tempfile
 
 import pytest
 
+from kernel_resources import resources
 from unity_webgpu_pathtracer_amd import abi, plugin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -63,39 +63,12 @@ def test_query_argument_errors_without_context():
             assert b"flag" in msg or b"SURFACE" in msg, msg
 
 
-def _device_flags():
-    """FLAGS / HIPFLAGS of csrc/Makefile (minus -Wall): the flags pt_query.hip is built with."""
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    flags = re.search(r"^FLAGS\s*:=\s*(.*)$", mk, re.M).group(1).split()
-    hip = re.search(r"^HIPFLAGS\s*:=\s*(.*)$", mk, re.M).group(1)
-    extra = hip.replace("$(FLAGS)", "").replace("--offload-arch=$(ARCH)", "").split()
-    return [f for f in flags if f != "-Wall"] + extra
-
-
-def _resources(src, defines=()):
-    out = subprocess.run(["hipcc", "--offload-arch=gfx950", "--cuda-device-only", "-c", src, "-o", os.devnull,
-                          "-Rpass-analysis=kernel-resource-usage"] + _device_flags() + list(defines),
-                         cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    res, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = res.setdefault(m.group(1), {})
-            continue
-        for key, name in (("VGPRs:", "vgprs"), ("ScratchSize", "scratch"), ("Occupancy", "occupancy"), ("VGPRs Spill", "vgpr_spill"), ("LDS Size", "lds")):
-            m = re.search(re.escape(key) + r"[^0-9]*(\d+)", line)
-            if m and cur is not None and key in line:
-                cur[name] = int(m.group(1))
-    return res
-
-
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not installed")
 @pytest.mark.parametrize("defines", [(), ("-DPT_Q_LDS_STACK=1",)], ids=["default", "stress"])
 def test_query_kernels_have_no_scratch(defines):
     """The CWBVH query kernels keep their whole stack in LDS + the HBM slab: no scratch, no spill, 8 waves per SIMD
     (DESIGN.md "Ray queries").  The HAS_TLAS ones keep the render's TLAS code and at least 4 waves per SIMD."""
-    res = _resources("pt_query.hip", defines)
+    res = resources("pt_query.hip", defines=defines)
     names = ["pt_query_" + m + s for m in ("closest", "anyhit", "surface") for s in ("", "_stats")]
     for n in names:
         assert n in res, (n, sorted(res))

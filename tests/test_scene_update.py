@@ -10,7 +10,7 @@ import tempfile
 import numpy as np
 import pytest
 
-from test_denoise import _resources
+from kernel_resources import resources
 from unity_webgpu_pathtracer_amd import abi, plugin, scenes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -119,7 +119,7 @@ def test_bounce_transforms_follow_bounce_cs():
 
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not installed")
 def test_tlas_kernel_resources():
-    res = _resources("pt_tlas.hip")
+    res = resources("pt_tlas.hip")
     names = {k: v for k, v in res.items() if "pt_tlas_" in k}
     assert len(names) == 3, list(res)
     for k, r in names.items():

@@ -78,11 +78,9 @@ int render_active(PTContext* c, const PTFrameParams* hostParams, int count, floa
         return fail(PT_ERR_UNSUPPORTED, std::string(who) + ": schedule " + std::to_string(schedule) + " has no pass over a block list (schedules 1, 2 and 3 do: PTSetSchedule)");
     if (!dOut) return fail(PT_ERR_INVALID_ARG, std::string(who) + ": output buffer == NULL");
     if ((const float4*)dOut == dAcc) return fail(PT_ERR_INVALID_ARG, std::string(who) + ": dOutput == dAccumulated (inactive pixels are copied from one to the other)");
-    const uint32_t spp = p.SamplesPerPass > 1 ? (uint32_t)p.SamplesPerPass : 1u;
-    const uint32_t bounces = p.MaxRayBounces > 1u ? p.MaxRayBounces : 1u;
-    if (spp > 4095u || bounces > 8191u) return fail(PT_ERR_UNSUPPORTED, "wavefront schedules pack SamplesPerPass <= 4095 and MaxRayBounces <= 8191");
-    const uint64_t m = (uint64_t)spp * (uint64_t)count;
-    const uint64_t maxIt = (uint64_t)spp * (bounces + 2u) + 4u;
+    uint32_t maxIterations;
+    if ((rc = wavefront_limits(p, maxIterations))) return rc;
+    const uint64_t m = (uint64_t)(p.SamplesPerPass > 1 ? p.SamplesPerPass : 1) * (uint64_t)count;
 
     const PTTileMap cover = pt_make_tile_map(p, c->rank, c->world);
     std::vector<uint32_t> ids;
@@ -117,31 +115,28 @@ int render_active(PTContext* c, const PTFrameParams* hostParams, int count, floa
 
     EventPair ep;
     if (c->profiling && (rc = take_event_pair(c, ep))) return rc;
-    if (c->nextSet >= c->numSets) c->nextSet = 0u;
-    PTContext::WfSet& set = c->sets[c->nextSet];
-    c->nextSet = (c->nextSet + 1u) % c->numSets;
+    PTContext::WfSet& set = next_wavefront_set(c);
     const uint32_t slotsPerPass = (uint32_t)table.size() * 256u;
     // the arena only ever grows; a list of another length is a new carving of the same memory (ensure_wavefront)
-    if ((rc = ensure_wavefront(c, set, slotsPerPass * (uint32_t)count, (uint32_t)(maxIt > 65536u ? 65536u : maxIt)))) return rc;
+    if ((rc = ensure_wavefront(c, set, slotsPerPass * (uint32_t)count, maxIterations))) return rc;
     set.wf.slotsPerPass = slotsPerPass;
     // the call's snapshot of {block, sample count}: on the set's stream, before the init kernel.  The kernels never read a counter
     // the host shares between calls -- this call's init may run while the previous call's resolve is still pending.
     if ((rc = set.blockTable.send(table.data(), table.size() * sizeof(uint2), set.stream))) return rc;
-    PTListMap lm;
-    lm.frameBlocksX = A.blocksX;
-    lm.coverW = cover.coverW;
-    lm.coverH = cover.coverH;
-    lm.table = (const uint2*)set.blockTable.dev.ptr;
-
+    PTWfLaunch L = {};
+    L.params = &p;
+    L.batch = batch;
+    L.mapKind = PT_WF_MAP_LIST;
+    L.list.frameBlocksX = A.blocksX;
+    L.list.coverW = cover.coverW;
+    L.list.coverH = cover.coverH;
+    L.list.table = (const uint2*)set.blockTable.dev.ptr;
+    L.accumulated = dAcc;
+    L.output = dOut;
     HIP_TRY(hipEventRecord(set.callEv, c->stream));
-    if (c->update.pending) HIP_TRY(hipStreamWaitEvent(set.stream, c->update.done, 0));
-    if (c->profiling) HIP_TRY(hipEventRecord(ep.start, set.stream));
+    L.orderAfter = set.callEv;              // as a pass (render_to): only the frame copy and the resolve wait for the caller's stream
     uint32_t launches = 0;
-    const bool tuA = schedule == 1 && c->scene.hasTlas == 0u;
-    HIP_TRY((tuA ? pt_launch_wavefront_list : pt_launch_wavefront_list_b)(c->scene, p, batch, dAcc, dOut, lm, set.wf, (unsigned long long*)c->dStats.ptr, c->statsLevel > 0,
-                                                                         set.stream, set.callEv, &launches, trace_variant(schedule), c->wfIterations));
-    if (c->profiling) HIP_TRY(hipEventRecord(ep.stop, set.stream));
-    HIP_TRY(hipEventRecord(set.done, set.stream));
+    if ((rc = enqueue_wavefront(c, set, L, c->profiling ? ep.start.h : nullptr, c->profiling ? ep.stop.h : nullptr, launches))) return rc;
     HIP_TRY(hipStreamWaitEvent(c->stream, set.done, 0));
     if (c->profiling) {
         ep.launches = launches;

@@ -18,46 +18,41 @@ int trace_radiance(PTContext* c, const PTFrameParams& p, const PTRadianceRay* dR
     const int schedule = effective_schedule(c);
     if (schedule < 1 || schedule > 3)
         return fail(PT_ERR_UNSUPPORTED, std::string(who) + ": schedule " + std::to_string(schedule) + " has no pass over a ray list (schedules 1, 2 and 3 do: PTSetSchedule)");
-    const uint32_t spp = p.SamplesPerPass > 1 ? (uint32_t)p.SamplesPerPass : 1u;
-    const uint32_t bounces = p.MaxRayBounces > 1u ? p.MaxRayBounces : 1u;
-    if (spp > 4095u || bounces > 8191u) return fail(PT_ERR_UNSUPPORTED, "wavefront schedules pack SamplesPerPass <= 4095 and MaxRayBounces <= 8191");
+    uint32_t maxIterations;
+    if ((rc = wavefront_limits(p, maxIterations))) return rc;
     if (count == 0) return PT_OK;
-    const uint64_t maxIt = (uint64_t)spp * (bounces + 2u) + 4u;
     HIP_TRY(hipSetDevice(c->device));
-    const bool tuA = schedule == 1 && c->scene.hasTlas == 0u;
     uint32_t used = 0u;                 // bit k: set k carries a chunk of this call
     static_assert(PT_WF_SETS <= 32, "one bit per state set");
     for (uint64_t first = 0; first < count; first += PT_RADIANCE_CHUNK) {
         const uint32_t n = (uint32_t)(count - first < PT_RADIANCE_CHUNK ? count - first : PT_RADIANCE_CHUNK);
         EventPair ep;
         if (c->profiling && (rc = take_event_pair(c, ep))) return rc;
-        if (c->nextSet >= c->numSets) c->nextSet = 0u;
-        PTContext::WfSet& set = c->sets[c->nextSet];
-        used |= 1u << c->nextSet;
-        c->nextSet = (c->nextSet + 1u) % c->numSets;
+        uint32_t k;
+        PTContext::WfSet& set = next_wavefront_set(c, &k);
+        used |= 1u << k;
         const uint32_t numSlots = (n + 255u) & ~255u;
         // the arena only ever grows; a list of another length is a new carving of the same memory (ensure_wavefront)
-        if ((rc = ensure_wavefront(c, set, numSlots, (uint32_t)(maxIt > 65536u ? 65536u : maxIt)))) return rc;
+        if ((rc = ensure_wavefront(c, set, numSlots, maxIterations))) return rc;
         set.wf.slotsPerPass = numSlots;
-        PTRayMap rm;
-        rm.rays = dRays + first;
-        rm.count = n;
-        // the whole chain -- its init kernel reads the rays -- runs after what the context stream holds so far
+        PTWfLaunch L = {};
+        L.params = &p;
+        L.mapKind = PT_WF_MAP_RAYS;
+        L.rays.rays = dRays + first;
+        L.rays.count = n;
+        L.output = dOut + first;
+        // unlike a pass, the WHOLE chain waits for what the context stream holds so far: its init kernel reads the caller's rays
         HIP_TRY(hipEventRecord(set.callEv, c->stream));
         HIP_TRY(hipStreamWaitEvent(set.stream, set.callEv, 0));
-        if (c->update.pending) HIP_TRY(hipStreamWaitEvent(set.stream, c->update.done, 0));
-        if (c->profiling) HIP_TRY(hipEventRecord(ep.start, set.stream));
         uint32_t launches = 0;
-        HIP_TRY((tuA ? pt_launch_wavefront_rays : pt_launch_wavefront_rays_b)(c->scene, p, rm, dOut + first, set.wf, (unsigned long long*)c->dStats.ptr, c->statsLevel > 0,
-                                                                             set.stream, &launches, trace_variant(schedule), c->wfIterations));
-        if (c->profiling) HIP_TRY(hipEventRecord(ep.stop, set.stream));
-        HIP_TRY(hipEventRecord(set.done, set.stream));
+        if ((rc = enqueue_wavefront(c, set, L, c->profiling ? ep.start.h : nullptr, c->profiling ? ep.stop.h : nullptr, launches))) return rc;
         if (c->profiling) {
             ep.launches = launches;
             c->pending.push_back(std::move(ep));
         }
     }
-    // consumers of the context stream see every entry's result (a set that carried several chunks: its last record covers them)
+    // joined after the last chunk, not per sequence: the chunks of a call overlap.  Consumers of the context stream then see every
+    // entry's result (a set that carried several chunks: its last record covers them)
     for (uint32_t k = 0; k < c->numSets; ++k)
         if (used & (1u << k)) HIP_TRY(hipStreamWaitEvent(c->stream, c->sets[k].done, 0));
     return PT_OK;

@@ -36,6 +36,44 @@ int ensure_wavefront(PTContext* c, PTContext::WfSet& set, uint32_t numSlots, uin
     return PT_OK;
 }
 
+int wavefront_limits(const PTFrameParams& p, uint32_t& maxIterations)
+{
+    const uint32_t spp = p.SamplesPerPass > 1 ? (uint32_t)p.SamplesPerPass : 1u;
+    const uint32_t bounces = p.MaxRayBounces > 1u ? p.MaxRayBounces : 1u;
+    if (spp > 4095u || bounces > 8191u) return fail(PT_ERR_UNSUPPORTED, "wavefront schedules pack SamplesPerPass <= 4095 and MaxRayBounces <= 8191");
+    const uint64_t maxIt = (uint64_t)spp * (bounces + 2u) + 4u;
+    maxIterations = (uint32_t)(maxIt > 65536u ? 65536u : maxIt);
+    return PT_OK;
+}
+
+PTContext::WfSet& next_wavefront_set(PTContext* c, uint32_t* index)
+{
+    if (c->nextSet >= c->numSets) c->nextSet = 0u;
+    const uint32_t k = c->nextSet;
+    c->nextSet = (k + 1u) % c->numSets;
+    if (index) *index = k;
+    return c->sets[k];
+}
+
+int enqueue_wavefront(PTContext* c, PTContext::WfSet& set, PTWfLaunch& L, hipEvent_t profStart, hipEvent_t profStop, uint32_t& launches)
+{
+    L.scene = &c->scene;
+    L.buffers = &set.wf;
+    L.counters = (unsigned long long*)c->dStats.ptr;
+    L.fullStats = c->statsLevel > 0;
+    L.stream = set.stream;
+    L.schedule = effective_schedule(c);
+    L.iterationsOverride = c->wfIterations;
+    if (c->update.pending) HIP_TRY(hipStreamWaitEvent(set.stream, c->update.done, 0));     // the trace reads the scene before the resolve's wait
+    if (profStart) HIP_TRY(hipEventRecord(profStart, set.stream));
+    uint32_t n = 0;
+    HIP_TRY(pt_launch_wavefront(L, &n));
+    launches += n;
+    if (profStop) HIP_TRY(hipEventRecord(profStop, set.stream));
+    HIP_TRY(hipEventRecord(set.done, set.stream));
+    return PT_OK;
+}
+
 namespace {
 
 // p: imported and validated (import_frame_params).
@@ -64,10 +102,8 @@ int render_to(PTContext* c, const PTFrameParams& params, float4* dOut, const flo
     case 2:
     case 3:
     case 4: {
-        const uint32_t spp = p->SamplesPerPass > 1 ? (uint32_t)p->SamplesPerPass : 1u;
-        const uint32_t bounces = p->MaxRayBounces > 1u ? p->MaxRayBounces : 1u;
-        if (spp > 4095u || bounces > 8191u) return fail(PT_ERR_UNSUPPORTED, "wavefront schedules pack SamplesPerPass <= 4095 and MaxRayBounces <= 8191");
-        const uint64_t maxIt = (uint64_t)spp * (bounces + 2u) + 4u;
+        uint32_t maxIterations;
+        if ((rc = wavefront_limits(*p, maxIterations))) return rc;
         // A pass may be cut into SUB-FRAMES (PTSetSubFrames): interleaved subsets of the context's 16x16 blocks, each with its own
         // launch sequence on its own state set and stream, all writing the same output frame.  To the kernels a sub-frame is
         // tile ownership (rank + world * j of world * S); to the machine it is what a second pass in flight is -- other kernels to
@@ -78,9 +114,7 @@ int render_to(PTContext* c, const PTFrameParams& params, float4* dOut, const flo
         if (zeroOnce) HIP_TRY(hipMemsetAsync(dOut, 0, (size_t)p->OutputWidth * p->OutputHeight * sizeof(float4), c->stream));
         for (uint32_t j = 0; j < S; ++j) {
             const PTTileMap tmj = S == 1u ? tm : pt_make_tile_map(*p, c->rank + c->world * (int)j, c->world * (int)S);
-            if (c->nextSet >= c->numSets) c->nextSet = 0u;
-            PTContext::WfSet& set = c->sets[c->nextSet];
-            c->nextSet = (c->nextSet + 1u) % c->numSets;
+            PTContext::WfSet& set = next_wavefront_set(c);
             // every set IN USE is carved on the FIRST pass of a frame size (a no-op afterwards): a caller that times passes after a
             // short warm-up must not find the allocation of sets it has not reached yet inside its timed region.  Sets beyond
             // PTSetPassesInFlight are never allocated (0.6 GB each at 1080p).
@@ -88,24 +122,24 @@ int render_to(PTContext* c, const PTFrameParams& params, float4* dOut, const flo
             if ((uint64_t)slotsPerPass * batch.count > 0x3FFFFFFFull) return fail(PT_ERR_UNSUPPORTED, "batch too large: passes x owned pixels exceeds 2^30 slots");
             if (j == 0u)
                 for (uint32_t k = 0; k < c->numSets; ++k) {
-                    if ((rc = ensure_wavefront(c, c->sets[k], slotsPerPass * batch.count, (uint32_t)(maxIt > 65536u ? 65536u : maxIt)))) return rc;
+                    if ((rc = ensure_wavefront(c, c->sets[k], slotsPerPass * batch.count, maxIterations))) return rc;
                     c->sets[k].wf.slotsPerPass = slotsPerPass;
                 }
             // the launch chain runs on the set's own stream; only its resolve (which reads `accumulated` and writes `output`)
             // is ordered after what the caller has enqueued on the context stream so far, the previous pass included
             HIP_TRY(hipEventRecord(set.callEv, c->stream));
-            if (c->update.pending) HIP_TRY(hipStreamWaitEvent(set.stream, c->update.done, 0));     // the trace reads the scene before the resolve's wait
-            if (c->profiling && j == 0u) HIP_TRY(hipEventRecord(ep.start, set.stream));
-            uint32_t n = 0;
-            // the default schedule's kernels (refill trace + shade) come from the translation unit built without the post-RA scheduler,
-            // HAS_TLAS, the fused persistent kernel and the other schedules from the one built with it (csrc/Makefile)
-            const bool tuA = schedule == 1 && c->scene.hasTlas == 0u;
-            HIP_TRY((tuA ? pt_launch_wavefront : pt_launch_wavefront_b)(c->scene, *p, batch, dAcc, dOut, tmj, set.wf, (unsigned long long*)c->dStats.ptr, c->statsLevel > 0, set.stream, set.callEv,
-                                        c->world > 1 && !zeroOnce, &n, trace_variant(schedule), c->wfIterations));
-            launches += n;
-            if (c->profiling && j + 1u == S) HIP_TRY(hipEventRecord(ep.stop, set.stream));
-            HIP_TRY(hipEventRecord(set.done, set.stream));
-            HIP_TRY(hipStreamWaitEvent(c->stream, set.done, 0));          // consumers of the context stream see the finished frame
+            PTWfLaunch L = {};
+            L.params = p;
+            L.batch = batch;
+            L.mapKind = PT_WF_MAP_TILES;
+            L.tiles = tmj;
+            L.accumulated = dAcc;
+            L.output = dOut;
+            L.orderAfter = set.callEv;             // only the resolve waits for the caller's stream: the chain before it overlaps the previous pass
+            L.zeroOutputFirst = c->world > 1 && !zeroOnce;
+            // one EventPair spans the sub-frames: it starts on the first one's stream and stops on the last one's
+            if ((rc = enqueue_wavefront(c, set, L, c->profiling && j == 0u ? ep.start.h : nullptr, c->profiling && j + 1u == S ? ep.stop.h : nullptr, launches))) return rc;
+            HIP_TRY(hipStreamWaitEvent(c->stream, set.done, 0));          // joined per sequence: consumers of the context stream see the finished frame
         }
         break;
     }

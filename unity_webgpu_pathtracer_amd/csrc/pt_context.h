@@ -287,8 +287,6 @@ inline int effective_schedule(const PTContext* c)
     if (c->schedule >= 0) return c->schedule;
     return (c->nodes.used <= 80u * 16u && !c->scene.hasTlas) ? 0 : 1;
 }
-// pt_launch_wavefront's traceVariant of a wavefront schedule: 1 -> 2 (refill), 2 -> 1 (one ray per lane), 3 -> 0 (persistent), 4 -> 4 (fused)
-inline int trace_variant(int schedule) { return schedule == 4 ? 4 : (schedule == 1 ? 2 : (schedule == 2 ? 1 : 0)); }
 
 // the material slots that name a texture: baseColor, metallicRoughness, emission, occlusion (normal map is unused)
 constexpr int kTextureSlots[4] = {22, 23, 25, 26};
@@ -301,6 +299,14 @@ int ensure_frames(PTContext* c, uint32_t w, uint32_t h);                        
 int import_batch(const PTFrameParams* hostParams, int count, PTFrameParams& first, PTBatch& batch);      // pt_api_render.hip
 int take_event_pair(PTContext* c, EventPair& ep);                               // pt_api_render.hip: a start / stop pair for a profiled pass
 int ensure_wavefront(PTContext* c, PTContext::WfSet& set, uint32_t numSlots, uint32_t maxIterations);      // pt_api_render.hip
+// ---- enqueueing a wavefront launch sequence on the next state set (pt_api_render.hip): passes, adaptive passes, radiance queries ----
+// the limits the packed state word sets on SamplesPerPass / MaxRayBounces; maxIterations: the iteration bound a state set is carved for
+int wavefront_limits(const PTFrameParams& p, uint32_t& maxIterations);
+PTContext::WfSet& next_wavefront_set(PTContext* c, uint32_t* index = nullptr);      // state sets take turns; index (may be null): which one
+// The caller fills params, batch, the slot mapping, accumulated, output, orderAfter and zeroOutputFirst of L; scene, state set,
+// counters, stream, schedule and iterations come from c and set.  On set.stream, in order: wait for a pending scene update, record
+// profStart (null: none), the launch sequence, record profStop (null: none), record set.done.  launches += the sequence's kernel launches.
+int enqueue_wavefront(PTContext* c, PTContext::WfSet& set, PTWfLaunch& L, hipEvent_t profStart, hipEvent_t profStop, uint32_t& launches);
 // pt_api_adaptive.hip: the per-block 1 / ((k_b - 1) W_b) table on the device while adaptive state of the moments' size tracks
 // moments, else NULL (rc != PT_OK on a failed upload); minObs / minSamples: the minimum over the blocks this context owns
 // table == NULL: only the minima, nothing is uploaded

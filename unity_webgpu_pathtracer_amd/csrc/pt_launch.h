@@ -209,14 +209,6 @@ __host__ __device__ inline void pt_batch_pick(const PTBatch& b, uint32_t j, uint
     for (uint32_t k = 1; k < PT_MAX_BATCH; ++k) if (j == k) { seedRoot = b.seedRoot[k]; currentSample = b.currentSample[k]; }
 }
 
-// pt_wavefront.hip is compiled twice with different scheduler flags (csrc/Makefile): the translation unit built with -DPT_WF_TU_B
-// defines the same launcher under the name pt_launch_wavefront_b
-typedef hipError_t PTWfLauncher(const DScene& S, const PTFrameParams& P, const PTBatch& batch, const float4* accumulated, float4* output,
-                                const PTTileMap& tm, const PTWfBuffers& B, unsigned long long* gstats, bool fullStats,
-                                hipStream_t stream, hipEvent_t orderAfter, bool zeroOutputFirst,
-                                uint32_t* launchesOut, int traceVariant, uint32_t iterationsOverride);
-PTWfLauncher pt_launch_wavefront, pt_launch_wavefront_b;
-
 // ---- adaptive passes (include/ptmi_plugin.h Part 7): a pass over a LIST of 16x16 blocks, each with its own sample count ----
 // Slot s of pass j is j * slotsPerPass + e * 256 + tid with slotsPerPass = entries * 256; entry e of the per-call table is
 // {block id = by * frameBlocksX + bx, the block's sample count at the start of the call}.  Inside a block the lanes are laid
@@ -236,13 +228,10 @@ __host__ __device__ inline bool pt_list_slot_to_pixel(uint32_t frameBlocksX, uin
     py = by * 16u + (wave >> 1) * 8u + (lane >> 3);
     return px < coverW && py < coverH;
 }
-// The launch sequence of pt_launch_wavefront over the list: batch.currentSample is not read (pass j of entry e renders with
+// The launch sequence over the list (PTWfLaunch, below): batch.currentSample is not read (pass j of entry e renders with
 // CurrentSample = table[e].y + j * spp), the whole frame is copied from `accumulated` to `output` before the resolve (when
-// accumulated != NULL), schedule 4 (traceVariant 4) is not available.
-typedef hipError_t PTWfListLauncher(const DScene& S, const PTFrameParams& P, const PTBatch& batch, const float4* accumulated, float4* output,
-                                    const PTListMap& lm, const PTWfBuffers& B, unsigned long long* gstats, bool fullStats,
-                                    hipStream_t stream, hipEvent_t orderAfter, uint32_t* launchesOut, int traceVariant, uint32_t iterationsOverride);
-PTWfListLauncher pt_launch_wavefront_list, pt_launch_wavefront_list_b;
+// accumulated != NULL), nothing is zeroed, schedule 4 is not available.
+
 // ---- radiance queries (include/ptmi_plugin.h Part 8): a launch sequence over a caller's LIST OF RAYS ----
 // Slot s is entry s of the list (one pass, slotsPerPass = numSlots = count rounded up to 256; the slots past count start as
 // finished).  A path depends on its "pixel" only through how a sample starts: here sample 0 is the entry's ray and RNG state, and
@@ -252,12 +241,9 @@ struct PTRayMap {
     uint32_t count;
 };
 #define PT_RADIANCE_CHUNK (1u << 21)      // most entries of one launch sequence (a state set no larger than a 1080p frame's); <= 2^23
-// The launch sequence of pt_launch_wavefront over the list; the resolve writes out[s] = {colour / (float)spp, rng} for s < count and
-// depends on nothing but this sequence.  Schedule 4 (traceVariant 4) is not available.
-typedef hipError_t PTWfRaysLauncher(const DScene& S, const PTFrameParams& P, const PTRayMap& rm, PTRadiance* out, const PTWfBuffers& B,
-                                    unsigned long long* gstats, bool fullStats, hipStream_t stream, uint32_t* launchesOut, int traceVariant,
-                                    uint32_t iterationsOverride);
-PTWfRaysLauncher pt_launch_wavefront_rays, pt_launch_wavefront_rays_b;
+// The launch sequence over the ray list (PTWfLaunch, below): `output` is the PTRadiance array, the resolve writes
+// out[s] = {colour / (float)spp, rng} for s < count and depends on nothing but this sequence; batch, accumulated, orderAfter and
+// zeroOutputFirst are not read.  Schedule 4 is not available.
 // PTCameraRays (pt_kernels.hip): entry i = path_init's ray and RNG state of pixel indices[i] (NULL: pixel i); count <= 2^31
 hipError_t pt_launch_camera_rays(const PTFrameParams& P, const uint32_t* indices, uint32_t count, PTRadianceRay* rays, hipStream_t stream);
 #ifndef PT_WF_FUSED_GROUPS
@@ -272,3 +258,31 @@ hipError_t pt_launch_camera_rays(const PTFrameParams& P, const uint32_t* indices
 #define PT_WF_SETS 12            // path-state sets = passes that can be in flight at once, each on its own stream (3 -> 6 sets with 8 hardware queues: +12 %;
                                  // 6 -> 12 sets with 16 queues: +2 % at 1080p, +7 % at 960x540, -14 % time for a 1/8 share of a 1080p frame; 16: no better, 24: worse)
 #endif
+
+// ---- ONE wavefront launch sequence: what to render (the slot mapping), from and into what, on which stream, by which schedule ----
+enum PTWfMapKind : uint32_t { PT_WF_MAP_TILES, PT_WF_MAP_LIST, PT_WF_MAP_RAYS };
+struct PTWfLaunch {
+    const DScene* scene;
+    const PTFrameParams* params;
+    PTBatch batch;
+    PTWfMapKind mapKind;                    // which member of the union below is set
+    union {
+        PTTileMap tiles;                    // a pass (or a sub-frame of one) over the context's 16x16 blocks
+        PTListMap list;                     // a pass over a block list
+        PTRayMap rays;                      // a radiance query
+    };
+    const float4* accumulated;
+    void* output;                           // the frame (float4 per pixel); PT_WF_MAP_RAYS: the PTRadiance array
+    const PTWfBuffers* buffers;             // the state set the sequence runs on
+    unsigned long long* counters;           // the context's 16 counters (PTStats order)
+    bool fullStats;
+    hipStream_t stream;
+    hipEvent_t orderAfter;                  // may be null: the resolve -- and only it -- waits for this event
+    bool zeroOutputFirst;                   // PT_WF_MAP_TILES only: clear the frame before the resolve (pixels of other ranks read as zeros)
+    int schedule;                           // 1 ... 4 (PTSetSchedule)
+    uint32_t iterationsOverride;            // 0 = spp * (bounces + 2) + 4, capped by buffers->maxIterations
+};
+// Enqueues the sequence on L.stream without host synchronisation; launchesOut (may be null): kernel launches enqueued.
+// hipErrorNotSupported for schedule 4 over a list or rays.  pt_wavefront.hip is compiled twice with different scheduler flags
+// (csrc/Makefile); which compilation's kernels run is decided behind this one entry point.
+hipError_t pt_launch_wavefront(const PTWfLaunch& L, uint32_t* launchesOut);

@@ -1547,7 +1547,165 @@ size_t pt_wf_arena_layout(char* base, uint32_t numSlots, uint32_t residentWaves,
 
 } // namespace
 
+// One pass = a fixed sequence of launches on L.stream, no host synchronisation (see the file header).
+// L.orderAfter (may be null) is the event of the previous pass's resolve: this pass's resolve reads that pass's output as
+// AccumulatedOutput and, with ping-pong frames, overwrites the frame that resolve was still reading.
+// MAP = PTListMap: the pass over a block list; nothing is zeroed and the frame is copied instead.
+// MAP = PTRayMap: a radiance query: L.output is the PTRadiance array, nothing is ordered, zeroed or copied.
+// UNIT_A: this compilation of the file is the one without the post-RA scheduler (csrc/Makefile).  It is entered for the plain
+// refill trace only, the other one for everything else -- each instantiates only the kernels it can launch.
+namespace {
+
+// what traces the rays of an iteration -- or, fused, renders the whole pass in one launch
+enum class Trace { Refill, RefillTlas, Lane, Persist, Fused };
+Trace pick_trace(int schedule, bool tlas)
+{
+    // HAS_TLAS: schedules 1 and 4 walk the two levels through the refill scheduler, 2 and 3 with one ray per lane
+    if (tlas) return schedule == 1 || schedule == 4 ? Trace::RefillTlas : Trace::Lane;
+    return schedule == 1 ? Trace::Refill : schedule == 2 ? Trace::Lane : schedule == 3 ? Trace::Persist : Trace::Fused;
+}
+
+// f(std::true_type / std::false_type): a run-time flag picks a template argument of the one launch statement f holds
+template <class F> void with_flag(bool flag, F&& f) { if (flag) f(std::true_type{}); else f(std::false_type{}); }
+#define PT_FLAG(x) (decltype(x)::value)
+
+template <class MAP, bool UNIT_A>
+hipError_t launch_sequence(const PTWfLaunch& L, const MAP& tm, uint32_t* launchesOut)
+{
+    constexpr bool kList = kListMap<MAP>, kRays = kRayMap<MAP>;
+    const DScene& S = *L.scene;
+    const PTFrameParams& P = *L.params;
+    const PTBatch& batch = L.batch;
+    const PTWfBuffers& B = *L.buffers;
+    const bool fullStats = L.fullStats;
+    const hipStream_t stream = L.stream;
+    float4* const output = (float4*)L.output;
+    const uint32_t nb = B.numSlots >> 8, nbPass = B.slotsPerPass >> 8;
+    uint32_t launches = 0;
+    hipError_t e;
+    const bool tlas = S.hasTlas != 0u;
+    const Trace trace = pick_trace(L.schedule, tlas);
+    if (UNIT_A != (trace == Trace::Refill)) return hipErrorInvalidValue;       // pt_launch_wavefront picks the unit
+    if (trace == Trace::Fused) {
+        if constexpr (!UNIT_A && !kList && !kRays) {
+            // schedule 4: one persistent launch renders the whole pass (pt_wf_fused); then the ordered pixel write and the counter fold
+            if ((e = hipMemsetAsync(B.chunkHeads, 0, sizeof(uint32_t), stream)) != hipSuccess) return e;
+            const uint32_t maxWaves = B.numSlots / (64u * PT_WF_FUSED_GROUPS);           // contexts never outnumber the frame's slots (array sizes)
+            uint32_t waves = B.residentWaves / 8u * (uint32_t)PT_WF_FUSED_WAVES;          // CUs x 4 SIMDs x waves per SIMD
+            if (waves > maxWaves) waves = maxWaves;
+            if (waves == 0u) waves = 1u;
+            with_flag(fullStats, [&](auto stats) {
+                hipLaunchKernelGGL(pt_wf_fused<PT_FLAG(stats)>, dim3(waves), dim3(64), 0, stream, S, P, batch, tm, B);
+            });
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+            if (L.orderAfter && (e = hipStreamWaitEvent(stream, L.orderAfter, 0)) != hipSuccess) return e;
+            if (L.zeroOutputFirst &&
+                (e = hipMemsetAsync(output, 0, (size_t)P.OutputWidth * P.OutputHeight * sizeof(float4), stream)) != hipSuccess) return e;
+            hipLaunchKernelGGL(pt_wf_resolve, dim3(nbPass), dim3(256), 0, stream, P, batch, tm, B, (const float4*)B.pixsum, L.accumulated, output);
+            hipLaunchKernelGGL(pt_wf_fold_rows, dim3(256), dim3(256), 0, stream, B.statRows, B.numStatRows, L.counters);
+            if (launchesOut) *launchesOut = 3u;
+            return hipGetLastError();
+        } else {
+            return hipErrorNotSupported;
+        }
+    }
+    hipLaunchKernelGGL(pt_wf_init<MAP>, dim3(nb), dim3(256), 0, stream, P, batch, tm, B);
+    launches++;
+    const uint32_t spp = P.SamplesPerPass > 1 ? (uint32_t)P.SamplesPerPass : 1u;
+    const uint32_t bounces = P.MaxRayBounces > 1u ? P.MaxRayBounces : 1u;
+    // a sample needs at most (bounces + 1) closest-hit iterations + 1 to apply its last NEE; alpha-skips beyond that go to cleanup
+    uint32_t iterations = L.iterationsOverride ? L.iterationsOverride : spp * (bounces + 2u) + 4u;
+    if (iterations > B.maxIterations) iterations = B.maxIterations;
+    for (uint32_t it = 0; it < iterations; ++it) {
+        if constexpr (UNIT_A) {
+            const bool wide = PT_WF_RANGE >= 128u && pt_wf_wide_ranges(B.numSlots, B.residentWaves);         // pt_launch.h
+            const uint32_t blocks = wide ? (B.numSlots + 127u) / 128u : (B.numSlots + 63u) / 64u;
+            // the main launch, then the tail launch over the rays the main one's waves left suspended
+            auto refill = [&](auto tail, uint32_t grid) {
+                with_flag(fullStats, [&](auto stats) { with_flag(wide, [&](auto w) {
+                    hipLaunchKernelGGL((pt_wf_trace_refill<PT_FLAG(stats), PT_FLAG(tail), PT_FLAG(w) ? 128u : 64u>), dim3(grid), dim3(64), 0, stream, S, B, it);
+                }); });
+                launches++;
+            };
+            refill(std::false_type{}, blocks);
+            if (PT_WF_SUSPEND > 0u) refill(std::true_type{}, (blocks + PT_WF_TAIL_GROUP - 1u) / PT_WF_TAIL_GROUP);
+        } else {
+            if (trace == Trace::Persist) {
+                const uint32_t numChunks = (B.numSlots + PT_WF_CHUNK - 1u) / PT_WF_CHUNK;
+                uint32_t waves = B.residentWaves;
+                if (waves > numChunks) waves = numChunks;
+                with_flag(fullStats, [&](auto stats) {
+                    hipLaunchKernelGGL(pt_wf_trace_persist<PT_FLAG(stats)>, dim3(waves), dim3(64), 0, stream, S, B, it);
+                });
+            } else if (trace == Trace::RefillTlas) {
+                const uint32_t refillBlocks = (B.numSlots + PT_WF_RANGE - 1u) / PT_WF_RANGE;                 // one wave per range
+                const bool shared = PT_WF_TLAS_WG_WAVES > 1u && S.tlasNodeCount <= 0xFFFFu;     // several waves per workgroup: 16-bit TLAS stack entries
+                with_flag(fullStats, [&](auto stats) { with_flag(shared, [&](auto sh) {
+                    constexpr uint32_t WAVES = PT_FLAG(sh) ? PT_WF_TLAS_WG_WAVES : 1u;
+                    hipLaunchKernelGGL((pt_wf_trace_refill_tlas<PT_FLAG(stats), WAVES>), dim3((refillBlocks + WAVES - 1u) / WAVES), dim3(64u * WAVES), 0, stream, S, B, it);
+                }); });
+            } else {
+                with_flag(fullStats, [&](auto stats) { with_flag(tlas, [&](auto tl) {
+                    hipLaunchKernelGGL((pt_wf_trace<PT_FLAG(stats), PT_FLAG(tl)>), dim3(nb * 3u), dim3(256), 0, stream, S, B, it);
+                }); });
+            }
+            launches++;
+        }
+        with_flag(fullStats, [&](auto stats) {
+            hipLaunchKernelGGL((pt_wf_shade<PT_FLAG(stats), MAP>), dim3(B.numSlots / PT_WF_SHADE_BLOCK), dim3(PT_WF_SHADE_BLOCK), 0, stream, S, P, tm, B, it);
+        });
+        launches++;
+    }
+    const uint32_t cleanupBlocks = nb < 1024u ? nb : 1024u;          // 256 CUs x 4 workgroups; each strides over the slot blocks
+    with_flag(fullStats, [&](auto stats) { with_flag(!UNIT_A && tlas, [&](auto tl) {
+        constexpr bool TLAS = !UNIT_A && PT_FLAG(tl);                 // unit A renders flat scenes only
+        hipLaunchKernelGGL((pt_wf_cleanup<PT_FLAG(stats), TLAS, MAP>), dim3(cleanupBlocks), dim3(256), 0, stream, S, P, tm, B);
+    }); });
+    if (L.orderAfter && (e = hipStreamWaitEvent(stream, L.orderAfter, 0)) != hipSuccess) return e;
+    if (L.zeroOutputFirst &&
+        (e = hipMemsetAsync(output, 0, (size_t)P.OutputWidth * P.OutputHeight * sizeof(float4), stream)) != hipSuccess) return e;
+    if constexpr (kRays) {
+        hipLaunchKernelGGL(pt_wf_resolve_rays, dim3(nbPass), dim3(256), 0, stream, P, tm, B, (PTRadiance*)L.output);
+    } else if constexpr (kList) {
+        // pixels outside the list keep Accumulated, bit for bit: one copy of the frame, then the resolve overwrites the listed blocks
+        if (L.accumulated &&
+            (e = hipMemcpyAsync(output, L.accumulated, (size_t)P.OutputWidth * P.OutputHeight * sizeof(float4), hipMemcpyDeviceToDevice, stream)) != hipSuccess) return e;
+        hipLaunchKernelGGL(pt_wf_resolve_list, dim3(nbPass), dim3(256), 0, stream, P, batch, tm, B, (const float4*)B.color, L.accumulated, output);
+    } else {
+        hipLaunchKernelGGL(pt_wf_resolve, dim3(nbPass), dim3(256), 0, stream, P, batch, tm, B, (const float4*)B.color, L.accumulated, output);
+    }
+    hipLaunchKernelGGL(pt_wf_fold_rows, dim3(256), dim3(256), 0, stream, B.statRows, B.numStatRows, L.counters);
+    launches += 3;
+    if (launchesOut) *launchesOut = launches;
+    return hipGetLastError();
+}
+#undef PT_FLAG
+
+// the slot mapping picks the instantiation; what a mapping never uses is cleared here, whatever the caller left in it
+template <bool UNIT_A>
+hipError_t launch_mapped(const PTWfLaunch& L, uint32_t* launchesOut)
+{
+    PTWfLaunch M = L;
+    switch (L.mapKind) {
+    case PT_WF_MAP_TILES:
+        return launch_sequence<PTTileMap, UNIT_A>(M, M.tiles, launchesOut);
+    case PT_WF_MAP_LIST:
+        M.zeroOutputFirst = false;
+        return launch_sequence<PTListMap, UNIT_A>(M, M.list, launchesOut);
+    case PT_WF_MAP_RAYS:
+        M.batch = PTBatch{};
+        M.batch.count = 1u;
+        M.accumulated = nullptr;
+        M.orderAfter = nullptr;
+        M.zeroOutputFirst = false;
+        return launch_sequence<PTRayMap, UNIT_A>(M, M.rays, launchesOut);
+    }
+    return hipErrorInvalidValue;
+}
+} // namespace
+
 #ifdef PT_WF_TU_B
+// what every library links once: the arena layout and the launcher's entry point
 size_t pt_wf_arena_bytes(uint32_t numSlots, uint32_t residentWaves, bool needTlas, uint32_t maxIterations)
 {
     PTWfBuffers B = {};
@@ -1559,155 +1717,15 @@ PTWfBuffers pt_wf_arena_carve(void* base, uint32_t numSlots, uint32_t residentWa
     pt_wf_arena_layout((char*)base, numSlots, residentWaves, needTlas, maxIterations, B);
     return B;
 }
-#define pt_launch_wavefront pt_launch_wavefront_b
-#define pt_launch_wavefront_list pt_launch_wavefront_list_b
-#define pt_launch_wavefront_rays pt_launch_wavefront_rays_b
+hipError_t pt_wf_launch_unit_a(const PTWfLaunch& L, uint32_t* launchesOut);       // the other compilation of this file
+hipError_t pt_launch_wavefront(const PTWfLaunch& L, uint32_t* launchesOut)
+{
+    if (L.schedule < 1 || L.schedule > 4) return hipErrorInvalidValue;
+    if (L.schedule == 4 && L.mapKind != PT_WF_MAP_TILES) return hipErrorNotSupported;
+    // the default schedule on a flat scene -- refill trace + shade -- runs the kernels built without the post-RA scheduler
+    if (L.schedule == 1 && L.scene->hasTlas == 0u) return pt_wf_launch_unit_a(L, launchesOut);
+    return launch_mapped<false>(L, launchesOut);
+}
+#else
+hipError_t pt_wf_launch_unit_a(const PTWfLaunch& L, uint32_t* launchesOut) { return launch_mapped<true>(L, launchesOut); }
 #endif
-
-// One pass = a fixed sequence of launches on `stream`, no host synchronisation (see the file header).
-// `orderAfter` (may be null) is the event of the previous pass's resolve: this pass's resolve reads that pass's output as
-// AccumulatedOutput and, with ping-pong frames, overwrites the frame that resolve was still reading.
-// MAP = PTListMap: the pass over a block list (pt_launch_wavefront_list); zeroOutputFirst then is false and the frame is copied instead.
-// MAP = PTRayMap: a radiance query (pt_launch_wavefront_rays): `output` is the PTRadiance array, nothing is ordered, zeroed or copied.
-namespace {
-template <class MAP>
-hipError_t launch_wavefront(const DScene& S, const PTFrameParams& P, const PTBatch& batch, const float4* accumulated, float4* output,
-                            const MAP& tm, const PTWfBuffers& B, unsigned long long* gstats, bool fullStats,
-                            hipStream_t stream, hipEvent_t orderAfter, bool zeroOutputFirst,
-                            uint32_t* launchesOut, int traceVariant, uint32_t iterationsOverride)
-{
-    constexpr bool kList = kListMap<MAP>, kRays = kRayMap<MAP>;
-    const uint32_t nb = B.numSlots >> 8, nbPass = B.slotsPerPass >> 8;
-    uint32_t launches = 0;
-    hipError_t e;
-    const bool tlas = S.hasTlas != 0u;
-    if (tlas && traceVariant == 4) traceVariant = 2;      // schedule 4 with HAS_TLAS: the two-level walk runs through schedule 1's refill kernel
-    const bool tlasRefill = tlas && traceVariant == 2;    // schedule 1: two-level traversal through the refill scheduler
-    if (tlas) traceVariant = 1;          // schedules 2, 3: the one-ray-per-lane trace kernel
-    if constexpr (!kList && !kRays) if (traceVariant == 4 && !tlas) {
-        // schedule 4: one persistent launch renders the whole pass (pt_wf_fused); then the ordered pixel write and the counter fold
-        if ((e = hipMemsetAsync(B.chunkHeads, 0, sizeof(uint32_t), stream)) != hipSuccess) return e;
-        const uint32_t maxWaves = B.numSlots / (64u * PT_WF_FUSED_GROUPS);           // contexts never outnumber the frame's slots (array sizes)
-        uint32_t waves = B.residentWaves / 8u * (uint32_t)PT_WF_FUSED_WAVES;          // CUs x 4 SIMDs x waves per SIMD
-        if (waves > maxWaves) waves = maxWaves;
-        if (waves == 0u) waves = 1u;
-        if (fullStats) hipLaunchKernelGGL(pt_wf_fused<true>, dim3(waves), dim3(64), 0, stream, S, P, batch, tm, B);
-        else hipLaunchKernelGGL(pt_wf_fused<false>, dim3(waves), dim3(64), 0, stream, S, P, batch, tm, B);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if (orderAfter && (e = hipStreamWaitEvent(stream, orderAfter, 0)) != hipSuccess) return e;
-        if (zeroOutputFirst &&
-            (e = hipMemsetAsync(output, 0, (size_t)P.OutputWidth * P.OutputHeight * sizeof(float4), stream)) != hipSuccess) return e;
-        hipLaunchKernelGGL(pt_wf_resolve, dim3(nbPass), dim3(256), 0, stream, P, batch, tm, B, (const float4*)B.pixsum, accumulated, output);
-        hipLaunchKernelGGL(pt_wf_fold_rows, dim3(256), dim3(256), 0, stream, B.statRows, B.numStatRows, gstats);
-        if (launchesOut) *launchesOut = 3u;
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(pt_wf_init<MAP>, dim3(nb), dim3(256), 0, stream, P, batch, tm, B);
-    launches++;
-    const uint32_t spp = P.SamplesPerPass > 1 ? (uint32_t)P.SamplesPerPass : 1u;
-    const uint32_t bounces = P.MaxRayBounces > 1u ? P.MaxRayBounces : 1u;
-    // a sample needs at most (bounces + 1) closest-hit iterations + 1 to apply its last NEE; alpha-skips beyond that go to cleanup
-    uint32_t iterations = iterationsOverride ? iterationsOverride : spp * (bounces + 2u) + 4u;
-    if (iterations > B.maxIterations) iterations = B.maxIterations;
-    const uint32_t refillBlocks = (B.numSlots + PT_WF_RANGE - 1u) / PT_WF_RANGE;                 // one wave per workgroup
-    for (uint32_t it = 0; it < iterations; ++it) {
-        if (traceVariant == 0) {
-            const uint32_t numChunks = (B.numSlots + PT_WF_CHUNK - 1u) / PT_WF_CHUNK;
-            uint32_t waves = B.residentWaves;
-            if (waves > numChunks) waves = numChunks;
-            if (fullStats) hipLaunchKernelGGL(pt_wf_trace_persist<true>, dim3(waves), dim3(64), 0, stream, S, B, it);
-            else hipLaunchKernelGGL(pt_wf_trace_persist<false>, dim3(waves), dim3(64), 0, stream, S, B, it);
-        } else if (traceVariant == 2) {
-            const bool wide = PT_WF_RANGE >= 128u && pt_wf_wide_ranges(B.numSlots, B.residentWaves);         // pt_launch.h
-            const uint32_t blocks = wide ? (B.numSlots + 127u) / 128u : (B.numSlots + 63u) / 64u;
-            if (wide) {
-                if (fullStats) hipLaunchKernelGGL((pt_wf_trace_refill<true, false, 128u>), dim3(blocks), dim3(64), 0, stream, S, B, it);
-                else hipLaunchKernelGGL((pt_wf_trace_refill<false, false, 128u>), dim3(blocks), dim3(64), 0, stream, S, B, it);
-            } else {
-                if (fullStats) hipLaunchKernelGGL((pt_wf_trace_refill<true, false, 64u>), dim3(blocks), dim3(64), 0, stream, S, B, it);
-                else hipLaunchKernelGGL((pt_wf_trace_refill<false, false, 64u>), dim3(blocks), dim3(64), 0, stream, S, B, it);
-            }
-            if (PT_WF_SUSPEND > 0u) {
-                const uint32_t tailBlocks = (blocks + PT_WF_TAIL_GROUP - 1u) / PT_WF_TAIL_GROUP;
-                if (wide) {
-                    if (fullStats) hipLaunchKernelGGL((pt_wf_trace_refill<true, true, 128u>), dim3(tailBlocks), dim3(64), 0, stream, S, B, it);
-                    else hipLaunchKernelGGL((pt_wf_trace_refill<false, true, 128u>), dim3(tailBlocks), dim3(64), 0, stream, S, B, it);
-                } else {
-                    if (fullStats) hipLaunchKernelGGL((pt_wf_trace_refill<true, true, 64u>), dim3(tailBlocks), dim3(64), 0, stream, S, B, it);
-                    else hipLaunchKernelGGL((pt_wf_trace_refill<false, true, 64u>), dim3(tailBlocks), dim3(64), 0, stream, S, B, it);
-                }
-                launches++;
-            }
-        } else if (tlas && tlasRefill) {
-            if (PT_WF_TLAS_WG_WAVES > 1u && S.tlasNodeCount <= 0xFFFFu) {     // 16-bit TLAS stack entries
-                const uint32_t wgs = (refillBlocks + PT_WF_TLAS_WG_WAVES - 1u) / PT_WF_TLAS_WG_WAVES;
-                if (fullStats) hipLaunchKernelGGL((pt_wf_trace_refill_tlas<true, PT_WF_TLAS_WG_WAVES>), dim3(wgs), dim3(64u * PT_WF_TLAS_WG_WAVES), 0, stream, S, B, it);
-                else hipLaunchKernelGGL((pt_wf_trace_refill_tlas<false, PT_WF_TLAS_WG_WAVES>), dim3(wgs), dim3(64u * PT_WF_TLAS_WG_WAVES), 0, stream, S, B, it);
-            } else {
-                if (fullStats) hipLaunchKernelGGL((pt_wf_trace_refill_tlas<true, 1u>), dim3(refillBlocks), dim3(64), 0, stream, S, B, it);
-                else hipLaunchKernelGGL((pt_wf_trace_refill_tlas<false, 1u>), dim3(refillBlocks), dim3(64), 0, stream, S, B, it);
-            }
-        } else if (tlas) {
-            if (fullStats) hipLaunchKernelGGL((pt_wf_trace<true, true>), dim3(nb * 3u), dim3(256), 0, stream, S, B, it);
-            else hipLaunchKernelGGL((pt_wf_trace<false, true>), dim3(nb * 3u), dim3(256), 0, stream, S, B, it);
-        } else {
-            if (fullStats) hipLaunchKernelGGL((pt_wf_trace<true, false>), dim3(nb * 3u), dim3(256), 0, stream, S, B, it);
-            else hipLaunchKernelGGL((pt_wf_trace<false, false>), dim3(nb * 3u), dim3(256), 0, stream, S, B, it);
-        }
-        if (fullStats) hipLaunchKernelGGL((pt_wf_shade<true, MAP>), dim3(B.numSlots / PT_WF_SHADE_BLOCK), dim3(PT_WF_SHADE_BLOCK), 0, stream, S, P, tm, B, it);
-        else hipLaunchKernelGGL((pt_wf_shade<false, MAP>), dim3(B.numSlots / PT_WF_SHADE_BLOCK), dim3(PT_WF_SHADE_BLOCK), 0, stream, S, P, tm, B, it);
-        launches += 2;
-    }
-    const uint32_t cleanupBlocks = nb < 1024u ? nb : 1024u;          // 256 CUs x 4 workgroups; each strides over the slot blocks
-    if (tlas) {
-        if (fullStats) hipLaunchKernelGGL((pt_wf_cleanup<true, true, MAP>), dim3(cleanupBlocks), dim3(256), 0, stream, S, P, tm, B);
-        else hipLaunchKernelGGL((pt_wf_cleanup<false, true, MAP>), dim3(cleanupBlocks), dim3(256), 0, stream, S, P, tm, B);
-    } else {
-        if (fullStats) hipLaunchKernelGGL((pt_wf_cleanup<true, false, MAP>), dim3(cleanupBlocks), dim3(256), 0, stream, S, P, tm, B);
-        else hipLaunchKernelGGL((pt_wf_cleanup<false, false, MAP>), dim3(cleanupBlocks), dim3(256), 0, stream, S, P, tm, B);
-    }
-    if (orderAfter && (e = hipStreamWaitEvent(stream, orderAfter, 0)) != hipSuccess) return e;
-    if (zeroOutputFirst &&
-        (e = hipMemsetAsync(output, 0, (size_t)P.OutputWidth * P.OutputHeight * sizeof(float4), stream)) != hipSuccess) return e;
-    if constexpr (kRays) {
-        hipLaunchKernelGGL(pt_wf_resolve_rays, dim3(nbPass), dim3(256), 0, stream, P, tm, B, (PTRadiance*)output);
-    } else if constexpr (kList) {
-        // pixels outside the list keep Accumulated, bit for bit: one copy of the frame, then the resolve overwrites the listed blocks
-        if (accumulated &&
-            (e = hipMemcpyAsync(output, accumulated, (size_t)P.OutputWidth * P.OutputHeight * sizeof(float4), hipMemcpyDeviceToDevice, stream)) != hipSuccess) return e;
-        hipLaunchKernelGGL(pt_wf_resolve_list, dim3(nbPass), dim3(256), 0, stream, P, batch, tm, B, (const float4*)B.color, accumulated, output);
-    } else {
-        hipLaunchKernelGGL(pt_wf_resolve, dim3(nbPass), dim3(256), 0, stream, P, batch, tm, B, (const float4*)B.color, accumulated, output);
-    }
-    hipLaunchKernelGGL(pt_wf_fold_rows, dim3(256), dim3(256), 0, stream, B.statRows, B.numStatRows, gstats);
-    launches += 3;
-    if (launchesOut) *launchesOut = launches;
-    return hipGetLastError();
-}
-} // namespace
-
-hipError_t pt_launch_wavefront(const DScene& S, const PTFrameParams& P, const PTBatch& batch, const float4* accumulated, float4* output,
-                               const PTTileMap& tm, const PTWfBuffers& B, unsigned long long* gstats, bool fullStats,
-                               hipStream_t stream, hipEvent_t orderAfter, bool zeroOutputFirst,
-                               uint32_t* launchesOut, int traceVariant, uint32_t iterationsOverride)
-{
-    return launch_wavefront(S, P, batch, accumulated, output, tm, B, gstats, fullStats, stream, orderAfter, zeroOutputFirst, launchesOut, traceVariant, iterationsOverride);
-}
-
-hipError_t pt_launch_wavefront_list(const DScene& S, const PTFrameParams& P, const PTBatch& batch, const float4* accumulated, float4* output,
-                                    const PTListMap& lm, const PTWfBuffers& B, unsigned long long* gstats, bool fullStats,
-                                    hipStream_t stream, hipEvent_t orderAfter, uint32_t* launchesOut, int traceVariant, uint32_t iterationsOverride)
-{
-    if (traceVariant == 4) return hipErrorNotSupported;
-    return launch_wavefront(S, P, batch, accumulated, output, lm, B, gstats, fullStats, stream, orderAfter, false, launchesOut, traceVariant, iterationsOverride);
-}
-
-hipError_t pt_launch_wavefront_rays(const DScene& S, const PTFrameParams& P, const PTRayMap& rm, PTRadiance* out, const PTWfBuffers& B,
-                                    unsigned long long* gstats, bool fullStats, hipStream_t stream, uint32_t* launchesOut, int traceVariant,
-                                    uint32_t iterationsOverride)
-{
-    if (traceVariant == 4) return hipErrorNotSupported;
-    PTBatch batch = {};
-    batch.count = 1u;
-    return launch_wavefront(S, P, batch, nullptr, (float4*)out, rm, B, gstats, fullStats, stream, nullptr, false, launchesOut, traceVariant, iterationsOverride);
-}
