@@ -162,8 +162,8 @@ def test_list_mapped_kernels_keep_the_register_budget():
         for k, r in shade.items():
             print(f"[resources] unit {unit} {k}: {r}")
             assert r["scratch"] == 0 and r["vgprs"] <= 128 and r["occupancy"] >= 4, (unit, r)
-        for part in ("pt_wf_initI", "pt_wf_resolve_list"):
-            hits = [v for k, v in res.items() if part in k and ("PTListMap" in k or "resolve_list" in k)]
+        for part in ("pt_wf_initI", "pt_wf_resolveI"):
+            hits = [v for k, v in res.items() if part in k and "PTListMap" in k]
             assert hits, (part, sorted(res))
             for r in hits:
                 assert r["scratch"] == 0 and r["vgpr_spill"] == 0, (part, r)

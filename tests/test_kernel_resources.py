@@ -25,6 +25,10 @@ def test_trace_and_shade_kernels_keep_their_register_budget():
         assert r["scratch"] == 0 and r["vgpr_spill"] == 0, r
         assert r["occupancy"] == 8 and r["vgprs"] <= 64, r
         assert r["lds"] <= 5120, r                      # 32 one-wave workgroups per CU in 160 KB
+    # ... and the statistics instantiations of its main launch (fullStats renders): no scratch either.  (Those of the TAIL launch,
+    # ILb1ELb1E, have had 36 bytes since before this line was drawn; they are not held to it.)
+    for r in pick("pt_wf_trace_refillILb1ELb0E"):
+        assert r["scratch"] == 0, r
     # shade kernel: four waves per SIMD, no scratch
     for r in pick("pt_wf_shadeILb0E"):
         assert r["scratch"] == 0 and r["vgprs"] <= 128 and r["occupancy"] >= 4, r

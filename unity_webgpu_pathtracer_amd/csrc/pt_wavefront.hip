@@ -1,4 +1,4 @@
-// pt_wavefront.hip — schedules 1-3: the same per-pixel program as the megakernel, cut at the traversal calls.
+// pt_wavefront.hip — schedules 1-4: the same per-pixel program as the megakernel, cut at the traversal calls.
 //
 // Why: in one fused kernel the Disney-BSDF shading code sets the register budget (185 VGPRs -> 2 waves/SIMD, or
 // 128 with spills -> 4), and lanes that shade wait for lanes that traverse and vice versa (measured VALU lane
@@ -274,6 +274,13 @@ PT_DEV void store_miss(const PTWfBuffers& B, uint32_t slot)
     asm volatile("" : "+v"(far), "+v"(slot));
     f4_array(B, PT_F4_HIT)[slot] = make_float4(far, 0.0f, 0.0f, 0.0f);
 }
+// (the pin matters for the hit record as well: with its address hoisted out of the loop that finishes slab rays, the statistics
+// instantiations of the refill kernel spilled it -- 12 bytes of scratch)
+PT_DEV void store_hit(const PTWfBuffers& B, uint32_t slot, const TraceHit& hit)
+{
+    asm volatile("" : "+v"(slot));
+    f4_array(B, PT_F4_HIT)[slot] = make_float4(hit.t, hit.u, hit.v, pt_asfloat(hit.triIndex));
+}
 PT_DEV void store_occlusion(const PTWfBuffers& B, uint32_t kind, uint32_t slot, bool occluded)
 {
     asm volatile("" : "+v"(kind), "+v"(slot));
@@ -285,6 +292,88 @@ PT_DEV bool ray_exists(uint32_t f, uint32_t kind)
     if (kind == 0u) return fl_state(f) == PS_TRACE;
     if (kind == 1u) return fl_pending(f) && fl_env(f) != 0u;
     return fl_pending(f) && fl_light(f) != 0u;
+}
+
+// ---- the wave scheduler ------------------------------------------------------------------------------------------------
+// What the trace kernels that keep 64 resumable traversals in flight per wave share (pt_wf_trace_refill, pt_wf_trace_refill_tlas,
+// pt_wf_trace_persist, the trace phase of pt_wf_fused).  Each kernel enumerates its own candidates (slot range, chunk, context
+// group, pend mask) and owns its loop; the steps of the loop are written once, here and under "suspension" below.
+
+// Compaction of up to 64 candidates into the idle lanes: the lanes whose candidate exists (`valid`) put its `word` into xchg in
+// enumeration order, as many as there are idle lanes; afterwards an idle lane with rankI < take owns xchg[rankI].  consumed: how far
+// the caller's cursor moves (up to the first ray NOT taken).  The caller puts a wave barrier behind its reads of xchg.
+struct Compaction { uint32_t take, consumed, rankI; };
+PT_DEV Compaction compact_candidates(pt_lds_u32 xchg, bool idle, uint32_t nIdle, bool valid, uint32_t word)
+{
+    Compaction c;
+    c.rankI = rank_below(__ballot(idle));
+    const unsigned long long V = __ballot(valid);
+    const uint32_t nV = (uint32_t)__popcll(V);
+    c.take = nIdle < nV ? nIdle : nV;
+    const uint32_t rankV = rank_below(V);
+    c.consumed = 64u;
+    if (c.take < nV) c.consumed = (uint32_t)__ffsll((long long)__ballot(valid && rankV == c.take)) - 1u;   // first ray NOT taken
+    if (valid && rankV < c.take) xchg[rankV] = word;
+    __builtin_amdgcn_wave_barrier();
+    return c;
+}
+
+// The result of a finished ray.  Closest hit (kind 0): the miss record or (t, u, v, triIndex); shadow ray: the occlusion byte.
+// recordStored: the hit record is in memory already (kernels that write it at every improvement), so only a miss is stored.
+PT_DEV void store_result(const PTWfBuffers& B, uint32_t slot, uint32_t kind, bool hitAny, const TraceHit& hit, bool recordStored)
+{
+    if (kind == 0u) {
+        if (!hitAny) store_miss(B, slot);
+        else if (!recordStored) store_hit(B, slot, hit);
+    } else store_occlusion(B, kind, slot, hitAny);
+}
+
+// A lane takes the ray (slot, kind) of a flat scene.  false: a NaN ray, a certain miss -- its result is stored and the lane stays idle.
+PT_DEV bool start_ray(const PTWfBuffers& B, uint32_t slot, uint32_t kind, RayState& rs, Counters& cn)
+{
+    v3 o, d;
+    fetch_ray(B, slot, kind, o, d);
+    if (kind == 0u) cn.closestRays++; else cn.shadowRays++;
+    if (!ray_begin(rs, o, d, kind != 0u)) return true;
+    store_result(B, slot, kind, false, rs.hit, true);
+    return false;
+}
+
+// Two phases per wave iteration instead of ray_step's nested loops: (1) every lane with a triangle pending tests ONE
+// (the block runs when PT_WF_TRI_PARK lanes want it, or when nobody can do anything else), (2) every lane without a
+// triangle pending -- including those that have just tested their last one -- pops and visits its next node.  A lane
+// with k triangles spends k - 1 extra iterations in phase 1 while its neighbours keep visiting nodes; the triangle
+// block runs once per iteration at ~3x the lane utilisation of the nested loop (2.1 executions at 8 %).
+// Returns true when the lane's ray is complete.
+template <bool STATS, class ST>
+PT_DEV bool wave_step(const DScene& S, bool have, RayState& rs, ST& st, Counters& cn)
+{
+    const bool wantTri = have && rs.tg.y != 0u;
+    const uint32_t nT = (uint32_t)__popcll(__ballot(wantTri));
+    const uint32_t nN = (uint32_t)__popcll(__ballot(have && !wantTri));
+    bool fin = false;
+    if ((nT >= PT_WF_TRI_PARK || nN == 0u) && wantTri) fin = ray_tri_one<STATS>(S, rs, cn);
+    if (have && !fin && rs.tg.y == 0u) fin = ray_node_one<STATS>(S, rs, st, cn);
+    return fin;
+}
+
+// Before a wave parks its rays: a ray whose stack reaches into the HBM slab stays (a record only holds the LDS entries), so those
+// are finished first.  Returns the lane's `have`.
+template <bool STATS, class ST>
+PT_DEV bool finish_slab_rays(const DScene& S, const PTWfBuffers& B, bool have, uint32_t slot, uint32_t kind, RayState& rs, ST& st, Counters& cn)
+{
+    if (__ballot(have && rs.sp > PT_WF_LDS_STACK) != 0ull)                  // (spelled out: without it the main refill kernel comes to 63 VGPRs and 1,558 instructions instead of 58 and 1,507)
+    while (__ballot(have && rs.sp > PT_WF_LDS_STACK) != 0ull) {
+        if (have) {
+            // a lane may arrive with triangles pending: one triangle OR one node visit, whichever is next for it
+            const bool fin = rs.tg.y != 0u ? ray_tri_one<STATS>(S, rs, cn) : ray_node_one<STATS>(S, rs, st, cn);
+            if (fin) {
+                store_result(B, slot, kind, rs.hit.t < PT_FAR_PLANE, rs.hit, false);
+                have = false;
+            }
+        }
+    }
+    return have;
 }
 
 // ---- suspension (PT_WF_SUSPEND > 0) -----------------------------------------------------------------------------------
@@ -305,12 +394,13 @@ PT_DEV bool ray_exists(uint32_t f, uint32_t kind)
 #define PT_WF_SUSP_RECORD_ROWS 6u                                // uint4 rows a record has room for (pt_wf_arena_layout)
 static_assert(PT_WF_SUSP_ROWS <= PT_WF_SUSP_RECORD_ROWS, "a suspended ray's record does not fit its slot of the record array");
 
+// The record p of a suspended ray, in the record array of the refill kernel (B.susp) or in the LDS of the fused kernel.
+// ref: kind << 30 | the ray's slot (refill) or its context index within the wave (fused).
 // A record holds the LDS part of the stack; a ray whose stack reaches into the HBM slab is not suspended (it is finished first).
 template <class ST>
-PT_DEV void suspend_ray(const PTWfBuffers& B, uint32_t rec, uint32_t slot, uint32_t kind, const RayState& r, ST& st)
+PT_DEV void suspend_ray(uint4* p, uint32_t ref, const RayState& r, ST& st)
 {
-    uint4* p = B.susp + (size_t)rec * PT_WF_SUSP_ROWS;
-    p[0] = make_uint4(slot | (kind << 30), r.sp | (r.overflow ? 0x100u : 0u), r.ng.x, r.ng.y);
+    p[0] = make_uint4(ref, r.sp | (r.overflow ? 0x100u : 0u), r.ng.x, r.ng.y);
     p[1] = make_uint4(r.tg.x, r.tg.y, pt_asuint(r.hit.t), 0u);
 #pragma unroll
     for (uint32_t e = 0; e < PT_WF_SUSP_STACK_ROWS; ++e) {
@@ -318,6 +408,31 @@ PT_DEV void suspend_ray(const PTWfBuffers& B, uint32_t rec, uint32_t slot, uint3
         const pt_u2 y = (2u * e + 1u < PT_WF_LDS_STACK) ? (pt_u2)st.lds[(2u * e + 1u) * st.stride] : pt_u2{0u, 0u};
         p[2u + e] = make_uint4(x.x, x.y, y.x, y.y);
     }
+}
+// The lane resumes the ray of record p and returns its ref; slotBase + (ref & 0x3FFFFFFF) is the ray's slot.  Only t of the hit is
+// in a record: the best hit so far was left in the hit array.
+template <class ST>
+PT_DEV uint32_t resume_ray(const PTWfBuffers& B, const uint4* p, uint32_t slotBase, RayState& rs, ST& st)
+{
+    const uint4 a = p[0], b = p[1];
+    uint4 er[PT_WF_SUSP_STACK_ROWS];
+#pragma unroll
+    for (uint32_t e = 0; e < PT_WF_SUSP_STACK_ROWS; ++e) er[e] = p[2u + e];
+    const uint32_t kind = a.x >> 30;
+    v3 o, d;
+    fetch_ray(B, slotBase + (a.x & 0x3FFFFFFFu), kind, o, d);
+    ray_begin(rs, o, d, kind != 0u);                                  // same invDir / octinv4 as when the ray started
+    rs.sp = a.y & 0xFFu;
+    rs.overflow = (a.y & 0x100u) != 0u;
+    rs.ng = make_uint2(a.z, a.w);
+    rs.tg = make_uint2(b.x, b.y);
+    rs.hit.t = pt_asfloat(b.z);
+#pragma unroll
+    for (uint32_t e = 0; e < PT_WF_SUSP_STACK_ROWS; ++e) {
+        st.lds[(2u * e) * st.stride] = pt_u2{er[e].x, er[e].y};
+        if (2u * e + 1u < PT_WF_LDS_STACK) st.lds[(2u * e + 1u) * st.stride] = pt_u2{er[e].z, er[e].w};
+    }
+    return a.x;
 }
 
 // RANGE: slots per wave (64 or 128; pt_launch_wavefront picks by the size of the launch)
@@ -374,61 +489,29 @@ __global__ __launch_bounds__(64, PT_WF_TRACE_MIN_WAVES) void pt_wf_trace_refill(
         uint32_t nIdle = (uint32_t)__popcll(__ballot(!have));
         // ---- refill: compact the next candidates into the idle lanes
         while (cursor < nItems && (nIdle >= PT_WF_REFILL || nIdle == 64u)) {
-            const unsigned long long idle = __ballot(!have);
-            const uint32_t rankI = rank_below(idle);
             if (!TAIL) {
                 const uint32_t item = cursor + lane;
                 const uint32_t kind = item / RANGE;
                 const uint32_t slot = slotBase + (item & (RANGE - 1u));
                 bool valid = item < nItems && slot < B.numSlots;
                 if (valid) valid = ray_exists(B.flags[slot], kind);
-                const unsigned long long V = __ballot(valid);
-                const uint32_t nV = (uint32_t)__popcll(V);
-                const uint32_t take = nIdle < nV ? nIdle : nV;
-                const uint32_t rankV = rank_below(V);
-                uint32_t consumed = 64u;
-                if (take < nV) consumed = (uint32_t)__ffsll((long long)__ballot(valid && rankV == take)) - 1u;   // first ray NOT taken
-                if (valid && rankV < take) xchg[rankV] = item;
-                __builtin_amdgcn_wave_barrier();
-                if (!have && rankI < take) {
-                    const uint32_t it = xchg[rankI];
+                const Compaction c = compact_candidates(xchg, !have, nIdle, valid, item);
+                if (!have && c.rankI < c.take) {
+                    const uint32_t it = xchg[c.rankI];
                     myKind = it / RANGE;
                     mySlot = slotBase + (it & (RANGE - 1u));
-                    v3 o, d;
-                    fetch_ray(B, mySlot, myKind, o, d);
-                    if (myKind == 0u) cn.closestRays++; else cn.shadowRays++;
-                    if (ray_begin(rs, o, d, myKind != 0u)) {
-                        // NaN ray: certain miss
-                        if (myKind == 0u) store_miss(B, mySlot);
-                        else store_occlusion(B, myKind, mySlot, false);
-                    } else have = true;
+                    have = start_ray(B, mySlot, myKind, rs, cn);
                 }
                 __builtin_amdgcn_wave_barrier();
-                cursor += consumed;
+                cursor += c.consumed;
             } else {
+                const uint32_t rankI = rank_below(__ballot(!have));
                 const uint32_t left = nItems - cursor;
                 const uint32_t take = nIdle < left ? nIdle : left;
                 if (!have && rankI < take) {
-                    const uint4* p = B.susp + (size_t)xchg[cursor + rankI] * PT_WF_SUSP_ROWS;
-                    const uint4 a = p[0], b = p[1];
-                    uint4 er[PT_WF_SUSP_STACK_ROWS];
-#pragma unroll
-                    for (uint32_t e = 0; e < PT_WF_SUSP_STACK_ROWS; ++e) er[e] = p[2u + e];
-                    mySlot = a.x & 0x3FFFFFFFu;
-                    myKind = a.x >> 30;
-                    v3 o, d;
-                    fetch_ray(B, mySlot, myKind, o, d);
-                    ray_begin(rs, o, d, myKind != 0u);                // same invDir / octinv4 as when the ray started
-                    rs.sp = a.y & 0xFFu;
-                    rs.overflow = (a.y & 0x100u) != 0u;
-                    rs.ng = make_uint2(a.z, a.w);
-                    rs.tg = make_uint2(b.x, b.y);
-                    rs.hit.t = pt_asfloat(b.z);
-#pragma unroll
-                    for (uint32_t e = 0; e < PT_WF_SUSP_STACK_ROWS; ++e) {
-                        st.lds[(2u * e) * 64u] = pt_u2{er[e].x, er[e].y};
-                        if (2u * e + 1u < PT_WF_LDS_STACK) st.lds[(2u * e + 1u) * 64u] = pt_u2{er[e].z, er[e].w};
-                    }
+                    mySlot = resume_ray(B, B.susp + (size_t)xchg[cursor + rankI] * PT_WF_SUSP_ROWS, 0u, rs, st);
+                    myKind = mySlot >> 30;
+                    mySlot &= 0x3FFFFFFFu;
                     have = true;
                 }
                 cursor += take;
@@ -441,55 +524,23 @@ __global__ __launch_bounds__(64, PT_WF_TRACE_MIN_WAVES) void pt_wf_trace_refill(
         const bool exhausted = cursor >= nItems;
         const uint32_t stopAt = !exhausted ? PT_WF_REFILL : ((!TAIL && PT_WF_SUSPEND > 0u) ? 64u - PT_WF_SUSPEND : 64u);
         while (nIdle < stopAt) {
-            // Two phases per wave iteration instead of ray_step's nested loops: (1) every lane with a triangle pending tests ONE
-            // (the block runs when PT_WF_TRI_PARK lanes want it, or when nobody can do anything else), (2) every lane without a
-            // triangle pending -- including those that have just tested their last one -- pops and visits its next node.  A lane
-            // with k triangles spends k - 1 extra iterations in phase 1 while its neighbours keep visiting nodes; the triangle
-            // block runs once per iteration at ~3x the lane utilisation of the nested loop (2.1 executions at 8 %).
-            const bool wantTri = have && rs.tg.y != 0u;
-            const uint32_t nT = (uint32_t)__popcll(__ballot(wantTri));
-            const uint32_t nN = (uint32_t)__popcll(__ballot(have && !wantTri));
-            bool fin = false;
-            if ((nT >= PT_WF_TRI_PARK || nN == 0u) && wantTri) {
-                const float tBefore = rs.hit.t;
-                fin = ray_tri_one<STATS>(S, rs, cn);
-                // TAIL: the hit record goes to memory when a test improved it (a resumed ray has only t in registers).
-                // main launch: (u, v, triIndex) stay in registers and are written once, when the ray finishes or is suspended
-                if (TAIL && myKind == 0u && rs.hit.t < tBefore) f4_array(B, PT_F4_HIT)[mySlot] = make_float4(rs.hit.t, rs.hit.u, rs.hit.v, pt_asfloat(rs.hit.triIndex));
-            }
-            if (have && !fin && rs.tg.y == 0u) fin = ray_node_one<STATS>(S, rs, st, cn);
+            const float tBefore = rs.hit.t;
+            const bool fin = wave_step<STATS>(S, have, rs, st, cn);
+            // TAIL: the hit record goes to memory when a test improved it (a resumed ray has only t in registers).
+            // main launch: (u, v, triIndex) stay in registers and are written once, when the ray finishes or is suspended
+            if (TAIL && myKind == 0u && rs.hit.t < tBefore) f4_array(B, PT_F4_HIT)[mySlot] = make_float4(rs.hit.t, rs.hit.u, rs.hit.v, pt_asfloat(rs.hit.triIndex));
             if (fin) {
-                if (myKind == 0u) {
-                    if (!(rs.hit.t < PT_FAR_PLANE)) store_miss(B, mySlot);
-                    else if (!TAIL) f4_array(B, PT_F4_HIT)[mySlot] = make_float4(rs.hit.t, rs.hit.u, rs.hit.v, pt_asfloat(rs.hit.triIndex));
-                }
-                else store_occlusion(B, myKind, mySlot, rs.hit.t < PT_FAR_PLANE);
+                store_result(B, mySlot, myKind, rs.hit.t < PT_FAR_PLANE, rs.hit, TAIL);
                 have = false;
             }
             nIdle = (uint32_t)__popcll(__ballot(!have));
         }
         if (!TAIL && PT_WF_SUSPEND > 0u && exhausted && nIdle < 64u) {
-            // a ray whose stack reaches into the HBM slab stays (the record only holds the LDS entries): finish those first
-            if (__ballot(have && rs.sp > PT_WF_LDS_STACK) != 0ull) {
-                while (__ballot(have && rs.sp > PT_WF_LDS_STACK) != 0ull) {
-                    if (have) {
-                        // a lane may arrive with triangles pending: one triangle OR one node visit, whichever is next for it
-                        const bool fin = rs.tg.y != 0u ? ray_tri_one<STATS>(S, rs, cn) : ray_node_one<STATS>(S, rs, st, cn);
-                        if (fin) {
-                            if (myKind == 0u) {
-                                if (!(rs.hit.t < PT_FAR_PLANE)) store_miss(B, mySlot);
-                                else f4_array(B, PT_F4_HIT)[mySlot] = make_float4(rs.hit.t, rs.hit.u, rs.hit.v, pt_asfloat(rs.hit.triIndex));
-                            } else store_occlusion(B, myKind, mySlot, rs.hit.t < PT_FAR_PLANE);
-                            have = false;
-                        }
-                    }
-                }
-            }
+            have = finish_slab_rays<STATS>(S, B, have, mySlot, myKind, rs, st, cn);
             const unsigned long long act = __ballot(have);
             // a suspended bounce ray leaves its best hit so far in the hit array (the tail launch writes there only when it improves it)
-            if (have && myKind == 0u && rs.hit.t < PT_FAR_PLANE)
-                f4_array(B, PT_F4_HIT)[mySlot] = make_float4(rs.hit.t, rs.hit.u, rs.hit.v, pt_asfloat(rs.hit.triIndex));
-            if (have) suspend_ray(B, *PT_LDS_WORD(s_gw) * PT_WF_SUSPEND + rank_below(act), mySlot, myKind, rs, st);
+            if (have && myKind == 0u && rs.hit.t < PT_FAR_PLANE) store_hit(B, mySlot, rs.hit);
+            if (have) suspend_ray(B.susp + (size_t)(*PT_LDS_WORD(s_gw) * PT_WF_SUSPEND + rank_below(act)) * PT_WF_SUSP_ROWS, mySlot | (myKind << 30), rs, st);
             have = false;
             nSuspended = (uint32_t)__popcll(act);
             break;
@@ -616,31 +667,21 @@ __global__ __launch_bounds__(64 * WAVES, PT_WF_TLAS_MIN_WAVES) void pt_wf_trace_
                 slotBase = wgBase + c * kChunk;
                 cursor = 0u;
             }
-            const unsigned long long idle = __ballot(!have);
-            const uint32_t rankI = rank_below(idle);
             const uint32_t item = cursor + lane;
             const uint32_t kind = item / kChunk;
             const uint32_t slot = slotBase + (item & (kChunk - 1u));
             bool valid = item < nItems && slot < B.numSlots;
             if (valid) valid = ray_exists(B.flags[slot], kind);
-            const unsigned long long V = __ballot(valid);
-            const uint32_t nV = (uint32_t)__popcll(V);
-            const uint32_t take = nIdle < nV ? nIdle : nV;
-            const uint32_t rankV = rank_below(V);
-            uint32_t consumed = 64u;
-            if (take < nV) consumed = (uint32_t)__ffsll((long long)__ballot(valid && rankV == take)) - 1u;
-            if (valid && rankV < take) xchg[rankV] = item;
-            __builtin_amdgcn_wave_barrier();
-            if (!have && rankI < take) {
-                const uint32_t it = xchg[rankI];
+            const Compaction c = compact_candidates(xchg, !have, nIdle, valid, item);
+            if (!have && c.rankI < c.take) {
+                const uint32_t it = xchg[c.rankI];
                 myKind = it / kChunk;
                 mySlot = slotBase + (it & (kChunk - 1u));
                 v3 d;
                 fetch_ray(B, mySlot, myKind, O, d);
                 if (myKind == 0u) cn.closestRays++; else cn.shadowRays++;
                 if (pt_isnan(O.x) || pt_isnan(O.y) || pt_isnan(O.z) || pt_isnan(d.x) || pt_isnan(d.y) || pt_isnan(d.z)) {
-                    if (myKind == 0u) store_miss(B, mySlot);              // NaN ray: certain miss (traverse_tlas)
-                    else store_occlusion(B, myKind, mySlot, false);
+                    store_result(B, mySlot, myKind, false, rs.hit, true);     // NaN ray: certain miss (traverse_tlas)
                 } else {
                     const v3 D = normalize3(d);                           // tlas.hlsl:238-240
                     rD = mk3(1.0f / D.x, 1.0f / D.y, 1.0f / D.z);
@@ -651,7 +692,7 @@ __global__ __launch_bounds__(64 * WAVES, PT_WF_TLAS_MIN_WAVES) void pt_wf_trace_
                 }
             }
             __builtin_amdgcn_wave_barrier();
-            cursor += consumed;
+            cursor += c.consumed;
             nIdle = (uint32_t)__popcll(__ballot(!have));
         }
         if (nIdle == 64u) break;
@@ -739,8 +780,8 @@ __global__ __launch_bounds__(64 * WAVES, PT_WF_TLAS_MIN_WAVES) void pt_wf_trace_
                     }
                 }
                 if (finished) {
-                    if (myKind == 0u) { if (!(rs.hit.t < PT_FAR_PLANE)) store_miss(B, mySlot); }
-                    else store_occlusion(B, myKind, mySlot, false);
+                    // the hit record was stored when it improved; a shadow ray that gets here found nothing (stopNow below ends the others)
+                    store_result(B, mySlot, myKind, myKind == 0u && rs.hit.t < PT_FAR_PLANE, rs.hit, true);
                     if (STATS && toverflow) cn.overflows++;
                     have = false;
                 }
@@ -777,7 +818,7 @@ __global__ __launch_bounds__(64 * WAVES, PT_WF_TLAS_MIN_WAVES) void pt_wf_trace_
                     inBlas = false;
                     if (rs.anyHit) {
                         if (hitFound) {                                                                  // stopNow (tlas.hlsl:196-200)
-                            store_occlusion(B, myKind, mySlot, true);
+                            store_result(B, mySlot, myKind, true, rs.hit, true);
                             if (STATS && toverflow) cn.overflows++;
                             have = false;
                         }
@@ -803,7 +844,7 @@ __global__ __launch_bounds__(64 * WAVES, PT_WF_TLAS_MIN_WAVES) void pt_wf_trace_
 }
 
 // ------------------------------------------------------------------------------------------
-// persistent trace (schedule 1): the refill kernel above, made persistent.  The grid is exactly the number of
+// persistent trace (schedule 3): the refill kernel above, made persistent.  The grid is exactly the number of
 // waves the chip holds; a wave that has scanned its 64-slot chunk pulls the NEXT chunk index from a device counter
 // while its remaining rays are still in flight, so lanes are refilled continuously and nothing drains until the
 // very end of the launch.  Chunk counters are sharded 8 ways (one per XCD under round-robin workgroup placement,
@@ -865,35 +906,20 @@ __global__ __launch_bounds__(64, PT_WF_TRACE_MIN_WAVES) void pt_wf_trace_persist
                 slotBase = chunk * PT_WF_CHUNK;
                 cursor = 0u;
             }
-            const unsigned long long idle = __ballot(!have);
             const uint32_t item = cursor + lane;
             const uint32_t kind = item / PT_WF_CHUNK;
             const uint32_t slot = slotBase + (item & (PT_WF_CHUNK - 1u));
             bool valid = item < nItems && slot < B.numSlots;
             if (valid) valid = ray_exists(B.flags[slot], kind);
-            const unsigned long long V = __ballot(valid);
-            const uint32_t nV = (uint32_t)__popcll(V);
-            const uint32_t take = nIdle < nV ? nIdle : nV;
-            const uint32_t rankV = rank_below(V);
-            uint32_t consumed = 64u;
-            if (take < nV) consumed = (uint32_t)__ffsll((long long)__ballot(valid && rankV == take)) - 1u;
-            if (valid && rankV < take) xchg[rankV] = item;
-            __builtin_amdgcn_wave_barrier();
-            const uint32_t rankI = rank_below(idle);
-            if (!have && rankI < take) {
-                const uint32_t it = xchg[rankI];
+            const Compaction c = compact_candidates(xchg, !have, nIdle, valid, item);
+            if (!have && c.rankI < c.take) {
+                const uint32_t it = xchg[c.rankI];
                 myKind = it / PT_WF_CHUNK;
                 mySlot = slotBase + (it & (PT_WF_CHUNK - 1u));
-                v3 o, d;
-                fetch_ray(B, mySlot, myKind, o, d);
-                if (myKind == 0u) cn.closestRays++; else cn.shadowRays++;
-                if (ray_begin(rs, o, d, myKind != 0u)) {
-                    if (myKind == 0u) store_miss(B, mySlot);
-                    else store_occlusion(B, myKind, mySlot, false);
-                } else have = true;
+                have = start_ray(B, mySlot, myKind, rs, cn);
             }
             __builtin_amdgcn_wave_barrier();
-            cursor += consumed;
+            cursor += c.consumed;
             nIdle = (uint32_t)__popcll(__ballot(!have));
         }
         if (nIdle == 64u) break;                                      // no chunk left and nothing in flight
@@ -904,8 +930,7 @@ __global__ __launch_bounds__(64, PT_WF_TRACE_MIN_WAVES) void pt_wf_trace_persist
                 const bool fin = ray_step<STATS>(S, rs, st, cn);
                 if (myKind == 0u && rs.hit.t < tBefore) f4_array(B, PT_F4_HIT)[mySlot] = make_float4(rs.hit.t, rs.hit.u, rs.hit.v, pt_asfloat(rs.hit.triIndex));
                 if (fin) {
-                    if (myKind == 0u) { if (!(rs.hit.t < PT_FAR_PLANE)) store_miss(B, mySlot); }
-                    else store_occlusion(B, myKind, mySlot, rs.hit.t < PT_FAR_PLANE);
+                    store_result(B, mySlot, myKind, rs.hit.t < PT_FAR_PLANE, rs.hit, true);
                     have = false;
                 }
             }
@@ -1183,27 +1208,10 @@ __global__ __launch_bounds__(64, PT_WF_FUSED_WAVES) void pt_wf_fused(DScene S, P
             if (lane < 2u * K) (&s_pend[pn][0][0])[lane] = 0u;
             // parked rays first: lane i takes record i (all lanes are idle here)
             if (PT_WF_SUSPEND > 0u && lane < nSusp) {
-                const uint4 a = s_susp[lane][0], b = s_susp[lane][1];
-                myRef = a.x;
-                const uint32_t kind = myRef >> 30;
-                const uint32_t ctx = ctxBase + (myRef & 0x3FFFFFFFu);
-                v3 o, d;
-                fetch_ray(B, ctx, kind, o, d);
-                ray_begin(rs, o, d, kind != 0u);                     // same invDir / octinv4 as when the ray started
-                rs.sp = a.y & 0xFFu;
-                rs.overflow = (a.y & 0x100u) != 0u;
-                rs.ng = make_uint2(a.z, a.w);
-                rs.tg = make_uint2(b.x, b.y);
-                rs.hit.t = pt_asfloat(b.z);
-                if (kind == 0u && rs.hit.t < PT_FAR_PLANE) {         // the best hit so far was left in the hit array
-                    const float4 h = f4_array(B, PT_F4_HIT)[ctx];
+                myRef = resume_ray(B, s_susp[lane], ctxBase, rs, st);
+                if ((myRef >> 30) == 0u && rs.hit.t < PT_FAR_PLANE) {   // the best hit so far was left in the hit array
+                    const float4 h = f4_array(B, PT_F4_HIT)[ctxBase + (myRef & 0x3FFFFFFFu)];
                     rs.hit.u = h.y; rs.hit.v = h.z; rs.hit.triIndex = pt_asuint(h.w);
-                }
-#pragma unroll
-                for (uint32_t e = 0; e < PT_WF_SUSP_STACK_ROWS; ++e) {
-                    const uint4 er = s_susp[lane][2u + e];
-                    st.lds[(2u * e) * 64u] = pt_u2{er.x, er.y};
-                    if (2u * e + 1u < PT_WF_LDS_STACK) st.lds[(2u * e + 1u) * 64u] = pt_u2{er.z, er.w};
                 }
                 have = true;
             }
@@ -1212,21 +1220,9 @@ __global__ __launch_bounds__(64, PT_WF_FUSED_WAVES) void pt_wf_fused(DScene S, P
             uint32_t cursor = 0u;
             bool startedNew = false;
 
-            auto finish = [&]() {                                    // the lane's ray is complete: write its result
-                const uint32_t kind = myRef >> 30;
-                const uint32_t ctx = ctxBase + (myRef & 0x3FFFFFFFu);
-                if (kind == 0u) {
-                    if (!(rs.hit.t < PT_FAR_PLANE)) store_miss(B, ctx);
-                    else f4_array(B, PT_F4_HIT)[ctx] = make_float4(rs.hit.t, rs.hit.u, rs.hit.v, pt_asfloat(rs.hit.triIndex));
-                } else store_occlusion(B, kind, ctx, rs.hit.t < PT_FAR_PLANE);
-                have = false;
-            };
-
             while (true) {
                 uint32_t nIdle = (uint32_t)__popcll(__ballot(!have));
                 while (cursor < nItems && (nIdle >= PT_WF_REFILL || nIdle == 64u)) {
-                    const unsigned long long idle = __ballot(!have);
-                    const uint32_t rankI = rank_below(idle);
                     const uint32_t item = cursor + lane;
                     const uint32_t kind = item / (64u * K);
                     const uint32_t local = item & (64u * K - 1u);    // group * 64 + lane of the context
@@ -1236,29 +1232,14 @@ __global__ __launch_bounds__(64, PT_WF_FUSED_WAVES) void pt_wf_fused(DScene S, P
                         // (a context with a parked ray got all its rays last round; one without a pixel is DONE)
                         valid = !((pw >> (local & 31u)) & 1u) && ray_exists(B.flags[ctxBase + local], kind);
                     }
-                    const unsigned long long V = __ballot(valid);
-                    const uint32_t nV = (uint32_t)__popcll(V);
-                    const uint32_t take = nIdle < nV ? nIdle : nV;
-                    const uint32_t rankV = rank_below(V);
-                    uint32_t consumed = 64u;
-                    if (take < nV) consumed = (uint32_t)__ffsll((long long)__ballot(valid && rankV == take)) - 1u;   // first ray NOT taken
-                    if (valid && rankV < take) xchg[rankV] = (kind << 30) | local;
-                    __builtin_amdgcn_wave_barrier();
-                    if (!have && rankI < take) {
-                        myRef = xchg[rankI];
-                        const uint32_t myKind = myRef >> 30;
-                        const uint32_t ctx = ctxBase + (myRef & 0x3FFFFFFFu);
-                        v3 o, d;
-                        fetch_ray(B, ctx, myKind, o, d);
-                        if (myKind == 0u) cn.closestRays++; else cn.shadowRays++;
-                        if (ray_begin(rs, o, d, myKind != 0u)) {
-                            if (myKind == 0u) store_miss(B, ctx);             // NaN ray: certain miss
-                            else store_occlusion(B, myKind, ctx, false);
-                        } else have = true;
+                    const Compaction c = compact_candidates(xchg, !have, nIdle, valid, (kind << 30) | local);
+                    if (!have && c.rankI < c.take) {
+                        myRef = xchg[c.rankI];
+                        have = start_ray(B, ctxBase + (myRef & 0x3FFFFFFFu), myRef >> 30, rs, cn);
                     }
                     __builtin_amdgcn_wave_barrier();
-                    if (take > 0u) startedNew = true;
-                    cursor += consumed;
+                    if (c.take > 0u) startedNew = true;
+                    cursor += c.consumed;
                     nIdle = (uint32_t)__popcll(__ballot(!have));
                 }
                 if (nIdle == 64u) break;
@@ -1267,37 +1248,19 @@ __global__ __launch_bounds__(64, PT_WF_FUSED_WAVES) void pt_wf_fused(DScene S, P
                 const bool mayPark = PT_WF_SUSPEND > 0u && exhausted && startedNew;
                 const uint32_t stopAt = !exhausted ? PT_WF_REFILL : (mayPark ? 64u - PT_WF_SUSPEND : 64u);
                 while (nIdle < stopAt) {
-                    const bool wantTri = have && rs.tg.y != 0u;
-                    const uint32_t nT = (uint32_t)__popcll(__ballot(wantTri));
-                    const uint32_t nN = (uint32_t)__popcll(__ballot(have && !wantTri));
-                    bool fin = false;
-                    if ((nT >= PT_WF_TRI_PARK || nN == 0u) && wantTri) fin = ray_tri_one<STATS>(S, rs, cn);
-                    if (have && !fin && rs.tg.y == 0u) fin = ray_node_one<STATS>(S, rs, st, cn);
-                    if (fin) finish();
+                    if (wave_step<STATS>(S, have, rs, st, cn)) {
+                        store_result(B, ctxBase + (myRef & 0x3FFFFFFFu), myRef >> 30, rs.hit.t < PT_FAR_PLANE, rs.hit, false);
+                        have = false;
+                    }
                     nIdle = (uint32_t)__popcll(__ballot(!have));
                 }
                 if (mayPark && nIdle < 64u) {
-                    // a ray whose stack reaches into the HBM slab stays (a record only holds the LDS entries): finish those first
-                    while (__ballot(have && rs.sp > PT_WF_LDS_STACK) != 0ull) {
-                        if (have) {
-                            const bool fin = rs.tg.y != 0u ? ray_tri_one<STATS>(S, rs, cn) : ray_node_one<STATS>(S, rs, st, cn);
-                            if (fin) finish();
-                        }
-                    }
+                    have = finish_slab_rays<STATS>(S, B, have, ctxBase + (myRef & 0x3FFFFFFFu), myRef >> 30, rs, st, cn);
                     const unsigned long long act = __ballot(have);
                     if (have) {
                         const uint32_t kind = myRef >> 30, local = myRef & 0x3FFFFFFFu;
-                        if (kind == 0u && rs.hit.t < PT_FAR_PLANE)
-                            f4_array(B, PT_F4_HIT)[ctxBase + local] = make_float4(rs.hit.t, rs.hit.u, rs.hit.v, pt_asfloat(rs.hit.triIndex));
-                        const uint32_t rec = rank_below(act);
-                        s_susp[rec][0] = make_uint4(myRef, rs.sp | (rs.overflow ? 0x100u : 0u), rs.ng.x, rs.ng.y);
-                        s_susp[rec][1] = make_uint4(rs.tg.x, rs.tg.y, pt_asuint(rs.hit.t), 0u);
-#pragma unroll
-                        for (uint32_t e = 0; e < PT_WF_SUSP_STACK_ROWS; ++e) {
-                            const pt_u2 x = st.lds[(2u * e) * 64u];
-                            const pt_u2 y = (2u * e + 1u < PT_WF_LDS_STACK) ? (pt_u2)st.lds[(2u * e + 1u) * 64u] : pt_u2{0u, 0u};
-                            s_susp[rec][2u + e] = make_uint4(x.x, x.y, y.x, y.y);
-                        }
+                        if (kind == 0u && rs.hit.t < PT_FAR_PLANE) store_hit(B, ctxBase + local, rs.hit);
+                        suspend_ray(s_susp[rank_below(act)], myRef, rs, st);
                         atomicOr(&s_pend[pn][local >> 6][(local >> 5) & 1u], 1u << (local & 31u));
                         have = false;
                     }
@@ -1403,14 +1366,17 @@ __global__ __launch_bounds__(256, 2) void pt_wf_cleanup(DScene S, PTFrameParams 
 
 // resolve: the pixel write of PathTracer.compute:89-98, applied to every pixel's sample sum -- for a batch, once per pass and in
 // pass order, each pass reading what the previous one would have written (the intermediate frames are never stored; the running
-// mean is the same chain of fp32 operations)
-__global__ __launch_bounds__(256) void pt_wf_resolve(PTFrameParams P, PTBatch batch, PTTileMap tm, PTWfBuffers B, const float4* __restrict__ sums,
+// mean is the same chain of fp32 operations).
+// MAP = PTListMap, the resolve of a pass over a block list: workgroup e writes the covered pixels of table entry e with the block's
+// own sample count (CurrentSample = n_b + j * spp).  Every other pixel of `output` was copied from `accumulated` by the launcher.
+template <class MAP = PTTileMap>
+__global__ __launch_bounds__(256) void pt_wf_resolve(PTFrameParams P, PTBatch batch, MAP tm, PTWfBuffers B, const float4* __restrict__ sums,
                                                      const float4* __restrict__ accumulated, float4* __restrict__ output)
 {
     const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
-    uint32_t px, py;
+    uint32_t px, py, pass, base;
     Counters cn = {};
-    if (slot < B.slotsPerPass && pt_slot_to_pixel(tm, slot, px, py)) {
+    if (slot < B.slotsPerPass && wf_pixel(tm, B, slot, blockIdx.x * 256u, px, py, pass, base)) {
         const uint32_t pixelIndex = py * P.OutputWidth + px;
         const uint32_t numSamples = P.SamplesPerPass > 1 ? (uint32_t)P.SamplesPerPass : 1u;
         const float fSamples = (float)numSamples;
@@ -1418,43 +1384,8 @@ __global__ __launch_bounds__(256) void pt_wf_resolve(PTFrameParams P, PTBatch ba
         for (uint32_t j = 0; j < batch.count; ++j) {
             uint32_t seedRoot, currentSample;
             pt_batch_pick(batch, j, seedRoot, currentSample);
+            if (kListMap<MAP>) currentSample = base + j * numSamples;
             const v3 color = xyz(sums[(size_t)j * B.slotsPerPass + slot]);      // per-pixel sample sum: B.color (schedules 1-3) or B.pixsum (schedule 4)
-            if (currentSample > 0u) {
-                if (j == 0u) {
-                    const float4 a = accumulated[pixelIndex];
-                    acc = mk3(a.x, a.y, a.z);
-                }
-                cn.pixelsRead++;
-                const float cs = (float)currentSample;
-                acc = (color + acc * cs) / (cs + fSamples);
-            } else {
-                acc = color / fSamples;
-            }
-            cn.pixelsWritten++;
-        }
-        output[pixelIndex] = make_float4(acc.x, acc.y, acc.z, 1.0f);
-    }
-    flush_counters<false>(cn, B.statRows, blockIdx.x * 4u + (threadIdx.x >> 6), threadIdx.x & 63u);
-}
-
-// resolve of a pass over a block list: workgroup e writes the covered pixels of table entry e with the block's own sample count
-// (the same chain of fp32 operations as pt_wf_resolve with CurrentSample = n_b + j * spp).  Every other pixel of `output` was
-// copied from `accumulated` by the launcher.
-__global__ __launch_bounds__(256) void pt_wf_resolve_list(PTFrameParams P, PTBatch batch, PTListMap lm, PTWfBuffers B, const float4* __restrict__ sums,
-                                                          const float4* __restrict__ accumulated, float4* __restrict__ output)
-{
-    const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
-    uint32_t px, py;
-    Counters cn = {};
-    const uint2 entry = lm.table[blockIdx.x];
-    if (pt_list_slot_to_pixel(lm.frameBlocksX, lm.coverW, lm.coverH, entry.x, threadIdx.x, px, py)) {
-        const uint32_t pixelIndex = py * P.OutputWidth + px;
-        const uint32_t numSamples = P.SamplesPerPass > 1 ? (uint32_t)P.SamplesPerPass : 1u;
-        const float fSamples = (float)numSamples;
-        v3 acc = mk3(0.0f);
-        for (uint32_t j = 0; j < batch.count; ++j) {
-            const uint32_t currentSample = entry.y + j * numSamples;
-            const v3 color = xyz(sums[(size_t)j * B.slotsPerPass + slot]);
             if (currentSample > 0u) {
                 if (j == 0u) {
                     const float4 a = accumulated[pixelIndex];
@@ -1601,7 +1532,7 @@ hipError_t launch_sequence(const PTWfLaunch& L, const MAP& tm, uint32_t* launche
             if (L.orderAfter && (e = hipStreamWaitEvent(stream, L.orderAfter, 0)) != hipSuccess) return e;
             if (L.zeroOutputFirst &&
                 (e = hipMemsetAsync(output, 0, (size_t)P.OutputWidth * P.OutputHeight * sizeof(float4), stream)) != hipSuccess) return e;
-            hipLaunchKernelGGL(pt_wf_resolve, dim3(nbPass), dim3(256), 0, stream, P, batch, tm, B, (const float4*)B.pixsum, L.accumulated, output);
+            hipLaunchKernelGGL(pt_wf_resolve<PTTileMap>, dim3(nbPass), dim3(256), 0, stream, P, batch, tm, B, (const float4*)B.pixsum, L.accumulated, output);
             hipLaunchKernelGGL(pt_wf_fold_rows, dim3(256), dim3(256), 0, stream, B.statRows, B.numStatRows, L.counters);
             if (launchesOut) *launchesOut = 3u;
             return hipGetLastError();
@@ -1670,10 +1601,9 @@ hipError_t launch_sequence(const PTWfLaunch& L, const MAP& tm, uint32_t* launche
         // pixels outside the list keep Accumulated, bit for bit: one copy of the frame, then the resolve overwrites the listed blocks
         if (L.accumulated &&
             (e = hipMemcpyAsync(output, L.accumulated, (size_t)P.OutputWidth * P.OutputHeight * sizeof(float4), hipMemcpyDeviceToDevice, stream)) != hipSuccess) return e;
-        hipLaunchKernelGGL(pt_wf_resolve_list, dim3(nbPass), dim3(256), 0, stream, P, batch, tm, B, (const float4*)B.color, L.accumulated, output);
-    } else {
-        hipLaunchKernelGGL(pt_wf_resolve, dim3(nbPass), dim3(256), 0, stream, P, batch, tm, B, (const float4*)B.color, L.accumulated, output);
     }
+    if constexpr (!kRays)
+        hipLaunchKernelGGL(pt_wf_resolve<MAP>, dim3(nbPass), dim3(256), 0, stream, P, batch, tm, B, (const float4*)B.color, L.accumulated, output);
     hipLaunchKernelGGL(pt_wf_fold_rows, dim3(256), dim3(256), 0, stream, B.statRows, B.numStatRows, L.counters);
     launches += 3;
     if (launchesOut) *launchesOut = launches;
