@@ -272,14 +272,16 @@ PT_DEV bool intersect_triangle_rows(float4 t0, float4 t1, float4 t2, uint32_t in
     return false;
 }
 
-PT_DEV void intersect_triangle(const float4* __restrict__ tris, uint32_t triAddr, v3 o, v3 d, TraceHit& hit)
+// The fetch around it, for both variants.  indexOffset: the instance's attribute offset (HAS_TLAS), 0 in a flat scene.
+template <bool TLAS_EPS>
+PT_DEV bool intersect_triangle(const float4* __restrict__ tris, uint32_t triAddr, uint32_t indexOffset, v3 o, v3 d, TraceHit& hit)
 {
     // all 48 bytes are requested before the first use, so the whole test costs ONE memory round trip
     // (left to itself hipcc sinks the v0 load under the determinant test: two dependent round trips)
     const float4* tp = tris + triAddr;                    // one address, rows at immediate offsets 0 / 16 / 32
     float4 t0 = tp[0], t1 = tp[1], t2 = tp[2];
     asm volatile("" : "+v"(t0.x), "+v"(t1.x), "+v"(t2.x), "+v"(t2.w));
-    intersect_triangle_rows<false>(t0, t1, t2, 0u, o, d, hit);
+    return intersect_triangle_rows<TLAS_EPS>(t0, t1, t2, indexOffset, o, d, hit);
 }
 
 // ---- the node visit of util/bvh.hlsl:150-176, shared by EVERY traversal variant in this file --------------------------
@@ -331,9 +333,8 @@ PT_DEV void cwbvh_visit_node(const uint4* __restrict__ nodes, uint32_t nodeOffse
     cwbvh_apply_node<STATS>(o, invDir, octinv4, tmax, n0, n1, n2, n3, n4, ng, tg, cn);
 }
 
-// util/bvh.hlsl:126-199 for one lane.  ANYHIT = shadow ray: stops at the first accepted triangle
-// (ShadowRayIntersect only uses the boolean, util/bvh.hlsl:228-233, so the result is identical).
-//
+// ---- the ray: its setup and ONE outer iteration of its walk, shared by every traversal in this file and in pt_wavefront.hip ----
+// The only test for a NaN ray.
 // A ray with a NaN in its origin or direction can never be accepted by IntersectTriangle (every product
 // with the NaN poisons `a` or `u`, and all its comparisons are false), but under HLSL/IEEE min-max
 // semantics its slab test passes for EVERY child (cmin = 0, cmax = tmax), so the reference walks the whole
@@ -341,39 +342,85 @@ PT_DEV void cwbvh_visit_node(const uint4* __restrict__ nodes, uint32_t nodeOffse
 // RandomCosineHemisphere return the zero vector and normalize() turn it into NaN (util/random.hlsl:34-41,
 // util/light.hlsl:141) -- about two NEE rays per 1080p/8spp frame.  One lane visiting 45k nodes + 250k
 // triangles stalls its whole kernel for ~80 ms, so the miss is returned immediately (same result).
-// anyHitBelow: the any-hit walk stops once hit.t < anyHitBelow.  The render starts every ray at hit.t = PT_FAR_PLANE, so the
-// default means "a triangle was accepted"; a ray query (pt_query.hip) that starts at its own tmax passes that tmax.
+PT_DEV bool ray_has_nan(v3 o, v3 d)
+{
+    return pt_isnan(o.x) || pt_isnan(o.y) || pt_isnan(o.z) || pt_isnan(d.x) || pt_isnan(d.y) || pt_isnan(d.z);
+}
+
+// The state of a CWBVH walk between two outer iterations.  Inside an instance (HAS_TLAS) o and d are the LOCAL ray.
+struct RayState {
+    v3 o, d, invDir;
+    uint32_t octinv4;
+    uint2 ng, tg;
+    uint32_t sp;
+    TraceHit hit;
+    bool anyHit, overflow;
+    bool hitFound;      // HAS_TLAS: a triangle of the instance was accepted since ray_begin (tlas.hlsl:133)
+};
+
+// Where an instance's BLAS starts in the node, triangle and attribute arrays (HAS_TLAS; a flat scene has none)
+struct BlasOffsets { uint32_t node, tri, attr; };
+
+// Starts a walk at the root: the only place that forms invDir and octinv4.  r.hit is left alone (an instance continues with the
+// t of the one before).  Returns true when the ray is finished before it started (ray_has_nan: a certain miss).
+PT_DEV bool ray_begin(RayState& r, v3 o, v3 d, bool anyHit)
+{
+    r.o = o; r.d = d; r.anyHit = anyHit; r.overflow = false; r.hitFound = false;
+    r.sp = 0u;
+    r.ng = make_uint2(0u, 0x80000000u);
+    r.tg = make_uint2(0u, 0u);
+    r.invDir = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+    r.octinv4 = (7u - ((d.x < 0.0f ? 4u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 1u : 0u))) * 0x1010101u;
+    return ray_has_nan(o, d);
+}
+
+// ONE iteration of the reference's outer while(true), util/bvh.hlsl:141-197 and (INST, inside an instance) tlas.hlsl:149-206:
+// [node step | adopt triangle group] -> all triangles of the group -> [pop | finish].  Returns true when the walk is complete.
+// INST selects the instance's offsets, the distance > 0 triangle test and what stops an any-hit ray: a triangle of THIS
+// instance was accepted (tlas.hlsl:196-200) -- since the first one stops the walk, that is the triangle just tested (asking the
+// accumulated r.hitFound instead costs pt_query_tlas_anyhit 95 instructions); in a flat scene, hit.t < anyHitBelow.
+// anyHit = shadow ray: stops at the first accepted triangle (ShadowRayIntersect only uses the boolean, util/bvh.hlsl:228-233,
+// so the result is identical).
+// anyHitBelow: the render starts every ray at hit.t = PT_FAR_PLANE, so the default means "a triangle was accepted"; a ray query
+// (pt_query.hip) that starts at its own tmax passes that tmax.
+template <bool STATS, bool INST, class ST>
+PT_DEV bool cwbvh_iteration(const DScene& S, RayState& r, BlasOffsets off, ST& st, Counters& cn, float anyHitBelow = PT_FAR_PLANE)
+{
+    if (r.ng.y > 0x00FFFFFFu) {
+        cwbvh_visit_node<STATS>(S.nodes, INST ? off.node : 0u, r.o, r.invDir, r.octinv4, r.hit.t, r.ng, r.tg, r.sp, r.overflow, st, cn);
+    } else {
+        r.tg.x = r.ng.x; r.tg.y = r.ng.y;       // (by member: copied whole, the pair becomes ONE 64-bit value in a caller that keeps the
+                                                //  state in a local, with 64-bit compares and moves: +6 ... 14 instructions per flat query kernel)
+        r.ng = make_uint2(0u, 0u);
+    }
+    while (r.tg.y != 0u) {
+        const uint32_t triangleIndex = 31u - (uint32_t)__clz((int)r.tg.y);
+        const uint32_t triAddr = r.tg.x + triangleIndex * 3u;
+        const bool accepted = intersect_triangle<INST>(S.tris, INST ? off.tri + triAddr : triAddr, INST ? off.attr : 0u, r.o, r.d, r.hit);
+        if (INST) r.hitFound = accepted | r.hitFound;
+        if (STATS) cn.triTests++;
+        r.tg.y -= 1u << triangleIndex;
+        if (r.anyHit && (INST ? accepted : r.hit.t < anyHitBelow)) { r.tg.y = 0u; r.ng.y = 0u; r.sp = 0u; }
+    }
+    if (r.ng.y <= 0x00FFFFFFu) {
+        if (r.sp > 0u) { --r.sp; r.ng = stack_pop(st, r.sp); }
+        else {
+            if (STATS && r.overflow) cn.overflows++;
+            return true;
+        }
+    }
+    return false;
+}
+
+// util/bvh.hlsl:126-199 for one lane
 template <bool STATS, class ST>
 PT_DEV void traverse_cwbvh(const DScene& S, v3 o, v3 d, bool anyHit, TraceHit& hit, ST& st, Counters& cn, float anyHitBelow = PT_FAR_PLANE)
 {
-    if (pt_isnan(o.x) || pt_isnan(o.y) || pt_isnan(o.z) || pt_isnan(d.x) || pt_isnan(d.y) || pt_isnan(d.z)) return;
-    v3 invDir = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-    uint32_t octinv4 = (7u - ((d.x < 0.0f ? 4u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 1u : 0u))) * 0x1010101u;
-    uint32_t sp = 0;
-    uint2 ng = make_uint2(0u, 0x80000000u);
-    uint2 tg = make_uint2(0u, 0u);
-    bool overflow = false;
-    while (true) {
-        if (ng.y > 0x00FFFFFFu) {
-            cwbvh_visit_node<STATS>(S.nodes, 0u, o, invDir, octinv4, hit.t, ng, tg, sp, overflow, st, cn);
-        } else {
-            tg = ng;
-            ng = make_uint2(0u, 0u);
-        }
-        while (tg.y != 0u) {
-            uint32_t triangleIndex = 31u - (uint32_t)__clz((int)tg.y);
-            uint32_t triAddr = tg.x + triangleIndex * 3u;
-            intersect_triangle(S.tris, triAddr, o, d, hit);
-            if (STATS) cn.triTests++;
-            tg.y -= 1u << triangleIndex;
-            if (anyHit && hit.t < anyHitBelow) { tg.y = 0u; ng.y = 0u; sp = 0u; }
-        }
-        if (ng.y <= 0x00FFFFFFu) {
-            if (sp > 0u) { --sp; ng = stack_pop(st, sp); }
-            else break;
-        }
-    }
-    if (STATS && overflow) cn.overflows++;
+    RayState r;
+    if (ray_begin(r, o, d, anyHit)) return;
+    r.hit = hit;
+    while (!cwbvh_iteration<STATS, false>(S, r, BlasOffsets{}, st, cn, anyHitBelow)) {}
+    hit = r.hit;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -398,15 +445,29 @@ PT_DEV v4 mul44c(float4 c0, float4 c1, float4 c2, float4 c3, v4 v)   // Matrix4x
     return r;
 }
 
-PT_DEV bool intersect_triangle_inst(const float4* __restrict__ tris, uint32_t triAddr, uint32_t attrOffset, v3 o, v3 d, TraceHit& hit)
+// Instance entry, tlas.hlsl:129-147: the world ray (wo, wd) through worldToLocal (w0..w3, its columns) is the local ray of a
+// walk that starts at the instance's root.  Who owns the instance record fetches the rows.
+PT_DEV void instance_enter(RayState& r, float4 w0, float4 w1, float4 w2, float4 w3, v3 wo, v3 wd, bool anyHit)
 {
-    const float4* tp = tris + triAddr;                    // one address, rows at immediate offsets 0 / 16 / 32
-    float4 t0 = tp[0], t1 = tp[1], t2 = tp[2];
-    asm volatile("" : "+v"(t0.x), "+v"(t1.x), "+v"(t2.x), "+v"(t2.w));
-    return intersect_triangle_rows<true>(t0, t1, t2, attrOffset, o, d, hit);
+    const v4 lo4 = mul44c(w0, w1, w2, w3, v4{wo.x, wo.y, wo.z, 1.0f});
+    const v4 ld4 = mul44c(w0, w1, w2, w3, v4{wd.x, wd.y, wd.z, 0.0f});
+    ray_begin(r, mk3(lo4.x, lo4.y, lo4.z), mk3(ld4.x, ld4.y, ld4.z), anyHit);
 }
 
-// tlas.hlsl:129-234 for one instance.  Returns hit.distance < FAR_PLANE; sets stopNow for an occluded shadow ray.
+// Instance exit, tlas.hlsl:208-229, for an instance that improved a closest hit: the local hit point through localToWorld
+// (l0..l3) is the world-space position, which is returned; r.hit.t becomes its distance from the world origin wo.
+template <bool STATS>
+PT_DEV v3 instance_exit(RayState& r, float4 l0, float4 l1, float4 l2, float4 l3, v3 wo, Counters& cn)
+{
+    if (STATS) cn.attrFetches++;
+    const v3 lp = r.o + r.hit.t * r.d;
+    const v4 wp = mul44c(l0, l1, l2, l3, v4{lp.x, lp.y, lp.z, 1.0f});
+    const v3 pos = mk3(wp.x, wp.y, wp.z);
+    r.hit.t = length3(pos - wo);
+    return pos;
+}
+
+// One instance: entry, the walk, exit.  Returns hit.distance < FAR_PLANE; sets stopNow for an occluded shadow ray.
 template <bool STATS, class ST>
 PT_DEV bool traverse_instance(const DScene& S, v3 wo, v3 wd, uint32_t instIndex, bool isShadow, HitRecord& rec, ST& st, Counters& cn,
                               bool& stopNow)
@@ -414,45 +475,17 @@ PT_DEV bool traverse_instance(const DScene& S, v3 wo, v3 wd, uint32_t instIndex,
     const float4* ip = S.instances + (size_t)instIndex * 9;
     const float4 w0 = ip[4], w1 = ip[5], w2 = ip[6], w3 = ip[7], ints = ip[8];
     if (STATS) cn.instanceVisits++;
-    const uint32_t nodeOffset = pt_asuint(ints.x), triOffset = pt_asuint(ints.y), attrOffset = pt_asuint(ints.z);
-    v4 lo4 = mul44c(w0, w1, w2, w3, v4{wo.x, wo.y, wo.z, 1.0f});
-    v4 ld4 = mul44c(w0, w1, w2, w3, v4{wd.x, wd.y, wd.z, 0.0f});
-    const v3 o = mk3(lo4.x, lo4.y, lo4.z), d = mk3(ld4.x, ld4.y, ld4.z);
-    v3 invDir = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-    uint32_t octinv4 = (7u - ((d.x < 0.0f ? 4u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 1u : 0u))) * 0x1010101u;
-    bool hitFound = false, overflow = false;
-    uint32_t sp = 0;
-    uint2 ng = make_uint2(0u, 0x80000000u), tg = make_uint2(0u, 0u);
-    while (true) {
-        if (ng.y > 0x00FFFFFFu) {
-            cwbvh_visit_node<STATS>(S.nodes, nodeOffset, o, invDir, octinv4, rec.h.t, ng, tg, sp, overflow, st, cn);
-        } else {
-            tg = ng;
-            ng = make_uint2(0u, 0u);
-        }
-        while (tg.y != 0u) {
-            uint32_t triangleIndex = 31u - (uint32_t)__clz((int)tg.y);
-            uint32_t triAddr = tg.x + triangleIndex * 3u;
-            hitFound = intersect_triangle_inst(S.tris, triOffset + triAddr, attrOffset, o, d, rec.h) | hitFound;
-            if (STATS) cn.triTests++;
-            tg.y -= 1u << triangleIndex;
-            if (isShadow && hitFound) { stopNow = true; tg.y = 0u; ng.y = 0u; sp = 0u; }
-        }
-        if (ng.y <= 0x00FFFFFFu) {
-            if (sp > 0u) { --sp; ng = stack_pop(st, sp); }
-            else break;
-        }
-    }
-    if (STATS && overflow) cn.overflows++;
-    if (!isShadow && hitFound) {
-        if (STATS) cn.attrFetches++;
-        const float4 l0 = ip[0], l1 = ip[1], l2 = ip[2], l3 = ip[3];
-        v3 lp = o + rec.h.t * d;
-        v4 wp = mul44c(l0, l1, l2, l3, v4{lp.x, lp.y, lp.z, 1.0f});
-        rec.pos = mk3(wp.x, wp.y, wp.z);
-        rec.h.t = length3(rec.pos - wo);
+    const BlasOffsets off = {pt_asuint(ints.x), pt_asuint(ints.y), pt_asuint(ints.z)};
+    RayState r;
+    instance_enter(r, w0, w1, w2, w3, wo, wd, isShadow);
+    r.hit = rec.h;
+    while (!cwbvh_iteration<STATS, true>(S, r, off, st, cn)) {}
+    if (isShadow && r.hitFound) stopNow = true;
+    if (!isShadow && r.hitFound) {
+        rec.pos = instance_exit<STATS>(r, ip[0], ip[1], ip[2], ip[3], wo, cn);
         rec.inst = instIndex;
     }
+    rec.h = r.hit;
     return rec.h.t < PT_FAR_PLANE;
 }
 
@@ -467,11 +500,47 @@ PT_DEV bool tlas_stack_pop(const uint32_t (&stack)[PT_BVH_STACK_SIZE], uint32_t&
     return true;
 }
 
+// One TLAS node, tlas.hlsl:246-331, over its four rows: what it is and, for an inner node, where the walk goes.  Both child boxes
+// are tested against the current t (PT_FAR_PLANE stands for a miss) and the nearer one comes first.  Fetches and stacks are the
+// caller's: it descends to `near` and pushes `far` when pushFar, or pops when nothingHit; in a leaf it walks `count` index slots
+// from `first`, then pops.
+struct TlasStep {
+    bool leaf, nothingHit, pushFar;
+    uint32_t near, far;         // inner node: child node indices
+    uint32_t first, count;      // leaf: its slots of the instance index list
+};
+PT_DEV TlasStep tlas_node_step(float4 a, float4 b, float4 c, float4 e, v3 O, v3 rD, float t)
+{
+    TlasStep s = {};
+    s.count = pt_asuint(c.w);
+    s.first = pt_asuint(e.w);
+    s.leaf = s.count != 0u;
+    if (!s.leaf) {
+        uint32_t left = pt_asuint(a.w), right = pt_asuint(b.w);
+        const v3 t1a = (mk3(a.x, a.y, a.z) - O) * rD, t2a = (mk3(b.x, b.y, b.z) - O) * rD;
+        const float tmina = pt_max(pt_max(pt_max(pt_min(t1a.x, t2a.x), pt_min(t1a.y, t2a.y)), pt_min(t1a.z, t2a.z)), 0.0f);
+        const float tmaxa = pt_min(pt_min(pt_min(pt_max(t1a.x, t2a.x), pt_max(t1a.y, t2a.y)), pt_max(t1a.z, t2a.z)), t);
+        float dist1 = tmina > tmaxa ? PT_FAR_PLANE : tmina;
+        const v3 t1b = (mk3(c.x, c.y, c.z) - O) * rD, t2b = (mk3(e.x, e.y, e.z) - O) * rD;
+        const float tminb = pt_max(pt_max(pt_max(pt_min(t1b.x, t2b.x), pt_min(t1b.y, t2b.y)), pt_min(t1b.z, t2b.z)), 0.0f);
+        const float tmaxb = pt_min(pt_min(pt_min(pt_max(t1b.x, t2b.x), pt_max(t1b.y, t2b.y)), pt_max(t1b.z, t2b.z)), t);
+        float dist2 = tminb > tmaxb ? PT_FAR_PLANE : tminb;
+        if (dist1 > dist2) {
+            const float h = dist1; dist1 = dist2; dist2 = h;
+            const uint32_t n = left; left = right; right = n;
+        }
+        s.near = left; s.far = right;
+        s.nothingHit = dist1 == PT_FAR_PLANE;
+        s.pushFar = dist2 != PT_FAR_PLANE;
+    }
+    return s;
+}
+
 // tlas.hlsl:236-332
 template <bool STATS, class ST>
 PT_DEV bool traverse_tlas(const DScene& S, v3 O, v3 dir, bool isShadow, HitRecord& rec, ST& st, Counters& cn)
 {
-    if (pt_isnan(O.x) || pt_isnan(O.y) || pt_isnan(O.z) || pt_isnan(dir.x) || pt_isnan(dir.y) || pt_isnan(dir.z)) return false;
+    if (ray_has_nan(O, dir)) return false;
     const v3 D = normalize3(dir);
     const v3 rD = mk3(1.0f / D.x, 1.0f / D.y, 1.0f / D.z);
     bool hitFound = false, overflow = false;
@@ -482,36 +551,22 @@ PT_DEV bool traverse_tlas(const DScene& S, v3 O, v3 dir, bool isShadow, HitRecor
         const float4* np = (const float4*)(T + (size_t)nodeIndex * 16u);
         const float4 a = np[0], b = np[1], c = np[2], e = np[3];
         if (STATS) cn.tlasNodeVisits++;
-        const uint32_t instanceCount = pt_asuint(c.w);
-        if (instanceCount == 0u) {
-            uint32_t left = pt_asuint(a.w), right = pt_asuint(b.w);
-            v3 t1a = (mk3(a.x, a.y, a.z) - O) * rD, t2a = (mk3(b.x, b.y, b.z) - O) * rD;
-            float tmina = pt_max(pt_max(pt_max(pt_min(t1a.x, t2a.x), pt_min(t1a.y, t2a.y)), pt_min(t1a.z, t2a.z)), 0.0f);
-            float tmaxa = pt_min(pt_min(pt_min(pt_max(t1a.x, t2a.x), pt_max(t1a.y, t2a.y)), pt_max(t1a.z, t2a.z)), rec.h.t);
-            float dist1 = tmina > tmaxa ? PT_FAR_PLANE : tmina;
-            v3 t1b = (mk3(c.x, c.y, c.z) - O) * rD, t2b = (mk3(e.x, e.y, e.z) - O) * rD;
-            float tminb = pt_max(pt_max(pt_max(pt_min(t1b.x, t2b.x), pt_min(t1b.y, t2b.y)), pt_min(t1b.z, t2b.z)), 0.0f);
-            float tmaxb = pt_min(pt_min(pt_min(pt_max(t1b.x, t2b.x), pt_max(t1b.y, t2b.y)), pt_max(t1b.z, t2b.z)), rec.h.t);
-            float dist2 = tminb > tmaxb ? PT_FAR_PLANE : tminb;
-            if (dist1 > dist2) {
-                float h = dist1; dist1 = dist2; dist2 = h;
-                uint32_t t = left; left = right; right = t;
-            }
-            if (dist1 == PT_FAR_PLANE) {
+        const TlasStep step = tlas_node_step(a, b, c, e, O, rD, rec.h.t);
+        if (!step.leaf) {
+            if (step.nothingHit) {
                 if (!tlas_stack_pop(stack, sp, nodeIndex)) break;
             } else {
-                nodeIndex = left;
-                if (dist2 != PT_FAR_PLANE) {
-                    if (sp < PT_BVH_STACK_SIZE) stack[sp] = right;
+                nodeIndex = step.near;
+                if (step.pushFar) {
+                    if (sp < PT_BVH_STACK_SIZE) stack[sp] = step.far;
                     else if (STATS) overflow = true;
                     sp++;
                 }
             }
         }
-        if (instanceCount > 0u) {
-            const uint32_t firstInstance = pt_asuint(e.w);
-            for (uint32_t i = 0; i < instanceCount; ++i) {
-                const uint32_t instanceIndex = pt_asuint(T[S.tlasIndexOffset + firstInstance + i]);
+        if (step.leaf) {
+            for (uint32_t i = 0; i < step.count; ++i) {
+                const uint32_t instanceIndex = pt_asuint(T[S.tlasIndexOffset + step.first + i]);
                 bool stopNow = false;
                 hitFound = traverse_instance<STATS>(S, O, dir, instanceIndex, isShadow, rec, st, cn, stopNow) | hitFound;
                 if (stopNow) {
@@ -1686,58 +1741,13 @@ PT_DEV void counters_to_array(const Counters& cn, uint32_t* vals)
 // ------------------------------------------------------------------------------------------
 // Resumable CWBVH traversal: the loop of traverse_cwbvh cut into steps, so that a wave can retire finished rays
 // and pull new ones into the idle lanes between steps (pt_wavefront.hip, refill trace kernel).  One call of
-// ray_step() is exactly one iteration of the reference's outer while(true) (util/bvh.hlsl:141-197):
-// [node step | adopt triangle group] -> all triangles of the group -> [pop | finish]; the per-ray operation order,
-// hence t/u/v/triIndex and the node/triangle counters, are those of traverse_cwbvh.
+// ray_step() is exactly one cwbvh_iteration of a flat scene; the per-ray operation order, hence t/u/v/triIndex and
+// the node/triangle counters, are those of traverse_cwbvh.
 // ------------------------------------------------------------------------------------------
-struct RayState {
-    v3 o, d, invDir;
-    uint32_t octinv4;
-    uint2 ng, tg;
-    uint32_t sp;
-    TraceHit hit;
-    bool anyHit, overflow;
-};
-
-// returns true when the ray is finished before it started (NaN ray: certain miss, see traverse_cwbvh)
-PT_DEV bool ray_begin(RayState& r, v3 o, v3 d, bool anyHit)
-{
-    r.o = o; r.d = d; r.anyHit = anyHit; r.overflow = false;
-    r.hit.t = PT_FAR_PLANE; r.hit.u = 0.0f; r.hit.v = 0.0f; r.hit.triIndex = 0u;
-    r.sp = 0u;
-    r.ng = make_uint2(0u, 0x80000000u);
-    r.tg = make_uint2(0u, 0u);
-    r.invDir = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-    r.octinv4 = (7u - ((d.x < 0.0f ? 4u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 1u : 0u))) * 0x1010101u;
-    return pt_isnan(o.x) || pt_isnan(o.y) || pt_isnan(o.z) || pt_isnan(d.x) || pt_isnan(d.y) || pt_isnan(d.z);
-}
-
-// one outer iteration; returns true when the traversal is complete
 template <bool STATS, class ST>
 PT_DEV bool ray_step(const DScene& S, RayState& r, ST& st, Counters& cn)
 {
-    if (r.ng.y > 0x00FFFFFFu) {
-        cwbvh_visit_node<STATS>(S.nodes, 0u, r.o, r.invDir, r.octinv4, r.hit.t, r.ng, r.tg, r.sp, r.overflow, st, cn);
-    } else {
-        r.tg = r.ng;
-        r.ng = make_uint2(0u, 0u);
-    }
-    while (r.tg.y != 0u) {
-        uint32_t triangleIndex = 31u - (uint32_t)__clz((int)r.tg.y);
-        uint32_t triAddr = r.tg.x + triangleIndex * 3u;
-        intersect_triangle(S.tris, triAddr, r.o, r.d, r.hit);
-        if (STATS) cn.triTests++;
-        r.tg.y -= 1u << triangleIndex;
-        if (r.anyHit && r.hit.t < PT_FAR_PLANE) { r.tg.y = 0u; r.ng.y = 0u; r.sp = 0u; }
-    }
-    if (r.ng.y <= 0x00FFFFFFu) {
-        if (r.sp > 0u) { --r.sp; r.ng = stack_pop(st, r.sp); }
-        else {
-            if (STATS && r.overflow) cn.overflows++;
-            return true;
-        }
-    }
-    return false;
+    return cwbvh_iteration<STATS, false>(S, r, BlasOffsets{}, st, cn);
 }
 
 // The traversal of ray_step in finer steps -- ONE triangle test, or (pop and) visit ONE node -- as separate phases, so that a wave
@@ -1748,7 +1758,7 @@ template <bool STATS>
 PT_DEV bool ray_tri_one(const DScene& S, RayState& r, Counters& cn)                 // precondition: r.tg.y != 0
 {
     const uint32_t triangleIndex = 31u - (uint32_t)__clz((int)r.tg.y);
-    intersect_triangle(S.tris, r.tg.x + triangleIndex * 3u, r.o, r.d, r.hit);
+    intersect_triangle<false>(S.tris, r.tg.x + triangleIndex * 3u, 0u, r.o, r.d, r.hit);
     if (STATS) cn.triTests++;
     r.tg.y -= 1u << triangleIndex;
     if (r.anyHit && r.hit.t < PT_FAR_PLANE) {

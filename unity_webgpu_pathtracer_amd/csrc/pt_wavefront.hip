@@ -334,6 +334,7 @@ PT_DEV bool start_ray(const PTWfBuffers& B, uint32_t slot, uint32_t kind, RaySta
     v3 o, d;
     fetch_ray(B, slot, kind, o, d);
     if (kind == 0u) cn.closestRays++; else cn.shadowRays++;
+    rs.hit = TraceHit{PT_FAR_PLANE, 0.0f, 0.0f, 0u};
     if (!ray_begin(rs, o, d, kind != 0u)) return true;
     store_result(B, slot, kind, false, rs.hit, true);
     return false;
@@ -426,7 +427,7 @@ PT_DEV uint32_t resume_ray(const PTWfBuffers& B, const uint4* p, uint32_t slotBa
     rs.overflow = (a.y & 0x100u) != 0u;
     rs.ng = make_uint2(a.z, a.w);
     rs.tg = make_uint2(b.x, b.y);
-    rs.hit.t = pt_asfloat(b.z);
+    rs.hit = TraceHit{pt_asfloat(b.z), 0.0f, 0.0f, 0u};
 #pragma unroll
     for (uint32_t e = 0; e < PT_WF_SUSP_STACK_ROWS; ++e) {
         st.lds[(2u * e) * st.stride] = pt_u2{er[e].x, er[e].y};
@@ -552,13 +553,13 @@ __global__ __launch_bounds__(64, PT_WF_TRACE_MIN_WAVES) void pt_wf_trace_refill(
 }
 
 // ------------------------------------------------------------------------------------------
-// HAS_TLAS through the refill scheduler (util/tlas.hlsl:129-332).  The two-level walk of a ray is cut so that the hot loop of
-// the wave contains ONE kind of step, the CWBVH iteration of the instance a lane is inside (ray_step with the instance's
-// node / triangle / attribute offsets and the tmin = 0 triangle test); whenever a lane's instance is finished it runs the
-// instance epilogue (world-space position and distance, tlas.hlsl:208-229) and walks the 2-wide TLAS -- a short, rarely taken
-// loop -- to the next instance whose box it hits.  Per lane: the BLAS stack in LDS (8 entries, deeper ones in the HBM slab) plus
-// a second, narrow LDS stack for TLAS node indices; the world-space ray is re-read from the slot arrays when an instance is
-// entered.  Same per-ray operation order as traverse_tlas, so frames and all counters stay bit-identical.
+// HAS_TLAS through the refill scheduler: traverse_tlas (pt_device.h) cut so that the hot loop of the wave contains ONE kind
+// of step, the cwbvh_iteration<INST> of the instance a lane is inside.  Whenever a lane's instance is finished it runs
+// instance_exit and walks the 2-wide TLAS -- tlas_node_step, a short, rarely taken loop -- to the next instance whose box it
+// hits, which it enters with instance_enter.  The arithmetic and the decisions are those shared functions; what this kernel owns
+// is where things live.  Per lane: the BLAS stack in LDS (8 entries, deeper ones in the HBM slab) plus a second, narrow LDS
+// stack for TLAS node indices; the world-space ray is re-read from the slot arrays when an instance is entered.  Same per-ray
+// operation order as traverse_tlas, so frames and all counters stay bit-identical.
 // ------------------------------------------------------------------------------------------
 #ifndef PT_WF_TLAS_LDS_STACK
 #define PT_WF_TLAS_LDS_STACK 8u
@@ -624,14 +625,15 @@ __global__ __launch_bounds__(64 * WAVES, PT_WF_TLAS_MIN_WAVES) void pt_wf_trace_
     st.gbase = B.stackSpill;
     st.gwave = PT_LDS_WORD(s_gw[wv]);
     RayState rs;
-    rs.sp = 0u; rs.anyHit = false; rs.overflow = false;
-    bool have = false, inBlas = false, needPop = false, hitFound = false;
+    rs.sp = 0u; rs.anyHit = false; rs.overflow = false; rs.hitFound = false;
+    bool have = false, inBlas = false, needPop = false;
     bool toverflow = false;                                                   // STATS: the ray's TLAS walk dropped an entry
     uint32_t mySlot = 0u, myKind = 0u, cursor = kCached ? nItems : 0u;       // WAVES > 1: no chunk yet
     bool more = kCached;                                                      // chunks may remain (WAVES > 1)
     v3 O = mk3(0.0f), rD = mk3(0.0f);
     uint32_t nodeIndex = 0u, tsp = 0u, nextInst = 0u, instLeft = 0u;
-    uint32_t nodeOffset = 0u, triOffset = 0u, attrOffset = 0u, instIndex = 0u;
+    BlasOffsets off = {0u, 0u, 0u};
+    uint32_t instIndex = 0u;
 
     // The empty asm statements keep the LDS access and the HBM-slab access of an entry in their own branches.  Without them the
     // compiler sinks the two into ONE access through a selected pointer -- a FLAT load / store (round 2's kernel had two of each in
@@ -680,8 +682,8 @@ __global__ __launch_bounds__(64 * WAVES, PT_WF_TLAS_MIN_WAVES) void pt_wf_trace_
                 v3 d;
                 fetch_ray(B, mySlot, myKind, O, d);
                 if (myKind == 0u) cn.closestRays++; else cn.shadowRays++;
-                if (pt_isnan(O.x) || pt_isnan(O.y) || pt_isnan(O.z) || pt_isnan(d.x) || pt_isnan(d.y) || pt_isnan(d.z)) {
-                    store_result(B, mySlot, myKind, false, rs.hit, true);     // NaN ray: certain miss (traverse_tlas)
+                if (ray_has_nan(O, d)) {
+                    store_result(B, mySlot, myKind, false, rs.hit, true);     // a certain miss
                 } else {
                     const v3 D = normalize3(d);                           // tlas.hlsl:238-240
                     rD = mk3(1.0f / D.x, 1.0f / D.y, 1.0f / D.z);
@@ -709,7 +711,7 @@ __global__ __launch_bounds__(64 * WAVES, PT_WF_TLAS_MIN_WAVES) void pt_wf_trace_
             //      itself: 19 TLAS steps per ray at a quarter of the lanes.
             //      The walk loop only visits TLAS nodes: lanes that reached a leaf (or still have instances of their leaf left) enter
             //      their instance together in ONE block after it.
-            // enter the next instance of the current TLAS leaf (tlas.hlsl:129-147)
+            // enter the next instance of the current TLAS leaf
             // ONE fetch: the record PTSetScene laid out per TLAS index slot (worldToLocal, offsets, instance index) instead of
             // TLASData[TLASIndexOffset + k] -> instance record (two dependent fetches; same values)
             auto enter_instance = [&]() {
@@ -718,14 +720,9 @@ __global__ __launch_bounds__(64 * WAVES, PT_WF_TLAS_MIN_WAVES) void pt_wf_trace_
                 instIndex = pt_asuint(ip[5].x);
                 nextInst++; instLeft--;
                 if (STATS) cn.instanceVisits++;
-                nodeOffset = pt_asuint(ints.x); triOffset = pt_asuint(ints.y); attrOffset = pt_asuint(ints.z);
+                off = BlasOffsets{pt_asuint(ints.x), pt_asuint(ints.y), pt_asuint(ints.z)};
                 const v3 wd = xyz(f4_array(B, 2u * myKind)[2u * (size_t)mySlot + 1u]);           // the direction row of the lane's ray record
-                const v4 lo4 = mul44c(w0, w1, w2, w3, v4{O.x, O.y, O.z, 1.0f});
-                const v4 ld4 = mul44c(w0, w1, w2, w3, v4{wd.x, wd.y, wd.z, 0.0f});
-                const float tKeep = rs.hit.t;
-                ray_begin(rs, mk3(lo4.x, lo4.y, lo4.z), mk3(ld4.x, ld4.y, ld4.z), myKind != 0u);
-                rs.hit.t = tKeep;
-                hitFound = false;
+                instance_enter(rs, w0, w1, w2, w3, O, wd, myKind != 0u);
                 inBlas = true;
             };
             if (have && !inBlas && instLeft == 0u) {
@@ -738,7 +735,7 @@ __global__ __launch_bounds__(64 * WAVES, PT_WF_TLAS_MIN_WAVES) void pt_wf_trace_
                         if (!tpop()) { finished = true; break; }
                         needPop = false;
                     }
-                    // visit TLAS node nodeIndex (tlas.hlsl:246-331)
+                    // visit TLAS node nodeIndex
                     float4 a, b, c, e;
                     if (kCached && nodeIndex < cachedNodes) {
                         const float4* cp = &s_tcache[nodeIndex * 4u];
@@ -752,29 +749,16 @@ __global__ __launch_bounds__(64 * WAVES, PT_WF_TLAS_MIN_WAVES) void pt_wf_trace_
                         asm volatile("" : "+v"(a.x), "+v"(b.x), "+v"(c.x), "+v"(c.w), "+v"(e.x), "+v"(e.w));
                     }
                     if (STATS) cn.tlasNodeVisits++;
-                    const uint32_t instanceCount = pt_asuint(c.w);
-                    if (instanceCount == 0u) {
-                        uint32_t left = pt_asuint(a.w), right = pt_asuint(b.w);
-                        const v3 t1a = (mk3(a.x, a.y, a.z) - O) * rD, t2a = (mk3(b.x, b.y, b.z) - O) * rD;
-                        const float tmina = pt_max(pt_max(pt_max(pt_min(t1a.x, t2a.x), pt_min(t1a.y, t2a.y)), pt_min(t1a.z, t2a.z)), 0.0f);
-                        const float tmaxa = pt_min(pt_min(pt_min(pt_max(t1a.x, t2a.x), pt_max(t1a.y, t2a.y)), pt_max(t1a.z, t2a.z)), rs.hit.t);
-                        float dist1 = tmina > tmaxa ? PT_FAR_PLANE : tmina;
-                        const v3 t1b = (mk3(c.x, c.y, c.z) - O) * rD, t2b = (mk3(e.x, e.y, e.z) - O) * rD;
-                        const float tminb = pt_max(pt_max(pt_max(pt_min(t1b.x, t2b.x), pt_min(t1b.y, t2b.y)), pt_min(t1b.z, t2b.z)), 0.0f);
-                        const float tmaxb = pt_min(pt_min(pt_min(pt_max(t1b.x, t2b.x), pt_max(t1b.y, t2b.y)), pt_max(t1b.z, t2b.z)), rs.hit.t);
-                        float dist2 = tminb > tmaxb ? PT_FAR_PLANE : tminb;
-                        if (dist1 > dist2) {
-                            const float h = dist1; dist1 = dist2; dist2 = h;
-                            const uint32_t t = left; left = right; right = t;
-                        }
-                        if (dist1 == PT_FAR_PLANE) needPop = true;
+                    const TlasStep step = tlas_node_step(a, b, c, e, O, rD, rs.hit.t);
+                    if (!step.leaf) {
+                        if (step.nothingHit) needPop = true;
                         else {
-                            nodeIndex = left;
-                            if (dist2 != PT_FAR_PLANE) tpush(right);
+                            nodeIndex = step.near;
+                            if (step.pushFar) tpush(step.far);
                         }
                     } else {
-                        nextInst = pt_asuint(e.w);
-                        instLeft = instanceCount;
+                        nextInst = step.first;
+                        instLeft = step.count;
                         needPop = true;                                    // after the leaf's instances
                         break;                                             // to the entry block below
                     }
@@ -790,47 +774,20 @@ __global__ __launch_bounds__(64 * WAVES, PT_WF_TLAS_MIN_WAVES) void pt_wf_trace_
             // ---- the hot step: one CWBVH iteration inside the current instance
             if (have && inBlas) {
                 const float tBefore = rs.hit.t;
-                bool blasDone = false;
-                {
-                    // ray_step with instance offsets and the HAS_TLAS triangle test (tlas.hlsl:149-206)
-                    if (rs.ng.y > 0x00FFFFFFu) {
-                        cwbvh_visit_node<STATS>(S.nodes, nodeOffset, rs.o, rs.invDir, rs.octinv4, rs.hit.t, rs.ng, rs.tg, rs.sp, rs.overflow, st, cn);
-                    } else {
-                        rs.tg = rs.ng;
-                        rs.ng = make_uint2(0u, 0u);
-                    }
-                    while (rs.tg.y != 0u) {
-                        const uint32_t triangleIndex = 31u - (uint32_t)__clz((int)rs.tg.y);
-                        const uint32_t triAddr = rs.tg.x + triangleIndex * 3u;
-                        hitFound = intersect_triangle_inst(S.tris, triOffset + triAddr, attrOffset, rs.o, rs.d, rs.hit) | hitFound;
-                        if (STATS) cn.triTests++;
-                        rs.tg.y -= 1u << triangleIndex;
-                        if (rs.anyHit && hitFound) { rs.tg.y = 0u; rs.ng.y = 0u; rs.sp = 0u; }
-                    }
-                    if (rs.ng.y <= 0x00FFFFFFu) {
-                        if (rs.sp > 0u) { --rs.sp; rs.ng = stack_pop(st, rs.sp); }
-                        else blasDone = true;
-                    }
-                }
+                const bool blasDone = cwbvh_iteration<STATS, true>(S, rs, off, st, cn);
                 if (myKind == 0u && rs.hit.t < tBefore) f4_array(B, PT_F4_HIT)[mySlot] = make_float4(rs.hit.t, rs.hit.u, rs.hit.v, pt_asfloat(rs.hit.triIndex));
                 if (blasDone) {
-                    if (STATS && rs.overflow) cn.overflows++;
                     inBlas = false;
                     if (rs.anyHit) {
-                        if (hitFound) {                                                                  // stopNow (tlas.hlsl:196-200)
+                        if (rs.hitFound) {                                                               // stopNow (tlas.hlsl:196-200)
                             store_result(B, mySlot, myKind, true, rs.hit, true);
                             if (STATS && toverflow) cn.overflows++;
                             have = false;
                         }
-                    } else if (hitFound) {
-                        // tlas.hlsl:208-229: world-space hit position and distance of the instance that improved the hit
-                        if (STATS) cn.attrFetches++;
+                    } else if (rs.hitFound) {
+                        // world-space hit position and distance of the instance that improved the hit
                         const float4* ip = S.instances + (size_t)instIndex * 9;
-                        const float4 l0 = ip[0], l1 = ip[1], l2 = ip[2], l3 = ip[3];
-                        const v3 lp = rs.o + rs.hit.t * rs.d;
-                        const v4 wp = mul44c(l0, l1, l2, l3, v4{lp.x, lp.y, lp.z, 1.0f});
-                        const v3 pos = mk3(wp.x, wp.y, wp.z);
-                        rs.hit.t = length3(pos - O);
+                        const v3 pos = instance_exit<STATS>(rs, ip[0], ip[1], ip[2], ip[3], O, cn);
                         ((float*)&f4_array(B, PT_F4_HIT)[mySlot])[0] = rs.hit.t;
                         f4_array(B, PT_F4_HIT2)[mySlot] = make_float4(pos.x, pos.y, pos.z, pt_asfloat(instIndex));
                     }
