@@ -67,6 +67,14 @@ PT_API const char* PTGetBVHBuildError(void);
 /* Build time of a handle in milliseconds: host wall time of BuildBVH, device time (kernels only) of PTBuildBVHDevice. */
 PT_API double PTGetBVHBuildMs(int index);
 
+/* Refit (Part 9 has the rule): the handle of BuildBVH / PTBuildBVHDevice keeps its topology and takes the boxes and triangle
+ * records of `vertices` (3 * triangleCount, the primitive order it was built from); GetCWBVHData then returns the refitted
+ * arrays.  Host only, no GPU.  Returns 1, or 0 with PTGetBVHBuildError() set for a bad handle, a count mismatch or a
+ * non-finite vertex.  PTRefitBVHArrays does the same in place on arrays the host copied out of a handle (nodeBytes = nodes *
+ * 80, triBytes = triangleCount * 48); arrays that are no CWBVH of triangleCount triangles are refused, never followed. */
+PT_API int   PTRefitBVH(int index, const PTFloat4* vertices, int triangleCount);
+PT_API int   PTRefitBVHArrays(PTFloat4* bvhNodes, uint64_t nodeBytes, PTFloat4* bvhTris, uint64_t triBytes, const PTFloat4* vertices, int triangleCount);
+
 /* plugin.cpp:111-118.  2-wide SAH BVH over the instances' world AABBs, Aila-Laine layout. */
 PT_API int   BuildTLAS(const PTBlasInstance* instances, int instanceCount);
 PT_API void  DestroyTLAS(int index);                                     /* plugin.cpp:120-130 */
@@ -755,6 +763,48 @@ PT_API int PTCameraRays(PTContext* ctx, const PTFrameParams* params, const uint3
 PT_API int PTTraceRadiance(PTContext* ctx, const PTFrameParams* params, const PTRadianceRay* dRays, uint64_t count, PTRadiance* dOut);
 /* Host arrays: staged through device buffers the context keeps and grows; synchronous. */
 PT_API int PTTraceRadianceHost(PTContext* ctx, const PTFrameParams* params, const PTRadianceRay* rays, uint64_t count, PTRadiance* out);
+
+/* =====================================================================================================================
+ * Part 9: geometry updates.  New vertex positions for one BLAS of the scene PTSetScene uploaded (skinning, cloth, a morph),
+ * without rebuilding or setting the scene again: the CWBVH is REFITTED on the GPU.
+ *
+ * The rule.  A refit keeps the topology: row n1 of every node (childBaseIndex, triBaseIndex, meta[8]), imask, the order of
+ * the triangle records and their primIdx, all counts.  It rewrites every triangle record (e2 = v[3p+2] - v[3p], e1 = v[3p+1] -
+ * v[3p], v0 = v[3p] for p = primIdx; the bytes BuildBVH writes) and every node's lo, exponents and 48 quantised bytes.  A leaf
+ * slot's box is the box of the original vertices of its popcount(meta >> 5) records from record (meta & 31) of triBaseIndex; an
+ * inner slot's box is the refitted box of that child; a node's box is the fold over its occupied slots in ascending order,
+ * all with compare-and-select (b < acc ? b : acc).  The encode is PTBuildBVHDevice's: per axis the smallest e in -120 ... 126
+ * with 255 * 2^e >= extent, q_lo = clamp(floor((c.mn - lo) / 2^e)), q_hi = clamp(ceil((c.mx - lo) / 2^e)) into 0 ... 255, empty
+ * slots 0.  Every step is exact or correctly rounded: PTReadGeometry after an update equals PTRefitBVH of the same tree and
+ * vertices byte for byte, and frames, queries and guides equal those of a fresh PTSetScene of the refitted arrays.  The tree's
+ * quality is the caller's to watch: a refit of a strongly deformed mesh traverses more nodes than a rebuild.
+ *
+ * The BLAS is named by the three offsets of its PTGpuInstance records: bvhOffset (nodes), triOffset (float4s),
+ * triAttributeOffset (triangles); 0, 0, 0 for a scene without HAS_TLAS.  vertices: 3 * triangleCount PTFloat4 in the BLAS's
+ * primitive order (BuildBVH's input order), w ignored.  attrs: NULL keeps the attribute records, otherwise triangleCount
+ * records replace the BLAS's (new normals and tangents).  The host variant copies both arrays before it returns and refuses
+ * non-finite vertices and, without HAS_TLAS, a materialIndex >= materialCount.  The device variant reads them in the context
+ * stream's order and does not look at the vertices: non-finite ones give an unspecified tree that is still memory-safe, since
+ * no index is rewritten; a device record whose materialIndex is out of range keeps the index it had.
+ * HAS_TLAS: the library does not touch the TLAS.  The world bounds of the instances of a deformed BLAS are the caller's to
+ * resend through PTUpdateInstances -- the caller has the vertices.
+ * The first update of a scene reads the node and triangle buffers back once (synchronising) and the first update of a BLAS
+ * walks it as PTSetScene's validation does; PTSetScene itself does nothing for this part.
+ * Ordering, accumulation, memory and lifetime are Part 5's: work enqueued before the call sees the old geometry, work enqueued
+ * after it the new; two generations of nodes + triangles (and of the attributes, once they are given), allocated on the first
+ * update, the current one copied into the other by every update; PTSetScene discards the state, PTDestroy frees it.
+ * Instances may share a BLAS only whole (the same three offsets): a BLAS whose root or first record lies inside another one's
+ * is refused; BLASes that overlap in any other way are the caller's to avoid -- a refit of one changes the other.
+ * Errors: PT_ERR_NO_SCENE before PTSetScene; PT_ERR_INVALID_ARG for a NULL context or array, offsets that name no BLAS, a
+ * triangleCount that is not the BLAS's, a refused array.
+ * PTReadGeometry: the current node, triangle and (dstAttrs != NULL) attribute buffers of the whole scene, in PTSetScene's
+ * layout and sizes.  Synchronising.  Before any geometry update it returns what PTSetScene was given.
+ * ===================================================================================================================== */
+PT_API int PTUpdateGeometry(PTContext* ctx, int32_t bvhOffset, int32_t triOffset, int32_t triAttributeOffset, const PTFloat4* vertices,
+                            int triangleCount, const PTTriangleAttributes* attrsOrNull);                  /* host arrays, copied before return */
+PT_API int PTUpdateGeometryDevice(PTContext* ctx, int32_t bvhOffset, int32_t triOffset, int32_t triAttributeOffset, const PTFloat4* dVertices,
+                                  int triangleCount, const PTTriangleAttributes* dAttrsOrNull);           /* device arrays, read in stream order */
+PT_API int PTReadGeometry(PTContext* ctx, void* dstNodes, uint64_t nodeBytes, void* dstTris, uint64_t triBytes, void* dstAttrs, uint64_t attrBytes);
 
 /* Text of the last error on the calling thread ("" if none). */
 PT_API const char* PTGetLastError(void);

@@ -10,6 +10,7 @@
 #include <deque>
 #include <string>
 #include "bvh_builder.h"
+#include "bvh_refit.h"
 #include "ptmi_plugin.h"
 
 namespace {
@@ -61,6 +62,27 @@ PT_API double PTGetBVHBuildMs(int index)
 {
     ptbvh::Cwbvh* b = get_slot(g_bvhs, index);
     return b ? b->buildMs : -1.0;
+}
+// Refit in place (bvh_refit.cpp): the handle keeps its topology, GetCWBVHData returns the refitted arrays.  No GPU involved.
+PT_API int PTRefitBVH(int index, const PTFloat4* vertices, int triangleCount)
+{
+    ptbvh::Cwbvh* b = get_slot(g_bvhs, index);
+    if (!b) { g_buildError = "no such BVH handle"; return 0; }
+    if (!vertices || triangleCount <= 0 || (uint32_t)triangleCount != b->triCount) { g_buildError = "vertices == NULL or triangleCount is not the handle's"; return 0; }
+    if (!ptbvh::refit_cwbvh(b->nodeData.data(), b->usedBlocks / 5u, b->triData.data(), (uint64_t)b->triCount * 3u, 0, 0, vertices, b->triCount, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+// The same on arrays the host copied out of a handle (the reference's host destroys the handle right after the copy)
+PT_API int PTRefitBVHArrays(PTFloat4* bvhNodes, uint64_t nodeBytes, PTFloat4* bvhTris, uint64_t triBytes, const PTFloat4* vertices, int triangleCount)
+{
+    if (!bvhNodes || !bvhTris || !vertices || triangleCount <= 0 || nodeBytes < 80 || nodeBytes % 80 || triBytes != (uint64_t)triangleCount * 48u) {
+        g_buildError = "NULL array, nodeBytes not a multiple of 80 or triBytes != triangleCount * 48";
+        return 0;
+    }
+    if (!ptbvh::refit_cwbvh(bvhNodes, nodeBytes / 80u, bvhTris, triBytes / 16u, 0, 0, vertices, (uint32_t)triangleCount, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
 }
 PT_API void DestroyBVH(int index) { free_slot(g_bvhs, index); }
 PT_API int IsBVHReady(int index) { return get_slot(g_bvhs, index) != nullptr; }

@@ -202,7 +202,8 @@ void discard_updates(PTContext* c)
 {
     PTContext::Update& u = c->update;
     if (u.stream) hipStreamSynchronize(u.stream);
-    for (PTContext::UpdGroup* g : {&u.inst, &u.lights, &u.mats}) *g = PTContext::UpdGroup();
+    for (PTContext::UpdGroup* g : {&u.inst, &u.lights, &u.mats, &u.geom, &u.attrs}) *g = PTContext::UpdGroup();
+    u.geometry = PTContext::Geometry();
     u.tlasWork.release();
     u.tlasW = {};
     u.pending = false;

@@ -22,6 +22,8 @@ InstGen inst_gen(void* base, uint32_t n)
     return g;
 }
 
+} // namespace
+
 // Opens an update of group g.  The update stream and both generations exist afterwards: their sizes depend on the scene alone and
 // PTSetScene discards the groups, so after a group's first update nothing is reallocated.  The generation an update writes is
 // not the current one; the update stream first waits until every piece of work that read it (enqueued before it stopped
@@ -66,6 +68,8 @@ int end_update(PTContext* c, PTContext::UpdGroup& g, int target)
     c->update.pending = true;
     return PT_OK;
 }
+
+namespace {
 
 bool finite_record(const PTBlasInstance& r)
 {

@@ -3,6 +3,8 @@
 #pragma once
 #include "pt_launch.h"
 #include "pt_tlas.h"
+#include "pt_refit.h"
+#include "bvh_refit.h"
 
 #include <cstring>
 #include <initializer_list>
@@ -226,8 +228,24 @@ struct PTContext {
         Event stagedEv[2];
         bool stagedRecorded[2] = {false, false};
     };
+    // geometry updates (PTUpdateGeometry): what the first one reads back and every later one reuses -- the topology never changes
+    struct GeomPlan {
+        int32_t key[3] = {0, 0, 0};                     // bvhOffset, triOffset, triAttributeOffset
+        uint32_t triCount = 0;
+        DeviceBuffer order;                             // ptbvh::RefitPlan::order on the device
+        std::vector<uint32_t> levelStart;
+    };
+    struct Geometry {
+        std::vector<PTFloat4> hostNodes;                // host copy of the node buffer (rows n1 and imask are what is read)
+        std::vector<uint32_t> hostTriW;                 // the .w word of every triangle row (primIdx in every third)
+        std::vector<int32_t> blasKeys;                  // HAS_TLAS: the three offsets of every instance (PTSetScene's records)
+        std::vector<GeomPlan> plans;                    // one per BLAS updated so far
+        DeviceBuffer nodeBox;                           // 24 B per node of the scene
+        DeviceBuffer verts;                             // the host variant's vertices on the device
+    };
     struct Update {
-        UpdGroup inst, lights, mats;
+        UpdGroup inst, lights, mats, geom, attrs;
+        Geometry geometry;
         Stream stream;
         Event done;                                     // the last update's completion
         Event input;                                    // PTUpdateInstancesDevice: the context stream up to the call
@@ -293,6 +311,11 @@ constexpr int kTextureSlots[4] = {22, 23, 25, 26};
 
 // pt_api_denoise.hip: PTDenoise's body; variance != nullptr is PTDenoiseMoments (dSrc then is never NULL)
 int denoise_frame(PTContext* c, const PTDenoiseParams* params, const void* dSrc, void* dDst, const PTDenoiseVariance* variance);
+// pt_api_update.hip: the three steps of every update of a group (begin: the target generation, free to write on the update
+// stream; stage: a host array through the target's pinned staging; end: the target becomes current)
+int begin_update(PTContext* c, PTContext::UpdGroup& g, size_t genBytes, size_t stagingBytes, int& target);
+int stage_host(PTContext* c, PTContext::UpdGroup& g, int target, const void* src, size_t bytes, void* dst);
+int end_update(PTContext* c, PTContext::UpdGroup& g, int target);
 int set_scene(PTContext* c, const PTSceneDesc* hostScene, bool validate);      // pt_api_context.hip; PTGroupSetScene validates once
 int drain_events(PTContext* c);                                                 // pt_api_context.hip
 int ensure_frames(PTContext* c, uint32_t w, uint32_t h);                        // pt_api_render.hip

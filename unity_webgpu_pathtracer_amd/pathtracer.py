@@ -728,6 +728,71 @@ class PathTracer:
         plugin.check(self.lib.PTReadTLAS(self.ctx, nodes.ctypes.data, nodes.nbytes, idx.ctypes.data, n, C.byref(count)))
         return nodes[:count.value * 64].copy(), idx
 
+    # ---- geometry updates (include/ptmi_plugin.h Part 9)
+    def update_geometry(self, vertices, mesh: int = None, tri_attrs=None):
+        """PTUpdateGeometry: new positions for one BLAS, refitted in place on the GPU.  vertices: (3 * triangles, 4) float32 in
+        the BLAS's primitive order (numpy), or a torch tensor on this context's device (PTUpdateGeometryDevice, ordered after
+        torch's current stream; tri_attrs then is a device tensor too).  tri_attrs (optional): the BLAS's abi.TRI_ATTR records.
+        Flat scene: mesh stays None.  HAS_TLAS scene: mesh indexes scene.mesh_ranges; the vertices are in the mesh's local space,
+        and the world bounds of the mesh's instances are recomputed (scenes.instance_world_bounds) and sent through
+        PTUpdateInstances -- the library does not touch the TLAS (with device tensors that is left to the caller).  Does not
+        reset accumulation."""
+        bvh = self._bvhScene
+        off = (0, 0, 0)
+        if bvh.gpu_instances is not None:
+            assert mesh is not None, "a HAS_TLAS scene needs the mesh index"
+            users = [i for i, inst in enumerate(self.scene.instances) if inst[0] == mesh]
+            if not users:
+                raise ValueError(f"mesh {mesh} has no instance in the scene: its BLAS cannot be named")
+            k = users[0]
+            off = tuple(int(bvh.gpu_instances[k][f]) for f in ("bvhOffset", "triOffset", "triAttributeOffset"))
+        if isinstance(vertices, np.ndarray):
+            v = np.ascontiguousarray(vertices, dtype=np.float32)
+            assert v.ndim == 2 and v.shape[1] == 4 and v.shape[0] % 3 == 0
+            a = None if tri_attrs is None else np.ascontiguousarray(tri_attrs)
+            assert a is None or a.nbytes == v.shape[0] // 3 * 128
+            plugin.check(self.lib.PTUpdateGeometry(self.ctx, *off, v.ctypes.data, v.shape[0] // 3, None if a is None else a.ctypes.data))
+        else:
+            import torch
+            assert vertices.is_contiguous() and vertices.dtype == torch.float32 and vertices.numel() % 12 == 0
+            assert tri_attrs is None or (tri_attrs.is_contiguous() and tri_attrs.numel() * tri_attrs.element_size() == vertices.numel() // 12 * 128)
+            cur = torch.cuda.current_stream(vertices.device)
+            ext = torch.cuda.ExternalStream(self.stream(), device=vertices.device)
+            ext.wait_stream(cur)
+            plugin.check(self.lib.PTUpdateGeometryDevice(self.ctx, *off, vertices.data_ptr(), vertices.numel() // 12,
+                                                         None if tri_attrs is None else tri_attrs.data_ptr()))
+            cur.wait_stream(ext)
+            if bvh.gpu_instances is not None:
+                import warnings
+                warnings.warn("update_geometry with device tensors on a HAS_TLAS scene: resend the instances' world bounds "
+                              "(PTUpdateInstances / update_instances_device), the vertices are not read back for them")
+            v = None
+        if v is None:
+            return
+        # later transform updates take the mesh's bounds from the scene's vertices: kept current in a copy of our own, made once
+        if not getattr(self, "_ownVertices", False):
+            from dataclasses import replace
+            self.scene = bvh.scene = replace(self.scene, vertices=self.scene.vertices.copy())
+            self._ownVertices = True
+        t0 = 0 if mesh is None else self.scene.mesh_ranges[mesh][0]
+        self.scene.vertices[t0 * 3:t0 * 3 + v.shape[0]] = v
+        if bvh.gpu_instances is not None:
+            from .scenes import instance_world_bounds
+            for k, (m, _, _) in enumerate(self.scene.instances):
+                if m != mesh:
+                    continue
+                l2w = bvh.gpu_instances[k]["localToWorld"].reshape(4, 4).T.astype(np.float64)
+                bvh.blas_instances[k]["aabbMin"], bvh.blas_instances[k]["aabbMax"] = instance_world_bounds(v, l2w)
+            plugin.check(self.lib.PTUpdateInstances(self.ctx, bvh.blas_instances.ctypes.data, bvh.blas_instances.shape[0]))
+
+    def read_geometry(self):
+        """PTReadGeometry: the current (nodes uint8[], tris uint8[], tri_attrs abi.TRI_ATTR[]) of the whole scene.  Synchronising."""
+        bvh = self._bvhScene
+        nodes, tris = np.empty(bvh.bvh_nodes.nbytes, np.uint8), np.empty(bvh.bvh_tris.nbytes, np.uint8)
+        attrs = np.empty(bvh.tri_attrs.shape, bvh.tri_attrs.dtype)
+        plugin.check(self.lib.PTReadGeometry(self.ctx, nodes.ctypes.data, nodes.nbytes, tris.ctypes.data, tris.nbytes, attrs.ctypes.data, attrs.nbytes))
+        return nodes, tris, attrs
+
     def close(self):
         if self.ctx:
             self.lib.PTDestroy(self.ctx)

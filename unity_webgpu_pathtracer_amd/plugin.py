@@ -28,6 +28,7 @@ sig = {
     "GetCWBVHNodesSize": (i32, [i32]), "GetCWBVHTrisSize": (i32, [i32]),
     "GetCWBVHData": (i32, [i32, C.POINTER(vp), C.POINTER(vp)]),
     "PTBuildBVHDevice": (i32, [i32, vp, i32]), "PTGetBVHBuildError": (C.c_char_p, []), "PTGetBVHBuildMs": (C.c_double, [i32]),
+    "PTRefitBVH": (i32, [i32, vp, i32]), "PTRefitBVHArrays": (i32, [vp, C.c_uint64, vp, C.c_uint64, vp, i32]),
     "BuildTLAS": (i32, [vp, i32]), "DestroyTLAS": (None, [i32]), "IsTLASReady": (i32, [i32]),
     "GetTLASNodesSize": (i32, [i32]), "GetTLASData": (i32, [i32, C.POINTER(vp), C.POINTER(vp)]),
     # Part 2 (render)
@@ -92,6 +93,10 @@ sig = {
     "PTCameraRays": (i32, [vp, C.POINTER(abi.PTFrameParams), vp, C.c_uint64, vp]),
     "PTTraceRadiance": (i32, [vp, C.POINTER(abi.PTFrameParams), vp, C.c_uint64, vp]),
     "PTTraceRadianceHost": (i32, [vp, C.POINTER(abi.PTFrameParams), vp, C.c_uint64, vp]),
+    # Part 9 (geometry updates)
+    "PTUpdateGeometry": (i32, [vp, C.c_int32, C.c_int32, C.c_int32, vp, i32, vp]),
+    "PTUpdateGeometryDevice": (i32, [vp, C.c_int32, C.c_int32, C.c_int32, vp, i32, vp]),
+    "PTReadGeometry": (i32, [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64]),
     "PTGetLastError": (C.c_char_p, []), "PTGetVersion": (i32, []),
 }
 EXPORTED_SYMBOLS = list(sig)
@@ -248,6 +253,24 @@ def build_cwbvh(vertices: np.ndarray, device: int = None, timing: dict = None):
         tris = np.ctypeslib.as_array(C.cast(pt, C.POINTER(C.c_uint8)), shape=(tb,)).copy()
     finally:
         TinyBVH.DestroyBVH(h)
+    return nodes, tris
+
+
+def refit_cwbvh(handle_or_arrays, vertices: np.ndarray):
+    """CWBVH refit on the host (include/ptmi_plugin.h Part 1): same topology, boxes and triangle records of `vertices`
+    ((3 * triangles, 4) float32 in the primitive order the tree was built from).
+    handle (int): PTRefitBVH refits the handle in place (GetCWBVHData then returns the refitted arrays); returns None.
+    (nodes uint8[], tris uint8[]) as build_cwbvh returns them: PTRefitBVHArrays on copies; returns the refitted (nodes, tris)."""
+    v = np.ascontiguousarray(vertices, dtype=np.float32)
+    assert v.ndim == 2 and v.shape[1] == 4 and v.shape[0] % 3 == 0
+    lib = load_library()
+    if isinstance(handle_or_arrays, (int, np.integer)):
+        if not lib.PTRefitBVH(int(handle_or_arrays), v.ctypes.data, v.shape[0] // 3):
+            raise PluginError(abi.PT_ERR_INVALID_ARG, "PTRefitBVH failed: " + lib.PTGetBVHBuildError().decode())
+        return None
+    nodes, tris = (np.array(a, dtype=np.uint8, copy=True).reshape(-1) for a in handle_or_arrays)
+    if not lib.PTRefitBVHArrays(nodes.ctypes.data, nodes.nbytes, tris.ctypes.data, tris.nbytes, v.ctypes.data, v.shape[0] // 3):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTRefitBVHArrays failed: " + lib.PTGetBVHBuildError().decode())
     return nodes, tris
 
 
