@@ -61,7 +61,9 @@ PT_API int   GetCWBVHData(int index, PTFloat4** bvhNodes, PTFloat4** bvhTris);
  * sort, Karras radix tree), greedy surface-area collapse to 8-wide, CWBVH encode, all in HIP kernels.  The tree differs from
  * BuildBVH's binned-SAH tree (so the bytes differ), every ray finds the same closest hit.  The handle lives in BuildBVH's
  * table: GetCWBVHNodesSize / GetCWBVHTrisSize / GetCWBVHData / IsBVHReady / DestroyBVH apply.  Returns -1 on degenerate input
- * or when deviceIndex is not a HIP device (PTGetBVHBuildError() has the text); there is no CPU fallback behind this entry. */
+ * or when deviceIndex is not a HIP device (PTGetBVHBuildError() has the text); there is no CPU fallback behind this entry.
+ * A vertex that is not finite is refused too ("vertex i is not finite", as PTRefitBVH says it): the host looks at the array
+ * before the upload, outside the interval PTGetBVHBuildMs reports. */
 PT_API int   PTBuildBVHDevice(int deviceIndex, const PTFloat4* vertices, int triangleCount);
 PT_API const char* PTGetBVHBuildError(void);
 /* Build time of a handle in milliseconds: host wall time of BuildBVH, device time (kernels only) of PTBuildBVHDevice. */

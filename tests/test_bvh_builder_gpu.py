@@ -1,14 +1,19 @@
 """PTBuildBVHDevice: the CWBVH builder that runs on the MI355X (csrc/bvh_builder_gpu.hip: LBVH -> 8-wide collapse -> CWBVH
 encode in HIP kernels).  It sits beside BuildBVH, whose bytes must equal the reference plugin's; this one
-builds a different tree in the same format, so its parity bar is HIT equality: every ray finds the same closest hit (bit-identical
-t, same primitive unless another triangle yields the very same t) as in the reference-built tree, the structure passes
-PTSetScene's index validation, and a frame rendered on the GPU over the device-built tree equals the oracle's render over the
-same bytes bit for bit."""
+builds a different tree in the same format.  Its own bar: after renumbering (the kernels claim node and triangle storage with
+atomicAdd) the bytes equal tests/lbvh_ref.py, the builder's rule restated in numpy float32.  Beside that, HIT
+equality: every ray finds the same closest hit (bit-identical t, same primitive unless another triangle yields the very same
+t) as in the reference-built tree, the structure passes PTSetScene's index validation, and a frame rendered on the GPU over
+the device-built tree equals the oracle's render over the same bytes bit for bit."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import lbvh_ref
+from lbvh_ref import check_structure
+from test_lbvh_ref import CASES, IDS, restated
+from test_refit import soup
 from unity_webgpu_pathtracer_amd import abi, plugin, scenes
 from unity_webgpu_pathtracer_amd.pathtracer import BVHScene, PathTracer
 
@@ -29,17 +34,6 @@ def _rays(scene, n, seed):
     return rays
 
 
-def _check_structure(nodes, tris, ntri):
-    n = np.frombuffer(nodes.tobytes(), abi.CWBVH_NODE)
-    t = np.frombuffer(tris.tobytes(), np.uint32).reshape(-1, 4)
-    assert t.shape[0] == ntri * 3
-    prim = np.sort(t[2::3, 3])
-    assert np.array_equal(prim, np.arange(ntri, dtype=np.uint32))          # every triangle stored exactly once
-    inner = ((n["meta"] & 0x18) == 0x18) & ((n["meta"] >> 5) == 1)
-    assert np.array_equal(np.array([bin(int(m)).count("1") for m in n["imask"]]), inner.sum(axis=1))
-    assert inner.sum() == len(n) - 1                                        # every node but the root is exactly one node's child
-
-
 @pytest.mark.parametrize("name,kw,nrays", [
     ("cornell", {}, 4000), ("zoo", {}, 20000), ("sponza", {"tex_size": 4, "detail": 0.15}, 20000), ("bunny", {}, 20000),
 ])
@@ -49,7 +43,7 @@ def test_device_built_tree_gives_the_same_hits(oracle, name, kw, nrays):
     tm = {}
     dev_nodes, dev_tris = plugin.build_cwbvh(s.vertices, device=0, timing=tm)
     print(f"[gpu builder] {name}: {s.tri_count} triangles, {dev_nodes.nbytes // 80} nodes (reference tree: {ref_nodes.nbytes // 80}), device build {tm['build_ms']:.2f} ms")
-    _check_structure(dev_nodes, dev_tris, s.tri_count)
+    check_structure(dev_nodes, dev_tris, s.tri_count)
     rays = _rays(s, nrays, seed=11)
     t_ref, p_ref, _ = oracle.trace(oracle.SceneBuffers(s, ref_nodes, ref_tris), rays)
     t_dev, p_dev, _ = oracle.trace(oracle.SceneBuffers(s, dev_nodes, dev_tris), rays)
@@ -79,16 +73,54 @@ def test_tiny_and_degenerate_inputs(oracle):
         v = np.zeros((ntri * 3, 4), np.float32)
         v[:, :3] = rng.uniform(-2, 2, (ntri, 1, 3)).repeat(3, axis=1).reshape(-1, 3) + rng.normal(0, 0.5, (ntri * 3, 3))
         nodes, tris = plugin.build_cwbvh(v, device=0)
-        _check_structure(nodes, tris, ntri)
+        check_structure(nodes, tris, ntri)
     dup = np.zeros((60, 4), np.float32)                                     # twenty identical triangles: equal Morton codes
     dup[:, :3] = np.tile(np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0]], np.float32), (20, 1))
     nodes, tris = plugin.build_cwbvh(dup, device=0)
-    _check_structure(nodes, tris, 20)
+    check_structure(nodes, tris, 20)
     flat = np.zeros((12, 4), np.float32)                                    # zero extent on one axis
     flat[:, :2] = rng.rand(12, 2)
-    _check_structure(*plugin.build_cwbvh(flat, device=0), 4)
+    check_structure(*plugin.build_cwbvh(flat, device=0), 4)
     assert lib.PTBuildBVHDevice(0, None, 5) == -1 and lib.PTBuildBVHDevice(0, dup.ctypes.data_as(C.c_void_p), 0) == -1
     assert lib.PTBuildBVHDevice(99, dup.ctypes.data_as(C.c_void_p), 20) == -1 and b"device" in lib.PTGetBVHBuildError()
+
+
+def _assert_equals_the_rule(name, v, built):
+    want_n, want_t = restated(name, v)
+    check_structure(*built, v.shape[0] // 3)
+    got_n, got_t = lbvh_ref.canonical(*built)
+    diff = lbvh_ref.first_difference(got_n, want_n)
+    assert diff is None, f"{name}: {diff}"
+    bad = np.nonzero((got_t.reshape(-1, 48) != want_t.reshape(-1, 48)).any(axis=1))[0]
+    assert bad.size == 0, f"{name}: {bad.size} triangle records differ, the first is record {bad[0]}"
+
+
+@pytest.mark.parametrize("name,v", CASES, ids=IDS)
+def test_device_tree_equals_the_restated_rule(name, v):
+    """canonical(PTBuildBVHDevice's tree) == lbvh_ref.build(v), byte for byte: keys, order, splits, greedy expansion, slots,
+    quantised boxes, meta bytes and triangle records are all the rule's.  A mismatch names the first node, its level and the
+    part that differs: keys / splits / expansion change the bases and meta of a node near the root, the slot assignment
+    permutes meta and bytes within a node, the fit or the encode changes origin, exponents or the low / high bytes alone."""
+    _assert_equals_the_rule(name, v, plugin.build_cwbvh(v, device=0))
+
+
+def test_two_builds_are_one_tree():
+    name, v = next(c for c in CASES if c[0] == "soup5000")
+    a, b = plugin.build_cwbvh(v, device=0), plugin.build_cwbvh(v, device=0)
+    print(f"[gpu builder] two builds of {name}: bytes equal before renumbering: nodes {np.array_equal(a[0], b[0])}, triangles {np.array_equal(a[1], b[1])}")
+    ca, cb = lbvh_ref.canonical(*a), lbvh_ref.canonical(*b)
+    assert lbvh_ref.first_difference(ca[0], cb[0]) is None, lbvh_ref.first_difference(ca[0], cb[0])
+    assert np.array_equal(ca[1], cb[1])
+
+
+def test_non_finite_vertices_are_refused():
+    lib = plugin.load_library()
+    name, v = "soup300", soup(300, 400)
+    for bad in (np.nan, np.inf, -np.inf):
+        w = v.copy()
+        w[3 * 137 + 1, 2] = bad
+        assert lib.PTBuildBVHDevice(0, w.ctypes.data_as(C.c_void_p), 300) == -1 and b"finite" in lib.PTGetBVHBuildError()
+        _assert_equals_the_rule(name, v, plugin.build_cwbvh(v, device=0))  # the clean soup right after: builds, and to the rule
 
 
 def test_frame_over_the_device_built_tree_is_bit_exact(oracle):
@@ -122,6 +154,12 @@ def test_build_time_250k_triangles():
     plugin.build_cwbvh(s.vertices, timing=cpu)
     plugin.build_cwbvh(s.vertices, device=0, timing=dev)                   # first call: module load + allocation warm-up
     n, t = plugin.build_cwbvh(s.vertices, device=0, timing=dev)
-    _check_structure(n, t, s.tri_count)
+    check_structure(n, t, s.tri_count)
+    # the large-scale pin: a refit with the vertices it was built from changes no byte (origin zero signs aside), so every box
+    # and every triangle record is the encode rule's for this topology
+    rn, rt = plugin.refit_cwbvh((n, t), s.vertices)
+    assert np.array_equal(rt, t)
+    assert lbvh_ref.first_difference(lbvh_ref.positive_zero_origins(rn), lbvh_ref.positive_zero_origins(n)) is None, \
+        lbvh_ref.first_difference(lbvh_ref.positive_zero_origins(rn), lbvh_ref.positive_zero_origins(n))
     print(f"[gpu builder] 250k triangles: CPU binned-SAH BuildBVH {cpu['build_ms']:.1f} ms, PTBuildBVHDevice kernels {dev['build_ms']:.2f} ms, {n.nbytes // 80} nodes")
     assert dev["build_ms"] < cpu["build_ms"]

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -159,7 +160,7 @@ __global__ __launch_bounds__(256) void pt_lbvh_fit(uint32_t n, const uint32_t* _
         __threadfence();
         Box b;
         const uint32_t refs[2] = {left[node], right[node]};
-        for (int k = 0; k < 3; ++k) { b.mn[k] = 1e30f; b.mx[k] = -1e30f; }
+        for (int k = 0; k < 3; ++k) { b.mn[k] = INFINITY; b.mx[k] = -INFINITY; }   // not a large finite number: coordinates past it are input too
         for (int c = 0; c < 2; ++c) {
             // children written by other threads are read past the L1 of this CU (sc1: served from L2 / memory)
             const Box* src = (refs[c] & LEAF_BIT) ? &prim[ids[refs[c] & ~LEAF_BIT]] : &nodeBox[refs[c]];
@@ -242,7 +243,7 @@ __global__ __launch_bounds__(64) void pt_cwbvh_level(WideArgs A, uint32_t levelS
     }
     // ---- node box, child boxes
     Box cb[8], nb;
-    for (int k = 0; k < 3; ++k) { nb.mn[k] = 1e30f; nb.mx[k] = -1e30f; }
+    for (int k = 0; k < 3; ++k) { nb.mn[k] = INFINITY; nb.mx[k] = -INFINITY; }
     for (uint32_t i = 0; i < count; ++i) {
         cb[i] = ref_box(A, child[i]);
         for (int k = 0; k < 3; ++k) { nb.mn[k] = fminf(nb.mn[k], cb[i].mn[k]); nb.mx[k] = fmaxf(nb.mx[k], cb[i].mx[k]); }
@@ -262,7 +263,7 @@ __global__ __launch_bounds__(64) void pt_cwbvh_level(WideArgs A, uint32_t levelS
         }
     }
     for (uint32_t round = 0; round < count; ++round) {
-        float best = 3e30f;
+        float best = INFINITY;                                       // every finite cost compares, however large the scene
         int bs = -1, bi = -1;
         for (int s = 0; s < 8; ++s) {
             if (childOf[s] >= 0) continue;
@@ -360,6 +361,9 @@ bool build_cwbvh_device(int device, const PTFloat4* verts, uint32_t n, Cwbvh& ou
 {
     if (!verts || n == 0) { err = "no triangles"; return false; }
     if (n > 0x7FFFFFF0u / 3u) { err = "too many triangles"; return false; }
+    // one NaN centroid would win the atomicMax on the scene bounds and take an axis out of EVERY Morton code: refuse, as the refit does
+    for (size_t i = 0; i < (size_t)n * 3; ++i)
+        if (!std::isfinite(verts[i].x) || !std::isfinite(verts[i].y) || !std::isfinite(verts[i].z)) { err = "vertex " + std::to_string(i) + " is not finite"; return false; }
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) { err = "no such HIP device (this builder has no CPU fallback; BuildBVH is the CPU builder)"; return false; }
     // the calling thread's current device is left as it was found
