@@ -779,7 +779,8 @@ PT_API int PTTraceRadianceHost(PTContext* ctx, const PTFrameParams* params, cons
  * with 255 * 2^e >= extent, q_lo = clamp(floor((c.mn - lo) / 2^e)), q_hi = clamp(ceil((c.mx - lo) / 2^e)) into 0 ... 255, empty
  * slots 0.  Every step is exact or correctly rounded: PTReadGeometry after an update equals PTRefitBVH of the same tree and
  * vertices byte for byte, and frames, queries and guides equal those of a fresh PTSetScene of the refitted arrays.  The tree's
- * quality is the caller's to watch: a refit of a strongly deformed mesh traverses more nodes than a rebuild.
+ * quality is the caller's to watch: a refit of a strongly deformed mesh traverses more nodes than a rebuild;
+ * Part 10 measures it (PTMeasureGeometry) and rebuilds in place (PTRebuildGeometry).
  *
  * The BLAS is named by the three offsets of its PTGpuInstance records: bvhOffset (nodes), triOffset (float4s),
  * triAttributeOffset (triangles); 0, 0, 0 for a scene without HAS_TLAS.  vertices: 3 * triangleCount PTFloat4 in the BLAS's
@@ -807,6 +808,71 @@ PT_API int PTUpdateGeometry(PTContext* ctx, int32_t bvhOffset, int32_t triOffset
 PT_API int PTUpdateGeometryDevice(PTContext* ctx, int32_t bvhOffset, int32_t triOffset, int32_t triAttributeOffset, const PTFloat4* dVertices,
                                   int triangleCount, const PTTriangleAttributes* dAttrsOrNull);           /* device arrays, read in stream order */
 PT_API int PTReadGeometry(PTContext* ctx, void* dstNodes, uint64_t nodeBytes, void* dstTris, uint64_t triBytes, void* dstAttrs, uint64_t attrBytes);
+
+/* =====================================================================================================================
+ * Part 10: geometry rebuilds and tree quality.  Part 9 keeps the topology; a pose that has drifted far from the one the tree was
+ * built for is traversed through ever looser boxes.  PTRebuildGeometry builds a NEW tree for the BLAS, in
+ * place, on the GPU: PTBuildBVHDevice's builder runs on the update stream, from vertices on the device, straight into the
+ * generation that is not current -- no node or triangle read-back, no PTSetScene.  PTMeasureGeometry tells the host when.
+ *
+ * Rebuild.  The arguments, ordering, generations, carry-over, attribute handling, the TLAS rule (the instances' world bounds are
+ * the caller's to resend), lifetime and errors are Part 9's: accumulation is not reset, PTSetScene discards everything,
+ * PTDestroy frees it.  The result is the tree of PTBuildBVHDevice's rule for these vertices, built at bvhOffset / triOffset of the
+ * target generation after the carry-over copy (node and row indices inside a BLAS are relative to its offsets).  All
+ * 3 * triangleCount triangle rows are rewritten; primIdx stays the caller's primitive order, so the attribute records still
+ * match.  Node numbering within the tree is the builder's (atomic allocation, level by level) and may differ from call to call.
+ * Node capacity.  The new tree's node count K generally differs from the old one's.  A BLAS's capacity is its node span in the
+ * scene PTSetScene was given: from bvhOffset to the next larger distinct bvhOffset among the instances, or to the end of the
+ * node buffer (a scene without HAS_TLAS: the whole buffer).  PTSetScene's validation only follows what a ray can reach, so a
+ * host that plans to rebuild pads the span with unreferenced (zero) nodes.  K <= capacity: the K nodes are written and nodes
+ * K ... capacity - 1 of the span are zero-filled.  K > capacity: PT_ERR_INVALID_ARG, the message names K and the capacity;
+ * nothing is ever written outside the span, no buffer grows, no offset moves.
+ * Non-finite vertices are refused by both variants with PT_ERR_INVALID_ARG ("vertex ... is not finite"): the host variant looks
+ * on the host, the device variant on the device (a flag the builder's bounds kernel writes, read before anything else of the
+ * build is launched) -- one NaN centroid would poison every Morton key.
+ * A refused call (bad arguments, over capacity, a non-finite vertex, an out-of-range materialIndex in a host array, a HIP error)
+ * leaves the scene exactly as it was: PTReadGeometry returns the same bytes, frames are the same, later calls work.
+ * Host traffic: one 4-byte counter per tree level and the flags are read back, never nodes or triangle rows.  The call
+ * therefore SYNCHRONISES WITH THE UPDATE STREAM (not with the passes in flight on the other streams).  The builder's work
+ * arrays and the sort's temporary storage live in the context, sized for the largest BLAS rebuilt so far: no allocation per
+ * call after the first.  After a rebuild PTUpdateGeometry refits the new tree and PTMeasureGeometry measures it.
+ *
+ * Quality.  nodeCount and levels are those of the nodes reachable from the root.  sahCost = 1 + the sum over every occupied
+ * slot of every reachable node of halfArea(slot) / rootHalfArea * (1 for an inner slot, popcount(meta >> 5) for a leaf slot),
+ * halfArea = ex*ey + ey*ez + ez*ex of the slot's decoded extent (q_hi - q_lo) * 2^e; rootHalfArea is that of the fold of the
+ * root's occupied slots' decoded boxes lo + q * 2^e; all in float64; rootHalfArea == 0 (a degenerate tree) gives sahCost = 0.  It
+ * is the expected number of node visits plus triangle tests of a random ray that hits the root box.
+ * PTMeasureGeometry measures the BLAS's current tree on the device (after the updates enqueued so far), synchronises and reads
+ * back one small record.  Before any update of the BLAS it walks it as the first update would; the BLAS's triangle count is
+ * then taken from its row span (triOffset to the next larger distinct triOffset among the instances, or the end of the rows).
+ * PTMeasureBVHArrays is the host twin (no GPU) on arrays as GetCWBVHData / PTReadGeometry return them (root = node 0): it
+ * refuses (0, PTGetBVHBuildError has the reason) anything that is not a CWBVH of triangleCount triangles; nodeCapacity there is
+ * nodeBytes / 80, so zero nodes appended to the array change nothing else.  Returns 1 on success.
+ * ===================================================================================================================== */
+typedef struct PTGeometryQuality {
+    uint32_t structSize;          /* sizeof(PTGeometryQuality) of the caller's header; members are only appended */
+    uint32_t nodeCapacity;        /* nodes of the BLAS's span */
+    uint32_t nodeCount;           /* nodes reachable from the root */
+    uint32_t triangleCount;
+    uint32_t levels;
+    uint32_t reserved;
+    double   rootHalfArea;
+    double   sahCost;
+} PTGeometryQuality;
+
+#ifdef __cplusplus
+static_assert(sizeof(PTGeometryQuality) == 40, "PTGeometryQuality is 40 bytes");
+#else
+_Static_assert(sizeof(PTGeometryQuality) == 40, "PTGeometryQuality is 40 bytes");
+#endif
+
+PT_API int PTRebuildGeometry(PTContext* ctx, int32_t bvhOffset, int32_t triOffset, int32_t triAttributeOffset, const PTFloat4* vertices,
+                             int triangleCount, const PTTriangleAttributes* attrsOrNull);                 /* host arrays, copied before return */
+PT_API int PTRebuildGeometryDevice(PTContext* ctx, int32_t bvhOffset, int32_t triOffset, int32_t triAttributeOffset, const PTFloat4* dVertices,
+                                   int triangleCount, const PTTriangleAttributes* dAttrsOrNull);          /* device arrays, read in stream order */
+PT_API int PTMeasureGeometry(PTContext* ctx, int32_t bvhOffset, int32_t triOffset, int32_t triAttributeOffset, PTGeometryQuality* out);
+PT_API int PTMeasureBVHArrays(const PTFloat4* bvhNodes, uint64_t nodeBytes, const PTFloat4* bvhTris, uint64_t triBytes, int triangleCount,
+                              PTGeometryQuality* out);                                                    /* host twin, no GPU */
 
 /* Text of the last error on the calling thread ("" if none). */
 PT_API const char* PTGetLastError(void);

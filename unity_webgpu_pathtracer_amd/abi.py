@@ -274,6 +274,27 @@ class PTRadiance(C.Structure):
 assert C.sizeof(PTRadianceRay) == 32 and C.sizeof(PTRadiance) == 16
 
 
+# ---------------------------------------------------------------------------------------
+# Part 10: geometry rebuilds and tree quality (PTRebuildGeometry / PTMeasureGeometry / PTMeasureBVHArrays)
+# ---------------------------------------------------------------------------------------
+class PTGeometryQuality(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("nodeCapacity", C.c_uint32), ("nodeCount", C.c_uint32), ("triangleCount", C.c_uint32),
+                ("levels", C.c_uint32), ("reserved", C.c_uint32), ("rootHalfArea", C.c_double), ("sahCost", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k in ("nodeCapacity", "nodeCount", "triangleCount", "levels", "rootHalfArea", "sahCost")}
+
+
+assert C.sizeof(PTGeometryQuality) == 40
+
+
+def geometry_quality() -> PTGeometryQuality:
+    """An empty PTGeometryQuality with structSize set, for PTMeasureGeometry / PTMeasureBVHArrays to fill."""
+    q = PTGeometryQuality()
+    q.structSize = C.sizeof(PTGeometryQuality)
+    return q
+
+
 def as_void_p(arr):
     """Borrowed host pointer of a C-contiguous numpy array (None -> NULL)."""
     if arr is None:

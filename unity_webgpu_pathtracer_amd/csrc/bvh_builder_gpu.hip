@@ -5,6 +5,10 @@
 // format of tiny_bvh.h:5844-5976), same handle table, a different tree -- so its parity bar is not byte equality but hit
 // equality: every ray finds the same closest hit (t, primitive) as in the reference-built tree (tests/test_bvh_builder_gpu.py).
 //
+// The pipeline is device_build_cwbvh (bvh_builder_gpu.h): the caller gives the stream, the vertices on the device, where the nodes
+// and rows go, the node capacity and the work arrays.  build_cwbvh_device wraps it for the handle table (allocates, uploads, times,
+// reads back); the in-place rebuild (pt_api_geometry.hip) runs it on the update stream straight into the scene's buffers.
+//
 // Pipeline (every step a kernel; the host only reads back one counter per tree level):
 //   1. pt_lbvh_bounds      triangle AABBs + scene centroid bounds (wave reduction + float atomics on ordered-uint keys)
 //   2. pt_lbvh_morton      63-bit keys: 3 x 21-bit Morton code of the centroid; the primitive index rides in a second word and
@@ -30,13 +34,15 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "bvh_builder.h"
+#include "bvh_builder_gpu.h"
 #include "ptmi_plugin.h"
 
 namespace ptbvh {
 
 namespace {
 
-#define GPU_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { err = std::string(#expr) + ": " + hipGetErrorString(_e); return false; } } while (0)
+#define GPU_TRY_RET(expr, ret) do { hipError_t _e = (expr); if (_e != hipSuccess) { err = std::string(#expr) + ": " + hipGetErrorString(_e); return ret; } } while (0)
+#define GPU_TRY(expr) GPU_TRY_RET(expr, false)
 
 struct Box { float mn[3], mx[3]; };
 
@@ -57,6 +63,13 @@ __global__ __launch_bounds__(256) void pt_lbvh_bounds(const float4* __restrict__
         bx.mn[2] = fminf(a.z, fminf(b.z, d.z)); bx.mx[2] = fmaxf(a.z, fmaxf(b.z, d.z));
         prim[i] = bx;
         for (int k = 0; k < 3; ++k) c[k] = 0.5f * (bx.mn[k] + bx.mx[k]);
+        // a vertex that is not finite: sceneKeys[6] is the flag, sceneKeys[7] keeps the first such vertex (the host refuses the build)
+        const float4 vv[3] = {a, b, d};
+        for (uint32_t k = 0; k < 3u; ++k)
+            if (!(fabsf(vv[k].x) < INFINITY) || !(fabsf(vv[k].y) < INFINITY) || !(fabsf(vv[k].z) < INFINITY)) {
+                atomicOr(&sceneKeys[6], 1u);
+                atomicMin(&sceneKeys[7], 3u * i + k);
+            }
     }
     // centroid bounds: wave reduction, then one atomic pair per wave and axis
     for (int k = 0; k < 3; ++k) {
@@ -187,8 +200,9 @@ struct WideArgs {
     const uint32_t *left, *right, *first, *last;
     uint32_t n;
     uint32_t* wideRoot;         // [wide node] binary reference it was made from
-    uint32_t maxWide;           // capacity of the wide-node pool (nodes, wideRoot)
-    uint32_t* counters;         // [0] wide nodes allocated, [1] triangle rows (float4) allocated, [2] pool-overflow flag
+    uint32_t maxWide;           // capacity of the wide-node pool (wideRoot)
+    uint32_t nodeCap;           // nodes that may be written at `nodes` (<= maxWide): a node past it is counted, not written
+    uint32_t* counters;         // [0] wide nodes allocated, [1] triangle rows (float4) allocated, [2] flags: 1 pool overflow, 2 a node past nodeCap
     uint4* nodes;               // PTCwbvhNode as 5 x uint4
     float4* tris;               // PTCwbvhTri as 3 x float4
 };
@@ -329,6 +343,8 @@ __global__ __launch_bounds__(64) void pt_cwbvh_level(WideArgs A, uint32_t levelS
             trisSeen += c;
         }
     }
+    // a tree larger than the caller's node span: its nodes are still counted (the host names the count), none is written past the span
+    if (w >= A.nodeCap) { atomicOr(&A.counters[2], 2u); return; }
     uint4* out = A.nodes + (size_t)w * 5u;
     out[0] = make_uint4(__float_as_uint(nb.mn[0]), __float_as_uint(nb.mn[1]), __float_as_uint(nb.mn[2]),
                         ((uint32_t)ex & 255u) | (((uint32_t)ey & 255u) << 8) | (((uint32_t)ez & 255u) << 16) | (imask << 24));
@@ -339,21 +355,119 @@ __global__ __launch_bounds__(64) void pt_cwbvh_level(WideArgs A, uint32_t levelS
     out[4] = make_uint4(pack4(q + 32), pack4(q + 36), pack4(q + 40), pack4(q + 44));
 }
 
-struct DevMem {
-    std::vector<void*> ptrs;
-    ~DevMem() { for (void* p : ptrs) hipFree(p); }
-    template <class T> bool alloc(T** out, size_t count, std::string& err)
-    {
-        void* p = nullptr;
-        hipError_t e = hipMalloc(&p, count * sizeof(T) + 16);
-        if (e != hipSuccess) { err = std::string("hipMalloc: ") + hipGetErrorString(e); return false; }
-        ptrs.push_back(p);
-        *out = (T*)p;
-        return true;
-    }
+size_t al256(size_t b) { return (b + 255) / 256 * 256; }
+
+// the work arrays, carved from one allocation
+struct Work {
+    Box *prim, *nodeBox;
+    uint32_t *scene, *ids, *idsSorted, *left, *right, *parentI, *parentL, *first, *last, *visits, *wideRoot, *counters;
+    uint64_t *keys, *keysSorted;
+    void* sortTemp;
+    size_t sortTempBytes, bytes;
 };
 
+size_t max_wide(uint32_t n) { return 2 * (size_t)n + 2; }      // a wide node has >= 2 inner children or at least one leaf child of its own: < 2n nodes
+
+bool carve(void* base, uint32_t n, Work& w)
+{
+    size_t tempBytes = 0;
+    if (rocprim::radix_sort_pairs(nullptr, tempBytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, 63, nullptr) != hipSuccess) return false;
+    char* p = (char*)base;
+    auto take = [&](size_t bytes) { char* q = p; p += al256(bytes + 16); return (void*)q; };
+    w.prim = (Box*)take((size_t)n * sizeof(Box)); w.nodeBox = (Box*)take((size_t)n * sizeof(Box));
+    w.scene = (uint32_t*)take(8 * 4); w.counters = (uint32_t*)take(4 * 4);
+    w.ids = (uint32_t*)take((size_t)n * 4); w.idsSorted = (uint32_t*)take((size_t)n * 4);
+    w.left = (uint32_t*)take((size_t)n * 4); w.right = (uint32_t*)take((size_t)n * 4);
+    w.parentI = (uint32_t*)take((size_t)n * 4); w.parentL = (uint32_t*)take((size_t)n * 4);
+    w.first = (uint32_t*)take((size_t)n * 4); w.last = (uint32_t*)take((size_t)n * 4);
+    w.visits = (uint32_t*)take((size_t)n * 4); w.wideRoot = (uint32_t*)take(max_wide(n) * 4);
+    w.keys = (uint64_t*)take((size_t)n * 8); w.keysSorted = (uint64_t*)take((size_t)n * 8);
+    w.sortTemp = take(tempBytes);
+    w.sortTempBytes = tempBytes;
+    w.bytes = (size_t)(p - (char*)base);
+    return true;
+}
+
 } // namespace
+
+size_t device_build_work_bytes(uint32_t n)
+{
+    Work w;
+    if (n == 0 || n > 0x7FFFFFF0u / 3u || !carve(nullptr, n, w)) return 0;
+    return w.bytes;
+}
+
+DeviceBuildStatus device_build_cwbvh(hipStream_t stream, const float4* dVerts, uint32_t n, uint4* nodes, float4* tris, uint32_t nodeCapacity,
+                                     void* work, bool checkFinite, DeviceBuildResult& out, std::string& err, hipEvent_t kernelsDone)
+{
+    out = DeviceBuildResult();
+    Work W;
+    if (!dVerts || !nodes || !tris || !work || n == 0 || n > 0x7FFFFFF0u / 3u || !carve(work, n, W)) { err = "device build: bad arguments"; return kBuildFailed; }
+    const size_t maxWide = max_wide(n);
+    const uint32_t nodeCap = nodeCapacity < maxWide ? nodeCapacity : (uint32_t)maxWide;
+    const uint32_t sceneInit[8] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0xFFFFFFFFu};
+    GPU_TRY_RET(hipMemcpyAsync(W.scene, sceneInit, sizeof(sceneInit), hipMemcpyHostToDevice, stream), kBuildFailed);
+    GPU_TRY_RET(hipMemsetAsync(W.visits, 0, (size_t)n * 4, stream), kBuildFailed);
+    const uint32_t blocks = (n + 255u) / 256u;
+    // a launch that fails (no code object for this device, bad configuration) leaves its outputs untouched: check every one
+    hipLaunchKernelGGL(pt_lbvh_bounds, dim3(blocks), dim3(256), 0, stream, dVerts, n, W.prim, W.scene);
+    GPU_TRY_RET(hipGetLastError(), kBuildFailed);
+    if (checkFinite) {
+        // one NaN centroid would win the atomicMax on the scene bounds and take an axis out of EVERY Morton code: refused here,
+        // before the sort, the hierarchy and the level kernels are launched
+        uint32_t flags[2] = {0u, 0u};
+        GPU_TRY_RET(hipMemcpyAsync(flags, W.scene + 6, sizeof(flags), hipMemcpyDeviceToHost, stream), kBuildFailed);
+        GPU_TRY_RET(hipStreamSynchronize(stream), kBuildFailed);
+        if (flags[0]) { out.badVertex = flags[1]; return kBuildNonFinite; }
+    }
+    hipLaunchKernelGGL(pt_lbvh_morton, dim3(blocks), dim3(256), 0, stream, W.prim, n, W.scene, W.keys, W.ids);
+    GPU_TRY_RET(hipGetLastError(), kBuildFailed);
+    size_t tempBytes = W.sortTempBytes;
+    GPU_TRY_RET(rocprim::radix_sort_pairs(W.sortTemp, tempBytes, W.keys, W.keysSorted, W.ids, W.idsSorted, n, 0, 63, stream), kBuildFailed);
+    uint32_t rootRef = LEAF_BIT | 0u;                                 // one triangle: the root is that leaf
+    if (n > 1) {
+        Tree t{W.keysSorted, n};
+        hipLaunchKernelGGL(pt_lbvh_hierarchy, dim3((n - 1 + 255u) / 256u), dim3(256), 0, stream, t, W.left, W.right, W.parentI, W.parentL, W.first, W.last);
+        GPU_TRY_RET(hipGetLastError(), kBuildFailed);
+        hipLaunchKernelGGL(pt_lbvh_fit, dim3(blocks), dim3(256), 0, stream, n, W.idsSorted, W.prim, W.left, W.right, W.parentI, W.parentL, W.nodeBox, W.visits);
+        GPU_TRY_RET(hipGetLastError(), kBuildFailed);
+        rootRef = 0u;
+    }
+    // level 0 = the root wide node
+    const uint32_t countersInit[4] = {1u, 0u, 0u, 0u};
+    GPU_TRY_RET(hipMemcpyAsync(W.counters, countersInit, sizeof(countersInit), hipMemcpyHostToDevice, stream), kBuildFailed);
+    GPU_TRY_RET(hipMemcpyAsync(W.wideRoot, &rootRef, 4, hipMemcpyHostToDevice, stream), kBuildFailed);
+    WideArgs A{dVerts, W.idsSorted, W.prim, W.nodeBox, W.left, W.right, W.first, W.last, n, W.wideRoot, (uint32_t)maxWide, nodeCap, W.counters, nodes, tris};
+    uint32_t levelStart = 0, levelEnd = 1, levels = 0;
+    out.levelStart.assign(1, 0u);
+    while (levelStart < levelEnd) {
+        if (levelEnd > maxWide) { err = "wide-node pool exhausted"; return kBuildFailed; }
+        hipLaunchKernelGGL(pt_cwbvh_level, dim3((levelEnd - levelStart + 63u) / 64u), dim3(64), 0, stream, A, levelStart, levelEnd);
+        GPU_TRY_RET(hipGetLastError(), kBuildFailed);
+        uint32_t allocated = 0;
+        GPU_TRY_RET(hipMemcpyAsync(&allocated, W.counters, 4, hipMemcpyDeviceToHost, stream), kBuildFailed);
+        GPU_TRY_RET(hipStreamSynchronize(stream), kBuildFailed);
+        if (allocated < levelEnd || allocated > maxWide) { err = "wide-node pool exhausted or corrupted (allocated " + std::to_string(allocated) + " of " + std::to_string(maxWide) + ")"; return kBuildFailed; }
+        out.levelStart.push_back(levelEnd);
+        levelStart = levelEnd;
+        levelEnd = allocated;
+        if (++levels > 4096u) { err = "tree depth out of range"; return kBuildFailed; }
+    }
+    if (kernelsDone) GPU_TRY_RET(hipEventRecord(kernelsDone, stream), kBuildFailed);
+    const uint32_t wideCount = levelEnd;
+    out.nodeCount = wideCount;
+    // every triangle must have been emitted exactly once (counters[1] = triangle rows written), at least the root node exists
+    uint32_t counters[4] = {0, 0, 0, 0};
+    GPU_TRY_RET(hipMemcpyAsync(counters, W.counters, sizeof(counters), hipMemcpyDeviceToHost, stream), kBuildFailed);
+    GPU_TRY_RET(hipStreamSynchronize(stream), kBuildFailed);
+    if (wideCount < 1u || counters[1] != 3u * n || (counters[2] & 1u)) {
+        err = "device build incomplete: " + std::to_string(wideCount) + " nodes, " + std::to_string(counters[1]) + " triangle rows for " + std::to_string(n) + " triangles";
+        return kBuildFailed;
+    }
+    // the span flag and the count say the same thing; either one refuses
+    if (wideCount > nodeCap || (counters[2] & 2u)) return kBuildOverCapacity;
+    return kBuildOk;
+}
 
 // Builds into `out` (host vectors, the layout BuildBVH produces).  deviceMs: device time from the upload's end to the last
 // kernel; returns false with a message on any HIP error.
@@ -373,15 +487,23 @@ bool build_cwbvh_device(int device, const PTFloat4* verts, uint32_t n, Cwbvh& ou
     hipStream_t stream;
     GPU_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     struct StreamGuard { hipStream_t s; ~StreamGuard() { hipStreamDestroy(s); } } guard{stream};
-    DevMem mem;
-    float4* dVerts; Box *dPrim, *dNodeBox; uint32_t *dScene, *dIds, *dIdsSorted, *dLeft, *dRight, *dParentI, *dParentL, *dFirst, *dLast, *dVisits, *dWideRoot, *dCounters;
-    uint64_t *dKeys, *dKeysSorted; uint4* dNodes; float4* dTris;
-    const size_t maxWide = 2 * (size_t)n + 2;                         // a wide node has >= 2 inner children or at least one leaf child of its own: < 2n nodes
-    if (!mem.alloc(&dVerts, (size_t)n * 3, err) || !mem.alloc(&dPrim, n, err) || !mem.alloc(&dNodeBox, n, err) || !mem.alloc(&dScene, 8, err) ||
-        !mem.alloc(&dIds, n, err) || !mem.alloc(&dIdsSorted, n, err) || !mem.alloc(&dKeys, n, err) || !mem.alloc(&dKeysSorted, n, err) ||
-        !mem.alloc(&dLeft, n, err) || !mem.alloc(&dRight, n, err) || !mem.alloc(&dParentI, n, err) || !mem.alloc(&dParentL, n, err) ||
-        !mem.alloc(&dFirst, n, err) || !mem.alloc(&dLast, n, err) || !mem.alloc(&dVisits, n, err) || !mem.alloc(&dWideRoot, maxWide, err) ||
-        !mem.alloc(&dCounters, 4, err) || !mem.alloc(&dNodes, maxWide * 5, err) || !mem.alloc(&dTris, (size_t)n * 3, err))
+    struct DevMem {
+        std::vector<void*> ptrs;
+        ~DevMem() { for (void* p : ptrs) hipFree(p); }
+        bool alloc(void** out, size_t bytes, std::string& err)
+        {
+            void* p = nullptr;
+            hipError_t e = hipMalloc(&p, bytes + 16);
+            if (e != hipSuccess) { err = std::string("hipMalloc: ") + hipGetErrorString(e); return false; }
+            ptrs.push_back(p);
+            *out = p;
+            return true;
+        }
+    } mem;
+    const size_t maxWide = max_wide(n), workBytes = device_build_work_bytes(n);
+    if (!workBytes) { err = "rocprim::radix_sort_pairs: size query failed"; return false; }
+    void *dVerts, *dNodes, *dTris, *dWork;
+    if (!mem.alloc(&dVerts, (size_t)n * 48, err) || !mem.alloc(&dNodes, maxWide * 80, err) || !mem.alloc(&dTris, (size_t)n * 48, err) || !mem.alloc(&dWork, workBytes, err))
         return false;
     GPU_TRY(hipMemcpyAsync(dVerts, verts, (size_t)n * 3 * sizeof(float4), hipMemcpyHostToDevice, stream));
     hipEvent_t e0, e1;
@@ -389,61 +511,13 @@ bool build_cwbvh_device(int device, const PTFloat4* verts, uint32_t n, Cwbvh& ou
     GPU_TRY(hipEventCreate(&e1));
     struct EventGuard { hipEvent_t a, b; ~EventGuard() { hipEventDestroy(a); hipEventDestroy(b); } } eguard{e0, e1};
     GPU_TRY(hipEventRecord(e0, stream));
-    const uint32_t sceneInit[8] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u};
-    GPU_TRY(hipMemcpyAsync(dScene, sceneInit, sizeof(sceneInit), hipMemcpyHostToDevice, stream));
-    GPU_TRY(hipMemsetAsync(dVisits, 0, (size_t)n * 4, stream));
-    const uint32_t blocks = (n + 255u) / 256u;
-    // a launch that fails (no code object for this device, bad configuration) leaves its outputs untouched: check every one
-    hipLaunchKernelGGL(pt_lbvh_bounds, dim3(blocks), dim3(256), 0, stream, dVerts, n, dPrim, dScene);
-    GPU_TRY(hipGetLastError());
-    hipLaunchKernelGGL(pt_lbvh_morton, dim3(blocks), dim3(256), 0, stream, dPrim, n, dScene, dKeys, dIds);
-    GPU_TRY(hipGetLastError());
-    {
-        size_t tempBytes = 0;
-        GPU_TRY(rocprim::radix_sort_pairs(nullptr, tempBytes, dKeys, dKeysSorted, dIds, dIdsSorted, n, 0, 63, stream));
-        char* dTemp;
-        if (!mem.alloc(&dTemp, tempBytes, err)) return false;
-        GPU_TRY(rocprim::radix_sort_pairs(dTemp, tempBytes, dKeys, dKeysSorted, dIds, dIdsSorted, n, 0, 63, stream));
+    DeviceBuildResult res;
+    const DeviceBuildStatus st = device_build_cwbvh(stream, (const float4*)dVerts, n, (uint4*)dNodes, (float4*)dTris, (uint32_t)maxWide, dWork, false, res, err, e1);
+    if (st != kBuildOk) {
+        if (st != kBuildFailed) err = "device build incomplete: " + std::to_string(res.nodeCount) + " nodes for " + std::to_string(n) + " triangles";
+        return false;
     }
-    uint32_t rootRef = LEAF_BIT | 0u;                                 // one triangle: the root is that leaf
-    if (n > 1) {
-        Tree t{dKeysSorted, n};
-        hipLaunchKernelGGL(pt_lbvh_hierarchy, dim3((n - 1 + 255u) / 256u), dim3(256), 0, stream, t, dLeft, dRight, dParentI, dParentL, dFirst, dLast);
-        GPU_TRY(hipGetLastError());
-        hipLaunchKernelGGL(pt_lbvh_fit, dim3(blocks), dim3(256), 0, stream, n, dIdsSorted, dPrim, dLeft, dRight, dParentI, dParentL, dNodeBox, dVisits);
-        GPU_TRY(hipGetLastError());
-        rootRef = 0u;
-    }
-    // level 0 = the root wide node
-    const uint32_t countersInit[4] = {1u, 0u, 0u, 0u};
-    GPU_TRY(hipMemcpyAsync(dCounters, countersInit, sizeof(countersInit), hipMemcpyHostToDevice, stream));
-    GPU_TRY(hipMemcpyAsync(dWideRoot, &rootRef, 4, hipMemcpyHostToDevice, stream));
-    WideArgs A{dVerts, dIdsSorted, dPrim, dNodeBox, dLeft, dRight, dFirst, dLast, n, dWideRoot, (uint32_t)maxWide, dCounters, dNodes, dTris};
-    uint32_t levelStart = 0, levelEnd = 1, levels = 0;
-    while (levelStart < levelEnd) {
-        if (levelEnd > maxWide) { err = "wide-node pool exhausted"; return false; }
-        hipLaunchKernelGGL(pt_cwbvh_level, dim3((levelEnd - levelStart + 63u) / 64u), dim3(64), 0, stream, A, levelStart, levelEnd);
-        GPU_TRY(hipGetLastError());
-        uint32_t allocated = 0;
-        GPU_TRY(hipMemcpyAsync(&allocated, dCounters, 4, hipMemcpyDeviceToHost, stream));
-        GPU_TRY(hipStreamSynchronize(stream));
-        if (allocated < levelEnd || allocated > maxWide) { err = "wide-node pool exhausted or corrupted (allocated " + std::to_string(allocated) + " of " + std::to_string(maxWide) + ")"; return false; }
-        levelStart = levelEnd;
-        levelEnd = allocated;
-        if (++levels > 4096u) { err = "tree depth out of range"; return false; }
-    }
-    GPU_TRY(hipEventRecord(e1, stream));
-    const uint32_t wideCount = levelEnd;
-    {
-        // every triangle must have been emitted exactly once (counters[1] = triangle rows written), at least the root node exists
-        uint32_t counters[4] = {0, 0, 0, 0};
-        GPU_TRY(hipMemcpyAsync(counters, dCounters, sizeof(counters), hipMemcpyDeviceToHost, stream));
-        GPU_TRY(hipStreamSynchronize(stream));
-        if (wideCount < 1u || counters[1] != 3u * n || counters[2] != 0u) {
-            err = "device build incomplete: " + std::to_string(wideCount) + " nodes, " + std::to_string(counters[1]) + " triangle rows for " + std::to_string(n) + " triangles";
-            return false;
-        }
-    }
+    const uint32_t wideCount = res.nodeCount;
     out.triCount = n;
     out.usedBlocks = wideCount * 5u;
     out.nodeData.assign((size_t)wideCount * 5, PTFloat4{0, 0, 0, 0});

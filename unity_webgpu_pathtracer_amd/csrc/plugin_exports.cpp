@@ -11,6 +11,7 @@
 #include <string>
 #include "bvh_builder.h"
 #include "bvh_refit.h"
+#include "bvh_quality.h"
 #include "ptmi_plugin.h"
 
 namespace {
@@ -81,6 +82,25 @@ PT_API int PTRefitBVHArrays(PTFloat4* bvhNodes, uint64_t nodeBytes, PTFloat4* bv
         return 0;
     }
     if (!ptbvh::refit_cwbvh(bvhNodes, nodeBytes / 80u, bvhTris, triBytes / 16u, 0, 0, vertices, (uint32_t)triangleCount, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+// Tree quality of such arrays (bvh_quality.cpp; Part 10 has the rule).  No GPU involved.
+PT_API int PTMeasureBVHArrays(const PTFloat4* bvhNodes, uint64_t nodeBytes, const PTFloat4* bvhTris, uint64_t triBytes, int triangleCount, PTGeometryQuality* out)
+{
+    if (!bvhNodes || !bvhTris || !out || triangleCount <= 0 || nodeBytes < 80 || nodeBytes % 80 || triBytes != (uint64_t)triangleCount * 48u) {
+        g_buildError = "NULL array or result, nodeBytes not a multiple of 80 or triBytes != triangleCount * 48";
+        return 0;
+    }
+    if (out->structSize < sizeof(PTGeometryQuality) || out->structSize > 4096u) {
+        g_buildError = "PTGeometryQuality.structSize is not set (must be sizeof(PTGeometryQuality) of the host's header)";
+        return 0;
+    }
+    ptbvh::Quality q;
+    if (!ptbvh::measure_cwbvh(bvhNodes, nodeBytes / 80u, bvhTris, triBytes / 16u, (uint32_t)triangleCount, q, g_buildError)) return 0;
+    out->nodeCapacity = q.nodeCapacity; out->nodeCount = q.nodeCount; out->triangleCount = q.triangleCount; out->levels = q.levels;
+    out->reserved = 0;
+    out->rootHalfArea = q.rootHalfArea; out->sahCost = q.sahCost;
     g_buildError.clear();
     return 1;
 }

@@ -1,4 +1,5 @@
-// pt_api_geometry.hip — geometry updates and PTReadGeometry (include/ptmi_plugin.h Part 9).
+// pt_api_geometry.hip — geometry updates and PTReadGeometry (include/ptmi_plugin.h Part 9); geometry rebuilds and
+// the tree-quality measure (Part 10).
 #include "pt_context.h"
 
 #include <cmath>
@@ -32,13 +33,25 @@ int ensure_host_copy(PTContext* c)
     return PT_OK;
 }
 
-// The plan of the BLAS the three offsets name; made (and the BLAS walked) on its first update
+// end of the span that starts at `off`: the next larger distinct offset among the instances' (field 0 nodes, 1 rows), or `total`
+uint64_t span_end(const PTContext::Geometry& G, int field, int32_t off, uint64_t total)
+{
+    uint64_t end = total;
+    for (size_t i = 0; i + 2 < G.blasKeys.size(); i += 3) {
+        const int32_t k = G.blasKeys[i + field];
+        if (k > off && (uint64_t)k < end) end = (uint64_t)k;
+    }
+    return end;
+}
+
+// The plan of the BLAS the three offsets name; made (and the BLAS walked) on its first update.  triCount == 0 (PTMeasureGeometry):
+// the BLAS's own count -- the plan's, or for a BLAS without one the count its row span holds.
 int find_plan(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t attrOffset, uint32_t triCount, PTContext::GeomPlan*& out)
 {
     PTContext::Geometry& G = c->update.geometry;
     for (PTContext::GeomPlan& p : G.plans)
         if (p.key[0] == bvhOffset && p.key[1] == triOffset && p.key[2] == attrOffset) {
-            if (p.triCount != triCount)
+            if (triCount && p.triCount != triCount)
                 return fail(PT_ERR_INVALID_ARG, "triangleCount (" + std::to_string(triCount) + ") != the BLAS's (" + std::to_string(p.triCount) + ")");
             out = &p;
             return PT_OK;
@@ -47,6 +60,7 @@ int find_plan(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t attrOf
     for (size_t i = 0; i + 2 < G.blasKeys.size() && !named; i += 3)
         named = G.blasKeys[i] == bvhOffset && G.blasKeys[i + 1] == triOffset && G.blasKeys[i + 2] == attrOffset;
     if (!named) return fail(PT_ERR_INVALID_ARG, "bvhOffset / triOffset / triAttributeOffset name no BLAS of the scene");
+    if (!triCount) triCount = (uint32_t)((span_end(G, 1, triOffset, G.hostTriW.size()) - (uint64_t)triOffset) / 3u);
     if ((uint64_t)attrOffset + triCount > c->attrs.used / 128u) return fail(PT_ERR_INVALID_ARG, "triangleCount reaches past the attribute records");
     ptbvh::RefitPlan plan;
     std::string why;
@@ -67,6 +81,7 @@ int find_plan(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t attrOf
     PTContext::GeomPlan p;
     p.key[0] = bvhOffset; p.key[1] = triOffset; p.key[2] = attrOffset;
     p.triCount = triCount;
+    p.nodeCapacity = (uint32_t)(span_end(G, 0, bvhOffset, G.hostNodes.size() / 5) - (uint64_t)bvhOffset);
     if (int rc = p.order.reserve(plan.order.size() * 4)) return rc;
     HIP_TRY(hipMemcpy(p.order.ptr, plan.order.data(), plan.order.size() * 4, hipMemcpyHostToDevice));
     p.levelStart.swap(plan.levelStart);
@@ -75,8 +90,41 @@ int find_plan(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t attrOf
     return PT_OK;
 }
 
+// The tree of the builder's rule for dVerts, built on the update stream at the BLAS's offsets of the generation being written
+// (after the carry-over copy).  Refusals return before anything of the context changes; on success the BLAS's plan is the new tree's.
+int rebuild_blas(PTContext* c, PTContext::GeomPlan& plan, char* dNodes, char* dTris, const float4* dVerts, bool checkFinite)
+{
+    PTContext::Update& u = c->update;
+    PTContext::Geometry& G = u.geometry;
+    const uint32_t n = plan.triCount, cap = plan.nodeCapacity;
+    const size_t workBytes = ptbvh::device_build_work_bytes(n);
+    if (!workBytes) return fail(PT_ERR_HIP, "rocprim::radix_sort_pairs: size query failed");
+    int rc;
+    // grown only for a larger BLAS; the builds that used the old arrays ran on the update stream
+    if (workBytes > G.buildWork.bytes && (rc = G.buildWork.reserve(workBytes, u.stream))) return rc;
+    ptbvh::DeviceBuildResult res;
+    std::string err;
+    uint4* nodes = (uint4*)(dNodes + (size_t)plan.key[0] * 80);
+    const ptbvh::DeviceBuildStatus st = ptbvh::device_build_cwbvh(u.stream, dVerts, n, nodes, (float4*)(dTris + (size_t)plan.key[1] * 16), cap,
+                                                                   G.buildWork.ptr, checkFinite, res, err);
+    if (st == ptbvh::kBuildNonFinite) return fail(PT_ERR_INVALID_ARG, "vertex " + std::to_string(res.badVertex) + " is not finite");
+    if (st == ptbvh::kBuildOverCapacity)
+        return fail(PT_ERR_INVALID_ARG, "the rebuilt tree has " + std::to_string(res.nodeCount) + " nodes, the BLAS's node span (its capacity) holds " + std::to_string(cap));
+    if (st != ptbvh::kBuildOk) return fail(PT_ERR_HIP, "geometry rebuild: " + err);
+    const uint32_t K = res.nodeCount;
+    if (K < cap) HIP_TRY(hipMemsetAsync(nodes + (size_t)K * 5u, 0, (size_t)(cap - K) * 80, u.stream));
+    // The builder allocates nodes level by level: index order is depth order, the new plan is the identity over 0 ... K - 1 with the
+    // level boundaries the build loop held.  The update stream is idle here (the build's last read-back), so nothing reads the old order.
+    std::vector<uint32_t> order(K);
+    for (uint32_t k = 0; k < K; ++k) order[k] = (uint32_t)plan.key[0] + k;
+    if (plan.order.bytes < (size_t)K * 4 && (rc = plan.order.reserve((size_t)cap * 4))) return rc;
+    HIP_TRY(hipMemcpy(plan.order.ptr, order.data(), (size_t)K * 4, hipMemcpyHostToDevice));
+    plan.levelStart.swap(res.levelStart);
+    return PT_OK;
+}
+
 int update_geometry(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t attrOffset, const PTFloat4* verts, int triangleCount,
-                    const PTTriangleAttributes* attrs, bool onDevice)
+                    const PTTriangleAttributes* attrs, bool onDevice, bool rebuild)
 {
     if (!c) return fail(PT_ERR_INVALID_ARG, "ctx == NULL");
     if (!verts) return fail(PT_ERR_INVALID_ARG, "vertices == NULL");
@@ -119,6 +167,10 @@ int update_geometry(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t 
         if ((rc = stage_host(c, u.geom, tg, verts, (size_t)triCount * 48, G.verts.ptr))) return rc;
         dVerts = (const float4*)G.verts.ptr;
     }
+    if (rebuild) {
+        // a refusal leaves the scene as it was: the generation being written is not current, and nothing below has run
+        if ((rc = rebuild_blas(c, *plan, dNodes, dTris, dVerts, onDevice))) return rc;
+    } else {
     PTRefitArgs A;
     A.nodes = (uint4*)dNodes;
     A.tris = (float4*)dTris;
@@ -127,6 +179,7 @@ int update_geometry(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t 
     A.order = (const uint32_t*)plan->order.ptr;
     A.nodeOff = (uint32_t)bvhOffset; A.triOff = (uint32_t)triOffset; A.triCount = triCount;
     HIP_TRY(pt_launch_refit(A, plan->levelStart.data(), (uint32_t)plan->levelStart.size() - 1u, u.stream, nullptr));
+    }
     char* dAttrs = nullptr;
     if (attrs) {
         dAttrs = (char*)u.attrs.gen[ta].ptr;
@@ -152,13 +205,56 @@ extern "C" {
 PT_API int PTUpdateGeometry(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t triAttributeOffset, const PTFloat4* vertices,
                             int triangleCount, const PTTriangleAttributes* attrsOrNull)
 {
-    return update_geometry(c, bvhOffset, triOffset, triAttributeOffset, vertices, triangleCount, attrsOrNull, false);
+    return update_geometry(c, bvhOffset, triOffset, triAttributeOffset, vertices, triangleCount, attrsOrNull, false, false);
 }
 
 PT_API int PTUpdateGeometryDevice(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t triAttributeOffset, const PTFloat4* dVertices,
                                   int triangleCount, const PTTriangleAttributes* dAttrsOrNull)
 {
-    return update_geometry(c, bvhOffset, triOffset, triAttributeOffset, dVertices, triangleCount, dAttrsOrNull, true);
+    return update_geometry(c, bvhOffset, triOffset, triAttributeOffset, dVertices, triangleCount, dAttrsOrNull, true, false);
+}
+
+PT_API int PTRebuildGeometry(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t triAttributeOffset, const PTFloat4* vertices,
+                             int triangleCount, const PTTriangleAttributes* attrsOrNull)
+{
+    return update_geometry(c, bvhOffset, triOffset, triAttributeOffset, vertices, triangleCount, attrsOrNull, false, true);
+}
+
+PT_API int PTRebuildGeometryDevice(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t triAttributeOffset, const PTFloat4* dVertices,
+                                   int triangleCount, const PTTriangleAttributes* dAttrsOrNull)
+{
+    return update_geometry(c, bvhOffset, triOffset, triAttributeOffset, dVertices, triangleCount, dAttrsOrNull, true, true);
+}
+
+PT_API int PTMeasureGeometry(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t triAttributeOffset, PTGeometryQuality* out)
+{
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx == NULL");
+    if (!out) return fail(PT_ERR_INVALID_ARG, "out == NULL");
+    if (out->structSize < sizeof(PTGeometryQuality) || out->structSize > 4096u)
+        return fail(PT_ERR_INVALID_ARG, "PTGeometryQuality.structSize is not set (must be sizeof(PTGeometryQuality) of the host's header)");
+    if (!c->hasScene) return fail(PT_ERR_NO_SCENE, "PTSetScene has not been called");
+    if (bvhOffset < 0 || triOffset < 0 || triAttributeOffset < 0) return fail(PT_ERR_INVALID_ARG, "a negative offset");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure_host_copy(c))) return rc;
+    PTContext::GeomPlan* plan = nullptr;
+    if ((rc = find_plan(c, bvhOffset, triOffset, triAttributeOffset, 0, plan))) return rc;
+    PTContext::Geometry& G = c->update.geometry;
+    const uint32_t K = plan->levelStart.back();
+    if ((rc = G.qualityWork.reserve(pt_quality_work_bytes(K), c->stream))) return rc;
+    // on the context stream: behind every update enqueued so far (end_update), as a query is
+    HIP_TRY(pt_launch_geometry_quality(c->scene.nodes, (const uint32_t*)plan->order.ptr, K, (double*)G.qualityWork.ptr, c->stream));
+    double r[2] = {0.0, 0.0};
+    HIP_TRY(hipMemcpyAsync(r, G.qualityWork.ptr, sizeof(r), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    out->nodeCapacity = plan->nodeCapacity;
+    out->nodeCount = K;
+    out->triangleCount = plan->triCount;
+    out->levels = (uint32_t)plan->levelStart.size() - 1u;
+    out->reserved = 0;
+    out->rootHalfArea = r[1];
+    out->sahCost = r[1] > 0.0 ? 1.0 + r[0] / r[1] : 0.0;
+    return PT_OK;
 }
 
 PT_API int PTReadGeometry(PTContext* c, void* dstNodes, uint64_t nodeBytes, void* dstTris, uint64_t triBytes, void* dstAttrs, uint64_t attrBytes)

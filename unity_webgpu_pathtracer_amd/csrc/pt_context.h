@@ -4,7 +4,9 @@
 #include "pt_launch.h"
 #include "pt_tlas.h"
 #include "pt_refit.h"
+#include "pt_quality.h"
 #include "bvh_refit.h"
+#include "bvh_builder_gpu.h"
 
 #include <cstring>
 #include <initializer_list>
@@ -228,10 +230,12 @@ struct PTContext {
         Event stagedEv[2];
         bool stagedRecorded[2] = {false, false};
     };
-    // geometry updates (PTUpdateGeometry): what the first one reads back and every later one reuses -- the topology never changes
+    // geometry updates (PTUpdateGeometry): what the first one reads back and every later one reuses -- a refit never changes the
+    // topology; a rebuild (PTRebuildGeometry) replaces the BLAS's plan with the new tree's
     struct GeomPlan {
         int32_t key[3] = {0, 0, 0};                     // bvhOffset, triOffset, triAttributeOffset
         uint32_t triCount = 0;
+        uint32_t nodeCapacity = 0;                      // the BLAS's node span in PTSetScene's buffer
         DeviceBuffer order;                             // ptbvh::RefitPlan::order on the device
         std::vector<uint32_t> levelStart;
     };
@@ -242,6 +246,8 @@ struct PTContext {
         std::vector<GeomPlan> plans;                    // one per BLAS updated so far
         DeviceBuffer nodeBox;                           // 24 B per node of the scene
         DeviceBuffer verts;                             // the host variant's vertices on the device
+        DeviceBuffer buildWork;                         // the builder's work arrays, sized for the largest BLAS rebuilt so far
+        DeviceBuffer qualityWork;                       // PTMeasureGeometry: results and per-workgroup partial sums
     };
     struct Update {
         UpdGroup inst, lights, mats, geom, attrs;

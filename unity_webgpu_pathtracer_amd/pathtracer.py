@@ -20,10 +20,14 @@ from .scenes import Scene, frame_params
 class BVHScene:
     """Scene buffers as BVHScene.cs holds them, uploaded into HBM by PTSetScene."""
 
-    def __init__(self, scene: Scene, build_device: int = None):
-        """build_device = None: BuildBVH (the reference's CPU builder, byte-identical); k: PTBuildBVHDevice on HIP device k."""
+    def __init__(self, scene: Scene, build_device: int = None, node_capacity=None):
+        """build_device = None: BuildBVH (the reference's CPU builder, byte-identical); k: PTBuildBVHDevice on HIP device k.
+        node_capacity: room for in-place rebuilds (PTRebuildGeometry) -- a float factor >= 1 on every BLAS's node count (rounded
+        up), or one absolute node count per BLAS (a number for a flat scene, a sequence per mesh otherwise); each BLAS's node span
+        is padded with zero nodes and later offsets follow.  None: today's bytes."""
         self.scene = scene
         self.build_device = build_device
+        self.node_capacity = node_capacity
         self.build_ms = {}
         self.tlas_data = None
         self.tlas_index_offset = 0
@@ -33,10 +37,26 @@ class BVHScene:
         else:
             # BVHScene.cs:629-659: BuildBVH over the world-space triangle soup, copy node/triangle bytes out
             self.bvh_nodes, self.bvh_tris = plugin.build_cwbvh(scene.vertices, device=build_device, timing=self.build_ms)
+            self.bvh_nodes = self._padded(self.bvh_nodes, 0)
+            self.blas_spans = [(0, self.bvh_nodes.nbytes // 80, 0, self.bvh_tris.nbytes // 48)]
         self.tri_attrs = np.ascontiguousarray(scene.tri_attrs)
         self.materials = np.ascontiguousarray(scene.materials, dtype=np.float32)
         self.lights = np.ascontiguousarray(scene.lights, dtype=np.float32)
         self.texture_data = np.ascontiguousarray(scene.texture_data, dtype=np.uint32)
+
+    def _padded(self, nodes: np.ndarray, blas: int) -> np.ndarray:
+        """nodes with zero nodes appended up to node_capacity's count for BLAS number `blas`"""
+        cap = self.node_capacity
+        if cap is None:
+            return nodes
+        count = nodes.nbytes // 80
+        if isinstance(cap, float):
+            assert cap >= 1.0, "node_capacity as a factor must be >= 1"
+            want = int(np.ceil(count * cap))
+        else:
+            want = int(cap[blas] if np.ndim(cap) else cap)
+        assert want >= count, f"node_capacity {want} is below the BLAS's {count} nodes"
+        return np.concatenate([nodes, np.zeros((want - count) * 80, np.uint8)])
 
     def _build_two_level(self, scene: Scene):
         """BVHScene.cs:600-758 with _useTLAS: one BLAS per unique mesh (local space), node / triangle buffers back to
@@ -47,6 +67,7 @@ class BVHScene:
         n_off = t_off = 0
         for t0, n in scene.mesh_ranges:
             nb, tb = plugin.build_cwbvh(scene.vertices[t0 * 3:(t0 + n) * 3], device=self.build_device)
+            nb = self._padded(nb, len(nodes))
             nodes.append(nb)
             tris.append(tb)
             node_off.append(n_off)
@@ -55,6 +76,7 @@ class BVHScene:
             t_off += tb.nbytes
         self.bvh_nodes = np.concatenate(nodes)
         self.bvh_tris = np.concatenate(tris)
+        self.blas_spans = [(node_off[m] // 80, nodes[m].nbytes // 80, tri_off[m] // 16, tris[m].nbytes // 48) for m in range(len(nodes))]
         gi = np.zeros(len(scene.instances), dtype=abi.GPU_INSTANCE)
         bi = np.zeros(len(scene.instances), dtype=abi.BLAS_INSTANCE)
         for k, (mesh, l2w, material) in enumerate(scene.instances):
@@ -140,7 +162,7 @@ class PathTracer:
                  samplesPerPass: int = 1, maxSamples: int = 100000, maxRayBounces: int = 4,
                  useRussianRoulette: bool = True, fireflyFilter: bool = False, maxFireflyLuminance: float = 10.0,
                  rank: int = 0, world_size: int = 1, reference_dispatch: bool = False, schedule: int = None,
-                 build_device: int = None, track_noise: bool = False):
+                 build_device: int = None, track_noise: bool = False, node_capacity=None):
         self.lib = plugin.load_library()
         self.track_noise = track_noise          # OnRenderImage records every pass in the moments (PTAccumulateMoments)
         self.scene = scene
@@ -162,7 +184,8 @@ class PathTracer:
         plugin.check(self.lib.PTCreate(device, C.byref(ctx)))
         self.ctx = ctx
         self.device = device
-        self._bvhScene = BVHScene(scene, build_device=build_device)
+        self._bvhScene = BVHScene(scene, build_device=build_device, node_capacity=node_capacity)
+        self._builtCost = {}                    # per BLAS: sahCost after its last build or rebuild (update_geometry's rebuild_above)
         self._bvhScene.PrepareShader(self.ctx)
         if world_size > 1:
             plugin.check(self.lib.PTSetTileOwnership(self.ctx, rank, world_size))
@@ -729,29 +752,58 @@ class PathTracer:
         return nodes[:count.value * 64].copy(), idx
 
     # ---- geometry updates (include/ptmi_plugin.h Part 9)
-    def update_geometry(self, vertices, mesh: int = None, tri_attrs=None):
+    def _blas_offsets(self, mesh):
+        bvh = self._bvhScene
+        if bvh.gpu_instances is None:
+            return (0, 0, 0)
+        assert mesh is not None, "a HAS_TLAS scene needs the mesh index"
+        users = [i for i, inst in enumerate(self.scene.instances) if inst[0] == mesh]
+        if not users:
+            raise ValueError(f"mesh {mesh} has no instance in the scene: its BLAS cannot be named")
+        return tuple(int(bvh.gpu_instances[users[0]][f]) for f in ("bvhOffset", "triOffset", "triAttributeOffset"))
+
+    def rebuild_geometry(self, vertices, mesh: int = None, tri_attrs=None):
+        """PTRebuildGeometry / PTRebuildGeometryDevice: update_geometry's contract, but the BLAS gets a new tree (the device
+        builder's, built in place on the GPU) instead of a refit.  The tree must fit the BLAS's node span (node_capacity)."""
+        self.update_geometry(vertices, mesh=mesh, tri_attrs=tri_attrs, _rebuild=True)
+        self._builtCost[mesh] = self.geometry_quality(mesh)["sahCost"]
+
+    def geometry_quality(self, mesh: int = None) -> dict:
+        """PTMeasureGeometry: nodeCapacity, nodeCount, triangleCount, levels, rootHalfArea and sahCost of the BLAS's current tree.
+        Synchronising."""
+        q = abi.geometry_quality()
+        plugin.check(self.lib.PTMeasureGeometry(self.ctx, *self._blas_offsets(mesh), C.byref(q)))
+        return q.as_dict()
+
+    def update_geometry(self, vertices, mesh: int = None, tri_attrs=None, rebuild_above: float = None, _rebuild: bool = False):
         """PTUpdateGeometry: new positions for one BLAS, refitted in place on the GPU.  vertices: (3 * triangles, 4) float32 in
         the BLAS's primitive order (numpy), or a torch tensor on this context's device (PTUpdateGeometryDevice, ordered after
         torch's current stream; tri_attrs then is a device tensor too).  tri_attrs (optional): the BLAS's abi.TRI_ATTR records.
         Flat scene: mesh stays None.  HAS_TLAS scene: mesh indexes scene.mesh_ranges; the vertices are in the mesh's local space,
         and the world bounds of the mesh's instances are recomputed (scenes.instance_world_bounds) and sent through
         PTUpdateInstances -- the library does not touch the TLAS (with device tensors that is left to the caller).  Does not
-        reset accumulation."""
+        reset accumulation.
+        rebuild_above (a ratio, no default): the refit is followed by PTMeasureGeometry; if sahCost exceeds rebuild_above x the cost
+        recorded after the BLAS's last build or rebuild, the same vertices go through PTRebuildGeometry.  Returns "refit" or
+        "rebuild" then, None otherwise."""
         bvh = self._bvhScene
-        off = (0, 0, 0)
-        if bvh.gpu_instances is not None:
-            assert mesh is not None, "a HAS_TLAS scene needs the mesh index"
-            users = [i for i, inst in enumerate(self.scene.instances) if inst[0] == mesh]
-            if not users:
-                raise ValueError(f"mesh {mesh} has no instance in the scene: its BLAS cannot be named")
-            k = users[0]
-            off = tuple(int(bvh.gpu_instances[k][f]) for f in ("bvhOffset", "triOffset", "triAttributeOffset"))
+        off = self._blas_offsets(mesh)
+        if rebuild_above is not None:
+            if mesh not in self._builtCost:     # the tree as built: measured on the host from the arrays PTSetScene was given
+                n0, cap, t0, nt = bvh.blas_spans[0 if mesh is None else mesh]
+                self._builtCost[mesh] = plugin.measure_cwbvh((bvh.bvh_nodes[n0 * 80:(n0 + cap) * 80], bvh.bvh_tris[t0 * 16:t0 * 16 + nt * 48]), nt)["sahCost"]
+            self.update_geometry(vertices, mesh=mesh, tri_attrs=tri_attrs)
+            if self.geometry_quality(mesh)["sahCost"] <= rebuild_above * self._builtCost[mesh]:
+                return "refit"
+            self.rebuild_geometry(vertices, mesh=mesh)         # the attributes were replaced by the refit above
+            return "rebuild"
+        fn_host, fn_device = (self.lib.PTRebuildGeometry, self.lib.PTRebuildGeometryDevice) if _rebuild else (self.lib.PTUpdateGeometry, self.lib.PTUpdateGeometryDevice)
         if isinstance(vertices, np.ndarray):
             v = np.ascontiguousarray(vertices, dtype=np.float32)
             assert v.ndim == 2 and v.shape[1] == 4 and v.shape[0] % 3 == 0
             a = None if tri_attrs is None else np.ascontiguousarray(tri_attrs)
             assert a is None or a.nbytes == v.shape[0] // 3 * 128
-            plugin.check(self.lib.PTUpdateGeometry(self.ctx, *off, v.ctypes.data, v.shape[0] // 3, None if a is None else a.ctypes.data))
+            plugin.check(fn_host(self.ctx, *off, v.ctypes.data, v.shape[0] // 3, None if a is None else a.ctypes.data))
         else:
             import torch
             assert vertices.is_contiguous() and vertices.dtype == torch.float32 and vertices.numel() % 12 == 0
@@ -759,8 +811,7 @@ class PathTracer:
             cur = torch.cuda.current_stream(vertices.device)
             ext = torch.cuda.ExternalStream(self.stream(), device=vertices.device)
             ext.wait_stream(cur)
-            plugin.check(self.lib.PTUpdateGeometryDevice(self.ctx, *off, vertices.data_ptr(), vertices.numel() // 12,
-                                                         None if tri_attrs is None else tri_attrs.data_ptr()))
+            plugin.check(fn_device(self.ctx, *off, vertices.data_ptr(), vertices.numel() // 12, None if tri_attrs is None else tri_attrs.data_ptr()))
             cur.wait_stream(ext)
             if bvh.gpu_instances is not None:
                 import warnings

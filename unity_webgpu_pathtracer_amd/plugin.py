@@ -97,6 +97,11 @@ sig = {
     "PTUpdateGeometry": (i32, [vp, C.c_int32, C.c_int32, C.c_int32, vp, i32, vp]),
     "PTUpdateGeometryDevice": (i32, [vp, C.c_int32, C.c_int32, C.c_int32, vp, i32, vp]),
     "PTReadGeometry": (i32, [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64]),
+    # Part 10 (geometry rebuilds and tree quality)
+    "PTRebuildGeometry": (i32, [vp, C.c_int32, C.c_int32, C.c_int32, vp, i32, vp]),
+    "PTRebuildGeometryDevice": (i32, [vp, C.c_int32, C.c_int32, C.c_int32, vp, i32, vp]),
+    "PTMeasureGeometry": (i32, [vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(abi.PTGeometryQuality)]),
+    "PTMeasureBVHArrays": (i32, [vp, C.c_uint64, vp, C.c_uint64, i32, C.POINTER(abi.PTGeometryQuality)]),
     "PTGetLastError": (C.c_char_p, []), "PTGetVersion": (i32, []),
 }
 EXPORTED_SYMBOLS = list(sig)
@@ -272,6 +277,18 @@ def refit_cwbvh(handle_or_arrays, vertices: np.ndarray):
     if not lib.PTRefitBVHArrays(nodes.ctypes.data, nodes.nbytes, tris.ctypes.data, tris.nbytes, v.ctypes.data, v.shape[0] // 3):
         raise PluginError(abi.PT_ERR_INVALID_ARG, "PTRefitBVHArrays failed: " + lib.PTGetBVHBuildError().decode())
     return nodes, tris
+
+
+def measure_cwbvh(arrays, triangle_count: int) -> dict:
+    """Tree quality on the host (PTMeasureBVHArrays, include/ptmi_plugin.h Part 10): arrays = (nodes uint8[], tris uint8[]) as
+    build_cwbvh returns them (zero nodes may be appended).  Returns nodeCapacity, nodeCount, triangleCount, levels, rootHalfArea
+    and sahCost; raises PluginError for anything that is not a CWBVH of triangle_count triangles."""
+    nodes, tris = (np.ascontiguousarray(np.asarray(a).view(np.uint8).reshape(-1)) for a in arrays)
+    lib = load_library()
+    q = abi.geometry_quality()
+    if not lib.PTMeasureBVHArrays(nodes.ctypes.data, nodes.nbytes, tris.ctypes.data, tris.nbytes, int(triangle_count), C.byref(q)):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTMeasureBVHArrays failed: " + lib.PTGetBVHBuildError().decode())
+    return q.as_dict()
 
 
 def build_tlas(instances: np.ndarray):
