@@ -874,6 +874,75 @@ PT_API int PTMeasureGeometry(PTContext* ctx, int32_t bvhOffset, int32_t triOffse
 PT_API int PTMeasureBVHArrays(const PTFloat4* bvhNodes, uint64_t nodeBytes, const PTFloat4* bvhTris, uint64_t triBytes, int triangleCount,
                               PTGeometryQuality* out);                                                    /* host twin, no GPU */
 
+/* =====================================================================================================================
+ * Part 11: skinned geometry.  Parts 9 and 10 take a deforming mesh once its new vertices exist; this part makes them, on the
+ * GPU, from what a skinned character changes per frame: a joint palette (48 bytes per joint).  PTSetSkin uploads the rest pose,
+ * the joint indices and the weights of one BLAS once; PTSkinGeometry then takes a palette, skins the vertices into a buffer the
+ * context owns and runs exactly the refit (Part 9) or rebuild (Part 10) the ...Device variants run on them.  No vertex is
+ * uploaded per frame and none is read back: the one number the host then lacks, the mesh's local box, is returned.
+ *
+ * The rule (skin_rule.h; bit-defined under DESIGN.md 3: one IEEE binary32 operation per operator, left to right, no
+ * contraction).  The palette is jointCount x 12 floats: the three rows of the 3x4 matrix M[j] that takes rest space to the BLAS's
+ * local space (joint world x inverse bind).  For a vertex with joints j0 ... j3 and weights w0 ... w3, each of the 12 elements of
+ * its blend matrix is  B = ((w0*M[j0] + w1*M[j1]) + w2*M[j2]) + w3*M[j3]  -- all four terms always, a zero weight is not
+ * skipped, the weights are used as given (not renormalised).  Position, per row r:  ((B[r][0]*x + B[r][1]*y) + B[r][2]*z) +
+ * B[r][3]; the output w is 0.  Normals and tangents, per corner:  v' = B3 * v (the rows without the translation), then
+ * v' * (1 / sqrt(dot(v', v')));  if dot is 0 or not finite the REST vector is kept.  B3 itself transforms the normals: the rule
+ * assumes joints without non-uniform scale (a sheared normal would need the inverse transpose).  The pads, uv0, uv1, uv2 and
+ * materialIndex of a record are copied from restAttrs.  Bounds: compare-and-select min and max over the 3 * T positions.
+ *
+ * PTSetSkin.  The BLAS is named and checked as in Part 9 (the three offsets, triangleCount).  restVertices: 3 * T PTFloat4 in the
+ * BLAS's primitive order (PTUpdateGeometry's input layout, w ignored); joints: 3 * T x 4 uint16; weights: 3 * T x 4 float;
+ * restAttrs: T records, or NULL (the attribute records then are never touched).  Checked once, on the host: 1 <= jointCount <=
+ * PT_SKIN_MAX_JOINTS, every joint index < jointCount, weights and rest vertices finite, and without HAS_TLAS every
+ * materialIndex < materialCount -- the kernels then index the palette and the materials with nothing else.  The arrays are
+ * copied before the call returns and stay on the device: 40 bytes per vertex, plus 128 bytes per triangle with restAttrs.  A
+ * second call for the same BLAS replaces its skin, a NULL desc removes it (both wait for the update stream); PTSetScene
+ * discards every skin, PTDestroy frees them.
+ *
+ * PTSkinGeometry (palette in host memory, copied before return; non-finite matrices are refused) and PTSkinGeometryDevice
+ * (palette in device memory, 16-byte aligned, read in the context stream's order; not inspected: non-finite matrices give an
+ * unspecified but memory-safe tree on a refit, and the builder's finiteness flag refuses them on a rebuild).  flags: 0 = refit,
+ * PT_SKIN_REBUILD = Part 10's rebuild with its capacity rule and refusals.  On the update stream, in this order: the palette
+ * upload, the skin kernel, the attribute records straight into the target attribute generation (a skin with restAttrs), then
+ * the refit or the rebuild.  Generations, carry-over, ordering against passes in flight, "accumulation is not reset" and "a
+ * refused call leaves the scene as it was" are Part 9's and Part 10's.  outBounds (may be NULL): min.xyz then max.xyz of the
+ * skinned vertices, a 24-byte read-back -- the call then synchronises with the update stream only (as a rebuild always does);
+ * with NULL a refit does not synchronise.  On a HAS_TLAS scene these are the local bounds whose transformed corners the caller
+ * sends through PTUpdateInstances.
+ * Errors: PT_ERR_NO_SCENE before PTSetScene; PT_ERR_INVALID_ARG for a NULL context or array, a BLAS without a skin, a jointCount
+ * that is not the skin's, a refused array.
+ *
+ * PTSkinVerticesHost is the host twin (no GPU): the same rule on the host, byte for byte.  outAttrs needs desc->restAttrs;
+ * outAttrs and outBounds may be NULL.  It makes PTSetSkin's checks (no material count) and refuses non-finite matrices; returns
+ * 1, or 0 with PTGetBVHBuildError() set.
+ * ===================================================================================================================== */
+#define PT_SKIN_MAX_JOINTS 1024u
+#define PT_SKIN_REBUILD    0x1u
+
+typedef struct PTSkinDesc {
+    uint32_t        structSize;   /* sizeof(PTSkinDesc) of the caller's header; members are only appended */
+    uint32_t        jointCount;   /* 1 ... PT_SKIN_MAX_JOINTS */
+    const PTFloat4* restVertices; /* 3 * triangleCount */
+    const uint16_t* joints;       /* 3 * triangleCount x 4 */
+    const float*    weights;      /* 3 * triangleCount x 4 */
+    const PTTriangleAttributes* restAttrs;   /* triangleCount, or NULL */
+} PTSkinDesc;
+
+#ifdef __cplusplus
+static_assert(sizeof(PTSkinDesc) == 40, "PTSkinDesc is 40 bytes");
+#else
+_Static_assert(sizeof(PTSkinDesc) == 40, "PTSkinDesc is 40 bytes");
+#endif
+
+PT_API int PTSetSkin(PTContext* ctx, int32_t bvhOffset, int32_t triOffset, int32_t triAttributeOffset, int triangleCount, const PTSkinDesc* descOrNull);
+PT_API int PTSkinGeometry(PTContext* ctx, int32_t bvhOffset, int32_t triOffset, int32_t triAttributeOffset, const float* jointMatrices,
+                          uint32_t jointCount, uint32_t flags, float* outBounds);                         /* host palette, copied before return */
+PT_API int PTSkinGeometryDevice(PTContext* ctx, int32_t bvhOffset, int32_t triOffset, int32_t triAttributeOffset, const float* dJointMatrices,
+                                uint32_t jointCount, uint32_t flags, float* outBounds);                   /* device palette, read in stream order */
+PT_API int PTSkinVerticesHost(const PTSkinDesc* desc, int triangleCount, const float* jointMatrices, PTFloat4* outVertices,
+                              PTTriangleAttributes* outAttrsOrNull, float* outBoundsOrNull);               /* host twin, no GPU */
+
 /* Text of the last error on the calling thread ("" if none). */
 PT_API const char* PTGetLastError(void);
 /* Library/ABI version: (major << 16) | minor. */

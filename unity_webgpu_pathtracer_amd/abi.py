@@ -295,6 +295,28 @@ def geometry_quality() -> PTGeometryQuality:
     return q
 
 
+# ---------------------------------------------------------------------------------------
+# Part 11: skinned geometry (PTSetSkin / PTSkinGeometry / PTSkinVerticesHost)
+# ---------------------------------------------------------------------------------------
+PT_SKIN_MAX_JOINTS = 1024
+PT_SKIN_REBUILD = 0x1
+
+
+class PTSkinDesc(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("jointCount", C.c_uint32), ("restVertices", C.c_void_p), ("joints", C.c_void_p),
+                ("weights", C.c_void_p), ("restAttrs", C.c_void_p)]
+
+
+assert C.sizeof(PTSkinDesc) == 40
+
+
+def skin_desc() -> PTSkinDesc:
+    """An empty PTSkinDesc with structSize set."""
+    d = PTSkinDesc()
+    d.structSize = C.sizeof(PTSkinDesc)
+    return d
+
+
 def as_void_p(arr):
     """Borrowed host pointer of a C-contiguous numpy array (None -> NULL)."""
     if arr is None:

@@ -12,6 +12,7 @@
 #include "bvh_builder.h"
 #include "bvh_refit.h"
 #include "bvh_quality.h"
+#include "skin_rule.h"
 #include "ptmi_plugin.h"
 
 namespace {
@@ -101,6 +102,22 @@ PT_API int PTMeasureBVHArrays(const PTFloat4* bvhNodes, uint64_t nodeBytes, cons
     out->nodeCapacity = q.nodeCapacity; out->nodeCount = q.nodeCount; out->triangleCount = q.triangleCount; out->levels = q.levels;
     out->reserved = 0;
     out->rootHalfArea = q.rootHalfArea; out->sahCost = q.sahCost;
+    g_buildError.clear();
+    return 1;
+}
+// Linear-blend skinning on the host (skin_host.cpp; Part 11 has the rule).  No GPU involved.
+PT_API int PTSkinVerticesHost(const PTSkinDesc* desc, int triangleCount, const float* jointMatrices, PTFloat4* outVertices,
+                              PTTriangleAttributes* outAttrsOrNull, float* outBoundsOrNull)
+{
+    if (!desc || !jointMatrices || !outVertices || triangleCount <= 0) { g_buildError = "NULL desc, matrices or result, or triangleCount <= 0"; return 0; }
+    if (desc->structSize < sizeof(PTSkinDesc) || desc->structSize > 4096u) {
+        g_buildError = "PTSkinDesc.structSize is not set (must be sizeof(PTSkinDesc) of the host's header)";
+        return 0;
+    }
+    if (outAttrsOrNull && !desc->restAttrs) { g_buildError = "outAttrs needs PTSkinDesc.restAttrs"; return 0; }
+    if (!ptskin::skin_check(*desc, (uint32_t)triangleCount, 0xFFFFFFFFu, g_buildError)) return 0;
+    if (!ptskin::skin_check_palette(jointMatrices, desc->jointCount, g_buildError)) return 0;
+    ptskin::skin_host(*desc, (uint32_t)triangleCount, jointMatrices, outVertices, outAttrsOrNull, outBoundsOrNull);
     g_buildError.clear();
     return 1;
 }

@@ -1,6 +1,7 @@
 // pt_api_geometry.hip — geometry updates and PTReadGeometry (include/ptmi_plugin.h Part 9); geometry rebuilds and
-// the tree-quality measure (Part 10).
+// the tree-quality measure (Part 10); skinned geometry (Part 11).
 #include "pt_context.h"
+#include "skin_rule.h"
 
 #include <cmath>
 
@@ -123,21 +124,41 @@ int rebuild_blas(PTContext* c, PTContext::GeomPlan& plan, char* dNodes, char* dT
     return PT_OK;
 }
 
+// PTSkinGeometry's vertex source: the BLAS's skin (PTSetSkin) and a joint palette instead of the caller's vertices
+struct SkinSource {
+    const float* palette;
+    uint32_t jointCount;
+    bool onDevice;
+    float* outBounds;
+};
+
+// Every geometry update: the vertices are the caller's (host arrays staged, or device arrays), or with `skin` those the skin kernel
+// makes from the BLAS's skin and the palette (verts, triangleCount and attrs then are unused: the skin has them).
 int update_geometry(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t attrOffset, const PTFloat4* verts, int triangleCount,
-                    const PTTriangleAttributes* attrs, bool onDevice, bool rebuild)
+                    const PTTriangleAttributes* attrs, bool onDevice, bool rebuild, const SkinSource* skin = nullptr)
 {
     if (!c) return fail(PT_ERR_INVALID_ARG, "ctx == NULL");
-    if (!verts) return fail(PT_ERR_INVALID_ARG, "vertices == NULL");
+    if (!skin && !verts) return fail(PT_ERR_INVALID_ARG, "vertices == NULL");
+    if (skin && !skin->palette) return fail(PT_ERR_INVALID_ARG, "jointMatrices == NULL");
     if (!c->hasScene) return fail(PT_ERR_NO_SCENE, "PTSetScene has not been called");
-    if (triangleCount <= 0 || bvhOffset < 0 || triOffset < 0 || attrOffset < 0) return fail(PT_ERR_INVALID_ARG, "triangleCount <= 0 or a negative offset");
-    const uint32_t triCount = (uint32_t)triangleCount;
+    if ((!skin && triangleCount <= 0) || bvhOffset < 0 || triOffset < 0 || attrOffset < 0) return fail(PT_ERR_INVALID_ARG, "triangleCount <= 0 or a negative offset");
     HIP_TRY(hipSetDevice(c->device));
     int rc;
     if ((rc = ensure_host_copy(c))) return rc;
     PTContext::GeomPlan* plan = nullptr;
-    if ((rc = find_plan(c, bvhOffset, triOffset, attrOffset, triCount, plan))) return rc;
+    if ((rc = find_plan(c, bvhOffset, triOffset, attrOffset, skin ? 0u : (uint32_t)triangleCount, plan))) return rc;
+    const uint32_t triCount = plan->triCount;
     const bool flat = !c->scene.hasTlas;                             // a flat scene's kernels index the materials with the records' materialIndex
-    if (!onDevice) {
+    const bool staged = !skin && !onDevice;                          // host arrays go through the groups' pinned staging
+    if (skin) {
+        const PTContext::GeomPlan::Skin& K = plan->skin;
+        if (!K.jointCount) return fail(PT_ERR_INVALID_ARG, "the BLAS has no skin (PTSetSkin)");
+        if (skin->jointCount != K.jointCount)
+            return fail(PT_ERR_INVALID_ARG, "jointCount (" + std::to_string(skin->jointCount) + ") != the skin's (" + std::to_string(K.jointCount) + ")");
+        std::string why;
+        if (!skin->onDevice && !ptskin::skin_check_palette(skin->palette, K.jointCount, why)) return fail(PT_ERR_INVALID_ARG, why);
+        if (skin->onDevice && ((uintptr_t)skin->palette & 15u)) return fail(PT_ERR_INVALID_ARG, "dJointMatrices is not 16-byte aligned");
+    } else if (!onDevice) {
         for (size_t i = 0; i < (size_t)triCount * 3; ++i)
             if (!std::isfinite(verts[i].x) || !std::isfinite(verts[i].y) || !std::isfinite(verts[i].z))
                 return fail(PT_ERR_INVALID_ARG, "vertex " + std::to_string(i) + " is not finite");
@@ -145,31 +166,64 @@ int update_geometry(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t 
             if (attrs[i].materialIndex >= c->scene.materialCount)
                 return fail(PT_ERR_INVALID_ARG, "triangle " + std::to_string(i) + ": materialIndex " + std::to_string(attrs[i].materialIndex) + " >= materialCount");
     }
+    const bool writeAttrs = skin ? plan->skin.restAttrs.ptr != nullptr : attrs != nullptr;
     PTContext::Update& u = c->update;
     PTContext::Geometry& G = u.geometry;
     const size_t nodeBytes = c->nodes.used, triBytes = c->tris.used, attrBytes = c->attrs.used;
     // staging is sized for the scene, not for the call: the groups never reallocate between updates (begin_update)
     int tg = 0, ta = 0;
-    if ((rc = begin_update(c, u.geom, al256(nodeBytes) + triBytes, onDevice ? 0 : triBytes, tg))) return rc;
-    if (attrs && (rc = begin_update(c, u.attrs, attrBytes, onDevice ? 0 : attrBytes, ta))) return rc;
+    if ((rc = begin_update(c, u.geom, al256(nodeBytes) + triBytes, staged ? triBytes : 0, tg))) return rc;
+    if (writeAttrs && (rc = begin_update(c, u.attrs, attrBytes, staged ? attrBytes : 0, ta))) return rc;
     // carry-over: the target generation is two updates old; everything this update does not rewrite comes from the current one
     char* dNodes = (char*)u.geom.gen[tg].ptr;
     char* dTris = dNodes + al256(nodeBytes);
     HIP_TRY(hipMemcpyAsync(dNodes, c->scene.nodes, nodeBytes, hipMemcpyDeviceToDevice, u.stream));
     HIP_TRY(hipMemcpyAsync(dTris, c->scene.tris, triBytes, hipMemcpyDeviceToDevice, u.stream));
+    PTSkinArgs S = {};
+    char* dAttrs = nullptr;
+    // the BLAS's attribute records of the target generation: the carry-over copy, then the new records
+    auto write_attrs = [&]() -> int {
+        dAttrs = (char*)u.attrs.gen[ta].ptr;
+        char* dst = dAttrs + (size_t)attrOffset * 128;
+        HIP_TRY(hipMemcpyAsync(dAttrs, c->scene.attrs, attrBytes, hipMemcpyDeviceToDevice, u.stream));
+        if (skin) HIP_TRY(pt_launch_skin_attrs(S, (float4*)dst, u.stream));          // each record once, no staging copy
+        else if (onDevice) HIP_TRY(pt_launch_refit_attrs((float4*)dst, (const float4*)attrs, triCount, flat ? c->scene.materialCount : 0xFFFFFFFFu, u.stream));
+        else if (int e = stage_host(c, u.attrs, ta, attrs, (size_t)triCount * 128, dst)) return e;
+        return PT_OK;
+    };
     const float4* dVerts = (const float4*)verts;
-    if (onDevice) {
+    if (onDevice || (skin && skin->onDevice)) {
         HIP_TRY(hipEventRecord(u.input, c->stream));
         HIP_TRY(hipStreamWaitEvent(u.stream, u.input, 0));
-    } else {
-        // 48 B per triangle, as the records: room for the largest BLAS, so that it is allocated once (first host update)
-        if (!G.verts.ptr && (rc = G.verts.reserve(triBytes))) return rc;
+    }
+    // 48 B per triangle, as the records: room for the largest BLAS, so that it is allocated once (first host update or skin)
+    if ((staged || skin) && !G.verts.ptr && (rc = G.verts.reserve(triBytes))) return rc;
+    if (skin) {
+        const PTContext::GeomPlan::Skin& K = plan->skin;
+        S.rest = (const float4*)K.rest.ptr; S.joints = (const uint2*)K.joints.ptr; S.weights = (const float4*)K.weights.ptr;
+        S.restAttrs = (const float4*)K.restAttrs.ptr;
+        S.triCount = triCount;
+        S.palette = (const float4*)skin->palette;
+        if (!skin->onDevice) {
+            if ((rc = G.palette.send(skin->palette, (size_t)K.jointCount * 48, u.stream))) return rc;
+            S.palette = (const float4*)G.palette.dev.ptr;
+        }
+        // grown only for a larger BLAS; the folds that used the old array ran on the update stream
+        if ((rc = G.skinWork.reserve(pt_skin_work_floats(triCount) * sizeof(float), u.stream))) return rc;
+        HIP_TRY(pt_launch_skin_vertices(S, (float4*)G.verts.ptr, (float*)G.skinWork.ptr, u.stream));
+        if (skin->outBounds) {
+            if ((rc = G.skinBounds.reserve(6 * sizeof(float)))) return rc;
+            HIP_TRY(hipMemcpyAsync(G.skinBounds.ptr, G.skinWork.ptr, 6 * sizeof(float), hipMemcpyDeviceToHost, u.stream));
+        }
+        dVerts = (const float4*)G.verts.ptr;
+        if (writeAttrs && (rc = write_attrs())) return rc;
+    } else if (staged) {
         if ((rc = stage_host(c, u.geom, tg, verts, (size_t)triCount * 48, G.verts.ptr))) return rc;
         dVerts = (const float4*)G.verts.ptr;
     }
     if (rebuild) {
         // a refusal leaves the scene as it was: the generation being written is not current, and nothing below has run
-        if ((rc = rebuild_blas(c, *plan, dNodes, dTris, dVerts, onDevice))) return rc;
+        if ((rc = rebuild_blas(c, *plan, dNodes, dTris, dVerts, onDevice || skin != nullptr))) return rc;
     } else {
     PTRefitArgs A;
     A.nodes = (uint4*)dNodes;
@@ -180,21 +234,55 @@ int update_geometry(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t 
     A.nodeOff = (uint32_t)bvhOffset; A.triOff = (uint32_t)triOffset; A.triCount = triCount;
     HIP_TRY(pt_launch_refit(A, plan->levelStart.data(), (uint32_t)plan->levelStart.size() - 1u, u.stream, nullptr));
     }
-    char* dAttrs = nullptr;
-    if (attrs) {
-        dAttrs = (char*)u.attrs.gen[ta].ptr;
-        char* dst = dAttrs + (size_t)attrOffset * 128;
-        HIP_TRY(hipMemcpyAsync(dAttrs, c->scene.attrs, attrBytes, hipMemcpyDeviceToDevice, u.stream));
-        if (onDevice) HIP_TRY(pt_launch_refit_attrs((float4*)dst, (const float4*)attrs, triCount, flat ? c->scene.materialCount : 0xFFFFFFFFu, u.stream));
-        else if ((rc = stage_host(c, u.attrs, ta, attrs, (size_t)triCount * 128, dst))) return rc;
+    if (skin && skin->outBounds) {
+        // 24 bytes: synchronises with the update stream only, not with the passes in flight
+        HIP_TRY(hipStreamSynchronize(u.stream));
+        memcpy(skin->outBounds, G.skinBounds.ptr, 6 * sizeof(float));
     }
+    if (!skin && writeAttrs && (rc = write_attrs())) return rc;
     if ((rc = end_update(c, u.geom, tg))) return rc;
     c->scene.nodes = (const uint4*)dNodes;
     c->scene.tris = (const float4*)dTris;
-    if (attrs) {
+    if (writeAttrs) {
         if ((rc = end_update(c, u.attrs, ta))) return rc;
         c->scene.attrs = (const float4*)dAttrs;
     }
+    return PT_OK;
+}
+
+// PTSetSkin: the desc's arrays onto the device, replacing the BLAS's skin; desc == NULL removes it
+int set_skin(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t attrOffset, int triangleCount, const PTSkinDesc* hostDesc)
+{
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx == NULL");
+    if (!c->hasScene) return fail(PT_ERR_NO_SCENE, "PTSetScene has not been called");
+    if (triangleCount <= 0 || bvhOffset < 0 || triOffset < 0 || attrOffset < 0) return fail(PT_ERR_INVALID_ARG, "triangleCount <= 0 or a negative offset");
+    PTSkinDesc d;
+    if (hostDesc)
+        if (int rc = import_struct(hostDesc, d, sizeof(PTSkinDesc), "PTSkinDesc", "desc == NULL")) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure_host_copy(c))) return rc;
+    PTContext::GeomPlan* plan = nullptr;
+    if ((rc = find_plan(c, bvhOffset, triOffset, attrOffset, (uint32_t)triangleCount, plan))) return rc;
+    const uint32_t triCount = plan->triCount;
+    std::string why;
+    if (hostDesc && !ptskin::skin_check(d, triCount, c->scene.hasTlas ? 0xFFFFFFFFu : c->scene.materialCount, why)) return fail(PT_ERR_INVALID_ARG, why);
+    // skin kernels enqueued so far read the arrays replaced or freed below
+    if (c->update.stream) HIP_TRY(hipStreamSynchronize(c->update.stream));
+    PTContext::GeomPlan::Skin K;
+    if (hostDesc) {
+        const size_t n = (size_t)triCount * 3u;
+        if ((rc = K.rest.reserve(n * 16)) || (rc = K.joints.reserve(n * 8)) || (rc = K.weights.reserve(n * 16))) return rc;
+        HIP_TRY(hipMemcpy(K.rest.ptr, d.restVertices, n * 16, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(K.joints.ptr, d.joints, n * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(K.weights.ptr, d.weights, n * 16, hipMemcpyHostToDevice));
+        if (d.restAttrs) {
+            if ((rc = K.restAttrs.reserve((size_t)triCount * 128))) return rc;
+            HIP_TRY(hipMemcpy(K.restAttrs.ptr, d.restAttrs, (size_t)triCount * 128, hipMemcpyHostToDevice));
+        }
+        K.jointCount = d.jointCount;
+    }
+    plan->skin = std::move(K);                                      // the old arrays are released with K
     return PT_OK;
 }
 
@@ -224,6 +312,27 @@ PT_API int PTRebuildGeometryDevice(PTContext* c, int32_t bvhOffset, int32_t triO
                                    int triangleCount, const PTTriangleAttributes* dAttrsOrNull)
 {
     return update_geometry(c, bvhOffset, triOffset, triAttributeOffset, dVertices, triangleCount, dAttrsOrNull, true, true);
+}
+
+PT_API int PTSetSkin(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t triAttributeOffset, int triangleCount, const PTSkinDesc* descOrNull)
+{
+    return set_skin(c, bvhOffset, triOffset, triAttributeOffset, triangleCount, descOrNull);
+}
+
+PT_API int PTSkinGeometry(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t triAttributeOffset, const float* jointMatrices,
+                          uint32_t jointCount, uint32_t flags, float* outBounds)
+{
+    if (flags & ~PT_SKIN_REBUILD) return fail(PT_ERR_INVALID_ARG, "unknown flags");
+    const SkinSource src = {jointMatrices, jointCount, false, outBounds};
+    return update_geometry(c, bvhOffset, triOffset, triAttributeOffset, nullptr, 0, nullptr, false, (flags & PT_SKIN_REBUILD) != 0, &src);
+}
+
+PT_API int PTSkinGeometryDevice(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t triAttributeOffset, const float* dJointMatrices,
+                                uint32_t jointCount, uint32_t flags, float* outBounds)
+{
+    if (flags & ~PT_SKIN_REBUILD) return fail(PT_ERR_INVALID_ARG, "unknown flags");
+    const SkinSource src = {dJointMatrices, jointCount, true, outBounds};
+    return update_geometry(c, bvhOffset, triOffset, triAttributeOffset, nullptr, 0, nullptr, false, (flags & PT_SKIN_REBUILD) != 0, &src);
 }
 
 PT_API int PTMeasureGeometry(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t triAttributeOffset, PTGeometryQuality* out)

@@ -5,6 +5,7 @@
 #include "pt_tlas.h"
 #include "pt_refit.h"
 #include "pt_quality.h"
+#include "pt_skin.h"
 #include "bvh_refit.h"
 #include "bvh_builder_gpu.h"
 
@@ -238,6 +239,11 @@ struct PTContext {
         uint32_t nodeCapacity = 0;                      // the BLAS's node span in PTSetScene's buffer
         DeviceBuffer order;                             // ptbvh::RefitPlan::order on the device
         std::vector<uint32_t> levelStart;
+        // PTSetSkin: the BLAS's skin on the device, 40 bytes per vertex (+ 128 per triangle with rest attributes); jointCount == 0: none
+        struct Skin {
+            uint32_t jointCount = 0;
+            DeviceBuffer rest, joints, weights, restAttrs;
+        } skin;
     };
     struct Geometry {
         std::vector<PTFloat4> hostNodes;                // host copy of the node buffer (rows n1 and imask are what is read)
@@ -245,9 +251,12 @@ struct PTContext {
         std::vector<int32_t> blasKeys;                  // HAS_TLAS: the three offsets of every instance (PTSetScene's records)
         std::vector<GeomPlan> plans;                    // one per BLAS updated so far
         DeviceBuffer nodeBox;                           // 24 B per node of the scene
-        DeviceBuffer verts;                             // the host variant's vertices on the device
+        DeviceBuffer verts;                             // the host variant's vertices on the device, or the skin kernel's
         DeviceBuffer buildWork;                         // the builder's work arrays, sized for the largest BLAS rebuilt so far
         DeviceBuffer qualityWork;                       // PTMeasureGeometry: results and per-workgroup partial sums
+        UploadTable palette;                            // PTSkinGeometry: the host palette, on the update stream
+        DeviceBuffer skinWork;                          // the skinned vertices' box and its per-workgroup partials
+        PinnedBuffer skinBounds;                        // ... read back (24 bytes)
     };
     struct Update {
         UpdGroup inst, lights, mats, geom, attrs;

@@ -335,6 +335,94 @@ def load_glb(path, unity_handedness=True, load_images=True, flip_axis=2, flip_v=
     return meshes, materials, images
 
 
+def load_glb_skins(path, unity_handedness=True, flip_axis=2):
+    """The skins of a .glb, as data: one entry per mesh primitive in load_glb's order (same arguments, same order), None for a
+    primitive of a node without a skin, else a dict:
+      joints        (3T, 4) uint16   JOINTS_0 expanded to the triangle soup of the primitive (through its indices, in the winding
+      weights       (3T, 4) float32  WEIGHTS_0 likewise                            load_glb gives it: vertex 3t + c = corner c of triangle t)
+      inverse_bind  (J, 4, 4) float64
+      parents       (J,) int32       each joint's parent among the skin's joints, -1 for a root
+      local         (J, 4, 4) float64  each joint's rest matrix relative to its parent (a root's includes its non-joint ancestors)
+    joint_matrices() turns them and a pose into PTSkinGeometry's palette.  As glTF defines skinning, the palette takes the
+    primitive's positions to the SCENE's space: the skinned node's own transform does not enter (use an identity local_to_world).
+    unity_handedness mirrors every matrix as load_glb mirrors the node transforms, M' = F M F, so that skinning the mirrored
+    positions with the mirrored palette is the mirror image of the right-handed result.
+    Not read: animations, morph targets, JOINTS_1 / WEIGHTS_1 (more than four influences)."""
+    with open(path, "rb") as f:
+        doc, blob = _glb_chunks(f.read())
+    if flip_axis not in (0, 1, 2):
+        raise ValueError("flip_axis must be 0, 1 or 2")
+    flip = np.eye(4)
+    if unity_handedness:
+        flip[flip_axis, flip_axis] = -1.0
+    nodes = doc.get("nodes", [])
+    world, parent_of, order = {}, {}, []
+
+    def visit(index, parent, parent_index):
+        world[index] = parent @ _node_matrix(nodes[index])
+        parent_of[index] = parent_index
+        order.append(index)
+        for child in nodes[index].get("children", []):
+            visit(child, world[index], index)
+
+    scene_nodes = doc["scenes"][doc.get("scene", 0)]["nodes"] if doc.get("scenes") else list(range(len(nodes)))
+    for n in scene_nodes:
+        visit(n, np.eye(4), -1)
+    out = []
+    for index in order:
+        node = nodes[index]
+        if "mesh" not in node:
+            continue
+        for prim in doc["meshes"][node["mesh"]]["primitives"]:
+            att = prim["attributes"]
+            if "skin" not in node or "JOINTS_0" not in att or "WEIGHTS_0" not in att:
+                out.append(None)
+                continue
+            count = doc["accessors"][att["POSITION"]]["count"]
+            idx = _accessor(doc, blob, prim["indices"]).reshape(-1).astype(np.int64) if "indices" in prim else np.arange(count)
+            if idx.size % 3 or (idx.size and int(idx.max()) >= count):
+                raise ValueError("index accessor does not describe triangles of this primitive")
+            if unity_handedness:
+                idx = idx.reshape(-1, 3)[:, ::-1].reshape(-1)
+            joints = _accessor(doc, blob, att["JOINTS_0"])
+            weights = _accessor(doc, blob, att["WEIGHTS_0"]).astype(np.float32)
+            skin = doc["skins"][node["skin"]]
+            jn = list(skin["joints"])
+            if len(joints) != count or len(weights) != count or (joints.size and int(joints.max()) >= len(jn)):
+                raise ValueError("JOINTS_0 / WEIGHTS_0 do not match the primitive or the skin")
+            ibm = (_accessor(doc, blob, skin["inverseBindMatrices"]).astype(np.float64).reshape(-1, 4, 4).transpose(0, 2, 1)
+                   if "inverseBindMatrices" in skin else np.tile(np.eye(4), (len(jn), 1, 1)))
+            parents = np.full(len(jn), -1, np.int32)
+            local = np.zeros((len(jn), 4, 4))
+            for j, n in enumerate(jn):
+                if n not in world:
+                    raise ValueError("a joint is not part of the scene")
+                p = parent_of[n]
+                while p >= 0 and p not in jn:
+                    p = parent_of[p]
+                parents[j] = jn.index(p) if p >= 0 else -1
+                local[j] = flip @ (np.linalg.inv(world[p]) @ world[n] if p >= 0 else world[n]) @ flip
+            out.append(dict(joints=np.ascontiguousarray(joints[idx].astype(np.uint16)), weights=np.ascontiguousarray(weights[idx]),
+                            inverse_bind=flip @ ibm @ flip, parents=parents, local=local))
+    return out
+
+
+def joint_matrices(skin, local_matrices=None):
+    """PTSkinGeometry's palette for one pose of a load_glb_skins skin: joint world x inverse bind, computed in float64, returned
+    as float32 (J, 3, 4).  local_matrices: (J, 4, 4), each joint's matrix relative to its parent; None = the rest pose."""
+    local = np.asarray(skin["local"] if local_matrices is None else local_matrices, np.float64)
+    parents = [int(p) for p in skin["parents"]]
+    world = [None] * len(parents)
+
+    def resolve(j):
+        if world[j] is None:
+            world[j] = local[j] if parents[j] < 0 else resolve(parents[j]) @ local[j]
+        return world[j]
+
+    m = np.stack([resolve(j) @ np.asarray(skin["inverse_bind"][j], np.float64) for j in range(len(parents))])
+    return np.ascontiguousarray(m[:, :3, :], np.float32)
+
+
 def pack_gltf_materials(materials, image_to_texture=None):
     """glTF material dicts (load_glb) -> (M, 32) MaterialData rows with the packing rules of BVHScene.cs:236-282.  glTF factors are
     linear while BVHScene applies pow(c, 2.2) to a Unity (gamma) colour, so the factor goes in as c^(1/2.2).  image_to_texture
@@ -351,9 +439,12 @@ def pack_gltf_materials(materials, image_to_texture=None):
     return np.stack(rows) if rows else np.stack([scenes.pack_material()])
 
 
-def write_glb(path, meshes, materials=None, node_matrices=None, interleave=False):
+def write_glb(path, meshes, materials=None, node_matrices=None, interleave=False, skins=None):
     """A small GLB writer for tests: one node + mesh + primitive per `Mesh` (positions, optional normals / uvs, optional indices),
-    float32 attributes, optionally interleaved into one strided bufferView; `node_matrices` (4x4 each) become node matrices."""
+    float32 attributes, optionally interleaved into one strided bufferView; `node_matrices` (4x4 each) become node matrices.
+    skins (optional): one entry per mesh, None or a dict as load_glb_skins returns it, with joints / weights per VERTEX of
+    mesh.positions -- written as JOINTS_0 (uint16) / WEIGHTS_0 (float32), one node per joint (its rest local matrix) and a skin
+    with the inverse bind matrices.  With skins=None the bytes are what they were before the argument existed."""
     import json
     import struct
     blob, views, accessors, gl_meshes, nodes = bytearray(), [], [], [], []
@@ -392,6 +483,12 @@ def write_glb(path, meshes, materials=None, node_matrices=None, interleave=False
                     acc["min"], acc["max"] = arr.min(axis=0).tolist(), arr.max(axis=0).tolist()
                 accessors.append(acc)
                 att[name] = len(accessors) - 1
+        skin = skins[k] if skins is not None else None
+        if skin is not None:
+            for name, arr, ct in (("JOINTS_0", np.ascontiguousarray(skin["joints"], np.uint16), 5123), ("WEIGHTS_0", np.ascontiguousarray(skin["weights"], np.float32), 5126)):
+                assert arr.shape == (len(m.positions), 4), name
+                accessors.append({"bufferView": add_view(arr.tobytes()), "componentType": ct, "count": len(arr), "type": "VEC4"})
+                att[name] = len(accessors) - 1
         prim = {"attributes": att, "material": int(m.material_index)}
         if m.indices is not None:
             idx = np.ascontiguousarray(m.indices)
@@ -403,8 +500,28 @@ def write_glb(path, meshes, materials=None, node_matrices=None, interleave=False
         if node_matrices is not None:
             node["matrix"] = np.asarray(node_matrices[k], np.float64).T.reshape(16).tolist()
         nodes.append(node)
-    doc = {"asset": {"version": "2.0"}, "scene": 0, "scenes": [{"nodes": list(range(len(nodes)))}], "nodes": nodes, "meshes": gl_meshes,
+    roots = list(range(len(nodes)))
+    gl_skins = []
+    for k, skin in enumerate(skins or []):
+        if skin is None:
+            continue
+        parents = [int(p) for p in skin["parents"]]
+        first = len(nodes)
+        for j, local in enumerate(skin["local"]):
+            node = {"name": f"joint{k}_{j}", "matrix": np.asarray(local, np.float64).T.reshape(16).tolist()}
+            kids = [first + c for c, p in enumerate(parents) if p == j]
+            if kids:
+                node["children"] = kids
+            nodes.append(node)
+        roots += [first + j for j, p in enumerate(parents) if p < 0]
+        ibm = np.ascontiguousarray(np.asarray(skin["inverse_bind"], np.float32).transpose(0, 2, 1))      # column-major
+        accessors.append({"bufferView": add_view(ibm.tobytes()), "componentType": 5126, "count": len(ibm), "type": "MAT4"})
+        gl_skins.append({"joints": list(range(first, first + len(parents))), "inverseBindMatrices": len(accessors) - 1})
+        nodes[k]["skin"] = len(gl_skins) - 1
+    doc = {"asset": {"version": "2.0"}, "scene": 0, "scenes": [{"nodes": roots}], "nodes": nodes, "meshes": gl_meshes,
            "accessors": accessors, "bufferViews": views, "buffers": [{"byteLength": len(blob)}]}
+    if gl_skins:
+        doc["skins"] = gl_skins
     if materials:
         doc["materials"] = materials
     js = json.dumps(doc).encode("utf-8")

@@ -762,6 +762,14 @@ class PathTracer:
             raise ValueError(f"mesh {mesh} has no instance in the scene: its BLAS cannot be named")
         return tuple(int(bvh.gpu_instances[users[0]][f]) for f in ("bvhOffset", "triOffset", "triAttributeOffset"))
 
+    def _built_cost(self, mesh):
+        """sahCost after the BLAS's last build or rebuild; the tree as built is measured on the host from the arrays PTSetScene was given"""
+        if mesh not in self._builtCost:
+            bvh = self._bvhScene
+            n0, cap, t0, nt = bvh.blas_spans[0 if mesh is None else mesh]
+            self._builtCost[mesh] = plugin.measure_cwbvh((bvh.bvh_nodes[n0 * 80:(n0 + cap) * 80], bvh.bvh_tris[t0 * 16:t0 * 16 + nt * 48]), nt)["sahCost"]
+        return self._builtCost[mesh]
+
     def rebuild_geometry(self, vertices, mesh: int = None, tri_attrs=None):
         """PTRebuildGeometry / PTRebuildGeometryDevice: update_geometry's contract, but the BLAS gets a new tree (the device
         builder's, built in place on the GPU) instead of a refit.  The tree must fit the BLAS's node span (node_capacity)."""
@@ -789,11 +797,8 @@ class PathTracer:
         bvh = self._bvhScene
         off = self._blas_offsets(mesh)
         if rebuild_above is not None:
-            if mesh not in self._builtCost:     # the tree as built: measured on the host from the arrays PTSetScene was given
-                n0, cap, t0, nt = bvh.blas_spans[0 if mesh is None else mesh]
-                self._builtCost[mesh] = plugin.measure_cwbvh((bvh.bvh_nodes[n0 * 80:(n0 + cap) * 80], bvh.bvh_tris[t0 * 16:t0 * 16 + nt * 48]), nt)["sahCost"]
             self.update_geometry(vertices, mesh=mesh, tri_attrs=tri_attrs)
-            if self.geometry_quality(mesh)["sahCost"] <= rebuild_above * self._builtCost[mesh]:
+            if self.geometry_quality(mesh)["sahCost"] <= rebuild_above * self._built_cost(mesh):
                 return "refit"
             self.rebuild_geometry(vertices, mesh=mesh)         # the attributes were replaced by the refit above
             return "rebuild"
@@ -835,6 +840,65 @@ class PathTracer:
                 l2w = bvh.gpu_instances[k]["localToWorld"].reshape(4, 4).T.astype(np.float64)
                 bvh.blas_instances[k]["aabbMin"], bvh.blas_instances[k]["aabbMax"] = instance_world_bounds(v, l2w)
             plugin.check(self.lib.PTUpdateInstances(self.ctx, bvh.blas_instances.ctypes.data, bvh.blas_instances.shape[0]))
+
+    # ---- skinned geometry (include/ptmi_plugin.h Part 11)
+    def set_skin(self, rest_vertices, joints, weights, mesh: int = None, rest_attrs=None, joint_count: int = None):
+        """PTSetSkin: the skin of one BLAS, uploaded once.  rest_vertices (3T, 4) float32 in the BLAS's primitive order
+        (update_geometry's layout), joints (3T, 4) uint16, weights (3T, 4) float32, rest_attrs (optional) the BLAS's abi.TRI_ATTR
+        records of the rest pose -- with them every skin_geometry also writes the skinned normals and tangents.  joint_count: the
+        palette's length (default: the largest joint index + 1).  rest_vertices = None removes the BLAS's skin."""
+        off = self._blas_offsets(mesh)
+        nt = self._bvhScene.blas_spans[0 if mesh is None else mesh][3]
+        if rest_vertices is None:
+            plugin.check(self.lib.PTSetSkin(self.ctx, *off, nt, None))
+            return
+        if joint_count is None:
+            joint_count = int(np.asarray(joints).max()) + 1
+        d, ntri, keep = plugin.skin_desc(rest_vertices, joints, weights, joint_count, rest_attrs)
+        plugin.check(self.lib.PTSetSkin(self.ctx, *off, ntri, C.byref(d)))
+
+    def skin_geometry(self, joint_matrices, mesh: int = None, rebuild: bool = False, rebuild_above: float = None):
+        """PTSkinGeometry: one joint palette in, the BLAS's vertices skinned on the GPU and refitted (rebuild=True: rebuilt, Part
+        10's rules) in place -- no vertex is uploaded or read back.  joint_matrices: numpy (J, 3, 4) or (J, 12) (rest space to the
+        mesh's local space: joint world x inverse bind), or a float32 torch tensor of that shape on this context's device
+        (PTSkinGeometryDevice, ordered after torch's current stream).  Returns the skinned vertices' bounds, (2, 3) float32: min, max.
+        HAS_TLAS scene: the world bounds of the mesh's instances are recomputed from those two corners
+        (scenes.instance_world_bounds) and sent through PTUpdateInstances.  Does not reset accumulation.
+        rebuild_above: update_geometry's policy -- refit, measure, and rebuild from the same palette if sahCost exceeds
+        rebuild_above x the cost after the BLAS's last build or rebuild; returns (bounds, "refit" or "rebuild") then."""
+        bvh = self._bvhScene
+        off = self._blas_offsets(mesh)
+        if rebuild_above is not None:
+            bounds = self.skin_geometry(joint_matrices, mesh=mesh)
+            if self.geometry_quality(mesh)["sahCost"] <= rebuild_above * self._built_cost(mesh):
+                return bounds, "refit"
+            return self.skin_geometry(joint_matrices, mesh=mesh, rebuild=True), "rebuild"
+        flags = abi.PT_SKIN_REBUILD if rebuild else 0
+        out = (C.c_float * 6)()
+        if isinstance(joint_matrices, np.ndarray):
+            m = plugin.joint_palette(joint_matrices)
+            plugin.check(self.lib.PTSkinGeometry(self.ctx, *off, m.ctypes.data, m.shape[0], flags, out))
+        else:
+            import torch
+            m = joint_matrices
+            assert m.is_contiguous() and m.dtype == torch.float32 and m.numel() % 12 == 0 and tuple(m.shape[1:]) in ((3, 4), (12,))
+            cur = torch.cuda.current_stream(m.device)
+            ext = torch.cuda.ExternalStream(self.stream(), device=m.device)
+            ext.wait_stream(cur)
+            plugin.check(self.lib.PTSkinGeometryDevice(self.ctx, *off, m.data_ptr(), m.numel() // 12, flags, out))
+            cur.wait_stream(ext)
+        bounds = np.array(out, np.float32).reshape(2, 3)
+        if rebuild:
+            self._builtCost[mesh] = self.geometry_quality(mesh)["sahCost"]
+        if bvh.gpu_instances is not None:
+            from .scenes import instance_world_bounds
+            for k, (m_, _, _) in enumerate(self.scene.instances):
+                if m_ != mesh:
+                    continue
+                l2w = bvh.gpu_instances[k]["localToWorld"].reshape(4, 4).T.astype(np.float64)
+                bvh.blas_instances[k]["aabbMin"], bvh.blas_instances[k]["aabbMax"] = instance_world_bounds(bounds, l2w)
+            plugin.check(self.lib.PTUpdateInstances(self.ctx, bvh.blas_instances.ctypes.data, bvh.blas_instances.shape[0]))
+        return bounds
 
     def read_geometry(self):
         """PTReadGeometry: the current (nodes uint8[], tris uint8[], tri_attrs abi.TRI_ATTR[]) of the whole scene.  Synchronising."""

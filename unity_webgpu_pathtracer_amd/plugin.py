@@ -102,6 +102,11 @@ sig = {
     "PTRebuildGeometryDevice": (i32, [vp, C.c_int32, C.c_int32, C.c_int32, vp, i32, vp]),
     "PTMeasureGeometry": (i32, [vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(abi.PTGeometryQuality)]),
     "PTMeasureBVHArrays": (i32, [vp, C.c_uint64, vp, C.c_uint64, i32, C.POINTER(abi.PTGeometryQuality)]),
+    # Part 11 (skinned geometry)
+    "PTSetSkin": (i32, [vp, C.c_int32, C.c_int32, C.c_int32, i32, C.POINTER(abi.PTSkinDesc)]),
+    "PTSkinGeometry": (i32, [vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
+    "PTSkinGeometryDevice": (i32, [vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
+    "PTSkinVerticesHost": (i32, [C.POINTER(abi.PTSkinDesc), i32, vp, vp, vp, C.POINTER(C.c_float)]),
     "PTGetLastError": (C.c_char_p, []), "PTGetVersion": (i32, []),
 }
 EXPORTED_SYMBOLS = list(sig)
@@ -289,6 +294,44 @@ def measure_cwbvh(arrays, triangle_count: int) -> dict:
     if not lib.PTMeasureBVHArrays(nodes.ctypes.data, nodes.nbytes, tris.ctypes.data, tris.nbytes, int(triangle_count), C.byref(q)):
         raise PluginError(abi.PT_ERR_INVALID_ARG, "PTMeasureBVHArrays failed: " + lib.PTGetBVHBuildError().decode())
     return q.as_dict()
+
+
+def skin_desc(rest_vertices, joints, weights, joint_count: int, rest_attrs=None):
+    """A PTSkinDesc over numpy arrays: rest_vertices (3T, 4) float32, joints (3T, 4) uint16, weights (3T, 4) float32, rest_attrs T
+    abi.TRI_ATTR records or None.  Returns (desc, triangle count, the arrays the desc borrows -- keep them alive while it is used)."""
+    v = np.ascontiguousarray(rest_vertices, dtype=np.float32)
+    j = np.ascontiguousarray(joints, dtype=np.uint16)
+    w = np.ascontiguousarray(weights, dtype=np.float32)
+    assert v.ndim == 2 and v.shape[1] == 4 and v.shape[0] % 3 == 0 and j.shape == v.shape and w.shape == v.shape
+    a = None if rest_attrs is None else np.ascontiguousarray(rest_attrs)
+    assert a is None or a.nbytes == v.shape[0] // 3 * 128
+    d = abi.skin_desc()
+    d.jointCount = int(joint_count)
+    d.restVertices, d.joints, d.weights = v.ctypes.data, j.ctypes.data, w.ctypes.data
+    d.restAttrs = None if a is None else a.ctypes.data
+    return d, v.shape[0] // 3, (v, j, w, a)
+
+
+def joint_palette(joint_matrices) -> np.ndarray:
+    """(J, 3, 4) or (J, 12) -> C-contiguous float32 (J, 12): the rows of each joint's 3x4 matrix."""
+    m = np.ascontiguousarray(joint_matrices, dtype=np.float32)
+    assert m.ndim in (2, 3) and m.size % 12 == 0 and m.shape[1:] in ((3, 4), (12,)), m.shape
+    return m.reshape(-1, 12)
+
+
+def skin_vertices(rest_vertices, joints, weights, joint_matrices, rest_attrs=None):
+    """Linear-blend skinning on the host (PTSkinVerticesHost, include/ptmi_plugin.h Part 11): the kernels' rule, byte for byte.
+    joint_matrices: (J, 3, 4) or (J, 12).  Returns (vertices (3T, 4) float32, attrs or None, bounds (2, 3) float32: min, max);
+    raises PluginError for a joint index >= J or non-finite weights, rest vertices or matrices."""
+    m = joint_palette(joint_matrices)
+    d, ntri, keep = skin_desc(rest_vertices, joints, weights, m.shape[0], rest_attrs)
+    out = np.empty((ntri * 3, 4), np.float32)
+    out_attrs = None if keep[3] is None else np.empty(keep[3].shape, keep[3].dtype)
+    bounds = (C.c_float * 6)()
+    lib = load_library()
+    if not lib.PTSkinVerticesHost(C.byref(d), ntri, m.ctypes.data, out.ctypes.data, None if out_attrs is None else out_attrs.ctypes.data, bounds):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTSkinVerticesHost failed: " + lib.PTGetBVHBuildError().decode())
+    return out, out_attrs, np.array(bounds, np.float32).reshape(2, 3)
 
 
 def build_tlas(instances: np.ndarray):
