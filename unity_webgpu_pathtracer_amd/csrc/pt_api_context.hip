@@ -16,16 +16,42 @@ thread_local std::string g_lastError;
 namespace {
 
 // Consecutive passes run on up to PT_WF_SETS streams so that one pass's launch tails are filled by its neighbours' kernels.
-// The HIP runtime multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues (default 4, one of them the context stream's) and
-// streams that share a queue serialise: more sets than queues is SLOWER than fewer sets.  The library never
-// touches the host's environment: it reads the variable the host chose (export GPU_MAX_HW_QUEUES=16 before
-// the first HIP call; bench.py, host/pt_host.c and the Python mirror do) and sizes the default number of passes in flight
-// to it: >= 16 queues -> 12 sets, >= 8 -> 6, otherwise 3.  PTSetPassesInFlight overrides.
-uint32_t default_passes_in_flight()
+// The HIP runtime multiplexes the streams of one priority level onto GPU_MAX_HW_QUEUES hardware queues (default 4) and streams
+// that share a queue serialise: more sets than queues is SLOWER than fewer sets.  The library never touches the
+// host's environment; it reads the limit the runtime was started with.
+uint32_t hw_queue_limit()
 {
     const char* e = getenv("GPU_MAX_HW_QUEUES");
     const long q = e ? strtol(e, nullptr, 10) : 4;
-    uint32_t n = q >= 16 ? 12u : (q >= 8 ? 6u : 3u);
+    return q < 1 ? 1u : (q > 1024 ? 1024u : (uint32_t)q);
+}
+
+// the priority levels nothing else in the process uses: greatest, then least, where they differ from normal (0)
+uint32_t private_levels(int level[2])
+{
+    int least = 0, greatest = 0;
+    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { (void)hipGetLastError(); return 0u; }
+    uint32_t n = 0;
+    if (greatest < 0) level[n++] = greatest;
+    if (least > 0) level[n++] = least;
+    return n;
+}
+
+// The default number of passes in flight follows the queues the set streams really have (profiles/own_queues_ab.md).
+// ownQueues: the sets with a queue of their own are those at a private level, two levels of GPU_MAX_HW_QUEUES each -- 8 with the
+// runtime's default of 4, which already carries 12 sets (the last four share the normal pool with the nearly idle context
+// stream), so only a limit below 4 gives fewer.  Otherwise every stream of the process shares the one normal pool, one queue of it
+// the context stream's: >= 16 queues -> 12 sets, >= 8 -> 6, otherwise 3.  PTSetPassesInFlight overrides.
+uint32_t default_passes_in_flight(bool ownQueues)
+{
+    uint32_t n;
+    if (ownQueues) {
+        const uint32_t own = sets_with_own_queue();
+        n = own >= 8u ? 12u : (own >= 6u ? 6u : 3u);
+    } else {
+        const uint32_t q = hw_queue_limit();
+        n = q >= 16u ? 12u : (q >= 8u ? 6u : 3u);
+    }
     return n < (uint32_t)PT_WF_SETS ? n : (uint32_t)PT_WF_SETS;
 }
 
@@ -214,6 +240,38 @@ void discard_updates(PTContext* c)
 RoctxRange::RoctxRange(const char* name) { if (roctx_api().push) roctx_api().push(name); }
 RoctxRange::~RoctxRange() { if (roctx_api().pop) roctx_api().pop(); }
 
+uint32_t sets_with_own_queue()
+{
+    int level[2];
+    const uint32_t limit = hw_queue_limit();
+    if (limit >= 16u) return 0u;                    // create_set_stream: the normal pool, as before
+    const uint32_t own = private_levels(level) * limit;
+    return own < (uint32_t)PT_WF_SETS ? own : (uint32_t)PT_WF_SETS;
+}
+
+int create_set_stream(uint32_t index, Stream& s)
+{
+    if (s.h) return PT_OK;
+    // A host that asked for 16 queues or more keeps what it had, call for call: the normal pool has a queue for every set, and
+    // twelve sets at the greatest level read no more there (profiles/own_queues_ab.md).
+    const uint32_t limit = hw_queue_limit(), k = index / limit;
+    if (limit >= 16u) return create(s);
+    int level[2];
+    const uint32_t levels = private_levels(level);
+    // at most PT_WF_SETS set streams exist per context, so at most that many queues outside the normal pool
+    if (index < (uint32_t)PT_WF_SETS && k < levels) {
+        // Where one level holds every set it is the greatest: twelve sets at the least level read 2.3 % less.  Where both are
+        // needed the least is filled first: at a limit of 4, sets 0-3 least and 4-7 greatest read 3.7 % more than the other
+        // way round (profiles/own_queues_ab.md).  The first is taken from runs with 16 queues and the levels forced, the second
+        // from runs at a limit of 4; limits of 5-15 themselves were not measured.
+        const bool both = levels == 2u && limit < (uint32_t)PT_WF_SETS;
+        if (hipStreamCreateWithPriority(&s.h, hipStreamNonBlocking, level[both ? 1u - k : k]) == hipSuccess) return PT_OK;
+        (void)hipGetLastError();
+        s.h = nullptr;
+    }
+    return create(s);
+}
+
 int drain_events(PTContext* c)
 {
     for (auto& ep : c->pending) {
@@ -384,9 +442,16 @@ PT_API int PTCreate(int deviceIndex, PTContext** outCtx)
     HIP_TRY(hipSetDevice(deviceIndex));
     PTContext* c = new PTContext();
     c->device = deviceIndex;
-    c->numSets = default_passes_in_flight();
     hipError_t se = hipStreamCreateWithFlags(&c->stream.h, hipStreamNonBlocking);
     if (se != hipSuccess) { delete c; return fail(PT_ERR_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(se)); }
+    // Where the sets are to have private levels, set 0's stream is made here: whether it really sits at one decides the default
+    // number of passes in flight.  Otherwise (16 queues or more, no levels) not one call differs from what it was.
+    if (sets_with_own_queue() > 0u) {
+        if (int rc = create_set_stream(0u, c->sets[0].stream)) { delete c; return rc; }
+        int priority = 0;
+        c->ownQueues = hipStreamGetPriority(c->sets[0].stream, &priority) == hipSuccess && priority != 0;
+    }
+    c->numSets = default_passes_in_flight(c->ownQueues);
     se = hipMalloc(&c->dStats.ptr, 16 * sizeof(unsigned long long));
     if (se != hipSuccess) { delete c; return fail(PT_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(se)); }
     hipMemsetAsync(c->dStats.ptr, 0, 16 * sizeof(unsigned long long), c->stream);
@@ -498,7 +563,7 @@ PT_API int PTSetPassesInFlight(PTContext* c, int passes)
     if (!c || passes < 0 || passes > PT_WF_SETS) return fail(PT_ERR_INVALID_ARG, "ctx == NULL or passes outside 0.." + std::to_string(PT_WF_SETS));
     HIP_TRY(hipSetDevice(c->device));
     for (auto& set : c->sets) if (set.stream) HIP_TRY(hipStreamSynchronize(set.stream));
-    c->numSets = passes == 0 ? default_passes_in_flight() : (uint32_t)passes;
+    c->numSets = passes == 0 ? default_passes_in_flight(c->ownQueues) : (uint32_t)passes;
     c->nextSet = 0u;
     // sets that are no longer used give their memory back
     for (uint32_t k = c->numSets; k < (uint32_t)PT_WF_SETS; ++k) {

@@ -16,7 +16,7 @@ int ensure_frames(PTContext* c, uint32_t w, uint32_t h)
 int ensure_wavefront(PTContext* c, PTContext::WfSet& set, uint32_t numSlots, uint32_t maxIterations)
 {
     int rc;
-    if ((rc = create(set.stream)) || (rc = create(set.callEv)) || (rc = create(set.done))) return rc;
+    if ((rc = create_set_stream((uint32_t)(&set - c->sets), set.stream)) || (rc = create(set.callEv)) || (rc = create(set.done))) return rc;
     const bool needTlas = c->scene.hasTlas != 0u;
     if (set.wf.flags && set.wf.numSlots == numSlots && set.wf.maxIterations >= maxIterations && (!needTlas || set.wf.tlasSpill)) return PT_OK;
     if (c->residentWaves == 0u) {
