@@ -356,12 +356,12 @@ PT_API int PTSetWavefrontIterations(PTContext* ctx, int iterations);
 /* Wavefront schedules: how many consecutive passes may be in flight at once, each on its own path-state set and HIP stream
  * (the pixel write of a pass is decoupled from its path loop, so pass k+1 traces while pass k drains; only the resolves are
  * ordered).  1 = passes run back to back (what a host that reads every frame back gets anyway).  0 (default) = sized to the
- * hardware queues the set streams get (streams that share a hardware queue serialise).  The HIP runtime keeps one pool of
- * GPU_MAX_HW_QUEUES queues (4 when unset) per stream priority level; with a limit below 16 the set streams are created at the
- * two levels nothing else in the process uses, so 2 x GPU_MAX_HW_QUEUES of them have a queue of their own whatever the host
- * exported: 8 or more (every limit >= 4, the unset default included) -> 12, 6 or 7 -> 6, fewer -> 3.  With 16 or more, or where
- * the runtime offers no such levels, the sets share the process's one pool: GPU_MAX_HW_QUEUES >= 16 -> 12, >= 8 -> 6, otherwise 3.  The library
- * never changes the environment itself.  A number above what has its own queue is legal, and slower, not wrong.  Each set costs
+ * hardware queues the set streams get (streams that share a hardware queue serialise).  The HIP runtime pools the streams of a
+ * process on GPU_MAX_HW_QUEUES queues (4 when unset); with a limit below 16 the set streams are created with a CU mask that
+ * enables every CU (hipExtStreamCreateWithCUMask), which the runtime never pools, so every set has a queue of its own whatever
+ * the host exported: 12.  Such a stream synchronises with the null stream.  With 16 or more, or where the
+ * runtime refuses such a stream, the sets share the process's one pool: GPU_MAX_HW_QUEUES >= 16 -> 12, >= 8 -> 6, otherwise 3.
+ * The library never changes the environment itself.  A number above what has its own queue is legal, and slower, not wrong.  Each set costs
  * ~290 B per owned pixel and is allocated on the first pass that can use it; lowering the number frees the sets no longer
  * used.  Same frame for every value. */
 PT_API int PTSetPassesInFlight(PTContext* ctx, int passes);

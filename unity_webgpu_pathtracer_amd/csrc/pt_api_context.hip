@@ -26,32 +26,33 @@ uint32_t hw_queue_limit()
     return q < 1 ? 1u : (q > 1024 ? 1024u : (uint32_t)q);
 }
 
-// the priority levels nothing else in the process uses: greatest, then least, where they differ from normal (0)
-uint32_t private_levels(int level[2])
+// A stream whose queue carries a CU mask -- here: every CU of the current device, no bit beyond them -- cannot be pooled by the
+// runtime, so it always gets a hardware queue of its own, at normal priority, whatever GPU_MAX_HW_QUEUES says.  The call takes
+// no flags: such a stream synchronises with the null stream.  false, with the error cleared and s.h null: no
+// such stream to be had.
+bool create_masked(Stream& s)
 {
-    int least = 0, greatest = 0;
-    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { (void)hipGetLastError(); return 0u; }
-    uint32_t n = 0;
-    if (greatest < 0) level[n++] = greatest;
-    if (least > 0) level[n++] = least;
-    return n;
+    int device = 0, cus = 0;
+    if (hipGetDevice(&device) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) {
+        (void)hipGetLastError();
+        return false;
+    }
+    std::vector<uint32_t> mask(((uint32_t)cus + 31u) / 32u, 0xFFFFFFFFu);       // hipDeviceProp_t::multiProcessorCount bits
+    if (cus % 32) mask.back() = (1u << (cus % 32)) - 1u;
+    if (hipExtStreamCreateWithCUMask(&s.h, (uint32_t)mask.size(), mask.data()) == hipSuccess) return true;
+    (void)hipGetLastError();
+    s.h = nullptr;
+    return false;
 }
 
-// The default number of passes in flight follows the queues the set streams really have (profiles/own_queues_ab.md).
-// ownQueues: the sets with a queue of their own are those at a private level, two levels of GPU_MAX_HW_QUEUES each -- 8 with the
-// runtime's default of 4, which already carries 12 sets (the last four share the normal pool with the nearly idle context
-// stream), so only a limit below 4 gives fewer.  Otherwise every stream of the process shares the one normal pool, one queue of it
-// the context stream's: >= 16 queues -> 12 sets, >= 8 -> 6, otherwise 3.  PTSetPassesInFlight overrides.
+// The default number of passes in flight follows the queues the set streams really have (profiles/normal_queues_ab.md).
+// ownQueues: set 0's stream was made with a queue of its own (create_set_stream), and so is every other set's: all PT_WF_SETS.
+// Otherwise every stream of the process shares the one normal pool, one queue of it the context stream's: >= 16 queues -> 12 sets,
+// >= 8 -> 6, otherwise 3.  PTSetPassesInFlight overrides.
 uint32_t default_passes_in_flight(bool ownQueues)
 {
-    uint32_t n;
-    if (ownQueues) {
-        const uint32_t own = sets_with_own_queue();
-        n = own >= 8u ? 12u : (own >= 6u ? 6u : 3u);
-    } else {
-        const uint32_t q = hw_queue_limit();
-        n = q >= 16u ? 12u : (q >= 8u ? 6u : 3u);
-    }
+    const uint32_t q = hw_queue_limit();
+    const uint32_t n = ownQueues || q >= 16u ? 12u : (q >= 8u ? 6u : 3u);
     return n < (uint32_t)PT_WF_SETS ? n : (uint32_t)PT_WF_SETS;
 }
 
@@ -240,34 +241,17 @@ void discard_updates(PTContext* c)
 RoctxRange::RoctxRange(const char* name) { if (roctx_api().push) roctx_api().push(name); }
 RoctxRange::~RoctxRange() { if (roctx_api().pop) roctx_api().pop(); }
 
-uint32_t sets_with_own_queue()
+int create_set_stream(uint32_t index, Stream& s, bool* ownQueue)
 {
-    int level[2];
-    const uint32_t limit = hw_queue_limit();
-    if (limit >= 16u) return 0u;                    // create_set_stream: the normal pool, as before
-    const uint32_t own = private_levels(level) * limit;
-    return own < (uint32_t)PT_WF_SETS ? own : (uint32_t)PT_WF_SETS;
-}
-
-int create_set_stream(uint32_t index, Stream& s)
-{
+    if (ownQueue) *ownQueue = false;
     if (s.h) return PT_OK;
-    // A host that asked for 16 queues or more keeps what it had, call for call: the normal pool has a queue for every set, and
-    // twelve sets at the greatest level read no more there (profiles/own_queues_ab.md).
-    const uint32_t limit = hw_queue_limit(), k = index / limit;
-    if (limit >= 16u) return create(s);
-    int level[2];
-    const uint32_t levels = private_levels(level);
-    // at most PT_WF_SETS set streams exist per context, so at most that many queues outside the normal pool
-    if (index < (uint32_t)PT_WF_SETS && k < levels) {
-        // Where one level holds every set it is the greatest: twelve sets at the least level read 2.3 % less.  Where both are
-        // needed the least is filled first: at a limit of 4, sets 0-3 least and 4-7 greatest read 3.7 % more than the other
-        // way round (profiles/own_queues_ab.md).  The first is taken from runs with 16 queues and the levels forced, the second
-        // from runs at a limit of 4; limits of 5-15 themselves were not measured.
-        const bool both = levels == 2u && limit < (uint32_t)PT_WF_SETS;
-        if (hipStreamCreateWithPriority(&s.h, hipStreamNonBlocking, level[both ? 1u - k : k]) == hipSuccess) return PT_OK;
-        (void)hipGetLastError();
-        s.h = nullptr;
+    // A host that asked for 16 queues or more keeps what it had, call for call: the normal pool has a queue for every set
+    // (profiles/own_queues_ab.md: that path reads less for even one more call in PTCreate).  Below that every set stream carries
+    // the all-CU mask; at most PT_WF_SETS set streams exist per context, so at most that many queues outside the pool.  Where
+    // the runtime refuses, the stream is an ordinary one of the normal pool.
+    if (hw_queue_limit() < 16u && index < (uint32_t)PT_WF_SETS && create_masked(s)) {
+        if (ownQueue) *ownQueue = true;
+        return PT_OK;
     }
     return create(s);
 }
@@ -444,12 +428,10 @@ PT_API int PTCreate(int deviceIndex, PTContext** outCtx)
     c->device = deviceIndex;
     hipError_t se = hipStreamCreateWithFlags(&c->stream.h, hipStreamNonBlocking);
     if (se != hipSuccess) { delete c; return fail(PT_ERR_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(se)); }
-    // Where the sets are to have private levels, set 0's stream is made here: whether it really sits at one decides the default
-    // number of passes in flight.  Otherwise (16 queues or more, no levels) not one call differs from what it was.
-    if (sets_with_own_queue() > 0u) {
-        if (int rc = create_set_stream(0u, c->sets[0].stream)) { delete c; return rc; }
-        int priority = 0;
-        c->ownQueues = hipStreamGetPriority(c->sets[0].stream, &priority) == hipSuccess && priority != 0;
+    // Where the sets are to have queues of their own, set 0's stream is made here: whether it really has one decides the default
+    // number of passes in flight.  Otherwise (16 queues or more) not one call differs from what it was.
+    if (hw_queue_limit() < 16u) {
+        if (int rc = create_set_stream(0u, c->sets[0].stream, &c->ownQueues)) { delete c; return rc; }
     }
     c->numSets = default_passes_in_flight(c->ownQueues);
     se = hipMalloc(&c->dStats.ptr, 16 * sizeof(unsigned long long));

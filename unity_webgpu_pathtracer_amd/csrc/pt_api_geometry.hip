@@ -119,7 +119,9 @@ int rebuild_blas(PTContext* c, PTContext::GeomPlan& plan, char* dNodes, char* dT
     std::vector<uint32_t> order(K);
     for (uint32_t k = 0; k < K; ++k) order[k] = (uint32_t)plan.key[0] + k;
     if (plan.order.bytes < (size_t)K * 4 && (rc = plan.order.reserve((size_t)cap * 4))) return rc;
-    HIP_TRY(hipMemcpy(plan.order.ptr, order.data(), (size_t)K * 4, hipMemcpyHostToDevice));
+    // on the update stream, not the null stream: a synchronous copy there waits for every set stream that blocks against it
+    HIP_TRY(hipMemcpyAsync(plan.order.ptr, order.data(), (size_t)K * 4, hipMemcpyHostToDevice, u.stream));
+    HIP_TRY(hipStreamSynchronize(u.stream));        // `order` is this function's
     plan.levelStart.swap(res.levelStart);
     return PT_OK;
 }
@@ -377,9 +379,11 @@ PT_API int PTReadGeometry(PTContext* c, void* dstNodes, uint64_t nodeBytes, void
     HIP_TRY(hipSetDevice(c->device));
     if (c->update.stream) HIP_TRY(hipStreamSynchronize(c->update.stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(dstNodes, c->scene.nodes, c->nodes.used, hipMemcpyDeviceToHost));
-    if (c->tris.used) HIP_TRY(hipMemcpy(dstTris, c->scene.tris, c->tris.used, hipMemcpyDeviceToHost));
-    if (dstAttrs && c->attrs.used) HIP_TRY(hipMemcpy(dstAttrs, c->scene.attrs, c->attrs.used, hipMemcpyDeviceToHost));
+    // on the context stream, not the null stream: passes in flight are not waited for (they do not write the scene)
+    HIP_TRY(hipMemcpyAsync(dstNodes, c->scene.nodes, c->nodes.used, hipMemcpyDeviceToHost, c->stream));
+    if (c->tris.used) HIP_TRY(hipMemcpyAsync(dstTris, c->scene.tris, c->tris.used, hipMemcpyDeviceToHost, c->stream));
+    if (dstAttrs && c->attrs.used) HIP_TRY(hipMemcpyAsync(dstAttrs, c->scene.attrs, c->attrs.used, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return PT_OK;
 }
 

@@ -77,13 +77,10 @@ PT_API int PTTraceRaysHost(PTContext* c, const PTRay* rays, uint64_t count, uint
     if ((rc = trace_rays(c, (const PTRay*)q.rays.ptr, count, flags, (PTRayHit*)q.hits.ptr, surf ? (PTRaySurface*)q.surface.ptr : nullptr))) return rc;
     HIP_TRY(hipMemcpyAsync(hits, q.hits.ptr, count * sizeof(PTRayHit), hipMemcpyDeviceToHost, c->stream));
     // surface records exist only where a closest hit was found: the rest of the caller's array is left as it was
-    if (surf) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        std::vector<PTRaySurface> tmp(count);
-        HIP_TRY(hipMemcpy(tmp.data(), q.surface.ptr, count * sizeof(PTRaySurface), hipMemcpyDeviceToHost));
-        for (uint64_t i = 0; i < count; ++i) if (hits[i].prim != 0xFFFFFFFFu) surface[i] = tmp[i];
-    }
+    std::vector<PTRaySurface> tmp(surf ? count : 0);
+    if (surf) HIP_TRY(hipMemcpyAsync(tmp.data(), q.surface.ptr, count * sizeof(PTRaySurface), hipMemcpyDeviceToHost, c->stream));     // not the null stream
     HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint64_t i = 0; surf && i < count; ++i) if (hits[i].prim != 0xFFFFFFFFu) surface[i] = tmp[i];
     return PT_OK;
 }
 

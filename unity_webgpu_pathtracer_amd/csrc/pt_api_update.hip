@@ -206,15 +206,18 @@ PT_API int PTReadTLAS(PTContext* c, void* dstNodes, uint64_t dstNodeBytes, uint3
     uint32_t nodes = u.origTlasNodes;
     const char* base = (const char*)c->tlas.ptr;
     if (u.inst.cur >= 0) {
-        HIP_TRY(hipMemcpy(&nodes, u.tlasW.ctrl, 4, hipMemcpyDeviceToHost));
+        // the copies of this call run on the context stream, not the null stream: passes in flight are not waited for
+        HIP_TRY(hipMemcpyAsync(&nodes, u.tlasW.ctrl, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
         if (nodes > 2u * n - 1u) return fail(PT_ERR_HIP, "internal: TLAS node count out of range");
         base = (const char*)inst_gen(u.inst.gen[u.inst.cur].ptr, n).raw;
     }
     const size_t idxOff = u.inst.cur >= 0 ? ((size_t)2 * n - 1) * 64 : (size_t)u.origTlasNodes * 64;
     if (dstNodeBytes < (uint64_t)nodes * 64 || dstIndexCount < n)
         return fail(PT_ERR_INVALID_ARG, "destination too small: " + std::to_string(nodes) + " nodes and " + std::to_string(n) + " indices");
-    HIP_TRY(hipMemcpy(dstNodes, base, (size_t)nodes * 64, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(dstIndices, base + idxOff, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpyAsync(dstNodes, base, (size_t)nodes * 64, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(dstIndices, base + idxOff, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     *outNodeCount = nodes;
     return PT_OK;
 }

@@ -52,12 +52,12 @@ using Event = Owned<hipEvent_t, hipEventDestroy>;
 // created on first use
 inline int create(Stream& s) { if (!s.h) HIP_TRY(hipStreamCreateWithFlags(&s.h, hipStreamNonBlocking)); return PT_OK; }
 inline int create(Event& e, unsigned flags = hipEventDisableTiming) { if (!e.h) HIP_TRY(hipEventCreateWithFlags(&e.h, flags)); return PT_OK; }
-// The stream of state set `index` (PTContext::sets), created on first use (pt_api_context.hip).  The runtime keeps one pool of
-// hardware queues PER STREAM PRIORITY LEVEL, each limited by GPU_MAX_HW_QUEUES, and everything else in the process -- the context
-// stream, the null stream, the host's own streams -- lives at the normal level: the sets fill one of the other two levels up to
-// the limit, then the other, and only the rest share the normal pool.  A level that cannot be had is create().
-int create_set_stream(uint32_t index, Stream& s);
-uint32_t sets_with_own_queue();                     // how many of the PT_WF_SETS indices create_set_stream gives a private level (0: none)
+// The stream of state set `index` (PTContext::sets), created on first use (pt_api_context.hip).  The runtime multiplexes the
+// streams of a process onto GPU_MAX_HW_QUEUES hardware queues, and streams that share one serialise.  Below a limit of 16 a set
+// stream is made with hipExtStreamCreateWithCUMask and every CU enabled: a queue that carries a CU mask is never pooled, so each
+// set has a hardware queue of its own at normal priority -- and, the call taking no flags, a stream that synchronises with the
+// null stream.  With 16 or more, or where the runtime refuses, it is create().  *ownQueue: made here with a queue of its own.
+int create_set_stream(uint32_t index, Stream& s, bool* ownQueue = nullptr);
 
 // One device allocation (Pinned: one page-locked host allocation).
 template <bool Pinned>
@@ -176,7 +176,7 @@ struct PTContext {
     uint32_t residentWaves = 0;                 // CUs x 4 SIMDs x 8 waves (device property, read once)
     uint32_t subFrames = 1;                     // launch chains a pass is cut into (PTSetSubFrames)
     uint32_t numSets = 0;                       // passes in flight = state sets in use (PTSetPassesInFlight); carved on first use
-    bool ownQueues = false;                     // PTCreate got set 0's stream at a private priority level: the default follows sets_with_own_queue()
+    bool ownQueues = false;                     // PTCreate got set 0's stream with a hardware queue of its own (create_set_stream): the default is every set
     uint32_t wfIterations = 0;                  // 0 = automatic
     // ray queries (PTTraceRays): grid caps per query kernel (read once), the CWBVH stack slab sized for the largest, host staging
     struct Query {
