@@ -947,6 +947,89 @@ PT_API int PTSkinGeometryDevice(PTContext* ctx, int32_t bvhOffset, int32_t triOf
 PT_API int PTSkinVerticesHost(const PTSkinDesc* desc, int triangleCount, const float* jointMatrices, PTFloat4* outVertices,
                               PTTriangleAttributes* outAttrsOrNull, float* outBoundsOrNull);               /* host twin, no GPU */
 
+/* =====================================================================================================================
+ * Part 12: morph targets.  A glTF character deforms in two steps: morph targets first, then the skin.  Part 11 is the second
+ * step; this part adds the first and runs both in one kernel.  PTSetMorph uploads the sparse targets of one BLAS once;
+ * PTMorphGeometry then takes one float per target (and optionally Part 11's joint palette), makes the vertices on the GPU and
+ * runs the refit (Part 9) or rebuild (Part 10) on them, exactly as PTSkinGeometry does.
+ *
+ * The data.  A morph has targetCount targets and up to three streams: position deltas (required, may be empty), normal deltas
+ * and tangent deltas (each optional: offsets and entries both NULL).  A stream is CSR over the BLAS's 3 * T corners, in
+ * PTUpdateGeometry's input order: offsets[3T + 1] (offsets[0] == 0, non-decreasing), then entries {dx, dy, dz, target}; the
+ * entries of one corner are in strictly ascending target order.  ONLY LISTED ENTRIES ARE APPLIED: a dense glTF target is the
+ * case where every corner lists every target; a listed zero delta is still multiplied and added; an unlisted delta does not
+ * exist (it is not a zero: -0, NaN and infinite-weight cases differ).
+ *
+ * The rule (morph_rule.h; bit-defined under DESIGN.md 3: one IEEE binary32 operation per operator, left to right, no
+ * contraction).  Position: acc = rest.xyz; for each entry of the corner in order, per component, acc = acc + w[target] * d (one
+ * product, one sum).  Without a palette the result is acc, output w = 0; with a palette it is Part 11's  B * (acc, 1)  with B the
+ * blend matrix of the BLAS's skin (its joints and weights; the skin's own rest pose is not used).  Normals and tangents, per
+ * corner, from the rest record's row: m = rest.xyz folded with the corner's entries of that stream in the same way.  Without a
+ * palette a corner with no entry in the stream is copied bit for bit; otherwise d = (m.x*m.x + m.y*m.y) + m.z*m.z, and the result
+ * is m * (1 / sqrt(d)), or the REST vector if d is 0 or not finite.  With a palette every corner is  B3 * m  normalised as in Part
+ * 11, and a dot that is 0 or not finite keeps the REST vector (not m).  A tangent's w, the pads, uv0 .. uv2 and materialIndex are
+ * the rest record's.  Bounds: compare-and-select min and max over the 3 * T output positions.
+ *
+ * PTSetMorph.  The BLAS is named and checked as in Part 9.  Checked once, on the host: 1 <= targetCount <=
+ * PT_MORPH_MAX_TARGETS; for every stream offsets[0] == 0, offsets non-decreasing, every target < targetCount, targets strictly
+ * ascending within a corner, deltas finite; rest vertices finite; without HAS_TLAS every materialIndex < materialCount; a normal
+ * or tangent stream needs restAttrs -- the kernels then index the weights with a stored target and nothing else.  The arrays
+ * are copied before the call returns and stay on the device, each stream as sliced ELL (slices of 64 corners, each padded to
+ * its longest corner; padding is stored, never applied): 16 bytes per vertex for the morph's OWN rest pose (kept even when the
+ * BLAS also has a skin: with both, the rest positions are on the device twice), 16 bytes per stored entry, 4 bytes per corner
+ * and per slice and stream, plus 128 bytes per triangle with restAttrs.  A second call replaces the morph, a NULL desc
+ * removes it (both wait for the update stream); PTSetScene discards every morph, PTDestroy frees them.
+ *
+ * PTMorphGeometry (weights and palette in host memory, copied before return; non-finite weights or matrices are refused before
+ * anything is enqueued) and PTMorphGeometryDevice (both in device memory, 16-byte aligned, read in the context stream's order,
+ * not inspected).  targetCount must be the morph's.  jointMatrices may be NULL: a plain morph, also on a skinned BLAS; a
+ * palette needs a skin on the BLAS with that jointCount.  flags: 0 = refit, PT_SKIN_REBUILD = Part 10's rebuild.  outBounds,
+ * ordering, generations, carry-over, "accumulation is not reset" and "a refused call leaves the scene as it was" are Part 11's.
+ * Errors: PT_ERR_NO_SCENE before PTSetScene; PT_ERR_INVALID_ARG for a NULL context or weights, a BLAS without a morph, a
+ * targetCount that is not the morph's, a palette without a skin, a jointCount that is not the skin's, a refused array.
+ *
+ * PTMorphVerticesHost is the host twin (no GPU): the same rule, byte for byte.  skin (with jointMatrices) supplies joints and
+ * weights only; jointMatrices == NULL is a plain morph, jointMatrices without skin is refused.  outAttrs needs desc->restAttrs.
+ * Returns 1, or 0 with PTGetBVHBuildError() set.  PTMorphLayoutHost is the host's conversion of one CSR stream into the device
+ * layout, for tests: outCount[cornerCount], outSliceBase[ceil(cornerCount / 64) + 1], outEntries[the returned count]; slot s of
+ * corner c is outEntries[outSliceBase[c / 64] + 64 * s + c % 64] and is the corner's s-th entry if s < outCount[c], else padding
+ * (all zero).  With all three NULL it only returns the stored entry count; UINT64_MAX: that count does not fit 32 bits.
+ * ===================================================================================================================== */
+#define PT_MORPH_MAX_TARGETS 1024u
+
+typedef struct PTMorphEntry { float dx, dy, dz; uint32_t target; } PTMorphEntry;
+
+typedef struct PTMorphDesc {
+    uint32_t        structSize;   /* sizeof(PTMorphDesc) of the caller's header; members are only appended */
+    uint32_t        targetCount;  /* 1 ... PT_MORPH_MAX_TARGETS */
+    const PTFloat4* restVertices; /* 3 * triangleCount, the morph's own rest pose */
+    const PTTriangleAttributes* restAttrs;   /* triangleCount, or NULL; required by a normal or tangent stream */
+    const uint32_t*     positionOffsets;     /* 3 * triangleCount + 1 */
+    const PTMorphEntry* positionEntries;     /* may be NULL if positionOffsets[3 * triangleCount] == 0 */
+    const uint32_t*     normalOffsets;       /* both NULL: no stream */
+    const PTMorphEntry* normalEntries;
+    const uint32_t*     tangentOffsets;
+    const PTMorphEntry* tangentEntries;
+} PTMorphDesc;
+
+#ifdef __cplusplus
+static_assert(sizeof(PTMorphEntry) == 16, "PTMorphEntry is 16 bytes");
+static_assert(sizeof(PTMorphDesc) == 72, "PTMorphDesc is 72 bytes");
+#else
+_Static_assert(sizeof(PTMorphEntry) == 16, "PTMorphEntry is 16 bytes");
+_Static_assert(sizeof(PTMorphDesc) == 72, "PTMorphDesc is 72 bytes");
+#endif
+
+PT_API int PTSetMorph(PTContext* ctx, int32_t bvhOffset, int32_t triOffset, int32_t triAttributeOffset, int triangleCount, const PTMorphDesc* descOrNull);
+PT_API int PTMorphGeometry(PTContext* ctx, int32_t bvhOffset, int32_t triOffset, int32_t triAttributeOffset, const float* weights, uint32_t targetCount,
+                           const float* jointMatricesOrNull, uint32_t jointCount, uint32_t flags, float* outBounds);      /* host arrays, copied before return */
+PT_API int PTMorphGeometryDevice(PTContext* ctx, int32_t bvhOffset, int32_t triOffset, int32_t triAttributeOffset, const float* dWeights, uint32_t targetCount,
+                                 const float* dJointMatricesOrNull, uint32_t jointCount, uint32_t flags, float* outBounds); /* device arrays, read in stream order */
+PT_API int PTMorphVerticesHost(const PTMorphDesc* desc, const PTSkinDesc* skinOrNull, int triangleCount, const float* weights, const float* jointMatricesOrNull,
+                               PTFloat4* outVertices, PTTriangleAttributes* outAttrsOrNull, float* outBoundsOrNull);      /* host twin, no GPU */
+PT_API uint64_t PTMorphLayoutHost(const uint32_t* offsets, const PTMorphEntry* entries, uint32_t cornerCount, uint32_t* outCount, uint32_t* outSliceBase,
+                                  PTMorphEntry* outEntries);                                                               /* the device layout of one stream, for tests */
+
 /* Text of the last error on the calling thread ("" if none). */
 PT_API const char* PTGetLastError(void);
 /* Library/ABI version: (major << 16) | minor. */

@@ -317,6 +317,34 @@ def skin_desc() -> PTSkinDesc:
     return d
 
 
+# ---------------------------------------------------------------------------------------
+# Part 12: morph targets (PTSetMorph / PTMorphGeometry / PTMorphVerticesHost)
+# ---------------------------------------------------------------------------------------
+PT_MORPH_MAX_TARGETS = 1024
+MORPH_ENTRY = np.dtype([("dx", "<f4"), ("dy", "<f4"), ("dz", "<f4"), ("target", "<u4")])
+assert MORPH_ENTRY.itemsize == 16
+
+
+class PTMorphEntry(C.Structure):
+    _fields_ = [("dx", C.c_float), ("dy", C.c_float), ("dz", C.c_float), ("target", C.c_uint32)]
+
+
+class PTMorphDesc(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("targetCount", C.c_uint32), ("restVertices", C.c_void_p), ("restAttrs", C.c_void_p),
+                ("positionOffsets", C.c_void_p), ("positionEntries", C.c_void_p), ("normalOffsets", C.c_void_p), ("normalEntries", C.c_void_p),
+                ("tangentOffsets", C.c_void_p), ("tangentEntries", C.c_void_p)]
+
+
+assert C.sizeof(PTMorphDesc) == 72 and C.sizeof(PTMorphEntry) == 16
+
+
+def morph_desc() -> PTMorphDesc:
+    """An empty PTMorphDesc with structSize set."""
+    d = PTMorphDesc()
+    d.structSize = C.sizeof(PTMorphDesc)
+    return d
+
+
 def as_void_p(arr):
     """Borrowed host pointer of a C-contiguous numpy array (None -> NULL)."""
     if arr is None:

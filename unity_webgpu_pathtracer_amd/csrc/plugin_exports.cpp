@@ -9,10 +9,12 @@
 #include <cstddef>
 #include <deque>
 #include <string>
+#include <algorithm>
 #include "bvh_builder.h"
 #include "bvh_refit.h"
 #include "bvh_quality.h"
 #include "skin_rule.h"
+#include "morph_rule.h"
 #include "ptmi_plugin.h"
 
 namespace {
@@ -120,6 +122,46 @@ PT_API int PTSkinVerticesHost(const PTSkinDesc* desc, int triangleCount, const f
     ptskin::skin_host(*desc, (uint32_t)triangleCount, jointMatrices, outVertices, outAttrsOrNull, outBoundsOrNull);
     g_buildError.clear();
     return 1;
+}
+// Morph targets, then the skin, on the host (morph_host.cpp; Part 12 has the rule).  No GPU involved.
+PT_API int PTMorphVerticesHost(const PTMorphDesc* desc, const PTSkinDesc* skinOrNull, int triangleCount, const float* weights, const float* jointMatricesOrNull,
+                               PTFloat4* outVertices, PTTriangleAttributes* outAttrsOrNull, float* outBoundsOrNull)
+{
+    if (!desc || !weights || !outVertices || triangleCount <= 0) { g_buildError = "NULL desc, weights or result, or triangleCount <= 0"; return 0; }
+    if (desc->structSize < sizeof(PTMorphDesc) || desc->structSize > 4096u) {
+        g_buildError = "PTMorphDesc.structSize is not set (must be sizeof(PTMorphDesc) of the host's header)";
+        return 0;
+    }
+    if (skinOrNull && (skinOrNull->structSize < sizeof(PTSkinDesc) || skinOrNull->structSize > 4096u)) {
+        g_buildError = "PTSkinDesc.structSize is not set (must be sizeof(PTSkinDesc) of the host's header)";
+        return 0;
+    }
+    if (jointMatricesOrNull && !skinOrNull) { g_buildError = "a palette needs a skin"; return 0; }
+    if (outAttrsOrNull && !desc->restAttrs) { g_buildError = "outAttrs needs PTMorphDesc.restAttrs"; return 0; }
+    if (!ptmorph::morph_check(*desc, (uint32_t)triangleCount, 0xFFFFFFFFu, g_buildError)) return 0;
+    if (!ptmorph::morph_check_weights(weights, desc->targetCount, g_buildError)) return 0;
+    if (jointMatricesOrNull) {
+        if (!ptskin::skin_check(*skinOrNull, (uint32_t)triangleCount, 0xFFFFFFFFu, g_buildError)) return 0;
+        if (!ptskin::skin_check_palette(jointMatricesOrNull, skinOrNull->jointCount, g_buildError)) return 0;
+    }
+    ptmorph::morph_host(*desc, skinOrNull, (uint32_t)triangleCount, weights, jointMatricesOrNull, outVertices, outAttrsOrNull, outBoundsOrNull);
+    g_buildError.clear();
+    return 1;
+}
+// PTSetMorph's conversion of one CSR stream into the layout the kernels read (morph_host.cpp), for tests.  The stream is not checked here.
+PT_API uint64_t PTMorphLayoutHost(const uint32_t* offsets, const PTMorphEntry* entries, uint32_t cornerCount, uint32_t* outCount, uint32_t* outSliceBase,
+                                  PTMorphEntry* outEntries)
+{
+    if (!offsets) return 0;
+    const uint64_t stored = ptmorph::morph_layout_size(offsets, cornerCount);
+    if (stored > 0xFFFFFFFFull) return UINT64_MAX;
+    if (!outCount && !outSliceBase && !outEntries) return stored;
+    ptmorph::MorphLayout L;
+    ptmorph::morph_layout(offsets, entries, cornerCount, L);
+    if (outCount) std::copy(L.count.begin(), L.count.end(), outCount);
+    if (outSliceBase) std::copy(L.sliceBase.begin(), L.sliceBase.end(), outSliceBase);
+    if (outEntries) std::copy(L.entries.begin(), L.entries.end(), outEntries);
+    return stored;
 }
 PT_API void DestroyBVH(int index) { free_slot(g_bvhs, index); }
 PT_API int IsBVHReady(int index) { return get_slot(g_bvhs, index) != nullptr; }

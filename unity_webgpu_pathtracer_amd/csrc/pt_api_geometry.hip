@@ -1,7 +1,7 @@
 // pt_api_geometry.hip — geometry updates and PTReadGeometry (include/ptmi_plugin.h Part 9); geometry rebuilds and
-// the tree-quality measure (Part 10); skinned geometry (Part 11).
+// the tree-quality measure (Part 10); skinned geometry (Part 11); morph targets (Part 12).
 #include "pt_context.h"
-#include "skin_rule.h"
+#include "morph_rule.h"
 
 #include <cmath>
 
@@ -126,22 +126,26 @@ int rebuild_blas(PTContext* c, PTContext::GeomPlan& plan, char* dNodes, char* dT
     return PT_OK;
 }
 
-// PTSkinGeometry's vertex source: the BLAS's skin (PTSetSkin) and a joint palette instead of the caller's vertices
+// PTSkinGeometry's vertex source: the BLAS's skin (PTSetSkin) and a joint palette instead of the caller's vertices.  With
+// morphWeights it is PTMorphGeometry's: the BLAS's morph (PTSetMorph) and one weight per target, and the palette may be NULL.
 struct SkinSource {
     const float* palette;
     uint32_t jointCount;
     bool onDevice;
     float* outBounds;
+    const float* morphWeights = nullptr;
+    uint32_t targetCount = 0;
 };
 
 // Every geometry update: the vertices are the caller's (host arrays staged, or device arrays), or with `skin` those the skin kernel
-// makes from the BLAS's skin and the palette (verts, triangleCount and attrs then are unused: the skin has them).
+// or the morph kernel makes from the BLAS's skin or morph and the palette or weights (verts, triangleCount and attrs then are
+// unused: the skin or the morph has them).
 int update_geometry(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t attrOffset, const PTFloat4* verts, int triangleCount,
                     const PTTriangleAttributes* attrs, bool onDevice, bool rebuild, const SkinSource* skin = nullptr)
 {
     if (!c) return fail(PT_ERR_INVALID_ARG, "ctx == NULL");
     if (!skin && !verts) return fail(PT_ERR_INVALID_ARG, "vertices == NULL");
-    if (skin && !skin->palette) return fail(PT_ERR_INVALID_ARG, "jointMatrices == NULL");
+    if (skin && !skin->morphWeights && !skin->palette) return fail(PT_ERR_INVALID_ARG, "jointMatrices == NULL");
     if (!c->hasScene) return fail(PT_ERR_NO_SCENE, "PTSetScene has not been called");
     if ((!skin && triangleCount <= 0) || bvhOffset < 0 || triOffset < 0 || attrOffset < 0) return fail(PT_ERR_INVALID_ARG, "triangleCount <= 0 or a negative offset");
     HIP_TRY(hipSetDevice(c->device));
@@ -152,15 +156,25 @@ int update_geometry(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t 
     const uint32_t triCount = plan->triCount;
     const bool flat = !c->scene.hasTlas;                             // a flat scene's kernels index the materials with the records' materialIndex
     const bool staged = !skin && !onDevice;                          // host arrays go through the groups' pinned staging
-    if (skin) {
+    const bool morph = skin && skin->morphWeights;
+    if (morph) {
+        const PTContext::GeomPlan::Morph& M = plan->morph;
+        if (!M.targetCount) return fail(PT_ERR_INVALID_ARG, "the BLAS has no morph (PTSetMorph)");
+        if (skin->targetCount != M.targetCount)
+            return fail(PT_ERR_INVALID_ARG, "targetCount (" + std::to_string(skin->targetCount) + ") != the morph's (" + std::to_string(M.targetCount) + ")");
+        std::string why;
+        if (!skin->onDevice && !ptmorph::morph_check_weights(skin->morphWeights, M.targetCount, why)) return fail(PT_ERR_INVALID_ARG, why);
+        if (skin->onDevice && ((uintptr_t)skin->morphWeights & 15u)) return fail(PT_ERR_INVALID_ARG, "dWeights is not 16-byte aligned");
+    }
+    if (skin && skin->palette) {
         const PTContext::GeomPlan::Skin& K = plan->skin;
-        if (!K.jointCount) return fail(PT_ERR_INVALID_ARG, "the BLAS has no skin (PTSetSkin)");
+        if (!K.jointCount) return fail(PT_ERR_INVALID_ARG, morph ? "a palette needs a skin: the BLAS has no skin (PTSetSkin)" : "the BLAS has no skin (PTSetSkin)");
         if (skin->jointCount != K.jointCount)
             return fail(PT_ERR_INVALID_ARG, "jointCount (" + std::to_string(skin->jointCount) + ") != the skin's (" + std::to_string(K.jointCount) + ")");
         std::string why;
         if (!skin->onDevice && !ptskin::skin_check_palette(skin->palette, K.jointCount, why)) return fail(PT_ERR_INVALID_ARG, why);
         if (skin->onDevice && ((uintptr_t)skin->palette & 15u)) return fail(PT_ERR_INVALID_ARG, "dJointMatrices is not 16-byte aligned");
-    } else if (!onDevice) {
+    } else if (!skin && !onDevice) {
         for (size_t i = 0; i < (size_t)triCount * 3; ++i)
             if (!std::isfinite(verts[i].x) || !std::isfinite(verts[i].y) || !std::isfinite(verts[i].z))
                 return fail(PT_ERR_INVALID_ARG, "vertex " + std::to_string(i) + " is not finite");
@@ -168,7 +182,7 @@ int update_geometry(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t 
             if (attrs[i].materialIndex >= c->scene.materialCount)
                 return fail(PT_ERR_INVALID_ARG, "triangle " + std::to_string(i) + ": materialIndex " + std::to_string(attrs[i].materialIndex) + " >= materialCount");
     }
-    const bool writeAttrs = skin ? plan->skin.restAttrs.ptr != nullptr : attrs != nullptr;
+    const bool writeAttrs = morph ? plan->morph.restAttrs.ptr != nullptr : skin ? plan->skin.restAttrs.ptr != nullptr : attrs != nullptr;
     PTContext::Update& u = c->update;
     PTContext::Geometry& G = u.geometry;
     const size_t nodeBytes = c->nodes.used, triBytes = c->tris.used, attrBytes = c->attrs.used;
@@ -182,13 +196,15 @@ int update_geometry(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t 
     HIP_TRY(hipMemcpyAsync(dNodes, c->scene.nodes, nodeBytes, hipMemcpyDeviceToDevice, u.stream));
     HIP_TRY(hipMemcpyAsync(dTris, c->scene.tris, triBytes, hipMemcpyDeviceToDevice, u.stream));
     PTSkinArgs S = {};
+    PTMorphArgs MA = {};
     char* dAttrs = nullptr;
     // the BLAS's attribute records of the target generation: the carry-over copy, then the new records
     auto write_attrs = [&]() -> int {
         dAttrs = (char*)u.attrs.gen[ta].ptr;
         char* dst = dAttrs + (size_t)attrOffset * 128;
         HIP_TRY(hipMemcpyAsync(dAttrs, c->scene.attrs, attrBytes, hipMemcpyDeviceToDevice, u.stream));
-        if (skin) HIP_TRY(pt_launch_skin_attrs(S, (float4*)dst, u.stream));          // each record once, no staging copy
+        if (morph) HIP_TRY(pt_launch_morph_attrs(MA, skin->palette ? &S : nullptr, (float4*)dst, u.stream));
+        else if (skin) HIP_TRY(pt_launch_skin_attrs(S, (float4*)dst, u.stream));     // each record once, no staging copy
         else if (onDevice) HIP_TRY(pt_launch_refit_attrs((float4*)dst, (const float4*)attrs, triCount, flat ? c->scene.materialCount : 0xFFFFFFFFu, u.stream));
         else if (int e = stage_host(c, u.attrs, ta, attrs, (size_t)triCount * 128, dst)) return e;
         return PT_OK;
@@ -206,13 +222,25 @@ int update_geometry(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t 
         S.restAttrs = (const float4*)K.restAttrs.ptr;
         S.triCount = triCount;
         S.palette = (const float4*)skin->palette;
-        if (!skin->onDevice) {
+        if (skin->palette && !skin->onDevice) {
             if ((rc = G.palette.send(skin->palette, (size_t)K.jointCount * 48, u.stream))) return rc;
             S.palette = (const float4*)G.palette.dev.ptr;
         }
-        // grown only for a larger BLAS; the folds that used the old array ran on the update stream
+        if (morph) {
+            const PTContext::GeomPlan::Morph& M = plan->morph;
+            MA.rest = (const float4*)M.rest.ptr; MA.restAttrs = (const float4*)M.restAttrs.ptr;
+            MA.position = M.position.args(); MA.normal = M.normal.args(); MA.tangent = M.tangent.args();
+            MA.triCount = triCount;
+            MA.weights = skin->morphWeights;
+            if (!skin->onDevice) {
+                if ((rc = G.morphWeights.send(skin->morphWeights, (size_t)M.targetCount * 4, u.stream))) return rc;
+                MA.weights = (const float*)G.morphWeights.dev.ptr;
+            }
+        }
+        // grown only for a larger BLAS; the folds that used the old array ran on the update stream (the morph's work space is the skin's)
         if ((rc = G.skinWork.reserve(pt_skin_work_floats(triCount) * sizeof(float), u.stream))) return rc;
-        HIP_TRY(pt_launch_skin_vertices(S, (float4*)G.verts.ptr, (float*)G.skinWork.ptr, u.stream));
+        if (morph) HIP_TRY(pt_launch_morph_vertices(MA, skin->palette ? &S : nullptr, (float4*)G.verts.ptr, (float*)G.skinWork.ptr, u.stream));
+        else HIP_TRY(pt_launch_skin_vertices(S, (float4*)G.verts.ptr, (float*)G.skinWork.ptr, u.stream));
         if (skin->outBounds) {
             if ((rc = G.skinBounds.reserve(6 * sizeof(float)))) return rc;
             HIP_TRY(hipMemcpyAsync(G.skinBounds.ptr, G.skinWork.ptr, 6 * sizeof(float), hipMemcpyDeviceToHost, u.stream));
@@ -288,6 +316,55 @@ int set_skin(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t attrOff
     return PT_OK;
 }
 
+// PTSetMorph: the desc's arrays onto the device (each stream in the kernels' layout), replacing the BLAS's morph; desc == NULL removes it
+int set_morph(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t attrOffset, int triangleCount, const PTMorphDesc* hostDesc)
+{
+    if (!c) return fail(PT_ERR_INVALID_ARG, "ctx == NULL");
+    if (!c->hasScene) return fail(PT_ERR_NO_SCENE, "PTSetScene has not been called");
+    if (triangleCount <= 0 || bvhOffset < 0 || triOffset < 0 || attrOffset < 0) return fail(PT_ERR_INVALID_ARG, "triangleCount <= 0 or a negative offset");
+    PTMorphDesc d;
+    if (hostDesc)
+        if (int rc = import_struct(hostDesc, d, sizeof(PTMorphDesc), "PTMorphDesc", "desc == NULL")) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure_host_copy(c))) return rc;
+    PTContext::GeomPlan* plan = nullptr;
+    if ((rc = find_plan(c, bvhOffset, triOffset, attrOffset, (uint32_t)triangleCount, plan))) return rc;
+    const uint32_t triCount = plan->triCount, corners = triCount * 3u;
+    std::string why;
+    if (hostDesc && !ptmorph::morph_check(d, triCount, c->scene.hasTlas ? 0xFFFFFFFFu : c->scene.materialCount, why)) return fail(PT_ERR_INVALID_ARG, why);
+    PTContext::GeomPlan::Morph M;
+    // one stream: laid out on the host, then copied; an empty stream keeps 16 bytes so that its pointer says "present"
+    auto upload = [&](const uint32_t* off, const PTMorphEntry* ent, PTContext::GeomPlan::Morph::Stream& S) -> int {
+        ptmorph::MorphLayout L;
+        if (!ptmorph::morph_layout(off, ent, corners, L)) return fail(PT_ERR_INVALID_ARG, "the stream's stored entries (padding included) do not fit 32 bits");
+        const size_t bytes = L.entries.size() * sizeof(PTMorphEntry);
+        if (int e = S.count.reserve(L.count.size() * 4)) return e;
+        if (int e = S.sliceBase.reserve(L.sliceBase.size() * 4)) return e;
+        if (int e = S.entries.reserve(bytes ? bytes : 16)) return e;
+        HIP_TRY(hipMemcpy(S.count.ptr, L.count.data(), L.count.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(S.sliceBase.ptr, L.sliceBase.data(), L.sliceBase.size() * 4, hipMemcpyHostToDevice));
+        if (bytes) HIP_TRY(hipMemcpy(S.entries.ptr, L.entries.data(), bytes, hipMemcpyHostToDevice));
+        return PT_OK;
+    };
+    if (hostDesc) {
+        if ((rc = M.rest.reserve((size_t)corners * 16))) return rc;
+        HIP_TRY(hipMemcpy(M.rest.ptr, d.restVertices, (size_t)corners * 16, hipMemcpyHostToDevice));
+        if ((rc = upload(d.positionOffsets, d.positionEntries, M.position))) return rc;
+        if (d.normalOffsets && (rc = upload(d.normalOffsets, d.normalEntries, M.normal))) return rc;
+        if (d.tangentOffsets && (rc = upload(d.tangentOffsets, d.tangentEntries, M.tangent))) return rc;
+        if (d.restAttrs) {
+            if ((rc = M.restAttrs.reserve((size_t)triCount * 128))) return rc;
+            HIP_TRY(hipMemcpy(M.restAttrs.ptr, d.restAttrs, (size_t)triCount * 128, hipMemcpyHostToDevice));
+        }
+        M.targetCount = d.targetCount;
+    }
+    // morph kernels enqueued so far read the arrays replaced or freed below
+    if (c->update.stream) HIP_TRY(hipStreamSynchronize(c->update.stream));
+    plan->morph = std::move(M);                                     // the old arrays are released with M
+    return PT_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -334,6 +411,31 @@ PT_API int PTSkinGeometryDevice(PTContext* c, int32_t bvhOffset, int32_t triOffs
 {
     if (flags & ~PT_SKIN_REBUILD) return fail(PT_ERR_INVALID_ARG, "unknown flags");
     const SkinSource src = {dJointMatrices, jointCount, true, outBounds};
+    return update_geometry(c, bvhOffset, triOffset, triAttributeOffset, nullptr, 0, nullptr, false, (flags & PT_SKIN_REBUILD) != 0, &src);
+}
+
+PT_API int PTSetMorph(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t triAttributeOffset, int triangleCount, const PTMorphDesc* descOrNull)
+{
+    return set_morph(c, bvhOffset, triOffset, triAttributeOffset, triangleCount, descOrNull);
+}
+
+PT_API int PTMorphGeometry(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t triAttributeOffset, const float* weights, uint32_t targetCount,
+                           const float* jointMatricesOrNull, uint32_t jointCount, uint32_t flags, float* outBounds)
+{
+    if (flags & ~PT_SKIN_REBUILD) return fail(PT_ERR_INVALID_ARG, "unknown flags");
+    if (c && !weights) return fail(PT_ERR_INVALID_ARG, "weights == NULL");
+    SkinSource src = {jointMatricesOrNull, jointCount, false, outBounds};
+    src.morphWeights = weights; src.targetCount = targetCount;
+    return update_geometry(c, bvhOffset, triOffset, triAttributeOffset, nullptr, 0, nullptr, false, (flags & PT_SKIN_REBUILD) != 0, &src);
+}
+
+PT_API int PTMorphGeometryDevice(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t triAttributeOffset, const float* dWeights, uint32_t targetCount,
+                                 const float* dJointMatricesOrNull, uint32_t jointCount, uint32_t flags, float* outBounds)
+{
+    if (flags & ~PT_SKIN_REBUILD) return fail(PT_ERR_INVALID_ARG, "unknown flags");
+    if (c && !dWeights) return fail(PT_ERR_INVALID_ARG, "dWeights == NULL");
+    SkinSource src = {dJointMatricesOrNull, jointCount, true, outBounds};
+    src.morphWeights = dWeights; src.targetCount = targetCount;
     return update_geometry(c, bvhOffset, triOffset, triAttributeOffset, nullptr, 0, nullptr, false, (flags & PT_SKIN_REBUILD) != 0, &src);
 }
 

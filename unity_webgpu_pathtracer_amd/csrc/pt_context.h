@@ -6,6 +6,7 @@
 #include "pt_refit.h"
 #include "pt_quality.h"
 #include "pt_skin.h"
+#include "pt_morph.h"
 #include "bvh_refit.h"
 #include "bvh_builder_gpu.h"
 
@@ -251,6 +252,16 @@ struct PTContext {
             uint32_t jointCount = 0;
             DeviceBuffer rest, joints, weights, restAttrs;
         } skin;
+        // PTSetMorph: the BLAS's morph on the device, its own rest pose and each stream in morph_rule.h's layout; targetCount == 0: none
+        struct Morph {
+            struct Stream {
+                DeviceBuffer count, sliceBase, entries;
+                PTMorphStream args() const { return {(const uint32_t*)count.ptr, (const uint32_t*)sliceBase.ptr, (const float4*)entries.ptr}; }
+            };
+            uint32_t targetCount = 0;
+            DeviceBuffer rest, restAttrs;
+            Stream position, normal, tangent;
+        } morph;
     };
     struct Geometry {
         std::vector<PTFloat4> hostNodes;                // host copy of the node buffer (rows n1 and imask are what is read)
@@ -258,10 +269,11 @@ struct PTContext {
         std::vector<int32_t> blasKeys;                  // HAS_TLAS: the three offsets of every instance (PTSetScene's records)
         std::vector<GeomPlan> plans;                    // one per BLAS updated so far
         DeviceBuffer nodeBox;                           // 24 B per node of the scene
-        DeviceBuffer verts;                             // the host variant's vertices on the device, or the skin kernel's
+        DeviceBuffer verts;                             // the host variant's vertices on the device, or the skin or morph kernel's
         DeviceBuffer buildWork;                         // the builder's work arrays, sized for the largest BLAS rebuilt so far
         DeviceBuffer qualityWork;                       // PTMeasureGeometry: results and per-workgroup partial sums
         UploadTable palette;                            // PTSkinGeometry: the host palette, on the update stream
+        UploadTable morphWeights;                       // PTMorphGeometry: the host weights likewise
         DeviceBuffer skinWork;                          // the skinned vertices' box and its per-workgroup partials
         PinnedBuffer skinBounds;                        // ... read back (24 bytes)
     };

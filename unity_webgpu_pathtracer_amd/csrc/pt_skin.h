@@ -18,5 +18,7 @@ struct PTSkinArgs {
 size_t pt_skin_work_floats(uint32_t triCount);
 // pt_skin_vertices (3 * triCount skinned vertices into outVerts, one box per workgroup), then pt_skin_bounds_fold (work[0 ... 5])
 hipError_t pt_launch_skin_vertices(const PTSkinArgs& A, float4* outVerts, float* work, hipStream_t stream);
+// pt_skin_bounds_fold alone: `count` boxes of 6 floats (min.xyz, max.xyz) at `partial`, folded in index order into out[0 ... 5]
+hipError_t pt_launch_skin_bounds_fold(const float* partial, uint32_t count, float* out, hipStream_t stream);
 // pt_skin_attrs: the triCount attribute records of the skinned pose, each written once, to dstAttrs (the BLAS's first record)
 hipError_t pt_launch_skin_attrs(const PTSkinArgs& A, float4* dstAttrs, hipStream_t stream);

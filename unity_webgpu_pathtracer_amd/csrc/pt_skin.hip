@@ -105,6 +105,12 @@ hipError_t pt_launch_skin_vertices(const PTSkinArgs& A, float4* outVerts, float*
     return hipGetLastError();
 }
 
+hipError_t pt_launch_skin_bounds_fold(const float* partial, uint32_t count, float* out, hipStream_t stream)
+{
+    hipLaunchKernelGGL(pt_skin_bounds_fold, dim3(1), dim3(64), 0, stream, partial, count, out);
+    return hipGetLastError();
+}
+
 hipError_t pt_launch_skin_attrs(const PTSkinArgs& A, float4* dstAttrs, hipStream_t stream)
 {
     hipLaunchKernelGGL(pt_skin_attrs, dim3((A.triCount * 8u + 255u) / 256u), dim3(256), 0, stream, A, dstAttrs);

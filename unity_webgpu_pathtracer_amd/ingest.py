@@ -211,6 +211,24 @@ def _accessor(doc, blob, index):
     """One accessor as a (count, width) array of its component type converted per the glTF rules (normalised ints -> float)."""
     a = doc["accessors"][index]
     dt, width, count = np.dtype(_GLTF_COMPONENT[a["componentType"]]), _GLTF_WIDTH[a["type"]], a["count"]
+    if "sparse" in a:
+        # the dense accessor (zeros without a bufferView), then sparse.count elements replaced at sparse.indices
+        sp = a["sparse"]
+        out = _accessor_of(doc, blob, {k: v for k, v in a.items() if k != "sparse"})
+        where = _accessor_of(doc, blob, dict(sp["indices"], count=sp["count"], type="SCALAR")).reshape(-1).astype(np.int64)
+        if where.size and (int(where.max()) >= count or (np.diff(where) <= 0).any()):
+            raise ValueError("sparse accessor indices are out of range or not strictly increasing")
+        values = _accessor_of(doc, blob, dict(sp["values"], count=sp["count"], type=a["type"], componentType=a["componentType"],
+                                              normalized=a.get("normalized", False)))
+        out = out.astype(values.dtype)               # zeros of a normalised integer accessor are floats too
+        out[where] = values
+        return out
+    return _accessor_of(doc, blob, a)
+
+
+def _accessor_of(doc, blob, a):
+    """_accessor for an accessor given as a dict (its sparse part is the caller's)"""
+    dt, width, count = np.dtype(_GLTF_COMPONENT[a["componentType"]]), _GLTF_WIDTH[a["type"]], a["count"]
     if "bufferView" not in a:
         return np.zeros((count, width), dt)
     bv = doc["bufferViews"][a["bufferView"]]
@@ -347,7 +365,8 @@ def load_glb_skins(path, unity_handedness=True, flip_axis=2):
     primitive's positions to the SCENE's space: the skinned node's own transform does not enter (use an identity local_to_world).
     unity_handedness mirrors every matrix as load_glb mirrors the node transforms, M' = F M F, so that skinning the mirrored
     positions with the mirrored palette is the mirror image of the right-handed result.
-    Not read: animations, morph targets, JOINTS_1 / WEIGHTS_1 (more than four influences)."""
+    Morph targets and animations are load_glb_morphs' and load_glb_animations'.  Not read: JOINTS_1 / WEIGHTS_1 (more than four
+    influences)."""
     with open(path, "rb") as f:
         doc, blob = _glb_chunks(f.read())
     if flip_axis not in (0, 1, 2):
@@ -423,6 +442,204 @@ def joint_matrices(skin, local_matrices=None):
     return np.ascontiguousarray(m[:, :3, :], np.float32)
 
 
+def _scene_primitives(doc):
+    """(node index, primitive) of every mesh primitive in load_glb's order, and each visited node's parent (-1 for a root)"""
+    nodes = doc.get("nodes", [])
+    out, parent_of = [], {}
+
+    def visit(index, parent_index):
+        parent_of[index] = parent_index
+        node = nodes[index]
+        if "mesh" in node:
+            out.extend((index, prim) for prim in doc["meshes"][node["mesh"]]["primitives"])
+        for child in node.get("children", []):
+            visit(child, index)
+
+    for n in doc["scenes"][doc.get("scene", 0)]["nodes"] if doc.get("scenes") else list(range(len(nodes))):
+        visit(n, -1)
+    return out, parent_of
+
+
+def load_glb_morphs(path, unity_handedness=True, flip_axis=2):
+    """The morph targets of a .glb, as data: one entry per mesh primitive in load_glb's order (same arguments, same order), None
+    for a primitive without targets, else a dict:
+      position  (K, 3T, 3) float32   the targets' POSITION deltas expanded to the triangle soup of the primitive (through its
+      normal    (K, 3T, 3) or None   indices, in the winding load_glb gives it: vertex 3t + c = corner c of triangle t); NORMAL and
+      tangent   (K, 3T, 3) or None   TANGENT likewise, None unless every target has the attribute
+      weights   (K,) float32         the mesh's default weights (zeros if it has none)
+    Sparse accessors are honoured (an accessor without a bufferView is zeros).  unity_handedness mirrors the deltas' flip_axis
+    component and reverses the winding exactly as load_glb does for the rest arrays, so rest + sum(w * delta) of the mirrored
+    arrays is the mirror image of the right-handed result; a zero delta stays +0, so a mirrored target is as sparse as the file's.  PathTracer.set_morph takes the arrays as they are."""
+    with open(path, "rb") as f:
+        doc, blob = _glb_chunks(f.read())
+    if flip_axis not in (0, 1, 2):
+        raise ValueError("flip_axis must be 0, 1 or 2")
+    mirror = np.ones(3, np.float32)
+    if unity_handedness:
+        mirror[flip_axis] = -1.0
+    out = []
+    for index, prim in _scene_primitives(doc)[0]:
+        targets = prim.get("targets")
+        if not targets:
+            out.append(None)
+            continue
+        count = doc["accessors"][prim["attributes"]["POSITION"]]["count"]
+        idx = _accessor(doc, blob, prim["indices"]).reshape(-1).astype(np.int64) if "indices" in prim else np.arange(count)
+        if idx.size % 3 or (idx.size and int(idx.max()) >= count):
+            raise ValueError("index accessor does not describe triangles of this primitive")
+        if unity_handedness:
+            idx = idx.reshape(-1, 3)[:, ::-1].reshape(-1)
+        entry = {}
+        for name, key in (("POSITION", "position"), ("NORMAL", "normal"), ("TANGENT", "tangent")):
+            if not all(name in t for t in targets):
+                entry[key] = None
+                continue
+            arrays = [_accessor(doc, blob, t[name]).astype(np.float32) for t in targets]
+            if any(a.shape != (count, 3) for a in arrays):
+                raise ValueError(f"a morph target's {name} does not match the primitive")
+            # + 0: a zero delta stays +0 under the mirror (-0 + +0 is +0), so that a target's sparsity survives it (plugin.morph_csr)
+            entry[key] = np.ascontiguousarray(np.stack([a[idx] * mirror + np.float32(0) if unity_handedness else a[idx] for a in arrays]))
+        if entry["position"] is None:
+            entry["position"] = np.zeros((len(targets), len(idx), 3), np.float32)
+        w = doc["meshes"][doc["nodes"][index]["mesh"]].get("weights")
+        entry["weights"] = np.zeros(len(targets), np.float32) if w is None else np.asarray(w, np.float32)
+        if entry["weights"].shape != (len(targets),):
+            raise ValueError("the mesh's weights do not match its targets")
+        out.append(entry)
+    return out
+
+
+_CHANNEL_WIDTH = {"translation": 3, "rotation": 4, "scale": 3}
+
+
+def load_glb_animations(path, unity_handedness=True, flip_axis=2):
+    """The animations of a .glb, as data: one dict per animation,
+      name, duration (the latest keyframe, seconds)
+      channels    one dict per channel: node (glTF node index), path ("translation" / "rotation" / "scale" / "weights"),
+                  interpolation ("STEP" / "LINEAR" / "CUBICSPLINE"), times (n,) float64, values (n, 3 | 4 | K) float64 as stored
+                  (CUBICSPLINE: (3 n, width), in-tangent, value, out-tangent per keyframe; rotations x, y, z, w)
+      nodes       the file's node list (rest transforms, children), roots (the scene's root nodes)
+      primitives  one dict per mesh primitive in load_glb's order: node, joints (the skin's joint node indices, or None), weights
+                  (the mesh's default weights as (K,) float64, or None without targets)
+      flip        the 4x4 mirror that unity_handedness applies to every matrix (M' = F M F), the identity without it
+    sample_animation() evaluates one at a time t."""
+    with open(path, "rb") as f:
+        doc, blob = _glb_chunks(f.read())
+    if flip_axis not in (0, 1, 2):
+        raise ValueError("flip_axis must be 0, 1 or 2")
+    flip = np.eye(4)
+    if unity_handedness:
+        flip[flip_axis, flip_axis] = -1.0
+    nodes = doc.get("nodes", [])
+    roots = list(doc["scenes"][doc.get("scene", 0)]["nodes"]) if doc.get("scenes") else list(range(len(nodes)))
+    primitives = []
+    for index, prim in _scene_primitives(doc)[0]:
+        node = nodes[index]
+        att = prim["attributes"]
+        skinned = "skin" in node and "JOINTS_0" in att and "WEIGHTS_0" in att
+        w = doc["meshes"][node["mesh"]].get("weights")
+        k = len(prim.get("targets") or [])
+        primitives.append(dict(node=index, joints=list(doc["skins"][node["skin"]]["joints"]) if skinned else None,
+                               weights=None if not k else np.zeros(k) if w is None else np.asarray(w, np.float64)))
+    out = []
+    for anim in doc.get("animations", []):
+        channels = []
+        for ch in anim["channels"]:
+            if "node" not in ch["target"]:
+                continue
+            smp = anim["samplers"][ch["sampler"]]
+            path_, mode = ch["target"]["path"], smp.get("interpolation", "LINEAR")
+            if path_ not in ("translation", "rotation", "scale", "weights") or mode not in ("STEP", "LINEAR", "CUBICSPLINE"):
+                raise ValueError(f"animation channel {path_} / {mode} is not glTF 2.0")
+            times = _accessor(doc, blob, smp["input"]).reshape(-1).astype(np.float64)
+            values = _accessor(doc, blob, smp["output"]).astype(np.float64)
+            rows = len(times) * (3 if mode == "CUBICSPLINE" else 1)
+            if not len(times) or (np.diff(times) <= 0).any() or values.size % rows:
+                raise ValueError("an animation sampler's input is empty or not increasing, or its output does not match it")
+            values = values.reshape(rows, -1)
+            if path_ in _CHANNEL_WIDTH and values.shape[1] != _CHANNEL_WIDTH[path_]:
+                raise ValueError(f"a {path_} sampler's output has the wrong width")
+            channels.append(dict(node=int(ch["target"]["node"]), path=path_, interpolation=mode, times=times, values=values))
+        out.append(dict(name=anim.get("name", ""), duration=max([float(c["times"][-1]) for c in channels], default=0.0), channels=channels,
+                        nodes=nodes, roots=roots, primitives=primitives, flip=flip))
+    return out
+
+
+def _slerp(q0, q1, u):
+    """Spherical interpolation of two unit quaternions (x, y, z, w) along the shorter arc, float64"""
+    q0, q1 = np.asarray(q0, np.float64), np.asarray(q1, np.float64)
+    d = float(np.dot(q0, q1))
+    if d < 0.0:
+        q1, d = -q1, -d
+    theta = np.arccos(min(d, 1.0))
+    if theta < 1e-9:                                 # the same rotation: any blend of the two is it
+        return q0
+    return (np.sin((1.0 - u) * theta) * q0 + np.sin(u * theta) * q1) / np.sin(theta)
+
+
+def _sample_channel(ch, t):
+    """One channel at time t: clamped to the first and last keyframe outside the clip"""
+    if ch["interpolation"] == "CUBICSPLINE":
+        raise NotImplementedError("CUBICSPLINE animation samplers are not evaluated (STEP and LINEAR are)")
+    times, values = ch["times"], ch["values"]
+    if t <= times[0]:
+        return values[0]
+    if t >= times[-1]:
+        return values[-1]
+    k = int(np.searchsorted(times, t, side="right")) - 1
+    if ch["interpolation"] == "STEP":
+        return values[k]
+    u = (t - times[k]) / (times[k + 1] - times[k])
+    if ch["path"] == "rotation":
+        return _slerp(values[k] / np.linalg.norm(values[k]), values[k + 1] / np.linalg.norm(values[k + 1]), u)
+    return values[k] + u * (values[k + 1] - values[k])
+
+
+def sample_animation(anim, t):
+    """One load_glb_animations animation at time t (seconds), in float64: STEP and LINEAR samplers, LINEAR rotations by slerp along
+    the shorter arc, times outside a sampler's keyframes clamp to its first or last one; a CUBICSPLINE sampler raises
+    NotImplementedError.  Returns a dict with one entry per mesh primitive in load_glb's order:
+      local    None, or (J, 4, 4) float64: each joint's matrix relative to its parent joint (a root's includes its non-joint
+               ancestors), mirrored as load_glb_skins mirrors them -- what joint_matrices(skin, local) takes
+      weights  None, or (K,) float64: the morph weights -- the node's weights channel, else the mesh's defaults
+    A node that a translation / rotation / scale channel animates must store TRS, not a matrix (glTF 2.0 requires it)."""
+    nodes, flip = anim["nodes"], anim["flip"]
+    trs, weights = {}, {}
+    for ch in anim["channels"]:
+        v = _sample_channel(ch, float(t))
+        if ch["path"] == "weights":
+            weights[ch["node"]] = np.asarray(v, np.float64)
+        else:
+            if "matrix" in nodes[ch["node"]]:
+                raise ValueError("an animated node stores a matrix, not translation / rotation / scale")
+            trs.setdefault(ch["node"], {})[ch["path"]] = v / np.linalg.norm(v) if ch["path"] == "rotation" else v
+    world, parent_of = {}, {}
+
+    def visit(index, parent, parent_index):
+        node = nodes[index]
+        world[index] = parent @ _node_matrix(dict(node, **{k: list(v) for k, v in trs[index].items()}) if index in trs else node)
+        parent_of[index] = parent_index
+        for child in node.get("children", []):
+            visit(child, world[index], index)
+
+    for n in anim["roots"]:
+        visit(n, np.eye(4), -1)
+    out = {"local": [], "weights": []}
+    for prim in anim["primitives"]:
+        jn = prim["joints"]
+        local = None
+        if jn is not None:
+            local = np.zeros((len(jn), 4, 4))
+            for j, n in enumerate(jn):
+                p = parent_of[n]
+                while p >= 0 and p not in jn:
+                    p = parent_of[p]
+                local[j] = flip @ (np.linalg.inv(world[p]) @ world[n] if p >= 0 else world[n]) @ flip
+        out["local"].append(local)
+        out["weights"].append(None if prim["weights"] is None else weights.get(prim["node"], prim["weights"]))
+    return out
+
+
 def pack_gltf_materials(materials, image_to_texture=None):
     """glTF material dicts (load_glb) -> (M, 32) MaterialData rows with the packing rules of BVHScene.cs:236-282.  glTF factors are
     linear while BVHScene applies pow(c, 2.2) to a Unity (gamma) colour, so the factor goes in as c^(1/2.2).  image_to_texture
@@ -439,12 +656,36 @@ def pack_gltf_materials(materials, image_to_texture=None):
     return np.stack(rows) if rows else np.stack([scenes.pack_material()])
 
 
-def write_glb(path, meshes, materials=None, node_matrices=None, interleave=False, skins=None):
+def _trs_of(m):
+    """A node matrix without shear as glTF translation, rotation (x, y, z, w) and scale lists"""
+    m = np.asarray(m, np.float64)
+    scale = np.linalg.norm(m[:3, :3], axis=0)
+    r = m[:3, :3] / scale
+    w = np.sqrt(max(0.0, 1.0 + r[0, 0] + r[1, 1] + r[2, 2])) / 2.0
+    if w > 1e-6:
+        q = [(r[2, 1] - r[1, 2]) / (4 * w), (r[0, 2] - r[2, 0]) / (4 * w), (r[1, 0] - r[0, 1]) / (4 * w), w]
+    else:                                                # a half turn: the largest diagonal element names the axis
+        i = int(np.argmax(np.diag(r)))
+        j, k = (i + 1) % 3, (i + 2) % 3
+        x = np.sqrt(max(0.0, 1.0 + r[i, i] - r[j, j] - r[k, k])) / 2.0
+        q = [0.0, 0.0, 0.0, (r[k, j] - r[j, k]) / (4 * x)]
+        q[i], q[j], q[k] = x, (r[j, i] + r[i, j]) / (4 * x), (r[k, i] + r[i, k]) / (4 * x)
+    return m[:3, 3].tolist(), [float(c) for c in q], scale.tolist()
+
+
+def write_glb(path, meshes, materials=None, node_matrices=None, interleave=False, skins=None, morphs=None, animations=None):
     """A small GLB writer for tests: one node + mesh + primitive per `Mesh` (positions, optional normals / uvs, optional indices),
     float32 attributes, optionally interleaved into one strided bufferView; `node_matrices` (4x4 each) become node matrices.
     skins (optional): one entry per mesh, None or a dict as load_glb_skins returns it, with joints / weights per VERTEX of
     mesh.positions -- written as JOINTS_0 (uint16) / WEIGHTS_0 (float32), one node per joint (its rest local matrix) and a skin
-    with the inverse bind matrices.  With skins=None the bytes are what they were before the argument existed."""
+    with the inverse bind matrices.  With skins=None the bytes are what they were before the argument existed.
+    morphs (optional): one entry per mesh, None or a dict with position / normal / tangent: (K, V, 3) deltas per VERTEX of
+    mesh.positions (normal and tangent may be None or absent), weights: (K,) default weights or None, sparse: True writes every
+    target accessor as a sparse accessor without a bufferView (the rows that are not all +0).
+    animations (optional): dicts with name and channels, each channel a dict with node (the index of a mesh, whose node it is, or
+    ("joint", mesh index, joint index)), path, interpolation, times (n,) and values (n, width) -- written as float32 samplers; a
+    joint that a channel animates is written with translation / rotation / scale instead of a matrix (it must have no shear).
+    With morphs=None and animations=None the bytes are what they were before the arguments existed."""
     import json
     import struct
     blob, views, accessors, gl_meshes, nodes = bytearray(), [], [], [], []
@@ -490,18 +731,42 @@ def write_glb(path, meshes, materials=None, node_matrices=None, interleave=False
                 accessors.append({"bufferView": add_view(arr.tobytes()), "componentType": ct, "count": len(arr), "type": "VEC4"})
                 att[name] = len(accessors) - 1
         prim = {"attributes": att, "material": int(m.material_index)}
+        morph = morphs[k] if morphs is not None else None
+        if morph is not None:
+            streams = [(name, np.asarray(morph[key], np.float32)) for name, key in (("POSITION", "position"), ("NORMAL", "normal"), ("TANGENT", "tangent"))
+                       if morph.get(key) is not None]
+            targets = [{} for _ in range(len(streams[0][1]))]
+            for name, arr in streams:
+                assert arr.shape == (len(targets), len(m.positions), 3), name
+                for t, delta in enumerate(arr):
+                    acc = {"componentType": 5126, "count": len(delta), "type": "VEC3"}
+                    if name == "POSITION":
+                        acc["min"], acc["max"] = delta.min(axis=0).tolist(), delta.max(axis=0).tolist()
+                    rows = np.nonzero((np.ascontiguousarray(delta).view(np.uint32) != 0).any(axis=1))[0]
+                    if not morph.get("sparse"):
+                        acc["bufferView"] = add_view(np.ascontiguousarray(delta).tobytes())
+                    elif len(rows):
+                        acc["sparse"] = {"count": len(rows), "indices": {"bufferView": add_view(rows.astype(np.uint32).tobytes()), "componentType": 5125},
+                                         "values": {"bufferView": add_view(np.ascontiguousarray(delta[rows]).tobytes())}}
+                    accessors.append(acc)
+                    targets[t][name] = len(accessors) - 1
+            prim["targets"] = targets
         if m.indices is not None:
             idx = np.ascontiguousarray(m.indices)
             ct = {np.dtype(np.uint8): 5121, np.dtype(np.uint16): 5123, np.dtype(np.uint32): 5125}[idx.dtype]
             accessors.append({"bufferView": add_view(idx.tobytes()), "componentType": ct, "count": int(idx.size), "type": "SCALAR"})
             prim["indices"] = len(accessors) - 1
         gl_meshes.append({"primitives": [prim]})
+        if morph is not None and morph.get("weights") is not None:
+            gl_meshes[-1]["weights"] = [float(w) for w in np.asarray(morph["weights"], np.float32)]
         node = {"mesh": k, "name": m.name or f"node{k}"}
         if node_matrices is not None:
             node["matrix"] = np.asarray(node_matrices[k], np.float64).T.reshape(16).tolist()
         nodes.append(node)
     roots = list(range(len(nodes)))
     gl_skins = []
+    animated = {tuple(ch["node"][1:]) for a in animations or [] for ch in a["channels"] if not isinstance(ch["node"], int) and ch["path"] != "weights"}
+    joint_node = {}
     for k, skin in enumerate(skins or []):
         if skin is None:
             continue
@@ -509,6 +774,10 @@ def write_glb(path, meshes, materials=None, node_matrices=None, interleave=False
         first = len(nodes)
         for j, local in enumerate(skin["local"]):
             node = {"name": f"joint{k}_{j}", "matrix": np.asarray(local, np.float64).T.reshape(16).tolist()}
+            if (k, j) in animated:
+                node = {"name": node["name"]}
+                node["translation"], node["rotation"], node["scale"] = _trs_of(local)
+            joint_node[(k, j)] = first + j
             kids = [first + c for c, p in enumerate(parents) if p == j]
             if kids:
                 node["children"] = kids
@@ -522,6 +791,22 @@ def write_glb(path, meshes, materials=None, node_matrices=None, interleave=False
            "accessors": accessors, "bufferViews": views, "buffers": [{"byteLength": len(blob)}]}
     if gl_skins:
         doc["skins"] = gl_skins
+    gl_anims = []
+    for a in animations or []:
+        samplers, channels = [], []
+        for ch in a["channels"]:
+            times = np.ascontiguousarray(ch["times"], np.float32).reshape(-1)
+            values = np.ascontiguousarray(ch["values"], np.float32).reshape(len(times) * (3 if ch["interpolation"] == "CUBICSPLINE" else 1), -1)
+            accessors.append({"bufferView": add_view(times.tobytes()), "componentType": 5126, "count": len(times), "type": "SCALAR",
+                              "min": [float(times.min())], "max": [float(times.max())]})
+            typ = {"translation": "VEC3", "scale": "VEC3", "rotation": "VEC4", "weights": "SCALAR"}[ch["path"]]
+            accessors.append({"bufferView": add_view(values.tobytes()), "componentType": 5126, "count": values.size if typ == "SCALAR" else len(values), "type": typ})
+            samplers.append({"input": len(accessors) - 2, "output": len(accessors) - 1, "interpolation": ch["interpolation"]})
+            node = ch["node"] if isinstance(ch["node"], int) else joint_node[tuple(ch["node"][1:])]
+            channels.append({"sampler": len(samplers) - 1, "target": {"node": int(node), "path": ch["path"]}})
+        gl_anims.append({"name": a.get("name", ""), "samplers": samplers, "channels": channels})
+    if gl_anims:
+        doc["animations"] = gl_anims
     if materials:
         doc["materials"] = materials
     js = json.dumps(doc).encode("utf-8")

@@ -866,7 +866,6 @@ class PathTracer:
         (scenes.instance_world_bounds) and sent through PTUpdateInstances.  Does not reset accumulation.
         rebuild_above: update_geometry's policy -- refit, measure, and rebuild from the same palette if sahCost exceeds
         rebuild_above x the cost after the BLAS's last build or rebuild; returns (bounds, "refit" or "rebuild") then."""
-        bvh = self._bvhScene
         off = self._blas_offsets(mesh)
         if rebuild_above is not None:
             bounds = self.skin_geometry(joint_matrices, mesh=mesh)
@@ -890,15 +889,81 @@ class PathTracer:
         bounds = np.array(out, np.float32).reshape(2, 3)
         if rebuild:
             self._builtCost[mesh] = self.geometry_quality(mesh)["sahCost"]
-        if bvh.gpu_instances is not None:
-            from .scenes import instance_world_bounds
-            for k, (m_, _, _) in enumerate(self.scene.instances):
-                if m_ != mesh:
-                    continue
-                l2w = bvh.gpu_instances[k]["localToWorld"].reshape(4, 4).T.astype(np.float64)
-                bvh.blas_instances[k]["aabbMin"], bvh.blas_instances[k]["aabbMax"] = instance_world_bounds(bounds, l2w)
-            plugin.check(self.lib.PTUpdateInstances(self.ctx, bvh.blas_instances.ctypes.data, bvh.blas_instances.shape[0]))
+        self._send_instance_bounds(mesh, bounds)
         return bounds
+
+    # ---- morph targets (include/ptmi_plugin.h Part 12)
+    def set_morph(self, rest_vertices, position_deltas, normal_deltas=None, tangent_deltas=None, mesh: int = None, rest_attrs=None,
+                  target_count: int = None):
+        """PTSetMorph: the morph targets of one BLAS, uploaded once.  rest_vertices (3T, 4) float32 in the BLAS's primitive order
+        (update_geometry's layout).  Each deltas argument is a dense (K, 3T, 3) float32 array (converted by plugin.morph_csr: a corner
+        lists a target unless its delta is exactly +0, +0, +0) or an (offsets, entries) CSR tuple; normal_deltas and tangent_deltas
+        need rest_attrs, the BLAS's abi.TRI_ATTR records of the rest pose -- with rest_attrs every morph_geometry also writes the
+        records.  target_count: default the dense array's K, or for a CSR position stream its largest target + 1.
+        rest_vertices = None removes the BLAS's morph."""
+        off = self._blas_offsets(mesh)
+        nt = self._bvhScene.blas_spans[0 if mesh is None else mesh][3]
+        if rest_vertices is None:
+            plugin.check(self.lib.PTSetMorph(self.ctx, *off, nt, None))
+            return
+        if target_count is None:
+            if isinstance(position_deltas, tuple):
+                target_count = int(np.asarray(position_deltas[1])["target"].max()) + 1 if len(position_deltas[1]) else 1
+            else:
+                target_count = len(position_deltas)
+        d, ntri, keep = plugin.morph_desc(rest_vertices, target_count, position_deltas, normal_deltas, tangent_deltas, rest_attrs)
+        plugin.check(self.lib.PTSetMorph(self.ctx, *off, ntri, C.byref(d)))
+
+    def morph_geometry(self, weights, joint_matrices=None, mesh: int = None, rebuild: bool = False, rebuild_above: float = None):
+        """PTMorphGeometry: one weight per target in (and optionally skin_geometry's joint palette: morph first, then the skin), the
+        BLAS's vertices made on the GPU and refitted (rebuild=True: rebuilt, Part 10's rules) in place -- no vertex is uploaded or
+        read back.  weights: numpy (K,), joint_matrices numpy (J, 3, 4) or (J, 12) or None; or float32 torch tensors on this
+        context's device (PTMorphGeometryDevice, ordered after torch's current stream; both on the device then).  Returns the
+        vertices' bounds, (2, 3) float32: min, max.  HAS_TLAS scene: the world bounds of the mesh's instances are recomputed from
+        those two corners and sent through PTUpdateInstances.  Does not reset accumulation.
+        rebuild_above: update_geometry's policy; returns (bounds, "refit" or "rebuild") then."""
+        off = self._blas_offsets(mesh)
+        if rebuild_above is not None:
+            bounds = self.morph_geometry(weights, joint_matrices, mesh=mesh)
+            if self.geometry_quality(mesh)["sahCost"] <= rebuild_above * self._built_cost(mesh):
+                return bounds, "refit"
+            return self.morph_geometry(weights, joint_matrices, mesh=mesh, rebuild=True), "rebuild"
+        flags = abi.PT_SKIN_REBUILD if rebuild else 0
+        out = (C.c_float * 6)()
+        if isinstance(weights, np.ndarray):
+            w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+            m = None if joint_matrices is None else plugin.joint_palette(joint_matrices)
+            plugin.check(self.lib.PTMorphGeometry(self.ctx, *off, w.ctypes.data, len(w), None if m is None else m.ctypes.data,
+                                                  0 if m is None else m.shape[0], flags, out))
+        else:
+            import torch
+            w, m = weights, joint_matrices
+            assert w.is_contiguous() and w.dtype == torch.float32 and w.dim() == 1
+            assert m is None or (m.is_contiguous() and m.dtype == torch.float32 and m.numel() % 12 == 0 and tuple(m.shape[1:]) in ((3, 4), (12,)))
+            cur = torch.cuda.current_stream(w.device)
+            ext = torch.cuda.ExternalStream(self.stream(), device=w.device)
+            ext.wait_stream(cur)
+            plugin.check(self.lib.PTMorphGeometryDevice(self.ctx, *off, w.data_ptr(), w.numel(), None if m is None else m.data_ptr(),
+                                                        0 if m is None else m.numel() // 12, flags, out))
+            cur.wait_stream(ext)
+        bounds = np.array(out, np.float32).reshape(2, 3)
+        if rebuild:
+            self._builtCost[mesh] = self.geometry_quality(mesh)["sahCost"]
+        self._send_instance_bounds(mesh, bounds)
+        return bounds
+
+    def _send_instance_bounds(self, mesh, bounds):
+        """HAS_TLAS: the world bounds of the mesh's instances from its local box, through PTUpdateInstances"""
+        bvh = self._bvhScene
+        if bvh.gpu_instances is None:
+            return
+        from .scenes import instance_world_bounds
+        for k, (m_, _, _) in enumerate(self.scene.instances):
+            if m_ != mesh:
+                continue
+            l2w = bvh.gpu_instances[k]["localToWorld"].reshape(4, 4).T.astype(np.float64)
+            bvh.blas_instances[k]["aabbMin"], bvh.blas_instances[k]["aabbMax"] = instance_world_bounds(bounds, l2w)
+        plugin.check(self.lib.PTUpdateInstances(self.ctx, bvh.blas_instances.ctypes.data, bvh.blas_instances.shape[0]))
 
     def read_geometry(self):
         """PTReadGeometry: the current (nodes uint8[], tris uint8[], tri_attrs abi.TRI_ATTR[]) of the whole scene.  Synchronising."""

@@ -107,6 +107,12 @@ sig = {
     "PTSkinGeometry": (i32, [vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
     "PTSkinGeometryDevice": (i32, [vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
     "PTSkinVerticesHost": (i32, [C.POINTER(abi.PTSkinDesc), i32, vp, vp, vp, C.POINTER(C.c_float)]),
+    # Part 12 (morph targets)
+    "PTSetMorph": (i32, [vp, C.c_int32, C.c_int32, C.c_int32, i32, C.POINTER(abi.PTMorphDesc)]),
+    "PTMorphGeometry": (i32, [vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
+    "PTMorphGeometryDevice": (i32, [vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
+    "PTMorphVerticesHost": (i32, [C.POINTER(abi.PTMorphDesc), C.POINTER(abi.PTSkinDesc), i32, vp, vp, vp, vp, C.POINTER(C.c_float)]),
+    "PTMorphLayoutHost": (C.c_uint64, [vp, vp, C.c_uint32, vp, vp, vp]),
     "PTGetLastError": (C.c_char_p, []), "PTGetVersion": (i32, []),
 }
 EXPORTED_SYMBOLS = list(sig)
@@ -332,6 +338,95 @@ def skin_vertices(rest_vertices, joints, weights, joint_matrices, rest_attrs=Non
     if not lib.PTSkinVerticesHost(C.byref(d), ntri, m.ctypes.data, out.ctypes.data, None if out_attrs is None else out_attrs.ctypes.data, bounds):
         raise PluginError(abi.PT_ERR_INVALID_ARG, "PTSkinVerticesHost failed: " + lib.PTGetBVHBuildError().decode())
     return out, out_attrs, np.array(bounds, np.float32).reshape(2, 3)
+
+
+def morph_csr(deltas):
+    """Dense deltas (K, 3T, 3) float32 -> one CSR stream (offsets (3T + 1,) uint32, entries abi.MORPH_ENTRY[]): every corner lists, in
+    ascending target order, the targets whose delta is not exactly (+0, +0, +0) -- compared as bit patterns, so a triple with a -0
+    stays listed (acc + w * -0 can differ from acc in the sign of a zero).  Dropping the +0 triple never changes a position under
+    finite weights; a normal or tangent corner left with no entry is copied instead of renormalised (include/ptmi_plugin.h Part 12)."""
+    d = np.ascontiguousarray(deltas, dtype=np.float32)
+    assert d.ndim == 3 and d.shape[2] == 3, d.shape
+    listed = (d.view(np.uint32) != 0).any(axis=2).T                  # (3T, K): the bit patterns, so that -0 is listed
+    offsets = np.zeros(d.shape[1] + 1, np.uint32)
+    offsets[1:] = np.cumsum(listed.sum(axis=1))
+    corner, target = np.nonzero(listed)                                # row-major: by corner, then ascending target
+    entries = np.zeros(len(corner), abi.MORPH_ENTRY)
+    entries["dx"], entries["dy"], entries["dz"] = d[target, corner, 0], d[target, corner, 1], d[target, corner, 2]
+    entries["target"] = target
+    return offsets, entries
+
+
+def morph_stream(stream, corners: int):
+    """A stream as PTMorphDesc takes it: None, a dense (K, 3T, 3) array (morph_csr) or an (offsets, entries) tuple -> (offsets, entries) or None"""
+    if stream is None:
+        return None
+    if isinstance(stream, tuple):
+        off, ent = np.ascontiguousarray(stream[0], dtype=np.uint32), np.ascontiguousarray(stream[1], dtype=abi.MORPH_ENTRY)
+    else:
+        off, ent = morph_csr(stream)
+    assert off.shape == (corners + 1,), (off.shape, corners)
+    return off, ent
+
+
+def morph_desc(rest_vertices, target_count: int, position, normal=None, tangent=None, rest_attrs=None):
+    """A PTMorphDesc over numpy arrays: rest_vertices (3T, 4) float32; position / normal / tangent each a dense (K, 3T, 3) array or an
+    (offsets, entries) CSR tuple (normal and tangent may be None); rest_attrs T abi.TRI_ATTR records or None.  Returns (desc,
+    triangle count, the arrays the desc borrows -- keep them alive while it is used)."""
+    v = np.ascontiguousarray(rest_vertices, dtype=np.float32)
+    assert v.ndim == 2 and v.shape[1] == 4 and v.shape[0] % 3 == 0
+    a = None if rest_attrs is None else np.ascontiguousarray(rest_attrs)
+    assert a is None or a.nbytes == v.shape[0] // 3 * 128
+    streams = [morph_stream(s, v.shape[0]) for s in (position, normal, tangent)]
+    assert streams[0] is not None, "the position stream is required (it may be empty)"
+    d = abi.morph_desc()
+    d.targetCount = int(target_count)
+    d.restVertices = v.ctypes.data
+    d.restAttrs = None if a is None else a.ctypes.data
+    for name, s in zip(("position", "normal", "tangent"), streams):
+        if s is not None:
+            setattr(d, name + "Offsets", s[0].ctypes.data)
+            setattr(d, name + "Entries", s[1].ctypes.data if len(s[1]) else None)
+    return d, v.shape[0] // 3, (v, a, streams)
+
+
+def morph_vertices(rest_vertices, position, weights, normal=None, tangent=None, rest_attrs=None, skin=None, joint_matrices=None, target_count=None):
+    """Morph targets, then the skin, on the host (PTMorphVerticesHost, include/ptmi_plugin.h Part 12): the kernels' rule, byte for byte.
+    weights: (K,) float32.  skin: (joints (3T, 4) uint16, weights (3T, 4) float32) with joint_matrices (J, 3, 4) or (J, 12), or both None.
+    target_count: the morph's (default: the number of weights).
+    Returns (vertices (3T, 4) float32, attrs or None, bounds (2, 3) float32: min, max); raises PluginError for a refused array."""
+    w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+    d, ntri, keep = morph_desc(rest_vertices, len(w) if target_count is None else target_count, position, normal, tangent, rest_attrs)
+    if len(w) != d.targetCount or any(not isinstance(s, tuple) and s is not None and len(s) != len(w) for s in (position, normal, tangent)):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, f"{len(w)} weights do not match the targets")
+    m = sd = keep2 = None
+    if joint_matrices is not None:
+        m = joint_palette(joint_matrices)
+        if skin is not None:
+            sd, _, keep2 = skin_desc(rest_vertices, skin[0], skin[1], m.shape[0])
+    out = np.empty((ntri * 3, 4), np.float32)
+    out_attrs = None if keep[1] is None else np.empty(keep[1].shape, keep[1].dtype)
+    bounds = (C.c_float * 6)()
+    lib = load_library()
+    if not lib.PTMorphVerticesHost(C.byref(d), None if sd is None else C.byref(sd), ntri, w.ctypes.data, None if m is None else m.ctypes.data,
+                                   out.ctypes.data, None if out_attrs is None else out_attrs.ctypes.data, bounds):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTMorphVerticesHost failed: " + lib.PTGetBVHBuildError().decode())
+    return out, out_attrs, np.array(bounds, np.float32).reshape(2, 3)
+
+
+def morph_layout(offsets, entries):
+    """PTSetMorph's device layout of one CSR stream (PTMorphLayoutHost): -> (count (n,) uint32, sliceBase (ceil(n / 64) + 1,) uint32,
+    stored entries abi.MORPH_ENTRY[]).  Slot s of corner c is stored[sliceBase[c // 64] + 64 * s + c % 64], applied only if s < count[c]."""
+    off = np.ascontiguousarray(offsets, dtype=np.uint32)
+    ent = np.ascontiguousarray(entries, dtype=abi.MORPH_ENTRY)
+    n = len(off) - 1
+    lib = load_library()
+    stored = lib.PTMorphLayoutHost(off.ctypes.data, ent.ctypes.data, n, None, None, None)
+    if stored >= 1 << 32:
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "the stored entries do not fit 32 bits")
+    count, base, out = np.zeros(n, np.uint32), np.zeros((n + 63) // 64 + 1, np.uint32), np.zeros(stored, abi.MORPH_ENTRY)
+    lib.PTMorphLayoutHost(off.ctypes.data, ent.ctypes.data, n, count.ctypes.data, base.ctypes.data, out.ctypes.data if stored else None)
+    return count, base, out
 
 
 def build_tlas(instances: np.ndarray):
