@@ -1511,6 +1511,25 @@ PT_DEV void generate_camera_ray(const PTFrameParams& P, uint32_t pixelX, uint32_
 // up to three rays: env shadow (if hasPending && env.valid), light shadow (if hasPending && light.valid) and
 // the next closest-hit ray (if state == PS_TRACE).  Every float and every RNG draw happens in the reference's
 // order, whatever the schedule.
+//
+// OVERLAP (opt-in by template parameter; the wavefront shade and cleanup kernels): a sample that ends on a surface hit
+// AFTER its NEE was prepared (roulette kill, pdf <= 0, NaN BSDF sample) leaves state == PS_ENDING && hasPending, and
+// without the opt-in the next call does nothing but (1) and (3) for it: a whole trace + shade round for two shadow
+// rays.  With the opt-in, if the pixel has another sample to come, (3) is split: the next sample's ray is started in
+// the SAME call (cn.paths++, ro, rd, scatterPdf, maxRoughness, rng, state = PS_TRACE, depth = 0), and radiance, color
+// and sampleIdx are left as the old sample has them.  The slot is then "tracing, previous sample's finish pending":
+// all three rays fly together, and the next call runs (1) on the old radiance, the deferred rest of (3) -- firefly
+// clamp, color += radiance, sampleIdx++, then radiance = 0, throughput = 1, depth = 0 -- and (2) for the new ray's hit.
+// Why nothing changes: the ray of a sample depends on the pixel, the frame parameters and the RNG state only, and
+// (1) and the fold of (3) draw no random number, so the RNG is in the same state whether the ray is drawn before or
+// after them; the ray start writes none of radiance, color, sampleIdx, the pending NEE terms or green, which is all
+// (1) and the fold read; throughput and depth are dead between the roulette kill and the reset.  So every operation on
+// radiance and color, and every draw, happens with the same operands in the same per-path order; only paths++ moves one
+// call earlier.  A pixel's LAST sample never overlaps: PS_DONE and the pixel write are as without the opt-in.
+// The overlapped state needs no state code: it is state == PS_TRACE && hasPending && depth == 0, which no other path
+// reaches -- path_shade_hit sets hasPending only on the branch that then either ends the sample or increments depth
+// (an alpha skip keeps depth but prepares no NEE).  Whoever looks for rays to trace therefore finds all three with
+// the tests it already makes.
 // ------------------------------------------------------------------------------------------
 enum : uint32_t { PS_TRACE = 0u, PS_ENDING = 1u, PS_DONE = 2u };
 
@@ -1524,17 +1543,29 @@ struct PathRegs {
     bool hasPending, green;
 };
 
-PT_DEV void path_start_sample(const PTFrameParams& P, uint32_t pixelX, uint32_t pixelY, PathRegs& r, Counters& cn)
+// A sample starts in two parts: the accumulators of the path, and its first ray.  With OVERLAP (above) the ray of the next
+// sample is started while the previous sample still owns the accumulators.
+PT_DEV void path_reset_sample(PathRegs& r)
 {
-    cn.paths++;
     r.radiance = mk3(0.0f);
     r.throughput = mk3(1.0f);
     r.depth = 0u;
+}
+PT_DEV void path_start_ray(const PTFrameParams& P, uint32_t pixelX, uint32_t pixelY, PathRegs& r, Counters& cn)
+{
+    cn.paths++;
     r.scatterPdf = 0.0f;
     r.maxRoughness = 0.0f;
     generate_camera_ray(P, pixelX, pixelY, r.rng, r.ro, r.rd);
     r.state = PS_TRACE;
 }
+PT_DEV void path_start_sample(const PTFrameParams& P, uint32_t pixelX, uint32_t pixelY, PathRegs& r, Counters& cn)
+{
+    path_reset_sample(r);
+    path_start_ray(P, pixelX, pixelY, r, cn);
+}
+// "tracing, previous sample's finish pending" (OVERLAP above)
+PT_DEV bool path_overlapped(const PathRegs& r) { return r.state == PS_TRACE && r.hasPending && r.depth == 0u; }
 
 // seedRoot / currentSample: RngSeedRoot and CurrentSample of the pass the path belongs to (P's own, or those of pass j of a batch)
 PT_DEV void path_init(const PTFrameParams& P, uint32_t seedRoot, uint32_t currentSample, uint32_t pixelX, uint32_t pixelY, uint32_t pixelIndex,
@@ -1558,10 +1589,11 @@ PT_DEV void path_init(const PTFrameParams& P, uint32_t seedRoot, uint32_t curren
 // to), BEFORE the BSDF is sampled.  The wavefront shade kernel writes them to the slot arrays there, so that their 15
 // registers are free while sample_brdf runs (pt_wavefront.hip); the other schedules keep them in registers and pass nothing.
 struct NoNeeSink { PT_DEV void operator()(PathRegs&) const {} };
-// Source: how a sample starts.  The camera's (the default; every render) draws its jitter and lens numbers from the path's RNG;
-// a radiance query restarts from the caller's ray and draws nothing (pt_wavefront.hip RaySample).
+// Source: how the ray of a sample starts (path_start_ray's part; path_reset_sample is the caller's).  The camera's (the default;
+// every render) draws its jitter and lens numbers from the path's RNG; a radiance query restarts from the caller's ray and draws
+// nothing (pt_wavefront.hip RaySample).
 struct CameraSample {
-    PT_DEV void operator()(const PTFrameParams& P, uint32_t pixelX, uint32_t pixelY, PathRegs& r, Counters& cn) const { path_start_sample(P, pixelX, pixelY, r, cn); }
+    PT_DEV void operator()(const PTFrameParams& P, uint32_t pixelX, uint32_t pixelY, PathRegs& r, Counters& cn) const { path_start_ray(P, pixelX, pixelY, r, cn); }
 };
 
 // ---- (1) radiance += DirectLight(...) * throughput      (util/pathtrace.hlsl:93, deferred until the shadow rays are in)
@@ -1669,20 +1701,30 @@ PT_DEV void path_shade_hit(const DScene& S, const PTFrameParams& P, PathRegs& r,
 }
 
 // ---- (3) end of a sample                                 (PathTracer.compute:77-98)
-template <bool INLINE_RESOLVE, class Source = CameraSample>
+// The fold of a finished sample into the pixel: firefly clamp, color += radiance, sampleIdx++.
+PT_DEV void path_fold_sample(const PTFrameParams& P, PathRegs& r)
+{
+    if (P.UseFireflyFilter) {
+        float lum = luminance3(r.radiance);
+        if (lum > P.MaxFireflyLuminance) r.radiance = r.radiance * (P.MaxFireflyLuminance / lum);
+    }
+    r.color = r.color + r.radiance;
+    r.sampleIdx++;
+}
+
+// OVERLAP: a sample that ended with its NEE pending starts the next sample's ray here, unless it is the pixel's last
+// (path_step's header).  `source` has ONE call site whatever OVERLAP is (the camera ray is ~150 instructions).
+template <bool INLINE_RESOLVE, class Source = CameraSample, bool OVERLAP = false>
 PT_DEV void path_end_sample(const PTFrameParams& P, PathRegs& r, uint32_t pixelX, uint32_t pixelY, uint32_t pixelIndex,
                             const float4* __restrict__ accumulated, float4* __restrict__ output, Counters& cn, Source source = Source())
 {
+    bool startRay = false;
     if (r.state == PS_ENDING && !r.hasPending) {
-        if (P.UseFireflyFilter) {
-            float lum = luminance3(r.radiance);
-            if (lum > P.MaxFireflyLuminance) r.radiance = r.radiance * (P.MaxFireflyLuminance / lum);
-        }
-        r.color = r.color + r.radiance;
-        r.sampleIdx++;
+        path_fold_sample(P, r);
         const uint32_t numSamples = P.SamplesPerPass > 1 ? (uint32_t)P.SamplesPerPass : 1u;
         if (r.sampleIdx < numSamples) {
-            source(P, pixelX, pixelY, r, cn);
+            path_reset_sample(r);
+            startRay = true;
         } else if (!INLINE_RESOLVE) {
             r.state = PS_DONE;
         } else {
@@ -1702,18 +1744,27 @@ PT_DEV void path_end_sample(const PTFrameParams& P, PathRegs& r, uint32_t pixelX
             cn.pixelsWritten++;
             r.state = PS_DONE;
         }
+    } else if (OVERLAP && r.state == PS_ENDING && r.sampleIdx + 1u < (P.SamplesPerPass > 1 ? (uint32_t)P.SamplesPerPass : 1u)) {
+        r.depth = 0u;                                             // dead until the deferred reset; 0 marks the overlapped state
+        startRay = true;
     }
+    if (startRay) source(P, pixelX, pixelY, r, cn);
 }
 
-template <bool STATS, bool INLINE_RESOLVE = true, class NeeSink = NoNeeSink, class Source = CameraSample>
+template <bool STATS, bool INLINE_RESOLVE = true, class NeeSink = NoNeeSink, class Source = CameraSample, bool OVERLAP = false>
 PT_DEV void path_step(const DScene& S, const PTFrameParams& P, PathRegs& r, const HitRecord& rec, bool occEnv, bool occLight,
                       uint32_t pixelX, uint32_t pixelY, uint32_t pixelIndex,
                       const float4* __restrict__ accumulated, float4* __restrict__ output, Counters& cn, NeeSink neeSink = NeeSink(),
                       Source source = Source())
 {
+    const bool deferred = OVERLAP && path_overlapped(r);
     path_apply_pending(r, occEnv, occLight);
+    if (deferred) {                                               // the previous sample's finish, then the rest of this sample's start
+        path_fold_sample(P, r);
+        path_reset_sample(r);
+    }
     if (r.state == PS_TRACE) path_shade_hit<STATS, NeeSink>(S, P, r, rec, cn, neeSink);
-    path_end_sample<INLINE_RESOLVE, Source>(P, r, pixelX, pixelY, pixelIndex, accumulated, output, cn, source);
+    path_end_sample<INLINE_RESOLVE, Source, OVERLAP>(P, r, pixelX, pixelY, pixelIndex, accumulated, output, cn, source);
 }
 
 // Wave-level helpers (wave64).

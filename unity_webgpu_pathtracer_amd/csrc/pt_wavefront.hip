@@ -28,6 +28,9 @@ namespace {
 #define PT_WF_SHARDS 8u         // chunk counters, one per XCD
 
 // flags word: [1:0] state | [2] hasPending | [4:3] env.valid | [5] light.valid | [6] green | [18:7] sampleIdx | [31:19] depth
+// The overlapped state of pt_device.h ("tracing, previous sample's finish pending") is state TRACE + hasPending + depth 0, with
+// green and sampleIdx still the previous sample's: no bit and no state code of its own (code 3 stays unused), unambiguous at any
+// spp and bounce limit, and ray_exists() reports its three rays as it reports everyone's.
 PT_DEV uint32_t pack_flags(const PathRegs& r)
 {
     return (r.state & 3u) | ((r.hasPending ? 1u : 0u) << 2) | ((r.env.valid & 3u) << 3) | ((r.light.valid & 1u) << 5) |
@@ -129,19 +132,18 @@ PT_DEV bool wf_pixel(const PTRayMap& rm, const PTWfBuffers& B, uint32_t slot, ui
     return slot < rm.count;
 }
 template <class MAP> constexpr bool kRayMap = std::is_same<MAP, PTRayMap>::value;
-// How a sample of a list entry starts (the Source of path_step): path_start_sample with the entry's ray in place of the camera's,
-// and no RNG draw.  The entry is two 16-byte vector loads by slot: {origin.xyz, direction.x} {direction.yz, rng, reserved}.
+// How the ray of a list entry's sample starts (the Source of path_step): path_start_ray with the entry's ray in place of the
+// camera's, and no RNG draw.  Like path_start_ray it leaves radiance, throughput and depth alone: with the next-sample overlap the
+// previous sample's radiance is still live when it runs (pt_device.h).
+// The entry is two 16-byte vector loads by slot: {origin.xyz, direction.x} {direction.yz, rng, reserved}.
 struct RaySample {
     const PTRadianceRay* rays; uint32_t slot;
-    PT_DEV void operator()(const PTFrameParams&, uint32_t, uint32_t, PathRegs& r, Counters& cn) const { start(r, cn); }
-    PT_DEV void start(PathRegs& r, Counters& cn) const
+    PT_DEV void operator()(const PTFrameParams&, uint32_t, uint32_t, PathRegs& r, Counters& cn) const { start_ray(r, cn); }
+    PT_DEV void start_ray(PathRegs& r, Counters& cn) const
     {
         const float4* e = (const float4*)(rays + slot);
         const float4 a = e[0], b = e[1];
         cn.paths++;
-        r.radiance = mk3(0.0f);
-        r.throughput = mk3(1.0f);
-        r.depth = 0u;
         r.scatterPdf = 0.0f;
         r.maxRoughness = 0.0f;
         r.ro = mk3(a.x, a.y, a.z);
@@ -160,7 +162,8 @@ PT_DEV void ray_path_init(const PTRayMap& rm, uint32_t slot, PathRegs& r, Counte
     r.env.contribution = mk3(0.0f); r.light.contribution = mk3(0.0f);
     r.neeOrigin = mk3(0.0f); r.pendThroughput = mk3(0.0f);
     r.hasPending = false; r.green = false;
-    RaySample{rm.rays, slot}.start(r, cn);
+    path_reset_sample(r);
+    RaySample{rm.rays, slot}.start_ray(r, cn);
 }
 
 template <class MAP = PTTileMap>
@@ -996,10 +999,12 @@ PT_DEV bool shade_slot(const DScene& S, const PTFrameParams& P, const MAP& tm, c
             B.pthr[s2] = f4(q.pendThroughput, 0.0f);
         }
     };
+    // OVERLAP (pt_device.h): a sample that ends with its NEE pending starts its successor's ray in this step, so the slot's next
+    // trace round carries the camera ray next to the two shadow rays instead of the shadow rays alone
     if constexpr (kRayMap<MAP>)
-        path_step<STATS, false, Sink, RaySample>(S, P, r, ch, occEnv, occLight, 0u, 0u, 0u, nullptr, nullptr, cn, Sink{B, slot}, RaySample{tm.rays, pixelSlot});
+        path_step<STATS, false, Sink, RaySample, true>(S, P, r, ch, occEnv, occLight, 0u, 0u, 0u, nullptr, nullptr, cn, Sink{B, slot}, RaySample{tm.rays, pixelSlot});
     else
-        path_step<STATS, false, Sink>(S, P, r, ch, occEnv, occLight, px, py, py * P.OutputWidth + px, nullptr, nullptr, cn, Sink{B, slot});
+        path_step<STATS, false, Sink, CameraSample, true>(S, P, r, ch, occEnv, occLight, px, py, py * P.OutputWidth + px, nullptr, nullptr, cn, Sink{B, slot});
     // the store addresses are formed HERE from a slot the compiler cannot connect with the one the loads used: otherwise the
     // thirteen 64-bit load addresses stay in registers across the whole step to be reused by these stores
     uint32_t storeSlot = slot;
@@ -1307,10 +1312,12 @@ __global__ __launch_bounds__(256, 2) void pt_wf_cleanup(DScene S, PTFrameParams 
                     else traverse_cwbvh<STATS>(S, r.ro, r.rd, false, ch.h, st, cn);
                     cn.closestRays++;
                 }
+                // OVERLAP: a slot can arrive with the previous sample's finish pending (all three rays above exist for it), and
+                // the loop may as well go on the way the shade kernel would have
                 if constexpr (kRayMap<MAP>)
-                    path_step<STATS, false, NoNeeSink, RaySample>(S, P, r, ch, occEnv, occLight, 0u, 0u, 0u, nullptr, nullptr, cn, NoNeeSink(), RaySample{tm.rays, slot});
+                    path_step<STATS, false, NoNeeSink, RaySample, true>(S, P, r, ch, occEnv, occLight, 0u, 0u, 0u, nullptr, nullptr, cn, NoNeeSink(), RaySample{tm.rays, slot});
                 else
-                    path_step<STATS, false>(S, P, r, ch, occEnv, occLight, px, py, py * P.OutputWidth + px, nullptr, nullptr, cn);
+                    path_step<STATS, false, NoNeeSink, CameraSample, true>(S, P, r, ch, occEnv, occLight, px, py, py * P.OutputWidth + px, nullptr, nullptr, cn);
             }
             B.flags[slot] = pack_flags(r);
             B.color[slot] = f4(r.color, 0.0f);
