@@ -1030,6 +1030,77 @@ PT_API int PTMorphVerticesHost(const PTMorphDesc* desc, const PTSkinDesc* skinOr
 PT_API uint64_t PTMorphLayoutHost(const uint32_t* offsets, const PTMorphEntry* entries, uint32_t cornerCount, uint32_t* outCount, uint32_t* outSliceBase,
                                   PTMorphEntry* outEntries);                                                               /* the device layout of one stream, for tests */
 
+/* =====================================================================================================================
+ * Part 13: irradiance gathers.  How much light arrives AT a surface point?  Part 8 answers it along one ray; a lightmap texel
+ * or a light probe wants the irradiance E at a receiver: a position and a normal.  The host hands over a list of receivers and
+ * a sample range, the path tracer builds every gather direction itself, lights the receiver directly (NEE at the receiver:
+ * point and spot lights included) and runs the samples of an entry in parallel.  An addition beside the reference's ABI,
+ * detected by symbol; PTGetVersion is unchanged.
+ *
+ * The rule (bit-exact).  A receiver is a white Lambertian point with normal N; irradiance is PI times the radiance it sends out.
+ *  - Seeding.  Sample j (0 <= j < samples) of entry i is independent of the entry's other samples: its RNG starts at
+ *    s = seed_i; pt_rng_next(&s); s += firstSample + j  (uint32 arithmetic) and depends on nothing else, so the samples
+ *    [a, a + n) of one call are the samples of any split of that range into calls.
+ *  - The receiver step runs in the order of the render's material branch (path_shade_hit) with the same code for everything
+ *    but the BSDF.  No alpha draw and no roulette at the receiver.  hit.position = P, hit.normal = hit.ffnormal = N (as
+ *    given, never re-normalised).  The NEE origin is P + N * PT_EPSILON.  Environment NEE and light NEE take the render's
+ *    draws, light pick and EvalLight arithmetic; the BSDF is Lambert, f = pdf = max(dot(N, L), 0) / PT_PI; the validity codes
+ *    stay (a traced ray that adds nothing when pdf <= 0).  Then two draws r1, r2:
+ *    L = onb_to_world(make_onb(N), cosine_sample_hemisphere(r1, r2)), pdf = L_local.z / PT_PI.  With pdf > 0 the path goes
+ *    on with direction L, origin P + L * PT_EPSILON, throughput (1, 1, 1) exactly (the Lambert term over the pdf, never
+ *    divided out), scatterPdf = pdf, maxRoughness = 1 and depth 1; else the sample ends.  Either way the receiver's NEE is
+ *    pending with throughput 1 and the radiance so far is 0.
+ *  - The rest of the path is the render's own: firefly filter, Russian roulette, environment, lights, textures and HAS_TLAS of
+ *    `params`; MaxRayBounces counts the receiver as the first bounce.  SamplesPerPass is not read.  A sample's value is
+ *    e_j = c_j * PT_PI per channel (one fp32 multiply), c_j being the sample's radiance after the fold (the firefly filter
+ *    acts on c_j).
+ *  - out[i].rgb = (e_0 + e_1 + ...) / (float)samples, summed in ascending j; out[i].m2 = the sum of luminance3(e_j)^2 in the
+ *    same order (the sample variance of the luminance is (m2 - samples * lum(rgb)^2) / (samples - 1)).  Nothing past `count`
+ *    is written.
+ *  - PTGatherRays writes, for slot i * samples + j, the ray {origin, direction} and the RNG state the receiver step leaves:
+ *    what PTTraceRadiance continues from.  A sample that ended at the receiver gets a NaN direction.  It needs a scene (the
+ *    NEE draws depend on the lights and the environment) and counts nothing in PTStats.
+ *  - Stream-ordered on the context's stream like Part 8; dRecv, dOut and dRays are 16-byte aligned.  Slot i * samples + j
+ *    carries sample j of entry i; a launch sequence holds floor(2^21 / samples) whole entries, longer lists are cut into
+ *    such chunks, each on the next state set, joined after the last one.
+ *  - PTStats: paths = count x samples; rays and fetches by the render's definitions (the receiver's shadow rays and light
+ *    fetch included); pixelsWritten and pixelsRead do not move.  With profiling on, every chunk is one entry of PTGetTimings.
+ *  - Schedules 1, 2 and 3; schedules 0 and 4 return PT_ERR_UNSUPPORTED, as do samples == 0, samples > 65536 and
+ *    MaxRayBounces > 8191.  PT_ERR_INVALID_ARG for a NULL or misaligned pointer and (PTGatherIrradianceHost) a nonzero
+ *    `reserved`; PT_ERR_NO_SCENE before PTSetScene.  count == 0 returns PT_OK and launches nothing.  No CPU fallback.
+ * ===================================================================================================================== */
+#define PT_GATHER_MAX_SAMPLES 65536u
+
+typedef struct PTReceiver {       /* 32 bytes: two 16-byte loads */
+    float    position[3];
+    uint32_t seed;
+    float    normal[3];           /* unit normal, used as given */
+    uint32_t reserved;            /* must be 0 (PTGatherIrradianceHost checks it; the device path ignores it) */
+} PTReceiver;
+
+typedef struct PTIrradiance {     /* 16 bytes */
+    float    rgb[3];              /* irradiance E: mean over the samples */
+    float    m2;                  /* sum over the samples of luminance(e_j)^2 */
+} PTIrradiance;
+
+#ifdef __cplusplus
+static_assert(sizeof(PTReceiver) == 32, "PTReceiver is 32 bytes");
+static_assert(sizeof(PTIrradiance) == 16, "PTIrradiance is 16 bytes");
+#else
+_Static_assert(sizeof(PTReceiver) == 32, "PTReceiver is 32 bytes");
+_Static_assert(sizeof(PTIrradiance) == 16, "PTIrradiance is 16 bytes");
+#endif
+
+/* Device pointers, stream-ordered on the context's stream. */
+PT_API int PTGatherIrradiance(PTContext* ctx, const PTFrameParams* params, const PTReceiver* dRecv, uint64_t count, uint32_t firstSample, uint32_t samples,
+                              PTIrradiance* dOut);
+/* Host arrays: staged through device buffers the context keeps and grows; synchronous. */
+PT_API int PTGatherIrradianceHost(PTContext* ctx, const PTFrameParams* params, const PTReceiver* recv, uint64_t count, uint32_t firstSample, uint32_t samples,
+                                  PTIrradiance* out);
+/* dRays: count * samples entries, entry-major. */
+PT_API int PTGatherRays(PTContext* ctx, const PTFrameParams* params, const PTReceiver* dRecv, uint64_t count, uint32_t firstSample, uint32_t samples,
+                        PTRadianceRay* dRays);
+
 /* Text of the last error on the calling thread ("" if none). */
 PT_API const char* PTGetLastError(void);
 /* Library/ABI version: (major << 16) | minor. */

@@ -274,6 +274,21 @@ class PTRadiance(C.Structure):
 assert C.sizeof(PTRadianceRay) == 32 and C.sizeof(PTRadiance) == 16
 
 
+# ---- irradiance gathers (include/ptmi_plugin.h Part 13)
+PT_GATHER_MAX_SAMPLES = 65536
+
+
+class PTReceiver(C.Structure):
+    _fields_ = [("position", C.c_float * 3), ("seed", C.c_uint32), ("normal", C.c_float * 3), ("reserved", C.c_uint32)]
+
+
+class PTIrradiance(C.Structure):
+    _fields_ = [("rgb", C.c_float * 3), ("m2", C.c_float)]
+
+
+assert C.sizeof(PTReceiver) == 32 and C.sizeof(PTIrradiance) == 16
+
+
 # ---------------------------------------------------------------------------------------
 # Part 10: geometry rebuilds and tree quality (PTRebuildGeometry / PTMeasureGeometry / PTMeasureBVHArrays)
 # ---------------------------------------------------------------------------------------

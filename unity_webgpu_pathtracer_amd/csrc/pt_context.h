@@ -228,6 +228,10 @@ struct PTContext {
     struct Radiance {
         DeviceBuffer rays, out;
     } radiance;
+    // irradiance gathers (PTGatherIrradianceHost): likewise
+    struct Gather {
+        DeviceBuffer recv, out;
+    } gather;
     // scene updates (PTUpdateInstances / Lights / Materials): two generations of what an update rewrites, allocated on the first
     // update of each kind and discarded by PTSetScene.  cur = -1 while PTSetScene's own buffers are current.
     struct UpdGroup {

@@ -1330,9 +1330,26 @@ struct NeeRay { v3 dir; v3 contribution; uint32_t valid; };
 
 PT_DEV v3 nee_scatter_pos(const SurfHit& hit) { return hit.position + hit.normal * PT_EPSILON; }
 
+// Bsdf: what the two halves evaluate at the sampled direction, f = bsdf(mat, V, L, onb, pdf, sh).  The default is the material's
+// Disney BSDF (every render); an irradiance gather puts a white Lambertian receiver in its place (LambertBsdf) and shares every
+// draw, the light pick and the EvalLight arithmetic below.
+struct DisneyBsdf {
+    PT_DEV v3 operator()(const Material& mat, v3 V, v3 L, const Onb& onb, float& pdf, const BsdfShared& sh) const { return eval_brdf_onb(mat, V, L, onb, pdf, sh); }
+};
+// f = pdf = max(dot(N, L), 0) / PT_PI with the receiver's normal as given (include/ptmi_plugin.h Part 13)
+struct LambertBsdf {
+    v3 N;
+    PT_DEV v3 operator()(const Material&, v3, v3 L, const Onb&, float& pdf, const BsdfShared&) const
+    {
+        pdf = pt_max(dot3(N, L), 0.0f) / PT_PI;
+        return mk3(pdf);
+    }
+};
+
 // environment half of DirectLight (:123-160)
+template <class Bsdf = DisneyBsdf>
 PT_DEV void nee_prepare_environment(const DScene& S, const PTFrameParams& P, v3 rayDir, const SurfHit& hit, const Material& mat,
-                                    uint32_t& rng, NeeRay& out, const BsdfShared& sh, const Onb& ffOnb)
+                                    uint32_t& rng, NeeRay& out, const BsdfShared& sh, const Onb& ffOnb, Bsdf bsdf = Bsdf())
 {
     out.valid = 0u;
     out.contribution = mk3(0.0f);
@@ -1351,7 +1368,7 @@ PT_DEV void nee_prepare_environment(const DScene& S, const PTFrameParams& P, v3 
     out.dir = lightDir;
     out.valid = 1u;
     float spdf = 0.0f;
-    v3 sf = eval_brdf_onb(mat, -rayDir, lightDir, ffOnb, spdf, sh);          // ffOnb = make_onb(hit.ffnormal)
+    v3 sf = bsdf(mat, -rayDir, lightDir, ffOnb, spdf, sh);          // ffOnb = make_onb(hit.ffnormal)
     if (spdf > 0.0f) {
         float misWeight = power_heuristic(lightPdf, spdf);
         if (misWeight > 0.0f) {
@@ -1362,9 +1379,9 @@ PT_DEV void nee_prepare_environment(const DScene& S, const PTFrameParams& P, v3 
 }
 
 // analytic-light half of DirectLight (:162-170) + SampleOneLight (:47-58) + EvalLight (:60-114)
-template <bool STATS>
+template <bool STATS, class Bsdf = DisneyBsdf>
 PT_DEV void nee_prepare_light(const DScene& S, v3 rayDir, const SurfHit& hit, const Material& mat, v3 scatterPos,
-                              uint32_t& rng, NeeRay& out, Counters& cn, const BsdfShared& sh, const Onb& ffOnb)
+                              uint32_t& rng, NeeRay& out, Counters& cn, const BsdfShared& sh, const Onb& ffOnb, Bsdf bsdf = Bsdf())
 {
     out.valid = 0u;
     out.contribution = mk3(0.0f);
@@ -1428,7 +1445,7 @@ PT_DEV void nee_prepare_light(const DScene& S, v3 rayDir, const SurfHit& hit, co
     out.dir = lsDirection;
     out.valid = 1u;
     float pdf = 0.0f;
-    v3 f = eval_brdf_onb(mat, -rayDir, lsDirection, onb_of_normal(hit.normal, hit.ffnormal, ffOnb), pdf, sh);       // EvalBRDF(..., hit.normal, ...): GetONB(normal)
+    v3 f = bsdf(mat, -rayDir, lsDirection, onb_of_normal(hit.normal, hit.ffnormal, ffOnb), pdf, sh);       // EvalBRDF(..., hit.normal, ...): GetONB(normal)
     float lightPdf = 1.0f;
     if (lsPdf > 0.0f) lightPdf = lsPdf;
     out.contribution = Li * f / lightPdf;

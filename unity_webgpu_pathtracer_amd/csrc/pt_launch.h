@@ -246,6 +246,22 @@ struct PTRayMap {
 // zeroOutputFirst are not read.  Schedule 4 is not available.
 // PTCameraRays (pt_kernels.hip): entry i = path_init's ray and RNG state of pixel indices[i] (NULL: pixel i); count <= 2^31
 hipError_t pt_launch_camera_rays(const PTFrameParams& P, const uint32_t* indices, uint32_t count, PTRadianceRay* rays, hipStream_t stream);
+
+// ---- irradiance gathers (include/ptmi_plugin.h Part 13; pt_gather.hip): a launch sequence over RECEIVERS x SAMPLES ----
+// Slot s carries sample s % samples of entry s / samples (entry-major: neighbouring lanes share a receiver).  The sequence is the
+// ray list's with two kernels exchanged: pt_wf_gather_init does the receiver step where pt_wf_init would load a ray, and
+// pt_wf_gather_resolve folds an entry's samples where pt_wf_resolve_rays would write one entry per slot.  Everything between them
+// is the PTRayMap instantiations of trace, shade and cleanup with SamplesPerPass forced to 1, so the Source of the ray map is never
+// called (rays == NULL) and no sample ever overlaps a successor.
+struct PTGatherMap {
+    const PTReceiver* recv;        // 16-byte aligned
+    uint32_t entries, samples;     // entries * samples <= PT_RADIANCE_CHUNK
+    uint32_t firstSample;
+};
+// the two kernels of a gather's launch sequence on state set B, and PTGatherRays (slots [0, entries * samples) of one launch)
+hipError_t pt_launch_gather_init(const DScene& S, const PTFrameParams& P, const PTGatherMap& gm, const PTWfBuffers& B, bool fullStats, hipStream_t stream);
+hipError_t pt_launch_gather_resolve(const PTGatherMap& gm, const PTWfBuffers& B, PTIrradiance* out, hipStream_t stream);
+hipError_t pt_launch_gather_rays(const DScene& S, const PTFrameParams& P, const PTGatherMap& gm, PTRadianceRay* rays, hipStream_t stream);
 #ifndef PT_WF_FUSED_GROUPS
 #define PT_WF_FUSED_GROUPS 2u   // schedule 4: groups of 64 path contexts a persistent wave owns (power of two <= 4: numSlots is a multiple of 256).
                                 // Sponza-class 1080p / 8 spp, one pass in flight: 1: 29.9 ms, 2: 25.2, 4: 27.9, 8: 31.4
@@ -260,7 +276,7 @@ hipError_t pt_launch_camera_rays(const PTFrameParams& P, const uint32_t* indices
 #endif
 
 // ---- ONE wavefront launch sequence: what to render (the slot mapping), from and into what, on which stream, by which schedule ----
-enum PTWfMapKind : uint32_t { PT_WF_MAP_TILES, PT_WF_MAP_LIST, PT_WF_MAP_RAYS };
+enum PTWfMapKind : uint32_t { PT_WF_MAP_TILES, PT_WF_MAP_LIST, PT_WF_MAP_RAYS, PT_WF_MAP_GATHER };
 struct PTWfLaunch {
     const DScene* scene;
     const PTFrameParams* params;
@@ -270,9 +286,10 @@ struct PTWfLaunch {
         PTTileMap tiles;                    // a pass (or a sub-frame of one) over the context's 16x16 blocks
         PTListMap list;                     // a pass over a block list
         PTRayMap rays;                      // a radiance query
+        PTGatherMap gather;                 // an irradiance gather
     };
     const float4* accumulated;
-    void* output;                           // the frame (float4 per pixel); PT_WF_MAP_RAYS: the PTRadiance array
+    void* output;                           // the frame (float4 per pixel); PT_WF_MAP_RAYS: the PTRadiance array; PT_WF_MAP_GATHER: the PTIrradiance array
     const PTWfBuffers* buffers;             // the state set the sequence runs on
     unsigned long long* counters;           // the context's 16 counters (PTStats order)
     bool fullStats;
@@ -283,6 +300,6 @@ struct PTWfLaunch {
     uint32_t iterationsOverride;            // 0 = spp * (bounces + 2) + 4, capped by buffers->maxIterations
 };
 // Enqueues the sequence on L.stream without host synchronisation; launchesOut (may be null): kernel launches enqueued.
-// hipErrorNotSupported for schedule 4 over a list or rays.  pt_wavefront.hip is compiled twice with different scheduler flags
+// hipErrorNotSupported for schedule 4 over a list, rays or a gather.  pt_wavefront.hip is compiled twice with different scheduler flags
 // (csrc/Makefile); which compilation's kernels run is decided behind this one entry point.
 hipError_t pt_launch_wavefront(const PTWfLaunch& L, uint32_t* launchesOut);

@@ -20,29 +20,12 @@
 // same per-path order as in schedule 0, so frames and counters are bit-identical between schedules and to the oracle.
 #include "pt_device.h"
 #include "pt_launch.h"
+#include "pt_wf_state.h"
 #include <type_traits>
 
 namespace {
 
 #define PT_WF_CHUNK 64u         // slots per work chunk of the persistent trace kernel (= one scan window per ray kind)
-#define PT_WF_SHARDS 8u         // chunk counters, one per XCD
-
-// flags word: [1:0] state | [2] hasPending | [4:3] env.valid | [5] light.valid | [6] green | [18:7] sampleIdx | [31:19] depth
-// The overlapped state of pt_device.h ("tracing, previous sample's finish pending") is state TRACE + hasPending + depth 0, with
-// green and sampleIdx still the previous sample's: no bit and no state code of its own (code 3 stays unused), unambiguous at any
-// spp and bounce limit, and ray_exists() reports its three rays as it reports everyone's.
-PT_DEV uint32_t pack_flags(const PathRegs& r)
-{
-    return (r.state & 3u) | ((r.hasPending ? 1u : 0u) << 2) | ((r.env.valid & 3u) << 3) | ((r.light.valid & 1u) << 5) |
-           ((r.green ? 1u : 0u) << 6) | ((r.sampleIdx & 0xFFFu) << 7) | ((r.depth & 0x1FFFu) << 19);
-}
-PT_DEV uint32_t fl_state(uint32_t f) { return f & 3u; }
-PT_DEV bool fl_pending(uint32_t f) { return (f >> 2) & 1u; }
-PT_DEV uint32_t fl_env(uint32_t f) { return (f >> 3) & 3u; }
-PT_DEV uint32_t fl_light(uint32_t f) { return (f >> 5) & 1u; }
-
-PT_DEV float4 f4(v3 v, float w) { return make_float4(v.x, v.y, v.z, w); }
-PT_DEV v3 xyz(float4 v) { return mk3(v.x, v.y, v.z); }
 
 // float4 state array k of the set (pt_launch.h PT_F4_*), addressed from ONE base pointer
 PT_DEV float4* f4_array(const PTWfBuffers& B, uint32_t k) { return B.f4base + (size_t)k * B.f4stride; }
@@ -54,46 +37,7 @@ PT_DEV void fetch_ray(const PTWfBuffers& B, uint32_t slot, uint32_t kind, v3& o,
     d = xyz(rec[1]);
 }
 
-PT_DEV void store_path(const PTWfBuffers& B, uint32_t slot, const PathRegs& r, bool writeNee)
-{
-    B.flags[slot] = pack_flags(r);
-    B.rng[slot] = r.rng;
-    B.ray[0][2u * slot] = f4(r.ro, r.scatterPdf);
-    B.ray[0][2u * slot + 1u] = f4(r.rd, r.maxRoughness);
-    B.rad[slot] = f4(r.radiance, 0.0f);
-    B.thr[slot] = f4(r.throughput, 0.0f);
-    B.color[slot] = f4(r.color, 0.0f);
-    if (writeNee) {
-        B.ray[1][2u * slot] = f4(r.neeOrigin, 0.0f);
-        B.ray[1][2u * slot + 1u] = f4(r.env.dir, 0.0f);
-        B.ray[2][2u * slot] = f4(r.neeOrigin, 0.0f);
-        B.ray[2][2u * slot + 1u] = f4(r.light.dir, 0.0f);
-        B.envC[slot] = f4(r.env.contribution, 0.0f);
-        B.lightC[slot] = f4(r.light.contribution, 0.0f);
-        B.pthr[slot] = f4(r.pendThroughput, 0.0f);
-    }
-}
-
-// per-wave counter rows: one wave owns a row, so a plain read-modify-write is race-free across launches of one stream
-template <bool STATS>
-PT_DEV void flush_counters(const Counters& cn, unsigned long long* rows, uint32_t row, uint32_t lane)
-{
-    uint32_t vals[PT_NUM_COUNTERS];
-    counters_to_array(cn, vals);
-    unsigned long long* p = rows + (size_t)row * 16u;
-#pragma unroll
-    for (int i = 0; i < PT_NUM_COUNTERS; ++i) {
-        if (!STATS && (i >= 3 && i <= 9)) continue;
-        if (!STATS && i >= 12) continue;
-        if (i == 12) {
-            uint32_t m = wave_max_u32(vals[i]);
-            if (lane == 0 && m > p[i]) p[i] = m;
-        } else {
-            uint32_t s = wave_sum_u32(vals[i]);
-            if (lane == 0 && s) p[i] += s;
-        }
-    }
-}
+// pack_flags / store_path / flush_counters: pt_wf_state.h (shared with pt_gather.hip)
 
 // ------------------------------------------------------------------------------------------
 // init: every owned pixel starts its first sample (camera ray in the slot, state = TRACE)
@@ -1446,7 +1390,8 @@ size_t pt_wf_arena_layout(char* base, uint32_t numSlots, uint32_t residentWaves,
 // L.orderAfter (may be null) is the event of the previous pass's resolve: this pass's resolve reads that pass's output as
 // AccumulatedOutput and, with ping-pong frames, overwrites the frame that resolve was still reading.
 // MAP = PTListMap: the pass over a block list; nothing is zeroed and the frame is copied instead.
-// MAP = PTRayMap: a radiance query: L.output is the PTRadiance array, nothing is ordered, zeroed or copied.
+// MAP = PTRayMap: a radiance query: L.output is the PTRadiance array, nothing is ordered, zeroed or copied.  An irradiance gather
+// (PT_WF_MAP_GATHER) runs the same instantiations between pt_gather.hip's init and resolve kernels.
 // UNIT_A: this compilation of the file is the one without the post-RA scheduler (csrc/Makefile).  It is entered for the plain
 // refill trace only, the other one for everything else -- each instantiates only the kernels it can launch.
 namespace {
@@ -1504,7 +1449,10 @@ hipError_t launch_sequence(const PTWfLaunch& L, const MAP& tm, uint32_t* launche
             return hipErrorNotSupported;
         }
     }
-    hipLaunchKernelGGL(pt_wf_init<MAP>, dim3(nb), dim3(256), 0, stream, P, batch, tm, B);
+    // an irradiance gather is the ray list's sequence with its own first and last kernel (pt_gather.hip)
+    const bool gather = kRays && L.mapKind == PT_WF_MAP_GATHER;
+    if (gather) { if ((e = pt_launch_gather_init(S, P, L.gather, B, fullStats, stream)) != hipSuccess) return e; }
+    else hipLaunchKernelGGL(pt_wf_init<MAP>, dim3(nb), dim3(256), 0, stream, P, batch, tm, B);
     launches++;
     const uint32_t spp = P.SamplesPerPass > 1 ? (uint32_t)P.SamplesPerPass : 1u;
     const uint32_t bounces = P.MaxRayBounces > 1u ? P.MaxRayBounces : 1u;
@@ -1560,7 +1508,8 @@ hipError_t launch_sequence(const PTWfLaunch& L, const MAP& tm, uint32_t* launche
     if (L.zeroOutputFirst &&
         (e = hipMemsetAsync(output, 0, (size_t)P.OutputWidth * P.OutputHeight * sizeof(float4), stream)) != hipSuccess) return e;
     if constexpr (kRays) {
-        hipLaunchKernelGGL(pt_wf_resolve_rays, dim3(nbPass), dim3(256), 0, stream, P, tm, B, (PTRadiance*)L.output);
+        if (gather) { if ((e = pt_launch_gather_resolve(L.gather, B, (PTIrradiance*)L.output, stream)) != hipSuccess) return e; }
+        else hipLaunchKernelGGL(pt_wf_resolve_rays, dim3(nbPass), dim3(256), 0, stream, P, tm, B, (PTRadiance*)L.output);
     } else if constexpr (kList) {
         // pixels outside the list keep Accumulated, bit for bit: one copy of the frame, then the resolve overwrites the listed blocks
         if (L.accumulated &&
@@ -1593,6 +1542,19 @@ hipError_t launch_mapped(const PTWfLaunch& L, uint32_t* launchesOut)
         M.orderAfter = nullptr;
         M.zeroOutputFirst = false;
         return launch_sequence<PTRayMap, UNIT_A>(M, M.rays, launchesOut);
+    case PT_WF_MAP_GATHER: {
+        // the ray map's kernels with one sample per slot: they never call its Source, so there is no list behind it
+        const PTRayMap slots = {nullptr, L.gather.entries * L.gather.samples};
+        PTFrameParams P1 = *L.params;
+        P1.SamplesPerPass = 1;
+        M.params = &P1;
+        M.batch = PTBatch{};
+        M.batch.count = 1u;
+        M.accumulated = nullptr;
+        M.orderAfter = nullptr;
+        M.zeroOutputFirst = false;
+        return launch_sequence<PTRayMap, UNIT_A>(M, slots, launchesOut);
+    }
     }
     return hipErrorInvalidValue;
 }

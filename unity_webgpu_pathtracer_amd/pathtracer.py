@@ -431,6 +431,78 @@ class PathTracer:
         cur.wait_stream(ext)                   # torch's later work sees the results -- and any reuse of these buffers comes after
         return out
 
+    # ---- irradiance gathers (include/ptmi_plugin.h Part 13)
+    def _receivers(self, positions, normals, seeds):
+        """(n, 8) float32 PTReceiver rows -- position xyz, seed bits, normal xyz, 0 -- of the kind the positions are (numpy or a
+        device tensor); seeds None = the entry index."""
+        if isinstance(positions, np.ndarray) or not hasattr(positions, "device"):
+            pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+            nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+            assert pos.shape == nrm.shape, (pos.shape, nrm.shape)
+            n = pos.shape[0]
+            recv = np.zeros((n, 8), np.float32)
+            recv[:, 0:3], recv[:, 4:7] = pos, nrm
+            sd = np.arange(n, dtype=np.uint32) if seeds is None else np.ascontiguousarray(np.asarray(seeds).astype(np.uint32)).reshape(n)
+            recv[:, 3] = sd.view(np.float32)
+            return recv
+        import torch
+        assert positions.dtype == torch.float32 and normals.dtype == torch.float32 and positions.shape == normals.shape, (positions.shape, normals.shape)
+        n = positions.reshape(-1, 3).shape[0]
+        recv = torch.zeros((n, 8), dtype=torch.float32, device=positions.device)
+        recv[:, 0:3], recv[:, 4:7] = positions.reshape(-1, 3), normals.reshape(-1, 3).to(positions.device)
+        if seeds is None:
+            sd = torch.arange(n, dtype=torch.int32, device=positions.device)
+        else:
+            sd = torch.as_tensor(seeds, device=positions.device).reshape(n).to(torch.int64).bitwise_and(0xFFFFFFFF)
+            sd = torch.where(sd >= 2 ** 31, sd - 2 ** 32, sd).to(torch.int32)
+        recv.view(torch.int32)[:, 3] = sd
+        return recv
+
+    def irradiance(self, positions, normals, spp: int = 64, first_sample: int = 0, seeds=None, params: abi.PTFrameParams = None):
+        """Irradiance at surface points on the GPU: lightmap texels, light probes.  Every receiver is a white Lambertian point;
+        its `spp` samples run in parallel, lit directly by every light type (NEE at the receiver) and by the render's own paths
+        from there on (bounces -- the receiver counts as the first --, roulette, firefly filter from `params`, default this tracer's).
+
+        positions, normals: (n, 3) float32, unit normals; seeds: (n,) uint32, None = the entry index.  Samples
+        [first_sample, first_sample + spp) of an entry are the same whatever calls they are split into.
+          numpy arrays -> PTGatherIrradianceHost, returns numpy;
+          torch tensors on this context's device -> PTGatherIrradiance zero-copy, ordered against torch's current stream both ways.
+        Returns (n, 4) float32: irradiance rgb (mean over the samples) and m2, the sum of the samples' squared luminance."""
+        p = self._radiance_params(params)
+        recv = self._receivers(positions, normals, seeds)
+        n = recv.shape[0]
+        if isinstance(recv, np.ndarray):
+            out = np.empty((n, 4), np.float32)
+            plugin.check(self.lib.PTGatherIrradianceHost(self.ctx, C.byref(p), recv.ctypes.data, n, first_sample & 0xFFFFFFFF, spp, out.ctypes.data))
+            return out
+        import torch
+        out = torch.empty((n, 4), dtype=torch.float32, device=recv.device)
+        cur = torch.cuda.current_stream(recv.device)
+        ext = torch.cuda.ExternalStream(self.stream(), device=recv.device)
+        ext.wait_stream(cur)
+        plugin.check(self.lib.PTGatherIrradiance(self.ctx, C.byref(p), recv.data_ptr(), n, first_sample & 0xFFFFFFFF, spp, out.data_ptr()))
+        cur.wait_stream(ext)
+        return out
+
+    def gather_rays(self, positions, normals, spp: int = 64, first_sample: int = 0, seeds=None, params: abi.PTFrameParams = None):
+        """PTGatherRays: the gather ray and RNG state each sample of irradiance() leaves the receiver with, as radiance() takes
+        them: (n * spp, 8) float32 rows, entry-major (row i * spp + j = sample first_sample + j of entry i); a sample that ended at
+        the receiver has a NaN direction.  numpy in, numpy out; device tensors in, a device tensor out."""
+        import torch
+        p = self._radiance_params(params)
+        recv = self._receivers(positions, normals, seeds)
+        as_numpy = isinstance(recv, np.ndarray)
+        dev = torch.device(f"cuda:{self.device}")
+        d_recv = torch.from_numpy(recv).to(dev) if as_numpy else recv
+        n = recv.shape[0]
+        rays = torch.empty((n * max(spp, 0), 8), dtype=torch.float32, device=dev)
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
+        ext.wait_stream(cur)
+        plugin.check(self.lib.PTGatherRays(self.ctx, C.byref(p), d_recv.data_ptr(), n, first_sample & 0xFFFFFFFF, spp, rays.data_ptr()))
+        cur.wait_stream(ext)
+        return rays.cpu().numpy() if as_numpy else rays
+
     def camera_ray(self, x: float, y: float, params: abi.PTFrameParams = None) -> np.ndarray:
         """The pinhole ray through the centre of pixel (x, y): util/camera.hlsl:13-42 without jitter and lens, in float32 with
         the device's operation order.  Returns one (8,) float32 ray row with tmax = PT_FAR_PLANE."""

@@ -113,6 +113,10 @@ sig = {
     "PTMorphGeometryDevice": (i32, [vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
     "PTMorphVerticesHost": (i32, [C.POINTER(abi.PTMorphDesc), C.POINTER(abi.PTSkinDesc), i32, vp, vp, vp, vp, C.POINTER(C.c_float)]),
     "PTMorphLayoutHost": (C.c_uint64, [vp, vp, C.c_uint32, vp, vp, vp]),
+    # Part 13 (irradiance gathers)
+    "PTGatherIrradiance": (i32, [vp, C.POINTER(abi.PTFrameParams), vp, C.c_uint64, C.c_uint32, C.c_uint32, vp]),
+    "PTGatherIrradianceHost": (i32, [vp, C.POINTER(abi.PTFrameParams), vp, C.c_uint64, C.c_uint32, C.c_uint32, vp]),
+    "PTGatherRays": (i32, [vp, C.POINTER(abi.PTFrameParams), vp, C.c_uint64, C.c_uint32, C.c_uint32, vp]),
     "PTGetLastError": (C.c_char_p, []), "PTGetVersion": (i32, []),
 }
 EXPORTED_SYMBOLS = list(sig)
