@@ -1101,6 +1101,98 @@ PT_API int PTGatherIrradianceHost(PTContext* ctx, const PTFrameParams* params, c
 PT_API int PTGatherRays(PTContext* ctx, const PTFrameParams* params, const PTReceiver* dRecv, uint64_t count, uint32_t firstSample, uint32_t samples,
                         PTRadianceRay* dRays);
 
+/* =====================================================================================================================
+ * Part 14: lightmap charts.  Part 13 answers "what is the irradiance at these receivers"; this part makes the receivers of a
+ * lightmap from a mesh and an atlas size, on the GPU, and turns the gathered list back into an image: PTRasterizeChart
+ * rasterises the UV chart of one BLAS of the CURRENT scene into a compacted device list of PTReceiver entries, one per covered
+ * texel; PTGatherIrradiance gathers; PTResolveLightmap scatters the PTIrradiance list into an RGBA image and dilates the chart
+ * borders.  No vertex, receiver or texel crosses the bus.  An addition beside the reference's ABI, detected by symbol;
+ * PTGetVersion is unchanged.
+ *
+ * The rasterisation rule (chart_rule.h; coverage is decided in integers, so any evaluation order gives the same bytes).
+ *  - Inputs.  The BLAS is named as in Parts 9 to 12 (bvhOffset, triOffset, triAttributeOffset, triangleCount).  instance: -1 for
+ *    the identity transform, else the index of a PTGpuInstance record as it currently stands on the device, whose three offsets
+ *    must be the ones given: its localToWorld places the receivers, its worldToLocal turns the normals.  width, height: 1 ...
+ *    8192.  Lightmap UVs: 6 floats per triangle (u0 v0 u1 v1 u2 v2), indexed by primIdx (the BLAS's primitive order), or NULL:
+ *    uv0, uv1, uv2 of the BLAS's current PTTriangleAttributes.  Geometry is the CURRENT generation of the triangle records (v0,
+ *    e1, e2, primIdx) and attribute records: a chart made after a refit, rebuild, skin or morph sees the deformed mesh.
+ *  - Snap.  Corner k of primitive p: X_k = (int64)rintf(u_k * (float)(width * 256)), Y_k = (int64)rintf(v_k * (float)(height *
+ *    256)): one fp32 multiply, round half even, 8 sub-texel bits.  A triangle with a non-finite UV or any |X|, |Y| > 2^23 is not
+ *    in the chart (this is how a caller excludes triangles).  No wrap, no repeat.
+ *  - Edge functions, int64, exact: E(a, b; s) = (b.X - a.X) * (s.Y - a.Y) - (b.Y - a.Y) * (s.X - a.X); A = E(p0, p1; p2).  A
+ *    triangle with A == 0 is skipped, and so is one whose fp32 cross(e1, e2) (cross3's expression) has a squared length (dot3's)
+ *    that is 0 or not finite.  A negative A flips the sign of all three edge values: mirrored charts rasterise.
+ *  - Coverage.  Texel (x, y), 0 <= x < width, 0 <= y < height, is sampled at s = (256 x + 128, 256 y + 128) and covered by p
+ *    when E(p1, p2; s), E(p2, p0; s) and E(p0, p1; s), so signed, are all >= 0 (edges are inclusive).  Its owner is the covering
+ *    primitive with the lowest primIdx: shared edges are watertight, overlaps deterministic.
+ *  - Barycentrics.  b1 = (float)((double)E(p2, p0; s) / (double)A) (corner 1, the role of a hit's u), b2 = (float)((double)
+ *    E(p0, p1; s) / (double)A) (corner 2, a hit's v); the conversions are exact, the fp64 divide and the narrowing correctly
+ *    rounded.  Corner 0 gets 1.0f - b1 - b2.
+ *  - Receiver.  Local position per component (v0 + e1 * b1) + e2 * b2 from the triangle record, so the receiver lies on the
+ *    triangle the intersector sees; world position per row r  ((m[r] * x + m[4 + r] * y) + m[8 + r] * z) + m[12 + r]  with m =
+ *    localToWorld (instance -1: the local position).  Normal: n = (n0 * (1.0f - b1 - b2) + n1 * b1) + n2 * b2 per component, then
+ *    n * (1 / sqrt((n.x*n.x + n.y*n.y) + n.z*n.z)); with an instance then t[r] = ((n.x * w[4r] + n.y * w[4r + 1]) + n.z *
+ *    w[4r + 2]) + 0.0f * w[4r + 3] with w = worldToLocal, normalised the same way (the render's HAS_TLAS hit).  If any component
+ *    of the result is not finite, cross(e1, e2) takes n's place through the same steps.  seed = seedBase + texelIndex in uint32
+ *    arithmetic, texelIndex = y * width + x; reserved = 0.  Every fp32 operator is one binary32 operation, left to right.
+ *  - Output.  The covered texels in ascending texelIndex: texels[i] and recv[i].  A texel's receiver depends on its own index,
+ *    its owner and the inputs only.
+ *
+ * PTRasterizeChart.  Device arrays (dTexels 4-byte, dRecv and dUvs 16-byte aligned), on the context's stream and ordered like
+ * PTGatherRays; every scene update joins that stream.  *count receives the number of covered texels: an 8-byte read-back, so
+ * THE CALL SYNCHRONISES WITH THE CONTEXT STREAM.  dTexels == NULL and dRecv == NULL: only the count.  count > capacity:
+ * PT_ERR_INVALID_ARG with *count set and nothing written.  The compaction runs on the device (owner map, per-block counts, a
+ * scan, emit).  The first call on a scene reads the node and triangle buffers back once and the first call on a BLAS walks it,
+ * as Part 9's first update does.  Memory, in the context, grown on demand, kept across PTSetScene, freed by PTDestroy: 4 bytes
+ * per texel (the owner map), 4 per 256 texels, 8 per triangle; PTResolveLightmap with dilate > 0: 16 bytes per texel.
+ * Errors: PT_ERR_NO_SCENE before PTSetScene; PT_ERR_INVALID_ARG for a NULL context, desc or count, a misaligned pointer, only one
+ * of dTexels and dRecv, offsets that name no BLAS, a triangleCount that is not the BLAS's, an instance out of range or of
+ * another BLAS, a size outside 1 ... 8192, a nonzero reserved field.
+ *
+ * PTResolveLightmap.  image: width * height RGBA float32, 16-byte aligned.  Every texel is cleared to 0, then image[texels[i]] =
+ * (irr[i].rgb, 1.0f).  Texel indices must be unique (with duplicates one of them is written); an index >= width * height is
+ * skipped (the host twin refuses it).  Then `dilate` passes, 0 ... 16; pass p reads the image of pass p - 1: a texel with w != 0
+ * is copied; a texel with w == 0 looks at its 8 neighbours inside the image in the order (dy, dx) = (-1,-1), (-1,0), (-1,1),
+ * (0,-1), (0,1), (1,-1), (1,0), (1,1); with n > 0 of them at w != 0 it becomes (((0 + rgb_a) + rgb_b) + ...) / (float)n over
+ * those, in that order, with w = 0.5f, else it stays 0.  The result ends in the caller's image; the second image is the
+ * context's.  Stream-ordered on the context's stream, not synchronising, needs no scene.
+ *
+ * The host twins (no context, no GPU; they return 1, or 0 with PTGetBVHBuildError() set).  PTRasterizeChartHost: tris = the BLAS's
+ * 3 * triangleCount rows and attrs = its triangleCount records as PTReadGeometry returns them (from triOffset, from
+ * triAttributeOffset); the desc's offsets and instance are not read; localToWorld and worldToLocal: 16 floats each in the
+ * record's memory order, or both NULL.  count > capacity returns 0 with *count set.  PTResolveLightmapHost: the same image.
+ * ===================================================================================================================== */
+#define PT_CHART_MAX_SIZE   8192u
+#define PT_CHART_MAX_DILATE 16u
+
+typedef struct PTChartDesc {
+    uint32_t structSize;          /* sizeof(PTChartDesc) of the caller's header; members are only appended */
+    int32_t  bvhOffset, triOffset, triAttributeOffset;
+    int32_t  triangleCount;
+    int32_t  instance;            /* -1: identity */
+    uint32_t width, height;       /* 1 ... PT_CHART_MAX_SIZE */
+    uint32_t seedBase;
+    uint32_t reserved[3];         /* must be 0 */
+} PTChartDesc;
+
+#ifdef __cplusplus
+static_assert(sizeof(PTChartDesc) == 48, "PTChartDesc is 48 bytes");
+#else
+_Static_assert(sizeof(PTChartDesc) == 48, "PTChartDesc is 48 bytes");
+#endif
+
+/* Device arrays, on the context's stream; synchronises (the count). */
+PT_API int PTRasterizeChart(PTContext* ctx, const PTChartDesc* desc, const float* dUvsOrNull, uint32_t* dTexels, PTReceiver* dRecv, uint64_t capacity,
+                            uint64_t* count);
+PT_API int PTRasterizeChartHost(const PTChartDesc* desc, const PTFloat4* tris, const PTTriangleAttributes* attrs, const float* uvsOrNull,
+                                const float* localToWorldOrNull, const float* worldToLocalOrNull, uint32_t* texels, PTReceiver* recv, uint64_t capacity,
+                                uint64_t* count);                                                          /* host twin, no GPU */
+/* Device arrays, stream-ordered on the context's stream. */
+PT_API int PTResolveLightmap(PTContext* ctx, const uint32_t* dTexels, const PTIrradiance* dIrr, uint64_t count, uint32_t width, uint32_t height,
+                             uint32_t dilate, void* dImage);
+PT_API int PTResolveLightmapHost(const uint32_t* texels, const PTIrradiance* irr, uint64_t count, uint32_t width, uint32_t height, uint32_t dilate,
+                                 void* image);                                                             /* host twin, no GPU */
+
 /* Text of the last error on the calling thread ("" if none). */
 PT_API const char* PTGetLastError(void);
 /* Library/ABI version: (major << 16) | minor. */

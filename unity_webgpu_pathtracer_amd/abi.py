@@ -289,6 +289,30 @@ class PTIrradiance(C.Structure):
 assert C.sizeof(PTReceiver) == 32 and C.sizeof(PTIrradiance) == 16
 
 
+# ---- lightmap charts (include/ptmi_plugin.h Part 14)
+PT_CHART_MAX_SIZE = 8192
+PT_CHART_MAX_DILATE = 16
+
+
+class PTChartDesc(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("bvhOffset", C.c_int32), ("triOffset", C.c_int32), ("triAttributeOffset", C.c_int32),
+                ("triangleCount", C.c_int32), ("instance", C.c_int32), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("seedBase", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+assert C.sizeof(PTChartDesc) == 48
+
+
+def chart_desc(width: int, height: int, triangle_count: int, offsets=(0, 0, 0), instance: int = -1, seed: int = 0) -> PTChartDesc:
+    """A PTChartDesc with structSize set: the BLAS by its three offsets, the atlas size, the instance (-1: identity), seedBase."""
+    d = PTChartDesc()
+    d.structSize = C.sizeof(PTChartDesc)
+    d.bvhOffset, d.triOffset, d.triAttributeOffset = (int(o) for o in offsets)
+    d.triangleCount, d.instance = int(triangle_count), int(instance)
+    d.width, d.height, d.seedBase = int(width), int(height), int(seed) & 0xFFFFFFFF
+    return d
+
+
 # ---------------------------------------------------------------------------------------
 # Part 10: geometry rebuilds and tree quality (PTRebuildGeometry / PTMeasureGeometry / PTMeasureBVHArrays)
 # ---------------------------------------------------------------------------------------

@@ -15,6 +15,7 @@
 #include "bvh_quality.h"
 #include "skin_rule.h"
 #include "morph_rule.h"
+#include "chart_rule.h"
 #include "ptmi_plugin.h"
 
 namespace {
@@ -162,6 +163,31 @@ PT_API uint64_t PTMorphLayoutHost(const uint32_t* offsets, const PTMorphEntry* e
     if (outSliceBase) std::copy(L.sliceBase.begin(), L.sliceBase.end(), outSliceBase);
     if (outEntries) std::copy(L.entries.begin(), L.entries.end(), outEntries);
     return stored;
+}
+// Lightmap charts on the host (chart_host.cpp; Part 14 has the rule).  No GPU involved.
+PT_API int PTRasterizeChartHost(const PTChartDesc* desc, const PTFloat4* tris, const PTTriangleAttributes* attrs, const float* uvsOrNull,
+                                const float* localToWorldOrNull, const float* worldToLocalOrNull, uint32_t* texels, PTReceiver* recv, uint64_t capacity,
+                                uint64_t* count)
+{
+    if (!desc || !count) { g_buildError = "NULL desc or count"; return 0; }
+    *count = 0;
+    if (desc->structSize < sizeof(PTChartDesc) || desc->structSize > 4096u) {
+        g_buildError = "PTChartDesc.structSize is not set (must be sizeof(PTChartDesc) of the host's header)";
+        return 0;
+    }
+    if (desc->triangleCount <= 0) { g_buildError = "triangleCount <= 0"; return 0; }
+    if (desc->reserved[0] || desc->reserved[1] || desc->reserved[2]) { g_buildError = "PTChartDesc.reserved != 0"; return 0; }
+    const ptchart::ChartInput in = {tris, attrs, uvsOrNull, localToWorldOrNull, worldToLocalOrNull, (uint32_t)desc->triangleCount, desc->width, desc->height,
+                                    desc->seedBase};
+    if (!ptchart::chart_rasterize_host(in, texels, recv, capacity, *count, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+PT_API int PTResolveLightmapHost(const uint32_t* texels, const PTIrradiance* irr, uint64_t count, uint32_t width, uint32_t height, uint32_t dilate, void* image)
+{
+    if (!ptchart::chart_resolve_host(texels, irr, count, width, height, dilate, (float*)image, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
 }
 PT_API void DestroyBVH(int index) { free_slot(g_bvhs, index); }
 PT_API int IsBVHReady(int index) { return get_slot(g_bvhs, index) != nullptr; }

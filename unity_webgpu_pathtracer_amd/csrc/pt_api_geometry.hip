@@ -9,6 +9,8 @@ namespace {
 
 size_t al256(size_t b) { return (b + 255) / 256 * 256; }
 
+} // namespace
+
 // What the first geometry update of a scene reads back, once (synchronising): the node buffer, the .w words of the triangle
 // rows and, with HAS_TLAS, the instances' offsets.  PTSetScene's own buffers serve in every generation: a refit never
 // rewrites row n1, imask or a primIdx, and instance updates keep the offsets rows.
@@ -34,6 +36,8 @@ int ensure_host_copy(PTContext* c)
     return PT_OK;
 }
 
+namespace {
+
 // end of the span that starts at `off`: the next larger distinct offset among the instances' (field 0 nodes, 1 rows), or `total`
 uint64_t span_end(const PTContext::Geometry& G, int field, int32_t off, uint64_t total)
 {
@@ -44,6 +48,8 @@ uint64_t span_end(const PTContext::Geometry& G, int field, int32_t off, uint64_t
     }
     return end;
 }
+
+} // namespace
 
 // The plan of the BLAS the three offsets name; made (and the BLAS walked) on its first update.  triCount == 0 (PTMeasureGeometry):
 // the BLAS's own count -- the plan's, or for a BLAS without one the count its row span holds.
@@ -90,6 +96,8 @@ int find_plan(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t attrOf
     out = &G.plans.back();
     return PT_OK;
 }
+
+namespace {
 
 // The tree of the builder's rule for dVerts, built on the update stream at the BLAS's offsets of the generation being written
 // (after the carry-over copy).  Refusals return before anything of the context changes; on success the BLAS's plan is the new tree's.

@@ -7,6 +7,7 @@
 #include "pt_quality.h"
 #include "pt_skin.h"
 #include "pt_morph.h"
+#include "pt_lightmap.h"
 #include "bvh_refit.h"
 #include "bvh_builder_gpu.h"
 
@@ -232,6 +233,14 @@ struct PTContext {
     struct Gather {
         DeviceBuffer recv, out;
     } gather;
+    // lightmap charts (PTRasterizeChart / PTResolveLightmap): grown on demand, kept across PTSetScene
+    struct Lightmap {
+        DeviceBuffer owner;                     // 4 B per texel: the owner map
+        DeviceBuffer blockBase;                 // 4 B per 256-texel block, then the 8-byte total
+        DeviceBuffer prims;                     // 4 B per triangle twice: the record of every primitive, the list of large records
+        DeviceBuffer image;                     // 16 B per texel: the resolve's second image
+        PinnedBuffer count;                     // the total, read back
+    } lightmap;
     // scene updates (PTUpdateInstances / Lights / Materials): two generations of what an update rewrites, allocated on the first
     // update of each kind and discarded by PTSetScene.  cur = -1 while PTSetScene's own buffers are current.
     struct UpdGroup {
@@ -354,6 +363,10 @@ int denoise_frame(PTContext* c, const PTDenoiseParams* params, const void* dSrc,
 int begin_update(PTContext* c, PTContext::UpdGroup& g, size_t genBytes, size_t stagingBytes, int& target);
 int stage_host(PTContext* c, PTContext::UpdGroup& g, int target, const void* src, size_t bytes, void* dst);
 int end_update(PTContext* c, PTContext::UpdGroup& g, int target);
+// pt_api_geometry.hip: what the first geometry call of a scene reads back, once (synchronising), and the plan of the BLAS the three
+// offsets name (made, and the BLAS walked, on its first use); triCount == 0: the BLAS's own count
+int ensure_host_copy(PTContext* c);
+int find_plan(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t attrOffset, uint32_t triCount, PTContext::GeomPlan*& out);
 int set_scene(PTContext* c, const PTSceneDesc* hostScene, bool validate);      // pt_api_context.hip; PTGroupSetScene validates once
 int drain_events(PTContext* c);                                                 // pt_api_context.hip
 int ensure_frames(PTContext* c, uint32_t w, uint32_t h);                        // pt_api_render.hip

@@ -458,7 +458,7 @@ class PathTracer:
         recv.view(torch.int32)[:, 3] = sd
         return recv
 
-    def irradiance(self, positions, normals, spp: int = 64, first_sample: int = 0, seeds=None, params: abi.PTFrameParams = None):
+    def irradiance(self, positions=None, normals=None, spp: int = 64, first_sample: int = 0, seeds=None, params: abi.PTFrameParams = None, receivers=None):
         """Irradiance at surface points on the GPU: lightmap texels, light probes.  Every receiver is a white Lambertian point;
         its `spp` samples run in parallel, lit directly by every light type (NEE at the receiver) and by the render's own paths
         from there on (bounces -- the receiver counts as the first --, roulette, firefly filter from `params`, default this tracer's).
@@ -467,9 +467,16 @@ class PathTracer:
         [first_sample, first_sample + spp) of an entry are the same whatever calls they are split into.
           numpy arrays -> PTGatherIrradianceHost, returns numpy;
           torch tensors on this context's device -> PTGatherIrradiance zero-copy, ordered against torch's current stream both ways.
+        receivers (instead of positions, normals and seeds): ready-made (n, 8) float32 PTReceiver rows, as chart_receivers returns them.
         Returns (n, 4) float32: irradiance rgb (mean over the samples) and m2, the sum of the samples' squared luminance."""
         p = self._radiance_params(params)
-        recv = self._receivers(positions, normals, seeds)
+        if receivers is not None:
+            assert positions is None and normals is None and seeds is None, "receivers come instead of positions, normals and seeds"
+            assert receivers.dtype == np.float32 or str(receivers.dtype) == "torch.float32", receivers.dtype
+            assert receivers.ndim == 2 and receivers.shape[1] == 8, receivers.shape
+            recv = np.ascontiguousarray(receivers) if isinstance(receivers, np.ndarray) else receivers.contiguous()
+        else:
+            recv = self._receivers(positions, normals, seeds)
         n = recv.shape[0]
         if isinstance(recv, np.ndarray):
             out = np.empty((n, 4), np.float32)
@@ -502,6 +509,88 @@ class PathTracer:
         plugin.check(self.lib.PTGatherRays(self.ctx, C.byref(p), d_recv.data_ptr(), n, first_sample & 0xFFFFFFFF, spp, rays.data_ptr()))
         cur.wait_stream(ext)
         return rays.cpu().numpy() if as_numpy else rays
+
+    # ---- lightmap charts (include/ptmi_plugin.h Part 14)
+    def _chart_desc(self, width, height, mesh, instance, seed) -> abi.PTChartDesc:
+        bvh = self._bvhScene
+        off = self._blas_offsets(mesh)
+        if bvh.gpu_instances is None:
+            assert instance in (None, -1), "a flat scene has no instances"
+            inst = -1
+        elif instance is None:
+            inst = [i for i, rec in enumerate(self.scene.instances) if rec[0] == mesh][0]      # the mesh's first instance
+        else:
+            inst = int(instance)
+        return abi.chart_desc(width, height, bvh.blas_spans[0 if mesh is None else mesh][3], off, inst, seed)
+
+    def chart_receivers(self, width: int, height: int, mesh: int = None, instance: int = None, uvs=None, seed: int = 0):
+        """PTRasterizeChart: the lightmap receivers of one mesh, made on the GPU from the scene's CURRENT geometry (after any
+        update_geometry / skin_geometry / morph_geometry).  One receiver per texel of the width x height atlas whose centre the
+        mesh's UV chart covers; where triangles overlap in UV space the one with the lowest primitive index owns the texel.
+
+        mesh names the BLAS as update_geometry does (None on a flat scene).  HAS_TLAS: `instance` picks whose transform places the
+        receivers (default: the mesh's first instance; -1: the mesh's local space).  uvs: (T, 6) float32 lightmap UVs per primitive
+        (u0 v0 u1 v1 u2 v2; numpy, or a float32 tensor on this context's device), None = the attribute records' uv0 .. uv2; a
+        triangle with a NaN UV is left out.  seed: receiver i gets seed + its texel index.
+        Returns (texels, receivers): device tensors, (n,) int32 holding the texel indices y * width + x in ascending order (all
+        < 2^26), and (n, 8) float32 PTReceiver rows that irradiance() takes as `receivers=`.  Synchronises (the count is read back).
+        Several meshes in one atlas are the caller's business: concatenate the lists of several calls (torch.cat) and resolve once;
+        texels two meshes both cover then appear twice, and resolve_lightmap writes one of them."""
+        import torch
+        dev = torch.device(f"cuda:{self.device}")
+        d = self._chart_desc(width, height, mesh, instance, seed)
+        d_uvs = None
+        if uvs is not None:
+            d_uvs = uvs if isinstance(uvs, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(uvs, dtype=np.float32)).to(dev)
+            assert d_uvs.dtype == torch.float32 and d_uvs.is_contiguous() and d_uvs.numel() == d.triangleCount * 6 and d_uvs.device == dev, (d_uvs.shape, d_uvs.dtype)
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
+        ext.wait_stream(cur)
+        count = C.c_uint64()
+        uv_ptr = None if d_uvs is None else d_uvs.data_ptr()
+        # a small atlas: arrays for every texel, one call; a large one: count first
+        cap = int(width) * int(height)
+        if not (0 < cap <= 1 << 22):
+            plugin.check(self.lib.PTRasterizeChart(self.ctx, C.byref(d), uv_ptr, None, None, 0, C.byref(count)))
+            cap = count.value
+        texels = torch.empty((max(cap, 1),), dtype=torch.int32, device=dev)
+        recv = torch.empty((max(cap, 1), 8), dtype=torch.float32, device=dev)
+        plugin.check(self.lib.PTRasterizeChart(self.ctx, C.byref(d), uv_ptr, texels.data_ptr(), recv.data_ptr(), cap, C.byref(count)))
+        cur.wait_stream(ext)
+        return texels[:count.value], recv[:count.value]
+
+    def resolve_lightmap(self, texels, irradiance, width: int, height: int, dilate: int = 2):
+        """PTResolveLightmap: scatter gathered irradiance back into an atlas and dilate the chart borders, on the GPU.  texels: (n,)
+        int32 / uint32 device tensor of unique texel indices (chart_receivers'), irradiance: (n, 4) float32 device tensor
+        (irradiance()'s).  Returns an (height, width, 4) float32 device tensor: rgb, and w = 1 on the list's texels, 0.5 on texels a
+        dilation pass filled (the mean of the filled ones among the 8 neighbours), 0 elsewhere.  dilate: 0 ... 16 passes."""
+        import torch
+        assert texels.element_size() == 4 and texels.dim() == 1 and texels.is_contiguous(), (texels.dtype, texels.shape)
+        assert irradiance.dtype == torch.float32 and irradiance.is_contiguous() and irradiance.shape == (texels.shape[0], 4), irradiance.shape
+        dev = texels.device
+        n = texels.shape[0]
+        image = torch.empty((max(int(height), 1), max(int(width), 1), 4), dtype=torch.float32, device=dev)
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
+        ext.wait_stream(cur)
+        plugin.check(self.lib.PTResolveLightmap(self.ctx, texels.data_ptr() if n else None, irradiance.data_ptr() if n else None, n, int(width), int(height),
+                                                int(dilate), image.data_ptr()))
+        cur.wait_stream(ext)
+        return image
+
+    def bake_lightmap(self, width: int, height: int, spp: int = 64, mesh: int = None, instance: int = None, uvs=None, dilate: int = 2, seed: int = 0,
+                      first_sample: int = 0, params: abi.PTFrameParams = None, as_tensor: bool = False):
+        """A lightmap of one mesh: chart_receivers, PTGatherIrradiance over them, resolve_lightmap -- nothing but the final image
+        leaves the device.  spp, first_sample and params are irradiance()'s (samples [first_sample, first_sample + spp) of every
+        texel; two bakes over disjoint ranges fold by 5.18's rule), the rest chart_receivers' and resolve_lightmap's.
+        Returns (height, width, 4) float32 -- numpy, or with as_tensor a device tensor; w tells baked (1), dilated (0.5), empty (0)."""
+        texels, recv = self.chart_receivers(width, height, mesh=mesh, instance=instance, uvs=uvs, seed=seed)
+        if recv.shape[0]:
+            irr = self.irradiance(receivers=recv, spp=spp, first_sample=first_sample, params=params)
+        else:                                                       # a chart that covers nothing: an empty image
+            irr = recv.new_empty((0, 4))
+        image = self.resolve_lightmap(texels, irr, width, height, dilate=dilate)
+        return image if as_tensor else image.cpu().numpy()
 
     def camera_ray(self, x: float, y: float, params: abi.PTFrameParams = None) -> np.ndarray:
         """The pinhole ray through the centre of pixel (x, y): util/camera.hlsl:13-42 without jitter and lens, in float32 with

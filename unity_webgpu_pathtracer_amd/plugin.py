@@ -117,6 +117,11 @@ sig = {
     "PTGatherIrradiance": (i32, [vp, C.POINTER(abi.PTFrameParams), vp, C.c_uint64, C.c_uint32, C.c_uint32, vp]),
     "PTGatherIrradianceHost": (i32, [vp, C.POINTER(abi.PTFrameParams), vp, C.c_uint64, C.c_uint32, C.c_uint32, vp]),
     "PTGatherRays": (i32, [vp, C.POINTER(abi.PTFrameParams), vp, C.c_uint64, C.c_uint32, C.c_uint32, vp]),
+    # Part 14 (lightmap charts)
+    "PTRasterizeChart": (i32, [vp, C.POINTER(abi.PTChartDesc), vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "PTRasterizeChartHost": (i32, [C.POINTER(abi.PTChartDesc), vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "PTResolveLightmap": (i32, [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
+    "PTResolveLightmapHost": (i32, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
     "PTGetLastError": (C.c_char_p, []), "PTGetVersion": (i32, []),
 }
 EXPORTED_SYMBOLS = list(sig)
@@ -431,6 +436,44 @@ def morph_layout(offsets, entries):
     count, base, out = np.zeros(n, np.uint32), np.zeros((n + 63) // 64 + 1, np.uint32), np.zeros(stored, abi.MORPH_ENTRY)
     lib.PTMorphLayoutHost(off.ctypes.data, ent.ctypes.data, n, count.ctypes.data, base.ctypes.data, out.ctypes.data if stored else None)
     return count, base, out
+
+
+def rasterize_chart(tris, attrs, width: int, height: int, uvs=None, local_to_world=None, world_to_local=None, seed: int = 0):
+    """A lightmap chart on the host (PTRasterizeChartHost, include/ptmi_plugin.h Part 14): the kernels' rule, byte for byte.
+    tris: the BLAS's triangle rows, (3T, 4) float32 or their bytes, as PTReadGeometry returns them; attrs: its T abi.TRI_ATTR records;
+    uvs: (T, 6) float32 lightmap UVs by primitive, None = the records' uv0 .. uv2; local_to_world, world_to_local: 16 floats each in
+    PTGpuInstance's memory order, or both None.  Returns (texels (n,) uint32 ascending, receivers (n, 8) float32 PTReceiver rows)."""
+    t = np.ascontiguousarray(np.asarray(tris).view(np.uint8).reshape(-1))
+    a = np.ascontiguousarray(attrs)
+    ntri = t.nbytes // 48
+    assert t.nbytes == ntri * 48 and a.nbytes == ntri * 128, (t.nbytes, a.nbytes)
+    u = None if uvs is None else np.ascontiguousarray(uvs, dtype=np.float32).reshape(ntri, 6)
+    m = [None if x is None else np.ascontiguousarray(x, dtype=np.float32).reshape(16) for x in (local_to_world, world_to_local)]
+    ptr = lambda x: None if x is None else x.ctypes.data
+    d = abi.chart_desc(width, height, ntri, seed=seed)
+    lib = load_library()
+    count = C.c_uint64()
+    if not lib.PTRasterizeChartHost(C.byref(d), t.ctypes.data, a.ctypes.data, ptr(u), ptr(m[0]), ptr(m[1]), None, None, 0, C.byref(count)):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTRasterizeChartHost failed: " + lib.PTGetBVHBuildError().decode())
+    texels, recv = np.empty(count.value, np.uint32), np.empty((count.value, 8), np.float32)
+    if not lib.PTRasterizeChartHost(C.byref(d), t.ctypes.data, a.ctypes.data, ptr(u), ptr(m[0]), ptr(m[1]), texels.ctypes.data, recv.ctypes.data,
+                                    count.value, C.byref(count)):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTRasterizeChartHost failed: " + lib.PTGetBVHBuildError().decode())
+    return texels, recv
+
+
+def resolve_lightmap(texels, irradiance, width: int, height: int, dilate: int = 2) -> np.ndarray:
+    """Scatter and dilate on the host (PTResolveLightmapHost, include/ptmi_plugin.h Part 14): texels (n,) uint32, irradiance (n, 4)
+    float32 PTIrradiance rows -> (height, width, 4) float32: rgb and w = 1 on the list's texels, 0.5 on dilated ones, 0 elsewhere.
+    Raises PluginError for an index >= width * height or dilate > 16."""
+    t = np.ascontiguousarray(texels, dtype=np.uint32).reshape(-1)
+    e = np.ascontiguousarray(irradiance, dtype=np.float32).reshape(-1, 4)
+    assert len(t) == len(e), (t.shape, e.shape)
+    image = np.empty((max(int(height), 0), max(int(width), 0), 4), np.float32)
+    lib = load_library()
+    if not lib.PTResolveLightmapHost(t.ctypes.data, e.ctypes.data, len(t), int(width), int(height), int(dilate), image.ctypes.data):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTResolveLightmapHost failed: " + lib.PTGetBVHBuildError().decode())
+    return image
 
 
 def build_tlas(instances: np.ndarray):
