@@ -1193,6 +1193,105 @@ PT_API int PTResolveLightmap(PTContext* ctx, const uint32_t* dTexels, const PTIr
 PT_API int PTResolveLightmapHost(const uint32_t* texels, const PTIrradiance* irr, uint64_t count, uint32_t width, uint32_t height, uint32_t dilate,
                                  void* image);                                                             /* host twin, no GPU */
 
+/* =====================================================================================================================
+ * Part 15: SH light probes.  Parts 13 and 14 bake the static surfaces; what lights an object that MOVES through the baked
+ * scene is a probe: a point without a normal that keeps the light arriving from every direction as nine spherical-harmonic
+ * coefficients per channel (bands 0 to 2), from which the irradiance for any normal is nine multiply-adds.  The host hands over
+ * positions and a sample range; directions, paths, projection and the direct light of point and spot lights are made on the
+ * GPU.  An addition beside the reference's ABI, detected by symbol; PTGetVersion is unchanged.
+ *
+ * The rule (bit-exact; sh_rule.h is its one definition: the kernels, the host twins and tests/probe_ref.py evaluate it).
+ *  - Seeding.  Part 13's, word for word: sample j (0 <= j < samples) of probe i starts at s = seed_i; pt_rng_next(&s);
+ *    s += firstSample + j  (uint32 arithmetic).  Samples are independent of each other: the samples [a, a + n) of one call are
+ *    the samples of any split of that range into calls.
+ *  - Direction.  Two draws r1, r2 (pt_random_float): z = 1.0f - 2.0f * r1; rho = sqrt(max(1.0f - z * z, 0.0f));
+ *    phi = PT_TWO_PI * r2; w = (rho * pt_cos(phi), rho * pt_sin(phi), z).  Uniform on the sphere, pdf 1 / (4 PI); one fp32
+ *    operation per operator, pt_sin / pt_cos of ptmi_math.h, no renormalisation.
+ *  - Path.  PTTraceRadiance's: the sample is the path whose first ray is {origin P, direction w} with the RNG state after the
+ *    two draws -- the state Part 8 starts an entry with: depth 0, nothing pending --, and everything after that is the
+ *    render's code under `params` (bounces, roulette, firefly filter, environment, lights, textures, HAS_TLAS).  SamplesPerPass
+ *    is not read.  The sample's value L_j is the path's colour after the fold, so rectangle lights and the sky are seen as a
+ *    camera ray sees them.
+ *  - Basis.  Real SH with x, y, z the components of w, in this order and as these expression trees:
+ *      Y0 = 0.28209479f               Y1 = 0.48860251f * y           Y2 = 0.48860251f * z
+ *      Y3 = 0.48860251f * x           Y4 = 1.09254843f * (x * y)     Y5 = 1.09254843f * (y * z)
+ *      Y6 = 0.31539157f * (3.0f * (z * z) - 1.0f)                    Y7 = 1.09254843f * (x * z)
+ *      Y8 = 0.54627422f * (x * x - y * y)
+ *  - Projection.  Lane l of 64 owns the samples j = l, l + 64, ... in ascending j.  Its 28 partial sums start at +0.0f:
+ *    acc[k][c] = acc[k][c] + L_j[c] * Y_k(w_j)  (a multiply, then an add; no fma) and m2 = m2 + lum * lum with
+ *    lum = (L.r * 0.299f + L.g * 0.587f) + L.b * 0.114f.  The 64 partials v[0..63] of each sum are folded by the fixed tree:
+ *    for h = 32, 16, 8, 4, 2, 1: v[l] = v[l] + v[l + h] for every l < h.  sh[k][c] = (v[0] * 12.566371f) / (float)samples;
+ *    m2 is v[0], unscaled.
+ *  - Delta lights (flag PT_PROBE_DELTA_LIGHTS).  No path can hit a point or a spot light, so they are added after the scaling,
+ *    for every light of the scene in ascending index that is a point or a spot light: lsDirection, lsDistance and
+ *    Li = emission * falloff exactly as the render's light NEE makes them (SampleOneLight and EvalLight) with scatterPos = P;
+ *    one any-hit ray {P, lsDirection, tmax = PT_FAR_PLANE} by Part 3's rules (the render's shadow ray, which has no far end: a
+ *    light that geometry encloses lights no probe, as it lights no pixel and no receiver).  A pair whose light is of another
+ *    type, or whose Li is zero in every channel, has tmax = 0 -- Part 3's miss without a walk -- and is skipped.  A visible pair
+ *    adds sh[k][c] = sh[k][c] + Li[c] * Y_k(lsDirection); an occluded or skipped pair adds nothing, so the bits stay.
+ *    (Cosine-convolved, the term is Li * max(dot(N, L), 0): what Part 13's receiver gets from the same light.)
+ *  - Evaluation.  E(N)[c] = the sum over k = 0 ... 8, ascending, from +0.0f, of (A_k * sh[k][c]) * Y_k(N) with
+ *    A = 3.14159265f (k = 0), 2.09439510f (k = 1, 2, 3), 0.78539816f (k = 4 ... 8).  PTProbeIrradiance: out[q] = {E(normal_q) of
+ *    probe probe_q, m2 = 0}; a probe index >= probeCount yields zeros and reads nothing.
+ *  - PTProbeRays writes, for slot i * samples + j, the PTRadianceRay {P, w, the RNG state after the two draws, 0}: what
+ *    PTTraceRadiance continues from.  It needs no scene and counts nothing.
+ *  - Nothing past `count` is written.  Stream-ordered on the context's stream like Part 13; every device pointer is 16-byte
+ *    aligned.  Slot i * samples + j carries sample j of probe i; a launch sequence holds floor(2^21 / samples) whole probes,
+ *    longer lists are cut into such chunks on successive state sets, joined after the last one.  The delta rays of the whole
+ *    call run first, on the context's stream, in scratch the context keeps and grows (64 bytes per probe and light).
+ *  - PTStats: paths = count x samples with or without the flag; rays and fetches by the render's definitions; pixelsWritten and
+ *    pixelsRead do not move.  With the flag and PTSetStatsLevel(ctx, 1), shadowRays also grows by count x lightCount (Part 3
+ *    counts every ray of a batch).  With profiling on, every chunk is one entry of PTGetTimings.
+ *  - Schedules 1, 2 and 3; schedules 0 and 4 return PT_ERR_UNSUPPORTED, as do samples == 0, samples > 65536 and
+ *    MaxRayBounces > 8191.  PT_ERR_INVALID_ARG for a NULL or misaligned pointer and an unknown flag bit; PT_ERR_NO_SCENE
+ *    before PTSetScene (PTProbeSH, PTProbeSHHost).  count == 0 returns PT_OK and launches nothing.  No CPU fallback.
+ *  - The host twins take no context and no GPU; they return 1, or 0 with PTGetBVHBuildError() set.  PTProbeDirectionsHost
+ *    writes PTProbeRays' entries.  PTProbeProjectHost: directions and colours are count x samples x 3 floats, entry-major;
+ *    out[i] is the projection above (no delta term: that needs a scene).  PTProbeIrradianceHost is PTProbeIrradiance.
+ * ===================================================================================================================== */
+#define PT_PROBE_DELTA_LIGHTS 1u  /* add the direct light of point and spot lights */
+
+typedef struct PTProbe {          /* 16 bytes: one 16-byte load */
+    float    position[3];
+    uint32_t seed;
+} PTProbe;
+
+typedef struct PTProbeCoeffs {    /* 112 bytes: seven 16-byte stores; what PTProbeSH writes (C has one name space for both) */
+    float    sh[9][3];            /* coefficient k, channel c */
+    float    m2;                  /* sum over the samples of luminance(L_j)^2 */
+} PTProbeCoeffs;
+
+typedef struct PTProbeQuery {     /* 16 bytes */
+    float    normal[3];           /* unit normal, used as given */
+    uint32_t probe;               /* index into the PTProbeCoeffs array */
+} PTProbeQuery;
+
+#ifdef __cplusplus
+static_assert(sizeof(PTProbe) == 16, "PTProbe is 16 bytes");
+static_assert(sizeof(PTProbeCoeffs) == 112, "PTProbeCoeffs is 112 bytes");
+static_assert(sizeof(PTProbeQuery) == 16, "PTProbeQuery is 16 bytes");
+#else
+_Static_assert(sizeof(PTProbe) == 16, "PTProbe is 16 bytes");
+_Static_assert(sizeof(PTProbeCoeffs) == 112, "PTProbeCoeffs is 112 bytes");
+_Static_assert(sizeof(PTProbeQuery) == 16, "PTProbeQuery is 16 bytes");
+#endif
+
+/* Device pointers, stream-ordered on the context's stream. */
+PT_API int PTProbeSH(PTContext* ctx, const PTFrameParams* params, const PTProbe* dProbes, uint64_t count, uint32_t firstSample, uint32_t samples,
+                     uint32_t flags, PTProbeCoeffs* dOut);
+/* Host arrays: staged through device buffers the context keeps and grows; synchronous. */
+PT_API int PTProbeSHHost(PTContext* ctx, const PTFrameParams* params, const PTProbe* probes, uint64_t count, uint32_t firstSample, uint32_t samples,
+                         uint32_t flags, PTProbeCoeffs* out);
+/* dRays: count * samples entries, entry-major. */
+PT_API int PTProbeRays(PTContext* ctx, const PTFrameParams* params, const PTProbe* dProbes, uint64_t count, uint32_t firstSample, uint32_t samples,
+                       PTRadianceRay* dRays);
+/* dSH: probeCount entries; dQueries, dOut: count entries. */
+PT_API int PTProbeIrradiance(PTContext* ctx, const PTProbeCoeffs* dSH, uint64_t probeCount, const PTProbeQuery* dQueries, uint64_t count, PTIrradiance* dOut);
+/* host twins, no GPU */
+PT_API int PTProbeDirectionsHost(const PTProbe* probes, uint64_t count, uint32_t firstSample, uint32_t samples, PTRadianceRay* rays);
+PT_API int PTProbeProjectHost(const float* directions, const float* colours, uint64_t count, uint32_t samples, PTProbeCoeffs* out);
+PT_API int PTProbeIrradianceHost(const PTProbeCoeffs* sh, uint64_t probeCount, const PTProbeQuery* queries, uint64_t count, PTIrradiance* out);
+
 /* Text of the last error on the calling thread ("" if none). */
 PT_API const char* PTGetLastError(void);
 /* Library/ABI version: (major << 16) | minor. */

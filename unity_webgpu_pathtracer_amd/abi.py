@@ -289,6 +289,25 @@ class PTIrradiance(C.Structure):
 assert C.sizeof(PTReceiver) == 32 and C.sizeof(PTIrradiance) == 16
 
 
+# ---- SH light probes (include/ptmi_plugin.h Part 15)
+PT_PROBE_DELTA_LIGHTS = 1
+
+
+class PTProbe(C.Structure):
+    _fields_ = [("position", C.c_float * 3), ("seed", C.c_uint32)]
+
+
+class PTProbeCoeffs(C.Structure):
+    _fields_ = [("sh", (C.c_float * 3) * 9), ("m2", C.c_float)]
+
+
+class PTProbeQuery(C.Structure):
+    _fields_ = [("normal", C.c_float * 3), ("probe", C.c_uint32)]
+
+
+assert C.sizeof(PTProbe) == 16 and C.sizeof(PTProbeCoeffs) == 112 and C.sizeof(PTProbeQuery) == 16
+
+
 # ---- lightmap charts (include/ptmi_plugin.h Part 14)
 PT_CHART_MAX_SIZE = 8192
 PT_CHART_MAX_DILATE = 16

@@ -16,6 +16,7 @@
 #include "skin_rule.h"
 #include "morph_rule.h"
 #include "chart_rule.h"
+#include "sh_rule.h"
 #include "ptmi_plugin.h"
 
 namespace {
@@ -186,6 +187,25 @@ PT_API int PTRasterizeChartHost(const PTChartDesc* desc, const PTFloat4* tris, c
 PT_API int PTResolveLightmapHost(const uint32_t* texels, const PTIrradiance* irr, uint64_t count, uint32_t width, uint32_t height, uint32_t dilate, void* image)
 {
     if (!ptchart::chart_resolve_host(texels, irr, count, width, height, dilate, (float*)image, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+// SH light probes on the host (probe_host.cpp; Part 15 has the rule).  No GPU involved.
+PT_API int PTProbeDirectionsHost(const PTProbe* probes, uint64_t count, uint32_t firstSample, uint32_t samples, PTRadianceRay* rays)
+{
+    if (!ptsh::probe_directions_host(probes, count, firstSample, samples, rays, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+PT_API int PTProbeProjectHost(const float* directions, const float* colours, uint64_t count, uint32_t samples, PTProbeCoeffs* out)
+{
+    if (!ptsh::probe_project_host(directions, colours, count, samples, out, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+PT_API int PTProbeIrradianceHost(const PTProbeCoeffs* sh, uint64_t probeCount, const PTProbeQuery* queries, uint64_t count, PTIrradiance* out)
+{
+    if (!ptsh::probe_irradiance_host(sh, probeCount, queries, count, out, g_buildError)) return 0;
     g_buildError.clear();
     return 1;
 }

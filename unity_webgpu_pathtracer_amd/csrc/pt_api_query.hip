@@ -13,15 +13,6 @@ int check_query_flags(uint32_t flags)
     return PT_OK;
 }
 
-int query_prepare(PTContext* c)
-{
-    PTContext::Query& q = c->query;
-    if (q.slab.ptr) return PT_OK;
-    HIP_TRY(pt_query_grid_caps(c->device, q.caps));
-    for (uint32_t cap : q.caps) q.capMax = cap > q.capMax ? cap : q.capMax;
-    return q.slab.reserve((size_t)q.capMax * pt_query_slab_bytes_per_wave());
-}
-
 int trace_rays(PTContext* c, const PTRay* dRays, uint64_t count, uint32_t flags, PTRayHit* dHits, PTRaySurface* dSurface)
 {
     int rc = query_prepare(c);
@@ -37,6 +28,15 @@ int trace_rays(PTContext* c, const PTRay* dRays, uint64_t count, uint32_t flags,
     return PT_OK;
 }
 } // namespace
+
+int query_prepare(PTContext* c)
+{
+    PTContext::Query& q = c->query;
+    if (q.slab.ptr) return PT_OK;
+    HIP_TRY(pt_query_grid_caps(c->device, q.caps));
+    for (uint32_t cap : q.caps) q.capMax = cap > q.capMax ? cap : q.capMax;
+    return q.slab.reserve((size_t)q.capMax * pt_query_slab_bytes_per_wave());
+}
 
 extern "C" {
 

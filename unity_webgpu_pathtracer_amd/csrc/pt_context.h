@@ -233,6 +233,12 @@ struct PTContext {
     struct Gather {
         DeviceBuffer recv, out;
     } gather;
+    // SH light probes (PTProbeSH): the delta lights' rays, Li and any-hit records of a call, 64 bytes per (probe, light) pair,
+    // written and read in stream order behind the context stream; PTProbeSHHost's staging
+    struct Probe {
+        DeviceBuffer deltaRays, deltaLi, deltaHits;
+        DeviceBuffer probes, out;
+    } probe;
     // lightmap charts (PTRasterizeChart / PTResolveLightmap): grown on demand, kept across PTSetScene
     struct Lightmap {
         DeviceBuffer owner;                     // 4 B per texel: the owner map
@@ -367,6 +373,7 @@ int end_update(PTContext* c, PTContext::UpdGroup& g, int target);
 // offsets name (made, and the BLAS walked, on its first use); triCount == 0: the BLAS's own count
 int ensure_host_copy(PTContext* c);
 int find_plan(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t attrOffset, uint32_t triCount, PTContext::GeomPlan*& out);
+int query_prepare(PTContext* c);                                                // pt_api_query.hip: the grid caps and the stack slab of the query kernels, on first use
 int set_scene(PTContext* c, const PTSceneDesc* hostScene, bool validate);      // pt_api_context.hip; PTGroupSetScene validates once
 int drain_events(PTContext* c);                                                 // pt_api_context.hip
 int ensure_frames(PTContext* c, uint32_t w, uint32_t h);                        // pt_api_render.hip

@@ -262,6 +262,28 @@ struct PTGatherMap {
 hipError_t pt_launch_gather_init(const DScene& S, const PTFrameParams& P, const PTGatherMap& gm, const PTWfBuffers& B, bool fullStats, hipStream_t stream);
 hipError_t pt_launch_gather_resolve(const PTGatherMap& gm, const PTWfBuffers& B, PTIrradiance* out, hipStream_t stream);
 hipError_t pt_launch_gather_rays(const DScene& S, const PTFrameParams& P, const PTGatherMap& gm, PTRadianceRay* rays, hipStream_t stream);
+
+// ---- SH light probes (include/ptmi_plugin.h Part 15; pt_probe.hip): a launch sequence over PROBES x SAMPLES ----
+// The gather's arrangement with its own first and last kernel: pt_wf_probe_init leaves in slot s = entry * samples + j the state
+// a radiance query starts the ray {P, w_j} with, and pt_wf_probe_resolve, one wave per probe, projects the slots' colours onto
+// the nine basis functions (w_j is made again from the seed, never stored) and adds the delta lights.
+struct PTProbeMap {
+    const PTProbe* probes;         // 16-byte aligned
+    uint32_t entries, samples;     // entries * samples <= PT_RADIANCE_CHUNK
+    uint32_t firstSample;
+    // PT_PROBE_DELTA_LIGHTS: pair p = entry * lightCount + light of THIS chunk's entries; lightCount == 0: no delta term
+    uint32_t lightCount;
+    const float4* deltaRays;       // 2 per pair: the any-hit ray {P, lsDirection.x} {lsDirection.yz, tmax, 0}; tmax == 0: skipped
+    const float4* deltaLi;         // 1 per pair: Li
+    const float4* deltaHits;       // 1 per pair: the any-hit record (prim == 0xFFFFFFFF: visible)
+};
+hipError_t pt_launch_probe_init(const PTProbeMap& pm, const PTWfBuffers& B, hipStream_t stream);
+hipError_t pt_launch_probe_resolve(const PTProbeMap& pm, const PTWfBuffers& B, PTProbeCoeffs* out, hipStream_t stream);
+hipError_t pt_launch_probe_rays(const PTProbeMap& pm, PTRadianceRay* rays, hipStream_t stream);
+// pairs [0, entries * S.lightCount) of pm.probes: the any-hit rays and Li (<= 2^28 pairs per launch)
+hipError_t pt_launch_probe_delta_rays(const DScene& S, const PTProbe* probes, uint32_t entries, float4* rays, float4* li, hipStream_t stream);
+hipError_t pt_launch_probe_irradiance(const PTProbeCoeffs* sh, uint64_t probeCount, const PTProbeQuery* queries, uint32_t count, PTIrradiance* out,
+                                      hipStream_t stream);
 #ifndef PT_WF_FUSED_GROUPS
 #define PT_WF_FUSED_GROUPS 2u   // schedule 4: groups of 64 path contexts a persistent wave owns (power of two <= 4: numSlots is a multiple of 256).
                                 // Sponza-class 1080p / 8 spp, one pass in flight: 1: 29.9 ms, 2: 25.2, 4: 27.9, 8: 31.4
@@ -276,7 +298,7 @@ hipError_t pt_launch_gather_rays(const DScene& S, const PTFrameParams& P, const 
 #endif
 
 // ---- ONE wavefront launch sequence: what to render (the slot mapping), from and into what, on which stream, by which schedule ----
-enum PTWfMapKind : uint32_t { PT_WF_MAP_TILES, PT_WF_MAP_LIST, PT_WF_MAP_RAYS, PT_WF_MAP_GATHER };
+enum PTWfMapKind : uint32_t { PT_WF_MAP_TILES, PT_WF_MAP_LIST, PT_WF_MAP_RAYS, PT_WF_MAP_GATHER, PT_WF_MAP_PROBE };
 struct PTWfLaunch {
     const DScene* scene;
     const PTFrameParams* params;
@@ -287,9 +309,10 @@ struct PTWfLaunch {
         PTListMap list;                     // a pass over a block list
         PTRayMap rays;                      // a radiance query
         PTGatherMap gather;                 // an irradiance gather
+        PTProbeMap probe;                   // SH light probes
     };
     const float4* accumulated;
-    void* output;                           // the frame (float4 per pixel); PT_WF_MAP_RAYS: the PTRadiance array; PT_WF_MAP_GATHER: the PTIrradiance array
+    void* output;                           // the frame (float4 per pixel); PT_WF_MAP_RAYS: the PTRadiance array; PT_WF_MAP_GATHER: the PTIrradiance array; PT_WF_MAP_PROBE: the PTProbeCoeffs array
     const PTWfBuffers* buffers;             // the state set the sequence runs on
     unsigned long long* counters;           // the context's 16 counters (PTStats order)
     bool fullStats;
@@ -300,6 +323,6 @@ struct PTWfLaunch {
     uint32_t iterationsOverride;            // 0 = spp * (bounces + 2) + 4, capped by buffers->maxIterations
 };
 // Enqueues the sequence on L.stream without host synchronisation; launchesOut (may be null): kernel launches enqueued.
-// hipErrorNotSupported for schedule 4 over a list, rays or a gather.  pt_wavefront.hip is compiled twice with different scheduler flags
+// hipErrorNotSupported for schedule 4 over a list, rays, a gather or probes.  pt_wavefront.hip is compiled twice with different scheduler flags
 // (csrc/Makefile); which compilation's kernels run is decided behind this one entry point.
 hipError_t pt_launch_wavefront(const PTWfLaunch& L, uint32_t* launchesOut);

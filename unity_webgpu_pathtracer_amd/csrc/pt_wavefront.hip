@@ -1391,7 +1391,8 @@ size_t pt_wf_arena_layout(char* base, uint32_t numSlots, uint32_t residentWaves,
 // AccumulatedOutput and, with ping-pong frames, overwrites the frame that resolve was still reading.
 // MAP = PTListMap: the pass over a block list; nothing is zeroed and the frame is copied instead.
 // MAP = PTRayMap: a radiance query: L.output is the PTRadiance array, nothing is ordered, zeroed or copied.  An irradiance gather
-// (PT_WF_MAP_GATHER) runs the same instantiations between pt_gather.hip's init and resolve kernels.
+// (PT_WF_MAP_GATHER) runs the same instantiations between pt_gather.hip's init and resolve kernels, SH light probes (PT_WF_MAP_PROBE)
+// between pt_probe.hip's.
 // UNIT_A: this compilation of the file is the one without the post-RA scheduler (csrc/Makefile).  It is entered for the plain
 // refill trace only, the other one for everything else -- each instantiates only the kernels it can launch.
 namespace {
@@ -1451,7 +1452,10 @@ hipError_t launch_sequence(const PTWfLaunch& L, const MAP& tm, uint32_t* launche
     }
     // an irradiance gather is the ray list's sequence with its own first and last kernel (pt_gather.hip)
     const bool gather = kRays && L.mapKind == PT_WF_MAP_GATHER;
+    // ... and so are SH light probes (pt_probe.hip)
+    const bool probe = kRays && L.mapKind == PT_WF_MAP_PROBE;
     if (gather) { if ((e = pt_launch_gather_init(S, P, L.gather, B, fullStats, stream)) != hipSuccess) return e; }
+    else if (probe) { if ((e = pt_launch_probe_init(L.probe, B, stream)) != hipSuccess) return e; }
     else hipLaunchKernelGGL(pt_wf_init<MAP>, dim3(nb), dim3(256), 0, stream, P, batch, tm, B);
     launches++;
     const uint32_t spp = P.SamplesPerPass > 1 ? (uint32_t)P.SamplesPerPass : 1u;
@@ -1509,6 +1513,7 @@ hipError_t launch_sequence(const PTWfLaunch& L, const MAP& tm, uint32_t* launche
         (e = hipMemsetAsync(output, 0, (size_t)P.OutputWidth * P.OutputHeight * sizeof(float4), stream)) != hipSuccess) return e;
     if constexpr (kRays) {
         if (gather) { if ((e = pt_launch_gather_resolve(L.gather, B, (PTIrradiance*)L.output, stream)) != hipSuccess) return e; }
+        else if (probe) { if ((e = pt_launch_probe_resolve(L.probe, B, (PTProbeCoeffs*)L.output, stream)) != hipSuccess) return e; }
         else hipLaunchKernelGGL(pt_wf_resolve_rays, dim3(nbPass), dim3(256), 0, stream, P, tm, B, (PTRadiance*)L.output);
     } else if constexpr (kList) {
         // pixels outside the list keep Accumulated, bit for bit: one copy of the frame, then the resolve overwrites the listed blocks
@@ -1542,9 +1547,10 @@ hipError_t launch_mapped(const PTWfLaunch& L, uint32_t* launchesOut)
         M.orderAfter = nullptr;
         M.zeroOutputFirst = false;
         return launch_sequence<PTRayMap, UNIT_A>(M, M.rays, launchesOut);
-    case PT_WF_MAP_GATHER: {
+    case PT_WF_MAP_GATHER:
+    case PT_WF_MAP_PROBE: {
         // the ray map's kernels with one sample per slot: they never call its Source, so there is no list behind it
-        const PTRayMap slots = {nullptr, L.gather.entries * L.gather.samples};
+        const PTRayMap slots = {nullptr, L.mapKind == PT_WF_MAP_PROBE ? L.probe.entries * L.probe.samples : L.gather.entries * L.gather.samples};
         PTFrameParams P1 = *L.params;
         P1.SamplesPerPass = 1;
         M.params = &P1;

@@ -1,5 +1,5 @@
 // pt_wf_state.h — how a slot's path state is packed and stored (PTWfBuffers, pt_launch.h): shared by the kernel files that start
-// paths in a state set -- pt_wavefront.hip (camera rays, ray lists) and pt_gather.hip (irradiance gathers).
+// paths in a state set -- pt_wavefront.hip (camera rays, ray lists), pt_gather.hip (irradiance gathers) and pt_probe.hip (SH probes).
 #pragma once
 #include "pt_device.h"
 #include "pt_launch.h"

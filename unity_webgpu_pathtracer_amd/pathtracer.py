@@ -155,6 +155,17 @@ class BVHScene:
         plugin.check(plugin.load_library().PTSetScene(ctx, C.byref(self.desc())))
 
 
+def probe_grid(lo, hi, counts) -> np.ndarray:
+    """Probe positions on a regular grid: counts = (nx, ny, nz) points from corner lo to corner hi inclusive (a count of 1 sits in
+    the middle of its axis).  Returns (nx * ny * nz, 3) float32, x fastest, as probe_sh() takes them."""
+    lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+    counts = [int(c) for c in counts]
+    assert len(counts) == 3 and min(counts) >= 1, counts
+    axes = [np.linspace(lo[a], hi[a], counts[a]) if counts[a] > 1 else np.array([0.5 * (lo[a] + hi[a])]) for a in range(3)]
+    z, y, x = np.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
+    return np.stack([x.reshape(-1), y.reshape(-1), z.reshape(-1)], axis=1).astype(np.float32)
+
+
 class PathTracer:
     """One render context on one GPU, driven exactly as PathTracer.cs drives the compute shader."""
 
@@ -509,6 +520,103 @@ class PathTracer:
         plugin.check(self.lib.PTGatherRays(self.ctx, C.byref(p), d_recv.data_ptr(), n, first_sample & 0xFFFFFFFF, spp, rays.data_ptr()))
         cur.wait_stream(ext)
         return rays.cpu().numpy() if as_numpy else rays
+
+    # ---- SH light probes (include/ptmi_plugin.h Part 15)
+    def _probes(self, positions, seeds):
+        """(n, 4) float32 PTProbe rows -- position xyz, seed bits -- of the kind the positions are; seeds None = the probe index."""
+        if isinstance(positions, np.ndarray) or not hasattr(positions, "device"):
+            return plugin.probe_rows(positions, seeds)
+        import torch
+        assert positions.dtype == torch.float32, positions.dtype
+        pos = positions.reshape(-1, 3)
+        n = pos.shape[0]
+        rows = torch.empty((n, 4), dtype=torch.float32, device=pos.device)
+        rows[:, 0:3] = pos
+        if seeds is None:
+            sd = torch.arange(n, dtype=torch.int32, device=pos.device)
+        else:
+            sd = torch.as_tensor(seeds, device=pos.device).reshape(n).to(torch.int64).bitwise_and(0xFFFFFFFF)
+            sd = torch.where(sd >= 2 ** 31, sd - 2 ** 32, sd).to(torch.int32)
+        rows.view(torch.int32)[:, 3] = sd
+        return rows
+
+    def probe_sh(self, positions, spp: int = 256, first_sample: int = 0, seeds=None, delta_lights: bool = True, params: abi.PTFrameParams = None):
+        """SH light probes on the GPU: what lights an object that moves through a baked scene.  Every probe is a point without a
+        normal; its `spp` samples -- uniform directions made on the GPU, each a path of the render's own (bounces, roulette, firefly
+        filter from `params`, default this tracer's) -- run in parallel and are projected onto real SH bands 0 to 2.  delta_lights:
+        add the direct light of point and spot lights, which no path can hit (one shadow ray per probe and light).
+
+        positions: (n, 3) float32; seeds: (n,) uint32, None = the probe index.  Samples [first_sample, first_sample + spp) of a
+        probe are the same whatever calls they are split into (average the coefficients of equal-sized calls).
+          numpy array -> PTProbeSHHost, returns numpy;
+          torch tensor on this context's device -> PTProbeSH zero-copy, ordered against torch's current stream both ways.
+        Returns (sh, m2): sh (n, 9, 3) float32, coefficient k and channel c; m2 (n,) the sum of the samples' squared luminance."""
+        p = self._radiance_params(params)
+        rows = self._probes(positions, seeds)
+        n = rows.shape[0]
+        flags = abi.PT_PROBE_DELTA_LIGHTS if delta_lights else 0
+        if isinstance(rows, np.ndarray):
+            out = np.empty((n, 28), np.float32)
+            plugin.check(self.lib.PTProbeSHHost(self.ctx, C.byref(p), rows.ctypes.data, n, first_sample & 0xFFFFFFFF, spp, flags, out.ctypes.data))
+            return out[:, :27].reshape(n, 9, 3).copy(), out[:, 27].copy()
+        import torch
+        out = torch.empty((n, 28), dtype=torch.float32, device=rows.device)
+        cur = torch.cuda.current_stream(rows.device)
+        ext = torch.cuda.ExternalStream(self.stream(), device=rows.device)
+        ext.wait_stream(cur)
+        plugin.check(self.lib.PTProbeSH(self.ctx, C.byref(p), rows.data_ptr(), n, first_sample & 0xFFFFFFFF, spp, flags, out.data_ptr()))
+        cur.wait_stream(ext)
+        return out[:, :27].reshape(n, 9, 3), out[:, 27]
+
+    def probe_rays(self, positions, spp: int = 256, first_sample: int = 0, seeds=None, params: abi.PTFrameParams = None):
+        """PTProbeRays: the ray and RNG state each sample of probe_sh() starts with, as radiance() takes them: (n * spp, 8) float32
+        rows, entry-major (row i * spp + j = sample first_sample + j of probe i).  numpy in, numpy out; a device tensor in, a
+        device tensor out."""
+        import torch
+        p = self._radiance_params(params)
+        rows = self._probes(positions, seeds)
+        as_numpy = isinstance(rows, np.ndarray)
+        dev = torch.device(f"cuda:{self.device}")
+        d_rows = torch.from_numpy(rows).to(dev) if as_numpy else rows
+        n = rows.shape[0]
+        rays = torch.empty((n * max(spp, 0), 8), dtype=torch.float32, device=dev)
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
+        ext.wait_stream(cur)
+        plugin.check(self.lib.PTProbeRays(self.ctx, C.byref(p), d_rows.data_ptr(), n, first_sample & 0xFFFFFFFF, spp, rays.data_ptr()))
+        cur.wait_stream(ext)
+        return rays.cpu().numpy() if as_numpy else rays
+
+    def probe_irradiance(self, sh, normals, probes):
+        """PTProbeIrradiance: the irradiance the coefficients of probe_sh() give for unit normals.  sh (n, 9, 3), normals (q, 3),
+        probes (q,) indices into sh (an index >= n gives zeros).  Returns (q, 4) float32 PTIrradiance rows, m2 = 0.  numpy in, numpy
+        out; device tensors in, a device tensor out."""
+        import torch
+        dev = torch.device(f"cuda:{self.device}")
+        as_numpy = isinstance(sh, np.ndarray) or not hasattr(sh, "device")
+        if as_numpy:
+            d_sh = torch.from_numpy(plugin.probe_coeff_rows(sh)).to(dev)
+            d_q = torch.from_numpy(plugin.probe_query_rows(normals, probes)).to(dev)
+        else:
+            assert sh.dtype == torch.float32 and normals.dtype == torch.float32, (sh.dtype, normals.dtype)
+            d_sh = torch.zeros((sh.reshape(-1, 27).shape[0], 28), dtype=torch.float32, device=dev)
+            d_sh[:, :27] = sh.reshape(-1, 27)
+            nrm = normals.reshape(-1, 3)
+            d_q = torch.empty((nrm.shape[0], 4), dtype=torch.float32, device=dev)
+            d_q[:, 0:3] = nrm
+            idx = torch.as_tensor(probes, device=dev).reshape(-1).to(torch.int64).bitwise_and(0xFFFFFFFF)
+            d_q.view(torch.int32)[:, 3] = torch.where(idx >= 2 ** 31, idx - 2 ** 32, idx).to(torch.int32)
+        q = d_q.shape[0]
+        out = torch.empty((q, 4), dtype=torch.float32, device=dev)
+        if q:
+            cur = torch.cuda.current_stream(dev)
+            ext = torch.cuda.ExternalStream(self.stream(), device=dev)
+            ext.wait_stream(cur)
+            plugin.check(self.lib.PTProbeIrradiance(self.ctx, d_sh.data_ptr() if d_sh.shape[0] else None, d_sh.shape[0], d_q.data_ptr(), q, out.data_ptr()))
+            cur.wait_stream(ext)
+        return out.cpu().numpy() if as_numpy else out
+
+    probe_grid = staticmethod(probe_grid)
 
     # ---- lightmap charts (include/ptmi_plugin.h Part 14)
     def _chart_desc(self, width, height, mesh, instance, seed) -> abi.PTChartDesc:

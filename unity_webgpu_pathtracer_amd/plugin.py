@@ -122,6 +122,14 @@ sig = {
     "PTRasterizeChartHost": (i32, [C.POINTER(abi.PTChartDesc), vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "PTResolveLightmap": (i32, [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
     "PTResolveLightmapHost": (i32, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
+    # Part 15 (SH light probes)
+    "PTProbeSH": (i32, [vp, C.POINTER(abi.PTFrameParams), vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
+    "PTProbeSHHost": (i32, [vp, C.POINTER(abi.PTFrameParams), vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
+    "PTProbeRays": (i32, [vp, C.POINTER(abi.PTFrameParams), vp, C.c_uint64, C.c_uint32, C.c_uint32, vp]),
+    "PTProbeIrradiance": (i32, [vp, vp, C.c_uint64, vp, C.c_uint64, vp]),
+    "PTProbeDirectionsHost": (i32, [vp, C.c_uint64, C.c_uint32, C.c_uint32, vp]),
+    "PTProbeProjectHost": (i32, [vp, vp, C.c_uint64, C.c_uint32, vp]),
+    "PTProbeIrradianceHost": (i32, [vp, C.c_uint64, vp, C.c_uint64, vp]),
     "PTGetLastError": (C.c_char_p, []), "PTGetVersion": (i32, []),
 }
 EXPORTED_SYMBOLS = list(sig)
@@ -474,6 +482,72 @@ def resolve_lightmap(texels, irradiance, width: int, height: int, dilate: int = 
     if not lib.PTResolveLightmapHost(t.ctypes.data, e.ctypes.data, len(t), int(width), int(height), int(dilate), image.ctypes.data):
         raise PluginError(abi.PT_ERR_INVALID_ARG, "PTResolveLightmapHost failed: " + lib.PTGetBVHBuildError().decode())
     return image
+
+
+def probe_rows(positions, seeds=None) -> np.ndarray:
+    """(n, 4) float32 PTProbe rows -- position xyz, seed bits -- from (n, 3) positions; seeds None = the probe index."""
+    pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+    n = pos.shape[0]
+    rows = np.empty((n, 4), np.float32)
+    rows[:, 0:3] = pos
+    sd = np.arange(n, dtype=np.uint32) if seeds is None else np.ascontiguousarray(np.asarray(seeds).astype(np.uint32)).reshape(n)
+    rows[:, 3] = sd.view(np.float32)
+    return rows
+
+
+def probe_directions(positions, spp: int, first_sample: int = 0, seeds=None) -> np.ndarray:
+    """The sample rays of SH light probes on the host (PTProbeDirectionsHost, include/ptmi_plugin.h Part 15): (n * spp, 8) float32
+    PTRadianceRay rows, entry-major -- origin xyz, direction xyz, RNG state bits, 0 -- bit for bit what PTProbeRays writes."""
+    rows = probe_rows(positions, seeds)
+    rays = np.empty((rows.shape[0] * max(int(spp), 0), 8), np.float32)
+    lib = load_library()
+    if not lib.PTProbeDirectionsHost(rows.ctypes.data, rows.shape[0], first_sample & 0xFFFFFFFF, int(spp), rays.ctypes.data):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTProbeDirectionsHost failed: " + lib.PTGetBVHBuildError().decode())
+    return rays
+
+
+def probe_project(directions, colours):
+    """Project per-sample radiance onto SH bands 0 to 2 on the host (PTProbeProjectHost): directions, colours (n, spp, 3) float32 ->
+    sh (n, 9, 3) float32 and m2 (n,), by the kernels' lane partials and fold tree; no delta lights (they need a scene)."""
+    d = np.ascontiguousarray(directions, dtype=np.float32)
+    c = np.ascontiguousarray(colours, dtype=np.float32)
+    assert d.ndim == 3 and d.shape[2] == 3 and d.shape == c.shape, (d.shape, c.shape)
+    n, spp = d.shape[0], d.shape[1]
+    out = np.empty((n, 28), np.float32)
+    lib = load_library()
+    if not lib.PTProbeProjectHost(d.ctypes.data, c.ctypes.data, n, spp, out.ctypes.data):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTProbeProjectHost failed: " + lib.PTGetBVHBuildError().decode())
+    return out[:, :27].reshape(n, 9, 3).copy(), out[:, 27].copy()
+
+
+def probe_query_rows(normals, probes) -> np.ndarray:
+    """(q, 4) float32 PTProbeQuery rows -- normal xyz, probe index bits"""
+    nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+    rows = np.empty((nrm.shape[0], 4), np.float32)
+    rows[:, 0:3] = nrm
+    rows[:, 3] = np.ascontiguousarray(np.asarray(probes).astype(np.uint32)).reshape(nrm.shape[0]).view(np.float32)
+    return rows
+
+
+def probe_coeff_rows(sh, m2=None) -> np.ndarray:
+    """(n, 28) float32 PTProbeCoeffs rows from sh (n, 9, 3) and m2 (n,) (None: zeros)"""
+    s = np.ascontiguousarray(sh, dtype=np.float32).reshape(-1, 27)
+    rows = np.zeros((s.shape[0], 28), np.float32)
+    rows[:, :27] = s
+    if m2 is not None:
+        rows[:, 27] = np.asarray(m2, np.float32).reshape(-1)
+    return rows
+
+
+def probe_irradiance(sh, normals, probes) -> np.ndarray:
+    """Irradiance from probe coefficients on the host (PTProbeIrradianceHost): sh (n, 9, 3), normals (q, 3) unit, probes (q,)
+    indices -> (q, 4) float32 PTIrradiance rows (m2 = 0); an index >= n gives zeros."""
+    rows, q = probe_coeff_rows(sh), probe_query_rows(normals, probes)
+    out = np.empty((q.shape[0], 4), np.float32)
+    lib = load_library()
+    if not lib.PTProbeIrradianceHost(rows.ctypes.data, rows.shape[0], q.ctypes.data, q.shape[0], out.ctypes.data):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTProbeIrradianceHost failed: " + lib.PTGetBVHBuildError().decode())
+    return out
 
 
 def build_tlas(instances: np.ndarray):
