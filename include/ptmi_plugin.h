@@ -1292,6 +1292,103 @@ PT_API int PTProbeDirectionsHost(const PTProbe* probes, uint64_t count, uint32_t
 PT_API int PTProbeProjectHost(const float* directions, const float* colours, uint64_t count, uint32_t samples, PTProbeCoeffs* out);
 PT_API int PTProbeIrradianceHost(const PTProbeCoeffs* sh, uint64_t probeCount, const PTProbeQuery* queries, uint64_t count, PTIrradiance* out);
 
+/* =====================================================================================================================
+ * Part 16: probe volumes.  Part 15 evaluates one probe the caller names.  A point BETWEEN the probes of a regular grid is lit
+ * by the eight probes around it, and a blend that does not know where the walls are leaks light through them: the probe in the
+ * lit room brightens the dark room next door.  So every probe also keeps a small octahedral map of the distances it sees, and
+ * the lookup weighs each corner by trilinear position, by the side of the surface it is on (wrap shading) and by a Chebyshev
+ * bound on its visibility.  The host hands over positions and normals -- Part 13's receivers, so the lists of
+ * PTRasterizeChart go in unchanged -- and gets irradiance back.  An addition detected by symbol; PTGetVersion is unchanged.
+ *
+ * The rule (bit-exact; volume_rule.h is its one definition: the kernels, the host twins and tests/volume_ref.py evaluate it;
+ * every fp32 operator below is one IEEE binary32 operation in the order written, no fma).
+ *  - Depth record.  PTProbeDepthMap holds an 8 x 8 octahedral map, texel l = v * 8 + u: moments[l][0] is the weighted mean
+ *    distance, moments[l][1] the weighted mean squared distance.
+ *  - Texel direction d_l.  a = ((float)u + 0.5f) * 0.25f - 1.0f, b likewise from v (never 0).  z = (1.0f - |a|) - |b|.
+ *    If z < 0: x = (1.0f - |b|) * sgn(a), y = (1.0f - |a|) * sgn(b); otherwise x = a, y = b.
+ *    len = sqrt((x * x + y * y) + z * z); d_l = (x / len, y / len, z / len).
+ *  - Samples.  Sample j of probe i has Part 15's seeding and direction w_j, word for word.  Its ray is the PTRay
+ *    {P, w_j, tmax = maxDistance, 0}, traced as a closest-hit query by Part 3's rules; dist_j is the returned t, which is
+ *    maxDistance on a miss: a far or absent surface reads maxDistance.
+ *  - Accumulation.  Every texel sums over ALL samples in ascending j from +0.0f (no fold: one texel's sums are sequential):
+ *    c = max((d.x * w.x + d.y * w.y) + d.z * w.z, 0.0f); c2 = c * c; c4 = c2 * c2; c8 = c4 * c4; c16 = c8 * c8;
+ *    wt = c16 * c16  (cos^32);  sw = sw + wt;  s1 = s1 + wt * dist;  s2 = s2 + wt * (dist * dist).
+ *    If sw > 0: mean = s1 / sw, mean2 = s2 / sw.  If sw == 0, no sample reached the texel and it counts as open:
+ *    mean = maxDistance, mean2 = maxDistance * maxDistance.
+ *  - Grid.  The probe at integer (ix, iy, iz) has index (iz * ny + iy) * nx + ix and position
+ *    Q[a] = origin[a] + (float)i_a * spacing[a].
+ *  - Lookup of the query {position P, normal N} (the seed is ignored):
+ *    1. Pb[a] = P[a] + N[a] * normalBias.
+ *    2. Per axis: g = (P[a] - origin[a]) / spacing[a]; g = g > 0.0f ? g : 0.0f (a NaN lands on 0);
+ *       g = min(g, (float)(counts[a] - 1)).  With counts[a] > 1: i0 = min((uint32_t)g, counts[a] - 2), f = g - (float)i0;
+ *       otherwise i0 = 0, f = 0.0f.
+ *    3. Corners o = 0 ... 7 ascending; bit a of o selects the upper probe on axis a: i_a = min(i0 + bit, counts[a] - 1),
+ *       t_a = bit ? f : 1.0f - f, tri = (t_x * t_y) * t_z.  A corner with tri == 0.0f is skipped and reads nothing.
+ *    4. w = 1.0f.  v = Q - Pb, r = sqrt((v.x * v.x + v.y * v.y) + v.z * v.z).  Only if r > 0:
+ *       dir = v / r.
+ *       PT_GRID_WRAP: t = (((dir.x * N.x + dir.y * N.y) + dir.z * N.z) + 1.0f) * 0.5f; w = w * (t * t + 0.2f).
+ *       PT_GRID_VISIBILITY: e = -dir (from the probe to the point), s = (|e.x| + |e.y|) + |e.z|, a = e.x / s, b = e.y / s;
+ *       if e.z < 0: a' = (1.0f - |b|) * sgn(a), b' = (1.0f - |a|) * sgn(b), with sgn(0) = +1.
+ *       u = min((uint32_t)((a * 0.5f + 0.5f) * 8.0f), 7), v likewise from b (a NaN lands on 0); nearest texel, no filter.
+ *       With that texel's mean and mean2, if r > mean: var = |mean2 - mean * mean|, dl = r - mean,
+ *       ch = var / (var + dl * dl), w = w * ((ch * ch) * ch).
+ *       Then, flags or not: if w < 0.2f, w = w * ((w * w) * 25.0f) (the crush); w = w * tri.
+ *    5. E_o = Part 15's E(N) of the corner's coefficients; acc[c] = acc[c] + w * E_o[c]; sumW = sumW + w.
+ *    6. out.rgb[c] = sumW > 0 ? acc[c] / sumW : 0; out.m2 = sumW, the support the point had (1 up to rounding with both
+ *       flags off).
+ *  - PTProbeDepth: stream-ordered on the context's stream.  The rays and hit records live in scratch the context keeps, 48
+ *    bytes per sample, sized for one chunk of floor(2^21 / samples) whole probes; chunks run one after another on that
+ *    stream.  PTStats moves as a PTTraceRays call of the same rays moves it.  PTProbeGridIrradiance needs no scene.
+ *  - Nothing past `count` is written.  Every device pointer is 16-byte aligned.  dDepth may be NULL only without
+ *    PT_GRID_VISIBILITY.
+ *  - PT_ERR_INVALID_ARG for a NULL or misaligned pointer, an unknown flag bit, a nonzero `reserved`, a count of 0 or above
+ *    1024 on an axis, an origin that is not finite, a spacing that is not finite and positive, a normalBias that is not
+ *    finite and non-negative, a maxDistance that is not finite, not positive or not below PT_FAR_PLANE.  PT_ERR_UNSUPPORTED
+ *    for samples == 0 and samples > 65536.  PT_ERR_NO_SCENE for PTProbeDepth before PTSetScene.  count == 0 returns PT_OK
+ *    and launches nothing.  Arguments are checked before the context is used.  No CPU fallback.
+ *  - The host twins take no context and no GPU; they return 1, or 0 with PTGetBVHBuildError() set.
+ *    PTProbeDepthProjectHost takes the count x samples distances as an array, entry-major, and makes the directions itself.
+ *    PTProbeGridIrradianceHost is PTProbeGridIrradiance.
+ * ===================================================================================================================== */
+#define PT_GRID_WRAP        1u    /* weigh a corner by the side of the surface it is on */
+#define PT_GRID_VISIBILITY  2u    /* weigh a corner by the Chebyshev bound of its depth record */
+
+typedef struct PTProbeDepthMap {     /* 512 bytes: one 8-byte store per lane of a wave */
+    float    moments[64][2];      /* texel l = v * 8 + u: mean distance, mean squared distance */
+} PTProbeDepthMap;
+
+typedef struct PTProbeGrid {      /* 48 bytes; a host struct, passed by pointer */
+    float    origin[3];           /* the position of probe (0, 0, 0) */
+    uint32_t flags;               /* PT_GRID_... */
+    float    spacing[3];          /* finite, > 0 */
+    float    normalBias;          /* finite, >= 0 */
+    uint32_t counts[3];           /* 1 ... 1024 probes per axis, x fastest */
+    uint32_t reserved;            /* must be 0 */
+} PTProbeGrid;
+
+#ifdef __cplusplus
+static_assert(sizeof(PTProbeDepthMap) == 512, "PTProbeDepthMap is 512 bytes");
+static_assert(sizeof(PTProbeGrid) == 48, "PTProbeGrid is 48 bytes");
+#else
+_Static_assert(sizeof(PTProbeDepthMap) == 512, "PTProbeDepthMap is 512 bytes");
+_Static_assert(sizeof(PTProbeGrid) == 48, "PTProbeGrid is 48 bytes");
+#endif
+
+/* Device pointers, stream-ordered on the context's stream. */
+PT_API int PTProbeDepth(PTContext* ctx, const PTProbe* dProbes, uint64_t count, uint32_t firstSample, uint32_t samples, float maxDistance,
+                        PTProbeDepthMap* dOut);
+/* Host arrays: staged through device buffers the context keeps and grows; synchronous. */
+PT_API int PTProbeDepthHost(PTContext* ctx, const PTProbe* probes, uint64_t count, uint32_t firstSample, uint32_t samples, float maxDistance,
+                            PTProbeDepthMap* out);
+/* dSH, dDepth: one entry per probe of the grid; dQueries, dOut: count entries. */
+PT_API int PTProbeGridIrradiance(PTContext* ctx, const PTProbeGrid* grid, const PTProbeCoeffs* dSH, const PTProbeDepthMap* dDepth,
+                                 const PTReceiver* dQueries, uint64_t count, PTIrradiance* dOut);
+/* host twins, no GPU */
+PT_API int PTProbeDepthProjectHost(const PTProbe* probes, uint64_t count, uint32_t firstSample, uint32_t samples, const float* distances,
+                                   float maxDistance, PTProbeDepthMap* out);
+PT_API int PTProbeGridIrradianceHost(const PTProbeGrid* grid, const PTProbeCoeffs* sh, const PTProbeDepthMap* depth, const PTReceiver* queries,
+                                     uint64_t count, PTIrradiance* out);
+
 /* Text of the last error on the calling thread ("" if none). */
 PT_API const char* PTGetLastError(void);
 /* Library/ABI version: (major << 16) | minor. */

@@ -308,6 +308,24 @@ class PTProbeQuery(C.Structure):
 assert C.sizeof(PTProbe) == 16 and C.sizeof(PTProbeCoeffs) == 112 and C.sizeof(PTProbeQuery) == 16
 
 
+# ---- probe volumes (include/ptmi_plugin.h Part 16)
+PT_GRID_WRAP = 1
+PT_GRID_VISIBILITY = 2
+PT_GRID_MAX_AXIS = 1024
+
+
+class PTProbeDepthMap(C.Structure):
+    _fields_ = [("moments", (C.c_float * 2) * 64)]
+
+
+class PTProbeGrid(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("flags", C.c_uint32), ("spacing", C.c_float * 3), ("normalBias", C.c_float),
+                ("counts", C.c_uint32 * 3), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(PTProbeDepthMap) == 512 and C.sizeof(PTProbeGrid) == 48
+
+
 # ---- lightmap charts (include/ptmi_plugin.h Part 14)
 PT_CHART_MAX_SIZE = 8192
 PT_CHART_MAX_DILATE = 16

@@ -17,6 +17,7 @@
 #include "morph_rule.h"
 #include "chart_rule.h"
 #include "sh_rule.h"
+#include "volume_rule.h"
 #include "ptmi_plugin.h"
 
 namespace {
@@ -206,6 +207,21 @@ PT_API int PTProbeProjectHost(const float* directions, const float* colours, uin
 PT_API int PTProbeIrradianceHost(const PTProbeCoeffs* sh, uint64_t probeCount, const PTProbeQuery* queries, uint64_t count, PTIrradiance* out)
 {
     if (!ptsh::probe_irradiance_host(sh, probeCount, queries, count, out, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+// Probe volumes on the host (volume_host.cpp; Part 16 has the rule).  No GPU involved.
+PT_API int PTProbeDepthProjectHost(const PTProbe* probes, uint64_t count, uint32_t firstSample, uint32_t samples, const float* distances,
+                                   float maxDistance, PTProbeDepthMap* out)
+{
+    if (!ptvol::depth_project_host(probes, count, firstSample, samples, distances, maxDistance, out, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+PT_API int PTProbeGridIrradianceHost(const PTProbeGrid* grid, const PTProbeCoeffs* sh, const PTProbeDepthMap* depth, const PTReceiver* queries,
+                                     uint64_t count, PTIrradiance* out)
+{
+    if (!ptvol::grid_irradiance_host(grid, sh, depth, queries, count, out, g_buildError)) return 0;
     g_buildError.clear();
     return 1;
 }

@@ -239,6 +239,12 @@ struct PTContext {
         DeviceBuffer deltaRays, deltaLi, deltaHits;
         DeviceBuffer probes, out;
     } probe;
+    // probe volumes (PTProbeDepth): the rays and hit records of one chunk, 48 bytes per sample, used in stream order on the
+    // context stream; PTProbeDepthHost's staging
+    struct Volume {
+        DeviceBuffer rays, hits;
+        DeviceBuffer probes, out;
+    } volume;
     // lightmap charts (PTRasterizeChart / PTResolveLightmap): grown on demand, kept across PTSetScene
     struct Lightmap {
         DeviceBuffer owner;                     // 4 B per texel: the owner map

@@ -284,6 +284,16 @@ hipError_t pt_launch_probe_rays(const PTProbeMap& pm, PTRadianceRay* rays, hipSt
 hipError_t pt_launch_probe_delta_rays(const DScene& S, const PTProbe* probes, uint32_t entries, float4* rays, float4* li, hipStream_t stream);
 hipError_t pt_launch_probe_irradiance(const PTProbeCoeffs* sh, uint64_t probeCount, const PTProbeQuery* queries, uint32_t count, PTIrradiance* out,
                                       hipStream_t stream);
+// ---- probe volumes (include/ptmi_plugin.h Part 16; pt_volume.hip) ----
+// A depth bake of one chunk (entries * samples <= 2^21): the rays kernel writes 2 float4 per slot = entry * samples + j, the
+// closest-hit query (pt_launch_query) writes 1 float4 per slot, the resolve turns them into one 512-byte record per probe.
+hipError_t pt_launch_probe_depth_rays(const PTProbe* probes, uint32_t entries, uint32_t samples, uint32_t firstSample, float maxDistance, float4* rays,
+                                      hipStream_t stream);
+hipError_t pt_launch_probe_depth_resolve(const PTProbe* probes, uint32_t entries, uint32_t samples, uint32_t firstSample, float maxDistance,
+                                         const float4* hits, PTProbeDepthMap* out, hipStream_t stream);
+// the grid has passed ptvol::check_grid; depth may be null without PT_GRID_VISIBILITY
+hipError_t pt_launch_probe_grid_irradiance(const PTProbeGrid& grid, const PTProbeCoeffs* sh, const PTProbeDepthMap* depth, const PTReceiver* queries,
+                                           uint32_t count, PTIrradiance* out, hipStream_t stream);
 #ifndef PT_WF_FUSED_GROUPS
 #define PT_WF_FUSED_GROUPS 2u   // schedule 4: groups of 64 path contexts a persistent wave owns (power of two <= 4: numSlots is a multiple of 256).
                                 // Sponza-class 1080p / 8 spp, one pass in flight: 1: 29.9 ms, 2: 25.2, 4: 27.9, 8: 31.4

@@ -618,6 +618,52 @@ class PathTracer:
 
     probe_grid = staticmethod(probe_grid)
 
+    # ---- probe volumes (include/ptmi_plugin.h Part 16)
+    def probe_depth(self, positions, spp: int = 256, max_distance: float = 1.0, first_sample: int = 0, seeds=None):
+        """PTProbeDepth: an 8 x 8 octahedral map of the distances each probe sees, what a probe volume's lookup keeps light from
+        leaking through walls with.  Sample j of a probe has probe_sh()'s direction; its ray is a closest-hit query that ends at
+        max_distance, and every texel keeps the cos^32-weighted mean distance and mean squared distance of all samples.
+
+        positions: (n, 3) float32; seeds: (n,) uint32, None = the probe index.
+          numpy array -> PTProbeDepthHost, returns numpy;
+          torch tensor on this context's device -> PTProbeDepth zero-copy, ordered against torch's current stream both ways.
+        Returns (n, 64, 2) float32: texel v * 8 + u, mean and mean square."""
+        rows = self._probes(positions, seeds)
+        n = rows.shape[0]
+        if isinstance(rows, np.ndarray):
+            out = np.empty((n, 64, 2), np.float32)
+            plugin.check(self.lib.PTProbeDepthHost(self.ctx, rows.ctypes.data, n, first_sample & 0xFFFFFFFF, spp, max_distance, out.ctypes.data))
+            return out
+        import torch
+        out = torch.empty((n, 64, 2), dtype=torch.float32, device=rows.device)
+        cur = torch.cuda.current_stream(rows.device)
+        ext = torch.cuda.ExternalStream(self.stream(), device=rows.device)
+        ext.wait_stream(cur)
+        plugin.check(self.lib.PTProbeDepth(self.ctx, rows.data_ptr(), n, first_sample & 0xFFFFFFFF, spp, max_distance, out.data_ptr()))
+        cur.wait_stream(ext)
+        return out
+
+    def bake_probe_volume(self, lo, hi, counts, spp: int = 256, depth_spp: int = 256, max_distance: float = None, first_sample: int = 0, seeds=None,
+                          delta_lights: bool = True, params: abi.PTFrameParams = None) -> "ProbeVolume":
+        """A probe volume over the box lo ... hi: counts = (nx, ny, nz) probes, the outer ones on the box's faces (a count of 1 sits
+        in the middle of its axis).  Bakes probe_sh(spp) and probe_depth(depth_spp) at plugin.probe_grid_positions of the grid; both
+        stay on the device.  max_distance: where a depth ray ends, default 1.5 x the diagonal of a cell.  Returns a ProbeVolume."""
+        import torch
+        lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+        counts = [int(c) for c in counts]
+        assert len(counts) == 3 and min(counts) >= 1 and (hi >= lo).all(), (counts, lo, hi)
+        origin = [lo[a] if counts[a] > 1 else 0.5 * (lo[a] + hi[a]) for a in range(3)]
+        spacing = [(hi[a] - lo[a]) / (counts[a] - 1) if counts[a] > 1 else (hi[a] - lo[a] if hi[a] > lo[a] else 1.0) for a in range(3)]
+        grid = plugin.probe_grid_desc(origin, spacing, counts)
+        if max_distance is None:
+            max_distance = 1.5 * float(np.linalg.norm([grid.spacing[a] for a in range(3)]))
+        dev = torch.device(f"cuda:{self.device}")
+        pos = torch.from_numpy(plugin.probe_grid_positions(grid)).to(dev)
+        d_seeds = None if seeds is None else torch.from_numpy(np.asarray(seeds).astype(np.int64)).to(dev)
+        sh, m2 = self.probe_sh(pos, spp=spp, first_sample=first_sample, seeds=d_seeds, delta_lights=delta_lights, params=params)
+        depth = self.probe_depth(pos, spp=depth_spp, max_distance=max_distance, first_sample=first_sample, seeds=d_seeds)
+        return ProbeVolume(self, grid, sh, m2, depth, max_distance)
+
     # ---- lightmap charts (include/ptmi_plugin.h Part 14)
     def _chart_desc(self, width, height, mesh, instance, seed) -> abi.PTChartDesc:
         bvh = self._bvhScene
@@ -1252,6 +1298,68 @@ class PathTracer:
             self.close()
         except Exception:
             pass
+
+
+class ProbeVolume:
+    """A baked probe grid on the device (PathTracer.bake_probe_volume; include/ptmi_plugin.h Part 16): the grid, the SH
+    coefficients (n, 9, 3), their luminance moments (n,) and the depth records (n, 64, 2), x fastest."""
+
+    def __init__(self, tracer: "PathTracer", grid: abi.PTProbeGrid, sh, m2, depth, max_distance: float):
+        import torch
+        self.tracer, self.grid, self.sh, self.m2, self.depth, self.max_distance = tracer, grid, sh, m2, depth, float(max_distance)
+        n = sh.shape[0]
+        assert n == grid.counts[0] * grid.counts[1] * grid.counts[2] and depth.shape == (n, 64, 2), (sh.shape, depth.shape)
+        self._rows = torch.zeros((n, 28), dtype=torch.float32, device=sh.device)          # PTProbeCoeffs rows
+        self._rows[:, :27] = sh.reshape(n, 27)
+        self._rows[:, 27] = m2
+        self._depth = depth.contiguous()
+
+    @property
+    def counts(self):
+        return tuple(int(c) for c in self.grid.counts)
+
+    def positions(self) -> np.ndarray:
+        return plugin.probe_grid_positions(self.grid)
+
+    def default_normal_bias(self) -> float:
+        """a fifth of the smallest spacing along an axis that has more than one probe (0 for a single probe)"""
+        s = [self.grid.spacing[a] for a in range(3) if self.grid.counts[a] > 1]
+        return 0.2 * min(s) if s else 0.0
+
+    def irradiance(self, positions=None, normals=None, receivers=None, wrap: bool = True, visibility: bool = True, normal_bias: float = None):
+        """PTProbeGridIrradiance: the irradiance the volume gives at points with unit normals, blended from the up to eight probes
+        around each point.  wrap: weigh a probe by the side of the surface it is on; visibility: weigh it by the Chebyshev bound of
+        its depth record, which keeps a lit room's probes out of the dark room next door.  normal_bias: how far the point is moved
+        along its normal before the distance to a probe is taken (None: default_normal_bias()).
+
+        positions, normals: (q, 3) float32, or receivers: (q, 8) float32 PTReceiver rows as chart_receivers returns them.  numpy in,
+        numpy out; device tensors in, a device tensor out.  Returns (q, 4) float32: irradiance rgb and the support sumW."""
+        import torch
+        pt = self.tracer
+        dev = self._rows.device
+        if receivers is not None:
+            assert positions is None and normals is None, "receivers come instead of positions and normals"
+            as_numpy = isinstance(receivers, np.ndarray)
+            recv = torch.from_numpy(np.ascontiguousarray(receivers, dtype=np.float32)).to(dev) if as_numpy else receivers.contiguous()
+        else:
+            as_numpy = isinstance(positions, np.ndarray) or not hasattr(positions, "device")
+            if as_numpy:
+                recv = torch.from_numpy(plugin.receiver_rows(positions, normals)).to(dev)
+            else:
+                recv = pt._receivers(positions, normals, None)
+        assert recv.dtype == torch.float32 and recv.ndim == 2 and recv.shape[1] == 8, (recv.dtype, recv.shape)
+        g = abi.PTProbeGrid.from_buffer_copy(self.grid)
+        g.flags = (abi.PT_GRID_WRAP if wrap else 0) | (abi.PT_GRID_VISIBILITY if visibility else 0)
+        g.normalBias = self.default_normal_bias() if normal_bias is None else float(normal_bias)
+        q = recv.shape[0]
+        out = torch.empty((q, 4), dtype=torch.float32, device=dev)
+        if q:
+            cur = torch.cuda.current_stream(dev)
+            ext = torch.cuda.ExternalStream(pt.stream(), device=dev)
+            ext.wait_stream(cur)
+            plugin.check(pt.lib.PTProbeGridIrradiance(pt.ctx, C.byref(g), self._rows.data_ptr(), self._depth.data_ptr(), recv.data_ptr(), q, out.data_ptr()))
+            cur.wait_stream(ext)
+        return out.cpu().numpy() if as_numpy else out
 
 
 def select_blocks(tiles, samples, threshold: float, max_samples: int, add_samples: int, dilate: bool) -> np.ndarray:

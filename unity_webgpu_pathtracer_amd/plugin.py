@@ -130,6 +130,12 @@ sig = {
     "PTProbeDirectionsHost": (i32, [vp, C.c_uint64, C.c_uint32, C.c_uint32, vp]),
     "PTProbeProjectHost": (i32, [vp, vp, C.c_uint64, C.c_uint32, vp]),
     "PTProbeIrradianceHost": (i32, [vp, C.c_uint64, vp, C.c_uint64, vp]),
+    # Part 16 (probe volumes)
+    "PTProbeDepth": (i32, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, vp]),
+    "PTProbeDepthHost": (i32, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, vp]),
+    "PTProbeGridIrradiance": (i32, [vp, C.POINTER(abi.PTProbeGrid), vp, vp, vp, C.c_uint64, vp]),
+    "PTProbeDepthProjectHost": (i32, [vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, C.c_float, vp]),
+    "PTProbeGridIrradianceHost": (i32, [C.POINTER(abi.PTProbeGrid), vp, vp, vp, C.c_uint64, vp]),
     "PTGetLastError": (C.c_char_p, []), "PTGetVersion": (i32, []),
 }
 EXPORTED_SYMBOLS = list(sig)
@@ -547,6 +553,69 @@ def probe_irradiance(sh, normals, probes) -> np.ndarray:
     lib = load_library()
     if not lib.PTProbeIrradianceHost(rows.ctypes.data, rows.shape[0], q.ctypes.data, q.shape[0], out.ctypes.data):
         raise PluginError(abi.PT_ERR_INVALID_ARG, "PTProbeIrradianceHost failed: " + lib.PTGetBVHBuildError().decode())
+    return out
+
+
+def probe_grid_desc(origin, spacing, counts, wrap: bool = True, visibility: bool = True, normal_bias: float = 0.0) -> abi.PTProbeGrid:
+    """The PTProbeGrid (include/ptmi_plugin.h Part 16) of a regular lattice: probe (ix, iy, iz) at origin + i * spacing, x fastest."""
+    g = abi.PTProbeGrid()
+    for a in range(3):
+        g.origin[a], g.spacing[a], g.counts[a] = float(origin[a]), float(spacing[a]), int(counts[a])
+    g.flags = (abi.PT_GRID_WRAP if wrap else 0) | (abi.PT_GRID_VISIBILITY if visibility else 0)
+    g.normalBias = float(normal_bias)
+    return g
+
+
+def probe_grid_positions(grid: abi.PTProbeGrid) -> np.ndarray:
+    """The rule's fp32 position Q of every probe of a grid: Q[a] = origin[a] + (float)i_a * spacing[a], one float32 multiply and
+    one add.  Returns (nx * ny * nz, 3) float32, x fastest, as probe_sh() and probe_depth() take them."""
+    axes = [(np.float32(grid.origin[a]) + np.arange(grid.counts[a], dtype=np.uint32).astype(np.float32) * np.float32(grid.spacing[a])).astype(np.float32)
+            for a in range(3)]
+    z, y, x = np.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
+    return np.stack([x.reshape(-1), y.reshape(-1), z.reshape(-1)], axis=1).astype(np.float32)
+
+
+def receiver_rows(positions, normals) -> np.ndarray:
+    """(n, 8) float32 PTReceiver rows -- position xyz, seed 0, normal xyz, 0 -- for a lookup, which ignores the seed"""
+    pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+    nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+    assert pos.shape == nrm.shape, (pos.shape, nrm.shape)
+    rows = np.zeros((pos.shape[0], 8), np.float32)
+    rows[:, 0:3], rows[:, 4:7] = pos, nrm
+    return rows
+
+
+def probe_depth_project(positions, distances, max_distance: float, first_sample: int = 0, seeds=None) -> np.ndarray:
+    """The octahedral depth records of probes on the host (PTProbeDepthProjectHost, include/ptmi_plugin.h Part 16): distances
+    (n, spp) float32, the closest-hit t of every sample's ray (max_distance on a miss); the directions are made from the seeds.
+    Returns (n, 64, 2) float32: per texel the weighted mean distance and mean squared distance, bit for bit what PTProbeDepth
+    writes for the same distances."""
+    rows = probe_rows(positions, seeds)
+    d = np.ascontiguousarray(distances, dtype=np.float32)
+    assert d.ndim == 2 and d.shape[0] == rows.shape[0], (d.shape, rows.shape)
+    out = np.empty((rows.shape[0], 64, 2), np.float32)
+    lib = load_library()
+    if not lib.PTProbeDepthProjectHost(rows.ctypes.data, rows.shape[0], first_sample & 0xFFFFFFFF, d.shape[1], d.ctypes.data, max_distance, out.ctypes.data):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTProbeDepthProjectHost failed: " + lib.PTGetBVHBuildError().decode())
+    return out
+
+
+def probe_grid_irradiance(grid: abi.PTProbeGrid, sh, depth, positions=None, normals=None, receivers=None) -> np.ndarray:
+    """A probe volume's lookup on the host (PTProbeGridIrradianceHost): sh (n, 9, 3), depth (n, 64, 2) or None (without
+    PT_GRID_VISIBILITY), n the grid's probes; positions and unit normals (q, 3), or ready-made (q, 8) PTReceiver rows.
+    Returns (q, 4) float32: irradiance rgb and the support sumW."""
+    rows = probe_coeff_rows(sh)
+    recv = receiver_rows(positions, normals) if receivers is None else np.ascontiguousarray(receivers, dtype=np.float32).reshape(-1, 8)
+    n = int(grid.counts[0]) * int(grid.counts[1]) * int(grid.counts[2])
+    d = None
+    if depth is not None:
+        d = np.ascontiguousarray(depth, dtype=np.float32).reshape(-1, 128)
+    if 1 <= min(grid.counts) and max(grid.counts) <= abi.PT_GRID_MAX_AXIS:           # (the twin refuses other counts itself)
+        assert rows.shape[0] == n and (d is None or d.shape[0] == n), (rows.shape, n)
+    out = np.empty((recv.shape[0], 4), np.float32)
+    lib = load_library()
+    if not lib.PTProbeGridIrradianceHost(C.byref(grid), rows.ctypes.data, None if d is None else d.ctypes.data, recv.ctypes.data, recv.shape[0], out.ctypes.data):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTProbeGridIrradianceHost failed: " + lib.PTGetBVHBuildError().decode())
     return out
 
 
