@@ -1389,6 +1389,74 @@ PT_API int PTProbeDepthProjectHost(const PTProbe* probes, uint64_t count, uint32
 PT_API int PTProbeGridIrradianceHost(const PTProbeGrid* grid, const PTProbeCoeffs* sh, const PTProbeDepthMap* depth, const PTReceiver* queries,
                                      uint64_t count, PTIrradiance* out);
 
+/* =====================================================================================================================
+ * Part 17: the lightmap denoiser.  "The bake is the gather" (DESIGN.md 5.19), so a cheaper bake is one that needs fewer samples
+ * per texel.  PTDenoiseLightmap filters a gathered list in texel space between PTGatherIrradiance and PTResolveLightmap: list
+ * in, list out.  Part 4's filter cannot do it: its guides are a camera's, and it knows nothing of charts -- two texels that
+ * touch in an atlas may lie in different rooms or on either side of a fold, and an image filter bleeds light across such a
+ * seam.  Here every texel has an exact world position and normal (its PTReceiver) and a variance (PTIrradiance.m2), and a tap
+ * that is no neighbour in the world is cut whatever its normal and plane are.  An addition detected by symbol; PTGetVersion is
+ * unchanged.
+ *
+ * The rule (bit-exact; lmfilter_rule.h is its one definition and states it in full: the kernels, the host twin and
+ * tests/lmfilter_ref.py evaluate it; only + - * /, sqrtf, fabsf, comparisons and max; every fp32 operator is one IEEE binary32
+ * operation, left to right).  In short:
+ *  1. Entry i at texel texels[i]: e = rgb, l = luminance3(e), S = (float)samples, v = max((m2 - S*l*l) / (S - 1), 0) / S, the
+ *     variance of the mean luminance.  An entry with a non-finite rgb, m2, position or normal (or a NaN v) is bad: its 16 input
+ *     bytes are its output and it is never a tap.  Texel indices must be unique and < width * height: the twin refuses
+ *     otherwise, the device skips an index out of range and lets one of several duplicates win, as PTResolveLightmap does.
+ *  2. Footprint h2_p: the smallest |P_q - P_p|^2 > 0 over the covered, not bad 4-neighbours (left, right, up, down), else 0.  A
+ *     texel with h2 == 0 is isolated: it keeps its e bit for bit and may still be a tap of others.
+ *  3. Position cut: the tap at the offset (ox, oy) is admitted when |P_q - P_p|^2 <= (sigmaPosition * sigmaPosition) * h2_p *
+ *     (float)(ox*ox + oy*oy); the offset (0, 0) always is.  This is what stops chart-to-chart bleeding.
+ *  4. Level k = 0 ... iterations - 1, step s = 2^k: 5 x 5 taps at (dx, dy) * s, dy outer, dx inner, ascending, sums from 0 in that
+ *     order; w = ((h[dx] * h[dy]) * w_n) * w_z * w_l with h = {1/16, 1/4, 3/8, 1/4, 1/16}; w_n = max(dot(N_p, N_q), 0) squared
+ *     normalPower times; z = |dot(N_p, P_q - P_p)| / (sigmaPlane * sqrt(h2_p) * (float)s + 1e-12f), w_z = (1 / (1 + z*z))^2;
+ *     x = |l_p - l_q| / (sigmaLuminance * sqrt(g_p) + 1e-6f), w_l = (1 / (1 + x*x))^2; g_p = the {1/4, 1/2, 1/4}^2 blur of v over
+ *     the admitted taps of the 3 x 3 at step 1, divided by the weights it used, from the level's input.
+ *     e' = sum(w * e_q) / sum(w); v' = sum(w*w * v_q) / (sum(w) * sum(w)); a texel whose sum(w) is not > 0 keeps (e, v).
+ *  5. out[i].rgb = the final e; out[i].m2 = the final v: THE VARIANCE ESTIMATE OF THE FILTERED LUMINANCE, NOT A SUM OF SQUARES
+ *     (a denoised list is not folded with further samples by m2).  iterations == 0: the input's rgb and the v of step 1.
+ *     Nothing past `count` is written.
+ *
+ * PTDenoiseLightmap.  Device arrays (dTexels 4-byte, dRecv, dIrr and dOut 16-byte aligned); dOut may equal dIrr.  Stream-ordered
+ * on the context's stream, does not synchronise, needs no scene.  Kernels: a scatter of the list into a state image (e, v) and
+ * two guide images (P, h2) and (N, flags), the footprint, one launch per level between two state images, and a collect back
+ * into the list.  Memory, in the context, grown on demand, kept across PTSetScene, freed by PTDestroy: 64 bytes per texel (two
+ * 16-byte state images and 32 bytes of guides): 4.3 GB at 8192 x 8192.
+ * Errors: PT_ERR_INVALID_ARG for a NULL context, params, or (count > 0) array; a misaligned pointer; a structSize below this
+ * header's; samples outside 2 ... 2^24, iterations > 8, normalPower > 7; a sigma that is not finite and positive; a size outside
+ * 1 ... 8192; count > width * height; a nonzero reserved word.  count == 0 returns PT_OK and launches nothing.  Arguments are
+ * checked before the context is used.  No CPU fallback.
+ * PTDenoiseLightmapHost: the host twin, no context, no GPU; returns 1, or 0 with PTGetBVHBuildError() set.
+ * ===================================================================================================================== */
+#define PT_LMFILTER_MAX_ITERATIONS   8u
+#define PT_LMFILTER_MAX_NORMAL_POWER 7u
+#define PT_LMFILTER_MAX_SAMPLES      16777216u
+
+typedef struct PTLightmapDenoiseParams {
+    uint32_t structSize;          /* sizeof(PTLightmapDenoiseParams) of the caller's header; members are only appended */
+    uint32_t samples;             /* 2 ... 2^24: the total number of samples behind m2 */
+    uint32_t iterations;          /* 0 ... 8 a-trous levels; suggested 5 */
+    uint32_t normalPower;         /* 0 ... 7: the normal weight is the cosine squared that many times; suggested 5 */
+    float    sigmaLuminance;      /* > 0, finite; suggested 4 */
+    float    sigmaPosition;       /* > 0, finite; suggested 4 */
+    float    sigmaPlane;          /* > 0, finite; suggested 1 */
+    uint32_t reserved[5];         /* must be 0 */
+} PTLightmapDenoiseParams;
+
+#ifdef __cplusplus
+static_assert(sizeof(PTLightmapDenoiseParams) == 48, "PTLightmapDenoiseParams is 48 bytes");
+#else
+_Static_assert(sizeof(PTLightmapDenoiseParams) == 48, "PTLightmapDenoiseParams is 48 bytes");
+#endif
+
+/* Device arrays, stream-ordered on the context's stream. */
+PT_API int PTDenoiseLightmap(PTContext* ctx, const PTLightmapDenoiseParams* params, const uint32_t* dTexels, const PTReceiver* dRecv,
+                             const PTIrradiance* dIrr, uint64_t count, uint32_t width, uint32_t height, PTIrradiance* dOut);
+PT_API int PTDenoiseLightmapHost(const PTLightmapDenoiseParams* params, const uint32_t* texels, const PTReceiver* recv, const PTIrradiance* irr,
+                                 uint64_t count, uint32_t width, uint32_t height, PTIrradiance* out);        /* host twin, no GPU */
+
 /* Text of the last error on the calling thread ("" if none). */
 PT_API const char* PTGetLastError(void);
 /* Library/ABI version: (major << 16) | minor. */

@@ -350,6 +350,30 @@ def chart_desc(width: int, height: int, triangle_count: int, offsets=(0, 0, 0), 
     return d
 
 
+# ---- the lightmap denoiser (include/ptmi_plugin.h Part 17)
+PT_LMFILTER_MAX_ITERATIONS = 8
+PT_LMFILTER_MAX_NORMAL_POWER = 7
+PT_LMFILTER_MAX_SAMPLES = 1 << 24
+
+
+class PTLightmapDenoiseParams(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("samples", C.c_uint32), ("iterations", C.c_uint32), ("normalPower", C.c_uint32),
+                ("sigmaLuminance", C.c_float), ("sigmaPosition", C.c_float), ("sigmaPlane", C.c_float), ("reserved", C.c_uint32 * 5)]
+
+
+assert C.sizeof(PTLightmapDenoiseParams) == 48
+
+
+def lightmap_denoise_params(samples: int, iterations: int = 5, sigma_luminance: float = 4.0, sigma_position: float = 4.0, sigma_plane: float = 1.0,
+                            normal_power: int = 5) -> PTLightmapDenoiseParams:
+    """A PTLightmapDenoiseParams with structSize set and the header's suggested values; samples: the total behind m2."""
+    p = PTLightmapDenoiseParams()
+    p.structSize = C.sizeof(PTLightmapDenoiseParams)
+    p.samples, p.iterations, p.normalPower = int(samples), int(iterations), int(normal_power)
+    p.sigmaLuminance, p.sigmaPosition, p.sigmaPlane = float(sigma_luminance), float(sigma_position), float(sigma_plane)
+    return p
+
+
 # ---------------------------------------------------------------------------------------
 # Part 10: geometry rebuilds and tree quality (PTRebuildGeometry / PTMeasureGeometry / PTMeasureBVHArrays)
 # ---------------------------------------------------------------------------------------

@@ -18,6 +18,7 @@
 #include "chart_rule.h"
 #include "sh_rule.h"
 #include "volume_rule.h"
+#include "lmfilter_rule.h"
 #include "ptmi_plugin.h"
 
 namespace {
@@ -222,6 +223,14 @@ PT_API int PTProbeGridIrradianceHost(const PTProbeGrid* grid, const PTProbeCoeff
                                      uint64_t count, PTIrradiance* out)
 {
     if (!ptvol::grid_irradiance_host(grid, sh, depth, queries, count, out, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+// The lightmap denoiser on the host (lmfilter_host.cpp; Part 17 has the rule).  No GPU involved.
+PT_API int PTDenoiseLightmapHost(const PTLightmapDenoiseParams* params, const uint32_t* texels, const PTReceiver* recv, const PTIrradiance* irr, uint64_t count,
+                                 uint32_t width, uint32_t height, PTIrradiance* out)
+{
+    if (!ptlmf::denoise_host(params, texels, recv, irr, count, width, height, out, g_buildError)) return 0;
     g_buildError.clear();
     return 1;
 }

@@ -8,6 +8,7 @@
 #include "pt_skin.h"
 #include "pt_morph.h"
 #include "pt_lightmap.h"
+#include "pt_lmfilter.h"
 #include "bvh_refit.h"
 #include "bvh_builder_gpu.h"
 
@@ -253,6 +254,11 @@ struct PTContext {
         DeviceBuffer image;                     // 16 B per texel: the resolve's second image
         PinnedBuffer count;                     // the total, read back
     } lightmap;
+    // the lightmap denoiser (PTDenoiseLightmap): 64 B per texel, grown on demand, kept across PTSetScene
+    struct LightmapFilter {
+        DeviceBuffer state[2];                  // 16 B per texel each: (e, v), the levels go from one to the other
+        DeviceBuffer guideP, guideN;            // 16 B per texel each: (P, h2) and (N, flags)
+    } lmfilter;
     // scene updates (PTUpdateInstances / Lights / Materials): two generations of what an update rewrites, allocated on the first
     // update of each kind and discarded by PTSetScene.  cur = -1 while PTSetScene's own buffers are current.
     struct UpdGroup {

@@ -732,15 +732,42 @@ class PathTracer:
         cur.wait_stream(ext)
         return image
 
+    def denoise_lightmap(self, texels, receivers, irradiance, width: int, height: int, samples: int, iterations: int = 5, params=None):
+        """PTDenoiseLightmap: a chart-aware a-trous filter over a gathered list, in texel space, on the GPU (Part 17 has the rule).
+        texels: (n,) int32 / uint32 device tensor of unique texel indices and receivers: (n, 8) float32 PTReceiver rows
+        (chart_receivers'), irradiance: (n, 4) float32 (irradiance()'s, of `samples` samples per texel, 2 or more).  iterations:
+        0 ... 8 levels; params: a dict of abi.lightmap_denoise_params' keywords (sigma_luminance, sigma_position, sigma_plane,
+        normal_power, iterations) or a PTLightmapDenoiseParams.  Returns an (n, 4) float32 device tensor that resolve_lightmap
+        takes: the filtered rgb, and in m2's place the variance estimate of the filtered luminance.  Texels that touch in the atlas
+        but not in the world do not mix.  Ordered against torch's current stream both ways."""
+        import torch
+        assert texels.element_size() == 4 and texels.dim() == 1 and texels.is_contiguous(), (texels.dtype, texels.shape)
+        n = texels.shape[0]
+        assert receivers.dtype == torch.float32 and receivers.is_contiguous() and receivers.shape == (n, 8), receivers.shape
+        assert irradiance.dtype == torch.float32 and irradiance.is_contiguous() and irradiance.shape == (n, 4), irradiance.shape
+        p = plugin.lightmap_denoise_params(samples, iterations, params)
+        dev = texels.device
+        out = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
+        ext.wait_stream(cur)
+        plugin.check(self.lib.PTDenoiseLightmap(self.ctx, C.byref(p), texels.data_ptr() if n else None, receivers.data_ptr() if n else None,
+                                                irradiance.data_ptr() if n else None, n, int(width), int(height), out.data_ptr() if n else None))
+        cur.wait_stream(ext)
+        return out
+
     def bake_lightmap(self, width: int, height: int, spp: int = 64, mesh: int = None, instance: int = None, uvs=None, dilate: int = 2, seed: int = 0,
-                      first_sample: int = 0, params: abi.PTFrameParams = None, as_tensor: bool = False):
+                      first_sample: int = 0, params: abi.PTFrameParams = None, as_tensor: bool = False, denoise=None):
         """A lightmap of one mesh: chart_receivers, PTGatherIrradiance over them, resolve_lightmap -- nothing but the final image
         leaves the device.  spp, first_sample and params are irradiance()'s (samples [first_sample, first_sample + spp) of every
         texel; two bakes over disjoint ranges fold by 5.18's rule), the rest chart_receivers' and resolve_lightmap's.
+        denoise: None, or what denoise_lightmap runs between the gather and the resolve: a number of levels, or a dict of its parameters.
         Returns (height, width, 4) float32 -- numpy, or with as_tensor a device tensor; w tells baked (1), dilated (0.5), empty (0)."""
         texels, recv = self.chart_receivers(width, height, mesh=mesh, instance=instance, uvs=uvs, seed=seed)
         if recv.shape[0]:
             irr = self.irradiance(receivers=recv, spp=spp, first_sample=first_sample, params=params)
+            if denoise is not None:
+                irr = self.denoise_lightmap(texels, recv, irr, width, height, spp, params=plugin.lightmap_denoise_params(spp, 5, denoise))
         else:                                                       # a chart that covers nothing: an empty image
             irr = recv.new_empty((0, 4))
         image = self.resolve_lightmap(texels, irr, width, height, dilate=dilate)

@@ -136,6 +136,9 @@ sig = {
     "PTProbeGridIrradiance": (i32, [vp, C.POINTER(abi.PTProbeGrid), vp, vp, vp, C.c_uint64, vp]),
     "PTProbeDepthProjectHost": (i32, [vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, C.c_float, vp]),
     "PTProbeGridIrradianceHost": (i32, [C.POINTER(abi.PTProbeGrid), vp, vp, vp, C.c_uint64, vp]),
+    # Part 17 (the lightmap denoiser)
+    "PTDenoiseLightmap": (i32, [vp, C.POINTER(abi.PTLightmapDenoiseParams), vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp]),
+    "PTDenoiseLightmapHost": (i32, [C.POINTER(abi.PTLightmapDenoiseParams), vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp]),
     "PTGetLastError": (C.c_char_p, []), "PTGetVersion": (i32, []),
 }
 EXPORTED_SYMBOLS = list(sig)
@@ -488,6 +491,36 @@ def resolve_lightmap(texels, irradiance, width: int, height: int, dilate: int = 
     if not lib.PTResolveLightmapHost(t.ctypes.data, e.ctypes.data, len(t), int(width), int(height), int(dilate), image.ctypes.data):
         raise PluginError(abi.PT_ERR_INVALID_ARG, "PTResolveLightmapHost failed: " + lib.PTGetBVHBuildError().decode())
     return image
+
+
+def lightmap_denoise_params(samples: int, iterations: int = 5, denoise=None) -> abi.PTLightmapDenoiseParams:
+    """The parameters of a lightmap denoise: `denoise` is None, a number of levels, a ready PTLightmapDenoiseParams, or a dict of
+    abi.lightmap_denoise_params' keywords that overrides `iterations` and the suggested values."""
+    if isinstance(denoise, abi.PTLightmapDenoiseParams):
+        return denoise
+    kw = {"iterations": iterations}
+    if isinstance(denoise, dict):
+        kw.update(denoise)
+    elif denoise is not None:
+        kw["iterations"] = int(denoise)
+    return abi.lightmap_denoise_params(kw.pop("samples", samples), **kw)
+
+
+def denoise_lightmap(texels, receivers, irradiance, width: int, height: int, samples: int, iterations: int = 5, params=None) -> np.ndarray:
+    """The lightmap denoiser on the host (PTDenoiseLightmapHost, include/ptmi_plugin.h Part 17): the kernels' rule, byte for byte.
+    texels (n,) uint32 unique texel indices, receivers (n, 8) float32 PTReceiver rows, irradiance (n, 4) float32 PTIrradiance rows of
+    `samples` samples.  params: a dict of abi.lightmap_denoise_params' keywords, or a PTLightmapDenoiseParams.  Returns (n, 4)
+    float32: the filtered rgb and the variance estimate of the filtered luminance.  Raises PluginError for what the twin refuses."""
+    t = np.ascontiguousarray(texels, dtype=np.uint32).reshape(-1)
+    r = np.ascontiguousarray(receivers, dtype=np.float32).reshape(-1, 8)
+    e = np.ascontiguousarray(irradiance, dtype=np.float32).reshape(-1, 4)
+    assert len(t) == len(r) == len(e), (t.shape, r.shape, e.shape)
+    p = lightmap_denoise_params(samples, iterations, params)
+    out = np.empty((len(t), 4), np.float32)
+    lib = load_library()
+    if not lib.PTDenoiseLightmapHost(C.byref(p), t.ctypes.data, r.ctypes.data, e.ctypes.data, len(t), int(width), int(height), out.ctypes.data):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTDenoiseLightmapHost failed: " + lib.PTGetBVHBuildError().decode())
+    return out
 
 
 def probe_rows(positions, seeds=None) -> np.ndarray:
