@@ -8,7 +8,10 @@ init kernel, per iteration the trace launches and the shade kernel, then cleanup
   schedule 4, flat scene      3                    (fused persistent kernel, resolve, fold)
   schedule 4, HAS_TLAS        20                   (runs schedule 1's HAS_TLAS sequence)
   schedule 0                  1                    (the megakernel)
-A pass over a block list and a radiance query of one chunk run the same sequence; schedules 0 and 4 have neither."""
+A pass over a block list and a radiance query, an irradiance gather or an SH probe call of one chunk run the same sequence
+(a gather and a probe call run one sample per slot: 16 entries x 4 samples = 64 slots, rounded up to 256, the same 8 iterations);
+schedules 0 and 4 have none of them.  A list call cut into k chunks runs k sequences: a chunk holds 2^21 slots."""
+import numpy as np
 import pytest
 
 from unity_webgpu_pathtracer_amd import scenes
@@ -46,6 +49,11 @@ def _launches(pt, call):
     return pt.timings().kernelLaunches
 
 
+def _points(rays, n):
+    """n fixed points in front of the camera, one unit along the first n camera rays, facing back at it"""
+    return rays[:n, 0:3] + rays[:n, 3:6], -rays[:n, 3:6]
+
+
 @pytest.mark.parametrize("kind", ["flat", "tlas"])
 @pytest.mark.parametrize("schedule", [0, 1, 2, 3, 4])
 def test_launches_per_call(schedule, kind):
@@ -62,6 +70,9 @@ def test_launches_per_call(schedule, kind):
             rays = pt.camera_rays(params=p)
             assert rays.shape == (W * H, 8)                      # 1,024 rays: one chunk
             got["radiance"] = _launches(pt, lambda: pt.radiance(rays, spp=1, params=p))
+            pos, nrm = _points(rays, 16)
+            got["irradiance"] = _launches(pt, lambda: pt.irradiance(pos, nrm, spp=4, params=p))
+            got["probe_sh"] = _launches(pt, lambda: pt.probe_sh(pos, spp=4, delta_lights=False, params=p))
         print(f"[launch sequence] schedule {schedule} {kind}: {got}, expected {want} each")
         assert all(n == want for n in got.values()), (got, want)
     finally:
@@ -78,5 +89,23 @@ def test_two_sub_frames_are_two_sequences():
         got = _launches(pt, lambda: pt.render_pass(p))
         print(f"[launch sequence] two sub-frames: {got}, expected {2 * EXPECTED[(1, 'flat')]}")
         assert got == 2 * EXPECTED[(1, "flat")]
+    finally:
+        pt.close()
+
+
+def test_chunks_are_sequences():
+    """The smallest lists that reach a second chunk of 2^21 slots, schedule 1 on a flat scene: two sequences each"""
+    want = 2 * EXPECTED[(1, "flat")]
+    pt = _tracer("flat", 1)
+    try:
+        p = pt.params(seed=0x1A2B)
+        rays = pt.camera_rays(params=p)
+        many = np.tile(rays, ((1 << 21) // len(rays) + 1, 1))[:(1 << 21) + 1]                 # chunks of 2^21 and 1
+        pos, nrm = _points(rays, 33)                                                        # 65,536 samples each: chunks of 32 and 1
+        got = {"radiance": _launches(pt, lambda: pt.radiance(many, spp=1, params=p)),
+               "irradiance": _launches(pt, lambda: pt.irradiance(pos, nrm, spp=65536, params=p)),
+               "probe_sh": _launches(pt, lambda: pt.probe_sh(pos, spp=65536, delta_lights=False, params=p))}
+        print(f"[launch sequence] two chunks: {got}, expected {want} each")
+        assert all(n == want for n in got.values()), (got, want)
     finally:
         pt.close()

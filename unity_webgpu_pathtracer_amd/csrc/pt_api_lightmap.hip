@@ -5,8 +5,6 @@
 
 namespace {
 
-bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1u)) != 0u; }
-
 int check_size(uint32_t width, uint32_t height, const char* who)
 {
     if (width < 1u || width > ptchart::kMaxSize || height < 1u || height > ptchart::kMaxSize)

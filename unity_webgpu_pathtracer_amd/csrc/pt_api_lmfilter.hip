@@ -3,12 +3,6 @@
 #include "pt_context.h"
 #include "lmfilter_rule.h"
 
-namespace {
-
-bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1u)) != 0u; }
-
-} // namespace
-
 extern "C" {
 
 PT_API int PTDenoiseLightmap(PTContext* c, const PTLightmapDenoiseParams* hostParams, const uint32_t* dTexels, const PTReceiver* dRecv, const PTIrradiance* dIrr,

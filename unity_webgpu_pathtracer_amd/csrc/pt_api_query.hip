@@ -20,12 +20,11 @@ int trace_rays(PTContext* c, const PTRay* dRays, uint64_t count, uint32_t flags,
     const uint32_t mode = (flags & PT_QUERY_SURFACE) ? 2u : (flags & PT_QUERY_ANY_HIT) ? 1u : 0u;
     const bool stats = c->statsLevel > 0;
     const uint32_t cap = c->query.caps[pt_query_kernel_index(c->scene.hasTlas != 0u, mode, stats)];
-    for (uint64_t first = 0; first < count; first += kQueryLaunchRays) {
-        const uint64_t n = count - first < kQueryLaunchRays ? count - first : kQueryLaunchRays;
-        HIP_TRY(pt_launch_query(c->scene, (const float4*)(dRays + first), (uint32_t)n, mode, stats, (float4*)(dHits + first),
+    return for_each_launch(count, kQueryLaunchRays, [&](uint64_t first, uint32_t n) {
+        HIP_TRY(pt_launch_query(c->scene, (const float4*)(dRays + first), n, mode, stats, (float4*)(dHits + first),
                                 mode == 2u ? (float4*)(dSurface + first) : nullptr, (uint2*)c->query.slab.ptr, cap, (unsigned long long*)c->dStats.ptr, c->stream));
-    }
-    return PT_OK;
+        return PT_OK;
+    });
 }
 } // namespace
 
@@ -68,7 +67,8 @@ PT_API int PTTraceRaysHost(PTContext* c, const PTRay* rays, uint64_t count, uint
     HIP_TRY(hipSetDevice(c->device));
     RoctxRange range("PT ray query (host)");
     const bool surf = (flags & PT_QUERY_SURFACE) != 0u;
-    // the staging buffers regrow without a drain: every use of them ends in this call's final synchronise
+    // not host_round_trip: a third buffer, and the surface records come back through a temporary.  The staging buffers regrow
+    // without a drain for its reason
     PTContext::Query& q = c->query;
     if ((rc = q.rays.reserve(count * sizeof(PTRay)))) return rc;
     if ((rc = q.hits.reserve(count * sizeof(PTRayHit)))) return rc;

@@ -74,6 +74,55 @@ int enqueue_wavefront(PTContext* c, PTContext::WfSet& set, PTWfLaunch& L, hipEve
     return PT_OK;
 }
 
+// The one place where the stream ordering of a list call is written down (the contract is at the declaration, pt_context.h).
+// Each chunk is a launch sequence on the next state set and its stream, as a pass is (render_to), ordered after what the caller has
+// enqueued on the context stream so far -- its list; for SH probes also the delta lights' records -- and before what it enqueues
+// next.  The context stream joins the sets only after the last chunk is enqueued, so the chunks of one call overlap as passes in
+// flight do.  Two CALLS do not: the second one's list is ordered after the stream's tail, and that is the first one's join.
+// render_to and render_active do NOT go through here, and should not: a pass orders only its resolve behind the context stream
+// (orderAfter), joins per sequence and carves every set on the first pass, for measured reasons.
+int enqueue_list_chunks(PTContext* c, const PTFrameParams& p, uint64_t count, uint64_t perChunk, uint32_t slotsPerEntry, const char* rangeName,
+                        ListChunkFill fill, void* fillArg)
+{
+    RoctxRange range(rangeName);
+    int rc;
+    uint32_t maxIterations;
+    if ((rc = wavefront_limits(p, maxIterations))) return rc;
+    if (count == 0) return PT_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    uint32_t used = 0u;                 // bit k: set k carries a chunk of this call
+    static_assert(PT_WF_SETS <= 32, "one bit per state set");
+    for (uint64_t first = 0; first < count; first += perChunk) {
+        const uint32_t n = (uint32_t)(count - first < perChunk ? count - first : perChunk);
+        EventPair ep;
+        if (c->profiling && (rc = take_event_pair(c, ep))) return rc;
+        uint32_t k;
+        PTContext::WfSet& set = next_wavefront_set(c, &k);
+        used |= 1u << k;
+        const uint32_t numSlots = (n * slotsPerEntry + 255u) & ~255u;
+        // the arena only ever grows; a list of another length is a new carving of the same memory (ensure_wavefront)
+        if ((rc = ensure_wavefront(c, set, numSlots, maxIterations))) return rc;
+        set.wf.slotsPerPass = numSlots;
+        PTWfLaunch L = {};
+        L.params = &p;
+        fill(fillArg, first, n, L);
+        // unlike a pass, the WHOLE chain waits for what the context stream holds so far: its init kernel reads the caller's list
+        HIP_TRY(hipEventRecord(set.callEv, c->stream));
+        HIP_TRY(hipStreamWaitEvent(set.stream, set.callEv, 0));
+        uint32_t launches = 0;
+        if ((rc = enqueue_wavefront(c, set, L, c->profiling ? ep.start.h : nullptr, c->profiling ? ep.stop.h : nullptr, launches))) return rc;
+        if (c->profiling) {
+            ep.launches = launches;
+            c->pending.push_back(std::move(ep));
+        }
+    }
+    // joined after the last chunk, not per sequence: the chunks of a call overlap.  Consumers of the context stream then see every
+    // entry's result (a set that carried several chunks: its last record covers them)
+    for (uint32_t k = 0; k < c->numSets; ++k)
+        if (used & (1u << k)) HIP_TRY(hipStreamWaitEvent(c->stream, c->sets[k].done, 0));
+    return PT_OK;
+}
+
 namespace {
 
 // p: imported and validated (import_frame_params).

@@ -5,8 +5,6 @@
 
 namespace {
 
-bool misaligned(const void* p) { return ((uintptr_t)p & 15u) != 0u; }
-
 int check_depth_args(uint32_t samples, float maxDistance, const char* who)
 {
     std::string err;
@@ -33,14 +31,13 @@ int probe_depth(PTContext* c, const PTProbe* dProbes, uint64_t count, uint32_t f
     if ((rc = W.hits.reserve(slots * sizeof(float4), c->stream))) return rc;
     const bool stats = c->statsLevel > 0;
     const uint32_t cap = c->query.caps[pt_query_kernel_index(c->scene.hasTlas != 0u, PT_QUERY_CLOSEST, stats)];
-    for (uint64_t first = 0; first < count; first += perChunk) {
-        const uint32_t n = (uint32_t)(count - first < perChunk ? count - first : perChunk);
+    return for_each_launch(count, perChunk, [&](uint64_t first, uint32_t n) {
         HIP_TRY(pt_launch_probe_depth_rays(dProbes + first, n, samples, firstSample, maxDistance, (float4*)W.rays.ptr, c->stream));
         HIP_TRY(pt_launch_query(c->scene, (const float4*)W.rays.ptr, n * samples, PT_QUERY_CLOSEST, stats, (float4*)W.hits.ptr, nullptr,
                                 (uint2*)c->query.slab.ptr, cap, (unsigned long long*)c->dStats.ptr, c->stream));
         HIP_TRY(pt_launch_probe_depth_resolve(dProbes + first, n, samples, firstSample, maxDistance, (const float4*)W.hits.ptr, dOut + first, c->stream));
-    }
-    return PT_OK;
+        return PT_OK;
+    });
 }
 
 } // namespace
@@ -59,21 +56,13 @@ PT_API int PTProbeDepth(PTContext* c, const PTProbe* dProbes, uint64_t count, ui
 PT_API int PTProbeDepthHost(PTContext* c, const PTProbe* probes, uint64_t count, uint32_t firstSample, uint32_t samples, float maxDistance, PTProbeDepthMap* out)
 {
     if (!c) return fail(PT_ERR_INVALID_ARG, "PTProbeDepthHost: ctx == NULL");
-    int rc = check_depth_args(samples, maxDistance, "PTProbeDepthHost");
-    if (rc) return rc;
+    if (int rc = check_depth_args(samples, maxDistance, "PTProbeDepthHost")) return rc;
     if (!probes || !out) return fail(PT_ERR_INVALID_ARG, "PTProbeDepthHost: probes/out == NULL");
     if (!c->hasScene) return fail(PT_ERR_NO_SCENE, "PTSetScene has not been called");
     if (count == 0) return PT_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    PTContext::Volume& W = c->volume;
-    // the staging buffers regrow without a drain: every use of them ends in this call's final synchronise
-    if ((rc = W.probes.reserve(count * sizeof(PTProbe)))) return rc;
-    if ((rc = W.out.reserve(count * sizeof(PTProbeDepthMap)))) return rc;
-    HIP_TRY(hipMemcpyAsync(W.probes.ptr, probes, count * sizeof(PTProbe), hipMemcpyHostToDevice, c->stream));
-    if ((rc = probe_depth(c, (const PTProbe*)W.probes.ptr, count, firstSample, samples, maxDistance, (PTProbeDepthMap*)W.out.ptr))) return rc;
-    HIP_TRY(hipMemcpyAsync(out, W.out.ptr, count * sizeof(PTProbeDepthMap), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return PT_OK;
+    return host_round_trip(c, c->volume.host, probes, count, out, [&](const PTProbe* dProbes, PTProbeDepthMap* dOut) {
+        return probe_depth(c, dProbes, count, firstSample, samples, maxDistance, dOut);
+    });
 }
 
 PT_API int PTProbeGridIrradiance(PTContext* c, const PTProbeGrid* grid, const PTProbeCoeffs* dSH, const PTProbeDepthMap* dDepth, const PTReceiver* dQueries,
@@ -88,12 +77,10 @@ PT_API int PTProbeGridIrradiance(PTContext* c, const PTProbeGrid* grid, const PT
         return fail(PT_ERR_INVALID_ARG, "PTProbeGridIrradiance: sh/depth/queries/out is not 16-byte aligned");
     if (count == 0) return PT_OK;
     HIP_TRY(hipSetDevice(c->device));
-    constexpr uint64_t kPerLaunch = 1ull << 30;
-    for (uint64_t first = 0; first < count; first += kPerLaunch) {
-        const uint32_t n = (uint32_t)(count - first < kPerLaunch ? count - first : kPerLaunch);
+    return for_each_launch(count, 1ull << 30, [&](uint64_t first, uint32_t n) {
         HIP_TRY(pt_launch_probe_grid_irradiance(*grid, dSH, dDepth, dQueries + first, n, dOut + first, c->stream));
-    }
-    return PT_OK;
+        return PT_OK;
+    });
 }
 
 } // extern "C"

@@ -15,6 +15,7 @@
 #include <cstring>
 #include <initializer_list>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -149,6 +150,9 @@ struct UploadTable {
 
 struct EventPair { Event start, stop; uint32_t launches = 0; };
 
+// what a host variant stages a caller's list and its results in on the device (host_round_trip), grown on demand; one per feature
+struct HostStaging { DeviceBuffer in, out; };
+
 struct PTContext {
     int device = 0;
     Stream stream;
@@ -226,25 +230,19 @@ struct PTContext {
         uint32_t lastM = 0;                     // samples the call added per block; 0 = none pending
         UploadTable momentsTable, invDof;       // on the context stream
     } adaptive;
-    // radiance queries (PTTraceRadianceHost): host staging, grown on demand
-    struct Radiance {
-        DeviceBuffer rays, out;
-    } radiance;
-    // irradiance gathers (PTGatherIrradianceHost): likewise
-    struct Gather {
-        DeviceBuffer recv, out;
-    } gather;
+    HostStaging radiance;                       // radiance queries (PTTraceRadianceHost)
+    HostStaging gather;                         // irradiance gathers (PTGatherIrradianceHost)
     // SH light probes (PTProbeSH): the delta lights' rays, Li and any-hit records of a call, 64 bytes per (probe, light) pair,
     // written and read in stream order behind the context stream; PTProbeSHHost's staging
     struct Probe {
         DeviceBuffer deltaRays, deltaLi, deltaHits;
-        DeviceBuffer probes, out;
+        HostStaging host;
     } probe;
     // probe volumes (PTProbeDepth): the rays and hit records of one chunk, 48 bytes per sample, used in stream order on the
     // context stream; PTProbeDepthHost's staging
     struct Volume {
         DeviceBuffer rays, hits;
-        DeviceBuffer probes, out;
+        HostStaging host;
     } volume;
     // lightmap charts (PTRasterizeChart / PTResolveLightmap): grown on demand, kept across PTSetScene
     struct Lightmap {
@@ -363,12 +361,66 @@ inline int import_frame_params(const PTFrameParams* in, PTFrameParams& p)
     return rc ? rc : validate_params(p);
 }
 
+// a device pointer the kernels read or write in units of `a` bytes; NULL counts as aligned (the NULL checks are the callers')
+inline bool misaligned(const void* p, uintptr_t a = 16) { return ((uintptr_t)p & (a - 1u)) != 0u; }
+
 // auto (-1): scenes whose whole BVH is a handful of nodes (Cornell box: 1 node) have no traversal to speak of; the
 // wavefront's per-iteration path-state traffic then costs more than it buys (measured 8.7 vs 10.5 Grays/s)
 inline int effective_schedule(const PTContext* c)
 {
     if (c->schedule >= 0) return c->schedule;
     return (c->nodes.used <= 80u * 16u && !c->scene.hasTlas) ? 0 : 1;
+}
+
+// What the entry points that make `samples` samples per list entry check after the context (gathers, SH probes): params, the
+// sample count, the bounce limit.  p1: params with one sample per slot
+inline int import_sampled_params(const PTFrameParams* hostParams, uint32_t samples, const char* who, PTFrameParams& p1)
+{
+    if (!hostParams) return fail(PT_ERR_INVALID_ARG, std::string(who) + ": params == NULL");
+    if (int rc = import_frame_params(hostParams, p1)) return rc;
+    p1.SamplesPerPass = 1;
+    if (samples == 0u || samples > PT_GATHER_MAX_SAMPLES)
+        return fail(PT_ERR_UNSUPPORTED, std::string(who) + ": samples = " + std::to_string(samples) + " (1 ... " + std::to_string(PT_GATHER_MAX_SAMPLES) + ")");
+    if (p1.MaxRayBounces > 8191u) return fail(PT_ERR_UNSUPPORTED, std::string(who) + ": MaxRayBounces > 8191 does not fit the packed path state");
+    return PT_OK;
+}
+
+// a list call needs a scene and a schedule with launch sequences; noun: what the list holds ("ray", "receiver", "probe")
+inline int check_list_schedule(const PTContext* c, const char* who, const char* noun)
+{
+    if (!c->hasScene) return fail(PT_ERR_NO_SCENE, "PTSetScene has not been called");
+    const int schedule = effective_schedule(c);
+    if (schedule < 1 || schedule > 3)
+        return fail(PT_ERR_UNSUPPORTED, std::string(who) + ": schedule " + std::to_string(schedule) + " has no pass over a " + noun + " list (schedules 1, 2 and 3 do: PTSetSchedule)");
+    return PT_OK;
+}
+
+// fn(first, n) for every launch of at most perLaunch (<= 2^32 - 1) entries that `count` entries are cut into, in order; stops at
+// the first rc != PT_OK
+template <class Fn>
+int for_each_launch(uint64_t count, uint64_t perLaunch, Fn&& fn)
+{
+    for (uint64_t first = 0; first < count; first += perLaunch)
+        if (int rc = fn(first, (uint32_t)(count - first < perLaunch ? count - first : perLaunch))) return rc;
+    return PT_OK;
+}
+
+// A host variant's round trip: `count` entries of the caller's `in` to the device, body(dIn, dOut) -- the device variant's, which
+// enqueues on the context stream or joins it --, `count` results back into `out`, synchronised.  count == 0: the body's checks only.
+// The staging buffers regrow without a drain: every use of them ends in this call's final synchronise.
+template <class In, class Out, class Body>
+int host_round_trip(PTContext* c, HostStaging& s, const In* in, uint64_t count, Out* out, Body&& body)
+{
+    int rc;
+    if (count) {
+        HIP_TRY(hipSetDevice(c->device));
+        if ((rc = s.in.reserve(count * sizeof(In))) || (rc = s.out.reserve(count * sizeof(Out)))) return rc;
+        HIP_TRY(hipMemcpyAsync(s.in.ptr, in, count * sizeof(In), hipMemcpyHostToDevice, c->stream));
+    }
+    if ((rc = body((const In*)s.in.ptr, (Out*)s.out.ptr)) || count == 0) return rc;
+    HIP_TRY(hipMemcpyAsync(out, s.out.ptr, count * sizeof(Out), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return PT_OK;
 }
 
 // the material slots that name a texture: baseColor, metallicRoughness, emission, occlusion (normal map is unused)
@@ -392,7 +444,7 @@ int ensure_frames(PTContext* c, uint32_t w, uint32_t h);                        
 int import_batch(const PTFrameParams* hostParams, int count, PTFrameParams& first, PTBatch& batch);      // pt_api_render.hip
 int take_event_pair(PTContext* c, EventPair& ep);                               // pt_api_render.hip: a start / stop pair for a profiled pass
 int ensure_wavefront(PTContext* c, PTContext::WfSet& set, uint32_t numSlots, uint32_t maxIterations);      // pt_api_render.hip
-// ---- enqueueing a wavefront launch sequence on the next state set (pt_api_render.hip): passes, adaptive passes, radiance queries ----
+// ---- enqueueing a wavefront launch sequence on the next state set (pt_api_render.hip): passes, adaptive passes, list calls ----
 // the limits the packed state word sets on SamplesPerPass / MaxRayBounces; maxIterations: the iteration bound a state set is carved for
 int wavefront_limits(const PTFrameParams& p, uint32_t& maxIterations);
 PTContext::WfSet& next_wavefront_set(PTContext* c, uint32_t* index = nullptr);      // state sets take turns; index (may be null): which one
@@ -400,6 +452,21 @@ PTContext::WfSet& next_wavefront_set(PTContext* c, uint32_t* index = nullptr);  
 // counters, stream, schedule and iterations come from c and set.  On set.stream, in order: wait for a pending scene update, record
 // profStart (null: none), the launch sequence, record profStop (null: none), record set.done.  launches += the sequence's kernel launches.
 int enqueue_wavefront(PTContext* c, PTContext::WfSet& set, PTWfLaunch& L, hipEvent_t profStart, hipEvent_t profStop, uint32_t& launches);
+// A list call (radiance queries, irradiance gathers, SH probes): one launch sequence per chunk of perChunk whole entries of a
+// list of `count`, each entry slotsPerEntry slots (perChunk * slotsPerEntry <= PT_RADIANCE_CHUNK), under the ROCTX range
+// rangeName.  Each sequence runs on the next state set and its stream, behind what the context stream holds at that moment; the
+// context stream joins every set used, once, after the last chunk (pt_api_render.hip has the reasons).  The caller has checked
+// the scene and the schedule (check_list_schedule); p is checked against wavefront_limits here, then count == 0 returns PT_OK.
+// fill(first, n, L): the slot mapping and the output of chunk [first, first + n) into L, whose params are p already.
+using ListChunkFill = void (*)(void* fill, uint64_t first, uint32_t n, PTWfLaunch& L);
+int enqueue_list_chunks(PTContext* c, const PTFrameParams& p, uint64_t count, uint64_t perChunk, uint32_t slotsPerEntry, const char* rangeName,
+                        ListChunkFill fill, void* fillArg);
+template <class Fill>
+int enqueue_list_chunks(PTContext* c, const PTFrameParams& p, uint64_t count, uint64_t perChunk, uint32_t slotsPerEntry, const char* rangeName, Fill&& fill)
+{
+    return enqueue_list_chunks(c, p, count, perChunk, slotsPerEntry, rangeName,
+                               [](void* f, uint64_t first, uint32_t n, PTWfLaunch& L) { (*(std::remove_reference_t<Fill>*)f)(first, n, L); }, (void*)&fill);
+}
 // pt_api_adaptive.hip: the per-block 1 / ((k_b - 1) W_b) table on the device while adaptive state of the moments' size tracks
 // moments, else NULL (rc != PT_OK on a failed upload); minObs / minSamples: the minimum over the blocks this context owns
 // table == NULL: only the minima, nothing is uploaded

@@ -9,6 +9,7 @@ upload (BVHScene.cs:629-667), then binds the buffers (BVHScene.cs:140-167) throu
 All compute goes through the C-ABI of libunity-webgpu-pathtracer-plugin.so (include/ptmi_plugin.h); nothing
 here renders, traverses or shades on the host.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -338,6 +339,40 @@ class PathTracer:
     def passes_in_flight(self) -> int:
         return self.lib.PTGetPassesInFlight(self.ctx)
 
+    # ---- what the calls that take or return device tensors share
+    @contextlib.contextmanager
+    def _ordered(self, dev):
+        """Orders what the block enqueues on the context stream against torch's current stream on `dev`, both ways, without a
+        host synchronisation."""
+        import torch
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
+        ext.wait_stream(cur)                   # the inputs and the fresh outputs are ready before the call's work runs
+        yield
+        cur.wait_stream(ext)                   # torch's later work sees the results -- and any reuse of these buffers comes after
+
+    @staticmethod
+    def _seed_bits(seeds, n, dev):
+        """(n,) int32 on `dev` holding the bits of uint32 seeds; None = the entry index"""
+        import torch
+        if seeds is None:
+            return torch.arange(n, dtype=torch.int32, device=dev)
+        sd = torch.as_tensor(seeds, device=dev).reshape(n).to(torch.int64).bitwise_and(0xFFFFFFFF)
+        return torch.where(sd >= 2 ** 31, sd - 2 ** 32, sd).to(torch.int32)
+
+    def _sample_rays(self, fn, rows, p, first_sample, spp):
+        """PTGatherRays / PTProbeRays (`fn`) over receiver / probe rows: the (n * spp, 8) ray rows, numpy for numpy rows (uploaded
+        and read back), else a device tensor"""
+        import torch
+        as_numpy = isinstance(rows, np.ndarray)
+        dev = torch.device(f"cuda:{self.device}")
+        d_rows = torch.from_numpy(rows).to(dev) if as_numpy else rows
+        n = rows.shape[0]
+        rays = torch.empty((n * max(spp, 0), 8), dtype=torch.float32, device=dev)
+        with self._ordered(dev):
+            plugin.check(fn(self.ctx, C.byref(p), d_rows.data_ptr(), n, first_sample & 0xFFFFFFFF, spp, rays.data_ptr()))
+        return rays.cpu().numpy() if as_numpy else rays
+
     # ---- ray queries (include/ptmi_plugin.h Part 3)
     def trace_rays(self, rays, any_hit: bool = False, surface: bool = False):
         """Trace a batch of rays against the context's scene on the GPU.
@@ -367,11 +402,8 @@ class PathTracer:
         n = rays.shape[0]
         hits = torch.empty((n, 4), dtype=torch.float32, device=dev)
         surf = torch.zeros((n, 12), dtype=torch.float32, device=dev) if surface else None
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
-        ext.wait_stream(cur)                   # the rays and the fresh outputs are ready before the query runs
-        plugin.check(self.lib.PTTraceRays(self.ctx, rays.data_ptr(), n, flags, hits.data_ptr(), surf.data_ptr() if surface else None))
-        cur.wait_stream(ext)                   # torch's later work sees the results -- and any reuse of these buffers comes after
+        with self._ordered(dev):
+            plugin.check(self.lib.PTTraceRays(self.ctx, rays.data_ptr(), n, flags, hits.data_ptr(), surf.data_ptr() if surface else None))
         return (hits, surf) if surface else hits
 
     # ---- radiance queries (include/ptmi_plugin.h Part 8)
@@ -405,11 +437,8 @@ class PathTracer:
             assert pixels.device == dev and pixels.dim() == 1 and pixels.is_contiguous() and pixels.element_size() == 4, (pixels.device, pixels.shape, pixels.dtype)
             idx, n = pixels, pixels.numel()
         rays = torch.empty((n, 8), dtype=torch.float32, device=dev)
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
-        ext.wait_stream(cur)
-        plugin.check(self.lib.PTCameraRays(self.ctx, C.byref(p), idx.data_ptr() if idx is not None and n else None, n, rays.data_ptr()))
-        cur.wait_stream(ext)
+        with self._ordered(dev):
+            plugin.check(self.lib.PTCameraRays(self.ctx, C.byref(p), idx.data_ptr() if idx is not None and n else None, n, rays.data_ptr()))
         return rays.cpu().numpy() if as_numpy else rays
 
     def radiance(self, rays, spp: int = 1, params: abi.PTFrameParams = None):
@@ -435,11 +464,8 @@ class PathTracer:
         dev = rays.device
         n = rays.shape[0]
         out = torch.empty((n, 4), dtype=torch.float32, device=dev)
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
-        ext.wait_stream(cur)                   # the rays and the fresh output are ready before the query runs
-        plugin.check(self.lib.PTTraceRadiance(self.ctx, C.byref(p), rays.data_ptr(), n, out.data_ptr()))
-        cur.wait_stream(ext)                   # torch's later work sees the results -- and any reuse of these buffers comes after
+        with self._ordered(dev):
+            plugin.check(self.lib.PTTraceRadiance(self.ctx, C.byref(p), rays.data_ptr(), n, out.data_ptr()))
         return out
 
     # ---- irradiance gathers (include/ptmi_plugin.h Part 13)
@@ -461,12 +487,7 @@ class PathTracer:
         n = positions.reshape(-1, 3).shape[0]
         recv = torch.zeros((n, 8), dtype=torch.float32, device=positions.device)
         recv[:, 0:3], recv[:, 4:7] = positions.reshape(-1, 3), normals.reshape(-1, 3).to(positions.device)
-        if seeds is None:
-            sd = torch.arange(n, dtype=torch.int32, device=positions.device)
-        else:
-            sd = torch.as_tensor(seeds, device=positions.device).reshape(n).to(torch.int64).bitwise_and(0xFFFFFFFF)
-            sd = torch.where(sd >= 2 ** 31, sd - 2 ** 32, sd).to(torch.int32)
-        recv.view(torch.int32)[:, 3] = sd
+        recv.view(torch.int32)[:, 3] = self._seed_bits(seeds, n, positions.device)
         return recv
 
     def irradiance(self, positions=None, normals=None, spp: int = 64, first_sample: int = 0, seeds=None, params: abi.PTFrameParams = None, receivers=None):
@@ -495,31 +516,15 @@ class PathTracer:
             return out
         import torch
         out = torch.empty((n, 4), dtype=torch.float32, device=recv.device)
-        cur = torch.cuda.current_stream(recv.device)
-        ext = torch.cuda.ExternalStream(self.stream(), device=recv.device)
-        ext.wait_stream(cur)
-        plugin.check(self.lib.PTGatherIrradiance(self.ctx, C.byref(p), recv.data_ptr(), n, first_sample & 0xFFFFFFFF, spp, out.data_ptr()))
-        cur.wait_stream(ext)
+        with self._ordered(recv.device):
+            plugin.check(self.lib.PTGatherIrradiance(self.ctx, C.byref(p), recv.data_ptr(), n, first_sample & 0xFFFFFFFF, spp, out.data_ptr()))
         return out
 
     def gather_rays(self, positions, normals, spp: int = 64, first_sample: int = 0, seeds=None, params: abi.PTFrameParams = None):
         """PTGatherRays: the gather ray and RNG state each sample of irradiance() leaves the receiver with, as radiance() takes
         them: (n * spp, 8) float32 rows, entry-major (row i * spp + j = sample first_sample + j of entry i); a sample that ended at
         the receiver has a NaN direction.  numpy in, numpy out; device tensors in, a device tensor out."""
-        import torch
-        p = self._radiance_params(params)
-        recv = self._receivers(positions, normals, seeds)
-        as_numpy = isinstance(recv, np.ndarray)
-        dev = torch.device(f"cuda:{self.device}")
-        d_recv = torch.from_numpy(recv).to(dev) if as_numpy else recv
-        n = recv.shape[0]
-        rays = torch.empty((n * max(spp, 0), 8), dtype=torch.float32, device=dev)
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
-        ext.wait_stream(cur)
-        plugin.check(self.lib.PTGatherRays(self.ctx, C.byref(p), d_recv.data_ptr(), n, first_sample & 0xFFFFFFFF, spp, rays.data_ptr()))
-        cur.wait_stream(ext)
-        return rays.cpu().numpy() if as_numpy else rays
+        return self._sample_rays(self.lib.PTGatherRays, self._receivers(positions, normals, seeds), self._radiance_params(params), first_sample, spp)
 
     # ---- SH light probes (include/ptmi_plugin.h Part 15)
     def _probes(self, positions, seeds):
@@ -532,12 +537,7 @@ class PathTracer:
         n = pos.shape[0]
         rows = torch.empty((n, 4), dtype=torch.float32, device=pos.device)
         rows[:, 0:3] = pos
-        if seeds is None:
-            sd = torch.arange(n, dtype=torch.int32, device=pos.device)
-        else:
-            sd = torch.as_tensor(seeds, device=pos.device).reshape(n).to(torch.int64).bitwise_and(0xFFFFFFFF)
-            sd = torch.where(sd >= 2 ** 31, sd - 2 ** 32, sd).to(torch.int32)
-        rows.view(torch.int32)[:, 3] = sd
+        rows.view(torch.int32)[:, 3] = self._seed_bits(seeds, n, pos.device)
         return rows
 
     def probe_sh(self, positions, spp: int = 256, first_sample: int = 0, seeds=None, delta_lights: bool = True, params: abi.PTFrameParams = None):
@@ -561,31 +561,15 @@ class PathTracer:
             return out[:, :27].reshape(n, 9, 3).copy(), out[:, 27].copy()
         import torch
         out = torch.empty((n, 28), dtype=torch.float32, device=rows.device)
-        cur = torch.cuda.current_stream(rows.device)
-        ext = torch.cuda.ExternalStream(self.stream(), device=rows.device)
-        ext.wait_stream(cur)
-        plugin.check(self.lib.PTProbeSH(self.ctx, C.byref(p), rows.data_ptr(), n, first_sample & 0xFFFFFFFF, spp, flags, out.data_ptr()))
-        cur.wait_stream(ext)
+        with self._ordered(rows.device):
+            plugin.check(self.lib.PTProbeSH(self.ctx, C.byref(p), rows.data_ptr(), n, first_sample & 0xFFFFFFFF, spp, flags, out.data_ptr()))
         return out[:, :27].reshape(n, 9, 3), out[:, 27]
 
     def probe_rays(self, positions, spp: int = 256, first_sample: int = 0, seeds=None, params: abi.PTFrameParams = None):
         """PTProbeRays: the ray and RNG state each sample of probe_sh() starts with, as radiance() takes them: (n * spp, 8) float32
         rows, entry-major (row i * spp + j = sample first_sample + j of probe i).  numpy in, numpy out; a device tensor in, a
         device tensor out."""
-        import torch
-        p = self._radiance_params(params)
-        rows = self._probes(positions, seeds)
-        as_numpy = isinstance(rows, np.ndarray)
-        dev = torch.device(f"cuda:{self.device}")
-        d_rows = torch.from_numpy(rows).to(dev) if as_numpy else rows
-        n = rows.shape[0]
-        rays = torch.empty((n * max(spp, 0), 8), dtype=torch.float32, device=dev)
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
-        ext.wait_stream(cur)
-        plugin.check(self.lib.PTProbeRays(self.ctx, C.byref(p), d_rows.data_ptr(), n, first_sample & 0xFFFFFFFF, spp, rays.data_ptr()))
-        cur.wait_stream(ext)
-        return rays.cpu().numpy() if as_numpy else rays
+        return self._sample_rays(self.lib.PTProbeRays, self._probes(positions, seeds), self._radiance_params(params), first_sample, spp)
 
     def probe_irradiance(self, sh, normals, probes):
         """PTProbeIrradiance: the irradiance the coefficients of probe_sh() give for unit normals.  sh (n, 9, 3), normals (q, 3),
@@ -604,16 +588,12 @@ class PathTracer:
             nrm = normals.reshape(-1, 3)
             d_q = torch.empty((nrm.shape[0], 4), dtype=torch.float32, device=dev)
             d_q[:, 0:3] = nrm
-            idx = torch.as_tensor(probes, device=dev).reshape(-1).to(torch.int64).bitwise_and(0xFFFFFFFF)
-            d_q.view(torch.int32)[:, 3] = torch.where(idx >= 2 ** 31, idx - 2 ** 32, idx).to(torch.int32)
+            d_q.view(torch.int32)[:, 3] = self._seed_bits(probes, -1, dev)
         q = d_q.shape[0]
         out = torch.empty((q, 4), dtype=torch.float32, device=dev)
         if q:
-            cur = torch.cuda.current_stream(dev)
-            ext = torch.cuda.ExternalStream(self.stream(), device=dev)
-            ext.wait_stream(cur)
-            plugin.check(self.lib.PTProbeIrradiance(self.ctx, d_sh.data_ptr() if d_sh.shape[0] else None, d_sh.shape[0], d_q.data_ptr(), q, out.data_ptr()))
-            cur.wait_stream(ext)
+            with self._ordered(dev):
+                plugin.check(self.lib.PTProbeIrradiance(self.ctx, d_sh.data_ptr() if d_sh.shape[0] else None, d_sh.shape[0], d_q.data_ptr(), q, out.data_ptr()))
         return out.cpu().numpy() if as_numpy else out
 
     probe_grid = staticmethod(probe_grid)
@@ -636,11 +616,8 @@ class PathTracer:
             return out
         import torch
         out = torch.empty((n, 64, 2), dtype=torch.float32, device=rows.device)
-        cur = torch.cuda.current_stream(rows.device)
-        ext = torch.cuda.ExternalStream(self.stream(), device=rows.device)
-        ext.wait_stream(cur)
-        plugin.check(self.lib.PTProbeDepth(self.ctx, rows.data_ptr(), n, first_sample & 0xFFFFFFFF, spp, max_distance, out.data_ptr()))
-        cur.wait_stream(ext)
+        with self._ordered(rows.device):
+            plugin.check(self.lib.PTProbeDepth(self.ctx, rows.data_ptr(), n, first_sample & 0xFFFFFFFF, spp, max_distance, out.data_ptr()))
         return out
 
     def bake_probe_volume(self, lo, hi, counts, spp: int = 256, depth_spp: int = 256, max_distance: float = None, first_sample: int = 0, seeds=None,
@@ -697,20 +674,17 @@ class PathTracer:
         if uvs is not None:
             d_uvs = uvs if isinstance(uvs, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(uvs, dtype=np.float32)).to(dev)
             assert d_uvs.dtype == torch.float32 and d_uvs.is_contiguous() and d_uvs.numel() == d.triangleCount * 6 and d_uvs.device == dev, (d_uvs.shape, d_uvs.dtype)
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
-        ext.wait_stream(cur)
-        count = C.c_uint64()
-        uv_ptr = None if d_uvs is None else d_uvs.data_ptr()
-        # a small atlas: arrays for every texel, one call; a large one: count first
-        cap = int(width) * int(height)
-        if not (0 < cap <= 1 << 22):
-            plugin.check(self.lib.PTRasterizeChart(self.ctx, C.byref(d), uv_ptr, None, None, 0, C.byref(count)))
-            cap = count.value
-        texels = torch.empty((max(cap, 1),), dtype=torch.int32, device=dev)
-        recv = torch.empty((max(cap, 1), 8), dtype=torch.float32, device=dev)
-        plugin.check(self.lib.PTRasterizeChart(self.ctx, C.byref(d), uv_ptr, texels.data_ptr(), recv.data_ptr(), cap, C.byref(count)))
-        cur.wait_stream(ext)
+        with self._ordered(dev):
+            count = C.c_uint64()
+            uv_ptr = None if d_uvs is None else d_uvs.data_ptr()
+            # a small atlas: arrays for every texel, one call; a large one: count first
+            cap = int(width) * int(height)
+            if not (0 < cap <= 1 << 22):
+                plugin.check(self.lib.PTRasterizeChart(self.ctx, C.byref(d), uv_ptr, None, None, 0, C.byref(count)))
+                cap = count.value
+            texels = torch.empty((max(cap, 1),), dtype=torch.int32, device=dev)
+            recv = torch.empty((max(cap, 1), 8), dtype=torch.float32, device=dev)
+            plugin.check(self.lib.PTRasterizeChart(self.ctx, C.byref(d), uv_ptr, texels.data_ptr(), recv.data_ptr(), cap, C.byref(count)))
         return texels[:count.value], recv[:count.value]
 
     def resolve_lightmap(self, texels, irradiance, width: int, height: int, dilate: int = 2):
@@ -724,12 +698,9 @@ class PathTracer:
         dev = texels.device
         n = texels.shape[0]
         image = torch.empty((max(int(height), 1), max(int(width), 1), 4), dtype=torch.float32, device=dev)
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
-        ext.wait_stream(cur)
-        plugin.check(self.lib.PTResolveLightmap(self.ctx, texels.data_ptr() if n else None, irradiance.data_ptr() if n else None, n, int(width), int(height),
-                                                int(dilate), image.data_ptr()))
-        cur.wait_stream(ext)
+        with self._ordered(dev):
+            plugin.check(self.lib.PTResolveLightmap(self.ctx, texels.data_ptr() if n else None, irradiance.data_ptr() if n else None, n, int(width), int(height),
+                                                    int(dilate), image.data_ptr()))
         return image
 
     def denoise_lightmap(self, texels, receivers, irradiance, width: int, height: int, samples: int, iterations: int = 5, params=None):
@@ -748,12 +719,9 @@ class PathTracer:
         p = plugin.lightmap_denoise_params(samples, iterations, params)
         dev = texels.device
         out = torch.empty((n, 4), dtype=torch.float32, device=dev)
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
-        ext.wait_stream(cur)
-        plugin.check(self.lib.PTDenoiseLightmap(self.ctx, C.byref(p), texels.data_ptr() if n else None, receivers.data_ptr() if n else None,
-                                                irradiance.data_ptr() if n else None, n, int(width), int(height), out.data_ptr() if n else None))
-        cur.wait_stream(ext)
+        with self._ordered(dev):
+            plugin.check(self.lib.PTDenoiseLightmap(self.ctx, C.byref(p), texels.data_ptr() if n else None, receivers.data_ptr() if n else None,
+                                                    irradiance.data_ptr() if n else None, n, int(width), int(height), out.data_ptr() if n else None))
         return out
 
     def bake_lightmap(self, width: int, height: int, spp: int = 64, mesh: int = None, instance: int = None, uvs=None, dilate: int = 2, seed: int = 0,
@@ -1068,11 +1036,8 @@ class PathTracer:
         assert records.is_contiguous() and records.numel() * records.element_size() % 192 == 0
         n = records.numel() * records.element_size() // 192
         dev = records.device
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
-        ext.wait_stream(cur)
-        plugin.check(self.lib.PTUpdateInstancesDevice(self.ctx, records.data_ptr(), n))
-        cur.wait_stream(ext)
+        with self._ordered(dev):
+            plugin.check(self.lib.PTUpdateInstancesDevice(self.ctx, records.data_ptr(), n))
 
     def update_lights(self, lights: np.ndarray):
         """PTUpdateLights: (k, 16) float32 PTLight records, 1 <= k <= the scene's light count."""
@@ -1155,11 +1120,8 @@ class PathTracer:
             import torch
             assert vertices.is_contiguous() and vertices.dtype == torch.float32 and vertices.numel() % 12 == 0
             assert tri_attrs is None or (tri_attrs.is_contiguous() and tri_attrs.numel() * tri_attrs.element_size() == vertices.numel() // 12 * 128)
-            cur = torch.cuda.current_stream(vertices.device)
-            ext = torch.cuda.ExternalStream(self.stream(), device=vertices.device)
-            ext.wait_stream(cur)
-            plugin.check(fn_device(self.ctx, *off, vertices.data_ptr(), vertices.numel() // 12, None if tri_attrs is None else tri_attrs.data_ptr()))
-            cur.wait_stream(ext)
+            with self._ordered(vertices.device):
+                plugin.check(fn_device(self.ctx, *off, vertices.data_ptr(), vertices.numel() // 12, None if tri_attrs is None else tri_attrs.data_ptr()))
             if bvh.gpu_instances is not None:
                 import warnings
                 warnings.warn("update_geometry with device tensors on a HAS_TLAS scene: resend the instances' world bounds "
@@ -1223,11 +1185,8 @@ class PathTracer:
             import torch
             m = joint_matrices
             assert m.is_contiguous() and m.dtype == torch.float32 and m.numel() % 12 == 0 and tuple(m.shape[1:]) in ((3, 4), (12,))
-            cur = torch.cuda.current_stream(m.device)
-            ext = torch.cuda.ExternalStream(self.stream(), device=m.device)
-            ext.wait_stream(cur)
-            plugin.check(self.lib.PTSkinGeometryDevice(self.ctx, *off, m.data_ptr(), m.numel() // 12, flags, out))
-            cur.wait_stream(ext)
+            with self._ordered(m.device):
+                plugin.check(self.lib.PTSkinGeometryDevice(self.ctx, *off, m.data_ptr(), m.numel() // 12, flags, out))
         bounds = np.array(out, np.float32).reshape(2, 3)
         if rebuild:
             self._builtCost[mesh] = self.geometry_quality(mesh)["sahCost"]
@@ -1282,12 +1241,9 @@ class PathTracer:
             w, m = weights, joint_matrices
             assert w.is_contiguous() and w.dtype == torch.float32 and w.dim() == 1
             assert m is None or (m.is_contiguous() and m.dtype == torch.float32 and m.numel() % 12 == 0 and tuple(m.shape[1:]) in ((3, 4), (12,)))
-            cur = torch.cuda.current_stream(w.device)
-            ext = torch.cuda.ExternalStream(self.stream(), device=w.device)
-            ext.wait_stream(cur)
-            plugin.check(self.lib.PTMorphGeometryDevice(self.ctx, *off, w.data_ptr(), w.numel(), None if m is None else m.data_ptr(),
-                                                        0 if m is None else m.numel() // 12, flags, out))
-            cur.wait_stream(ext)
+            with self._ordered(w.device):
+                plugin.check(self.lib.PTMorphGeometryDevice(self.ctx, *off, w.data_ptr(), w.numel(), None if m is None else m.data_ptr(),
+                                                            0 if m is None else m.numel() // 12, flags, out))
         bounds = np.array(out, np.float32).reshape(2, 3)
         if rebuild:
             self._builtCost[mesh] = self.geometry_quality(mesh)["sahCost"]
@@ -1381,11 +1337,8 @@ class ProbeVolume:
         q = recv.shape[0]
         out = torch.empty((q, 4), dtype=torch.float32, device=dev)
         if q:
-            cur = torch.cuda.current_stream(dev)
-            ext = torch.cuda.ExternalStream(pt.stream(), device=dev)
-            ext.wait_stream(cur)
-            plugin.check(pt.lib.PTProbeGridIrradiance(pt.ctx, C.byref(g), self._rows.data_ptr(), self._depth.data_ptr(), recv.data_ptr(), q, out.data_ptr()))
-            cur.wait_stream(ext)
+            with pt._ordered(dev):
+                plugin.check(pt.lib.PTProbeGridIrradiance(pt.ctx, C.byref(g), self._rows.data_ptr(), self._depth.data_ptr(), recv.data_ptr(), q, out.data_ptr()))
         return out.cpu().numpy() if as_numpy else out
 
 
