@@ -1457,6 +1457,114 @@ PT_API int PTDenoiseLightmap(PTContext* ctx, const PTLightmapDenoiseParams* para
 PT_API int PTDenoiseLightmapHost(const PTLightmapDenoiseParams* params, const uint32_t* texels, const PTReceiver* recv, const PTIrradiance* irr,
                                  uint64_t count, uint32_t width, uint32_t height, PTIrradiance* out);        /* host twin, no GPU */
 
+/* =====================================================================================================================
+ * Part 18: probe placement.  Part 16's probes sit on a regular grid, and in a real scene some of them land inside walls,
+ * pillars and furniture.  A probe inside closed geometry sees no light: its coefficients are zero, its depth record holds
+ * the inside of the object, and it darkens every point whose cell contains it.  A probe a few millimetres in front of a
+ * wall wastes half of its sphere.  PTProbePlace is the short pass before the bake that fixes both: it traces a fixed set of
+ * rays from each probe, counts the faces seen from behind, pushes the probe out of the object it is in or away from the
+ * face it is too close to -- within its own cell --, and marks what stays buried; PTProbeGridIrradiancePlaced is Part 16's
+ * lookup that honours the result.  An addition detected by symbol; PTGetVersion is unchanged.
+ *
+ * The rule (bit-exact; placement_rule.h is its one definition: the kernels, the host twins and tests/placement_ref.py
+ * evaluate it; every fp32 operator below is one IEEE binary32 operation in the order written, no fma).
+ *  - Limits.  lim[a] = maxOffset * spacing[a].  An offset o PASSES when |o[a]| <= lim[a] on every axis; a NaN fails.  A stored
+ *    offset that does not pass is read as (0, 0, 0), whole.
+ *  - One STEP for a probe {P, seed} whose stored offset reads o:
+ *    1. O[a] = P[a] + o[a].  Sample j (0 <= j < samples) has Part 15's seeding and direction w_j for (seed, firstSample, j),
+ *       word for word; every step uses the same directions.  Its ray is the PTRay {O, w_j, tmax = maxDistance, 0}, traced as a
+ *       closest-hit query with PT_QUERY_SURFACE by Part 3's rules.
+ *    2. Sample j is a HIT iff its PTRayHit.prim != 0xFFFFFFFF; only then is its PTRaySurface read (Part 3 leaves it
+ *       untouched on a miss).  With n the record's normal: c = (w.x * n.x + w.y * n.y) + w.z * n.z.  The sample is BACK iff
+ *       c > 0, otherwise FRONT: a NaN counts as front.
+ *    3. back and front are the counts.  nearestBack is the back sample with the smallest (bits(t), j) in lexicographic order,
+ *       bits(t) the uint32 pattern of the hit's t -- for the positive t a hit has, the order of the floats --; nearestFront
+ *       the same among the front samples; farthestFront the front sample with the largest bits(t), the lowest j among equals.
+ *       No floating-point sum is involved: counts, and exact selections.
+ *    4. inside = (float)back > backfaceShare * (float)samples.
+ *    5. The move (relocation steps only).  If inside: len = tNearestBack + minFrontDistance * 0.5f and
+ *       cand[a] = o[a] + w_nb[a] * len -- through the nearest face seen from behind.  Else, if a front sample exists and
+ *       tNearestFront < minFrontDistance: len = minFrontDistance - tNearestFront and cand[a] = o[a] - w_nf[a] * len --
+ *       straight away from the nearest face.  Otherwise cand = o.  cand becomes the offset iff it passes the limits; a refused
+ *       candidate leaves o as it was, bit for bit (what is stored is o as read: a stored offset that did not pass is
+ *       stored back as 0).
+ *  - PTProbePlace runs `iterations` relocation steps and then one more trace that only classifies: iterations + 1 traces;
+ *    state (0 live, PT_PROBE_INSIDE) and the statistics describe the FINAL offset.  iterations == 0 classifies the grid
+ *    positions.  It starts from o = 0 -- with PT_PLACE_KEEP_OFFSETS from the offsets already in dOut (read as above), which
+ *    is how a caller places again after a geometry update.
+ *  - PTProbePlaceStats (optional, one per probe, written by the last step only): the counts, the three sample indices
+ *    (0xFFFFFFFF where there is none) and their t (0 where there is none).
+ *  - The placed lookup is Part 16's with two changes.  A corner whose placement state has PT_PROBE_INSIDE is skipped exactly
+ *    as a corner with tri == 0 is: it reads neither coefficients nor depth and adds nothing to sumW.  Otherwise step 4 (distance,
+ *    direction, texel) uses Q[a] = Q_grid[a] + offset[a] (one add); tri stays the grid's.  With dPlacement == NULL the call IS
+ *    PTProbeGridIrradiance, bit for bit (that path does not execute the add: (-0) + 0 would change a sign bit).
+ *  - PTProbePlace: stream-ordered on the context's stream; no state set is involved, so it can run beside passes in flight.
+ *    Chunks hold floor(2^20 / samples) whole probes, and a chunk goes through all its steps before the next one starts.  The
+ *    rays, hit and surface records live in scratch the context keeps: 96 bytes per sample, 96 MB at most; growing it drains
+ *    that stream.  PTStats moves as the iterations + 1 PTTraceRays(..., PT_QUERY_SURFACE) calls over the same rays move it.
+ *  - Nothing past `count` is written.  Every device pointer is 16-byte aligned.
+ *  - PT_ERR_INVALID_ARG for a NULL or misaligned pointer (dStats may be NULL), an unknown flag bit, a spacing that is not
+ *    finite and positive, a maxDistance that is not finite, not positive or not below PT_FAR_PLANE, a minFrontDistance that is
+ *    not finite and non-negative, a backfaceShare outside [0, 1], a maxOffset outside [0, 0.5), iterations > 16.
+ *    PT_ERR_UNSUPPORTED for samples == 0 and samples > 65536.  PT_ERR_NO_SCENE for PTProbePlace before PTSetScene.
+ *    count == 0 returns PT_OK and launches nothing.  Arguments are checked before the context is used.  No CPU fallback.
+ *  - The host twins take no context and no GPU; they return 1, or 0 with PTGetBVHBuildError() set.  PTProbePlaceStepHost is
+ *    ONE step over the hit and surface records of count x samples rays, entry-major, as PTTraceRaysHost returns them for the
+ *    rays of step 1: inout[i].offset is read (as above) and, with move != 0, replaced; inout[i].state and stats[i] (stats may be
+ *    NULL) describe the offset the records were traced from.  PTProbeGridIrradiancePlacedHost is PTProbeGridIrradiancePlaced.
+ * ===================================================================================================================== */
+#define PT_PROBE_INSIDE        1u /* PTProbePlacement.state: buried; the placed lookup leaves the probe out */
+#define PT_PLACE_KEEP_OFFSETS  1u /* PTProbePlace flag: start from the offsets in dOut, not from 0 */
+#define PT_PLACE_MAX_ITERATIONS 16u
+
+typedef struct PTProbePlacement { /* 16 bytes: one 16-byte load */
+    float    offset[3];           /* added to the grid position; |offset[a]| <= maxOffset * spacing[a] */
+    uint32_t state;               /* 0 = live, PT_PROBE_INSIDE */
+} PTProbePlacement;
+
+typedef struct PTProbePlaceParams { /* 32 bytes; a host struct, passed by pointer */
+    float    spacing[3];          /* the grid's spacing; finite, > 0 */
+    float    maxDistance;         /* where a placement ray ends; finite, > 0, below PT_FAR_PLANE */
+    float    minFrontDistance;    /* a probe closer than this to a face it sees from the front moves away; finite, >= 0 */
+    float    backfaceShare;       /* [0, 1]: inside when more than this share of the samples are back */
+    float    maxOffset;           /* [0, 0.5): the limit of an offset, a fraction of the spacing per axis */
+    uint32_t iterations;          /* 0 ... 16 relocation steps */
+} PTProbePlaceParams;
+
+typedef struct PTProbePlaceStats { /* 32 bytes: two 16-byte stores */
+    uint32_t back, front;         /* the counts of the last step */
+    uint32_t nearestBack, nearestFront, farthestFront;       /* sample indices; 0xFFFFFFFF: none */
+    float    tNearestBack, tNearestFront, tFarthestFront;    /* their t; 0: none */
+} PTProbePlaceStats;
+
+#ifdef __cplusplus
+static_assert(sizeof(PTProbePlacement) == 16, "PTProbePlacement is 16 bytes");
+static_assert(sizeof(PTProbePlaceParams) == 32, "PTProbePlaceParams is 32 bytes");
+static_assert(sizeof(PTProbePlaceStats) == 32, "PTProbePlaceStats is 32 bytes");
+#else
+_Static_assert(sizeof(PTProbePlacement) == 16, "PTProbePlacement is 16 bytes");
+_Static_assert(sizeof(PTProbePlaceParams) == 32, "PTProbePlaceParams is 32 bytes");
+_Static_assert(sizeof(PTProbePlaceStats) == 32, "PTProbePlaceStats is 32 bytes");
+#endif
+
+/* Device pointers, stream-ordered on the context's stream. */
+PT_API int PTProbePlace(PTContext* ctx, const PTProbe* dProbes, uint64_t count, uint32_t firstSample, uint32_t samples,
+                        const PTProbePlaceParams* params, uint32_t flags, PTProbePlacement* dOut, PTProbePlaceStats* dStats /* may be NULL */);
+/* Host arrays: staged through device buffers the context keeps and grows; synchronous. */
+PT_API int PTProbePlaceHost(PTContext* ctx, const PTProbe* probes, uint64_t count, uint32_t firstSample, uint32_t samples,
+                            const PTProbePlaceParams* params, uint32_t flags, PTProbePlacement* out, PTProbePlaceStats* stats /* may be NULL */);
+/* dSH, dDepth, dPlacement: one entry per probe of the grid; dQueries, dOut: count entries. */
+PT_API int PTProbeGridIrradiancePlaced(PTContext* ctx, const PTProbeGrid* grid, const PTProbeCoeffs* dSH, const PTProbeDepthMap* dDepth,
+                                       const PTProbePlacement* dPlacement /* NULL = PTProbeGridIrradiance */, const PTReceiver* dQueries,
+                                       uint64_t count, PTIrradiance* dOut);
+/* host twins, no GPU */
+PT_API int PTProbePlaceStepHost(const PTProbe* probes, uint64_t count, uint32_t firstSample, uint32_t samples, const PTProbePlaceParams* params,
+                                const PTRayHit* hits, const PTRaySurface* surfaces, int move, PTProbePlacement* inout,
+                                PTProbePlaceStats* stats /* may be NULL */);
+PT_API int PTProbeGridIrradiancePlacedHost(const PTProbeGrid* grid, const PTProbeCoeffs* sh, const PTProbeDepthMap* depth,
+                                           const PTProbePlacement* placement /* NULL = PTProbeGridIrradianceHost */, const PTReceiver* queries,
+                                           uint64_t count, PTIrradiance* out);
+
 /* Text of the last error on the calling thread ("" if none). */
 PT_API const char* PTGetLastError(void);
 /* Library/ABI version: (major << 16) | minor. */

@@ -326,6 +326,46 @@ class PTProbeGrid(C.Structure):
 assert C.sizeof(PTProbeDepthMap) == 512 and C.sizeof(PTProbeGrid) == 48
 
 
+# ---- probe placement (include/ptmi_plugin.h Part 18)
+PT_PROBE_INSIDE = 1
+PT_PLACE_KEEP_OFFSETS = 1
+PT_PLACE_MAX_ITERATIONS = 16
+
+
+class PTProbePlacement(C.Structure):
+    _fields_ = [("offset", C.c_float * 3), ("state", C.c_uint32)]
+
+
+class PTProbePlaceParams(C.Structure):
+    _fields_ = [("spacing", C.c_float * 3), ("maxDistance", C.c_float), ("minFrontDistance", C.c_float), ("backfaceShare", C.c_float),
+                ("maxOffset", C.c_float), ("iterations", C.c_uint32)]
+
+
+class PTProbePlaceStats(C.Structure):
+    _fields_ = [("back", C.c_uint32), ("front", C.c_uint32), ("nearestBack", C.c_uint32), ("nearestFront", C.c_uint32),
+                ("farthestFront", C.c_uint32), ("tNearestBack", C.c_float), ("tNearestFront", C.c_float), ("tFarthestFront", C.c_float)]
+
+
+assert C.sizeof(PTProbePlacement) == 16 and C.sizeof(PTProbePlaceParams) == 32 and C.sizeof(PTProbePlaceStats) == 32
+# one PTProbePlaceStats row as a numpy record
+PLACE_STATS_DTYPE = [("back", "<u4"), ("front", "<u4"), ("nearestBack", "<u4"), ("nearestFront", "<u4"), ("farthestFront", "<u4"),
+                     ("tNearestBack", "<f4"), ("tNearestFront", "<f4"), ("tFarthestFront", "<f4")]
+
+
+def probe_place_params(spacing, max_distance: float = None, min_front_distance: float = None, backface_share: float = 0.25,
+                       max_offset: float = 0.45, iterations: int = 4) -> PTProbePlaceParams:
+    """PTProbePlaceParams for a grid of `spacing` (one number or three).  max_distance: default the spacing's diagonal;
+    min_front_distance: default 0.2 of the smallest spacing."""
+    s = [float(x) for x in (np.broadcast_to(np.asarray(spacing, np.float64), (3,)))]
+    p = PTProbePlaceParams()
+    for a in range(3):
+        p.spacing[a] = s[a]
+    p.maxDistance = float(np.linalg.norm(s)) if max_distance is None else float(max_distance)
+    p.minFrontDistance = 0.2 * min(s) if min_front_distance is None else float(min_front_distance)
+    p.backfaceShare, p.maxOffset, p.iterations = float(backface_share), float(max_offset), int(iterations)
+    return p
+
+
 # ---- lightmap charts (include/ptmi_plugin.h Part 14)
 PT_CHART_MAX_SIZE = 8192
 PT_CHART_MAX_DILATE = 16

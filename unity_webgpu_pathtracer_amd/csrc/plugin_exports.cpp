@@ -18,6 +18,7 @@
 #include "chart_rule.h"
 #include "sh_rule.h"
 #include "volume_rule.h"
+#include "placement_rule.h"
 #include "lmfilter_rule.h"
 #include "ptmi_plugin.h"
 
@@ -223,6 +224,21 @@ PT_API int PTProbeGridIrradianceHost(const PTProbeGrid* grid, const PTProbeCoeff
                                      uint64_t count, PTIrradiance* out)
 {
     if (!ptvol::grid_irradiance_host(grid, sh, depth, queries, count, out, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+// Probe placement on the host (placement_host.cpp; Part 18 has the rule).  No GPU involved.
+PT_API int PTProbePlaceStepHost(const PTProbe* probes, uint64_t count, uint32_t firstSample, uint32_t samples, const PTProbePlaceParams* params,
+                                const PTRayHit* hits, const PTRaySurface* surfaces, int move, PTProbePlacement* inout, PTProbePlaceStats* stats)
+{
+    if (!ptplace::place_step_host(probes, count, firstSample, samples, params, hits, surfaces, move, inout, stats, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+PT_API int PTProbeGridIrradiancePlacedHost(const PTProbeGrid* grid, const PTProbeCoeffs* sh, const PTProbeDepthMap* depth, const PTProbePlacement* placement,
+                                           const PTReceiver* queries, uint64_t count, PTIrradiance* out)
+{
+    if (!ptplace::grid_irradiance_placed_host(grid, sh, depth, placement, queries, count, out, g_buildError)) return 0;
     g_buildError.clear();
     return 1;
 }

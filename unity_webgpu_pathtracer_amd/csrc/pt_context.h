@@ -244,6 +244,14 @@ struct PTContext {
         DeviceBuffer rays, hits;
         HostStaging host;
     } volume;
+    // probe placement (PTProbePlace): the rays, hit and surface records of one chunk, 96 bytes per sample, used in stream order on
+    // the context stream; PTProbePlaceHost's staging (its statistics come back through hostStats)
+    struct Placement {
+        DeviceBuffer rays, hits, surfaces;
+        HostStaging host;
+        DeviceBuffer hostStats;                 // regrows without a drain, as HostStaging does: every use of it ends in the synchronise
+                                                // that closes the PTProbePlaceHost call that made it (host_round_trip)
+    } placement;
     // lightmap charts (PTRasterizeChart / PTResolveLightmap): grown on demand, kept across PTSetScene
     struct Lightmap {
         DeviceBuffer owner;                     // 4 B per texel: the owner map

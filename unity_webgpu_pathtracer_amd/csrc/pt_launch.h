@@ -294,6 +294,18 @@ hipError_t pt_launch_probe_depth_resolve(const PTProbe* probes, uint32_t entries
 // the grid has passed ptvol::check_grid; depth may be null without PT_GRID_VISIBILITY
 hipError_t pt_launch_probe_grid_irradiance(const PTProbeGrid& grid, const PTProbeCoeffs* sh, const PTProbeDepthMap* depth, const PTReceiver* queries,
                                            uint32_t count, PTIrradiance* out, hipStream_t stream);
+// ---- probe placement (include/ptmi_plugin.h Part 18; pt_placement.hip) ----
+// One step of one chunk (entries * samples <= 2^20): the rays kernel writes 2 float4 per slot = entry * samples + j from the origin
+// P + the offset as the rule reads it, the closest-hit query with surface records (pt_launch_query, mode 2) writes 1 and 3 float4
+// per slot, the step kernel turns them into the probe's new 16 bytes (move) and state, and its statistics where stats != null.
+hipError_t pt_launch_probe_place_rays(const PTProbe* probes, uint32_t entries, uint32_t samples, uint32_t firstSample, const PTProbePlaceParams& params,
+                                      const PTProbePlacement* placement, float4* rays, hipStream_t stream);
+hipError_t pt_launch_probe_place_step(const PTProbe* probes, uint32_t entries, uint32_t samples, uint32_t firstSample, const PTProbePlaceParams& params,
+                                      const float4* hits, const float4* surfaces, bool move, PTProbePlacement* placement, PTProbePlaceStats* stats,
+                                      hipStream_t stream);
+// placement is not null; otherwise as pt_launch_probe_grid_irradiance
+hipError_t pt_launch_probe_grid_irradiance_placed(const PTProbeGrid& grid, const PTProbeCoeffs* sh, const PTProbeDepthMap* depth, const PTProbePlacement* placement,
+                                                  const PTReceiver* queries, uint32_t count, PTIrradiance* out, hipStream_t stream);
 #ifndef PT_WF_FUSED_GROUPS
 #define PT_WF_FUSED_GROUPS 2u   // schedule 4: groups of 64 path contexts a persistent wave owns (power of two <= 4: numSlots is a multiple of 256).
                                 // Sponza-class 1080p / 8 spp, one pass in flight: 1: 29.9 ms, 2: 25.2, 4: 27.9, 8: 31.4

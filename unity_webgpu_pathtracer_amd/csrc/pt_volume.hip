@@ -12,6 +12,7 @@
 #include "pt_device.h"
 #include "pt_launch.h"
 #include "volume_rule.h"
+#include "pt_volume_loads.h"
 
 namespace {
 
@@ -77,21 +78,8 @@ __global__ __launch_bounds__(256) void pt_probe_grid_irradiance(PTProbeGrid G, c
     const float4 q0 = ((const float4*)queries)[2u * (size_t)q], q1 = ((const float4*)queries)[2u * (size_t)q + 1u];
     const float P[3] = {q0.x, q0.y, q0.z}, N[3] = {q1.x, q1.y, q1.z};
     float o[4];
-    ptvol::lookup(G, P, N,
-                  [&](uint32_t probe, float co[27]) {
-                      const float4* s = (const float4*)(sh + probe);
-#pragma unroll
-                      for (uint32_t t = 0; t < 7u; ++t) {
-                          const float4 v = s[t];
-                          co[4u * t] = v.x; co[4u * t + 1u] = v.y; co[4u * t + 2u] = v.z;
-                          if (t < 6u) co[4u * t + 3u] = v.w;
-                      }
-                  },
-                  [&](uint32_t probe, uint32_t texel, float& mean, float& mean2) {
-                      const float2 m = ((const float2*)(depth + probe))[texel];
-                      mean = m.x; mean2 = m.y;
-                  },
-                  o);
+    ptvol::lookup(G, P, N, [&](uint32_t probe, float co[27]) { pt_load_probe_sh(sh, probe, co); },
+                  [&](uint32_t probe, uint32_t texel, float& mean, float& mean2) { pt_load_probe_depth(depth, probe, texel, mean, mean2); }, o);
     ((float4*)out)[q] = make_float4(o[0], o[1], o[2], o[3]);
 }
 

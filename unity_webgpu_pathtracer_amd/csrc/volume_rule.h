@@ -5,6 +5,7 @@
 // give the same bits.  tests/volume_ref.py restates it.  Seeding, sphere direction and E(N) are sh_rule.h's.
 #pragma once
 #include "sh_rule.h"
+#include <type_traits>
 
 #define PT_VOL_HD PT_SH_HD
 
@@ -156,10 +157,15 @@ PT_VOL_HD float crush(float w)
     return w;
 }
 
-// One query, whole: sh and depth are read through the two callables, so that the kernel can use 16- and 8-byte loads.
+// One query, whole: sh and depth are read through the callables, so that the kernel can use 16- and 8-byte loads.
 //   loadSH(probe, float co[27]); loadDepth(probe, texel, float& mean, float& mean2)
-template <class LoadSH, class LoadDepth>
-PT_VOL_HD void lookup(const PTProbeGrid& G, const float P[3], const float N[3], LoadSH loadSH, LoadDepth loadDepth, float out[4])
+//   loadPlacement(probe, float off[3], uint32_t& state): Part 18's placed lookup -- a corner that is PT_PROBE_INSIDE is skipped as
+//   one with tri == 0 is, a live one stands at Q + off for the weights.  With NoPlacement the switch is made at compile time: that
+//   path neither loads nor adds ((-0) + 0 would change a sign bit), so Part 16's lookup keeps its bits.
+struct NoPlacement {};
+
+template <class LoadSH, class LoadDepth, class LoadPlacement>
+PT_VOL_HD void lookup(const PTProbeGrid& G, const float P[3], const float N[3], LoadSH loadSH, LoadDepth loadDepth, LoadPlacement loadPlacement, float out[4])
 {
     const float Pb[3] = {P[0] + N[0] * G.normalBias, P[1] + N[1] * G.normalBias, P[2] + N[2] * G.normalBias};
     const Cell c = cell_of(G, P);
@@ -169,6 +175,13 @@ PT_VOL_HD void lookup(const PTProbeGrid& G, const float P[3], const float N[3], 
         float Q[3], w, r;
         const float tri = corner(G, c, o, probe, Q);
         if (tri == 0.0f) continue;                              // reads nothing
+        if constexpr (!std::is_same<LoadPlacement, NoPlacement>::value) {
+            float off[3];
+            uint32_t state;
+            loadPlacement(probe, off, state);
+            if (state & PT_PROBE_INSIDE) continue;              // reads nothing more
+            for (uint32_t a = 0; a < 3u; ++a) Q[a] = Q[a] + off[a];
+        }
         if (corner_weight(G.flags, Q, Pb, N, w, r, texel)) {
             float mean, mean2;
             loadDepth(probe, texel, mean, mean2);
@@ -184,6 +197,12 @@ PT_VOL_HD void lookup(const PTProbeGrid& G, const float P[3], const float N[3], 
     }
     for (uint32_t ch = 0; ch < 3u; ++ch) out[ch] = sumW > 0.0f ? acc[ch] / sumW : 0.0f;
     out[3] = sumW;
+}
+
+template <class LoadSH, class LoadDepth>
+PT_VOL_HD void lookup(const PTProbeGrid& G, const float P[3], const float N[3], LoadSH loadSH, LoadDepth loadDepth, float out[4])
+{
+    lookup(G, P, N, loadSH, loadDepth, NoPlacement{}, out);
 }
 
 // ---- the host twins and the checks the entry points share (volume_host.cpp); false: err says why ----

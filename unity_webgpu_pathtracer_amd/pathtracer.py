@@ -620,11 +620,54 @@ class PathTracer:
             plugin.check(self.lib.PTProbeDepth(self.ctx, rows.data_ptr(), n, first_sample & 0xFFFFFFFF, spp, max_distance, out.data_ptr()))
         return out
 
+    # ---- probe placement (include/ptmi_plugin.h Part 18)
+    def place_probes(self, positions, spacing, spp: int = 64, iterations: int = 4, max_distance: float = None, min_front_distance: float = None,
+                     backface_share: float = 0.25, max_offset: float = 0.45, first_sample: int = 0, seeds=None, start=None, stats: bool = False):
+        """PTProbePlace: move the probes of a grid out of geometry and mark the buried ones, before the bake.  Each of the
+        `iterations` relocation steps traces `spp` closest-hit rays with surface records from every probe (probe_sh()'s directions),
+        counts the faces seen from behind, and moves a probe through the nearest such face when more than `backface_share` of its
+        samples see one (it is inside an object), or straight away from a face nearer than `min_front_distance`; a move that would
+        take the probe further than `max_offset` x spacing from its grid position on an axis is refused.  One more trace classifies
+        the final positions.
+
+        positions: (n, 3) float32; spacing: the grid's, one number or three; seeds: (n,) uint32, None = the probe index.
+        Defaults: max_distance = the spacing's diagonal, min_front_distance = 0.2 x the smallest spacing.
+        start: (n, 3) offsets to start from (PT_PLACE_KEEP_OFFSETS: placing again after a geometry update), None = zeros.
+          numpy array -> PTProbePlaceHost, returns numpy;
+          torch tensor on this context's device -> PTProbePlace zero-copy, ordered against torch's current stream both ways.
+        Returns (offsets (n, 3) float32, states (n,): 0 live, abi.PT_PROBE_INSIDE buried -- uint32 in numpy, int32 on the device),
+        and with stats=True also the (n,) numpy records of abi.PLACE_STATS_DTYPE that describe the final positions."""
+        q = abi.probe_place_params(spacing, max_distance, min_front_distance, backface_share, max_offset, iterations)
+        rows = self._probes(positions, seeds)
+        n = rows.shape[0]
+        flags = 0 if start is None else abi.PT_PLACE_KEEP_OFFSETS
+        if isinstance(rows, np.ndarray):
+            out = plugin.probe_placement_rows(start, None, n)
+            assert out.shape[0] == n, (out.shape, n)
+            st = np.zeros(n, abi.PLACE_STATS_DTYPE)
+            plugin.check(self.lib.PTProbePlaceHost(self.ctx, rows.ctypes.data, n, first_sample & 0xFFFFFFFF, spp, C.byref(q), flags, out.ctypes.data,
+                                                   st.ctypes.data if stats else None))
+            res = (out[:, 0:3].copy(), out[:, 3].copy().view(np.uint32))
+            return res + (st,) if stats else res
+        import torch
+        out = torch.zeros((n, 4), dtype=torch.float32, device=rows.device)
+        if start is not None:
+            out[:, 0:3] = torch.as_tensor(start, dtype=torch.float32, device=rows.device).reshape(n, 3)
+        d_st = torch.zeros((n, 8), dtype=torch.int32, device=rows.device) if stats else None
+        with self._ordered(rows.device):
+            plugin.check(self.lib.PTProbePlace(self.ctx, rows.data_ptr(), n, first_sample & 0xFFFFFFFF, spp, C.byref(q), flags, out.data_ptr(),
+                                               d_st.data_ptr() if stats else None))
+        res = (out[:, 0:3], out.view(torch.int32)[:, 3])
+        return res + (d_st.cpu().numpy().view(abi.PLACE_STATS_DTYPE).reshape(n),) if stats else res
+
     def bake_probe_volume(self, lo, hi, counts, spp: int = 256, depth_spp: int = 256, max_distance: float = None, first_sample: int = 0, seeds=None,
-                          delta_lights: bool = True, params: abi.PTFrameParams = None) -> "ProbeVolume":
+                          delta_lights: bool = True, params: abi.PTFrameParams = None, relocate=None) -> "ProbeVolume":
         """A probe volume over the box lo ... hi: counts = (nx, ny, nz) probes, the outer ones on the box's faces (a count of 1 sits
         in the middle of its axis).  Bakes probe_sh(spp) and probe_depth(depth_spp) at plugin.probe_grid_positions of the grid; both
-        stay on the device.  max_distance: where a depth ray ends, default 1.5 x the diagonal of a cell.  Returns a ProbeVolume."""
+        stay on the device.  max_distance: where a depth ray ends, default 1.5 x the diagonal of a cell.
+        relocate: None or False -- the probes stay on the grid; True, or a dict of place_probes() arguments -- place_probes() runs
+        first (the grid's spacing, first_sample and seeds), both bakes are made at position + offset (one float32 add per component,
+        on the host), and the placement stays on the device for the lookup (ProbeVolume.placement).  Returns a ProbeVolume."""
         import torch
         lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
         counts = [int(c) for c in counts]
@@ -635,11 +678,21 @@ class PathTracer:
         if max_distance is None:
             max_distance = 1.5 * float(np.linalg.norm([grid.spacing[a] for a in range(3)]))
         dev = torch.device(f"cuda:{self.device}")
-        pos = torch.from_numpy(plugin.probe_grid_positions(grid)).to(dev)
+        h_pos = plugin.probe_grid_positions(grid)
+        pos = torch.from_numpy(h_pos).to(dev)
         d_seeds = None if seeds is None else torch.from_numpy(np.asarray(seeds).astype(np.int64)).to(dev)
+        placement = None
+        if relocate is not None and relocate is not False:
+            args = dict(first_sample=first_sample)
+            args.update({} if relocate is True else dict(relocate))
+            offsets, states = self.place_probes(pos, [grid.spacing[a] for a in range(3)], seeds=d_seeds, **args)[:2]
+            placement = torch.zeros((pos.shape[0], 4), dtype=torch.float32, device=dev)
+            placement[:, 0:3] = offsets
+            placement.view(torch.int32)[:, 3] = states
+            pos = torch.from_numpy((h_pos + offsets.cpu().numpy()).astype(np.float32)).to(dev)
         sh, m2 = self.probe_sh(pos, spp=spp, first_sample=first_sample, seeds=d_seeds, delta_lights=delta_lights, params=params)
         depth = self.probe_depth(pos, spp=depth_spp, max_distance=max_distance, first_sample=first_sample, seeds=d_seeds)
-        return ProbeVolume(self, grid, sh, m2, depth, max_distance)
+        return ProbeVolume(self, grid, sh, m2, depth, max_distance, placement)
 
     # ---- lightmap charts (include/ptmi_plugin.h Part 14)
     def _chart_desc(self, width, height, mesh, instance, seed) -> abi.PTChartDesc:
@@ -1285,11 +1338,15 @@ class PathTracer:
 
 class ProbeVolume:
     """A baked probe grid on the device (PathTracer.bake_probe_volume; include/ptmi_plugin.h Part 16): the grid, the SH
-    coefficients (n, 9, 3), their luminance moments (n,) and the depth records (n, 64, 2), x fastest."""
+    coefficients (n, 9, 3), their luminance moments (n,) and the depth records (n, 64, 2), x fastest.  placement: None, or the
+    (n, 4) float32 PTProbePlacement rows of bake_probe_volume(relocate=...) (Part 18) -- offset xyz and state bits; sh and depth were
+    then baked at position + offset, and irradiance() leaves out the probes marked PT_PROBE_INSIDE."""
 
-    def __init__(self, tracer: "PathTracer", grid: abi.PTProbeGrid, sh, m2, depth, max_distance: float):
+    def __init__(self, tracer: "PathTracer", grid: abi.PTProbeGrid, sh, m2, depth, max_distance: float, placement=None):
         import torch
         self.tracer, self.grid, self.sh, self.m2, self.depth, self.max_distance = tracer, grid, sh, m2, depth, float(max_distance)
+        self.placement = None if placement is None else placement.contiguous()
+        assert placement is None or placement.shape == (sh.shape[0], 4), placement.shape
         n = sh.shape[0]
         assert n == grid.counts[0] * grid.counts[1] * grid.counts[2] and depth.shape == (n, 64, 2), (sh.shape, depth.shape)
         self._rows = torch.zeros((n, 28), dtype=torch.float32, device=sh.device)          # PTProbeCoeffs rows
@@ -1310,10 +1367,11 @@ class ProbeVolume:
         return 0.2 * min(s) if s else 0.0
 
     def irradiance(self, positions=None, normals=None, receivers=None, wrap: bool = True, visibility: bool = True, normal_bias: float = None):
-        """PTProbeGridIrradiance: the irradiance the volume gives at points with unit normals, blended from the up to eight probes
-        around each point.  wrap: weigh a probe by the side of the surface it is on; visibility: weigh it by the Chebyshev bound of
-        its depth record, which keeps a lit room's probes out of the dark room next door.  normal_bias: how far the point is moved
-        along its normal before the distance to a probe is taken (None: default_normal_bias()).
+        """PTProbeGridIrradiancePlaced (PTProbeGridIrradiance for a volume without a placement): the irradiance the volume gives at
+        points with unit normals, blended from the up to eight probes around each point.  wrap: weigh a probe by the side of the
+        surface it is on; visibility: weigh it by the Chebyshev bound of its depth record, which keeps a lit room's probes out of
+        the dark room next door.  normal_bias: how far the point is moved along its normal before the distance to a probe is taken
+        (None: default_normal_bias()).
 
         positions, normals: (q, 3) float32, or receivers: (q, 8) float32 PTReceiver rows as chart_receivers returns them.  numpy in,
         numpy out; device tensors in, a device tensor out.  Returns (q, 4) float32: irradiance rgb and the support sumW."""
@@ -1338,7 +1396,8 @@ class ProbeVolume:
         out = torch.empty((q, 4), dtype=torch.float32, device=dev)
         if q:
             with pt._ordered(dev):
-                plugin.check(pt.lib.PTProbeGridIrradiance(pt.ctx, C.byref(g), self._rows.data_ptr(), self._depth.data_ptr(), recv.data_ptr(), q, out.data_ptr()))
+                plugin.check(pt.lib.PTProbeGridIrradiancePlaced(pt.ctx, C.byref(g), self._rows.data_ptr(), self._depth.data_ptr(),
+                                                                None if self.placement is None else self.placement.data_ptr(), recv.data_ptr(), q, out.data_ptr()))
         return out.cpu().numpy() if as_numpy else out
 
 

@@ -139,6 +139,12 @@ sig = {
     # Part 17 (the lightmap denoiser)
     "PTDenoiseLightmap": (i32, [vp, C.POINTER(abi.PTLightmapDenoiseParams), vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp]),
     "PTDenoiseLightmapHost": (i32, [C.POINTER(abi.PTLightmapDenoiseParams), vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp]),
+    # Part 18 (probe placement)
+    "PTProbePlace": (i32, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(abi.PTProbePlaceParams), C.c_uint32, vp, vp]),
+    "PTProbePlaceHost": (i32, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(abi.PTProbePlaceParams), C.c_uint32, vp, vp]),
+    "PTProbeGridIrradiancePlaced": (i32, [vp, C.POINTER(abi.PTProbeGrid), vp, vp, vp, vp, C.c_uint64, vp]),
+    "PTProbePlaceStepHost": (i32, [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(abi.PTProbePlaceParams), vp, vp, i32, vp, vp]),
+    "PTProbeGridIrradiancePlacedHost": (i32, [C.POINTER(abi.PTProbeGrid), vp, vp, vp, vp, C.c_uint64, vp]),
     "PTGetLastError": (C.c_char_p, []), "PTGetVersion": (i32, []),
 }
 EXPORTED_SYMBOLS = list(sig)
@@ -633,9 +639,46 @@ def probe_depth_project(positions, distances, max_distance: float, first_sample:
     return out
 
 
-def probe_grid_irradiance(grid: abi.PTProbeGrid, sh, depth, positions=None, normals=None, receivers=None) -> np.ndarray:
+def probe_placement_rows(offsets=None, states=None, n: int = None) -> np.ndarray:
+    """(n, 4) float32 PTProbePlacement rows -- offset xyz, state bits -- from (n, 3) offsets and (n,) states (None: zeros)"""
+    if offsets is None:
+        rows = np.zeros((int(n), 4), np.float32)
+    else:
+        off = np.ascontiguousarray(offsets, dtype=np.float32).reshape(-1, 3)
+        rows = np.zeros((off.shape[0], 4), np.float32)
+        rows[:, 0:3] = off
+    if states is not None:
+        rows[:, 3] = np.ascontiguousarray(np.asarray(states).astype(np.uint32)).reshape(rows.shape[0]).view(np.float32)
+    return rows
+
+
+def probe_place_step(positions, hits, surfaces, params: abi.PTProbePlaceParams, move: bool = True, offsets=None, first_sample: int = 0, seeds=None):
+    """One step of probe placement on the host (PTProbePlaceStepHost, include/ptmi_plugin.h Part 18).  hits (n * spp, 4) and
+    surfaces (n * spp, 12) float32 are the PTRayHit and PTRaySurface rows, entry-major, that trace_rays(surface=True) returns for the
+    rays {P + o, w_j, params.maxDistance}; offsets (n, 3): the stored offsets (None: zeros), read as the rule reads them.
+    Returns (offsets (n, 3) float32, states (n,) uint32, stats (n,) records of abi.PLACE_STATS_DTYPE): with move the offsets after
+    the step; states and stats describe the offsets the records were traced from."""
+    rows = probe_rows(positions, seeds)
+    n = rows.shape[0]
+    h = np.ascontiguousarray(hits, dtype=np.float32).reshape(-1, 4)
+    s = np.ascontiguousarray(surfaces, dtype=np.float32).reshape(-1, 12)
+    assert h.shape[0] == s.shape[0] and (n == 0 or h.shape[0] % n == 0), (h.shape, s.shape, n)
+    spp = h.shape[0] // n if n else 1
+    pl = probe_placement_rows(offsets, None, n)
+    assert pl.shape[0] == n, (pl.shape, n)
+    stats = np.zeros(n, abi.PLACE_STATS_DTYPE)
+    lib = load_library()
+    if not lib.PTProbePlaceStepHost(rows.ctypes.data, n, first_sample & 0xFFFFFFFF, spp, C.byref(params), h.ctypes.data, s.ctypes.data, 1 if move else 0,
+                                    pl.ctypes.data, stats.ctypes.data):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTProbePlaceStepHost failed: " + lib.PTGetBVHBuildError().decode())
+    return pl[:, 0:3].copy(), pl[:, 3].copy().view(np.uint32), stats
+
+
+def probe_grid_irradiance(grid: abi.PTProbeGrid, sh, depth, positions=None, normals=None, receivers=None, placement=None) -> np.ndarray:
     """A probe volume's lookup on the host (PTProbeGridIrradianceHost): sh (n, 9, 3), depth (n, 64, 2) or None (without
     PT_GRID_VISIBILITY), n the grid's probes; positions and unit normals (q, 3), or ready-made (q, 8) PTReceiver rows.
+    placement: None, or (n, 4) float32 PTProbePlacement rows (probe_placement_rows) for the placed lookup of Part 18
+    (PTProbeGridIrradiancePlacedHost): a probe marked PT_PROBE_INSIDE is left out, a live one weighs in from its placed position.
     Returns (q, 4) float32: irradiance rgb and the support sumW."""
     rows = probe_coeff_rows(sh)
     recv = receiver_rows(positions, normals) if receivers is None else np.ascontiguousarray(receivers, dtype=np.float32).reshape(-1, 8)
@@ -647,6 +690,13 @@ def probe_grid_irradiance(grid: abi.PTProbeGrid, sh, depth, positions=None, norm
         assert rows.shape[0] == n and (d is None or d.shape[0] == n), (rows.shape, n)
     out = np.empty((recv.shape[0], 4), np.float32)
     lib = load_library()
+    if placement is not None:
+        pl = np.ascontiguousarray(placement, dtype=np.float32).reshape(-1, 4)
+        assert pl.shape[0] == rows.shape[0], (pl.shape, rows.shape)
+        if not lib.PTProbeGridIrradiancePlacedHost(C.byref(grid), rows.ctypes.data, None if d is None else d.ctypes.data, pl.ctypes.data, recv.ctypes.data,
+                                                   recv.shape[0], out.ctypes.data):
+            raise PluginError(abi.PT_ERR_INVALID_ARG, "PTProbeGridIrradiancePlacedHost failed: " + lib.PTGetBVHBuildError().decode())
+        return out
     if not lib.PTProbeGridIrradianceHost(C.byref(grid), rows.ctypes.data, None if d is None else d.ctypes.data, recv.ctypes.data, recv.shape[0], out.ctypes.data):
         raise PluginError(abi.PT_ERR_INVALID_ARG, "PTProbeGridIrradianceHost failed: " + lib.PTGetBVHBuildError().decode())
     return out
