@@ -1565,6 +1565,121 @@ PT_API int PTProbeGridIrradiancePlacedHost(const PTProbeGrid* grid, const PTProb
                                            const PTProbePlacement* placement /* NULL = PTProbeGridIrradianceHost */, const PTReceiver* queries,
                                            uint64_t count, PTIrradiance* out);
 
+/* =====================================================================================================================
+ * Part 19: adaptive gathers.  Part 13 gives every receiver the same `samples`, whether it sits in plain view of a point light
+ * or in a corner only third-bounce light reaches.  PTGatherIrradianceAdaptive is the loop the render has for frames (Parts 6
+ * and 7), for lists: gather a few samples of every entry, keep the entries whose mean luminance is still noisy, gather more of
+ * those only, until none is left.  PTIrradiance.m2 carries what the decision needs, Part 13's seeding makes [a, a + n) the same
+ * samples however it is cut into calls, and every round IS a PTGatherIrradiance over a compacted list -- no gather kernel knows
+ * of this part.  An addition detected by symbol; PTGetVersion is unchanged.
+ *
+ * The rule (bit-exact; adaptive_gather_rule.h is its one definition: the kernels, the host twins and tests/adaptive_gather_ref.py
+ * evaluate it; only + - * /, max and comparisons; every fp32 operator is one IEEE binary32 operation, left to right, no fma).
+ *  1. Rounds.  Round 0 gathers the samples [firstSample, firstSample + minSamples) of every entry; round r >= 1 gathers
+ *     [firstSample + minSamples + (r - 1) * addSamples, ... + addSamples) of the entries still active (uint32 arithmetic, as
+ *     Part 13's seeding).  Each round is exactly PTGatherIrradiance over the active entries' 32 receiver bytes, copied unchanged
+ *     (the seed travels with them).  An entry that is dropped stays dropped, so every active entry of a round holds the same
+ *     count n.
+ *  2. Select, for an active entry with accumulated (rgb, m2) and count n:  S = (float)n;  l = luminance3(rgb);
+ *     v = max((m2 - S*l*l) / (S - 1), 0) / S  (Part 17's step 1, word for word);  d = max(l, darkFloor);
+ *     noisy = v > (threshold * threshold) * (d * d).  In this order: an entry whose rgb or m2 is not finite stops as NON-FINITE;
+ *     one that is not noisy (a NaN v compares false) stops BY THRESHOLD; one with n + addSamples > maxSamples stops BY MAXSAMPLES;
+ *     every other entry stays active.  The next active list is the surviving entry indices in the order of the list they were
+ *     selected from (ascending for the loop): a stable compaction, so the result does not depend on launch geometry.  The
+ *     survivors' receivers go beside them in the same order.
+ *  3. Fold of a round's result (rgb_new, m2_new) of m samples into (rgb, m2) of n samples:
+ *     rgb' = (rgb * (float)n + rgb_new * (float)m) / (float)(n + m) per channel;  m2' = m2 + m2_new;  n' = n + m  (the
+ *     running-mean form of Part 7).  n == 0 writes: the round's result is the entry, bit for bit.
+ *  4. Result.  out[i] is the accumulated PTIrradiance, counts[i] = n_i.  The loop ends when the active list is empty.
+ *  5. Equalise (optional): what lets the denoiser and any other consumer that assumes ONE `samples` take the list.  For a chosen
+ *     samplesEq (2 ... 2^24), with l and v as in step 2 from (rgb, m2, n_i):  out.rgb = rgb;
+ *     out.m2 = S*l*l + (v*S) * (S - 1)  with S = (float)samplesEq, so that Part 17's step 1 at samples = samplesEq recovers the
+ *     entry's own variance of the mean.  An entry with a non-finite rgb or m2, or with n_i outside 2 ... 2^24, passes through byte
+ *     for byte.  THIS IS A REWRITE OF m2, NOT NEW STATISTICS: an equalised list is not folded with further samples.
+ * Like every variance-led stop, the decision uses the very samples it stops on, so among equally noisy entries those whose
+ * first samples happen to agree stop first: the estimate is slightly biased towards stopping early.  minSamples is the guard.
+ * Because a gather of an entry does not depend on its neighbours in the list (Part 13), (out[i], counts[i]) equals what steps 2
+ * and 3 make of PTGatherIrradiance results for the same receiver over the same sample ranges, bit for bit.
+ *
+ * PTGatherIrradianceAdaptive: the whole loop.  Each round enqueues the gather as Part 13 does (the same chunks, state sets and
+ * PTStats accounting), folds, selects, and reads the survivor and stop counts back (32 bytes): one synchronisation per round; it
+ * returns synchronised.  dCounts and outStats may be NULL.  Working memory in the context, grown on demand, kept across
+ * PTSetScene, freed by PTDestroy: 56 bytes per entry (two index lists of 4, one compacted receiver list of 32, one round-result
+ * list of 16) and 16 bytes per 256 entries.  PTGatherIrradianceAdaptiveHost: host arrays, staged like PTGatherIrradianceHost.
+ * The steps, for callers that drive rounds themselves, on device arrays, stream-ordered on the context's stream (no scene needed):
+ *  - PTSelectReceivers: step 2 over the list dActive[0 .. activeCount) (NULL: every entry 0 .. activeCount - 1) with the count n;
+ *    dAcc and dRecv hold entryCount entries and are read through the index; an index >= entryCount is left out (and counted
+ *    nowhere).  Writes the survivors to dOutActive / dOutRecv (activeCount entries each; nothing past the survivor count is
+ *    written; neither may alias an input), their number to *survivors and, if given, stopped[3] = by threshold, by maxSamples,
+ *    non-finite.  Synchronises (the counts are read back).
+ *  - PTFoldIrradiance: step 3; dNew[k] (m samples) folds into dAcc[dActive[k]] (n samples; n == 0 writes), and dCounts (may be
+ *    NULL) gets n + m there.  Indices are unique; n + m <= 2^24.
+ *  - PTEqualiseIrradiance: step 5; dOut may equal dIrr.
+ * Errors: PT_ERR_INVALID_ARG for a NULL or misaligned pointer (indices and counts 4 bytes, the rest 16), a structSize below this
+ * header's, a nonzero reserved word, minSamples outside 2 ... 65536, addSamples outside 1 ... 65536, maxSamples outside
+ * minSamples ... 2^24, a threshold that is not finite and > 0, a darkFloor that is not finite and >= 0, n outside 2 ... 2^24
+ * (select), m outside 1 ... 65536 or n + m > 2^24 (fold), samplesEq outside 2 ... 2^24, activeCount > entryCount, more than 2^31
+ * entries, (PTGatherIrradianceAdaptiveHost) a nonzero PTReceiver.reserved; the offending number is in PTGetLastError.
+ * PT_ERR_UNSUPPORTED for schedules 0 and 4 and MaxRayBounces > 8191, PT_ERR_NO_SCENE before PTSetScene (the loop only).
+ * count == 0 returns PT_OK and launches nothing.  Arguments are checked before the context is used.  Nothing past `count` is
+ * written.  No CPU fallback.  The host twins take no context and no GPU; they return 1, or 0 with PTGetBVHBuildError() set, and
+ * also refuse an index >= entryCount.
+ * ===================================================================================================================== */
+#define PT_ADAPTIVE_GATHER_MAX_TOTAL   16777216u    /* 2^24: every count is exact in fp32 */
+#define PT_ADAPTIVE_GATHER_MAX_ENTRIES 2147483648u  /* 2^31 */
+
+typedef struct PTAdaptiveGather { /* a host struct, passed by pointer */
+    uint32_t structSize;          /* sizeof(PTAdaptiveGather) of the caller's header; members are only appended */
+    uint32_t firstSample;         /* first sample index of the call */
+    uint32_t minSamples;          /* 2 ... PT_GATHER_MAX_SAMPLES: round 0 */
+    uint32_t addSamples;          /* 1 ... PT_GATHER_MAX_SAMPLES: every later round */
+    uint32_t maxSamples;          /* minSamples ... 2^24: no entry gets more */
+    float    threshold;           /* finite, > 0: the relative standard error of the mean luminance to reach */
+    float    darkFloor;           /* finite, >= 0: below this luminance the error is measured against darkFloor */
+    uint32_t reserved[5];         /* must be 0 */
+} PTAdaptiveGather;
+
+typedef struct PTAdaptiveGatherStats {
+    uint32_t rounds;              /* gathers run */
+    uint32_t maxCount;            /* the largest counts[i] */
+    uint64_t samples;             /* samples gathered over all entries and rounds (the paths PTStats counted) */
+    uint64_t stoppedThreshold;    /* entries stopped by threshold, */
+    uint64_t stoppedMaxSamples;   /*   by maxSamples, */
+    uint64_t stoppedNonFinite;    /*   as non-finite: the three add up to count */
+} PTAdaptiveGatherStats;
+
+#ifdef __cplusplus
+static_assert(sizeof(PTAdaptiveGather) == 48, "PTAdaptiveGather is 48 bytes");
+static_assert(sizeof(PTAdaptiveGatherStats) == 40, "PTAdaptiveGatherStats is 40 bytes");
+#else
+_Static_assert(sizeof(PTAdaptiveGather) == 48, "PTAdaptiveGather is 48 bytes");
+_Static_assert(sizeof(PTAdaptiveGatherStats) == 40, "PTAdaptiveGatherStats is 40 bytes");
+#endif
+
+/* Device pointers; returns synchronised. */
+PT_API int PTGatherIrradianceAdaptive(PTContext* ctx, const PTFrameParams* params, const PTAdaptiveGather* adaptive, const PTReceiver* dRecv,
+                                      uint64_t count, PTIrradiance* dOut, uint32_t* dCounts /* may be NULL */,
+                                      PTAdaptiveGatherStats* outStats /* host, may be NULL */);
+/* Host arrays: staged through device buffers the context keeps and grows; synchronous. */
+PT_API int PTGatherIrradianceAdaptiveHost(PTContext* ctx, const PTFrameParams* params, const PTAdaptiveGather* adaptive, const PTReceiver* recv,
+                                          uint64_t count, PTIrradiance* out, uint32_t* counts /* may be NULL */,
+                                          PTAdaptiveGatherStats* outStats /* may be NULL */);
+/* the steps: device arrays, stream-ordered on the context's stream */
+PT_API int PTSelectReceivers(PTContext* ctx, const PTAdaptiveGather* adaptive, uint32_t n, const uint32_t* dActive /* NULL = every entry */,
+                             uint64_t activeCount, const PTIrradiance* dAcc, const PTReceiver* dRecv, uint64_t entryCount, uint32_t* dOutActive,
+                             PTReceiver* dOutRecv, uint64_t* survivors /* host */, uint64_t* stopped /* host, 3 words, may be NULL */);
+PT_API int PTFoldIrradiance(PTContext* ctx, const uint32_t* dActive /* NULL = every entry */, uint64_t activeCount, const PTIrradiance* dNew,
+                            uint32_t m, uint32_t n, uint64_t entryCount, PTIrradiance* dAcc, uint32_t* dCounts /* may be NULL */);
+PT_API int PTEqualiseIrradiance(PTContext* ctx, const PTIrradiance* dIrr, const uint32_t* dCounts, uint64_t count, uint32_t samplesEq,
+                                PTIrradiance* dOut);
+/* host twins, no GPU */
+PT_API int PTSelectReceiversHost(const PTAdaptiveGather* adaptive, uint32_t n, const uint32_t* active /* NULL = every entry */, uint64_t activeCount,
+                                 const PTIrradiance* acc, const PTReceiver* recv, uint64_t entryCount, uint32_t* outActive, PTReceiver* outRecv,
+                                 uint64_t* survivors, uint64_t* stopped /* 3 words, may be NULL */);
+PT_API int PTFoldIrradianceHost(const uint32_t* active /* NULL = every entry */, uint64_t activeCount, const PTIrradiance* fresh, uint32_t m,
+                                uint32_t n, uint64_t entryCount, PTIrradiance* acc, uint32_t* counts /* may be NULL */);
+PT_API int PTEqualiseIrradianceHost(const PTIrradiance* irr, const uint32_t* counts, uint64_t count, uint32_t samplesEq, PTIrradiance* out);
+
 /* Text of the last error on the calling thread ("" if none). */
 PT_API const char* PTGetLastError(void);
 /* Library/ABI version: (major << 16) | minor. */

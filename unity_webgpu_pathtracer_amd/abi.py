@@ -414,6 +414,39 @@ def lightmap_denoise_params(samples: int, iterations: int = 5, sigma_luminance: 
     return p
 
 
+# ---- adaptive gathers (include/ptmi_plugin.h Part 19)
+PT_ADAPTIVE_GATHER_MAX_TOTAL = 1 << 24
+PT_ADAPTIVE_GATHER_MAX_ENTRIES = 1 << 31
+
+
+class PTAdaptiveGather(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("firstSample", C.c_uint32), ("minSamples", C.c_uint32), ("addSamples", C.c_uint32),
+                ("maxSamples", C.c_uint32), ("threshold", C.c_float), ("darkFloor", C.c_float), ("reserved", C.c_uint32 * 5)]
+
+
+class PTAdaptiveGatherStats(C.Structure):
+    _fields_ = [("rounds", C.c_uint32), ("maxCount", C.c_uint32), ("samples", C.c_uint64), ("stoppedThreshold", C.c_uint64),
+                ("stoppedMaxSamples", C.c_uint64), ("stoppedNonFinite", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+assert C.sizeof(PTAdaptiveGather) == 48 and C.sizeof(PTAdaptiveGatherStats) == 40
+
+
+def adaptive_gather(threshold: float, min_samples: int = 16, add_samples: int = 16, max_samples: int = 1024, dark_floor: float = 0.0,
+                    first_sample: int = 0) -> PTAdaptiveGather:
+    """A PTAdaptiveGather with structSize set: the relative standard error of the mean luminance to reach, the samples of round 0,
+    of every later round and at most, the luminance below which the error is measured against dark_floor, the first sample index."""
+    a = PTAdaptiveGather()
+    a.structSize = C.sizeof(PTAdaptiveGather)
+    a.firstSample = int(first_sample) & 0xFFFFFFFF
+    a.minSamples, a.addSamples, a.maxSamples = int(min_samples), int(add_samples), int(max_samples)
+    a.threshold, a.darkFloor = float(threshold), float(dark_floor)
+    return a
+
+
 # ---------------------------------------------------------------------------------------
 # Part 10: geometry rebuilds and tree quality (PTRebuildGeometry / PTMeasureGeometry / PTMeasureBVHArrays)
 # ---------------------------------------------------------------------------------------

@@ -20,6 +20,7 @@
 #include "volume_rule.h"
 #include "placement_rule.h"
 #include "lmfilter_rule.h"
+#include "adaptive_gather_rule.h"
 #include "ptmi_plugin.h"
 
 namespace {
@@ -247,6 +248,27 @@ PT_API int PTDenoiseLightmapHost(const PTLightmapDenoiseParams* params, const ui
                                  uint32_t width, uint32_t height, PTIrradiance* out)
 {
     if (!ptlmf::denoise_host(params, texels, recv, irr, count, width, height, out, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+// The steps of an adaptive gather on the host (adaptive_gather_host.cpp; Part 19 has the rule).  No GPU involved.
+PT_API int PTSelectReceiversHost(const PTAdaptiveGather* adaptive, uint32_t n, const uint32_t* active, uint64_t activeCount, const PTIrradiance* acc,
+                                 const PTReceiver* recv, uint64_t entryCount, uint32_t* outActive, PTReceiver* outRecv, uint64_t* survivors, uint64_t* stopped)
+{
+    if (!ptag::select_host(adaptive, n, active, activeCount, acc, recv, entryCount, outActive, outRecv, survivors, stopped, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+PT_API int PTFoldIrradianceHost(const uint32_t* active, uint64_t activeCount, const PTIrradiance* fresh, uint32_t m, uint32_t n, uint64_t entryCount,
+                                PTIrradiance* acc, uint32_t* counts)
+{
+    if (!ptag::fold_host(active, activeCount, fresh, m, n, entryCount, acc, counts, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+PT_API int PTEqualiseIrradianceHost(const PTIrradiance* irr, const uint32_t* counts, uint64_t count, uint32_t samplesEq, PTIrradiance* out)
+{
+    if (!ptag::equalise_host(irr, counts, count, samplesEq, out, g_buildError)) return 0;
     g_buildError.clear();
     return 1;
 }

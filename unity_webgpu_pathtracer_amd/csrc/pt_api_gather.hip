@@ -2,9 +2,8 @@
 // DESIGN.md 5.18).
 #include "pt_context.h"
 
-namespace {
-
-// One launch sequence per chunk of floor(PT_RADIANCE_CHUNK / samples) whole entries (enqueue_list_chunks)
+// One launch sequence per chunk of floor(PT_RADIANCE_CHUNK / samples) whole entries (enqueue_list_chunks); also a round of
+// PTGatherIrradianceAdaptive (pt_api_adaptive_gather.hip)
 int gather_irradiance(PTContext* c, const PTFrameParams& p1, const PTReceiver* dRecv, uint64_t count, uint32_t firstSample, uint32_t samples,
                       PTIrradiance* dOut, const char* who)
 {
@@ -19,8 +18,6 @@ int gather_irradiance(PTContext* c, const PTFrameParams& p1, const PTReceiver* d
         L.output = dOut + first;
     });
 }
-
-} // namespace
 
 extern "C" {
 

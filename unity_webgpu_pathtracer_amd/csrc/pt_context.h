@@ -9,6 +9,7 @@
 #include "pt_morph.h"
 #include "pt_lightmap.h"
 #include "pt_lmfilter.h"
+#include "pt_adaptive_gather.h"
 #include "bvh_refit.h"
 #include "bvh_builder_gpu.h"
 
@@ -265,6 +266,17 @@ struct PTContext {
         DeviceBuffer state[2];                  // 16 B per texel each: (e, v), the levels go from one to the other
         DeviceBuffer guideP, guideN;            // 16 B per texel each: (P, h2) and (N, flags)
     } lmfilter;
+    // adaptive gathers (PTGatherIrradianceAdaptive and its steps): 56 B per entry and 16 B per 256 entries, grown on demand, kept
+    // across PTSetScene
+    struct AdaptiveGather {
+        DeviceBuffer active[2];                 // 4 B per entry each: the active list of a round and of the next
+        DeviceBuffer recv;                      // 32 B per entry: the active entries' receivers, compacted
+        DeviceBuffer result;                    // 16 B per entry: what a round's gather wrote
+        DeviceBuffer blockCounts;               // 16 B per 256-entry block, then the four 8-byte totals
+        PinnedBuffer totals;                    // the totals, read back
+        HostStaging host;                       // PTGatherIrradianceAdaptiveHost's staging
+        DeviceBuffer hostCounts;                // ... and its counts: regrows without a drain, as HostStaging does
+    } adaptiveGather;
     // scene updates (PTUpdateInstances / Lights / Materials): two generations of what an update rewrites, allocated on the first
     // update of each kind and discarded by PTSetScene.  cur = -1 while PTSetScene's own buffers are current.
     struct UpdGroup {
@@ -445,6 +457,9 @@ int end_update(PTContext* c, PTContext::UpdGroup& g, int target);
 // offsets name (made, and the BLAS walked, on its first use); triCount == 0: the BLAS's own count
 int ensure_host_copy(PTContext* c);
 int find_plan(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t attrOffset, uint32_t triCount, PTContext::GeomPlan*& out);
+// pt_api_gather.hip: PTGatherIrradiance's body, one launch sequence per chunk of floor(PT_RADIANCE_CHUNK / samples) whole entries
+int gather_irradiance(PTContext* c, const PTFrameParams& p1, const PTReceiver* dRecv, uint64_t count, uint32_t firstSample, uint32_t samples,
+                      PTIrradiance* dOut, const char* who);
 int query_prepare(PTContext* c);                                                // pt_api_query.hip: the grid caps and the stack slab of the query kernels, on first use
 int set_scene(PTContext* c, const PTSceneDesc* hostScene, bool validate);      // pt_api_context.hip; PTGroupSetScene validates once
 int drain_events(PTContext* c);                                                 // pt_api_context.hip

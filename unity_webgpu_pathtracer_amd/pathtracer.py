@@ -520,6 +520,69 @@ class PathTracer:
             plugin.check(self.lib.PTGatherIrradiance(self.ctx, C.byref(p), recv.data_ptr(), n, first_sample & 0xFFFFFFFF, spp, out.data_ptr()))
         return out
 
+    # ---- adaptive gathers (include/ptmi_plugin.h Part 19)
+    def irradiance_adaptive(self, positions=None, normals=None, threshold: float = None, min_samples: int = 16, add_samples: int = 16,
+                            max_samples: int = 1024, dark_floor: float = None, first_sample: int = 0, seeds=None, params: abi.PTFrameParams = None,
+                            receivers=None):
+        """irradiance() with more samples only where the result is still noisy (PTGatherIrradianceAdaptive; Part 19 has the rule):
+        `min_samples` of every receiver, then rounds of `add_samples` for the receivers whose relative standard error of the mean
+        luminance is above `threshold`, until none is left or `max_samples` would be passed.  A receiver that stops stays stopped.
+        Every round is irradiance() over the receivers still active, so the result of a receiver is the fold (plugin.fold_irradiance)
+        of irradiance() results over the same sample ranges, bit for bit.
+
+        Inputs as irradiance(): numpy -> PTGatherIrradianceAdaptiveHost, returns numpy; device tensors -> zero-copy, ordered
+        against torch's current stream both ways (the call itself synchronises once per round).
+        dark_floor: the luminance below which the error is measured against dark_floor instead of the receiver's own luminance
+        (a black receiver would never converge relatively).  None: 1 % of the mean luminance of the finite entries of a
+        `min_samples` gather -- computed here by running round 0 through irradiance() first and passing the number down, so the
+        C call keeps one contract; that costs one extra round 0.
+        Returns (irradiance (n, 4) float32: rgb and m2 over the receiver's own samples, counts (n,) int32 / uint32: samples per
+        receiver, stats: a dict of PTAdaptiveGatherStats -- rounds, samples, stoppedThreshold, stoppedMaxSamples, stoppedNonFinite,
+        maxCount -- and darkFloor)."""
+        assert threshold is not None, "threshold: the relative standard error to reach"
+        p = self._radiance_params(params)
+        if receivers is not None:
+            assert positions is None and normals is None and seeds is None, "receivers come instead of positions, normals and seeds"
+            assert receivers.dtype == np.float32 or str(receivers.dtype) == "torch.float32", receivers.dtype
+            assert receivers.ndim == 2 and receivers.shape[1] == 8, receivers.shape
+            recv = np.ascontiguousarray(receivers) if isinstance(receivers, np.ndarray) else receivers.contiguous()
+        else:
+            recv = self._receivers(positions, normals, seeds)
+        n = recv.shape[0]
+        if dark_floor is None:
+            first = self.irradiance(receivers=recv, spp=min_samples, first_sample=first_sample, params=p) if n else np.zeros((0, 4), np.float32)
+            first = first if isinstance(first, np.ndarray) else first.cpu().numpy()
+            rgb = first[np.isfinite(first).all(axis=1), :3].astype(np.float64)
+            dark_floor = 0.01 * float((rgb @ np.array([0.299, 0.587, 0.114])).mean()) if len(rgb) else 0.0
+            dark_floor = dark_floor if np.isfinite(dark_floor) and dark_floor > 0.0 else 0.0
+        a = abi.adaptive_gather(threshold, min_samples, add_samples, max_samples, dark_floor, first_sample)
+        st = abi.PTAdaptiveGatherStats()
+        if isinstance(recv, np.ndarray):
+            out, counts = np.empty((n, 4), np.float32), np.empty(n, np.uint32)
+            plugin.check(self.lib.PTGatherIrradianceAdaptiveHost(self.ctx, C.byref(p), C.byref(a), recv.ctypes.data, n, out.ctypes.data, counts.ctypes.data,
+                                                                 C.byref(st)))
+        else:
+            import torch
+            out = torch.empty((n, 4), dtype=torch.float32, device=recv.device)
+            counts = torch.empty((n,), dtype=torch.int32, device=recv.device)
+            with self._ordered(recv.device):
+                plugin.check(self.lib.PTGatherIrradianceAdaptive(self.ctx, C.byref(p), C.byref(a), recv.data_ptr(), n, out.data_ptr(), counts.data_ptr(),
+                                                                 C.byref(st)))
+        return out, counts, dict(st.as_dict(), darkFloor=float(a.darkFloor))
+
+    def equalise_irradiance(self, irradiance, counts, samples_eq: int):
+        """PTEqualiseIrradiance: rewrites m2 of an irradiance_adaptive() list (device tensors: (n, 4) float32 and (n,) int32 counts) so
+        that denoise_lightmap(..., samples=samples_eq) recovers every entry's own variance of the mean.  Returns a new (n, 4) tensor."""
+        import torch
+        n = irradiance.shape[0]
+        assert irradiance.dtype == torch.float32 and irradiance.is_contiguous() and irradiance.shape == (n, 4), irradiance.shape
+        assert counts.element_size() == 4 and counts.is_contiguous() and counts.shape == (n,), counts.shape
+        out = torch.empty_like(irradiance)
+        with self._ordered(irradiance.device):
+            plugin.check(self.lib.PTEqualiseIrradiance(self.ctx, irradiance.data_ptr() if n else None, counts.data_ptr() if n else None, n, int(samples_eq),
+                                                       out.data_ptr() if n else None))
+        return out
+
     def gather_rays(self, positions, normals, spp: int = 64, first_sample: int = 0, seeds=None, params: abi.PTFrameParams = None):
         """PTGatherRays: the gather ray and RNG state each sample of irradiance() leaves the receiver with, as radiance() takes
         them: (n * spp, 8) float32 rows, entry-major (row i * spp + j = sample first_sample + j of entry i); a sample that ended at
@@ -778,21 +841,44 @@ class PathTracer:
         return out
 
     def bake_lightmap(self, width: int, height: int, spp: int = 64, mesh: int = None, instance: int = None, uvs=None, dilate: int = 2, seed: int = 0,
-                      first_sample: int = 0, params: abi.PTFrameParams = None, as_tensor: bool = False, denoise=None):
+                      first_sample: int = 0, params: abi.PTFrameParams = None, as_tensor: bool = False, denoise=None, adaptive=None,
+                      return_counts: bool = False):
         """A lightmap of one mesh: chart_receivers, PTGatherIrradiance over them, resolve_lightmap -- nothing but the final image
         leaves the device.  spp, first_sample and params are irradiance()'s (samples [first_sample, first_sample + spp) of every
-        texel; two bakes over disjoint ranges fold by 5.18's rule), the rest chart_receivers' and resolve_lightmap's.
+        texel; the gathered lists of two bakes over disjoint ranges fold by plugin.fold_irradiance), the rest chart_receivers' and
+        resolve_lightmap's.
         denoise: None, or what denoise_lightmap runs between the gather and the resolve: a number of levels, or a dict of its parameters.
+        adaptive: None, or what replaces the gather by irradiance_adaptive(): a number (the threshold) or a dict of its keywords
+        (threshold, min_samples, add_samples, max_samples, dark_floor); spp is then max_samples unless the dict says otherwise.  With
+        denoise also given, the list is equalised to max_samples (equalise_irradiance) and the denoiser runs with samples = max_samples.
+        return_counts: also a (height, width) int32 image of the samples every texel got (spp without adaptive), 0 outside the chart.
         Returns (height, width, 4) float32 -- numpy, or with as_tensor a device tensor; w tells baked (1), dilated (0.5), empty (0)."""
+        import torch
         texels, recv = self.chart_receivers(width, height, mesh=mesh, instance=instance, uvs=uvs, seed=seed)
-        if recv.shape[0]:
-            irr = self.irradiance(receivers=recv, spp=spp, first_sample=first_sample, params=params)
-            if denoise is not None:
-                irr = self.denoise_lightmap(texels, recv, irr, width, height, spp, params=plugin.lightmap_denoise_params(spp, 5, denoise))
-        else:                                                       # a chart that covers nothing: an empty image
+        counts = None
+        if adaptive is not None:
+            kw = dict(adaptive) if isinstance(adaptive, dict) else {"threshold": float(adaptive)}
+            kw.setdefault("max_samples", spp)
+            spp = int(kw["max_samples"])
+        if not recv.shape[0]:                                       # a chart that covers nothing: an empty image
             irr = recv.new_empty((0, 4))
+        elif adaptive is None:
+            irr = self.irradiance(receivers=recv, spp=spp, first_sample=first_sample, params=params)
+        else:
+            irr, counts, _ = self.irradiance_adaptive(receivers=recv, first_sample=first_sample, params=params, **kw)
+            if denoise is not None:
+                irr = self.equalise_irradiance(irr, counts, spp)
+        if denoise is not None and recv.shape[0]:
+            irr = self.denoise_lightmap(texels, recv, irr, width, height, spp, params=plugin.lightmap_denoise_params(spp, 5, denoise))
         image = self.resolve_lightmap(texels, irr, width, height, dilate=dilate)
-        return image if as_tensor else image.cpu().numpy()
+        image = image if as_tensor else image.cpu().numpy()
+        if not return_counts:
+            return image
+        count_image = torch.zeros((max(int(height), 1) * max(int(width), 1),), dtype=torch.int32, device=texels.device)
+        if recv.shape[0]:
+            count_image[texels.long()] = counts.to(torch.int32) if counts is not None else torch.full_like(texels, spp, dtype=torch.int32)
+        count_image = count_image.reshape(max(int(height), 1), max(int(width), 1))
+        return image, (count_image if as_tensor else count_image.cpu().numpy())
 
     def camera_ray(self, x: float, y: float, params: abi.PTFrameParams = None) -> np.ndarray:
         """The pinhole ray through the centre of pixel (x, y): util/camera.hlsl:13-42 without jitter and lens, in float32 with

@@ -145,6 +145,19 @@ sig = {
     "PTProbeGridIrradiancePlaced": (i32, [vp, C.POINTER(abi.PTProbeGrid), vp, vp, vp, vp, C.c_uint64, vp]),
     "PTProbePlaceStepHost": (i32, [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(abi.PTProbePlaceParams), vp, vp, i32, vp, vp]),
     "PTProbeGridIrradiancePlacedHost": (i32, [C.POINTER(abi.PTProbeGrid), vp, vp, vp, vp, C.c_uint64, vp]),
+    # Part 19 (adaptive gathers)
+    "PTGatherIrradianceAdaptive": (i32, [vp, C.POINTER(abi.PTFrameParams), C.POINTER(abi.PTAdaptiveGather), vp, C.c_uint64, vp, vp,
+                                         C.POINTER(abi.PTAdaptiveGatherStats)]),
+    "PTGatherIrradianceAdaptiveHost": (i32, [vp, C.POINTER(abi.PTFrameParams), C.POINTER(abi.PTAdaptiveGather), vp, C.c_uint64, vp, vp,
+                                             C.POINTER(abi.PTAdaptiveGatherStats)]),
+    "PTSelectReceivers": (i32, [vp, C.POINTER(abi.PTAdaptiveGather), C.c_uint32, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64),
+                                C.POINTER(C.c_uint64)]),
+    "PTFoldIrradiance": (i32, [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.c_uint64, vp, vp]),
+    "PTEqualiseIrradiance": (i32, [vp, vp, vp, C.c_uint64, C.c_uint32, vp]),
+    "PTSelectReceiversHost": (i32, [C.POINTER(abi.PTAdaptiveGather), C.c_uint32, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64),
+                                    C.POINTER(C.c_uint64)]),
+    "PTFoldIrradianceHost": (i32, [vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.c_uint64, vp, vp]),
+    "PTEqualiseIrradianceHost": (i32, [vp, vp, C.c_uint64, C.c_uint32, vp]),
     "PTGetLastError": (C.c_char_p, []), "PTGetVersion": (i32, []),
 }
 EXPORTED_SYMBOLS = list(sig)
@@ -526,6 +539,78 @@ def denoise_lightmap(texels, receivers, irradiance, width: int, height: int, sam
     lib = load_library()
     if not lib.PTDenoiseLightmapHost(C.byref(p), t.ctypes.data, r.ctypes.data, e.ctypes.data, len(t), int(width), int(height), out.ctypes.data):
         raise PluginError(abi.PT_ERR_INVALID_ARG, "PTDenoiseLightmapHost failed: " + lib.PTGetBVHBuildError().decode())
+    return out
+
+
+def adaptive_gather_params(adaptive, **defaults) -> abi.PTAdaptiveGather:
+    """The parameters of an adaptive gather: `adaptive` is a number (the threshold), a ready PTAdaptiveGather, or a dict of
+    abi.adaptive_gather's keywords; `defaults` fill what a number or a dict leaves out."""
+    if isinstance(adaptive, abi.PTAdaptiveGather):
+        return adaptive
+    kw = dict(defaults)
+    if isinstance(adaptive, dict):
+        kw.update(adaptive)
+    else:
+        kw["threshold"] = float(adaptive)
+    return abi.adaptive_gather(**kw)
+
+
+def _active_list(active, entries):
+    if active is None:
+        return None, entries
+    a = np.ascontiguousarray(active, dtype=np.uint32).reshape(-1)
+    return a, len(a)
+
+
+def select_receivers(accumulated, receivers, n: int, adaptive, active=None):
+    """Step 2 of an adaptive gather on the host (PTSelectReceiversHost, include/ptmi_plugin.h Part 19): the kernels' rule, byte for
+    byte.  accumulated (e, 4) float32 PTIrradiance rows of `n` samples each, receivers (e, 8) float32 PTReceiver rows, active (a,)
+    uint32 indices into them (None: every entry); adaptive: what adaptive_gather_params takes.  Returns (indices (s,) uint32 of the
+    entries that go on, in the list's order, their receivers (s, 8), stopped (3,) uint64: by threshold, by max_samples, non-finite).
+    Raises PluginError for what the twin refuses."""
+    acc = np.ascontiguousarray(accumulated, dtype=np.float32).reshape(-1, 4)
+    recv = np.ascontiguousarray(receivers, dtype=np.float32).reshape(-1, 8)
+    assert len(acc) == len(recv), (acc.shape, recv.shape)
+    act, count = _active_list(active, len(acc))
+    a = adaptive_gather_params(adaptive)
+    out_active, out_recv = np.empty(count, np.uint32), np.empty((count, 8), np.float32)
+    survivors, stopped = C.c_uint64(), (C.c_uint64 * 3)()
+    lib = load_library()
+    if not lib.PTSelectReceiversHost(C.byref(a), int(n), None if act is None else act.ctypes.data, count, acc.ctypes.data, recv.ctypes.data, len(acc),
+                                     out_active.ctypes.data, out_recv.ctypes.data, C.byref(survivors), stopped):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTSelectReceiversHost failed: " + lib.PTGetBVHBuildError().decode())
+    return out_active[:survivors.value].copy(), out_recv[:survivors.value].copy(), np.array(list(stopped), np.uint64)
+
+
+def fold_irradiance(accumulated, n: int, fresh, m: int, active=None, counts=None):
+    """Step 3 of an adaptive gather on the host (PTFoldIrradianceHost, Part 19) -- and the fold of two bakes of the same receivers
+    over disjoint sample ranges: accumulated (e, 4) float32 PTIrradiance rows of `n` samples, fresh (a, 4) rows of `m` samples for the
+    entries active names ((a,) uint32 unique indices; None: every entry).  n == 0 writes.  Returns the folded (e, 4) rows -- the
+    running mean of rgb, the sum of m2 --, and with counts ((e,) uint32) also the counts with n + m at the folded entries."""
+    acc = np.array(accumulated, dtype=np.float32, order="C").reshape(-1, 4)
+    new = np.ascontiguousarray(fresh, dtype=np.float32).reshape(-1, 4)
+    act, count = _active_list(active, len(acc))
+    assert len(new) == count, (new.shape, count)
+    cnt = None if counts is None else np.array(counts, dtype=np.uint32).reshape(-1)
+    assert cnt is None or len(cnt) == len(acc), (cnt.shape, acc.shape)
+    lib = load_library()
+    if not lib.PTFoldIrradianceHost(None if act is None else act.ctypes.data, count, new.ctypes.data, int(m), int(n), len(acc), acc.ctypes.data,
+                                    None if cnt is None else cnt.ctypes.data):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTFoldIrradianceHost failed: " + lib.PTGetBVHBuildError().decode())
+    return acc if cnt is None else (acc, cnt)
+
+
+def equalise_irradiance(irradiance, counts, samples_eq: int) -> np.ndarray:
+    """Step 5 of an adaptive gather on the host (PTEqualiseIrradianceHost, Part 19): rewrites m2 of every (n, 4) PTIrradiance row of
+    counts[i] samples so that a consumer that assumes `samples_eq` samples everywhere -- the lightmap denoiser -- recovers the entry's
+    own variance of the mean.  Not new statistics: an equalised list is not folded further."""
+    e = np.ascontiguousarray(irradiance, dtype=np.float32).reshape(-1, 4)
+    cnt = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+    assert len(e) == len(cnt), (e.shape, cnt.shape)
+    out = np.empty_like(e)
+    lib = load_library()
+    if not lib.PTEqualiseIrradianceHost(e.ctypes.data, cnt.ctypes.data, len(e), int(samples_eq), out.ctypes.data):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTEqualiseIrradianceHost failed: " + lib.PTGetBVHBuildError().decode())
     return out
 
 
