@@ -1680,6 +1680,123 @@ PT_API int PTFoldIrradianceHost(const uint32_t* active /* NULL = every entry */,
                                 uint32_t n, uint64_t entryCount, PTIrradiance* acc, uint32_t* counts /* may be NULL */);
 PT_API int PTEqualiseIrradianceHost(const PTIrradiance* irr, const uint32_t* counts, uint64_t count, uint32_t samplesEq, PTIrradiance* out);
 
+/* =====================================================================================================================
+ * Part 20: reflection probes.  Lightmaps (Part 14) and SH probes (Parts 15, 16) carry cosine-convolved light: they are diffuse.
+ * What a glossy or metallic object that moves through the baked scene reads is a reflection probe: a radiance map around a point,
+ * prefiltered once per roughness level, so that one fetch answers "what does a surface of roughness r reflect from direction R".
+ * The host hands over positions and a sample range; the directions, the paths, the fold, the GGX prefilter and the lookup run on
+ * the GPU.  An addition beside the reference's ABI, detected by symbol; PTGetVersion is unchanged.
+ *
+ * Layout.  A probe's map has `levels` levels; level k is an (R >> k) x (R >> k) octahedral image of 16-byte PTReflectionTexel,
+ * texel index v * Rk + u with Rk = R >> k; the levels are concatenated in ascending k, the probes' maps are concatenated.  R =
+ * `res` is a power of two in [8, 256]; 2 <= levels <= log2(R) - 1, so the coarsest level is at least 4 x 4 (a 2 x 2 level has all
+ * four centres on the equator and cannot tell up from down).  Level k stands for roughness rho_k = (float)k / (float)(levels - 1).
+ * A base map (what the capture writes, what the prefilter reads) is level 0 alone: R * R texels per probe.
+ *
+ * The rule (bit-exact; reflection_rule.h is its one definition: the kernels, the host twins and tests/reflection_ref.py evaluate
+ * it; every fp32 operator below is one IEEE binary32 operation in the order written, no fma).
+ *  1. Texel directions.  direction(R, u, v, su, sv): a = (((float)u + su) / (float)R) * 2.0f - 1.0f, b likewise from v and sv.
+ *     z = (1.0f - |a|) - |b|.  If z < 0: x = (1.0f - |b|) * sgn(a), y = (1.0f - |a|) * sgn(b), with sgn(0) = +1; otherwise x = a,
+ *     y = b.  len = sqrt((x * x + y * y) + z * z); d = (x / len, y / len, z / len).  A centre has su = sv = 0.5f.
+ *     oct_coords(D): s = (|D.x| + |D.y|) + |D.z|, a = D.x / s, b = D.y / s; if D.z < 0: a' = (1.0f - |b|) * sgn(a),
+ *     b' = (1.0f - |a|) * sgn(b).  D need not be of unit length.
+ *  2. Capture.  Slot (i * R * R + t) * samples + j is sample j of texel t = v * R + u of probe i.  Seeding (uint32 arithmetic):
+ *     s = seed_i; pt_rng_next(&s); s += t; pt_rng_next(&s); s += firstSample + j.  Two draws r1, r2 (pt_random_float) give the
+ *     direction d = direction(R, u, v, r1, r2): a jittered point of the texel.  (float)u + r1 may round up to u + 1 (r1 lies in
+ *     [0, 1]): the direction then lies on the texel's edge, never beyond it.  The ray is the PTRadianceRay {P_i, d, the RNG state
+ *     after the two draws, 0}, and the path is PTTraceRadiance's (Part 8) under `params` with SamplesPerPass forced to 1: L_j is
+ *     the path's colour.  The texel is rgb[c] = (the sum over ascending j of L_j[c], from +0.0f) / (float)samples, and aux = the
+ *     sum over ascending j of lum_j * lum_j with lum = (L.r * 0.299f + L.g * 0.587f) + L.b * 0.114f, unscaled (a later fold of
+ *     two sample ranges can use it).  Samples are independent: PTReflectionRays writes the rays alone and needs no scene.
+ *  3. Prefilter.  Level 0 is the base, copied bit for bit.  For level k >= 1: alpha = rho_k * rho_k; a2 = alpha * alpha;
+ *     g = a2 - 1.0f.  Output texel o has the centre direction n at R >> k.  It walks the base texels s = 0 ... R * R - 1 in
+ *     ascending order: l, len = s's centre at R and J = 1.0f / ((len * len) * len), the octahedral map's solid-angle Jacobian;
+ *     c = (n.x * l.x + n.y * l.y) + n.z * l.z; s is skipped unless c > 0; h = (1.0f + c) * 0.5f; t = h * g + 1.0f;
+ *     w = (c * J) / (t * t); acc[ch] = acc[ch] + w * base[s].rgb[ch]; sw = sw + w, all from +0.0f.  Then rgb = acc / sw and
+ *     aux = sw.  This is the GGX split-sum prefilter with N = V = R in the distribution's rational form: no exp, no pow.  One
+ *     lane owns one output texel, so no cross-lane fold enters the rule.  A NaN or Inf in an unskipped base texel propagates.
+ *  4. Lookup of the query {position P, roughness, direction, probe}, in this order:
+ *     a. probe >= probeCount yields zeros (aux too) and reads nothing.
+ *     b. D = direction, used as given.
+ *     c. Box projection, only with dBoxes != NULL (dProbes then gives the probes' positions Q) and only if
+ *        bmin[a] <= P[a] <= bmax[a] on all three axes: t = +inf; for each axis in x, y, z with D[a] > 0,
+ *        t = min(t, (bmax[a] - P[a]) / D[a]); with D[a] < 0, t = min(t, (bmin[a] - P[a]) / D[a]).  If t is finite and > 0:
+ *        v[a] = (P[a] + D[a] * t) - Q[a]; r = sqrt((v.x * v.x + v.y * v.y) + v.z * v.z); if r > 0, D = v / r.  Otherwise D
+ *        keeps its bits.
+ *     d. (a, b) = oct_coords(D).
+ *     e. r = roughness > 0 ? roughness : 0 (a NaN lands on 0); r = r < 1 ? r : 1; lam = r * (float)(levels - 1);
+ *        k0 = min((uint32_t)lam, levels - 2); f = lam - (float)k0.
+ *     f. In each of the levels k0 and k0 + 1, bilinear: x = (a * 0.5f + 0.5f) * (float)Rk - 0.5f; x0 = floor(x) (held to
+ *        [-1, Rk - 1], which every a in [-1, 1] gives anyway); fx = x - x0; y likewise from b.  The taps (x0 + dx, y0 + dy), dy
+ *        outer, go through the octahedral wrap: a tap with x outside [0, Rk) becomes x' = x < 0 ? -1 - x : 2 * Rk - 1 - x and
+ *        y' = Rk - 1 - y; then the same test and rule run on y, mirroring x.  Every lerp is p + f * (q - p) -- equal taps give
+ *        their value exactly --: first along x in both rows, then along y.
+ *     g. rgb = A + f * (B - A) with A from level k0 and B from level k0 + 1; aux = 1.0f.
+ *
+ * Device pointers are 16-byte aligned; the calls are stream-ordered on the context's stream and nothing past `count` is written.
+ * PTReflectionCapture walks the list in slabs of whole texels of at most 2^22 slots through scratch the context keeps and grows
+ * (48 bytes per slot: the ray and its radiance; kept across PTSetScene, freed by PTDestroy): per slab the rays, PTTraceRadiance's
+ * launch sequences over them (chunks of 2^21 on successive state sets, joined by the context's stream), the fold.
+ * PTStats: paths grows by count * res * res * samples; pixel counters do not move.  With profiling on, every radiance chunk is
+ * one entry of PTGetTimings.  PTReflectionPrefilter and PTReflectionLookup need no scene.
+ * Errors: PT_ERR_INVALID_ARG for a NULL or misaligned pointer, a res or levels outside the ranges above, boxes without probes,
+ * dOutMaps overlapping dBase; PT_ERR_UNSUPPORTED for schedules 0 and 4, samples == 0, samples > 65536 and MaxRayBounces > 8191;
+ * PT_ERR_NO_SCENE for the capture before PTSetScene.  count == 0 returns PT_OK and launches nothing.  Arguments are checked
+ * before the context is used.  No CPU fallback.
+ * The host twins take no context and no GPU; they return 1, or 0 with PTGetBVHBuildError() set.  PTReflectionDirectionsHost
+ * writes PTReflectionRays' entries; PTReflectionFoldHost folds count * res * res * samples PTRadiance entries, slot-major, into
+ * base texels; PTReflectionPrefilterHost and PTReflectionLookupHost are the device calls.
+ * ===================================================================================================================== */
+typedef struct PTReflectionTexel {  /* 16 bytes */
+    float    rgb[3];
+    float    aux;                 /* base: sum of squared luminances; level k >= 1: the weight sum; a lookup: 1 */
+} PTReflectionTexel;
+
+typedef struct PTReflectionQuery {  /* 32 bytes: two 16-byte loads */
+    float    position[3];         /* read only by the box projection */
+    float    roughness;           /* clamped to [0, 1] */
+    float    direction[3];        /* the reflection direction, used as given */
+    uint32_t probe;               /* index into the maps */
+} PTReflectionQuery;
+
+typedef struct PTReflectionBox {    /* 32 bytes: the box a probe's map stands for */
+    float    bmin[3];
+    float    pad0;
+    float    bmax[3];
+    float    pad1;
+} PTReflectionBox;
+
+#ifdef __cplusplus
+static_assert(sizeof(PTReflectionTexel) == 16, "PTReflectionTexel is 16 bytes");
+static_assert(sizeof(PTReflectionQuery) == 32, "PTReflectionQuery is 32 bytes");
+static_assert(sizeof(PTReflectionBox) == 32, "PTReflectionBox is 32 bytes");
+#else
+_Static_assert(sizeof(PTReflectionTexel) == 16, "PTReflectionTexel is 16 bytes");
+_Static_assert(sizeof(PTReflectionQuery) == 32, "PTReflectionQuery is 32 bytes");
+_Static_assert(sizeof(PTReflectionBox) == 32, "PTReflectionBox is 32 bytes");
+#endif
+
+/* dRays: count * res * res * samples entries, slot-major. */
+PT_API int PTReflectionRays(PTContext* ctx, const PTFrameParams* params, const PTProbe* dProbes, uint64_t count, uint32_t res, uint32_t firstSample,
+                            uint32_t samples, PTRadianceRay* dRays);
+/* dOutBase: count * res * res base texels. */
+PT_API int PTReflectionCapture(PTContext* ctx, const PTFrameParams* params, const PTProbe* dProbes, uint64_t count, uint32_t res, uint32_t firstSample,
+                               uint32_t samples, PTReflectionTexel* dOutBase);
+/* Host arrays: staged through device buffers the context keeps and grows; synchronous. */
+PT_API int PTReflectionCaptureHost(PTContext* ctx, const PTFrameParams* params, const PTProbe* probes, uint64_t count, uint32_t res, uint32_t firstSample,
+                                   uint32_t samples, PTReflectionTexel* outBase);
+/* dBase: count base maps; dOutMaps: count whole maps, which must not overlap dBase. */
+PT_API int PTReflectionPrefilter(PTContext* ctx, const PTReflectionTexel* dBase, uint64_t count, uint32_t res, uint32_t levels, PTReflectionTexel* dOutMaps);
+/* dMaps: probeCount whole maps; dProbes, dBoxes: probeCount entries or NULL (boxes need probes); dQueries, dOut: count entries. */
+PT_API int PTReflectionLookup(PTContext* ctx, const PTReflectionTexel* dMaps, uint64_t probeCount, uint32_t res, uint32_t levels, const PTProbe* dProbes,
+                              const PTReflectionBox* dBoxes, const PTReflectionQuery* dQueries, uint64_t count, PTReflectionTexel* dOut);
+/* host twins, no GPU */
+PT_API int PTReflectionDirectionsHost(const PTProbe* probes, uint64_t count, uint32_t res, uint32_t firstSample, uint32_t samples, PTRadianceRay* rays);
+PT_API int PTReflectionFoldHost(const PTRadiance* radiance, uint64_t count, uint32_t res, uint32_t samples, PTReflectionTexel* out);
+PT_API int PTReflectionPrefilterHost(const PTReflectionTexel* base, uint64_t count, uint32_t res, uint32_t levels, PTReflectionTexel* outMaps);
+PT_API int PTReflectionLookupHost(const PTReflectionTexel* maps, uint64_t probeCount, uint32_t res, uint32_t levels, const PTProbe* probes,
+                                  const PTReflectionBox* boxes, const PTReflectionQuery* queries, uint64_t count, PTReflectionTexel* out);
+
 /* Text of the last error on the calling thread ("" if none). */
 PT_API const char* PTGetLastError(void);
 /* Library/ABI version: (major << 16) | minor. */

@@ -366,6 +366,26 @@ def probe_place_params(spacing, max_distance: float = None, min_front_distance: 
     return p
 
 
+# ---- reflection probes (include/ptmi_plugin.h Part 20)
+PT_REFLECTION_MIN_RES = 8
+PT_REFLECTION_MAX_RES = 256
+
+
+class PTReflectionTexel(C.Structure):
+    _fields_ = [("rgb", C.c_float * 3), ("aux", C.c_float)]
+
+
+class PTReflectionQuery(C.Structure):
+    _fields_ = [("position", C.c_float * 3), ("roughness", C.c_float), ("direction", C.c_float * 3), ("probe", C.c_uint32)]
+
+
+class PTReflectionBox(C.Structure):
+    _fields_ = [("bmin", C.c_float * 3), ("pad0", C.c_float), ("bmax", C.c_float * 3), ("pad1", C.c_float)]
+
+
+assert C.sizeof(PTReflectionTexel) == 16 and C.sizeof(PTReflectionQuery) == 32 and C.sizeof(PTReflectionBox) == 32
+
+
 # ---- lightmap charts (include/ptmi_plugin.h Part 14)
 PT_CHART_MAX_SIZE = 8192
 PT_CHART_MAX_DILATE = 16

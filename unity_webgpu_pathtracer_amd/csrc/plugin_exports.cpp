@@ -21,6 +21,7 @@
 #include "placement_rule.h"
 #include "lmfilter_rule.h"
 #include "adaptive_gather_rule.h"
+#include "reflection_rule.h"
 #include "ptmi_plugin.h"
 
 namespace {
@@ -269,6 +270,32 @@ PT_API int PTFoldIrradianceHost(const uint32_t* active, uint64_t activeCount, co
 PT_API int PTEqualiseIrradianceHost(const PTIrradiance* irr, const uint32_t* counts, uint64_t count, uint32_t samplesEq, PTIrradiance* out)
 {
     if (!ptag::equalise_host(irr, counts, count, samplesEq, out, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+// Reflection probes on the host (reflection_host.cpp; Part 20 has the rule).  No GPU involved.
+PT_API int PTReflectionDirectionsHost(const PTProbe* probes, uint64_t count, uint32_t res, uint32_t firstSample, uint32_t samples, PTRadianceRay* rays)
+{
+    if (!ptrefl::directions_host(probes, count, res, firstSample, samples, rays, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+PT_API int PTReflectionFoldHost(const PTRadiance* radiance, uint64_t count, uint32_t res, uint32_t samples, PTReflectionTexel* out)
+{
+    if (!ptrefl::fold_host(radiance, count, res, samples, out, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+PT_API int PTReflectionPrefilterHost(const PTReflectionTexel* base, uint64_t count, uint32_t res, uint32_t levels, PTReflectionTexel* outMaps)
+{
+    if (!ptrefl::prefilter_host(base, count, res, levels, outMaps, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+PT_API int PTReflectionLookupHost(const PTReflectionTexel* maps, uint64_t probeCount, uint32_t res, uint32_t levels, const PTProbe* probes,
+                                  const PTReflectionBox* boxes, const PTReflectionQuery* queries, uint64_t count, PTReflectionTexel* out)
+{
+    if (!ptrefl::lookup_host(maps, probeCount, res, levels, probes, boxes, queries, count, out, g_buildError)) return 0;
     g_buildError.clear();
     return 1;
 }

@@ -2,9 +2,7 @@
 // DESIGN.md 5.13).
 #include "pt_context.h"
 
-namespace {
-
-// One launch sequence per chunk of PT_RADIANCE_CHUNK rays (enqueue_list_chunks)
+// One launch sequence per chunk of PT_RADIANCE_CHUNK rays (enqueue_list_chunks); PTReflectionCapture traces its slabs through it too
 int trace_radiance(PTContext* c, const PTFrameParams& p, const PTRadianceRay* dRays, uint64_t count, PTRadiance* dOut, const char* who)
 {
     if (int rc = check_list_schedule(c, who, "ray")) return rc;
@@ -15,8 +13,6 @@ int trace_radiance(PTContext* c, const PTFrameParams& p, const PTRadianceRay* dR
         L.output = dOut + first;
     });
 }
-
-} // namespace
 
 extern "C" {
 

@@ -253,6 +253,12 @@ struct PTContext {
         DeviceBuffer hostStats;                 // regrows without a drain, as HostStaging does: every use of it ends in the synchronise
                                                 // that closes the PTProbePlaceHost call that made it (host_round_trip)
     } placement;
+    // reflection probes (PTReflectionCapture): the rays and the radiance of one slab of at most 2^22 slots, 48 bytes per slot, used
+    // in stream order behind the context stream, kept across PTSetScene; PTReflectionCaptureHost's staging
+    struct Reflection {
+        DeviceBuffer rays, radiance;
+        HostStaging host;
+    } reflection;
     // lightmap charts (PTRasterizeChart / PTResolveLightmap): grown on demand, kept across PTSetScene
     struct Lightmap {
         DeviceBuffer owner;                     // 4 B per texel: the owner map
@@ -460,6 +466,8 @@ int find_plan(PTContext* c, int32_t bvhOffset, int32_t triOffset, int32_t attrOf
 // pt_api_gather.hip: PTGatherIrradiance's body, one launch sequence per chunk of floor(PT_RADIANCE_CHUNK / samples) whole entries
 int gather_irradiance(PTContext* c, const PTFrameParams& p1, const PTReceiver* dRecv, uint64_t count, uint32_t firstSample, uint32_t samples,
                       PTIrradiance* dOut, const char* who);
+// pt_api_radiance.hip: PTTraceRadiance's body, one launch sequence per chunk of PT_RADIANCE_CHUNK rays
+int trace_radiance(PTContext* c, const PTFrameParams& p, const PTRadianceRay* dRays, uint64_t count, PTRadiance* dOut, const char* who);
 int query_prepare(PTContext* c);                                                // pt_api_query.hip: the grid caps and the stack slab of the query kernels, on first use
 int set_scene(PTContext* c, const PTSceneDesc* hostScene, bool validate);      // pt_api_context.hip; PTGroupSetScene validates once
 int drain_events(PTContext* c);                                                 // pt_api_context.hip

@@ -306,6 +306,18 @@ hipError_t pt_launch_probe_place_step(const PTProbe* probes, uint32_t entries, u
 // placement is not null; otherwise as pt_launch_probe_grid_irradiance
 hipError_t pt_launch_probe_grid_irradiance_placed(const PTProbeGrid& grid, const PTProbeCoeffs* sh, const PTProbeDepthMap* depth, const PTProbePlacement* placement,
                                                   const PTReceiver* queries, uint32_t count, PTIrradiance* out, hipStream_t stream);
+// ---- reflection probes (include/ptmi_plugin.h Part 20; pt_reflection.hip) ----
+// The list's texels [firstTexel, firstTexel + texels) -- texel g belongs to probe g / (res * res) --, texels * samples <= 2^30 slots:
+// the rays kernel writes one PTRadianceRay per slot = (g - firstTexel) * samples + j; the fold turns texels * samples PTRadiance
+// entries into `texels` base texels.
+hipError_t pt_launch_refl_rays(const PTProbe* probes, uint64_t firstTexel, uint32_t texels, uint32_t res, uint32_t firstSample, uint32_t samples,
+                               PTRadianceRay* rays, hipStream_t stream);
+hipError_t pt_launch_refl_fold(const PTRadiance* radiance, uint32_t texels, uint32_t samples, PTReflectionTexel* out, hipStream_t stream);
+// res and levels have passed ptrefl::check_layout; probes <= 65535 per launch
+hipError_t pt_launch_refl_prefilter(const PTReflectionTexel* base, uint32_t probes, uint32_t res, uint32_t levels, PTReflectionTexel* out, hipStream_t stream);
+// probes and boxes may be null (boxes only with probes)
+hipError_t pt_launch_refl_lookup(const PTReflectionTexel* maps, uint64_t probeCount, uint32_t res, uint32_t levels, const PTProbe* probes,
+                                 const PTReflectionBox* boxes, const PTReflectionQuery* queries, uint32_t count, PTReflectionTexel* out, hipStream_t stream);
 #ifndef PT_WF_FUSED_GROUPS
 #define PT_WF_FUSED_GROUPS 2u   // schedule 4: groups of 64 path contexts a persistent wave owns (power of two <= 4: numSlots is a multiple of 256).
                                 // Sponza-class 1080p / 8 spp, one pass in flight: 1: 29.9 ms, 2: 25.2, 4: 27.9, 8: 31.4

@@ -683,6 +683,82 @@ class PathTracer:
             plugin.check(self.lib.PTProbeDepth(self.ctx, rows.data_ptr(), n, first_sample & 0xFFFFFFFF, spp, max_distance, out.data_ptr()))
         return out
 
+    # ---- reflection probes (include/ptmi_plugin.h Part 20)
+    def reflection_rays(self, positions, res: int = 64, spp: int = 16, first_sample: int = 0, seeds=None, params: abi.PTFrameParams = None):
+        """PTReflectionRays: the ray and RNG state each sample of capture_reflection_probes() starts with, as radiance() takes them:
+        (n * res * res * spp, 8) float32 rows, slot-major (row (i * res * res + t) * spp + j = sample first_sample + j of texel t of
+        probe i).  numpy in, numpy out; a device tensor in, a device tensor out."""
+        import torch
+        p = self._radiance_params(params)
+        rows = self._probes(positions, seeds)
+        as_numpy = isinstance(rows, np.ndarray)
+        dev = torch.device(f"cuda:{self.device}")
+        d_rows = torch.from_numpy(rows).to(dev) if as_numpy else rows
+        n = rows.shape[0]
+        ok = abi.PT_REFLECTION_MIN_RES <= res <= abi.PT_REFLECTION_MAX_RES and 0 <= spp <= 65536     # (the call refuses the rest itself)
+        rays = torch.empty((n * res * res * spp if ok else 0, 8), dtype=torch.float32, device=dev)
+        with self._ordered(dev):
+            plugin.check(self.lib.PTReflectionRays(self.ctx, C.byref(p), d_rows.data_ptr() or 16, n, res, first_sample & 0xFFFFFFFF, spp, rays.data_ptr() or 16))
+        return rays.cpu().numpy() if as_numpy else rays            # (`or 16`: an empty tensor has no address, and count == 0 reads none)
+
+    def capture_reflection_base(self, positions, res: int = 64, spp: int = 16, first_sample: int = 0, seeds=None, params: abi.PTFrameParams = None):
+        """PTReflectionCapture: the base maps alone, (n, res * res, 4) float32 -- mean radiance rgb and the sum of the samples' squared
+        luminances per texel v * res + u of the octahedral map.  numpy positions -> PTReflectionCaptureHost, returns numpy; a device
+        tensor -> PTReflectionCapture zero-copy, ordered against torch's current stream both ways, returns a device tensor."""
+        p = self._radiance_params(params)
+        rows = self._probes(positions, seeds)
+        n = rows.shape[0]
+        ok = abi.PT_REFLECTION_MIN_RES <= res <= abi.PT_REFLECTION_MAX_RES
+        shape = (n, res * res if ok else 1, 4)
+        if isinstance(rows, np.ndarray):
+            out = np.empty(shape, np.float32)
+            plugin.check(self.lib.PTReflectionCaptureHost(self.ctx, C.byref(p), rows.ctypes.data, n, res, first_sample & 0xFFFFFFFF, spp, out.ctypes.data))
+            return out
+        import torch
+        out = torch.empty(shape, dtype=torch.float32, device=rows.device)
+        with self._ordered(rows.device):
+            plugin.check(self.lib.PTReflectionCapture(self.ctx, C.byref(p), rows.data_ptr() or 16, n, res, first_sample & 0xFFFFFFFF, spp, out.data_ptr() or 16))
+        return out
+
+    def prefilter_reflection(self, base, res: int, levels: int):
+        """PTReflectionPrefilter: base maps (n, res * res, 4) float32 -> whole maps (n, plugin.reflection_texel_count(res, levels), 4),
+        level k filtered with the GGX lobe of roughness k / (levels - 1).  numpy in, numpy out; a device tensor in, a device tensor
+        out."""
+        import torch
+        dev = torch.device(f"cuda:{self.device}")
+        as_numpy = isinstance(base, np.ndarray)
+        d_base = torch.from_numpy(np.ascontiguousarray(base, dtype=np.float32)).to(dev) if as_numpy else base.contiguous()
+        assert d_base.dtype == torch.float32 and d_base.dim() == 3 and d_base.shape[2] == 4, (d_base.dtype, d_base.shape)
+        n = d_base.shape[0]
+        ok = abi.PT_REFLECTION_MIN_RES <= res <= abi.PT_REFLECTION_MAX_RES and 1 <= levels <= 8
+        out = torch.empty((n, plugin.reflection_texel_count(res, levels) if ok else 1, 4), dtype=torch.float32, device=dev)
+        with self._ordered(dev):
+            plugin.check(self.lib.PTReflectionPrefilter(self.ctx, d_base.data_ptr() or 16, n, res, levels, out.data_ptr() or 32))
+        return out.cpu().numpy() if as_numpy else out
+
+    def capture_reflection_probes(self, positions, res: int = 64, spp: int = 16, levels: int = 5, first_sample: int = 0, seeds=None, boxes=None,
+                                  params: abi.PTFrameParams = None):
+        """Reflection probes on the GPU: what a glossy object that moves through a baked scene reads.  Every probe is an octahedral
+        radiance map of res x res texels around a point, `spp` paths of the render's own per texel (jittered inside the texel;
+        bounces, roulette, firefly filter from `params`, default this tracer's), prefiltered into `levels` levels of roughness
+        0 ... 1 with the GGX lobe.  boxes: None, or (bmin, bmax), each (n, 3) or (3,): the box each probe's surroundings stand for,
+        which lookup() projects directions onto (parallax correction).
+
+        positions: (n, 3) float32, numpy or a tensor on this context's device; seeds: (n,) uint32, None = the probe index.  Returns a
+        ReflectionProbes, whose maps stay on the device."""
+        import torch
+        dev = torch.device(f"cuda:{self.device}")
+        rows = self._probes(positions, seeds)
+        d_rows = torch.from_numpy(rows).to(dev) if isinstance(rows, np.ndarray) else rows
+        base = self.capture_reflection_base(d_rows[:, 0:3].contiguous(), res, spp, first_sample, d_rows.view(torch.int32)[:, 3], params)
+        maps = self.prefilter_reflection(base, res, levels)
+        d_boxes = None
+        if boxes is not None:
+            n = d_rows.shape[0]
+            lo, hi = (np.broadcast_to(np.asarray(b, np.float32), (n, 3)) for b in boxes)
+            d_boxes = torch.from_numpy(plugin.reflection_box_rows(lo, hi)).to(dev)
+        return ReflectionProbes(self, res, levels, maps, d_rows, d_boxes)
+
     # ---- probe placement (include/ptmi_plugin.h Part 18)
     def place_probes(self, positions, spacing, spp: int = 64, iterations: int = 4, max_distance: float = None, min_front_distance: float = None,
                      backface_share: float = 0.25, max_offset: float = 0.45, first_sample: int = 0, seeds=None, start=None, stats: bool = False):
@@ -1484,6 +1560,61 @@ class ProbeVolume:
             with pt._ordered(dev):
                 plugin.check(pt.lib.PTProbeGridIrradiancePlaced(pt.ctx, C.byref(g), self._rows.data_ptr(), self._depth.data_ptr(),
                                                                 None if self.placement is None else self.placement.data_ptr(), recv.data_ptr(), q, out.data_ptr()))
+        return out.cpu().numpy() if as_numpy else out
+
+
+class ReflectionProbes:
+    """Captured and prefiltered reflection probes on the device (PathTracer.capture_reflection_probes; include/ptmi_plugin.h Part
+    20): maps (n, plugin.reflection_texel_count(res, levels), 4) float32, the PTProbe rows (n, 4) and, with box projection, the
+    PTReflectionBox rows (n, 8)."""
+
+    def __init__(self, tracer: "PathTracer", res: int, levels: int, maps, probe_rows, box_rows=None):
+        self.tracer, self.res, self.levels = tracer, int(res), int(levels)
+        self.maps, self.probe_rows, self.box_rows = maps.contiguous(), probe_rows.contiguous(), None if box_rows is None else box_rows.contiguous()
+        n = self.probe_rows.shape[0]
+        assert self.maps.shape == (n, plugin.reflection_texel_count(res, levels), 4), self.maps.shape
+        assert self.box_rows is None or self.box_rows.shape == (n, 8), self.box_rows.shape
+
+    @property
+    def positions(self):
+        return self.probe_rows[:, 0:3]
+
+    def level(self, k: int):
+        """level k of every map as images: (n, res >> k, res >> k, 4), row v, column u; a view of the device maps"""
+        assert 0 <= k < self.levels, k
+        rk, first = self.res >> k, plugin.reflection_texel_count(self.res, k)
+        return self.maps[:, first:first + rk * rk].reshape(-1, rk, rk, 4)
+
+    def lookup(self, directions, roughness, probes, positions=None):
+        """PTReflectionLookup: the prefiltered radiance a surface of `roughness` (0 ... 1) reflects from `directions` (the reflection
+        vector, (q, 3) float32), read from probe `probes` ((q,) indices, or one): trilinear between the four nearest texels of the
+        two nearest levels.  positions: the surface points (q, 3); with boxes given at the capture, a direction from a point inside
+        its probe's box is first projected onto the box and re-aimed from the probe's position.  numpy in, numpy out; device
+        tensors in, a device tensor out.  Returns (q, 4) float32: rgb and 1 (zeros for a probe index out of range)."""
+        import torch
+        pt, dev = self.tracer, self.maps.device
+        as_numpy = isinstance(directions, np.ndarray) or not hasattr(directions, "device")
+        if as_numpy:
+            rows = torch.from_numpy(plugin.reflection_query_rows(directions, roughness, probes, positions)).to(dev)
+        else:
+            d = directions.reshape(-1, 3)
+            q = d.shape[0]
+            assert d.dtype == torch.float32, d.dtype
+            rows = torch.zeros((q, 8), dtype=torch.float32, device=dev)
+            if positions is not None:
+                rows[:, 0:3] = positions.reshape(q, 3)
+            rows[:, 3] = torch.as_tensor(roughness, dtype=torch.float32, device=dev).expand(q)
+            rows[:, 4:7] = d
+            idx = torch.as_tensor(probes, device=dev)
+            rows.view(torch.int32)[:, 7] = pt._seed_bits(idx.expand(q) if idx.dim() == 0 else idx, q, dev)
+        q = rows.shape[0]
+        use_boxes = self.box_rows is not None and positions is not None
+        out = torch.empty((q, 4), dtype=torch.float32, device=dev)
+        if q:
+            with pt._ordered(dev):
+                plugin.check(pt.lib.PTReflectionLookup(pt.ctx, self.maps.data_ptr() or None, self.maps.shape[0], self.res, self.levels,
+                                                       self.probe_rows.data_ptr() or None, self.box_rows.data_ptr() if use_boxes else None,
+                                                       rows.data_ptr(), q, out.data_ptr()))
         return out.cpu().numpy() if as_numpy else out
 
 

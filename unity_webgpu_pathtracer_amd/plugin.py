@@ -158,6 +158,16 @@ sig = {
                                     C.POINTER(C.c_uint64)]),
     "PTFoldIrradianceHost": (i32, [vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.c_uint64, vp, vp]),
     "PTEqualiseIrradianceHost": (i32, [vp, vp, C.c_uint64, C.c_uint32, vp]),
+    # Part 20 (reflection probes)
+    "PTReflectionRays": (i32, [vp, C.POINTER(abi.PTFrameParams), vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
+    "PTReflectionCapture": (i32, [vp, C.POINTER(abi.PTFrameParams), vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
+    "PTReflectionCaptureHost": (i32, [vp, C.POINTER(abi.PTFrameParams), vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
+    "PTReflectionPrefilter": (i32, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp]),
+    "PTReflectionLookup": (i32, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint64, vp]),
+    "PTReflectionDirectionsHost": (i32, [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
+    "PTReflectionFoldHost": (i32, [vp, C.c_uint64, C.c_uint32, C.c_uint32, vp]),
+    "PTReflectionPrefilterHost": (i32, [vp, C.c_uint64, C.c_uint32, C.c_uint32, vp]),
+    "PTReflectionLookupHost": (i32, [vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint64, vp]),
     "PTGetLastError": (C.c_char_p, []), "PTGetVersion": (i32, []),
 }
 EXPORTED_SYMBOLS = list(sig)
@@ -784,6 +794,94 @@ def probe_grid_irradiance(grid: abi.PTProbeGrid, sh, depth, positions=None, norm
         return out
     if not lib.PTProbeGridIrradianceHost(C.byref(grid), rows.ctypes.data, None if d is None else d.ctypes.data, recv.ctypes.data, recv.shape[0], out.ctypes.data):
         raise PluginError(abi.PT_ERR_INVALID_ARG, "PTProbeGridIrradianceHost failed: " + lib.PTGetBVHBuildError().decode())
+    return out
+
+
+def reflection_texel_count(res: int, levels: int = 1) -> int:
+    """Texels of one probe's map with `levels` levels (include/ptmi_plugin.h Part 20): level k is (res >> k) squared; levels = 1 is
+    a base map."""
+    return sum((int(res) >> k) ** 2 for k in range(int(levels)))
+
+
+def reflection_directions(positions, res: int, spp: int, first_sample: int = 0, seeds=None) -> np.ndarray:
+    """The sample rays of reflection probes on the host (PTReflectionDirectionsHost): (n * res * res * spp, 8) float32 PTRadianceRay
+    rows, slot-major -- row (i * res * res + t) * spp + j is sample first_sample + j of texel t of probe i --, bit for bit what
+    PTReflectionRays writes."""
+    rows = probe_rows(positions, seeds)
+    ok = abi.PT_REFLECTION_MIN_RES <= int(res) <= abi.PT_REFLECTION_MAX_RES           # (the twin refuses another res itself)
+    rays = np.empty((rows.shape[0] * int(res) ** 2 * max(int(spp), 0) if ok else 0, 8), np.float32)
+    lib = load_library()
+    if not lib.PTReflectionDirectionsHost(rows.ctypes.data, rows.shape[0], int(res), first_sample & 0xFFFFFFFF, int(spp), rays.ctypes.data):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTReflectionDirectionsHost failed: " + lib.PTGetBVHBuildError().decode())
+    return rays
+
+
+def reflection_fold(radiance, n: int, res: int) -> np.ndarray:
+    """Fold per-sample radiance into base texels on the host (PTReflectionFoldHost): radiance (n * res * res * spp, 4) float32
+    PTRadiance rows, slot-major -> (n, res * res, 4) float32: mean rgb and the sum of squared luminances."""
+    r = np.ascontiguousarray(radiance, dtype=np.float32).reshape(-1, 4)
+    texels = int(n) * int(res) ** 2
+    assert texels > 0 and r.shape[0] % texels == 0, (r.shape, n, res)
+    out = np.empty((int(n), int(res) ** 2, 4), np.float32)
+    lib = load_library()
+    if not lib.PTReflectionFoldHost(r.ctypes.data, int(n), int(res), r.shape[0] // texels, out.ctypes.data):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTReflectionFoldHost failed: " + lib.PTGetBVHBuildError().decode())
+    return out
+
+
+def reflection_prefilter(base, res: int, levels: int) -> np.ndarray:
+    """The GGX prefilter on the host (PTReflectionPrefilterHost): base (n, res * res, 4) float32 -> (n, reflection_texel_count(res,
+    levels), 4) float32, the levels in ascending order; level k stands for roughness k / (levels - 1)."""
+    b = np.ascontiguousarray(base, dtype=np.float32)
+    assert b.ndim == 3 and b.shape[2] == 4, b.shape
+    ok = abi.PT_REFLECTION_MIN_RES <= int(res) <= abi.PT_REFLECTION_MAX_RES and 1 <= int(levels) <= 8
+    if ok:
+        assert b.shape[1] == int(res) ** 2, (b.shape, res)
+    out = np.empty((b.shape[0], reflection_texel_count(res, levels) if ok else 1, 4), np.float32)
+    lib = load_library()
+    if not lib.PTReflectionPrefilterHost(b.ctypes.data, b.shape[0], int(res), int(levels), out.ctypes.data):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTReflectionPrefilterHost failed: " + lib.PTGetBVHBuildError().decode())
+    return out
+
+
+def reflection_query_rows(directions, roughness, probes, positions=None) -> np.ndarray:
+    """(q, 8) float32 PTReflectionQuery rows -- position xyz (None: zeros), roughness, direction xyz, probe index bits"""
+    d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+    q = d.shape[0]
+    rows = np.zeros((q, 8), np.float32)
+    if positions is not None:
+        rows[:, 0:3] = np.ascontiguousarray(positions, dtype=np.float32).reshape(q, 3)
+    rows[:, 3] = np.broadcast_to(np.asarray(roughness, np.float32), (q,))
+    rows[:, 4:7] = d
+    rows[:, 7] = np.ascontiguousarray(np.broadcast_to(np.asarray(probes).astype(np.uint32), (q,))).view(np.float32)
+    return rows
+
+
+def reflection_box_rows(bmin, bmax) -> np.ndarray:
+    """(n, 8) float32 PTReflectionBox rows -- bmin xyz, 0, bmax xyz, 0"""
+    lo = np.ascontiguousarray(bmin, dtype=np.float32).reshape(-1, 3)
+    rows = np.zeros((lo.shape[0], 8), np.float32)
+    rows[:, 0:3], rows[:, 4:7] = lo, np.ascontiguousarray(bmax, dtype=np.float32).reshape(-1, 3)
+    return rows
+
+
+def reflection_lookup(maps, res: int, levels: int, directions=None, roughness=0.0, probes=0, positions=None, probe_positions=None, boxes=None,
+                      queries=None) -> np.ndarray:
+    """A reflection probe's lookup on the host (PTReflectionLookupHost): maps (n, reflection_texel_count(res, levels), 4) float32;
+    directions (q, 3), roughness and probes one number or (q,), or ready-made (q, 8) PTReflectionQuery rows.  boxes: (n, 8)
+    PTReflectionBox rows (reflection_box_rows) for the box projection, which then needs probe_positions (n, 3) and the queries'
+    positions.  Returns (q, 4) float32: rgb and 1 (zeros for a probe index >= n)."""
+    m = np.ascontiguousarray(maps, dtype=np.float32)
+    assert m.ndim == 3 and m.shape[2] == 4, m.shape
+    qr = reflection_query_rows(directions, roughness, probes, positions) if queries is None else np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 8)
+    pr = None if probe_positions is None else probe_rows(probe_positions)
+    bx = None if boxes is None else np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 8)
+    assert (pr is None or pr.shape[0] == m.shape[0]) and (bx is None or bx.shape[0] == m.shape[0]), (m.shape, pr is None, bx is None)
+    out = np.empty((qr.shape[0], 4), np.float32)
+    lib = load_library()
+    if not lib.PTReflectionLookupHost(m.ctypes.data if m.shape[0] else None, m.shape[0], int(res), int(levels), None if pr is None else pr.ctypes.data,
+                                      None if bx is None else bx.ctypes.data, qr.ctypes.data, qr.shape[0], out.ctypes.data):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTReflectionLookupHost failed: " + lib.PTGetBVHBuildError().decode())
     return out
 
 
