@@ -330,6 +330,23 @@ PT_API void* PTGetStream(PTContext* ctx);
 PT_API int PTSetStatsLevel(PTContext* ctx, int level);
 PT_API int PTGetStats(PTContext* ctx, PTStats* out);
 PT_API int PTResetStats(PTContext* ctx);
+/* The mid-pass slot repack of the default schedule: passes over the context's own blocks, on frames large enough
+ * for it, move the state of their live paths to the front of the state set a few times per pass, so that the shading waves stay
+ * full.  Frames and PTStats do not depend on it.  Counted on the device since the context was created (PTResetStats leaves
+ * them), read with the same ordering as PTGetStats. */
+typedef struct PTRepackStats {
+    uint64_t sequences;            /* launch sequences that had at least one repack candidate          */
+    uint64_t candidates;           /* candidates: points of a sequence where the live slots are counted */
+    uint64_t repacks;              /* candidates at which the state was moved                           */
+    uint64_t slotsMoved;           /* live slots moved, summed over the repacks                         */
+} PTRepackStats;
+PT_API int PTGetRepackStats(PTContext* ctx, PTRepackStats* out);
+/* The rule of a repack on the host (csrc/repack_rule.h), no GPU involved: flags = numSlots 32-bit state words (a slot is live
+ * unless (word & 3) == 2; numSlots a multiple of 256), capacity = slots the temporary region holds, fill = fillNum / fillDen.
+ * outPlan[3] = {1 if the set is repacked else 0, live slots L, extent E}; outDest (may be NULL): the slot every live slot moves
+ * to (0xFFFFFFFF for a finished one).  Returns 1, or 0 for a NULL array, a numSlots that is no multiple of 256 or fillDen == 0. */
+PT_API int PTRepackPlanHost(const uint32_t* flags, uint32_t numSlots, uint32_t capacity, uint32_t fillNum, uint32_t fillDen,
+                            uint32_t* outPlan, uint32_t* outDest);
 
 PT_API int PTSetProfiling(PTContext* ctx, int enabled);
 PT_API int PTGetTimings(PTContext* ctx, PTTimings* out);

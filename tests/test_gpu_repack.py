@@ -1,0 +1,134 @@
+"""The mid-pass slot repack of the default schedule (csrc/pt_repack.hip, csrc/repack_rule.h).
+
+The product repacks only large frames.  A variant library (make -C unity_webgpu_pathtracer_amd/csrc stress-repack) switches it on
+for every state set of 256 slots or more, with a candidate after EVERY iteration and no fill threshold, so that frames of a few
+blocks are repacked again and again -- also right before the cleanup kernel.  A repack moves paths between slots and nothing
+else: every frame must equal the oracle's bit for bit, all 16 counters must equal the oracle's, and PTGetRepackStats must show
+that repacks really ran (and that at least one candidate was refused: too many live slots early on, none at the end)."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+STRESS = os.path.join(ROOT, "unity_webgpu_pathtracer_amd", "lib", "libpt-stress-repack.so")
+SEEDS = [0x5EED0001, 0x5EED0002, 0x5EED0003]
+
+# name -> (scene, its arguments, width, height, spp, bounces, what is special)
+CASES = {
+    "zoo": ("material_zoo", {}, 64, 32, 2, 2, {}),                                         # 8 blocks
+    "edge": ("material_zoo", {}, 48, 40, 2, 4, {}),                                        # no multiple of 16: slots finished at init, 9 blocks
+    "batch": ("material_zoo", {}, 32, 32, 2, 4, {"batch": 3}),                             # pixel slots beyond slotsPerPass
+    "tiles": ("material_zoo", {}, 64, 32, 2, 4, {"rank": 1, "world": 2}),
+    "subframes": ("material_zoo", {}, 64, 32, 2, 4, {"sub_frames": 2}),
+    "tlas": ("instanced_scene", {"count": 20}, 64, 48, 2, 4, {}),                          # HAS_TLAS
+    "cleanup": ("material_zoo", {}, 64, 32, 1, 4, {"iterations": 3}),                      # live, already repacked slots reach pt_wf_cleanup
+    "cornell": ("cornell_box", {}, 32, 32, 1, 4, {}),                                      # late candidates with nothing alive
+}
+
+CHILD = r'''
+import sys, numpy as np
+sys.path.insert(0, sys.argv[1])
+sys.path.insert(0, sys.argv[1] + "/tests")
+import torch
+from unity_webgpu_pathtracer_amd import scenes
+from unity_webgpu_pathtracer_amd.pathtracer import PathTracer
+from test_gpu_repack import CASES, SEEDS, case_params
+out = {}
+for name, (scene, kw, w, h, spp, bounces, extra) in CASES.items():
+    s = getattr(scenes, scene)(**kw)
+    for level in (0, 1):                                   # the kernels a render uses, then the ones that count everything
+        pt = PathTracer(s, width=w, height=h, samplesPerPass=spp, maxRayBounces=bounces, schedule=1, rank=extra.get("rank", 0),
+                        world_size=extra.get("world", 1))
+        pt.set_stats_level(level)
+        if "iterations" in extra:
+            pt.set_wavefront_iterations(extra["iterations"])
+        if "sub_frames" in extra:
+            pt.set_sub_frames(extra["sub_frames"])
+        params = case_params(s, w, h, spp, bounces, extra)
+        frame = torch.zeros((h, w, 4), dtype=torch.float32, device="cuda")
+        if "batch" in extra:
+            pt.render_batch_to(params, frame.data_ptr(), 0)
+        else:
+            pt.render_pass_to(params[0], frame.data_ptr(), 0)
+        pt.synchronize()
+        out[f"{name}_frame{level}"] = frame.cpu().numpy()
+        st, rp = pt.stats().as_dict(), pt.repack_stats().as_dict()
+        out[f"{name}_stats{level}"] = np.array([st[k] for k in sorted(st)], dtype=np.uint64)
+        out[f"{name}_repack{level}"] = np.array([rp[k] for k in ("sequences", "candidates", "repacks", "slotsMoved")], dtype=np.uint64)
+        print(f"[repack] {name} level {level}: {rp}", flush=True)
+        pt.close()
+np.savez(sys.argv[2], **out)
+'''
+
+
+def case_params(s, w, h, spp, bounces, extra):
+    from unity_webgpu_pathtracer_amd import scenes
+    return [scenes.frame_params(s, w, h, spp=spp, current_sample=k * spp, seed=SEEDS[k], max_bounces=bounces) for k in range(extra.get("batch", 1))]
+
+
+@pytest.fixture(scope="module")
+def stress_run(tmp_path_factory):
+    """every case rendered by the variant library, in ONE fresh child process"""
+    if not os.path.exists(STRESS):
+        subprocess.check_call(["make", "-C", os.path.join(ROOT, "unity_webgpu_pathtracer_amd", "csrc"), "stress-repack"], stdout=subprocess.DEVNULL)
+    out = str(tmp_path_factory.mktemp("repack") / "repack.npz")
+    subprocess.check_call([sys.executable, "-c", CHILD, ROOT, out], env=dict(os.environ, PT_PLUGIN=STRESS), timeout=600)
+    return np.load(out)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_repacked_frames_and_counters_equal_the_oracle(stress_run, oracle, name):
+    from unity_webgpu_pathtracer_amd import scenes
+    from unity_webgpu_pathtracer_amd.pathtracer import BVHScene
+    scene, kw, w, h, spp, bounces, extra = CASES[name]
+    s = getattr(scenes, scene)(**kw)
+    b = oracle.buffers_from_bvhscene(BVHScene(s))
+    ref, total = None, {}
+    for p in case_params(s, w, h, spp, bounces, extra):
+        ref, st = oracle.render(b, p, accumulated=ref, shadow_any_hit=True, tile_rank=extra.get("rank", 0), tile_world=extra.get("world", 1))
+        for k, v in st.as_dict().items():
+            total[k] = max(total.get(k, 0), v) if k == "maxStackDepth" else total.get(k, 0) + v
+    for level in (0, 1):
+        got = stress_run[f"{name}_frame{level}"]
+        assert np.array_equal(got.view(np.uint32), ref.view(np.uint32)), (name, level)
+        sequences, candidates, repacks, moved = (int(x) for x in stress_run[f"{name}_repack{level}"])
+        print(f"[repack] {name} level {level}: sequences {sequences} candidates {candidates} repacks {repacks} slots moved {moved}")
+        assert sequences == extra.get("sub_frames", 1), (name, sequences)
+        assert repacks >= 2 and candidates - repacks >= 1 and moved >= repacks, (name, candidates, repacks, moved)
+    assert np.array_equal(stress_run[f"{name}_stats1"], np.array([total[k] for k in sorted(total)], dtype=np.uint64)), name
+    # level 0 counts paths and rays only
+    for k in ("paths", "closestHitRays", "shadowRays"):
+        assert int(stress_run[f"{name}_stats0"][sorted(total).index(k)]) == total[k], (name, k)
+
+
+@pytest.mark.gpu
+def test_default_library_repacks_large_frames_only():
+    """The product's own thresholds: the smallest frame that is repacked (the boundary of the wide trace ranges, 512 x 512 on a
+    device of 256 CUs) against schedule 4, which has no slots to repack -- equal frames, equal counters --, and a frame below it."""
+    from unity_webgpu_pathtracer_amd import scenes
+    from unity_webgpu_pathtracer_amd.pathtracer import PathTracer
+    s = scenes.material_zoo()
+    frames, stats = {}, {}
+    for schedule in (1, 4):
+        pt = PathTracer(s, width=512, height=512, samplesPerPass=2, schedule=schedule)
+        pt.set_stats_level(1)
+        pt.render_pass(pt.params(seed=0xD0C5))
+        frames[schedule], stats[schedule] = pt.readback(), pt.stats().as_dict()
+        rp = pt.repack_stats().as_dict()
+        print(f"[repack] default library, 512x512, schedule {schedule}: {rp}")
+        if schedule == 1:
+            assert rp["sequences"] == 1 and rp["repacks"] > 0 and rp["slotsMoved"] > 0, rp
+        else:
+            assert rp == dict(sequences=0, candidates=0, repacks=0, slotsMoved=0), rp
+        pt.close()
+    assert np.array_equal(frames[1].view(np.uint32), frames[4].view(np.uint32))
+    assert stats[1] == stats[4]
+    pt = PathTracer(s, width=496, height=512, samplesPerPass=2, schedule=1)
+    pt.render_pass(pt.params(seed=0xD0C5))
+    pt.synchronize()
+    assert pt.repack_stats().as_dict() == dict(sequences=0, candidates=0, repacks=0, slotsMoved=0)
+    pt.close()

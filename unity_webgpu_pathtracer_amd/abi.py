@@ -139,6 +139,14 @@ class PTStats(C.Structure):
                    + 64 * self.tlasNodeVisits + 144 * self.instanceVisits)
 
 
+class PTRepackStats(C.Structure):
+    """PTGetRepackStats: the mid-pass slot repack of the default schedule, counted on the device since the context was created"""
+    _fields_ = [(n, C.c_uint64) for n in ("sequences", "candidates", "repacks", "slotsMoved")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class PTPresentParams(C.Structure):
     """Presentation.shader uniforms (PathTracer.cs:255-264); defaults = the inspector defaults (PathTracer.cs:41-48)."""
     _fields_ = [("OutputWidth", C.c_uint32), ("OutputHeight", C.c_uint32), ("Mode", C.c_int32), ("sRGB", C.c_int32),

@@ -22,6 +22,7 @@
 #include "lmfilter_rule.h"
 #include "adaptive_gather_rule.h"
 #include "reflection_rule.h"
+#include "repack_rule.h"
 #include "ptmi_plugin.h"
 
 namespace {
@@ -296,6 +297,18 @@ PT_API int PTReflectionLookupHost(const PTReflectionTexel* maps, uint64_t probeC
                                   const PTReflectionBox* boxes, const PTReflectionQuery* queries, uint64_t count, PTReflectionTexel* out)
 {
     if (!ptrefl::lookup_host(maps, probeCount, res, levels, probes, boxes, queries, count, out, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+// The slot-repack rule on the host (repack_host.cpp; repack_rule.h has the rule).  No GPU involved.
+PT_API int PTRepackPlanHost(const uint32_t* flags, uint32_t numSlots, uint32_t capacity, uint32_t fillNum, uint32_t fillDen, uint32_t* outPlan, uint32_t* outDest)
+{
+    ptrepack::Plan plan;
+    if (!flags || !outPlan || !ptrepack::plan_host(flags, numSlots, capacity, fillNum, fillDen, plan, outDest, nullptr)) {
+        g_buildError = "NULL flags or plan, numSlots not a multiple of 256, or fillDen == 0";
+        return 0;
+    }
+    outPlan[0] = plan.go; outPlan[1] = plan.live; outPlan[2] = plan.extent;
     g_buildError.clear();
     return 1;
 }

@@ -434,9 +434,9 @@ PT_API int PTCreate(int deviceIndex, PTContext** outCtx)
         if (int rc = create_set_stream(0u, c->sets[0].stream, &c->ownQueues)) { delete c; return rc; }
     }
     c->numSets = default_passes_in_flight(c->ownQueues);
-    se = hipMalloc(&c->dStats.ptr, 16 * sizeof(unsigned long long));
+    se = hipMalloc(&c->dStats.ptr, (16 + 4) * sizeof(unsigned long long));       // PTStats, PTRepackStats
     if (se != hipSuccess) { delete c; return fail(PT_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(se)); }
-    hipMemsetAsync(c->dStats.ptr, 0, 16 * sizeof(unsigned long long), c->stream);
+    hipMemsetAsync(c->dStats.ptr, 0, (16 + 4) * sizeof(unsigned long long), c->stream);
     *outCtx = c;
     return PT_OK;
 }
@@ -488,6 +488,19 @@ PT_API int PTGetStats(PTContext* c, PTStats* out)
     HIP_TRY(hipStreamSynchronize(c->stream));
     static_assert(sizeof(PTStats) == 16 * 8, "PTStats is 16 counters");
     memcpy(out, h, sizeof(PTStats));
+    return PT_OK;
+}
+
+// the four counters the repack's decide kernel adds to on the device (pt_wavefront.hip), read on demand
+PT_API int PTGetRepackStats(PTContext* c, PTRepackStats* out)
+{
+    if (!c || !out) return fail(PT_ERR_INVALID_ARG, "ctx/out == NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    unsigned long long h[4];
+    HIP_TRY(hipMemcpyAsync(h, (unsigned long long*)c->dStats.ptr + 16, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    static_assert(sizeof(PTRepackStats) == 4 * 8, "PTRepackStats is 4 counters");
+    memcpy(out, h, sizeof(PTRepackStats));
     return PT_OK;
 }
 

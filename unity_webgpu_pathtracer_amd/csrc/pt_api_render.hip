@@ -60,6 +60,7 @@ int enqueue_wavefront(PTContext* c, PTContext::WfSet& set, PTWfLaunch& L, hipEve
     L.scene = &c->scene;
     L.buffers = &set.wf;
     L.counters = (unsigned long long*)c->dStats.ptr;
+    L.repackStats = L.counters + 16;
     L.fullStats = c->statsLevel > 0;
     L.stream = set.stream;
     L.schedule = effective_schedule(c);

@@ -167,7 +167,7 @@ struct PTContext {
     int rank = 0, world = 1;
     int statsLevel = 0;
     int schedule = -1;                          // -1 auto (default), 0 megakernel, 1 wavefront + refill trace, 2, 3: see PTSetSchedule
-    DeviceBuffer dStats;                        // 16 counters, PTStats order
+    DeviceBuffer dStats;                        // 16 counters, PTStats order, then the 4 of PTRepackStats
     bool profiling = false;
     std::vector<EventPair> pending;             // recorded, not yet read
     std::vector<EventPair> freeEvents;

@@ -169,7 +169,14 @@ struct PTWfBuffers {
     uint32_t numSlots, numStatRows, maxIterations;
     uint32_t slotsPerPass;      // numSlots = passes of the batch x slotsPerPass; slot s belongs to pass s / slotsPerPass, pixel slot s % slotsPerPass
     uint32_t residentWaves;     // waves the device holds at the trace kernel's occupancy (CUs x 4 SIMDs x 8)
+    // ---- mid-pass slot repack (pt_repack.hip, repack_rule.h).  Appended: no kernel that does not read them moves ----
+    uint32_t* pixelOf;          // [numSlots] the pixel slot whose path a slot carries: the identity until a repack moves the path
+    uint32_t* rpPrefix;         // [numSlots / 256] live slots per block, then their exclusive prefix
+    uint32_t* rpCtl;            // [ptrepack::PT_REPACK_CTL_WORDS] the decision of the last candidate: go, L, E
+    char* rpTemp;               // the temporary SoA region of a repack: rpCapacity slots x PT_WF_REPACK_SLOT_BYTES
+    uint32_t rpCapacity;        // numSlots / 2
 };
+#define PT_WF_REPACK_SLOT_BYTES 204u     // flags, rng, pixelOf (4 each) + three 32-byte ray records + rad, thr, color, envC, lightC, pthr (16 each)
 
 // The arena of a state set: every array of PTWfBuffers carved from one allocation of pt_wf_arena_bytes() bytes.  Both are defined
 // in pt_wavefront.hip, by the one of its two compilations that every library links (-DPT_WF_TU_B), so the layout is by
@@ -326,6 +333,62 @@ hipError_t pt_launch_refl_lookup(const PTReflectionTexel* maps, uint64_t probeCo
 #define PT_WF_SUSPEND 16u       // refill trace kernel: a wave whose range is exhausted stops when this many rays or fewer are left, and leaves them
                                 // as records for the tail launch (pt_wavefront.hip); 0 = off.  Also the record slots per trace wave (pt_wf_arena_bytes)
 #endif
+// ---- mid-pass slot repack (schedule 1 over PTTileMap; pt_repack.hip, pt_wavefront.hip's launch sequence) ----
+// After the shade launch of a CANDIDATE iteration the live slots of the set are counted, and when few enough are left
+// (0 < L <= numSlots / 2 and L <= fill x E, E = end of the highest live block) their state is moved to slots [0, L): the
+// shade waves that follow are full again and the trace ranges dense.  Candidates: iteration first = FIRST_SPP x spp + FIRST_ADD,
+// then every STRIDE-th, at most MAX_CANDIDATES of them, none with fewer than MIN_LEFT iterations to go.  Measured on the
+// Sponza-class pass (profiles/slot_repack_ab.md): every slot is alive through iteration spp - 1, half of them at iteration 2 spp.
+// PT_WF_REPACK_MIN_SLOTS: sets of fewer slots keep their sequence; not defined = the pt_wf_wide_ranges boundary.
+#ifndef PT_WF_REPACK_MIN_ITERATIONS
+#define PT_WF_REPACK_MIN_ITERATIONS 12u
+#endif
+// Sweep on the Sponza-class benchmark, Mrays/s against the parent's 5,650 (profiles/slot_repack_ab.md): first spp + 2, stride 2, no
+// limit: 5,787; stride 1: 5,647 (a candidate is four launches whether it repacks or not); first 2 spp: 5,820; first 2 spp with
+// at most 7 / 6 / 5 candidates: 5,869 / 5,876 / 5,896 -- a repack of fewer than ~50 k slots costs more than the waves it saves.
+#ifndef PT_WF_REPACK_FIRST_SPP
+#define PT_WF_REPACK_FIRST_SPP 2u
+#endif
+#ifndef PT_WF_REPACK_FIRST_ADD
+#define PT_WF_REPACK_FIRST_ADD 0u
+#endif
+#ifndef PT_WF_REPACK_STRIDE
+#define PT_WF_REPACK_STRIDE 2u
+#endif
+#ifndef PT_WF_REPACK_MAX_CANDIDATES
+#define PT_WF_REPACK_MAX_CANDIDATES 5u
+#endif
+#ifndef PT_WF_REPACK_MIN_LEFT
+#define PT_WF_REPACK_MIN_LEFT 4u
+#endif
+#ifndef PT_WF_REPACK_FILL_NUM
+#define PT_WF_REPACK_FILL_NUM 3u
+#endif
+#ifndef PT_WF_REPACK_FILL_DEN
+#define PT_WF_REPACK_FILL_DEN 4u
+#endif
+inline bool pt_wf_repack_slots(uint32_t numSlots, uint32_t residentWaves)
+{
+#ifdef PT_WF_REPACK_MIN_SLOTS
+    return numSlots >= PT_WF_REPACK_MIN_SLOTS;
+#else
+    return pt_wf_wide_ranges(numSlots, residentWaves);
+#endif
+}
+// is the state after the shade launch of iteration `it` (of `iterations`) a candidate?
+inline bool pt_wf_repack_candidate(uint32_t it, uint32_t iterations, uint32_t spp)
+{
+    const uint32_t first = PT_WF_REPACK_FIRST_SPP * spp + PT_WF_REPACK_FIRST_ADD;
+    if (it < first || it + PT_WF_REPACK_MIN_LEFT >= iterations) return false;            // iterations after it: iterations - 1 - it
+    return (it - first) % PT_WF_REPACK_STRIDE == 0u && (it - first) / PT_WF_REPACK_STRIDE < PT_WF_REPACK_MAX_CANDIDATES;
+}
+// pt_repack.hip: the four launches of a candidate (count, scan and decide, move out, move back) on set B; the shade launch and the
+// cleanup launch of a sequence that repacks (the pixel of a slot from B.pixelOf, finished sums into B.pixsum).  stats may be null.
+hipError_t pt_launch_repack(const PTWfBuffers& B, uint32_t fillNum, uint32_t fillDen, bool firstOfSequence, unsigned long long* stats, hipStream_t stream);
+hipError_t pt_launch_repack_shade(const DScene& S, const PTFrameParams& P, const PTTileMap& tm, const PTWfBuffers& B, bool fullStats, uint32_t iteration,
+                                  hipStream_t stream);
+hipError_t pt_launch_repack_cleanup(const DScene& S, const PTFrameParams& P, const PTTileMap& tm, const PTWfBuffers& B, bool fullStats, uint32_t blocks,
+                                    hipStream_t stream);
 #ifndef PT_WF_SETS
 #define PT_WF_SETS 12            // path-state sets = passes that can be in flight at once, each on its own stream (3 -> 6 sets with 8 hardware queues: +12 %;
                                  // 6 -> 12 sets with 16 queues: +2 % at 1080p, +7 % at 960x540, -14 % time for a 1/8 share of a 1080p frame; 16: no better, 24: worse)
@@ -355,6 +418,7 @@ struct PTWfLaunch {
     bool zeroOutputFirst;                   // PT_WF_MAP_TILES only: clear the frame before the resolve (pixels of other ranks read as zeros)
     int schedule;                           // 1 ... 4 (PTSetSchedule)
     uint32_t iterationsOverride;            // 0 = spp * (bounces + 2) + 4, capped by buffers->maxIterations
+    unsigned long long* repackStats;        // may be null: the context's four repack counters (PTRepackStats order), added to on the device
 };
 // Enqueues the sequence on L.stream without host synchronisation; launchesOut (may be null): kernel launches enqueued.
 // hipErrorNotSupported for schedule 4 over a list, rays, a gather or probes.  pt_wavefront.hip is compiled twice with different scheduler flags

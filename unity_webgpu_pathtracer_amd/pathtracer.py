@@ -285,6 +285,12 @@ class PathTracer:
     def reset_stats(self):
         plugin.check(self.lib.PTResetStats(self.ctx))
 
+    def repack_stats(self) -> abi.PTRepackStats:
+        """PTGetRepackStats: launch sequences with a repack candidate, candidates, repacks done and live slots moved"""
+        st = abi.PTRepackStats()
+        plugin.check(self.lib.PTGetRepackStats(self.ctx, C.byref(st)))
+        return st
+
     def set_profiling(self, on: bool):
         plugin.check(self.lib.PTSetProfiling(self.ctx, 1 if on else 0))
 

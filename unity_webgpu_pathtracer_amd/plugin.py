@@ -44,6 +44,8 @@ sig = {
     "PTSynchronize": (i32, [vp]), "PTReadback": (i32, [vp, vp, C.c_uint64]),
     "PTGetFramePointer": (vp, [vp, i32]), "PTGetStream": (vp, [vp]),
     "PTSetStatsLevel": (i32, [vp, i32]), "PTGetStats": (i32, [vp, C.POINTER(abi.PTStats)]), "PTResetStats": (i32, [vp]),
+    "PTGetRepackStats": (i32, [vp, C.POINTER(abi.PTRepackStats)]),
+    "PTRepackPlanHost": (i32, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]),
     "PTSetProfiling": (i32, [vp, i32]), "PTGetTimings": (i32, [vp, C.POINTER(abi.PTTimings)]), "PTResetTimings": (i32, [vp]),
     "PTProcessMeshes": (i32, [vp, C.POINTER(abi.PTMeshDesc), C.c_uint32, C.c_uint32, vp, vp]),
     "PTCopyTextureData": (i32, [vp, C.POINTER(abi.PTTextureDesc), C.c_uint32, vp, C.c_uint64]),
