@@ -83,8 +83,10 @@ def _device_select(pt, acc, recv, n, params, active=None, pad=64):
     return got_a[:s], got_r[:s], np.array(list(stopped), np.uint64)
 
 
-@pytest.mark.parametrize("count", cases.SIZES)
+@pytest.mark.parametrize("count", cases.SIZES + [262144])
 def test_select_equals_twin(box, count):
+    """262,144 and 262,145 entries are 1,024 and 1,025 blocks: the last list of which each of the scan's 1,024 threads owns one
+    block count, and the first of which it owns two (csrc/pt_compact.h)"""
     pt, _ = box
     for pattern in cases.PATTERNS:
         acc, recv, keep = cases.generated_list(count, pattern, seed=count)
@@ -95,7 +97,7 @@ def test_select_equals_twin(box, count):
         _same(got[1], want[1], (count, pattern))
 
 
-@pytest.mark.parametrize("count", [257, 1000, 262145])
+@pytest.mark.parametrize("count", [257, 1000, 262144, 262145])
 def test_select_through_a_list_equals_twin(box, count):
     pt, _ = box
     acc, recv, keep = cases.generated_list(count, "random30", seed=count + 1)
@@ -130,7 +132,7 @@ def test_select_special_entries_equal_twin(box):
         assert len(got[0]) == kept and list(got[2]) == [150, by_max, 0], max_samples
 
 
-@pytest.mark.parametrize("count", [1, 257, 1000, 262145])
+@pytest.mark.parametrize("count", [1, 257, 1000, 262144, 262145])
 def test_fold_and_equalise_equal_twins(box, count):
     import torch
     pt, _ = box

@@ -157,6 +157,22 @@ def test_compaction_across_blocks_and_capacity(flat_zoo):
     _assert_same((texels[:n].cpu().numpy().view(np.uint32), recv[:n].cpu().numpy()), want)
 
 
+@pytest.mark.parametrize("size, blocks", [((16, 16), 1), ((512, 512), 1024), ((641, 409), 1025)])
+def test_compaction_where_the_scan_changes_its_runs(flat_zoo, size, blocks):
+    """Thread t of the scan's 1,024 owns the ceil(blocks / 1024) block counts from t times that number (csrc/pt_compact.h).  One
+    block: threads 1 to 1,023 own nothing.  1,024 blocks: every thread owns exactly one.  1,025 blocks: two each, the threads
+    from 513 up own nothing, and the last block holds 25 texels."""
+    w, h = size
+    want = _twin(flat_zoo, w, h, seed=1)
+    occupied = np.zeros(w * h, np.int64)
+    occupied[want[0]] = 1
+    counts = np.add.reduceat(occupied, np.arange(0, w * h, 256))
+    assert len(counts) == blocks and w * h - 256 * (blocks - 1) == {1: 256, 1024: 256, 1025: 25}[blocks]
+    if blocks > 1:
+        assert (counts == 0).sum() >= 1 and ((counts > 0) & (counts < 256)).sum() >= 50, "the case must hold partial and empty blocks"
+    _assert_same(_device(flat_zoo, w, h, seed=1), want)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # 2. the current generation of the geometry
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -108,25 +108,27 @@ def test_repacked_frames_and_counters_equal_the_oracle(stress_run, oracle, name)
 @pytest.mark.gpu
 def test_default_library_repacks_large_frames_only():
     """The product's own thresholds: the smallest frame that is repacked (the boundary of the wide trace ranges, 512 x 512 on a
-    device of 256 CUs) against schedule 4, which has no slots to repack -- equal frames, equal counters --, and a frame below it."""
+    device of 256 CUs) and the next wider one, in which a thread of the scan owns two blocks (csrc/pt_compact.h), against schedule 4,
+    which has no slots to repack -- equal frames, equal counters --, and a frame below it."""
     from unity_webgpu_pathtracer_amd import scenes
     from unity_webgpu_pathtracer_amd.pathtracer import PathTracer
     s = scenes.material_zoo()
-    frames, stats = {}, {}
-    for schedule in (1, 4):
-        pt = PathTracer(s, width=512, height=512, samplesPerPass=2, schedule=schedule)
-        pt.set_stats_level(1)
-        pt.render_pass(pt.params(seed=0xD0C5))
-        frames[schedule], stats[schedule] = pt.readback(), pt.stats().as_dict()
-        rp = pt.repack_stats().as_dict()
-        print(f"[repack] default library, 512x512, schedule {schedule}: {rp}")
-        if schedule == 1:
-            assert rp["sequences"] == 1 and rp["repacks"] > 0 and rp["slotsMoved"] > 0, rp
-        else:
-            assert rp == dict(sequences=0, candidates=0, repacks=0, slotsMoved=0), rp
-        pt.close()
-    assert np.array_equal(frames[1].view(np.uint32), frames[4].view(np.uint32))
-    assert stats[1] == stats[4]
+    for width in (512, 528):            # 1,024 and 1,056 blocks of 256 slots: the scan's 1,024 threads own one block count each, and two
+        frames, stats = {}, {}
+        for schedule in (1, 4):
+            pt = PathTracer(s, width=width, height=512, samplesPerPass=2, schedule=schedule)
+            pt.set_stats_level(1)
+            pt.render_pass(pt.params(seed=0xD0C5))
+            frames[schedule], stats[schedule] = pt.readback(), pt.stats().as_dict()
+            rp = pt.repack_stats().as_dict()
+            print(f"[repack] default library, {width}x512, schedule {schedule}: {rp}")
+            if schedule == 1:
+                assert rp["sequences"] == 1 and rp["repacks"] > 0 and rp["slotsMoved"] > 0, rp
+            else:
+                assert rp == dict(sequences=0, candidates=0, repacks=0, slotsMoved=0), rp
+            pt.close()
+        assert np.array_equal(frames[1].view(np.uint32), frames[4].view(np.uint32)), width
+        assert stats[1] == stats[4], width
     pt = PathTracer(s, width=496, height=512, samplesPerPass=2, schedule=1)
     pt.render_pass(pt.params(seed=0xD0C5))
     pt.synchronize()

@@ -1,12 +1,11 @@
 // pt_adaptive_gather.hip — adaptive gathers on the MI355X (include/ptmi_plugin.h Part 19): the rule of
 // adaptive_gather_rule.h in kernels.  Select: one lane per active entry reads its 4-byte index and, through it, the 16 bytes of
-// accumulated irradiance, and decides; the survivors are compacted in the three steps of pt_lightmap.hip -- pt_ag_count (per
-// 256-entry block, which also counts the block's stops by reason), pt_ag_scan (one workgroup: the exclusive prefix of the block
-// counts, the totals), pt_ag_emit (a lane's rank is the block's base plus the earlier waves' counts plus the popcount of the
-// ballot below its lane; it writes the index and copies the receiver as two 16-byte loads and stores).  Fold and equalise are
-// one lane per entry with 16-byte accesses.  No atomics at all, so the same input gives the same bytes whatever the launch
-// geometry.
+// accumulated irradiance, and decides; the survivors are compacted in the three steps of pt_compact.h -- pt_ag_count (which also
+// counts the block's stops by reason), pt_ag_scan (which also sums them), pt_ag_emit (it writes the index and copies the receiver
+// as two 16-byte loads and stores).  Fold and equalise are one lane per entry with 16-byte accesses.  No atomics at all, so the
+// same input gives the same bytes whatever the launch geometry.
 #include "pt_adaptive_gather.h"
+#include "pt_compact.h"
 #include "adaptive_gather_rule.h"
 
 using namespace ptag;
@@ -28,68 +27,42 @@ __device__ __forceinline__ uint32_t decide(const PTAgSelectArgs& A, uint32_t k, 
 
 __global__ __launch_bounds__(256) void pt_ag_count(PTAgSelectArgs A, uint32_t blocks)
 {
+    __shared__ uint32_t waveCount[4][4];
     uint32_t idx;
     const uint32_t r = decide(A, blockIdx.x * 256u + threadIdx.x, idx);
-    const int kept = __syncthreads_count(r == kActive);
-    const int byThreshold = __syncthreads_count(r == kByThreshold);
-    const int byMax = __syncthreads_count(r == kByMaxSamples);
-    const int nonFinite = __syncthreads_count(r == kNonFinite);
-    if (threadIdx.x == 0u) {
-        A.blockCounts[blockIdx.x] = (uint32_t)kept;
-        A.blockCounts[(size_t)blocks + blockIdx.x] = (uint32_t)byThreshold;
-        A.blockCounts[(size_t)blocks * 2u + blockIdx.x] = (uint32_t)byMax;
-        A.blockCounts[(size_t)blocks * 3u + blockIdx.x] = (uint32_t)nonFinite;
+#pragma unroll
+    for (uint32_t q = 0; q < 4u; ++q) {                             // column q: the block's entries with decision q
+        uint32_t total;
+        compact_rank_in_block(r == q, waveCount[q], total);
+        if (threadIdx.x == 0u) A.blockCounts[(size_t)blocks * q + blockIdx.x] = total;
     }
 }
+static_assert(kActive == 0u && kByThreshold == 1u && kByMaxSamples == 2u && kNonFinite == 3u, "the columns of blockCounts and the words of totals");
 
-// One workgroup: thread k owns a contiguous run of block counts; the runs' sums are scanned across the workgroup, then every run
-// of the survivor counts is rewritten as the exclusive prefix.  The three stop counts are only summed.  At most 2^31 / 256 counts:
-// 8,192 per thread.  Every total is below 2^32.
+// The survivor counts become their exclusive prefix; the three stop counts, a stride of `blocks` apart, are only summed, each in
+// a walk of its own, one count at a time: four columns in one walk, or two counts at once, and the kernel takes 34 or 25 VGPRs,
+// not its 20 (tests/test_adaptive_gather.py).  At most 2^31 / 256 counts: 8,192 per thread.
 __global__ __launch_bounds__(1024) void pt_ag_scan(uint32_t* __restrict__ blockCounts, uint32_t blocks, uint64_t* __restrict__ totals)
 {
     __shared__ uint32_t waveSum[4][16];
-    const uint32_t per = (blocks + 1023u) / 1024u;
-    const uint32_t lo = threadIdx.x * per < blocks ? threadIdx.x * per : blocks, hi = lo + per < blocks ? lo + per : blocks;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t sum[4] = {0u, 0u, 0u, 0u};
-    for (int q = 0; q < 4; ++q)
-        for (uint32_t j = lo; j < hi; ++j) sum[q] += blockCounts[(size_t)blocks * q + j];
-    uint32_t incl[4] = {sum[0], sum[1], sum[2], sum[3]};           // inclusive scans within the wave
-    for (int off = 1; off < 64; off <<= 1)
-        for (int q = 0; q < 4; ++q) {
-            const uint32_t v = __shfl_up(incl[q], off, 64);
-            if (lane >= (uint32_t)off) incl[q] += v;
-        }
-    if (lane == 63u)
-        for (int q = 0; q < 4; ++q) waveSum[q][wave] = incl[q];
-    __syncthreads();
-    uint32_t before = 0;
-    for (uint32_t w = 0; w < wave; ++w) before += waveSum[0][w];
-    uint32_t running = before + incl[0] - sum[0];
-    for (uint32_t j = lo; j < hi; ++j) {
-        const uint32_t c = blockCounts[j];
-        blockCounts[j] = running;
-        running += c;
-    }
-    if (threadIdx.x < 4u) {
-        uint32_t all = 0;
-        for (uint32_t w = 0; w < 16u; ++w) all += waveSum[threadIdx.x][w];
-        totals[threadIdx.x] = all;
+    uint32_t all = compact_scan_blocks(blockCounts, blocks, waveSum[0], [](uint32_t, uint32_t) {});
+    if (threadIdx.x == 0u) totals[0] = all;
+    for (uint32_t q = 1u; q < 4u; ++q) {
+        uint32_t stops = 0u;
+#pragma clang loop vectorize(disable)
+        for (uint32_t b = threadIdx.x; b < blocks; b += 1024u) stops += blockCounts[(size_t)blocks * q + b];
+        compact_scan_threads(stops, waveSum[q], all);
+        if (threadIdx.x == 0u) totals[q] = all;
     }
 }
 
 __global__ __launch_bounds__(256) void pt_ag_emit(PTAgSelectArgs A)
 {
     __shared__ uint32_t waveCount[4];
-    uint32_t idx;
+    uint32_t idx, total;
     const bool kept = decide(A, blockIdx.x * 256u + threadIdx.x, idx) == kActive;
-    const unsigned long long mask = __ballot(kept);
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (lane == 0u) waveCount[wave] = (uint32_t)__popcll(mask);
-    __syncthreads();
+    const uint32_t rank = A.blockCounts[blockIdx.x] + compact_rank_in_block(kept, waveCount, total);
     if (!kept) return;
-    uint32_t rank = A.blockCounts[blockIdx.x] + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-    for (uint32_t w = 0; w < wave; ++w) rank += waveCount[w];
     if (rank >= A.activeCount) return;                              // cannot happen: the counts are of these very decisions
     const float4 r0 = A.recv[(size_t)idx * 2u], r1 = A.recv[(size_t)idx * 2u + 1u];
     A.outActive[rank] = idx;

@@ -3,10 +3,11 @@
 // ends in one atomicMin on the owner word per covered texel; a record whose box holds more than kLargeBox texels is put on a list
 // instead, and pt_lm_coverage_large spreads the 64x64-texel tiles of those boxes over all workgroups (a tile is rejected by the
 // edge values at its corner samples; a wave covers 32x2 texels per step, two 128-byte segments of owner words).  The owner map
-// is then compacted: pt_lm_count (per 256-texel block), pt_lm_scan (one workgroup), pt_lm_emit (one lane per texel: its rank in
-// the block by ballot, the receiver by chart_receiver).  Resolve: pt_lm_scatter and pt_lm_dilate.  The only atomics are integer
-// min and add on 4-byte words, so the same input gives the same bytes.
+// is then compacted in the three steps of pt_compact.h: pt_lm_count, pt_lm_scan, pt_lm_emit (one lane per texel: its place in the
+// list, the receiver by chart_receiver).  Resolve: pt_lm_scatter and pt_lm_dilate.  The only atomics are integer min and add on
+// 4-byte words, so the same input gives the same bytes.
 #include "pt_lightmap.h"
+#include "pt_compact.h"
 #include "chart_rule.h"
 
 using namespace ptchart;
@@ -112,39 +113,18 @@ __global__ __launch_bounds__(256) void pt_lm_coverage_large(PTChartArgs A)
 
 __global__ __launch_bounds__(256) void pt_lm_count(const uint32_t* __restrict__ owner, uint32_t n, uint32_t* __restrict__ blockBase)
 {
+    __shared__ uint32_t waveCount[4];
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    const int covered = i < n && owner[i] != kNoOwner;
-    const int total = __syncthreads_count(covered);
-    if (threadIdx.x == 0u) blockBase[blockIdx.x] = (uint32_t)total;
+    uint32_t total;
+    compact_rank_in_block(i < n && owner[i] != kNoOwner, waveCount, total);
+    if (threadIdx.x == 0u) blockBase[blockIdx.x] = total;
 }
 
-// One workgroup: thread k owns a contiguous run of block counts; the runs' sums are scanned across the workgroup, then every run
-// is rewritten as the exclusive prefix.  At most 2^26 / 256 counts: 256 per thread.
+// at most 2^26 / 256 counts: 256 per thread
 __global__ __launch_bounds__(1024) void pt_lm_scan(uint32_t* __restrict__ blockBase, uint32_t blocks, uint64_t* __restrict__ total)
 {
     __shared__ uint32_t waveSum[16];
-    const uint32_t per = (blocks + 1023u) / 1024u;
-    const uint32_t lo = threadIdx.x * per < blocks ? threadIdx.x * per : blocks, hi = lo + per < blocks ? lo + per : blocks;
-    uint32_t sum = 0;
-    for (uint32_t j = lo; j < hi; ++j) sum += blockBase[j];
-    uint32_t incl = sum;                                            // inclusive scan within the wave
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t v = __shfl_up(incl, off, 64);
-        if ((threadIdx.x & 63u) >= (uint32_t)off) incl += v;
-    }
-    if ((threadIdx.x & 63u) == 63u) waveSum[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-    for (uint32_t w = 0; w < 16u; ++w) {
-        if (w < (threadIdx.x >> 6)) before += waveSum[w];
-        all += waveSum[w];
-    }
-    uint32_t running = before + incl - sum;
-    for (uint32_t j = lo; j < hi; ++j) {
-        const uint32_t c = blockBase[j];
-        blockBase[j] = running;
-        running += c;
-    }
+    const uint32_t all = compact_scan_blocks(blockBase, blocks, waveSum, [](uint32_t, uint32_t) {});
     if (threadIdx.x == 0u) *total = all;
 }
 
@@ -154,13 +134,9 @@ __global__ __launch_bounds__(256) void pt_lm_emit(PTChartArgs A, uint32_t* __res
     const uint32_t i = blockIdx.x * 256u + threadIdx.x, n = A.width * A.height;
     const uint32_t p = i < n ? A.owner[i] : kNoOwner;
     const bool covered = p < A.triCount;
-    const unsigned long long mask = __ballot(covered);
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (lane == 0u) waveCount[wave] = (uint32_t)__popcll(mask);
-    __syncthreads();
+    uint32_t total;
+    const uint32_t k = A.blockBase[blockIdx.x] + compact_rank_in_block(covered, waveCount, total);
     if (!covered) return;
-    uint32_t k = A.blockBase[blockIdx.x] + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-    for (uint32_t w = 0; w < wave; ++w) k += waveCount[w];
     const uint32_t t = A.recOfPrim[p];
     if (t >= A.triCount) return;                                    // cannot happen: the coverage kernel wrote it
     const float4 r0 = A.tris[(size_t)t * 3u], r1 = A.tris[(size_t)t * 3u + 1u], r2 = A.tris[(size_t)t * 3u + 2u];

@@ -6,15 +6,10 @@
 #include "pt_launch.h"
 #include "pt_wf_state.h"
 #include "pt_wf_shade.h"
+#include "pt_compact.h"
 #include "repack_rule.h"
 
 namespace {
-
-// number of set bits of a wave mask below this lane
-PT_DEV uint32_t rank_below(unsigned long long m)
-{
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
 
 // ------------------------------------------------------------------------------------------
 // The four kernels of a repack candidate.
@@ -43,51 +38,29 @@ static_assert(PT_REPACK_STATE_DONE == PS_DONE && PT_REPACK_BLOCK == 256u, "repac
 PT_DEV uint32_t* rp_u32(const PTWfBuffers& B, uint32_t k) { return (uint32_t*)((float4*)B.rpTemp + (size_t)PT_F4_HIT * B.rpCapacity) + (size_t)k * B.rpCapacity; }
 static_assert(PT_F4_HIT == 12u && PT_F4_HIT * 16u + 3u * 4u == PT_WF_REPACK_SLOT_BYTES, "the moved state is the twelve float4 planes before PT_F4_HIT and three words");
 
-// rank of the lane's slot among the live slots of its 256-slot block, and the block's live count (every lane of the block calls it)
-PT_DEV uint32_t rp_rank_in_block(bool live, uint32_t* s_wave, uint32_t& blockLive)
-{
-    const unsigned long long m = __ballot(live);
-    const uint32_t w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63u) == 0u) s_wave[w] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t before = 0u;
-    for (uint32_t i = 0; i < 4u; ++i) if (i < w) before += s_wave[i];
-    blockLive = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-    return before + rank_below(m);
-}
-
+// count and scan: the first two steps of pt_compact.h over the live slots
 __global__ __launch_bounds__(256) void pt_wf_repack_count(PTWfBuffers B)
 {
     __shared__ uint32_t s_wave[4];
     const uint32_t slot = blockIdx.x * 256u + threadIdx.x;                 // numSlots is a multiple of 256
     uint32_t blockLive;
-    rp_rank_in_block(ptrepack::slot_live(B.flags[slot]), s_wave, blockLive);
+    compact_rank_in_block(ptrepack::slot_live(B.flags[slot]), s_wave, blockLive);
     if (threadIdx.x == 0u) B.rpPrefix[blockIdx.x] = blockLive;
 }
 
-// one workgroup of 1024: thread t owns `per` consecutive blocks
+// ... which also finds the highest live block, decides, and counts for PTGetRepackStats
 __global__ __launch_bounds__(1024) void pt_wf_repack_scan(PTWfBuffers B, uint32_t fillNum, uint32_t fillDen, uint32_t firstOfSequence, unsigned long long* stats)
 {
     __shared__ uint32_t s_sum[16], s_hi[16];
-    const uint32_t nb = B.numSlots >> 8, t = threadIdx.x, lane = t & 63u, w = t >> 6;
-    const uint32_t per = (nb + 1023u) / 1024u;
-    const uint32_t b0 = t * per, b1 = b0 + per < nb ? b0 + per : nb;
-    uint32_t sum = 0u, hi = 0u;                                            // hi: highest live block + 1 (0: none)
-    for (uint32_t b = b0; b < b1; ++b) { const uint32_t c = B.rpPrefix[b]; sum += c; if (c) hi = b + 1u; }
-    uint32_t incl = sum;                                                   // inclusive prefix within the wave
+    uint32_t hi = 0u;                                                      // highest live block + 1 (0: none)
+    const uint32_t L = compact_scan_blocks(B.rpPrefix, B.numSlots >> 8, s_sum, [&](uint32_t b, uint32_t c) { if (c) hi = b + 1u; });
 #pragma unroll
-    for (uint32_t off = 1u; off < 64u; off <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)incl, off, 64); if (lane >= off) incl += o; }
-    uint32_t whi = hi;
-#pragma unroll
-    for (uint32_t off = 32u; off > 0u; off >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)whi, (int)off, 64); whi = o > whi ? o : whi; }
-    if (lane == 63u) s_sum[w] = incl;
-    if (lane == 0u) s_hi[w] = whi;
+    for (uint32_t off = 32u; off > 0u; off >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)hi, (int)off, 64); hi = o > hi ? o : hi; }
+    if ((threadIdx.x & 63u) == 0u) s_hi[threadIdx.x >> 6] = hi;
     __syncthreads();
-    uint32_t before = 0u, L = 0u, top = 0u;
-    for (uint32_t i = 0; i < 16u; ++i) { if (i < w) before += s_sum[i]; L += s_sum[i]; top = s_hi[i] > top ? s_hi[i] : top; }
-    uint32_t running = before + incl - sum;
-    for (uint32_t b = b0; b < b1; ++b) { const uint32_t c = B.rpPrefix[b]; B.rpPrefix[b] = running; running += c; }
-    if (t == 0u) {
+    if (threadIdx.x == 0u) {
+        uint32_t top = 0u;
+        for (uint32_t i = 0; i < 16u; ++i) top = s_hi[i] > top ? s_hi[i] : top;
         const uint32_t E = ptrepack::extent_of(top != 0u, top - 1u);
         const bool go = ptrepack::decide(L, E, B.rpCapacity, fillNum, fillDen);
         B.rpCtl[ptrepack::PT_REPACK_GO] = go ? 1u : 0u;
@@ -134,7 +107,7 @@ __global__ __launch_bounds__(256) void pt_wf_repack_out(PTWfBuffers B)
     const uint32_t f = B.flags[slot];
     const bool live = ptrepack::slot_live(f);
     uint32_t blockLive;
-    const uint32_t rank = rp_rank_in_block(live, s_wave, blockLive);
+    const uint32_t rank = compact_rank_in_block(live, s_wave, blockLive);
     if (!live) return;
     const uint32_t d = ptrepack::destination(B.rpPrefix[blockIdx.x], rank);
     if (d >= B.rpCapacity) return;                                         // never: the decision admits L <= capacity only

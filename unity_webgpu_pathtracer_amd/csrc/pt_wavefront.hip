@@ -22,6 +22,7 @@
 #include "pt_launch.h"
 #include "pt_wf_state.h"
 #include "pt_wf_shade.h"
+#include "pt_compact.h"                        // rank_below
 #include "repack_rule.h"
 #include <type_traits>
 
@@ -127,11 +128,6 @@ static_assert(PT_WF_RANGE >= 64u && (PT_WF_RANGE & (PT_WF_RANGE - 1u)) == 0u && 
 // texture-address path and counts against both memory counters.
 typedef volatile __attribute__((address_space(3))) uint32_t* pt_lds_u32;
 typedef volatile __attribute__((address_space(3))) uint16_t* pt_lds_u16;
-// number of set bits of a wave mask below this lane (v_mbcnt: no per-lane 64-bit "lanes below me" mask to keep in registers)
-PT_DEV uint32_t rank_below(unsigned long long m)
-{
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
 
 // Result stores of the trace kernels.  The empty asm pins the address arithmetic (and the constant miss record) to the
 // store instead of letting it be hoisted into registers that live across the whole traversal loop (64-VGPR budget).
