@@ -1814,6 +1814,131 @@ PT_API int PTReflectionPrefilterHost(const PTReflectionTexel* base, uint64_t cou
 PT_API int PTReflectionLookupHost(const PTReflectionTexel* maps, uint64_t probeCount, uint32_t res, uint32_t levels, const PTProbe* probes,
                                   const PTReflectionBox* boxes, const PTReflectionQuery* queries, uint64_t count, PTReflectionTexel* out);
 
+/* =====================================================================================================================
+ * Part 21: shading from the bakes.  Parts 13 to 20 bake diffuse and glossy light; this part uses it: the first hit of a ray is
+ * shaded from a probe volume (Parts 16, 18) and reflection probes (Part 20) with the split-sum approximation -- a view of the
+ * scene lit by the bakes, a way to check a bake by eye, a preview while the path tracer converges.  An addition beside the
+ * reference's ABI, detected by symbol; PTGetVersion is unchanged.
+ *
+ * Left out: transmission, clearcoat, sheen, anisotropy and alpha cut-outs are ignored (every hit is opaque, the specular lobe
+ * isotropic GGX over a Lambert base); one reflection probe per point, no blend; a miss is black; lights are seen only through the
+ * bakes.
+ *
+ * The rule (bit-exact; shade_rule.h is its one definition: the kernels, the host twins and tests/shade_ref.py evaluate it; every
+ * fp32 operator below is one IEEE binary32 operation in the order written, no fma; only + - * /, sqrt and comparisons).
+ *  1. The DFG table: res x res entries {A, B} of two floats, res in {16, 32, 64}, entry j * res + i.
+ *     mu = ((float)i + 0.5f) / (float)res is N.V; rho = ((float)j + 0.5f) / (float)res is perceptual roughness; alpha = rho * rho
+ *     (Part 20's level roughness); a2 = alpha * alpha.  V = (sqrt(1.0f - mu * mu), 0, mu).
+ *     smith_g(c, alpha): a = alpha * alpha; b = c * c; (2.0f * c) / (c + sqrt((a + b) - a * b)) -- the render's.
+ *     Sample (p, q), p radial and q azimuth, both 0 ... 63: xi = ((float)p + 0.5f) / 64.0f;
+ *     c2 = (1.0f - xi) / (1.0f + (a2 - 1.0f) * xi); s = sqrt(1.0f - c2); H = (s * C[q], s * S[q], sqrt(c2)), where C[q] and S[q]
+ *     are float literals: cos and sin of 2 pi (q + 0.5) / 64 in float64, rounded to float.  vh = V.x * H.x + V.z * H.z;
+ *     L.z = (2.0f * vh) * H.z - V.z; nl = L.z.  The sample counts only if nl > 0 and vh > 0: G = smith_g(mu, alpha) *
+ *     smith_g(nl, alpha); gv = (G * vh) / (H.z * mu); m = 1.0f - vh; m2 = m * m; Fc = (m2 * m2) * m; a = a + (1.0f - Fc) * gv;
+ *     b = b + Fc * gv.  Lane q sums its 64 radial samples in ascending p from +0.0f; the 64 lane partials are folded by Part 15's
+ *     tree (h = 32, 16, ..., 1: v[l] = v[l] + v[l + h] for l < h); A = a / 4096.0f, B = b / 4096.0f.
+ *  2. Terms of entry i from its ray, hit and surface record.  prim == 0xFFFFFFFF (a miss): material, terms and receiver are all
+ *     zero bits but material.flags = PT_SHADE_MISS and material.materialIndex = 0xFFFFFFFF; the query is zero but probe =
+ *     0xFFFFFFFF.  Otherwise the material record is what the render's material fetch returns for the hit (textures included):
+ *     baseColor, metallic, emission, roughness (the render's alpha, >= 0.001), occlusion, opacity, the material index, flags 0.
+ *     A surface record whose materialIndex is not below the scene's material count is taken as a miss.
+ *     len = sqrt((D.x * D.x + D.y * D.y) + D.z * D.z); Vd = (-D) / len, per component.  d = (N.x * Vd.x + N.y * Vd.y) + N.z * Vd.z
+ *     with N = PTRaySurface.normal; if d < 0, N = -N and d is taken again from the new N.  nDotV = max(d, 1e-4f).
+ *     R = (2.0f * d) * N - Vd.  diffuse = baseColor * (1.0f - metallic); f0 = 0.04f + metallic * (baseColor - 0.04f);
+ *     rho = sqrt(roughness); emission and occlusion are copied.  The receiver is {position, seed 0, N, 0}; the query is
+ *     {position, rho, R, probe}.
+ *     Probe choice.  d2_k = (v.x * v.x + v.y * v.y) + v.z * v.z with v = position - probe_k.  With boxes: among the probes k, in
+ *     ascending k, with bmin_k[a] <= position[a] <= bmax_k[a] on all three axes, the first one, then any with d2_k < the best so
+ *     far (a tie keeps the lower index).  If none was found, or without boxes: the same over all probes.  probeCount == 0 gives
+ *     0xFFFFFFFF, which Part 20 step 4a answers with zeros.
+ *  3. Compose.  An entry whose terms have nDotV > 0 false (a miss) gives {0, 0, 0, 0}.  Otherwise, on each table axis with
+ *     v = nDotV (x) and v = rho (y): x = v * (float)res - 0.5f; x = x > 0 ? x : 0 (a NaN lands on 0); x = x < (float)(res - 1) ? x :
+ *     (float)(res - 1); x0 = min((uint32_t)x, res - 2); fx = x - (float)x0.  (A, B) = the lerp along y of the lerps along x of the
+ *     entries (x0, y0), (x0 + 1, y0) and (x0, y0 + 1), (x0 + 1, y0 + 1); every lerp is p + f * (q - p).  Per channel c:
+ *     out[c] = emission[c] + occlusion * ((diffuse[c] * E[c]) * 0.31830988618379067f + spec[c] * (f0[c] * A + B)), E the
+ *     PTIrradiance's rgb and spec the PTReflectionTexel's; out[3] = 1.0f.
+ *  4. PTShadeBaked is steps 2 and 3 around Part 16's lookup (Part 18's when dPlacement is given) of the receiver and Part 20's
+ *     lookup of the query, one lane per entry, nothing in between stored: it equals PTShadeSurfaces, PTProbeGridIrradiancePlaced,
+ *     PTReflectionLookup and PTShadeCompose bit for bit.
+ *  5. PTShadeBakedFrame: for pixel (x, y) the ray of Part 4's guides at one sample per pixel -- origin CamToWorld * (0, 0, 0, 1),
+ *     direction normalize(CamToWorld * (CamInvProj * (u, v, 0, 1)).xyz0) with u = ((float)x + 0.5f) / (float)W * 2.0f - 1.0f, v
+ *     likewise from y and H, tmax PT_FAR_PLANE --, PTTraceRays(PT_QUERY_CLOSEST | PT_QUERY_SURFACE), PTShadeBaked; pixel y * W + x
+ *     of dOut.  dOutRays (may be NULL) receives the W * H PTRay entries.  The rays, hits and surface records go through scratch the
+ *     context keeps and grows (96 bytes per pixel; kept across PTSetScene, freed by PTDestroy).
+ *
+ * Device pointers are 16-byte aligned (the DFG table 8); the calls are stream-ordered on the context's stream and nothing past
+ * `count` is written.  Errors: PT_ERR_INVALID_ARG for a NULL or misaligned pointer, a DFG res outside {16, 32, 64}, a map res or
+ * levels outside Part 20's ranges, a grid Part 16 refuses, PT_GRID_VISIBILITY without depth, boxes without probes;
+ * PT_ERR_NO_SCENE for PTShadeSurfaces, PTShadeBaked and PTShadeBakedFrame before PTSetScene.  count == 0 returns PT_OK and
+ * launches nothing.  Arguments are checked before the context is used.  No CPU fallback.
+ * The host twins take no context and no GPU; they return 1, or 0 with PTGetBVHBuildError() set.  PTShadeTermsHost is step 2 after
+ * the material fetch: it takes the material records PTShadeSurfaces returned.
+ * ===================================================================================================================== */
+#define PT_SHADE_MISS 1u            /* PTShadeMaterial.flags */
+
+typedef struct PTShadeDFG {         /* 8 bytes: scale and bias of F0 */
+    float    a, b;
+} PTShadeDFG;
+
+typedef struct PTShadeMaterial {    /* 48 bytes: three 16-byte stores */
+    float    baseColor[3]; float    metallic;
+    float    emission[3];  float    roughness;       /* the render's alpha */
+    float    occlusion;    float    opacity;  uint32_t materialIndex;  uint32_t flags;       /* PT_SHADE_MISS */
+} PTShadeMaterial;
+
+typedef struct PTShadeTerms {       /* 48 bytes: three 16-byte loads */
+    float    diffuse[3];   float    rho;             /* perceptual roughness */
+    float    f0[3];        float    nDotV;           /* >= 1e-4 on a hit, 0 on a miss */
+    float    emission[3];  float    occlusion;
+} PTShadeTerms;
+
+typedef struct PTShadeInputs {      /* 120 bytes; a host struct, passed by pointer */
+    PTProbeGrid grid;                           /* Part 16; flags and normalBias as PTProbeGridIrradiance reads them */
+    const PTProbeCoeffs*     dSH;
+    const PTProbeDepthMap*   dDepth;            /* may be NULL without PT_GRID_VISIBILITY */
+    const PTProbePlacement*  dPlacement;        /* may be NULL: Part 16's lookup */
+    const PTReflectionTexel* dMaps;             /* probeCount whole maps; may be NULL with probeCount == 0 */
+    const PTProbe*           dProbes;           /* probeCount entries; may be NULL with probeCount == 0 */
+    const PTReflectionBox*   dBoxes;            /* may be NULL: no box rule in the choice, no box projection */
+    const PTShadeDFG*        dDFG;              /* dfgRes * dfgRes entries */
+    uint32_t probeCount, res, levels;           /* Part 20's layout */
+    uint32_t dfgRes;
+} PTShadeInputs;
+
+#ifdef __cplusplus
+static_assert(sizeof(PTShadeDFG) == 8, "PTShadeDFG is 8 bytes");
+static_assert(sizeof(PTShadeMaterial) == 48, "PTShadeMaterial is 48 bytes");
+static_assert(sizeof(PTShadeTerms) == 48, "PTShadeTerms is 48 bytes");
+static_assert(sizeof(PTShadeInputs) == 120, "PTShadeInputs is 120 bytes");
+#else
+_Static_assert(sizeof(PTShadeDFG) == 8, "PTShadeDFG is 8 bytes");
+_Static_assert(sizeof(PTShadeMaterial) == 48, "PTShadeMaterial is 48 bytes");
+_Static_assert(sizeof(PTShadeTerms) == 48, "PTShadeTerms is 48 bytes");
+_Static_assert(sizeof(PTShadeInputs) == 120, "PTShadeInputs is 120 bytes");
+#endif
+
+/* dOut: res * res entries. */
+PT_API int PTBakeDFG(PTContext* ctx, uint32_t res, PTShadeDFG* dOut);
+/* dRays, dHits, dSurface: what PTTraceRays(PT_QUERY_CLOSEST | PT_QUERY_SURFACE) read and wrote; dProbes, dBoxes: probeCount entries
+ * or NULL (boxes need probes); each output has count entries or is NULL. */
+PT_API int PTShadeSurfaces(PTContext* ctx, const PTRay* dRays, const PTRayHit* dHits, const PTRaySurface* dSurface, uint64_t count, const PTProbe* dProbes,
+                           const PTReflectionBox* dBoxes, uint32_t probeCount, PTShadeMaterial* dOutMaterial, PTShadeTerms* dOutTerms,
+                           PTReceiver* dOutReceivers, PTReflectionQuery* dOutQueries);
+/* dOut: count float4 entries. */
+PT_API int PTShadeCompose(PTContext* ctx, const PTShadeTerms* dTerms, const PTIrradiance* dIrradiance, const PTReflectionTexel* dReflection, uint64_t count,
+                          const PTShadeDFG* dDFG, uint32_t dfgRes, float* dOut);
+PT_API int PTShadeBaked(PTContext* ctx, const PTShadeInputs* inputs, const PTRay* dRays, const PTRayHit* dHits, const PTRaySurface* dSurface, uint64_t count,
+                        float* dOut);
+/* dOut: OutputWidth * OutputHeight float4 entries; dOutRays: as many PTRay entries, or NULL. */
+PT_API int PTShadeBakedFrame(PTContext* ctx, const PTFrameParams* params, const PTShadeInputs* inputs, float* dOut, PTRay* dOutRays);
+/* host twins, no GPU */
+PT_API int PTBakeDFGHost(uint32_t res, PTShadeDFG* out);
+PT_API int PTShadeTermsHost(const PTShadeMaterial* materials, const PTRay* rays, const PTRaySurface* surface, uint64_t count, const PTProbe* probes,
+                            const PTReflectionBox* boxes, uint32_t probeCount, PTShadeTerms* outTerms, PTReceiver* outReceivers,
+                            PTReflectionQuery* outQueries);
+PT_API int PTShadeComposeHost(const PTShadeTerms* terms, const PTIrradiance* irradiance, const PTReflectionTexel* reflection, uint64_t count,
+                              const PTShadeDFG* dfg, uint32_t dfgRes, float* out);
+
 /* Text of the last error on the calling thread ("" if none). */
 PT_API const char* PTGetLastError(void);
 /* Library/ABI version: (major << 16) | minor. */

@@ -394,6 +394,20 @@ class PTReflectionBox(C.Structure):
 assert C.sizeof(PTReflectionTexel) == 16 and C.sizeof(PTReflectionQuery) == 32 and C.sizeof(PTReflectionBox) == 32
 
 
+# ---- shading from the bakes (include/ptmi_plugin.h Part 21)
+PT_SHADE_MISS = 1
+PT_SHADE_DFG_RES = (16, 32, 64)
+
+
+class PTShadeInputs(C.Structure):
+    _fields_ = [("grid", PTProbeGrid), ("dSH", C.c_void_p), ("dDepth", C.c_void_p), ("dPlacement", C.c_void_p), ("dMaps", C.c_void_p),
+                ("dProbes", C.c_void_p), ("dBoxes", C.c_void_p), ("dDFG", C.c_void_p), ("probeCount", C.c_uint32), ("res", C.c_uint32),
+                ("levels", C.c_uint32), ("dfgRes", C.c_uint32)]
+
+
+assert C.sizeof(PTShadeInputs) == 120
+
+
 # ---- lightmap charts (include/ptmi_plugin.h Part 14)
 PT_CHART_MAX_SIZE = 8192
 PT_CHART_MAX_DILATE = 16

@@ -22,6 +22,7 @@
 #include "lmfilter_rule.h"
 #include "adaptive_gather_rule.h"
 #include "reflection_rule.h"
+#include "shade_rule.h"
 #include "repack_rule.h"
 #include "ptmi_plugin.h"
 
@@ -309,6 +310,28 @@ PT_API int PTRepackPlanHost(const uint32_t* flags, uint32_t numSlots, uint32_t c
         return 0;
     }
     outPlan[0] = plan.go; outPlan[1] = plan.live; outPlan[2] = plan.extent;
+    g_buildError.clear();
+    return 1;
+}
+// Shading from the bakes on the host (shade_host.cpp; Part 21 has the rule).  No GPU involved.
+PT_API int PTBakeDFGHost(uint32_t res, PTShadeDFG* out)
+{
+    if (!ptshade::bake_dfg_host(res, out, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+PT_API int PTShadeTermsHost(const PTShadeMaterial* materials, const PTRay* rays, const PTRaySurface* surface, uint64_t count, const PTProbe* probes,
+                            const PTReflectionBox* boxes, uint32_t probeCount, PTShadeTerms* outTerms, PTReceiver* outReceivers,
+                            PTReflectionQuery* outQueries)
+{
+    if (!ptshade::terms_host(materials, rays, surface, count, probes, boxes, probeCount, outTerms, outReceivers, outQueries, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+PT_API int PTShadeComposeHost(const PTShadeTerms* terms, const PTIrradiance* irradiance, const PTReflectionTexel* reflection, uint64_t count,
+                              const PTShadeDFG* dfg, uint32_t dfgRes, float* out)
+{
+    if (!ptshade::compose_host(terms, irradiance, reflection, count, dfg, dfgRes, out, g_buildError)) return 0;
     g_buildError.clear();
     return 1;
 }

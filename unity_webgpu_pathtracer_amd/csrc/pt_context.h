@@ -259,6 +259,11 @@ struct PTContext {
         DeviceBuffer rays, radiance;
         HostStaging host;
     } reflection;
+    // shading from the bakes (PTShadeBakedFrame): the rays, hit and surface records of a frame, 96 bytes per pixel, used in stream
+    // order on the context stream, kept across PTSetScene
+    struct Shade {
+        DeviceBuffer rays, hits, surfaces;
+    } shade;
     // lightmap charts (PTRasterizeChart / PTResolveLightmap): grown on demand, kept across PTSetScene
     struct Lightmap {
         DeviceBuffer owner;                     // 4 B per texel: the owner map

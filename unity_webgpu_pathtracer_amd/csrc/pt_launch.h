@@ -325,6 +325,21 @@ hipError_t pt_launch_refl_prefilter(const PTReflectionTexel* base, uint32_t prob
 // probes and boxes may be null (boxes only with probes)
 hipError_t pt_launch_refl_lookup(const PTReflectionTexel* maps, uint64_t probeCount, uint32_t res, uint32_t levels, const PTProbe* probes,
                                  const PTReflectionBox* boxes, const PTReflectionQuery* queries, uint32_t count, PTReflectionTexel* out, hipStream_t stream);
+// ---- shading from the bakes (include/ptmi_plugin.h Part 21; pt_shade_baked.hip) ----
+// res is 16, 32 or 64
+hipError_t pt_launch_shade_dfg(uint32_t res, PTShadeDFG* out, hipStream_t stream);
+// rays, hits, surfaces: a closest-hit query's with surface records; probes and boxes may be null (boxes only with probes, probes
+// only with probeCount == 0); every output may be null
+hipError_t pt_launch_shade_surfaces(const DScene& S, const PTRay* rays, const PTRayHit* hits, const PTRaySurface* surfaces, uint32_t count, const PTProbe* probes,
+                                    const PTReflectionBox* boxes, uint32_t probeCount, PTShadeMaterial* outMaterial, PTShadeTerms* outTerms,
+                                    PTReceiver* outReceivers, PTReflectionQuery* outQueries, hipStream_t stream);
+hipError_t pt_launch_shade_compose(const PTShadeTerms* terms, const PTIrradiance* irradiance, const PTReflectionTexel* reflection, uint32_t count,
+                                   const PTShadeDFG* dfg, uint32_t dfgRes, float4* out, hipStream_t stream);
+// the fused call: in.grid has passed ptvol::check_grid, in.res and in.levels ptrefl::check_layout; in.dPlacement picks the kernel
+hipError_t pt_launch_shade_baked(const DScene& S, const PTShadeInputs& in, const PTRay* rays, const PTRayHit* hits, const PTRaySurface* surfaces, uint32_t count,
+                                 float4* out, hipStream_t stream);
+// pixels [first, first + count) of the frame P describes: the guides' ray at one sample per pixel, tmax PT_FAR_PLANE
+hipError_t pt_launch_shade_frame_rays(const PTFrameParams& P, uint32_t first, uint32_t count, PTRay* rays, hipStream_t stream);
 #ifndef PT_WF_FUSED_GROUPS
 #define PT_WF_FUSED_GROUPS 2u   // schedule 4: groups of 64 path contexts a persistent wave owns (power of two <= 4: numSlots is a multiple of 256).
                                 // Sponza-class 1080p / 8 spp, one pass in flight: 1: 29.9 ms, 2: 25.2, 4: 27.9, 8: 31.4

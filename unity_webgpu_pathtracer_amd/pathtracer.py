@@ -765,6 +765,127 @@ class PathTracer:
             d_boxes = torch.from_numpy(plugin.reflection_box_rows(lo, hi)).to(dev)
         return ReflectionProbes(self, res, levels, maps, d_rows, d_boxes)
 
+    # ---- shading from the bakes (include/ptmi_plugin.h Part 21)
+    def _to_device(self, x, cols=None):
+        """(tensor on this context's device, was numpy): float32, contiguous, (n, cols) when cols is given"""
+        import torch
+        as_numpy = isinstance(x, np.ndarray)
+        t = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(torch.device(f"cuda:{self.device}")) if as_numpy else x.contiguous()
+        assert t.dtype == torch.float32 and (cols is None or (t.dim() == 2 and t.shape[1] == cols)), (t.dtype, t.shape, cols)
+        return t, as_numpy
+
+    def bake_dfg(self, res: int = 32):
+        """PTBakeDFG: the split-sum table of the specular BRDF on the GPU, a (res, res, 2) float32 device tensor -- row j =
+        perceptual roughness (j + 0.5) / res, column i = N.V (i + 0.5) / res, {scale, bias} of F0; plugin.bake_dfg is its twin."""
+        import torch
+        dev = torch.device(f"cuda:{self.device}")
+        ok = int(res) in abi.PT_SHADE_DFG_RES                                 # (the call refuses another res itself)
+        out = torch.empty((res, res, 2) if ok else (1, 1, 2), dtype=torch.float32, device=dev)
+        with self._ordered(dev):
+            plugin.check(self.lib.PTBakeDFG(self.ctx, int(res), out.data_ptr()))
+        return out
+
+    def shade_surfaces(self, rays, hits, surfaces, probes=None, boxes=None):
+        """PTShadeSurfaces: from what trace_rays(rays, surface=True) took and returned to what the bakes are asked -- the material
+        record the render's own fetch gives for every hit (n, 12), the shading terms (n, 12), the PTReceiver rows (n, 8) a probe
+        volume takes and the PTReflectionQuery rows (n, 8) reflection probes take.  probes: (k, 4) PTProbe rows or (k, 3)
+        positions, or None; boxes: (k, 8) PTReflectionBox rows or None.  numpy in, numpy out; device tensors in, device tensors
+        out."""
+        import torch
+        r, as_numpy = self._to_device(rays, 8)
+        h, _ = self._to_device(hits, 4)
+        s, _ = self._to_device(surfaces, 12)
+        n, dev = r.shape[0], r.device
+        assert h.shape[0] == n and s.shape[0] == n, (r.shape, h.shape, s.shape)
+        pr = None
+        if probes is not None:
+            pr = self._to_device(probes if probes.shape[1] == 4 else self._probes(probes, None), 4)[0]
+        bx = None if boxes is None else self._to_device(boxes, 8)[0]
+        k = 0 if pr is None else pr.shape[0]
+        outs = [torch.empty((n, c), dtype=torch.float32, device=dev) for c in (12, 12, 8, 8)]
+        if n:
+            with self._ordered(dev):
+                plugin.check(self.lib.PTShadeSurfaces(self.ctx, r.data_ptr(), h.data_ptr(), s.data_ptr(), n, pr.data_ptr() if k else None,
+                                                      None if bx is None else bx.data_ptr(), k, *[o.data_ptr() for o in outs]))
+        return tuple(o.cpu().numpy() for o in outs) if as_numpy else tuple(outs)
+
+    def shade_compose(self, terms, irradiance, reflection, dfg):
+        """PTShadeCompose: emission + occlusion * (diffuse * E / pi + spec * (f0 * A + B)) per entry, (A, B) bilinear in the DFG
+        table at (N.V, roughness).  terms (n, 12), irradiance (n, 4), reflection (n, 4), dfg (res, res, 2).  Returns (n, 4): rgb and
+        1, zeros for a miss.  numpy in, numpy out; device tensors in, a device tensor out."""
+        import torch
+        t, as_numpy = self._to_device(terms, 12)
+        e, _ = self._to_device(irradiance, 4)
+        s, _ = self._to_device(reflection, 4)
+        d, _ = self._to_device(dfg)
+        n = t.shape[0]
+        assert e.shape[0] == n and s.shape[0] == n and d.dim() == 3 and d.shape[0] == d.shape[1] and d.shape[2] == 2, (t.shape, e.shape, s.shape, d.shape)
+        out = torch.empty((n, 4), dtype=torch.float32, device=t.device)
+        if n:
+            with self._ordered(t.device):
+                plugin.check(self.lib.PTShadeCompose(self.ctx, t.data_ptr(), e.data_ptr(), s.data_ptr(), n, d.data_ptr(), d.shape[0], out.data_ptr()))
+        return out.cpu().numpy() if as_numpy else out
+
+    def _shade_inputs(self, volume, reflections, dfg, wrap=True, visibility=True, normal_bias=None, placement=True, boxes=True):
+        """(PTShadeInputs, the tensors it points into) from a ProbeVolume, a ReflectionProbes or None (no probes: the specular term
+        reads zeros) and a DFG table or None (a 32 x 32 table, baked once per context)"""
+        if dfg is None:
+            if getattr(self, "_dfg", None) is None:
+                self._dfg = self.bake_dfg(32)
+            dfg = self._dfg
+        d, _ = self._to_device(dfg)
+        s = abi.PTShadeInputs()
+        s.grid = abi.PTProbeGrid.from_buffer_copy(volume.grid)
+        s.grid.flags = (abi.PT_GRID_WRAP if wrap else 0) | (abi.PT_GRID_VISIBILITY if visibility else 0)
+        s.grid.normalBias = volume.default_normal_bias() if normal_bias is None else float(normal_bias)
+        s.dSH, s.dDepth = volume._rows.data_ptr(), volume._depth.data_ptr()
+        s.dPlacement = volume.placement.data_ptr() if placement and volume.placement is not None else None
+        s.res, s.levels = 8, 2
+        if reflections is not None and reflections.probe_rows.shape[0]:
+            s.dMaps, s.dProbes = reflections.maps.data_ptr(), reflections.probe_rows.data_ptr()
+            s.dBoxes = reflections.box_rows.data_ptr() if boxes and reflections.box_rows is not None else None
+            s.probeCount, s.res, s.levels = reflections.probe_rows.shape[0], reflections.res, reflections.levels
+        s.dDFG, s.dfgRes = d.data_ptr(), d.shape[0]
+        return s, (d, volume, reflections)
+
+    def shade_baked(self, rays, hits, surfaces, volume, reflections=None, dfg=None, **options):
+        """PTShadeBaked: the first hits of trace_rays(rays, surface=True) shaded from a ProbeVolume and a ReflectionProbes in one
+        kernel -- the material fetch, the terms, the volume's lookup (the placed one for a volume with a placement), the nearest
+        reflection probe's lookup (the nearest whose box holds the point, with boxes) and the compose step, bit for bit what
+        shade_surfaces, volume.irradiance, reflections.lookup and shade_compose give one after the other.  options: wrap,
+        visibility, normal_bias as ProbeVolume.irradiance takes them; placement=False, boxes=False leave those out.  Returns
+        (n, 4) float32: rgb and 1, zeros for a miss.  numpy in, numpy out; device tensors in, a device tensor out."""
+        import torch
+        r, as_numpy = self._to_device(rays, 8)
+        h, _ = self._to_device(hits, 4)
+        sf, _ = self._to_device(surfaces, 12)
+        n = r.shape[0]
+        assert h.shape[0] == n and sf.shape[0] == n, (r.shape, h.shape, sf.shape)
+        s, keep = self._shade_inputs(volume, reflections, dfg, **options)
+        out = torch.empty((n, 4), dtype=torch.float32, device=r.device)
+        if n:
+            with self._ordered(r.device):
+                plugin.check(self.lib.PTShadeBaked(self.ctx, C.byref(s), r.data_ptr(), h.data_ptr(), sf.data_ptr(), n, out.data_ptr()))
+        del keep
+        return out.cpu().numpy() if as_numpy else out
+
+    def render_baked(self, params: abi.PTFrameParams, volume, reflections=None, dfg=None, return_rays: bool = False, **options):
+        """PTShadeBakedFrame: the frame `params` describes (None: this tracer's), every pixel's centre ray traced to its first hit
+        and shaded from the bakes: a view of the scene lit by a ProbeVolume and a ReflectionProbes, as they are returned by
+        bake_probe_volume and capture_reflection_probes.  dfg: a DFG table, None = a 32 x 32 one baked once per context.  Returns
+        the (height, width, 4) float32 device tensor, and with return_rays the (height * width, 8) PTRay rows it traced."""
+        import torch
+        p = params or self.params(seed=0)
+        dev = torch.device(f"cuda:{self.device}")
+        s, keep = self._shade_inputs(volume, reflections, dfg, **options)
+        w, h = int(p.OutputWidth), int(p.OutputHeight)
+        out = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
+        rays = torch.empty((h * w, 8), dtype=torch.float32, device=dev) if return_rays else None
+        with self._ordered(dev):
+            plugin.check(self.lib.PTShadeBakedFrame(self.ctx, C.byref(p), C.byref(s), out.data_ptr(), rays.data_ptr() if return_rays else None))
+        del keep
+        return (out, rays) if return_rays else out
+
     # ---- probe placement (include/ptmi_plugin.h Part 18)
     def place_probes(self, positions, spacing, spp: int = 64, iterations: int = 4, max_distance: float = None, min_front_distance: float = None,
                      backface_share: float = 0.25, max_offset: float = 0.45, first_sample: int = 0, seeds=None, start=None, stats: bool = False):

@@ -170,6 +170,15 @@ sig = {
     "PTReflectionFoldHost": (i32, [vp, C.c_uint64, C.c_uint32, C.c_uint32, vp]),
     "PTReflectionPrefilterHost": (i32, [vp, C.c_uint64, C.c_uint32, C.c_uint32, vp]),
     "PTReflectionLookupHost": (i32, [vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint64, vp]),
+    # Part 21 (shading from the bakes)
+    "PTBakeDFG": (i32, [vp, C.c_uint32, vp]),
+    "PTShadeSurfaces": (i32, [vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, vp, vp]),
+    "PTShadeCompose": (i32, [vp, vp, vp, vp, C.c_uint64, vp, C.c_uint32, vp]),
+    "PTShadeBaked": (i32, [vp, C.POINTER(abi.PTShadeInputs), vp, vp, vp, C.c_uint64, vp]),
+    "PTShadeBakedFrame": (i32, [vp, C.POINTER(abi.PTFrameParams), C.POINTER(abi.PTShadeInputs), vp, vp]),
+    "PTBakeDFGHost": (i32, [C.c_uint32, vp]),
+    "PTShadeTermsHost": (i32, [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, vp]),
+    "PTShadeComposeHost": (i32, [vp, vp, vp, C.c_uint64, vp, C.c_uint32, vp]),
     "PTGetLastError": (C.c_char_p, []), "PTGetVersion": (i32, []),
 }
 EXPORTED_SYMBOLS = list(sig)
@@ -884,6 +893,56 @@ def reflection_lookup(maps, res: int, levels: int, directions=None, roughness=0.
     if not lib.PTReflectionLookupHost(m.ctypes.data if m.shape[0] else None, m.shape[0], int(res), int(levels), None if pr is None else pr.ctypes.data,
                                       None if bx is None else bx.ctypes.data, qr.ctypes.data, qr.shape[0], out.ctypes.data):
         raise PluginError(abi.PT_ERR_INVALID_ARG, "PTReflectionLookupHost failed: " + lib.PTGetBVHBuildError().decode())
+    return out
+
+
+def bake_dfg(res: int = 32) -> np.ndarray:
+    """The split-sum DFG table on the host (PTBakeDFGHost; include/ptmi_plugin.h Part 21): (res, res, 2) float32, row j = perceptual
+    roughness (j + 0.5) / res, column i = N.V (i + 0.5) / res, {scale, bias} of F0.  res is 16, 32 or 64."""
+    ok = int(res) in abi.PT_SHADE_DFG_RES                                     # (the twin refuses another res itself)
+    out = np.empty((int(res), int(res), 2) if ok else (1, 1, 2), np.float32)
+    lib = load_library()
+    if not lib.PTBakeDFGHost(int(res), out.ctypes.data):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTBakeDFGHost failed: " + lib.PTGetBVHBuildError().decode())
+    return out
+
+
+def shade_terms(materials, rays, surfaces, probe_positions=None, boxes=None):
+    """A hit's shading terms and lookup queries on the host (PTShadeTermsHost): materials (n, 12) float32 PTShadeMaterial rows as
+    PathTracer.shade_surfaces returns them, rays (n, 8) PTRay rows, surfaces (n, 12) PTRaySurface rows; probe_positions (k, 3) or
+    None (no probes), boxes (k, 8) PTReflectionBox rows or None.  Returns terms (n, 12), receivers (n, 8) and queries (n, 8),
+    all float32."""
+    m = np.ascontiguousarray(materials, dtype=np.float32).reshape(-1, 12)
+    r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+    s = np.ascontiguousarray(surfaces, dtype=np.float32).reshape(-1, 12)
+    n = m.shape[0]
+    assert r.shape[0] == n and s.shape[0] == n, (m.shape, r.shape, s.shape)
+    pr = None if probe_positions is None else probe_rows(probe_positions)
+    bx = None if boxes is None else np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 8)
+    assert bx is None or pr is None or bx.shape[0] == pr.shape[0], (bx.shape, pr.shape)
+    terms, recv, queries = np.empty((n, 12), np.float32), np.empty((n, 8), np.float32), np.empty((n, 8), np.float32)
+    lib = load_library()
+    if not lib.PTShadeTermsHost(m.ctypes.data, r.ctypes.data, s.ctypes.data, n, None if pr is None or not pr.shape[0] else pr.ctypes.data,
+                                None if bx is None else bx.ctypes.data, 0 if pr is None else pr.shape[0], terms.ctypes.data, recv.ctypes.data,
+                                queries.ctypes.data):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTShadeTermsHost failed: " + lib.PTGetBVHBuildError().decode())
+    return terms, recv, queries
+
+
+def shade_compose(terms, irradiance, reflection, dfg) -> np.ndarray:
+    """The compose step on the host (PTShadeComposeHost): terms (n, 12), irradiance (n, 4), reflection (n, 4), the DFG table
+    (res, res, 2), all float32.  Returns (n, 4) float32: rgb and 1 (zeros for a miss)."""
+    t = np.ascontiguousarray(terms, dtype=np.float32).reshape(-1, 12)
+    e = np.ascontiguousarray(irradiance, dtype=np.float32).reshape(-1, 4)
+    s = np.ascontiguousarray(reflection, dtype=np.float32).reshape(-1, 4)
+    d = np.ascontiguousarray(dfg, dtype=np.float32)
+    assert d.ndim == 3 and d.shape[0] == d.shape[1] and d.shape[2] == 2, d.shape
+    n = t.shape[0]
+    assert e.shape[0] == n and s.shape[0] == n, (t.shape, e.shape, s.shape)
+    out = np.empty((n, 4), np.float32)
+    lib = load_library()
+    if not lib.PTShadeComposeHost(t.ctypes.data, e.ctypes.data, s.ctypes.data, n, d.ctypes.data, d.shape[0], out.ctypes.data):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTShadeComposeHost failed: " + lib.PTGetBVHBuildError().decode())
     return out
 
 
