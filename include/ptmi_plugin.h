@@ -1939,6 +1939,91 @@ PT_API int PTShadeTermsHost(const PTShadeMaterial* materials, const PTRay* rays,
 PT_API int PTShadeComposeHost(const PTShadeTerms* terms, const PTIrradiance* irradiance, const PTReflectionTexel* reflection, uint64_t count,
                               const PTShadeDFG* dfg, uint32_t dfgRes, float* out);
 
+/* =====================================================================================================================
+ * Part 22: first hits shaded from baked lightmaps.  Part 21 reads diffuse light from the probe volume only; here a static surface
+ * reads its lightmap (Parts 13, 14, 17, 19 bake it) and everything else falls back to the volume.  The caller binds up to
+ * PT_LIGHTMAP_MAX_BINDINGS lightmaps to spans of primitives; a hit inside a span reads four texels of the image instead of up to
+ * eight probes.  An addition beside the reference's ABI, detected by symbol; PTGetVersion is unchanged; PTShadeInputs keeps its
+ * 120 bytes, PTShadeBaked and PTShadeBakedFrame their bits.
+ *
+ * Left out: taps from a neighbouring chart of the same atlas (chart padding and PTResolveLightmap's dilate are the caller's
+ * answer, as for every lightmapped renderer); directional (SH) lightmaps; several atlases blended; PTGroup wrappers; PTPresent of
+ * the result.
+ *
+ * The rule (bit-exact; lightmap_lookup_rule.h is its one definition: the kernels, the host twin and tests/lightmap_lookup_ref.py
+ * evaluate it; only + - * /, floorf and comparisons, every operator one IEEE binary32 operation in the order written, no fma).
+ * Entry i reads its ray, its PTRayHit and its PTRaySurface, exactly what PTShadeSurfaces reads.
+ *  1. No lightmap.  A miss as Part 21 step 2 defines it (prim == 0xFFFFFFFF, or a materialIndex not below the scene's material
+ *     count) has none.  d is Part 21 step 2's d BEFORE the flip: Vd = (-D) / len, d = (N.x * Vd.x + N.y * Vd.y) + N.z * Vd.z with
+ *     N = PTRaySurface.normal.  A hit with d < 0 is seen from behind: it matches only bindings with PT_LIGHTMAP_TWO_SIDED.
+ *  2. Binding choice.  In ascending k, binding k matches when (uint32_t)(hit.prim - firstPrim) < primCount, and instance ==
+ *     0xFFFFFFFF or instance == surface.instance, and the side rule holds.  The first match wins; none: PT_LIGHTMAP_NONE.
+ *  3. UV.  p = hit.prim - firstPrim; corner k is (dUvs[6p + 2k], dUvs[6p + 2k + 1]), without dUvs uv0, uv1, uv2 of attribute
+ *     record hit.prim.  b1 = hit.u, b2 = hit.v, w0 = 1.0f - b1 - b2; U = (u0 * w0 + u1 * b1) + u2 * b2, V likewise (Part 14's
+ *     interpolation form).
+ *  4. Footprint.  x = U * (float)width - 0.5f, y = V * (float)height - 0.5f.  Unless x > -1.0f && x < (float)width, and the same
+ *     of y and height, nothing is found (a NaN lands here).  xf = floorf(x), x0 = (int32_t)xf, fx = x - xf; likewise y.  The taps
+ *     are c00 = (x0, y0), c10 = (x0 + 1, y0), c01 = (x0, y0 + 1), c11 = (x0 + 1, y0 + 1).  A tap is valid when it lies inside the
+ *     image and its texel's w > 0.0f (covered 1.0, dilated 0.5; a cleared texel, a negative or a NaN w is not).
+ *  5. Filter, clamped to what is valid.  Row 0: both taps valid: r0 = c00 + fx * (c10 - c00) per channel; one: that tap; none: the
+ *     row is invalid.  Row 1 likewise from c01, c11.  Both rows valid: E = r0 + fy * (r1 - r0); one: that row; none: nothing is
+ *     found.  A constant image comes back exactly and no empty texel darkens a chart border; an invalid tap's rgb enters no
+ *     arithmetic.
+ *  6. Found: PTIrradiance {E.rgb, m2 = 0.0f} and the binding's index.  Otherwise zero bits and PT_LIGHTMAP_NONE.
+ *  7. PTShadeLightmapped is PTShadeBaked with one change: where steps 1 to 6 find a lightmap, E is the lightmap's and the volume
+ *     lookup is not executed for that entry; elsewhere E is Part 16's lookup (Part 18's with dPlacement).  It equals
+ *     PTShadeSurfaces, PTProbeGridIrradiance[Placed], PTLightmapLookup, "the lightmap's irradiance where binding !=
+ *     PT_LIGHTMAP_NONE, else the volume's", PTReflectionLookup and PTShadeCompose bit for bit; with nothing bound it equals
+ *     PTShadeBaked.  PTShadeLightmappedFrame is PTShadeBakedFrame's three steps with that kernel (the same scratch): it equals
+ *     PTTraceRays followed by PTShadeLightmapped over its rays.
+ *
+ * PTBindLightmaps validates on the host, copies the records into a table the context owns (the caller's array is not referenced
+ * after the call returns) and is stream-ordered on the context's stream.  count == 0 unbinds; PTSetScene unbinds (the spans name
+ * a scene); geometry, instance and material updates keep the table (primitive indices do not move).  The images and UV arrays
+ * stay the caller's and must outlive their use.  With nothing bound PTLightmapLookup answers "not found" for every entry.
+ * Errors: PT_ERR_NO_SCENE before PTSetScene; PT_ERR_INVALID_ARG for a NULL context, NULL bindings with count > 0, count >
+ * PT_LIGHTMAP_MAX_BINDINGS, a NULL or misaligned dImage, a misaligned dUvs, a size outside 1 ... PT_CHART_MAX_SIZE, primCount
+ * == 0 or a span past the scene's attribute count, an instance that is neither 0xFFFFFFFF nor below the scene's instance count
+ * (a flat scene has none), an unknown flag bit, a nonzero reserved word; a refused call leaves the previous table bound.  The
+ * other calls check their pointers as Part 21's do, and `inputs` exactly as PTShadeBaked checks it.  No CPU fallback.
+ * PTLightmapLookupHost is the twin: no context, no GPU, the bindings' pointers are host pointers; attrs may be NULL when every
+ * binding has dUvs; it returns 1, or 0 with PTGetBVHBuildError() set (the same refusals, spans against attrCount, instances
+ * unchecked).
+ * ===================================================================================================================== */
+#define PT_LIGHTMAP_TWO_SIDED    1u          /* PTLightmapBinding.flags */
+#define PT_LIGHTMAP_MAX_BINDINGS 64u
+#define PT_LIGHTMAP_NONE         0xFFFFFFFFu
+
+typedef struct PTLightmapBinding {  /* 48 bytes; a host struct, and the same bytes sit in the device table */
+    uint32_t firstPrim, primCount;  /* a span of TriangleAttributes indices: a BLAS's triAttributeOffset and triangleCount, or 0 and
+                                       the scene's whole count on a flat scene */
+    uint32_t instance;              /* 0xFFFFFFFF: any instance (and the only legal value on a flat scene) */
+    uint32_t flags;                 /* PT_LIGHTMAP_TWO_SIDED */
+    uint32_t width, height;         /* 1 ... PT_CHART_MAX_SIZE */
+    uint32_t reserved[2];           /* must be 0 */
+    const void*  dImage;            /* width * height RGBA float32 as PTResolveLightmap writes it: w > 0 marks a filled texel; 16-byte aligned */
+    const float* dUvs;              /* 6 floats per primitive of the span, PTRasterizeChart's layout, 8-byte aligned; NULL: uv0 .. uv2 of
+                                       the attribute record */
+} PTLightmapBinding;
+
+#ifdef __cplusplus
+static_assert(sizeof(PTLightmapBinding) == 48, "PTLightmapBinding is 48 bytes");
+#else
+_Static_assert(sizeof(PTLightmapBinding) == 48, "PTLightmapBinding is 48 bytes");
+#endif
+
+PT_API int PTBindLightmaps(PTContext* ctx, const PTLightmapBinding* bindings, uint32_t count);
+/* dRays, dHits, dSurface: as PTShadeSurfaces takes them; dOut: count entries; dOutBinding: count words, or NULL. */
+PT_API int PTLightmapLookup(PTContext* ctx, const PTRay* dRays, const PTRayHit* dHits, const PTRaySurface* dSurface, uint64_t count, PTIrradiance* dOut,
+                            uint32_t* dOutBinding);
+PT_API int PTShadeLightmapped(PTContext* ctx, const PTShadeInputs* inputs, const PTRay* dRays, const PTRayHit* dHits, const PTRaySurface* dSurface,
+                              uint64_t count, float* dOut);
+PT_API int PTShadeLightmappedFrame(PTContext* ctx, const PTFrameParams* params, const PTShadeInputs* inputs, float* dOut, PTRay* dOutRays);
+/* host twin, no GPU */
+PT_API int PTLightmapLookupHost(const PTLightmapBinding* bindings, uint32_t bindingCount, const PTTriangleAttributes* attrs, uint64_t attrCount,
+                                uint32_t materialCount, const PTRay* rays, const PTRayHit* hits, const PTRaySurface* surfaces, uint64_t count,
+                                PTIrradiance* out, uint32_t* outBinding);
+
 /* Text of the last error on the calling thread ("" if none). */
 PT_API const char* PTGetLastError(void);
 /* Library/ABI version: (major << 16) | minor. */

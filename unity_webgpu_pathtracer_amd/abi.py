@@ -408,6 +408,20 @@ class PTShadeInputs(C.Structure):
 assert C.sizeof(PTShadeInputs) == 120
 
 
+# ---- first hits shaded from baked lightmaps (include/ptmi_plugin.h Part 22)
+PT_LIGHTMAP_TWO_SIDED = 1
+PT_LIGHTMAP_MAX_BINDINGS = 64
+PT_LIGHTMAP_NONE = 0xFFFFFFFF
+
+
+class PTLightmapBinding(C.Structure):
+    _fields_ = [("firstPrim", C.c_uint32), ("primCount", C.c_uint32), ("instance", C.c_uint32), ("flags", C.c_uint32), ("width", C.c_uint32),
+                ("height", C.c_uint32), ("reserved", C.c_uint32 * 2), ("dImage", C.c_void_p), ("dUvs", C.c_void_p)]
+
+
+assert C.sizeof(PTLightmapBinding) == 48
+
+
 # ---- lightmap charts (include/ptmi_plugin.h Part 14)
 PT_CHART_MAX_SIZE = 8192
 PT_CHART_MAX_DILATE = 16

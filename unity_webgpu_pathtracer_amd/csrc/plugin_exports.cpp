@@ -23,6 +23,7 @@
 #include "adaptive_gather_rule.h"
 #include "reflection_rule.h"
 #include "shade_rule.h"
+#include "lightmap_lookup_rule.h"
 #include "repack_rule.h"
 #include "ptmi_plugin.h"
 
@@ -332,6 +333,15 @@ PT_API int PTShadeComposeHost(const PTShadeTerms* terms, const PTIrradiance* irr
                               const PTShadeDFG* dfg, uint32_t dfgRes, float* out)
 {
     if (!ptshade::compose_host(terms, irradiance, reflection, count, dfg, dfgRes, out, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+// The lightmap lookup on the host (lightmap_lookup_host.cpp; Part 22 has the rule).  No GPU involved.
+PT_API int PTLightmapLookupHost(const PTLightmapBinding* bindings, uint32_t bindingCount, const PTTriangleAttributes* attrs, uint64_t attrCount,
+                                uint32_t materialCount, const PTRay* rays, const PTRayHit* hits, const PTRaySurface* surfaces, uint64_t count,
+                                PTIrradiance* out, uint32_t* outBinding)
+{
+    if (!ptlm::lookup_host(bindings, bindingCount, attrs, attrCount, materialCount, rays, hits, surfaces, count, out, outBinding, g_buildError)) return 0;
     g_buildError.clear();
     return 1;
 }

@@ -301,6 +301,7 @@ int set_scene(PTContext* c, const PTSceneDesc* hostScene, bool validate)
     for (auto& set : c->sets) if (set.stream) HIP_TRY(hipStreamSynchronize(set.stream));   // no pass may still read the old scene
     HIP_TRY(hipStreamSynchronize(c->stream));
     discard_updates(c);
+    c->lightmaps.count = 0;             // the bound lightmaps' spans named the old scene (Part 22)
     int rc;
     if ((rc = upload(c, c->nodes, s->bvhNodes, s->bvhNodesBytes))) return rc;
     if ((rc = upload(c, c->tris, s->bvhTris, s->bvhTrisBytes))) return rc;

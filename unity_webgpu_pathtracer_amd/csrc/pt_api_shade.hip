@@ -12,8 +12,9 @@ int check_dfg(uint32_t res, const char* who)
     return PT_OK;
 }
 
-// what PTShadeBaked and PTShadeBakedFrame check of the struct before the context is used
-int check_inputs(const PTShadeInputs* in, const char* who)
+} // namespace
+
+int check_shade_inputs(const PTShadeInputs* in, const char* who)
 {
     const std::string w(who);
     if (!in) return fail(PT_ERR_INVALID_ARG, w + ": inputs == NULL");
@@ -29,6 +30,8 @@ int check_inputs(const PTShadeInputs* in, const char* who)
     return PT_OK;
 }
 
+namespace {
+
 int shade_baked(PTContext* c, const PTShadeInputs& in, const PTRay* dRays, const PTRayHit* dHits, const PTRaySurface* dSurface, uint64_t count, float4* dOut)
 {
     return for_each_launch(count, 1ull << 30, [&](uint64_t first, uint32_t n) {
@@ -38,6 +41,37 @@ int shade_baked(PTContext* c, const PTShadeInputs& in, const PTRay* dRays, const
 }
 
 } // namespace
+
+int shade_frame(PTContext* c, const PTFrameParams* hostParams, const PTShadeInputs* inputs, float* dOut, PTRay* dOutRays, const char* who, ShadeList shade)
+{
+    if (!c) return fail(PT_ERR_INVALID_ARG, std::string(who) + ": ctx == NULL");
+    PTFrameParams p;
+    int rc = import_frame_params(hostParams, p);
+    if (rc) return rc;
+    if ((rc = check_shade_inputs(inputs, who))) return rc;
+    if (!dOut || misaligned(dOut) || misaligned(dOutRays)) return fail(PT_ERR_INVALID_ARG, std::string(who) + ": out == NULL, or out/rays is not 16-byte aligned");
+    if (!c->hasScene) return fail(PT_ERR_NO_SCENE, "PTSetScene has not been called");
+    HIP_TRY(hipSetDevice(c->device));
+    RoctxRange range("PT shade baked frame (enqueue)");
+    if ((rc = query_prepare(c))) return rc;
+    const uint64_t pixels = (uint64_t)p.OutputWidth * p.OutputHeight;
+    PTContext::Shade& W = c->shade;
+    // growing drains the context stream, which every earlier frame ran on
+    if (!dOutRays && (rc = W.rays.reserve(pixels * sizeof(PTRay), c->stream))) return rc;
+    if ((rc = W.hits.reserve(pixels * sizeof(PTRayHit), c->stream))) return rc;
+    if ((rc = W.surfaces.reserve(pixels * sizeof(PTRaySurface), c->stream))) return rc;
+    PTRay* rays = dOutRays ? dOutRays : (PTRay*)W.rays.ptr;
+    const bool stats = c->statsLevel > 0;
+    const uint32_t cap = c->query.caps[pt_query_kernel_index(c->scene.hasTlas != 0u, 2u, stats)];
+    rc = for_each_launch(pixels, 1ull << 28, [&](uint64_t first, uint32_t n) {
+        HIP_TRY(pt_launch_shade_frame_rays(p, (uint32_t)first, n, rays + first, c->stream));
+        HIP_TRY(pt_launch_query(c->scene, (const float4*)(rays + first), n, 2u, stats, (float4*)((PTRayHit*)W.hits.ptr + first),
+                                (float4*)((PTRaySurface*)W.surfaces.ptr + first), (uint2*)c->query.slab.ptr, cap, (unsigned long long*)c->dStats.ptr, c->stream));
+        return PT_OK;
+    });
+    if (rc) return rc;
+    return shade(c, *inputs, rays, (const PTRayHit*)W.hits.ptr, (const PTRaySurface*)W.surfaces.ptr, pixels, (float4*)dOut);
+}
 
 extern "C" {
 
@@ -92,7 +126,7 @@ PT_API int PTShadeBaked(PTContext* c, const PTShadeInputs* inputs, const PTRay* 
                         float* dOut)
 {
     if (!c) return fail(PT_ERR_INVALID_ARG, "PTShadeBaked: ctx == NULL");
-    if (int rc = check_inputs(inputs, "PTShadeBaked")) return rc;
+    if (int rc = check_shade_inputs(inputs, "PTShadeBaked")) return rc;
     if (!dRays || !dHits || !dSurface || !dOut) return fail(PT_ERR_INVALID_ARG, "PTShadeBaked: rays/hits/surface/out == NULL");
     if (misaligned(dRays) || misaligned(dHits) || misaligned(dSurface) || misaligned(dOut))
         return fail(PT_ERR_INVALID_ARG, "PTShadeBaked: rays/hits/surface/out is not 16-byte aligned");
@@ -104,33 +138,7 @@ PT_API int PTShadeBaked(PTContext* c, const PTShadeInputs* inputs, const PTRay* 
 
 PT_API int PTShadeBakedFrame(PTContext* c, const PTFrameParams* hostParams, const PTShadeInputs* inputs, float* dOut, PTRay* dOutRays)
 {
-    if (!c) return fail(PT_ERR_INVALID_ARG, "PTShadeBakedFrame: ctx == NULL");
-    PTFrameParams p;
-    int rc = import_frame_params(hostParams, p);
-    if (rc) return rc;
-    if ((rc = check_inputs(inputs, "PTShadeBakedFrame"))) return rc;
-    if (!dOut || misaligned(dOut) || misaligned(dOutRays)) return fail(PT_ERR_INVALID_ARG, "PTShadeBakedFrame: out == NULL, or out/rays is not 16-byte aligned");
-    if (!c->hasScene) return fail(PT_ERR_NO_SCENE, "PTSetScene has not been called");
-    HIP_TRY(hipSetDevice(c->device));
-    RoctxRange range("PT shade baked frame (enqueue)");
-    if ((rc = query_prepare(c))) return rc;
-    const uint64_t pixels = (uint64_t)p.OutputWidth * p.OutputHeight;
-    PTContext::Shade& W = c->shade;
-    // growing drains the context stream, which every earlier frame ran on
-    if (!dOutRays && (rc = W.rays.reserve(pixels * sizeof(PTRay), c->stream))) return rc;
-    if ((rc = W.hits.reserve(pixels * sizeof(PTRayHit), c->stream))) return rc;
-    if ((rc = W.surfaces.reserve(pixels * sizeof(PTRaySurface), c->stream))) return rc;
-    PTRay* rays = dOutRays ? dOutRays : (PTRay*)W.rays.ptr;
-    const bool stats = c->statsLevel > 0;
-    const uint32_t cap = c->query.caps[pt_query_kernel_index(c->scene.hasTlas != 0u, 2u, stats)];
-    rc = for_each_launch(pixels, 1ull << 28, [&](uint64_t first, uint32_t n) {
-        HIP_TRY(pt_launch_shade_frame_rays(p, (uint32_t)first, n, rays + first, c->stream));
-        HIP_TRY(pt_launch_query(c->scene, (const float4*)(rays + first), n, 2u, stats, (float4*)((PTRayHit*)W.hits.ptr + first),
-                                (float4*)((PTRaySurface*)W.surfaces.ptr + first), (uint2*)c->query.slab.ptr, cap, (unsigned long long*)c->dStats.ptr, c->stream));
-        return PT_OK;
-    });
-    if (rc) return rc;
-    return shade_baked(c, *inputs, rays, (const PTRayHit*)W.hits.ptr, (const PTRaySurface*)W.surfaces.ptr, pixels, (float4*)dOut);
+    return shade_frame(c, hostParams, inputs, dOut, dOutRays, "PTShadeBakedFrame", shade_baked);
 }
 
 } // extern "C"

@@ -264,6 +264,13 @@ struct PTContext {
     struct Shade {
         DeviceBuffer rays, hits, surfaces;
     } shade;
+    // bound lightmaps (PTBindLightmaps): the table's device copy, rewritten in stream order on the context stream; count == 0:
+    // nothing bound (PTSetScene unbinds: the spans name a scene)
+    struct BoundLightmaps {
+        UploadTable table;                      // PT_LIGHTMAP_MAX_BINDINGS records, whatever the count
+        uint32_t count = 0;
+        const PTLightmapBinding* device() const { return count ? (const PTLightmapBinding*)table.dev.ptr : nullptr; }
+    } lightmaps;
     // lightmap charts (PTRasterizeChart / PTResolveLightmap): grown on demand, kept across PTSetScene
     struct Lightmap {
         DeviceBuffer owner;                     // 4 B per texel: the owner map
@@ -473,6 +480,12 @@ int gather_irradiance(PTContext* c, const PTFrameParams& p1, const PTReceiver* d
                       PTIrradiance* dOut, const char* who);
 // pt_api_radiance.hip: PTTraceRadiance's body, one launch sequence per chunk of PT_RADIANCE_CHUNK rays
 int trace_radiance(PTContext* c, const PTFrameParams& p, const PTRadianceRay* dRays, uint64_t count, PTRadiance* dOut, const char* who);
+// pt_api_shade.hip: what PTShadeBaked and PTShadeBakedFrame check of the struct before the context is used, and PTShadeBakedFrame's
+// body -- the frame's rays, the closest-hit walk with surface records into the context's scratch, then shade(...) over them
+int check_shade_inputs(const PTShadeInputs* in, const char* who);
+using ShadeList = int (*)(PTContext* c, const PTShadeInputs& in, const PTRay* dRays, const PTRayHit* dHits, const PTRaySurface* dSurface, uint64_t count,
+                          float4* dOut);
+int shade_frame(PTContext* c, const PTFrameParams* hostParams, const PTShadeInputs* inputs, float* dOut, PTRay* dOutRays, const char* who, ShadeList shade);
 int query_prepare(PTContext* c);                                                // pt_api_query.hip: the grid caps and the stack slab of the query kernels, on first use
 int set_scene(PTContext* c, const PTSceneDesc* hostScene, bool validate);      // pt_api_context.hip; PTGroupSetScene validates once
 int drain_events(PTContext* c);                                                 // pt_api_context.hip

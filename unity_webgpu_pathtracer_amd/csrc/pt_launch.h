@@ -340,6 +340,14 @@ hipError_t pt_launch_shade_baked(const DScene& S, const PTShadeInputs& in, const
                                  float4* out, hipStream_t stream);
 // pixels [first, first + count) of the frame P describes: the guides' ray at one sample per pixel, tmax PT_FAR_PLANE
 hipError_t pt_launch_shade_frame_rays(const PTFrameParams& P, uint32_t first, uint32_t count, PTRay* rays, hipStream_t stream);
+// ---- first hits shaded from baked lightmaps (include/ptmi_plugin.h Part 22; pt_shade_lightmap.hip) ----
+// table: bindingCount (<= PT_LIGHTMAP_MAX_BINDINGS) records on the device that have passed ptlm::check_bindings, or null with 0;
+// outBinding may be null
+hipError_t pt_launch_lightmap_lookup(const DScene& S, const PTLightmapBinding* table, uint32_t bindingCount, const PTRay* rays, const PTRayHit* hits,
+                                     const PTRaySurface* surfaces, uint32_t count, PTIrradiance* out, uint32_t* outBinding, hipStream_t stream);
+// pt_launch_shade_baked with the lightmap lookup in front of the volume's
+hipError_t pt_launch_shade_lightmapped(const DScene& S, const PTShadeInputs& in, const PTLightmapBinding* table, uint32_t bindingCount, const PTRay* rays,
+                                       const PTRayHit* hits, const PTRaySurface* surfaces, uint32_t count, float4* out, hipStream_t stream);
 #ifndef PT_WF_FUSED_GROUPS
 #define PT_WF_FUSED_GROUPS 2u   // schedule 4: groups of 64 path contexts a persistent wave owns (power of two <= 4: numSlots is a multiple of 256).
                                 // Sponza-class 1080p / 8 spp, one pass in flight: 1: 29.9 ms, 2: 25.2, 4: 27.9, 8: 31.4

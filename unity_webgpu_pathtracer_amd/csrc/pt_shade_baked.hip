@@ -9,87 +9,16 @@
 //     pt_shade_baked[_placed]  the fused call: the front of pt_shade_surfaces, volume_rule.h's lookup with pt_volume_loads.h's
 //                           loads, reflection_rule.h's lookup, the compose step -- nothing between them leaves the registers.  The
 //                           grid, the sizes and every base pointer arrive by value in the kernel arguments (scalar registers)
+//                           (the lane's text is pt_shade_hit.h's, which Part 22's kernels share)
 //     pt_shade_frame_rays   one lane per pixel: the guides' pinhole ray at one sample per pixel (pt_denoise.hip's expressions)
 //
 // The arithmetic is shade_rule.h's, which the host twins evaluate too.
 #include "pt_device.h"
 #include "pt_launch.h"
 #include "shade_rule.h"
-#include "pt_volume_loads.h"
+#include "pt_shade_hit.h"
 
 namespace {
-
-struct HitRecords {
-    bool miss;
-    PTShadeMaterial M;
-    PTShadeTerms T;
-    float P[3], N[3], R[3];
-    uint32_t probe;
-};
-
-// Steps 2 of the rule for entry i.  A surface record whose material index lies outside the scene's materials is taken as a miss:
-// nothing is read through it.
-PT_DEV void hit_records(const DScene& S, const PTRay* __restrict__ rays, const PTRayHit* __restrict__ hits, const PTRaySurface* __restrict__ surfaces,
-                        uint32_t i, const PTProbe* __restrict__ probes, const PTReflectionBox* __restrict__ boxes, uint32_t probeCount, HitRecords& h)
-{
-    h.M = {};
-    h.T = {};
-    for (uint32_t a = 0; a < 3u; ++a) h.P[a] = h.N[a] = h.R[a] = 0.0f;
-    h.probe = ptshade::kNoProbe;
-    const float4 hr = ((const float4*)hits)[i];
-    h.miss = pt_asuint(hr.w) == 0xFFFFFFFFu;
-    uint32_t materialIndex = 0xFFFFFFFFu;
-    float4 s0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), s1 = s0, s2 = s0;
-    if (!h.miss) {
-        const float4* sp = (const float4*)surfaces + (size_t)i * 3;
-        s0 = sp[0]; s1 = sp[1]; s2 = sp[2];
-        materialIndex = pt_asuint(s1.w);
-        h.miss = materialIndex >= S.materialCount;
-    }
-    if (h.miss) {
-        h.M.materialIndex = 0xFFFFFFFFu;
-        h.M.flags = PT_SHADE_MISS;
-        return;
-    }
-    const float4 r0 = ((const float4*)rays)[(size_t)i * 2], r1 = ((const float4*)rays)[(size_t)i * 2 + 1];
-    const float D[3] = {r0.w, r1.x, r1.y};
-    SurfHit sh = {};
-    sh.position = mk3(s0.x, s0.y, s0.z);
-    sh.distance = s0.w;
-    sh.normal = mk3(s1.x, s1.y, s1.z);
-    sh.uv = {s2.x, s2.y};
-    sh.materialIndex = (int32_t)materialIndex;
-    Counters cn = {};
-    const Material m = get_material<false>(S, sh.materialIndex, mk3(D[0], D[1], D[2]), sh, cn);
-    h.M.baseColor[0] = m.baseColor.x; h.M.baseColor[1] = m.baseColor.y; h.M.baseColor[2] = m.baseColor.z;
-    h.M.metallic = m.metallic;
-    h.M.emission[0] = m.emission.x; h.M.emission[1] = m.emission.y; h.M.emission[2] = m.emission.z;
-    h.M.roughness = m.roughness;
-    h.M.occlusion = m.occlusion;
-    h.M.opacity = m.opacity;
-    h.M.materialIndex = materialIndex;
-    h.M.flags = 0u;
-    h.P[0] = s0.x; h.P[1] = s0.y; h.P[2] = s0.z;
-    h.N[0] = s1.x; h.N[1] = s1.y; h.N[2] = s1.z;
-    ptshade::terms(h.M, D, h.N, h.R, h.T);
-    // k is the same in every lane of the wave: scalar loads
-    h.probe = ptshade::choose_probe(h.P, probeCount, boxes != nullptr,
-                                    [&](uint32_t k, float Q[3]) {
-                                        const float4 p = pt_uniform_load((const float4*)probes, k);
-                                        Q[0] = p.x; Q[1] = p.y; Q[2] = p.z;
-                                    },
-                                    [&](uint32_t k, float bmin[3], float bmax[3]) {
-                                        const float4 b0 = pt_uniform_load((const float4*)boxes, 2u * (size_t)k), b1 = pt_uniform_load((const float4*)boxes, 2u * (size_t)k + 1u);
-                                        bmin[0] = b0.x; bmin[1] = b0.y; bmin[2] = b0.z;
-                                        bmax[0] = b1.x; bmax[1] = b1.y; bmax[2] = b1.z;
-                                    });
-}
-
-PT_DEV void dfg_entry(const PTShadeDFG* __restrict__ dfg, uint32_t e, float ab[2])
-{
-    const float2 v = ((const float2*)dfg)[e];
-    ab[0] = v.x; ab[1] = v.y;
-}
 
 // Four entries per workgroup; a wave is whole in or whole out.
 __global__ __launch_bounds__(256) void pt_shade_dfg(uint32_t res, PTShadeDFG* __restrict__ out)
@@ -160,64 +89,18 @@ __global__ __launch_bounds__(256) void pt_shade_compose(const PTShadeTerms* __re
     out[i] = make_float4(o[0], o[1], o[2], o[3]);
 }
 
-template <bool PLACED>
-PT_DEV void shade_baked_body(const DScene& S, const PTShadeInputs& A, uint32_t mapTexels, const PTRay* __restrict__ rays, const PTRayHit* __restrict__ hits,
-                             const PTRaySurface* __restrict__ surfaces, uint32_t count, float4* __restrict__ out)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= count) return;
-    HitRecords h;
-    hit_records(S, rays, hits, surfaces, i, A.dProbes, A.dBoxes, A.probeCount, h);
-    float o[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (!h.miss) {
-        float E[4];
-        const auto loadSH = [&](uint32_t probe, float co[27]) { pt_load_probe_sh(A.dSH, probe, co); };
-        const auto loadDepth = [&](uint32_t probe, uint32_t texel, float& mean, float& mean2) { pt_load_probe_depth(A.dDepth, probe, texel, mean, mean2); };
-        if constexpr (PLACED)
-            ptvol::lookup(A.grid, h.P, h.N, loadSH, loadDepth,
-                          [&](uint32_t probe, float off[3], uint32_t& state) {
-                              const float4 v = ((const float4*)A.dPlacement)[probe];
-                              off[0] = v.x; off[1] = v.y; off[2] = v.z;
-                              state = pt_asuint(v.w);
-                          },
-                          E);
-        else
-            ptvol::lookup(A.grid, h.P, h.N, loadSH, loadDepth, E);
-        float spec[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (h.probe < A.probeCount) {
-            const float4* map = (const float4*)A.dMaps + (size_t)h.probe * mapTexels;
-            const auto load = [&](uint32_t t, float rgb[3]) {
-                const float4 v = map[t];
-                rgb[0] = v.x; rgb[1] = v.y; rgb[2] = v.z;
-            };
-            if (A.dBoxes) {
-                const float4 pr = ((const float4*)A.dProbes)[h.probe];
-                const float4 b0 = ((const float4*)A.dBoxes)[2u * (size_t)h.probe], b1 = ((const float4*)A.dBoxes)[2u * (size_t)h.probe + 1u];
-                const float Q[3] = {pr.x, pr.y, pr.z}, bmin[3] = {b0.x, b0.y, b0.z}, bmax[3] = {b1.x, b1.y, b1.z};
-                ptrefl::lookup(A.res, A.levels, h.P, h.T.rho, h.R, Q, bmin, bmax, load, spec);
-            } else {
-                ptrefl::lookup(A.res, A.levels, h.P, h.T.rho, h.R, nullptr, nullptr, nullptr, load, spec);
-            }
-        }
-        float Ad, Bd;
-        ptshade::dfg_lookup(A.dfgRes, h.T.nDotV, h.T.rho, [&](uint32_t k, float ab[2]) { dfg_entry(A.dDFG, k, ab); }, Ad, Bd);
-        ptshade::compose(h.T, E, spec, Ad, Bd, o);
-    }
-    out[i] = make_float4(o[0], o[1], o[2], o[3]);
-}
-
 __global__ __launch_bounds__(256) void pt_shade_baked(DScene S, PTShadeInputs A, uint32_t mapTexels, const PTRay* __restrict__ rays,
                                                       const PTRayHit* __restrict__ hits, const PTRaySurface* __restrict__ surfaces, uint32_t count,
                                                       float4* __restrict__ out)
 {
-    shade_baked_body<false>(S, A, mapTexels, rays, hits, surfaces, count, out);
+    shade_baked_body<false>(S, A, mapTexels, rays, hits, surfaces, count, out, [](uint32_t, float*) { return false; });
 }
 
 __global__ __launch_bounds__(256) void pt_shade_baked_placed(DScene S, PTShadeInputs A, uint32_t mapTexels, const PTRay* __restrict__ rays,
                                                              const PTRayHit* __restrict__ hits, const PTRaySurface* __restrict__ surfaces, uint32_t count,
                                                              float4* __restrict__ out)
 {
-    shade_baked_body<true>(S, A, mapTexels, rays, hits, surfaces, count, out);
+    shade_baked_body<true>(S, A, mapTexels, rays, hits, surfaces, count, out, [](uint32_t, float*) { return false; });
 }
 
 // pixel first + k of the frame: pt_denoise.hip's guide ray with n = 1 (the offset (0 + 0.5f) / 1.0f is 0.5f)

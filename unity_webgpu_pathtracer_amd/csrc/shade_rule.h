@@ -91,11 +91,19 @@ PT_SHADE_HD float dfg_scale(float folded) { return folded / 4096.0f; }
 // ---- terms ----
 // What a hit gives, after the material fetch.  N: the surface record's normal in, the face-forwarded one out; R: the reflection
 // direction.  The record's words that no rule names are zero.
-PT_SHADE_HD void terms(const PTShadeMaterial& M, const float D[3], float N[3], float R[3], PTShadeTerms& T)
+// The view vector Vd = (-D) / len and d = N . Vd of the normal as the surface record gives it, before any flip: d < 0 is a hit seen
+// from behind (Part 22's side rule reads it here too).
+PT_SHADE_HD float view_dot(const float D[3], const float N[3], float Vd[3])
 {
     const float len = pt_sqrt((D[0] * D[0] + D[1] * D[1]) + D[2] * D[2]);
-    const float Vd[3] = {(-D[0]) / len, (-D[1]) / len, (-D[2]) / len};
-    float d = (N[0] * Vd[0] + N[1] * Vd[1]) + N[2] * Vd[2];
+    for (uint32_t a = 0; a < 3u; ++a) Vd[a] = (-D[a]) / len;
+    return (N[0] * Vd[0] + N[1] * Vd[1]) + N[2] * Vd[2];
+}
+
+PT_SHADE_HD void terms(const PTShadeMaterial& M, const float D[3], float N[3], float R[3], PTShadeTerms& T)
+{
+    float Vd[3];
+    float d = view_dot(D, N, Vd);
     if (d < 0.0f) {
         for (uint32_t a = 0; a < 3u; ++a) N[a] = -N[a];
         d = (N[0] * Vd[0] + N[1] * Vd[1]) + N[2] * Vd[2];

@@ -886,6 +886,101 @@ class PathTracer:
         del keep
         return (out, rays) if return_rays else out
 
+    # ---- first hits shaded from baked lightmaps (include/ptmi_plugin.h Part 22)
+    def lightmap_binding(self, image, mesh: int = None, instance: int = None, uvs=None, two_sided: bool = False):
+        """One entry for bind_lightmaps: `image`, an (height, width, 4) float32 lightmap as bake_lightmap / resolve_lightmap return it
+        (numpy, or a tensor on this context's device; w > 0 marks a filled texel), bound to the primitives of one mesh.  mesh names
+        the BLAS as chart_receivers does (None on a flat scene: the whole scene).  instance: None = whichever instance was hit (the
+        only choice on a flat scene), else only hits of that instance read this image.  uvs: the (T, 6) float32 lightmap UVs the
+        image was baked with, None = the attribute records' uv0 .. uv2.  two_sided: hits seen from behind read it too.  The entry
+        keeps its tensors alive."""
+        import torch
+        dev = torch.device(f"cuda:{self.device}")
+        img = image if isinstance(image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image, dtype=np.float32)).to(dev)
+        img = img.contiguous()
+        assert img.dtype == torch.float32 and img.dim() == 3 and img.shape[2] == 4 and img.device == dev, (img.shape, img.dtype, img.device)
+        bvh = self._bvhScene
+        assert bvh.gpu_instances is not None or instance is None, "a flat scene has no instances"
+        first, count = self._blas_offsets(mesh)[2], bvh.blas_spans[0 if mesh is None else mesh][3]
+        d_uvs = None
+        if uvs is not None:
+            d_uvs = (uvs if isinstance(uvs, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(uvs, dtype=np.float32)).to(dev)).contiguous()
+            assert d_uvs.dtype == torch.float32 and d_uvs.numel() == count * 6 and d_uvs.device == dev, (d_uvs.shape, d_uvs.dtype)
+        b = abi.PTLightmapBinding()
+        b.firstPrim, b.primCount = int(first), int(count)
+        b.instance = abi.PT_LIGHTMAP_NONE if instance is None else int(instance)
+        b.flags = abi.PT_LIGHTMAP_TWO_SIDED if two_sided else 0
+        b.height, b.width = int(img.shape[0]), int(img.shape[1])
+        b.dImage = img.data_ptr()
+        b.dUvs = None if d_uvs is None else d_uvs.data_ptr()
+        return {"record": b, "image": img, "uvs": d_uvs, "mesh": mesh, "instance": instance, "two_sided": bool(two_sided)}
+
+    def bind_lightmaps(self, bindings):
+        """PTBindLightmaps: the list of lightmap_binding entries (at most 64; the first one that matches a hit wins) replaces what
+        was bound; an empty list unbinds.  Stream-ordered with the shading calls; the entries' tensors stay alive while bound."""
+        import torch
+        bindings = list(bindings or [])
+        table = (abi.PTLightmapBinding * max(len(bindings), 1))(*[b["record"] for b in bindings])
+        with self._ordered(torch.device(f"cuda:{self.device}")):
+            plugin.check(self.lib.PTBindLightmaps(self.ctx, table if bindings else None, len(bindings)))
+        self._lightmaps = bindings
+
+    @property
+    def lightmaps(self):
+        """the entries last bound through bind_lightmaps"""
+        return list(getattr(self, "_lightmaps", []))
+
+    def lightmap_lookup(self, rays, hits, surfaces):
+        """PTLightmapLookup: what the bound lightmaps hold at the first hits of trace_rays(rays, surface=True).  Returns
+        (irradiance (n, 4) float32, binding (n,)): rgb and 0 where a lightmap was found, with the index of its binding; zero bits and
+        PT_LIGHTMAP_NONE elsewhere.  plugin.lightmap_lookup is its twin.  numpy in, numpy out (the index as uint32); device tensors
+        in, device tensors out (the index as int32, PT_LIGHTMAP_NONE reading -1)."""
+        import torch
+        r, as_numpy = self._to_device(rays, 8)
+        h, _ = self._to_device(hits, 4)
+        s, _ = self._to_device(surfaces, 12)
+        n = r.shape[0]
+        assert h.shape[0] == n and s.shape[0] == n, (r.shape, h.shape, s.shape)
+        out = torch.empty((n, 4), dtype=torch.float32, device=r.device)
+        which = torch.empty((n,), dtype=torch.int32, device=r.device)
+        if n:
+            with self._ordered(r.device):
+                plugin.check(self.lib.PTLightmapLookup(self.ctx, r.data_ptr(), h.data_ptr(), s.data_ptr(), n, out.data_ptr(), which.data_ptr()))
+        return (out.cpu().numpy(), which.cpu().numpy().view(np.uint32)) if as_numpy else (out, which)
+
+    def shade_lightmapped(self, rays, hits, surfaces, volume, reflections=None, dfg=None, **options):
+        """PTShadeLightmapped: shade_baked, but a hit inside a bound lightmap's span reads its irradiance from the lightmap (four
+        texels) instead of the probe volume; every other hit falls back to the volume.  Arguments, options and result as
+        shade_baked's; with nothing bound the two are equal bit for bit."""
+        import torch
+        r, as_numpy = self._to_device(rays, 8)
+        h, _ = self._to_device(hits, 4)
+        sf, _ = self._to_device(surfaces, 12)
+        n = r.shape[0]
+        assert h.shape[0] == n and sf.shape[0] == n, (r.shape, h.shape, sf.shape)
+        s, keep = self._shade_inputs(volume, reflections, dfg, **options)
+        out = torch.empty((n, 4), dtype=torch.float32, device=r.device)
+        if n:
+            with self._ordered(r.device):
+                plugin.check(self.lib.PTShadeLightmapped(self.ctx, C.byref(s), r.data_ptr(), h.data_ptr(), sf.data_ptr(), n, out.data_ptr()))
+        del keep
+        return out.cpu().numpy() if as_numpy else out
+
+    def render_lightmapped(self, params: abi.PTFrameParams, volume, reflections=None, dfg=None, return_rays: bool = False, **options):
+        """PTShadeLightmappedFrame: render_baked with the bound lightmaps as the diffuse source of the surfaces they cover: static
+        surfaces read their lightmap, everything else the probe volume.  Arguments and result as render_baked's."""
+        import torch
+        p = params or self.params(seed=0)
+        dev = torch.device(f"cuda:{self.device}")
+        s, keep = self._shade_inputs(volume, reflections, dfg, **options)
+        w, h = int(p.OutputWidth), int(p.OutputHeight)
+        out = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
+        rays = torch.empty((h * w, 8), dtype=torch.float32, device=dev) if return_rays else None
+        with self._ordered(dev):
+            plugin.check(self.lib.PTShadeLightmappedFrame(self.ctx, C.byref(p), C.byref(s), out.data_ptr(), rays.data_ptr() if return_rays else None))
+        del keep
+        return (out, rays) if return_rays else out
+
     # ---- probe placement (include/ptmi_plugin.h Part 18)
     def place_probes(self, positions, spacing, spp: int = 64, iterations: int = 4, max_distance: float = None, min_front_distance: float = None,
                      backface_share: float = 0.25, max_offset: float = 0.45, first_sample: int = 0, seeds=None, start=None, stats: bool = False):

@@ -179,6 +179,12 @@ sig = {
     "PTBakeDFGHost": (i32, [C.c_uint32, vp]),
     "PTShadeTermsHost": (i32, [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, vp]),
     "PTShadeComposeHost": (i32, [vp, vp, vp, C.c_uint64, vp, C.c_uint32, vp]),
+    # Part 22 (first hits shaded from baked lightmaps)
+    "PTBindLightmaps": (i32, [vp, C.POINTER(abi.PTLightmapBinding), C.c_uint32]),
+    "PTLightmapLookup": (i32, [vp, vp, vp, vp, C.c_uint64, vp, vp]),
+    "PTShadeLightmapped": (i32, [vp, C.POINTER(abi.PTShadeInputs), vp, vp, vp, C.c_uint64, vp]),
+    "PTShadeLightmappedFrame": (i32, [vp, C.POINTER(abi.PTFrameParams), C.POINTER(abi.PTShadeInputs), vp, vp]),
+    "PTLightmapLookupHost": (i32, [C.POINTER(abi.PTLightmapBinding), C.c_uint32, vp, C.c_uint64, C.c_uint32, vp, vp, vp, C.c_uint64, vp, vp]),
     "PTGetLastError": (C.c_char_p, []), "PTGetVersion": (i32, []),
 }
 EXPORTED_SYMBOLS = list(sig)
@@ -944,6 +950,57 @@ def shade_compose(terms, irradiance, reflection, dfg) -> np.ndarray:
     if not lib.PTShadeComposeHost(t.ctypes.data, e.ctypes.data, s.ctypes.data, n, d.ctypes.data, d.shape[0], out.ctypes.data):
         raise PluginError(abi.PT_ERR_INVALID_ARG, "PTShadeComposeHost failed: " + lib.PTGetBVHBuildError().decode())
     return out
+
+
+def lightmap_bindings(bindings):
+    """(a ctypes array of PTLightmapBinding or None, what it points into) from a list of dicts for the host twin: image (h, w, 4)
+    float32, first_prim, prim_count, and optionally instance (None: any), uvs ((prim_count, 6) float32 or None: the attribute
+    records'), two_sided.  The arrays are copied to 16-byte aligned memory."""
+    def aligned(a):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        buf = np.empty(a.nbytes + 16, np.uint8)
+        off = (-buf.ctypes.data) % 16
+        out = buf[off:off + a.nbytes].view(np.float32).reshape(a.shape)
+        out[...] = a
+        return out
+    if not bindings:
+        return None, []
+    table, keep = (abi.PTLightmapBinding * len(bindings))(), []
+    for b, d in zip(table, bindings):
+        image = aligned(d["image"])
+        assert image.ndim == 3 and image.shape[2] == 4, image.shape
+        uvs = None if d.get("uvs") is None else aligned(np.asarray(d["uvs"], np.float32).reshape(-1, 6))
+        keep += [image, uvs]
+        b.firstPrim, b.primCount = int(d["first_prim"]), int(d["prim_count"])
+        b.instance = abi.PT_LIGHTMAP_NONE if d.get("instance") is None else int(d["instance"])
+        b.flags = int(d.get("flags", abi.PT_LIGHTMAP_TWO_SIDED if d.get("two_sided") else 0))
+        b.height, b.width = image.shape[0], image.shape[1]
+        b.dImage = image.ctypes.data
+        b.dUvs = None if uvs is None else uvs.ctypes.data
+    return table, keep
+
+
+def lightmap_lookup(bindings, tri_attrs, material_count: int, rays, hits, surfaces):
+    """The lightmap lookup on the host (PTLightmapLookupHost; include/ptmi_plugin.h Part 22).  bindings: a list of dicts as
+    lightmap_bindings takes them; tri_attrs: the scene's TRI_ATTRS records (or None when every binding has uvs) -- spans are
+    checked against their count; rays (n, 8), hits (n, 4), surfaces (n, 12) float32 rows as PathTracer.trace_rays(surface=True)
+    takes and returns them.  Returns (irradiance (n, 4) float32, binding (n,) uint32): rgb and 0 where a lightmap was found, zero
+    bits and PT_LIGHTMAP_NONE elsewhere."""
+    r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+    h = np.ascontiguousarray(hits, dtype=np.float32).reshape(-1, 4)
+    s = np.ascontiguousarray(surfaces, dtype=np.float32).reshape(-1, 12)
+    n = r.shape[0]
+    assert h.shape[0] == n and s.shape[0] == n, (r.shape, h.shape, s.shape)
+    table, keep = lightmap_bindings(bindings)
+    attrs = None if tri_attrs is None else np.ascontiguousarray(tri_attrs)
+    assert attrs is None or attrs.dtype.itemsize == 128, attrs.dtype
+    out, which = np.empty((n, 4), np.float32), np.empty(n, np.uint32)
+    lib = load_library()
+    if not lib.PTLightmapLookupHost(table, 0 if table is None else len(table), None if attrs is None else attrs.ctypes.data, 0 if attrs is None else attrs.shape[0],
+                                    int(material_count), r.ctypes.data, h.ctypes.data, s.ctypes.data, n, out.ctypes.data, which.ctypes.data):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTLightmapLookupHost failed: " + lib.PTGetBVHBuildError().decode())
+    del keep
+    return out, which
 
 
 def build_tlas(instances: np.ndarray):
