@@ -103,10 +103,15 @@ __global__ __launch_bounds__(256, 4) void pt_wf_trace(DScene S, PTWfBuffers B, u
 // A wave owns PT_WF_RANGE consecutive slots = 3 * PT_WF_RANGE potential rays, enumerated kind-major (all bounce
 // rays of the range, then the environment shadow rays, then the light shadow rays: neighbours in the enumeration are
 // neighbours on screen and of one kind, i.e. as coherent as this path tracer gets).  The wave keeps 64 resumable
-// traversals in flight; whenever PT_WF_REFILL or more lanes have retired their ray it scans the next 64 candidates
-// (one coalesced read of the flag words), ballots which exist, and compacts them into the idle lanes through a
-// 64-entry LDS exchange (rank-of-set-bit on both masks).  Rays of very different length therefore never hold a wave
-// hostage, and the enumeration order -- hence every result -- is independent of timing.
+// traversals in flight.  The main launch reads its range's flag words once, when the wave starts (one or two coalesced
+// loads per lane, requested together), ballots which rays exist kind by kind and writes them, in enumeration order, into
+// a list of 16-bit items in LDS (3 * RANGE entries: 768 bytes, 4,868 per workgroup, under the 5,120 that 32 workgroups
+// per CU allow).  Whenever PT_WF_REFILL or more lanes have retired their ray, the idle lane of rank r takes
+// list[cursor + r]: a refill round is one ballot, one rank and one LDS read in front of the ray fetch, no flag load.
+// (Before the list every round scanned the next 64 candidates' flag words and compacted them through a 64-entry LDS
+// exchange -- compact_candidates, which the HAS_TLAS, persistent and fused kernels still use -- and a steady-phase
+// range of ~340 rays was scanned about 19 times; profiles/trace_candidate_list_ab.md.)  Rays of very different length
+// never hold a wave hostage, and the enumeration order -- hence every result -- is independent of timing.
 // ------------------------------------------------------------------------------------------
 #ifndef PT_WF_RANGE
 #define PT_WF_RANGE 128u        // largest slots-per-wave the launcher may pick (power of two): two 8x8 tiles x 3 kinds = 384 candidate rays.
@@ -115,8 +120,9 @@ __global__ __launch_bounds__(256, 4) void pt_wf_trace(DScene S, PTWfBuffers B, u
 #define PT_WF_STAT_ROW_SETS 4u   // statRows holds this many x numSlots/64 counter rows (pt_wf_arena_layout)
 static_assert(PT_WF_RANGE >= 64u && (PT_WF_RANGE & (PT_WF_RANGE - 1u)) == 0u && PT_WF_STAT_ROW_SETS >= 3u,
               "one counter row per trace wave: the main trace launch uses rows numSlots/64 + wave, the tail launch rows 2 x numSlots/64 + wave");
+static_assert(3u * PT_WF_RANGE <= 65535u, "an item of the main launch's candidate list (kind * RANGE + offset) is a uint16_t");
 #ifndef PT_WF_REFILL
-#define PT_WF_REFILL 16u        // refill when at least this many lanes are idle
+#define PT_WF_REFILL 16u        // refill when at least this many lanes are idle (with the candidate list: 8 / 12 / 16 / 24 read 5,907 / 5,948 / 5,914-5,953 / 5,859 Mrays/s)
 #endif
 #ifndef PT_WF_TRI_PARK
 #define PT_WF_TRI_PARK 4u       // two-phase wave iteration (ray_tri_one / ray_node_one): lanes with triangles pending wait until that many lanes
@@ -304,7 +310,9 @@ template <bool STATS, bool TAIL, uint32_t RANGE>
 __global__ __launch_bounds__(64, PT_WF_TRACE_MIN_WAVES) void pt_wf_trace_refill(DScene S, PTWfBuffers B, uint32_t iteration)
 {
     __shared__ uint2 s_stack[PT_WF_LDS_STACK][64];
-    __shared__ uint32_t s_xchg[TAIL ? PT_WF_TAIL_GROUP * (PT_WF_SUSPEND ? PT_WF_SUSPEND : 1u) : 64u];
+    // tail launch: the packed record indices (32 bits each); main launch: the candidate list, 3 * RANGE items of 16 bits
+    __shared__ uint32_t s_xchg[TAIL ? PT_WF_TAIL_GROUP * (PT_WF_SUSPEND ? PT_WF_SUSPEND : 1u) : 3u * RANGE / 2u];
+    static_assert(TAIL || sizeof(s_stack) + sizeof(s_xchg) + sizeof(uint32_t) <= 5120u, "32 one-wave workgroups per CU must fit 160 KB of LDS: 5,120 bytes each");
     // the wave's counter row is parked in LDS until the end: kept in a register it is the one value the compiler spilled to
     // scratch, and ANY scratch costs this kernel its occupancy (see TravStackT)
     __shared__ uint32_t s_gw;
@@ -315,10 +323,33 @@ __global__ __launch_bounds__(64, PT_WF_TRACE_MIN_WAVES) void pt_wf_trace_refill(
     pt_lds_u32 xchg = (pt_lds_u32)&s_xchg[0];
     if (lane == 0u) s_gw = gw;
 
-    // candidates: the main launch scans the flag words of its slot range, kind-major; the tail launch walks the records that
-    // its PT_WF_TAIL_GROUP source waves left behind (their indices, packed, in s_xchg)
-    uint32_t nItems = 3u * RANGE;
-    if (TAIL) {
+    // candidates: the main launch reads the flag words of its slot range ONCE and lists the rays that exist, kind-major, in s_xchg
+    // (16-bit items, kind * RANGE + offset); the tail launch walks the records that its PT_WF_TAIL_GROUP source waves left behind
+    // (their indices, packed, in s_xchg).  Either way a refill round hands list[cursor ...] to the idle lanes in order.
+    uint32_t nItems = 0u;
+    if (!TAIL) {
+        const pt_lds_u16 list = (pt_lds_u16)&s_xchg[0];
+        constexpr uint32_t kWords = RANGE / 64u;                      // flag words per lane: both loads are requested together
+        uint32_t f[kWords];
+        bool in[kWords];
+#pragma unroll
+        for (uint32_t w = 0; w < kWords; ++w) {
+            const uint32_t slot = slotBase + w * 64u + lane;
+            in[w] = slot < B.numSlots;
+            f[w] = in[w] ? B.flags[slot] : 0u;
+        }
+#pragma unroll
+        for (uint32_t kind = 0; kind < 3u; ++kind) {
+#pragma unroll
+            for (uint32_t w = 0; w < kWords; ++w) {
+                const bool valid = in[w] && ray_exists(f[w], kind);
+                const unsigned long long V = __ballot(valid);
+                if (valid) list[nItems + rank_below(V)] = (uint16_t)(kind * RANGE + w * 64u + lane);
+                nItems += (uint32_t)__popcll(V);                      // wave-uniform: the number of rays so far
+            }
+        }
+        __builtin_amdgcn_wave_barrier();                              // no ray of the range: the loop below falls through to the zero report
+    } else {
         const uint32_t s0 = gw * PT_WF_TAIL_GROUP;
         uint32_t c = 0u;
         if (lane < PT_WF_TAIL_GROUP && s0 + lane < numWaves) c = B.suspCount[s0 + lane];
@@ -354,20 +385,16 @@ __global__ __launch_bounds__(64, PT_WF_TRACE_MIN_WAVES) void pt_wf_trace_refill(
         // ---- refill: compact the next candidates into the idle lanes
         while (cursor < nItems && (nIdle >= PT_WF_REFILL || nIdle == 64u)) {
             if (!TAIL) {
-                const uint32_t item = cursor + lane;
-                const uint32_t kind = item / RANGE;
-                const uint32_t slot = slotBase + (item & (RANGE - 1u));
-                bool valid = item < nItems && slot < B.numSlots;
-                if (valid) valid = ray_exists(B.flags[slot], kind);
-                const Compaction c = compact_candidates(xchg, !have, nIdle, valid, item);
-                if (!have && c.rankI < c.take) {
-                    const uint32_t it = xchg[c.rankI];
+                const uint32_t rankI = rank_below(__ballot(!have));
+                const uint32_t left = nItems - cursor;
+                const uint32_t take = nIdle < left ? nIdle : left;
+                if (!have && rankI < take) {
+                    const uint32_t it = ((pt_lds_u16)&s_xchg[0])[cursor + rankI];
                     myKind = it / RANGE;
                     mySlot = slotBase + (it & (RANGE - 1u));
                     have = start_ray(B, mySlot, myKind, rs, cn);
                 }
-                __builtin_amdgcn_wave_barrier();
-                cursor += c.consumed;
+                cursor += take;
             } else {
                 const uint32_t rankI = rank_below(__ballot(!have));
                 const uint32_t left = nItems - cursor;
