@@ -15,6 +15,7 @@
 //   * int(RandomFloat*LightCount) is clamped to LightCount-1 (RandomFloat can return exactly 1.0).
 #include "pt_oracle.h"
 #include "ptmi_math.h"
+#include "ptmi_math_switch.h"
 
 #include <atomic>
 #include <cstring>
@@ -1597,31 +1598,14 @@ float oracle_random_float(uint32_t* state) { return pt_random_float(state); }
 
 float oracle_math(int fn, float x, float y)
 {
-    switch (fn) {
-    case 0: return pt_sin(x);
-    case 1: return pt_cos(x);
-    case 2: return pt_log(x);
-    case 3: return pt_log2(x);
-    case 4: return pt_exp2(x);
-    case 5: return pt_pow(x, y);
-    case 6: return pt_acos(x);
-    case 7: return pt_asin(x);
-    case 8: return pt_sqrt(x);
-    case 9: return pt_rcp(x);
-    case 10: return pt_atan2(x, y);
-    case 11: return pt_fmod(x, y);
-    case 12: return pt_wrap01(x);
-    case 13: {                                    // the literal loops of util/texture.hlsl:41-48 (with this project's guard)
-        float u = x;
-        if (pt_abs(u) >= 16777216.0f) u = 0.0f;
-        while (u > 1.0f) u -= 1.0f;
-        while (u < 0.0f) u += 1.0f;
-        return u;
-    }
-    case 14: return pt_unorm8((uint32_t)x);       // the kernels' form of a texel channel ...
-    case 15: return (float)((uint32_t)x & 0xFFu) / 255.0f;    // ... and the division of util/texture.hlsl that the oracle performs
-    default: return 0.0f;
-    }
+    // 14, 15 take the byte as a number; every other function takes the floats themselves (include/ptmi_math_switch.h)
+    const uint32_t xbits = (fn == 14 || fn == 15) ? (uint32_t)x : pt_asuint(x);
+    return pt_asfloat(pt_math_switch(fn, xbits, pt_asuint(y)));
+}
+
+void oracle_math_n(int fn, const uint32_t* xbits, const uint32_t* ybits, uint64_t n, uint32_t* outbits)
+{
+    for (uint64_t i = 0; i < n; i++) outbits[i] = pt_math_switch(fn, xbits[i], ybits[i]);
 }
 
 float oracle_env_probe(const PTSceneDesc* scene, const PTFrameParams* params, int what, const float* in, uint64_t n, float* out)

@@ -80,6 +80,8 @@ int oracle_trace_rays(const PTSceneDesc* scene, const OracleRay* rays, uint64_t 
 /* Scalar entry points for unit tests. */
 float    oracle_random_float(uint32_t* state);                       /* util/random.hlsl:12-16 */
 float    oracle_math(int fn, float x, float y);                      /* ptmi_math.h: 0 sin 1 cos 2 log 3 log2 4 exp2 5 pow 6 acos 7 asin 8 sqrt 9 rcp 10 atan2(x = y-arg, y = x-arg) 11 fmod 12 wrap01 (closed form) 13 wrap01 (literal loops) */
+/* The same functions and the rest of the header (fn 16-32: ptmi_math_switch.h) over n elements, operands and results as bit patterns. */
+void     oracle_math_n(int fn, const uint32_t* xbits, const uint32_t* ybits, uint64_t n, uint32_t* outbits);
 /* Evaluates / samples the Disney BSDF in isolation (util/brdf.hlsl:114-340).
  * material: 32 floats of MaterialData (no textures); V, N, L world-space; returns f via out[0..2], pdf out[3]. */
 void     oracle_eval_brdf(const float* material, const float* V, const float* N, const float* L, float eta, float* out);

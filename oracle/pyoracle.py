@@ -72,6 +72,8 @@ def load_oracle():
         lib.oracle_random_float.argtypes = [C.POINTER(C.c_uint32)]
         lib.oracle_math.restype = C.c_float
         lib.oracle_math.argtypes = [C.c_int, C.c_float, C.c_float]
+        lib.oracle_math_n.restype = None
+        lib.oracle_math_n.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         lib.oracle_eval_brdf.restype = None
         lib.oracle_eval_brdf.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
         lib.oracle_sample_brdf.restype = None
@@ -90,6 +92,20 @@ def load_oracle():
         lib.oracle_env_probe.argtypes = [C.POINTER(abi.PTSceneDesc), C.POINTER(abi.PTFrameParams), C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
         _oracle = lib
     return _oracle
+
+
+def math_n(fn: int, xbits: np.ndarray, ybits: np.ndarray = None, lib=None) -> np.ndarray:
+    """include/ptmi_math.h, function `fn` of include/ptmi_math_switch.h, over arrays of uint32 bit patterns; returns the result bits.
+    `lib`: another build of the oracle exporting oracle_math_n (the clang build), loaded by the caller."""
+    lib = lib or load_oracle()
+    x = np.ascontiguousarray(xbits, dtype=np.uint32)
+    y = np.zeros_like(x) if ybits is None else np.ascontiguousarray(ybits, dtype=np.uint32)
+    assert x.ndim == 1 and x.shape == y.shape
+    out = np.empty_like(x)
+    fn_n = lib.oracle_math_n
+    fn_n.restype, fn_n.argtypes = None, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    fn_n(fn, x.ctypes.data, y.ctypes.data, x.size, out.ctypes.data)
+    return out
 
 
 _ref_plugin = None

@@ -4,7 +4,9 @@ The list adds 512 bytes of LDS to a one-wave workgroup, and 32 such workgroups m
 each); the kernel must stay at 8 waves per SIMD (<= 64 VGPRs, no scratch).  The change touched nothing else in unit a: the TAIL
 instantiations and every pt_wf_shade are, instruction for instruction, what the commit before it compiled to --
 tests/golden/wavefront_unit_a_streams.txt holds the instruction count and the SHA-256 of each of those streams (labels
-renumbered, comments dropped; tests/kernel_streams.py), taken from that commit with the same compiler."""
+renumbered, comments dropped; tests/kernel_streams.py), taken from that commit with the same compiler.  The pt_wf_shade streams
+were taken again when pt_exp2's scale was clamped at the top (include/ptmi_math.h; pow is in the shade step): 10 instructions more
+in each of the six, the tail streams untouched."""
 import os
 import shutil
 
