@@ -176,7 +176,7 @@ struct PTWfBuffers {
     char* rpTemp;               // the temporary SoA region of a repack: rpCapacity slots x PT_WF_REPACK_SLOT_BYTES
     uint32_t rpCapacity;        // numSlots / 2
 };
-#define PT_WF_REPACK_SLOT_BYTES 204u     // flags, rng, pixelOf (4 each) + three 32-byte ray records + rad, thr, color, envC, lightC, pthr (16 each)
+#define PT_WF_REPACK_SLOT_BYTES 184u     // flags, pixelOf (4 each) + three 32-byte ray records + rad, thr, color, envC, lightC (16 each): rng and pthr ride in their .w lanes
 
 // The arena of a state set: every array of PTWfBuffers carved from one allocation of pt_wf_arena_bytes() bytes.  Both are defined
 // in pt_wavefront.hip, by the one of its two compilations that every library links (-DPT_WF_TU_B), so the layout is by

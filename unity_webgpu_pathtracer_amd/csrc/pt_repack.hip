@@ -26,17 +26,20 @@ namespace {
 //     move out   the r-th live slot of block b -> position prefix[b] + r of the temporary SoA region (stable: still screen order)
 //     move back  temporary [0, L) -> slots [0, L); every slot of [L, E) becomes DONE
 // Both moves exit at once when the decision word says no.  What moves is what is live between a shade and a trace launch: flags,
-// rng, the three ray records, rad, thr, color, envC, lightC, pthr and the slot's pixel index (204 bytes); hit, hit2, occl and the
-// suspension records are dead there.  Going through a temporary and BACK, not switching regions, keeps every other kernel as it
-// is: no second set of base pointers, no extent.  The temporary holds numSlots / 2 slots and aliases stackSpill + susp, which the
-// trace launches fill before they read them (pt_wf_arena_layout, pt_wavefront.hip, proves the room or carves new memory).
+// the three ray records, rad, thr, color, envC, lightC and the slot's pixel index (184 bytes); the RNG state and the pending
+// throughput of a repacked sequence ride in the fourth lanes of rad, envC, lightC and thr (pt_wf_state.h), so B.rng and B.pthr hold
+// nothing of it; hit, hit2, occl and the suspension records are dead there.  Going through a temporary and BACK, not switching
+// regions, keeps every other kernel as it is: no second set of base pointers, no extent.  The temporary holds numSlots / 2 slots
+// and aliases stackSpill + susp, which the trace launches fill before they read them (pt_wf_arena_layout, pt_wavefront.hip,
+// proves the room or carves new memory).
 // ------------------------------------------------------------------------------------------
 static_assert(PT_REPACK_STATE_DONE == PS_DONE && PT_REPACK_BLOCK == 256u, "repack_rule.h restates the state code and the block");
 
-// the SoA layout of the temporary region for rpCapacity slots: twelve float4 planes in PT_F4_* order (a ray record takes two),
-// then three planes of 32-bit words (flags, rng, pixelOf)
-PT_DEV uint32_t* rp_u32(const PTWfBuffers& B, uint32_t k) { return (uint32_t*)((float4*)B.rpTemp + (size_t)PT_F4_HIT * B.rpCapacity) + (size_t)k * B.rpCapacity; }
-static_assert(PT_F4_HIT == 12u && PT_F4_HIT * 16u + 3u * 4u == PT_WF_REPACK_SLOT_BYTES, "the moved state is the twelve float4 planes before PT_F4_HIT and three words");
+// the SoA layout of the temporary region for rpCapacity slots: eleven float4 planes in PT_F4_* order (a ray record takes two),
+// then two planes of 32-bit words (flags, pixelOf)
+PT_DEV uint32_t* rp_u32(const PTWfBuffers& B, uint32_t k) { return (uint32_t*)((float4*)B.rpTemp + (size_t)PT_F4_PTHR * B.rpCapacity) + (size_t)k * B.rpCapacity; }
+static_assert(PT_F4_PTHR == 11u && PT_F4_LIGHTC + 1u == PT_F4_PTHR && PT_F4_PTHR * 16u + 2u * 4u == PT_WF_REPACK_SLOT_BYTES,
+              "the moved state is the eleven float4 planes before PT_F4_PTHR and two words");
 
 // count and scan: the first two steps of pt_compact.h over the live slots
 __global__ __launch_bounds__(256) void pt_wf_repack_count(PTWfBuffers B)
@@ -74,12 +77,12 @@ __global__ __launch_bounds__(1024) void pt_wf_repack_scan(PTWfBuffers B, uint32_
     }
 }
 
-// One slot's moved state, from one layout to the other: twelve float4 planes at a stride (PT_F4_* order: a ray record is two
-// consecutive float4 at index 2 * slot of a plane two strides wide) and three planes of words.  All loads are requested before the
+// One slot's moved state, from one layout to the other: eleven float4 planes at a stride (PT_F4_* order: a ray record is two
+// consecutive float4 at index 2 * slot of a plane two strides wide) and two planes of words.  All loads are requested before the
 // first store; spelled out plane by plane, so that nothing is indexed at run time and nothing goes to scratch.
-struct RpLayout { float4* f4; size_t stride; uint32_t *flags, *rng, *pixelOf; };
-PT_DEV RpLayout rp_set_layout(const PTWfBuffers& B) { return RpLayout{B.f4base, B.f4stride, B.flags, B.rng, B.pixelOf}; }
-PT_DEV RpLayout rp_temp_layout(const PTWfBuffers& B) { return RpLayout{(float4*)B.rpTemp, B.rpCapacity, rp_u32(B, 0u), rp_u32(B, 1u), rp_u32(B, 2u)}; }
+struct RpLayout { float4* f4; size_t stride; uint32_t *flags, *pixelOf; };
+PT_DEV RpLayout rp_set_layout(const PTWfBuffers& B) { return RpLayout{B.f4base, B.f4stride, B.flags, B.pixelOf}; }
+PT_DEV RpLayout rp_temp_layout(const PTWfBuffers& B) { return RpLayout{(float4*)B.rpTemp, B.rpCapacity, rp_u32(B, 0u), rp_u32(B, 1u)}; }
 PT_DEV void rp_copy(const RpLayout& s, size_t si, const RpLayout& d, size_t di, uint32_t flagsWord)
 {
     const float4* s0 = s.f4 + PT_F4_RAY0 * s.stride + 2u * si;
@@ -87,15 +90,15 @@ PT_DEV void rp_copy(const RpLayout& s, size_t si, const RpLayout& d, size_t di, 
     const float4* s2 = s.f4 + PT_F4_RAY2 * s.stride + 2u * si;
     const float4 a0 = s0[0], a1 = s0[1], b0 = s1[0], b1 = s1[1], c0 = s2[0], c1 = s2[1];
     const float4 rad = s.f4[PT_F4_RAD * s.stride + si], thr = s.f4[PT_F4_THR * s.stride + si], col = s.f4[PT_F4_COLOR * s.stride + si];
-    const float4 envC = s.f4[PT_F4_ENVC * s.stride + si], lightC = s.f4[PT_F4_LIGHTC * s.stride + si], pthr = s.f4[PT_F4_PTHR * s.stride + si];
-    const uint32_t rng = s.rng[si], pix = s.pixelOf[si];
+    const float4 envC = s.f4[PT_F4_ENVC * s.stride + si], lightC = s.f4[PT_F4_LIGHTC * s.stride + si];
+    const uint32_t pix = s.pixelOf[si];
     float4* d0 = d.f4 + PT_F4_RAY0 * d.stride + 2u * di;
     float4* d1 = d.f4 + PT_F4_RAY1 * d.stride + 2u * di;
     float4* d2 = d.f4 + PT_F4_RAY2 * d.stride + 2u * di;
     d0[0] = a0; d0[1] = a1; d1[0] = b0; d1[1] = b1; d2[0] = c0; d2[1] = c1;
     d.f4[PT_F4_RAD * d.stride + di] = rad; d.f4[PT_F4_THR * d.stride + di] = thr; d.f4[PT_F4_COLOR * d.stride + di] = col;
-    d.f4[PT_F4_ENVC * d.stride + di] = envC; d.f4[PT_F4_LIGHTC * d.stride + di] = lightC; d.f4[PT_F4_PTHR * d.stride + di] = pthr;
-    d.flags[di] = flagsWord; d.rng[di] = rng; d.pixelOf[di] = pix;
+    d.f4[PT_F4_ENVC * d.stride + di] = envC; d.f4[PT_F4_LIGHTC * d.stride + di] = lightC;
+    d.flags[di] = flagsWord; d.pixelOf[di] = pix;
 }
 
 __global__ __launch_bounds__(256) void pt_wf_repack_out(PTWfBuffers B)
@@ -128,7 +131,9 @@ __global__ __launch_bounds__(256) void pt_wf_repack_back(PTWfBuffers B)
 // ------------------------------------------------------------------------------------------
 // shade and cleanup of a repacked sequence: pt_wf_shade / pt_wf_cleanup over PTTileMap (pt_wavefront.hip) with the pixel slot taken
 // from B.pixelOf -- a slot's path belongs to the pixel that array says -- and a finished pixel's sample sum left in
-// B.pixsum[that pixel slot], because the slot itself may be given to another path (shade_slot's PIXSUM, as in schedule 4).
+// B.pixsum[that pixel slot], because the slot itself may be given to another path (shade_slot's PIXSUM, as in schedule 4).  Only
+// these kernels exist for a repacked sequence, so its state has a layout of its own (shade_slot's PACKED, cleanup_slots' REPACK):
+// 45 bytes fewer per live slot and step (profiles/packed_state_ab.md).
 // Same line as the shade kernel's: <= 128 VGPRs, no scratch, four waves per SIMD (tests/test_repack.py).
 // ------------------------------------------------------------------------------------------
 template <bool STATS>
@@ -140,7 +145,7 @@ __global__ __launch_bounds__(PT_WF_SHADE_BLOCK, PT_WF_SHADE_MIN_WAVES) void pt_w
     if (vb == 0u && threadIdx.x < PT_WF_SHARDS) B.chunkHeads[threadIdx.x * 32u] = 0u;   // as pt_wf_shade does
     const uint32_t f = B.flags[slot];
     Counters cn = {};
-    if (fl_state(f) != PS_DONE) shade_slot<STATS, true, PTTileMap>(S, P, tm, B, slot, B.pixelOf[slot], f, cn, vb * PT_WF_SHADE_BLOCK);
+    if (fl_state(f) != PS_DONE) shade_slot<STATS, true, PTTileMap, true>(S, P, tm, B, slot, B.pixelOf[slot], f, cn, vb * PT_WF_SHADE_BLOCK);
     flush_counters<STATS>(cn, B.statRows, vb * (PT_WF_SHADE_BLOCK / 64u) + (threadIdx.x >> 6), threadIdx.x & 63u);
 }
 

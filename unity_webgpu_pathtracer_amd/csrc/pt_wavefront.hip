@@ -49,7 +49,8 @@ __global__ __launch_bounds__(256) void pt_wf_init(PTFrameParams P, PTBatch batch
             if (kListMap<MAP>) currentSample = base + pass * (P.SamplesPerPass > 1 ? (uint32_t)P.SamplesPerPass : 1u);
             path_init(P, seedRoot, currentSample, px, py, py * P.OutputWidth + px, r, cn);
         }
-        store_path(B, slot, r, false);
+        // over the frame's own blocks the sequence may be a repacked one, which keeps the RNG state in rad.w (pt_wf_state.h)
+        store_path(B, slot, r, false, !kListMap<MAP> && !kRayMap<MAP> ? pt_asfloat(r.rng) : 0.0f);
     }
     // every lane of the wave takes part in the reduction (a lane that had returned would be read as garbage)
     flush_counters<false>(cn, B.statRows, blockIdx.x * 4u + (threadIdx.x >> 6), threadIdx.x & 63u);
@@ -1150,7 +1151,7 @@ size_t pt_wf_arena_layout(char* base, uint32_t numSlots, uint32_t residentWaves,
     // repack: the pixel index of a slot, the block counts, the decision, and the temporary region of numSlots / 2 slots.  Between a
     // shade and a trace launch stackSpill and susp hold nothing (a trace launch writes an entry or a record before it reads it),
     // and they were carved back to back: the region lies over them when they are large enough -- they are, for every set this
-    // file sizes today (96 + 12 bytes per slot at 128 slots per trace wave against 102) --, in memory of its own otherwise.
+    // file sizes today (96 + 12 bytes per slot at 128 slots per trace wave against 92) --, in memory of its own otherwise.
     B.pixelOf = (uint32_t*)carve(n * 4);
     B.rpPrefix = (uint32_t*)carve((n >> 8) * 4 + 4);
     B.rpCtl = (uint32_t*)carve(ptrepack::PT_REPACK_CTL_WORDS * 4);

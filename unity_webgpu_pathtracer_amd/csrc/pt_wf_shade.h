@@ -97,7 +97,9 @@ PT_DEV void ray_path_init(const PTRayMap& rm, uint32_t slot, PathRegs& r, Counte
 #endif
 
 // The path state of one slot as the flags word f describes it (state != DONE).  Used by the cleanup kernel; the shade kernel
-// requests the same words all at once (shade_slot).
+// requests the same words all at once (shade_slot).  PACKED: the layout of a repacked sequence (pt_wf_state.h) -- the RNG state
+// and the pending throughput come from the fourth lanes of rad, envC, lightC and thr; B.rng and B.pthr are not touched.
+template <bool PACKED = false>
 PT_DEV void load_path(const PTWfBuffers& B, uint32_t slot, uint32_t f, PathRegs& r)
 {
     r.state = fl_state(f);
@@ -107,21 +109,28 @@ PT_DEV void load_path(const PTWfBuffers& B, uint32_t slot, uint32_t f, PathRegs&
     r.green = (f >> 6) & 1u;
     r.sampleIdx = (f >> 7) & 0xFFFu;
     r.depth = f >> 19;
-    r.rng = B.rng[slot];
+    if constexpr (!PACKED) r.rng = B.rng[slot];
     float4 q;
     q = B.ray[0][2u * slot]; r.ro = xyz(q); r.scatterPdf = q.w;
     q = B.ray[0][2u * slot + 1u]; r.rd = xyz(q); r.maxRoughness = q.w;
-    r.radiance = xyz(B.rad[slot]);
-    r.throughput = xyz(B.thr[slot]);
+    q = B.rad[slot]; r.radiance = xyz(q);
+    if constexpr (PACKED) r.rng = pt_asuint(q.w);
+    const float4 qthr = B.thr[slot];
+    r.throughput = xyz(qthr);
     r.color = xyz(B.color[slot]);
     r.env.dir = mk3(0.0f); r.light.dir = mk3(0.0f); r.neeOrigin = mk3(0.0f);
     r.env.contribution = mk3(0.0f); r.light.contribution = mk3(0.0f); r.pendThroughput = mk3(0.0f);
     if (r.hasPending) {
-        r.env.contribution = xyz(B.envC[slot]);
-        r.light.contribution = xyz(B.lightC[slot]);
-        r.pendThroughput = xyz(B.pthr[slot]);
+        const float4 qe = B.envC[slot], ql = B.lightC[slot];
+        r.env.contribution = xyz(qe);
+        r.light.contribution = xyz(ql);
+        if constexpr (PACKED) r.pendThroughput = mk3(qe.w, ql.w, qthr.w);
+        else r.pendThroughput = xyz(B.pthr[slot]);
     }
 }
+
+// non-zero iff a and b differ in a bit
+PT_DEV uint32_t differing_bits(v3 a, v3 b) { return (pt_asuint(a.x) ^ pt_asuint(b.x)) | (pt_asuint(a.y) ^ pt_asuint(b.y)) | (pt_asuint(a.z) ^ pt_asuint(b.z)); }
 
 // Everything the shade step does for one slot (flags word f already read, state != DONE).
 // Every word of the slot's state is requested up front in ONE batch, whether the flags say it is meaningful or not (the pending
@@ -132,21 +141,37 @@ PT_DEV void load_path(const PTWfBuffers& B, uint32_t slot, uint32_t f, PathRegs&
 // every pixel has its own slot; a context's current pixel in schedule 4, which also wants the finished pixel's sample sum in
 // B.pixsum[pixelSlot]: PIXSUM).
 // wgSlot: see wf_pixel (only read under the list mapping).
-template <bool STATS, bool PIXSUM = false, class MAP = PTTileMap>
+// PACKED (with PIXSUM; the shade kernel of a repacked sequence, pt_repack.hip): the slot's state is in the packed layout of
+// pt_wf_state.h, and the step stores only what changes memory that somebody reads again --
+//   - B.rng and B.pthr are neither read nor written: the RNG state rides in rad.w, the pending throughput in envC.w, lightC.w
+//     (written by the sink with those arrays) and thr.w (every store of thr carries the current pendThroughput.z);
+//   - color is loaded with the batch, but stored only by a step that changed one of its three words: a step that folds no
+//     sample (about three in four) leaves the array alone;
+//   - a slot that ends the step DONE stores its flags word and pixsum[pixel] only: nothing reads its ray record, rad, thr or
+//     color again (the resolve reads pixsum, the cleanup skips DONE slots, a repack overwrites or marks them).
+// Every arithmetic operation of the path is the one of the unpacked step, in the same order.
+template <bool STATS, bool PIXSUM = false, class MAP = PTTileMap, bool PACKED = false>
 PT_DEV bool shade_slot(const DScene& S, const PTFrameParams& P, const MAP& tm, const PTWfBuffers& B, uint32_t slot, uint32_t pixelSlot,
                        uint32_t f, Counters& cn, uint32_t wgSlot = 0u)
 {
     uint32_t px, py, pass, base;
     wf_pixel(tm, B, pixelSlot, wgSlot, px, py, pass, base);
-    uint32_t rng = B.rng[slot];
+    static_assert(!PACKED || (PIXSUM && !kRayMap<MAP>), "the packed layout is a repacked sequence's: frames only, sums in pixsum");
+    uint32_t rng = 0u;
+    if constexpr (!PACKED) rng = B.rng[slot];
     float4 qro = B.ray[0][2u * slot], qrd = B.ray[0][2u * slot + 1u], qrad = B.rad[slot], qthr = B.thr[slot], qcol = B.color[slot];
-    float4 qenvC = B.envC[slot], qlightC = B.lightC[slot], qpthr = B.pthr[slot], qhit = B.hit[slot];
+    float4 qenvC = B.envC[slot], qlightC = B.lightC[slot], qpthr = PACKED ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : B.pthr[slot], qhit = B.hit[slot];
     uint32_t o0 = B.occl[slot], o1 = B.occl[(size_t)B.numSlots + slot];
     float4 qhit2 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (S.hasTlas) qhit2 = B.hit2[slot];
     // pinned: left alone, the compiler sinks each load into the branch that uses it again
+    if constexpr (PACKED)
+        asm volatile("" : "+v"(qro.x), "+v"(qrd.x), "+v"(qrad.x), "+v"(qthr.x), "+v"(qcol.x), "+v"(qenvC.x), "+v"(qlightC.x),
+                          "+v"(qhit.x), "+v"(o0), "+v"(o1), "+v"(qhit2.x));
+    else
     asm volatile("" : "+v"(rng), "+v"(qro.x), "+v"(qrd.x), "+v"(qrad.x), "+v"(qthr.x), "+v"(qcol.x), "+v"(qenvC.x), "+v"(qlightC.x), "+v"(qpthr.x),
                       "+v"(qhit.x), "+v"(o0), "+v"(o1), "+v"(qhit2.x));
+    if constexpr (PACKED) { rng = pt_asuint(qrad.w); qpthr = make_float4(qenvC.w, qlightC.w, qthr.w, 0.0f); }
     PathRegs r;
     r.state = fl_state(f);
     r.hasPending = fl_pending(f);
@@ -183,11 +208,30 @@ PT_DEV bool shade_slot(const DScene& S, const PTFrameParams& P, const MAP& tm, c
             B.ray[1][2u * s2 + 1u] = f4(q.env.dir, 0.0f);
             B.ray[2][2u * s2] = f4(q.neeOrigin, 0.0f);
             B.ray[2][2u * s2 + 1u] = f4(q.light.dir, 0.0f);
-            B.envC[s2] = f4(q.env.contribution, 0.0f);
-            B.lightC[s2] = f4(q.light.contribution, 0.0f);
-            B.pthr[s2] = f4(q.pendThroughput, 0.0f);
+            B.envC[s2] = f4(q.env.contribution, PACKED ? q.pendThroughput.x : 0.0f);
+            B.lightC[s2] = f4(q.light.contribution, PACKED ? q.pendThroughput.y : 0.0f);
+            if constexpr (!PACKED) B.pthr[s2] = f4(q.pendThroughput, 0.0f);
         }
     };
+    // PACKED: whether the step changes color.  Keeping the three loaded words to the end for that would cost three registers
+    // across sample_brdf, and the kernel sits on its 128-VGPR line.  Only a fold changes color, and a step folds in two places:
+    // in path_step's head (the deferred finish of an overlapped sample) and in its path_end_sample.  So the head is run HERE --
+    // the same calls in the same order; path_step then finds nothing pending and no overlapped state, and its own head does
+    // nothing -- and color is compared once after it and once at the end, each time against the value it had just before.
+    // The result is ONE word, non-zero iff a word of color changed, pinned so that it is formed there and the old color dies.
+    [[maybe_unused]] uint32_t colorDiff = 0u;
+    [[maybe_unused]] v3 colorBefore = r.color;
+    if constexpr (PACKED) {
+        const bool deferred = path_overlapped(r);
+        path_apply_pending(r, occEnv, occLight);
+        if (deferred) {
+            path_fold_sample(P, r);
+            path_reset_sample(r);
+        }
+        colorDiff = differing_bits(r.color, colorBefore);
+        asm volatile("" : "+v"(colorDiff));
+        colorBefore = r.color;
+    }
     // OVERLAP (pt_device.h): a sample that ends with its NEE pending starts its successor's ray in this step, so the slot's next
     // trace round carries the camera ray next to the two shadow rays instead of the shadow rays alone
     if constexpr (kRayMap<MAP>)
@@ -198,6 +242,16 @@ PT_DEV bool shade_slot(const DScene& S, const PTFrameParams& P, const MAP& tm, c
     // thirteen 64-bit load addresses stay in registers across the whole step to be reused by these stores
     uint32_t storeSlot = slot;
     asm volatile("" : "+v"(storeSlot));
+    if constexpr (PACKED) {
+        B.flags[storeSlot] = pack_flags(r);
+        if (r.state != PS_DONE) {
+            B.ray[0][2u * storeSlot] = f4(r.ro, r.scatterPdf);
+            B.ray[0][2u * storeSlot + 1u] = f4(r.rd, r.maxRoughness);
+            B.rad[storeSlot] = f4(r.radiance, pt_asfloat(r.rng));
+            B.thr[storeSlot] = f4(r.throughput, r.pendThroughput.z);
+            if ((colorDiff | differing_bits(r.color, colorBefore)) != 0u) B.color[storeSlot] = f4(r.color, 0.0f);
+        }
+    } else
     store_path(B, storeSlot, r, false);                             // the NEE arrays were written by the sink
     if (PIXSUM && r.state == PS_DONE) {
         uint32_t ps = pixelSlot;
@@ -212,7 +266,8 @@ PT_DEV bool shade_slot(const DScene& S, const PTFrameParams& P, const MAP& tm, c
 #endif
 // The body of the cleanup kernels: pixels still alive after the fixed number of iterations are run to completion, one lane per
 // slot with the megakernel's loop (trace <= 3 rays, path_step, repeat).  Normally a handful of lanes; correctness for any path length.
-// REPACK: the pixel of a slot is B.pixelOf's, and its sample sum goes to B.pixsum[that pixel slot] (pt_repack.hip).
+// REPACK: the pixel of a slot is B.pixelOf's, its sample sum goes to B.pixsum[that pixel slot], and its state is read from the
+// packed layout of a repacked sequence (pt_repack.hip, pt_wf_state.h).
 template <bool STATS, bool TLAS, bool REPACK, class MAP>
 PT_DEV void cleanup_slots(const DScene& S, const PTFrameParams& P, const MAP& tm, const PTWfBuffers& B, uint2 (&s_stack)[PT_LDS_STACK][256])
 {
@@ -228,7 +283,7 @@ PT_DEV void cleanup_slots(const DScene& S, const PTFrameParams& P, const MAP& tm
             const uint32_t pixelSlot = REPACK ? B.pixelOf[slot] : slot;
             wf_pixel(tm, B, pixelSlot, blk * 256u, px, py, pass, base);
             PathRegs r;
-            load_path(B, slot, f, r);
+            load_path<REPACK>(B, slot, f, r);
             if (r.hasPending) {
                 r.neeOrigin = xyz(B.ray[1][2u * slot]);
                 r.env.dir = xyz(B.ray[1][2u * slot + 1u]);

@@ -23,13 +23,18 @@ PT_DEV uint32_t fl_light(uint32_t f) { return (f >> 5) & 1u; }
 PT_DEV float4 f4(v3 v, float w) { return make_float4(v.x, v.y, v.z, w); }
 PT_DEV v3 xyz(float4 v) { return mk3(v.x, v.y, v.z); }
 
-PT_DEV void store_path(const PTWfBuffers& B, uint32_t slot, const PathRegs& r, bool writeNee)
+// The packed layout of a repacked sequence (PACKED; pt_repack.hip's kernels only): four words ride in lanes that
+// are dead everywhere else, and B.rng and B.pthr drop out of the step --
+//     rad.w = the RNG state          envC.w = pendThroughput.x          lightC.w = pendThroughput.y          thr.w = pendThroughput.z
+// radW: what goes into rad.w.  0 for everyone but pt_wf_init over PTTileMap, whose sequence may be a repacked one: it passes the
+// RNG state there as well.  A sequence that does not repack ignores the lane and overwrites it with 0.
+PT_DEV void store_path(const PTWfBuffers& B, uint32_t slot, const PathRegs& r, bool writeNee, float radW = 0.0f)
 {
     B.flags[slot] = pack_flags(r);
     B.rng[slot] = r.rng;
     B.ray[0][2u * slot] = f4(r.ro, r.scatterPdf);
     B.ray[0][2u * slot + 1u] = f4(r.rd, r.maxRoughness);
-    B.rad[slot] = f4(r.radiance, 0.0f);
+    B.rad[slot] = f4(r.radiance, radW);
     B.thr[slot] = f4(r.throughput, 0.0f);
     B.color[slot] = f4(r.color, 0.0f);
     if (writeNee) {
