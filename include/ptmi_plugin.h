@@ -2024,6 +2024,107 @@ PT_API int PTLightmapLookupHost(const PTLightmapBinding* bindings, uint32_t bind
                                 uint32_t materialCount, const PTRay* rays, const PTRayHit* hits, const PTRaySurface* surfaces, uint64_t count,
                                 PTIrradiance* out, uint32_t* outBinding);
 
+/* =====================================================================================================================
+ * Part 23: lightmap UVs.  Parts 14 to 22 rasterise, gather, filter, resolve, bind and shade from lightmap UVs that are the
+ * caller's; this part makes them: PTUnwrapCharts cuts one BLAS of the CURRENT scene into charts by facing, PTPackChartsHost
+ * places the few hundred chart rectangles in an atlas on the host, PTEmitChartUVs writes the (T, 6) float array that
+ * PTRasterizeChart and PTLightmapBinding.dUvs take.  Per-triangle work runs in kernels; no vertex and no UV crosses the bus.  An
+ * addition beside the reference's ABI, detected by symbol; PTGetVersion is unchanged.
+ *
+ * The rule (csrc/unwrap_rule.h has it in full; charts are decided on bits and integers, so any order of evaluation gives the
+ * same bytes).
+ *  - Corners.  Primitive p has corners c0, c1, c2: rows 3p .. 3p + 2 of dVertices -- 3 PTFloat4 per primitive in primIdx order,
+ *    the array PTUpdateGeometryDevice takes; the library does not check that it is what the BLAS holds --, or with NULL v0,
+ *    v0 + e1, v0 + e2 per component of the current triangle record of p.  Every component has + 0.0f applied, so -0 and +0 are
+ *    one value.  The NULL form welds less (v0 + e1 need not be the float the neighbour stores): a few more charts, a valid atlas.
+ *  - Class.  g = cross3(c1 - c0, c2 - c0).  p is excluded when a corner component is not finite or dot3(g, g) is 0 or not
+ *    finite.  Otherwise a = the axis of largest |g| (a later axis wins only by >) and cls = 2 a + (g[a] < 0).
+ *  - Charts.  Two included primitives of one class are linked when they share an edge: the same unordered pair of corner
+ *    values, all 96 bits per corner equal; an edge of three or more primitives links all of one class.  A chart is a connected
+ *    component; its label is its lowest primIdx; charts are listed in ascending label; chartOfPrim[p] is the chart's place in
+ *    that list, PT_UNWRAP_NO_CHART for an excluded p.
+ *  - Extents.  U = c[(a + 1) % 3], V = c[(a + 2) % 3]; umin, vmin, umax, vmax over the chart's corners (fp32 min / max, exact).
+ *  - Size and packing (PTPackChartsHost).  w = (uint32)ceilf((umax - umin) * texelsPerUnit) + 1 + 2 * padding, h likewise; a
+ *    product that is not finite or above 8192 does not fit.  Charts in the order h descending, w descending, label (firstPrim,
+ *    then place in the list) ascending go on shelves: x = y = shelf = 0; w > width fails; x + w > width opens a shelf (y += shelf;
+ *    x = 0; shelf = 0); the first chart of a shelf sets shelf = h; y + h > height fails; the origin is (x, y); x += w.
+ *    *rowsUsed = y + shelf whenever every width fits -- also when the height does not, so that a caller can rescale; 0 otherwise.
+ *  - UVs.  u_k = ((((U_k - umin) * texelsPerUnit) + (float)(ox + padding)) + 0.5f) / (float)width, v_k with V, vmin, oy,
+ *    height; every operator one binary32 operation.  umin lands on a texel centre: an axis-aligned a x b rectangle covers
+ *    exactly (floor(a tpu) + 1)(floor(b tpu) + 1) texels under PTRasterizeChart's inclusive edges.  Mirrored charts stay
+ *    mirrored.  An excluded primitive, and one whose chartOfPrim is not below chartCount, gets six quiet NaNs (0x7FC00000):
+ *    PTRasterizeChart leaves it out.
+ *  - Not done: overlap detection inside a chart (a surface that winds over itself while keeping one facing projects onto
+ *    itself; the lowest primitive owns the texel), mean-plane or conformal parameterisation (a face tilted 45 degrees gets 0.71 of
+ *    the density, the worst case 0.58), merging, rotation, welding by tolerance, per-instance scale.
+ *
+ * PTUnwrapCharts.  The BLAS is named as in Part 14 (the three offsets, triangleCount); reserved must be 0.  dVertices 16-byte,
+ * dChartOfPrim 4-byte, dCharts 16-byte aligned.  On the context's stream; *chartCount is read back, so THE CALL SYNCHRONISES
+ * WITH THE CONTEXT STREAM (several times: once per sweep of the component search).  dChartOfPrim == NULL and dCharts == NULL:
+ * only the count (and the stats).  count > capacity: PT_ERR_INVALID_ARG with *chartCount set and nothing written.  The steps:
+ * corners and class; vertex identity by three stable radix sorts over the z, y and x words, run heads and a scan; edge keys (lo
+ * id, hi id, class) in 64 bits, sorted, equal neighbours linked; components by hooking roots with atomicMin and full path
+ * compression until a sweep changes nothing (at most 64 sweeps, PT_ERR_HIP past that); heads compacted; extents by integer
+ * atomicMin / atomicMax on order-preserving keys.  stats (may be NULL): excluded primitives, linked edges (pairs of equal
+ * neighbours in the sorted edge list), single-triangle charts, sweeps (the one that found no change included; the only figure
+ * that depends on the order the hooks arrive in, so two calls may differ in it; the host twin reports 0).  Memory, in the
+ * context, grown on demand, kept across PTSetScene, freed by PTDestroy: 148 bytes per triangle and the sort's temporary storage.
+ * PTEmitChartUVs.  dChartOfPrim as PTUnwrapCharts wrote it; dCharts and dOrigins (x, y per chart; 8-byte aligned) are the
+ * mesh's slice of whatever list was packed, chartCount its length: several meshes share an atlas by packing their concatenated
+ * records once and emitting each mesh with its slice.  dUvs: 6 floats per primitive, 8-byte aligned.  Stream-ordered on the
+ * context's stream, not synchronising.
+ * Errors: Part 14's (no scene, NULL or misaligned pointers, only one of dChartOfPrim and dCharts, offsets that name no BLAS, a
+ * triangleCount that is not the BLAS's, a nonzero reserved field), plus a size outside 1 ... 8192, padding above 16,
+ * texelsPerUnit not finite or <= 0, a triangleCount T with 2 * bits(3 T) + 3 > 64 (bits(n): the width of n - 1).
+ * The host twins (no context, no GPU; 1, or 0 with PTGetBVHBuildError() set): tris = the BLAS's 3 * triangleCount rows as
+ * PTReadGeometry returns them (may be NULL with vertices), vertices = 3 * triangleCount rows or NULL; the desc's offsets are not
+ * read.  PTPackChartsHost is a pure host function; origins: 2 * chartCount words.
+ * ===================================================================================================================== */
+#define PT_UNWRAP_NO_CHART    0xFFFFFFFFu
+#define PT_UNWRAP_MAX_PADDING 16u
+#define PT_UNWRAP_MAX_SWEEPS  64u
+
+typedef struct PTUnwrapDesc {
+    uint32_t structSize;          /* sizeof(PTUnwrapDesc) of the caller's header; members are only appended */
+    int32_t  bvhOffset, triOffset, triAttributeOffset;
+    int32_t  triangleCount;
+    uint32_t reserved[7];         /* must be 0 */
+} PTUnwrapDesc;
+
+typedef struct PTUnwrapChart {    /* 32 bytes */
+    uint32_t firstPrim;           /* the label: the chart's lowest primIdx */
+    uint32_t cls;                 /* 2 * axis + (facing the negative direction) */
+    uint32_t triCount;
+    uint32_t reserved;            /* 0 */
+    float    umin, vmin, umax, vmax;
+} PTUnwrapChart;
+
+typedef struct PTUnwrapStats {
+    uint32_t excluded, linkedEdges, singleCharts, sweeps;
+} PTUnwrapStats;
+
+#ifdef __cplusplus
+static_assert(sizeof(PTUnwrapDesc) == 48 && sizeof(PTUnwrapChart) == 32 && sizeof(PTUnwrapStats) == 16, "Part 23 struct sizes");
+#else
+_Static_assert(sizeof(PTUnwrapDesc) == 48 && sizeof(PTUnwrapChart) == 32 && sizeof(PTUnwrapStats) == 16, "Part 23 struct sizes");
+#endif
+
+/* Device arrays, on the context's stream; synchronises (the count). */
+PT_API int PTUnwrapCharts(PTContext* ctx, const PTUnwrapDesc* desc, const PTFloat4* dVerticesOrNull, uint32_t* dChartOfPrim, PTUnwrapChart* dCharts,
+                          uint32_t capacity, uint32_t* chartCount, PTUnwrapStats* statsOrNull);
+/* Device arrays, stream-ordered on the context's stream. */
+PT_API int PTEmitChartUVs(PTContext* ctx, const PTUnwrapDesc* desc, const PTFloat4* dVerticesOrNull, const uint32_t* dChartOfPrim,
+                          const PTUnwrapChart* dCharts, const int32_t* dOrigins, uint32_t chartCount, uint32_t width, uint32_t height, uint32_t padding,
+                          float texelsPerUnit, float* dUvs);
+/* host twins, no GPU */
+PT_API int PTUnwrapChartsHost(const PTUnwrapDesc* desc, const PTFloat4* tris, const PTFloat4* verticesOrNull, uint32_t* chartOfPrim, PTUnwrapChart* charts,
+                              uint32_t capacity, uint32_t* chartCount, PTUnwrapStats* statsOrNull);
+PT_API int PTPackChartsHost(const PTUnwrapChart* charts, uint32_t chartCount, uint32_t width, uint32_t height, uint32_t padding, float texelsPerUnit,
+                            int32_t* origins, uint32_t* rowsUsed);
+PT_API int PTEmitChartUVsHost(const PTUnwrapDesc* desc, const PTFloat4* tris, const PTFloat4* verticesOrNull, const uint32_t* chartOfPrim,
+                              const PTUnwrapChart* charts, const int32_t* origins, uint32_t chartCount, uint32_t width, uint32_t height, uint32_t padding,
+                              float texelsPerUnit, float* uvs);
+
 /* Text of the last error on the calling thread ("" if none). */
 PT_API const char* PTGetLastError(void);
 /* Library/ABI version: (major << 16) | minor. */

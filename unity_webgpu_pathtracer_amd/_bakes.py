@@ -1,4 +1,4 @@
-"""PathTracer's bakes (include/ptmi_plugin.h Parts 13 to 22): irradiance gathers, lightmap charts and their filter, SH probes,
+"""PathTracer's bakes (include/ptmi_plugin.h Parts 13 to 23): irradiance gathers, lightmap charts and their filter, SH probes,
 probe volumes and placement, reflection probes, and first hits shaded from all of them -- with `ProbeVolume` and
 `ReflectionProbes`, the bakes that stay on the device."""
 import ctypes as C
@@ -583,6 +583,63 @@ class Bakes(HostCalls):
             count_image[texels.long()] = counts.to(torch.int32) if counts is not None else torch.full_like(texels, spp, dtype=torch.int32)
         count_image = count_image.reshape(max(int(height), 1), max(int(width), 1))
         return image, self._result([count_image], as_numpy=not as_tensor)
+
+    # ---- lightmap UVs (include/ptmi_plugin.h Part 23)
+    def unwrap_lightmap(self, width: int, height: int, mesh: int = None, texels_per_unit: float = None, padding: int = 2, vertices=None) -> "LightmapUnwrap":
+        """Lightmap UVs of one mesh, made on the GPU from the scene's CURRENT geometry: PTUnwrapCharts cuts the mesh into charts by
+        facing (connected triangles whose normals share their dominant axis and its sign), plugin.pack_charts places the chart
+        rectangles on shelves on the host, PTEmitChartUVs writes the UVs.  No vertex and no UV leaves the device; the chart records
+        (32 bytes per chart) do.
+
+        mesh names the BLAS as update_geometry does (None on a flat scene).  texels_per_unit: the density in the mesh's local units;
+        None = the largest one plugin.fit_chart_density finds for this atlas.  padding: empty texels around every chart (0 ... 16).
+        vertices: a (3T, 4) float32 tensor on this context's device in the BLAS's primitive order -- what update_geometry takes --,
+        None = the corners the triangle records hold, which weld a little less (a few more charts).
+        Returns a LightmapUnwrap; its uvs go unchanged into chart_receivers(uvs=), bake_lightmap(uvs=) and lightmap_binding(uvs=).
+        Raises ValueError when the charts do not fit the atlas at texels_per_unit.  Synchronises."""
+        dev = self._device
+        count = self._bvhScene.blas_spans[0 if mesh is None else mesh][3]
+        d = abi.unwrap_desc(count, self._blas_offsets(mesh))
+        d_verts = None
+        if vertices is not None:
+            d_verts, _ = self._as_rows(vertices, cols=4, strict=True)
+            assert d_verts.shape[0] == 3 * count and d_verts.device == dev, (d_verts.shape, d_verts.device)
+        v_ptr = None if d_verts is None else d_verts.data_ptr()
+        n, st = C.c_uint32(), abi.PTUnwrapStats()
+        chart_of_prim = torch.empty((count,), dtype=torch.int32, device=dev)
+        with self._ordered(dev):
+            # a mesh of a few charts: one call with room for 4096; more: the count first
+            cap = 4096
+            d_charts = torch.empty((cap, 8), dtype=torch.float32, device=dev)
+            rc = self.lib.PTUnwrapCharts(self.ctx, C.byref(d), v_ptr, chart_of_prim.data_ptr(), d_charts.data_ptr(), cap, C.byref(n), C.byref(st))
+            if rc != abi.PT_OK and n.value > cap:
+                cap = n.value
+                d_charts = torch.empty((cap, 8), dtype=torch.float32, device=dev)
+                rc = self.lib.PTUnwrapCharts(self.ctx, C.byref(d), v_ptr, chart_of_prim.data_ptr(), d_charts.data_ptr(), cap, C.byref(n), C.byref(st))
+            plugin.check(rc)
+        d_charts = d_charts[:n.value]
+        charts = d_charts.cpu().numpy().view(abi.UNWRAP_CHART_DTYPE).reshape(-1)
+        if texels_per_unit is None:
+            texels_per_unit, _ = plugin.fit_chart_density(charts, width, height, padding)
+        origins, rows = plugin.pack_charts(charts, width, height, texels_per_unit, padding)
+        if origins is None:
+            raise ValueError(f"the charts do not fit {width} x {height} at {texels_per_unit} texels per unit (rows needed: {rows}, 0 = a chart is too wide)")
+        d_origins = torch.from_numpy(origins).to(dev)
+        uvs = torch.empty((count, 6), dtype=torch.float32, device=dev)
+        with self._ordered(dev):
+            plugin.check(self.lib.PTEmitChartUVs(self.ctx, C.byref(d), v_ptr, chart_of_prim.data_ptr(), address(d_charts, "dummy"), address(d_origins, "dummy", 1),
+                                                 n.value, int(width), int(height), int(padding), float(texels_per_unit), uvs.data_ptr()))
+        return LightmapUnwrap(uvs, chart_of_prim, charts, origins, float(texels_per_unit), int(rows), st.as_dict())
+
+
+class LightmapUnwrap:
+    """What PathTracer.unwrap_lightmap returns (include/ptmi_plugin.h Part 23): uvs, the (T, 6) float32 device tensor that
+    chart_receivers, bake_lightmap and lightmap_binding take; chart_of_prim, (T,) int32 on the device (-1: an excluded triangle);
+    charts, the numpy records of abi.UNWRAP_CHART_DTYPE; origins, (n, 2) int32 numpy; texels_per_unit; rows_used; stats."""
+
+    def __init__(self, uvs, chart_of_prim, charts, origins, texels_per_unit, rows_used, stats):
+        self.uvs, self.chart_of_prim, self.charts, self.origins = uvs, chart_of_prim, charts, origins
+        self.texels_per_unit, self.rows_used, self.stats = texels_per_unit, rows_used, stats
 
 
 class ProbeVolume:

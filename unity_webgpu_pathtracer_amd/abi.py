@@ -446,6 +446,43 @@ def chart_desc(width: int, height: int, triangle_count: int, offsets=(0, 0, 0), 
     return d
 
 
+# ---- lightmap UVs (include/ptmi_plugin.h Part 23)
+PT_UNWRAP_NO_CHART = 0xFFFFFFFF
+PT_UNWRAP_MAX_PADDING = 16
+PT_UNWRAP_MAX_SWEEPS = 64
+
+
+class PTUnwrapDesc(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("bvhOffset", C.c_int32), ("triOffset", C.c_int32), ("triAttributeOffset", C.c_int32),
+                ("triangleCount", C.c_int32), ("reserved", C.c_uint32 * 7)]
+
+
+class PTUnwrapChart(C.Structure):
+    _fields_ = [("firstPrim", C.c_uint32), ("cls", C.c_uint32), ("triCount", C.c_uint32), ("reserved", C.c_uint32),
+                ("umin", C.c_float), ("vmin", C.c_float), ("umax", C.c_float), ("vmax", C.c_float)]
+
+
+class PTUnwrapStats(C.Structure):
+    _fields_ = [("excluded", C.c_uint32), ("linkedEdges", C.c_uint32), ("singleCharts", C.c_uint32), ("sweeps", C.c_uint32)]
+
+    def as_dict(self):
+        return {"excluded": self.excluded, "linked_edges": self.linkedEdges, "single_charts": self.singleCharts, "sweeps": self.sweeps}
+
+
+UNWRAP_CHART_DTYPE = [("firstPrim", "<u4"), ("cls", "<u4"), ("triCount", "<u4"), ("reserved", "<u4"), ("umin", "<f4"), ("vmin", "<f4"), ("umax", "<f4"),
+                      ("vmax", "<f4")]
+assert C.sizeof(PTUnwrapDesc) == 48 and C.sizeof(PTUnwrapChart) == 32 and C.sizeof(PTUnwrapStats) == 16
+
+
+def unwrap_desc(triangle_count: int, offsets=(0, 0, 0)) -> PTUnwrapDesc:
+    """A PTUnwrapDesc with structSize set: the BLAS by its three offsets and its triangle count."""
+    d = PTUnwrapDesc()
+    d.structSize = C.sizeof(PTUnwrapDesc)
+    d.bvhOffset, d.triOffset, d.triAttributeOffset = (int(o) for o in offsets)
+    d.triangleCount = int(triangle_count)
+    return d
+
+
 # ---- the lightmap denoiser (include/ptmi_plugin.h Part 17)
 PT_LMFILTER_MAX_ITERATIONS = 8
 PT_LMFILTER_MAX_NORMAL_POWER = 7

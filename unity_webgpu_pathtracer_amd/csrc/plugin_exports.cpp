@@ -25,6 +25,7 @@
 #include "shade_rule.h"
 #include "lightmap_lookup_rule.h"
 #include "repack_rule.h"
+#include "unwrap_rule.h"
 #include "ptmi_plugin.h"
 
 namespace {
@@ -342,6 +343,47 @@ PT_API int PTLightmapLookupHost(const PTLightmapBinding* bindings, uint32_t bind
                                 PTIrradiance* out, uint32_t* outBinding)
 {
     if (!ptlm::lookup_host(bindings, bindingCount, attrs, attrCount, materialCount, rays, hits, surfaces, count, out, outBinding, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+// Lightmap UVs on the host (unwrap_host.cpp; Part 23 has the rule).  No GPU involved.
+namespace {
+bool unwrap_desc_ok(const PTUnwrapDesc* desc, const char* who)
+{
+    if (!desc) { g_buildError = std::string(who) + ": desc == NULL"; return false; }
+    if (desc->structSize < sizeof(PTUnwrapDesc) || desc->structSize > 4096u) {
+        g_buildError = "PTUnwrapDesc.structSize is not set (must be sizeof(PTUnwrapDesc) of the host's header)";
+        return false;
+    }
+    for (uint32_t r : desc->reserved) if (r) { g_buildError = "PTUnwrapDesc.reserved != 0"; return false; }
+    return ptunwrap::unwrap_check_count(desc->triangleCount, who, g_buildError);
+}
+} // namespace
+PT_API int PTUnwrapChartsHost(const PTUnwrapDesc* desc, const PTFloat4* tris, const PTFloat4* verticesOrNull, uint32_t* chartOfPrim, PTUnwrapChart* charts,
+                              uint32_t capacity, uint32_t* chartCount, PTUnwrapStats* statsOrNull)
+{
+    if (!chartCount) { g_buildError = "PTUnwrapChartsHost: chartCount == NULL"; return 0; }
+    *chartCount = 0;
+    if (!unwrap_desc_ok(desc, "PTUnwrapChartsHost")) return 0;
+    if (!ptunwrap::unwrap_charts_host(tris, verticesOrNull, (uint32_t)desc->triangleCount, chartOfPrim, charts, capacity, *chartCount, statsOrNull, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+PT_API int PTPackChartsHost(const PTUnwrapChart* charts, uint32_t chartCount, uint32_t width, uint32_t height, uint32_t padding, float texelsPerUnit,
+                            int32_t* origins, uint32_t* rowsUsed)
+{
+    if (!rowsUsed) { g_buildError = "PTPackChartsHost: rowsUsed == NULL"; return 0; }
+    if (!ptunwrap::pack_charts_host(charts, chartCount, width, height, padding, texelsPerUnit, origins, *rowsUsed, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+PT_API int PTEmitChartUVsHost(const PTUnwrapDesc* desc, const PTFloat4* tris, const PTFloat4* verticesOrNull, const uint32_t* chartOfPrim,
+                              const PTUnwrapChart* charts, const int32_t* origins, uint32_t chartCount, uint32_t width, uint32_t height, uint32_t padding,
+                              float texelsPerUnit, float* uvs)
+{
+    if (!unwrap_desc_ok(desc, "PTEmitChartUVsHost")) return 0;
+    if (!ptunwrap::emit_uvs_host(tris, verticesOrNull, (uint32_t)desc->triangleCount, chartOfPrim, charts, origins, chartCount, width, height, padding,
+                                 texelsPerUnit, uvs, g_buildError)) return 0;
     g_buildError.clear();
     return 1;
 }

@@ -10,6 +10,7 @@
 #include "pt_lightmap.h"
 #include "pt_lmfilter.h"
 #include "pt_adaptive_gather.h"
+#include "pt_unwrap.h"
 #include "bvh_refit.h"
 #include "bvh_builder_gpu.h"
 
@@ -279,6 +280,12 @@ struct PTContext {
         DeviceBuffer image;                     // 16 B per texel: the resolve's second image
         PinnedBuffer count;                     // the total, read back
     } lightmap;
+    // lightmap UVs (PTUnwrapCharts): kUnwrapBytesPerTriangle per triangle and the sort's temporary storage, grown on demand,
+    // kept across PTSetScene
+    struct Unwrap {
+        DeviceBuffer work;
+        PinnedBuffer small;                     // the counters and sweep flags, read back
+    } unwrap;
     // the lightmap denoiser (PTDenoiseLightmap): 64 B per texel, grown on demand, kept across PTSetScene
     struct LightmapFilter {
         DeviceBuffer state[2];                  // 16 B per texel each: (e, v), the levels go from one to the other

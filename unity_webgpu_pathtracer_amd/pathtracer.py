@@ -11,7 +11,7 @@ here renders, traverses or shades on the host.
 
 This module keeps the scene, the construction, the render passes, the presentation, the statistics and the schedule.  The
 other parts of the header are mixins of `PathTracer`, one module each: _queries.py (Parts 3 and 8, camera, pick, focus),
-_denoise.py (Parts 4, 6 and 7), _updates.py (Parts 5 and 9 to 12) and _bakes.py (Parts 13 to 22, with `ProbeVolume` and
+_denoise.py (Parts 4, 6 and 7), _updates.py (Parts 5 and 9 to 12) and _bakes.py (Parts 13 to 23, with `ProbeVolume` and
 `ReflectionProbes`); what they share -- the two call forms among it -- is _hostcalls.py.
 """
 import ctypes as C
@@ -19,7 +19,7 @@ import ctypes as C
 import numpy as np
 
 from . import abi, plugin
-from ._bakes import Bakes, ProbeVolume, ReflectionProbes, probe_grid        # noqa: F401 (re-exported)
+from ._bakes import Bakes, LightmapUnwrap, ProbeVolume, ReflectionProbes, probe_grid        # noqa: F401 (re-exported)
 from ._denoise import Denoise, list_slot_to_pixel, select_blocks           # noqa: F401 (re-exported)
 from ._queries import Queries
 from ._updates import Updates

@@ -185,6 +185,12 @@ sig = {
     "PTShadeLightmapped": (i32, [vp, C.POINTER(abi.PTShadeInputs), vp, vp, vp, C.c_uint64, vp]),
     "PTShadeLightmappedFrame": (i32, [vp, C.POINTER(abi.PTFrameParams), C.POINTER(abi.PTShadeInputs), vp, vp]),
     "PTLightmapLookupHost": (i32, [C.POINTER(abi.PTLightmapBinding), C.c_uint32, vp, C.c_uint64, C.c_uint32, vp, vp, vp, C.c_uint64, vp, vp]),
+    # Part 23 (lightmap UVs)
+    "PTUnwrapCharts": (i32, [vp, C.POINTER(abi.PTUnwrapDesc), vp, vp, vp, C.c_uint32, u32p, C.POINTER(abi.PTUnwrapStats)]),
+    "PTEmitChartUVs": (i32, [vp, C.POINTER(abi.PTUnwrapDesc), vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, vp]),
+    "PTUnwrapChartsHost": (i32, [C.POINTER(abi.PTUnwrapDesc), vp, vp, vp, vp, C.c_uint32, u32p, C.POINTER(abi.PTUnwrapStats)]),
+    "PTPackChartsHost": (i32, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, vp, u32p]),
+    "PTEmitChartUVsHost": (i32, [C.POINTER(abi.PTUnwrapDesc), vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, vp]),
     "PTGetLastError": (C.c_char_p, []), "PTGetVersion": (i32, []),
 }
 EXPORTED_SYMBOLS = list(sig)
@@ -1019,3 +1025,93 @@ def build_tlas(instances: np.ndarray):
     finally:
         TinyBVH.DestroyTLAS(h)
     return nodes, idx
+
+
+# ---- lightmap UVs on the host (include/ptmi_plugin.h Part 23)
+def _unwrap_sources(tris, vertices):
+    """(tris bytes or None, vertices (3T, 4) or None, T) of the twins' two corner sources"""
+    t = None if tris is None else np.ascontiguousarray(np.asarray(tris).view(np.uint8).reshape(-1))
+    v = None if vertices is None else np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 4)
+    assert t is not None or v is not None, "the triangle rows or the vertices"
+    ntri = v.shape[0] // 3 if v is not None else t.nbytes // 48
+    assert (v is None or v.shape[0] == ntri * 3) and (t is None or t.nbytes == ntri * 48), (ntri, None if t is None else t.nbytes)
+    return t, v, ntri
+
+
+def unwrap_charts(tris, vertices=None, return_stats: bool = False):
+    """The charts of a mesh on the host (PTUnwrapChartsHost, include/ptmi_plugin.h Part 23): the kernels' rule, byte for byte.
+    tris: the BLAS's triangle rows, (3T, 4) float32 or their bytes, as PTReadGeometry returns them (None with vertices);
+    vertices: (3T, 4) float32 in primitive order, None = the records' v0, v0 + e1, v0 + e2.  Returns (chart_of_prim (T,) uint32 with
+    abi.PT_UNWRAP_NO_CHART for excluded triangles, charts: records of abi.UNWRAP_CHART_DTYPE), and with return_stats a dict."""
+    t, v, ntri = _unwrap_sources(tris, vertices)
+    ptr = lambda x: None if x is None else x.ctypes.data
+    lib = load_library()
+    d = abi.unwrap_desc(ntri)
+    count, st = C.c_uint32(), abi.PTUnwrapStats()
+    if not lib.PTUnwrapChartsHost(C.byref(d), ptr(t), ptr(v), None, None, 0, C.byref(count), C.byref(st)):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTUnwrapChartsHost failed: " + lib.PTGetBVHBuildError().decode())
+    of, charts = np.empty(ntri, np.uint32), np.zeros(count.value, abi.UNWRAP_CHART_DTYPE)
+    if not lib.PTUnwrapChartsHost(C.byref(d), ptr(t), ptr(v), of.ctypes.data, charts.ctypes.data, count.value, C.byref(count), C.byref(st)):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTUnwrapChartsHost failed: " + lib.PTGetBVHBuildError().decode())
+    return (of, charts, st.as_dict()) if return_stats else (of, charts)
+
+
+def pack_charts(charts, width: int, height: int, texels_per_unit: float, padding: int = 2):
+    """The shelf packer (PTPackChartsHost, include/ptmi_plugin.h Part 23; a pure host function).  charts: records of
+    abi.UNWRAP_CHART_DTYPE -- of one mesh, or the concatenated records of several.  Returns (origins (n, 2) int32: x, y per chart,
+    or None when the charts do not fit, rows_used: the rows the shelves take, set whenever every chart's width fits -- also past the
+    height --, else 0).  Raises PluginError for a size, padding or density out of range."""
+    c = np.ascontiguousarray(charts, dtype=abi.UNWRAP_CHART_DTYPE).reshape(-1)
+    origins, rows = np.zeros((len(c), 2), np.int32), C.c_uint32()
+    lib = load_library()
+    if lib.PTPackChartsHost(c.ctypes.data if len(c) else None, len(c), int(width), int(height), int(padding), float(texels_per_unit),
+                            origins.ctypes.data if len(c) else None, C.byref(rows)):
+        return origins, rows.value
+    msg = lib.PTGetBVHBuildError().decode()
+    if "rows" in msg or "wider" in msg:
+        return None, rows.value
+    raise PluginError(abi.PT_ERR_INVALID_ARG, "PTPackChartsHost failed: " + msg)
+
+
+def emit_chart_uvs(tris, chart_of_prim, charts, origins, width: int, height: int, texels_per_unit: float, padding: int = 2, vertices=None):
+    """The lightmap UVs of a mesh on the host (PTEmitChartUVsHost, include/ptmi_plugin.h Part 23).  tris, vertices: as unwrap_charts
+    takes them; chart_of_prim: its first result; charts, origins: the mesh's slice of what pack_charts placed.  Returns (T, 6)
+    float32: u0 v0 u1 v1 u2 v2 per primitive, six NaNs for an excluded one."""
+    t, v, ntri = _unwrap_sources(tris, vertices)
+    of = np.ascontiguousarray(chart_of_prim, dtype=np.uint32).reshape(ntri)
+    c = np.ascontiguousarray(charts, dtype=abi.UNWRAP_CHART_DTYPE).reshape(-1)
+    o = np.ascontiguousarray(origins, dtype=np.int32).reshape(len(c), 2)
+    ptr = lambda x: None if x is None or not x.size else x.ctypes.data
+    uvs = np.empty((ntri, 6), np.float32)
+    lib = load_library()
+    d = abi.unwrap_desc(ntri)
+    if not lib.PTEmitChartUVsHost(C.byref(d), ptr(t), ptr(v), of.ctypes.data, ptr(c), ptr(o), len(c), int(width), int(height), int(padding),
+                                  float(texels_per_unit), uvs.ctypes.data):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTEmitChartUVsHost failed: " + lib.PTGetBVHBuildError().decode())
+    return uvs
+
+
+def fit_chart_density(charts, width: int, height: int, padding: int = 2):
+    """The largest density of 16 bisection steps at which pack_charts fits the charts into width x height: hi is the density at
+    which the widest or tallest chart just fits (its side without padding and the texel that holds umin), then 16 halvings of
+    [0, hi] keep the largest density that packs.  Returns (texels_per_unit, last_rejected: the smallest density tried that did not
+    fit, or None).  Raises ValueError when nothing fits (an atlas smaller than the padding, or no chart with an extent)."""
+    c = np.ascontiguousarray(charts, dtype=abi.UNWRAP_CHART_DTYPE).reshape(-1)
+    du = float((c["umax"].astype(np.float64) - c["umin"]).max()) if len(c) else 0.0
+    dv = float((c["vmax"].astype(np.float64) - c["vmin"]).max()) if len(c) else 0.0
+    room_w, room_h = int(width) - 1 - 2 * int(padding), int(height) - 1 - 2 * int(padding)
+    if room_w < 1 or room_h < 1 or max(du, dv) <= 0.0:
+        raise ValueError("no density fits: the atlas is smaller than the padding, or no chart has an extent")
+    hi = float(np.float32(min(room_w / du if du > 0 else np.inf, room_h / dv if dv > 0 else np.inf)))
+    if pack_charts(c, width, height, hi, padding)[0] is not None:
+        return hi, None
+    lo, rejected = 0.0, hi
+    for _ in range(16):
+        mid = float(np.float32(0.5 * (lo + hi)))
+        if mid > 0.0 and pack_charts(c, width, height, mid, padding)[0] is not None:
+            lo = mid
+        else:
+            hi = rejected = mid
+    if lo <= 0.0:
+        raise ValueError("no density of the bisection fits the atlas")
+    return lo, rejected
