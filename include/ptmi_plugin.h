@@ -2125,6 +2125,115 @@ PT_API int PTEmitChartUVsHost(const PTUnwrapDesc* desc, const PTFloat4* tris, co
                               const PTUnwrapChart* charts, const int32_t* origins, uint32_t chartCount, uint32_t width, uint32_t height, uint32_t padding,
                               float texelsPerUnit, float* uvs);
 
+/* =====================================================================================================================
+ * Part 24: direct light at first hits.  Parts 21 and 22 see the scene's analytic lights only through the bakes: a light moved
+ * with PTUpdateLights, a skinned character's shadow, a point light's highlight on metal and a shadow edge sharper than a
+ * lightmap texel are all missing from their frames.  This part is the other half of mixed lighting: sky, emissive surfaces and
+ * bounced light stay in the bakes, the point, spot and rectangle lights are evaluated at every first hit with shadow rays, every
+ * frame.  An addition beside the reference's ABI, detected by symbol; PTGetVersion is unchanged.
+ *
+ * Left out: sky for misses; the Disney lobes Part 21 leaves out; directional lights (they light nothing in the render either); a
+ * bounded shadow ray; the indirect light of the analytic lights (bake with the lights muted, or accept it twice); PTGroup
+ * wrappers; PTPresent of the result.
+ *
+ * The rule (bit-exact; csrc/direct_rule.h is its one definition: the kernels, the host twins and tests/direct_ref.py evaluate
+ * it; every fp32 operator below is one IEEE binary32 operation in the order written, no fma; only + - * /, sqrt, saturate,
+ * |x|, comparisons and pt_random_float).  dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z; normalize(v) = v * (1.0f /
+ * sqrt(dot(v, v))) per component -- the render's; max(x, y) below is "y > x ? y : x" read left to right as written.
+ *  1. Inputs.  Entry i has its PTRay (direction D), the PTShadeTerms and the PTReceiver PTShadeSurfaces writes for it: position
+ *     P, and N already turned towards the viewer.
+ *  2. Miss.  An entry whose terms have nDotV > 0 false is a miss: all its pairs are skipped, its result is four zero words.
+ *  3. Hit.  Vd is Part 21 step 2's: len = sqrt((D.x * D.x + D.y * D.y) + D.z * D.z); Vd = (-D) / len.  alpha = rho * rho (Part
+ *     20's level roughness, the alpha the DFG table was integrated with); alpha = minAlpha > alpha ? minAlpha : alpha; a2 = alpha *
+ *     alpha.  O = P + N * PT_EPSILON: per component b = N * PT_EPSILON, then P + b.
+ *  4. Pairs.  The lights of the current scene in ascending index; a point light contributes 1 pair, a spot light 1, a rectangle
+ *     light S * S with k = b * S + a (a = k % S, b = k / S); any other type none.  pairsPerEntry is the sum; pair (i, l, k) has
+ *     index i * pairsPerEntry + offset_l + k.
+ *  5. Light sample at scatterPos = O, with the light's derived rows n = normalize(cross(u, v)) (rectangle) or normalize(u)
+ *     (spot) and nn = normalize(n), as PTSetScene and PTUpdateLights derive them.
+ *     Point and spot: q = O - position; lsDistance = sqrt(dot(q, q)); L = -(q * (1.0f / lsDistance)) per component -- the
+ *     render's -normalize(O - position); the render takes a spot light's distance from position - O, whose squares are the same
+ *     bits.
+ *     Rectangle: r1 = ((float)a + x1) / (float)S, r2 = ((float)b + x2) / (float)S; p = (position + u * r1) + v * r2; q = p - O;
+ *     lsDistance = sqrt(dot(q, q)); L = q / lsDistance; lsNormal = n.  With PT_DIRECT_CENTERED x1 = x2 = 0.5f and nothing is
+ *     drawn.  Otherwise the entry's state is s = seed; pt_rng_next(&s); s += (uint32_t)i; and x1, then x2, are drawn with
+ *     pt_random_float(&s) for every pair of every rectangle light in ascending pair index, whether or not the pair ends up
+ *     counting: no draw depends on visibility or on the material.
+ *     falloff: lsDistance > range gives 0; otherwise r = lsDistance / range and falloff = saturate((1.0f / (1.0f + (25.0f * r)
+ *     * r)) * saturate((1.0f - r) * 5.0f)).  Rectangle and spot: cosTheta = dot(normalize(-L), nn).  Rectangle: cosTheta < 0
+ *     gives falloff 0.  Spot, with v.x and v.y the cosines of the outer and inner cone: cosTheta < v.x gives 0; v.x < cosTheta <
+ *     v.y gives falloff = falloff * ((cosTheta - v.x) / (v.y - v.x)).  Li = emission * falloff.
+ *  6. BRDF at L, isotropic GGX over Lambert, the model the bakes are composed with.  nl = dot(N, L); a pair with nl > 0 false is
+ *     skipped.  H = Vd + L; len = sqrt(dot(H, H)); a len that is not > 0 leaves the specular term out (f = diffuse *
+ *     0.31830988618379067f).  Otherwise H = H / len; nh = max(0, dot(N, H)); vh = max(0, dot(Vd, H)) (a NaN lands on 0);
+ *     t = (nh * nh) * (a2 - 1.0f) + 1.0f; D = a2 / ((3.14159265f * t) * t); G = smith_g(nDotV, alpha) * smith_g(nl, alpha) with
+ *     Part 21's smith_g; m = 1.0f - vh; Fc = ((m * m) * (m * m)) * m; F[c] = f0[c] + (1.0f - f0[c]) * Fc; sp = (D * G) / ((4.0f *
+ *     nl) * nDotV); f[c] = diffuse[c] * 0.31830988618379067f + F[c] * sp.
+ *  7. Weight and contribution.  w = 1.0f for a point or spot light; for a rectangle light w = ((area * |dot(lsNormal, L)|) /
+ *     (lsDistance * lsDistance)) / (float)(S * S).  c[ch] = ((Li[ch] * f[ch]) * nl) * w.  A pair counts only if all three c are
+ *     finite and at least one is > 0.  A pair that does not count has origin and direction 0, tmax = 0 (Part 3's miss without a
+ *     walk) and zero contribution.  The shadow ray of a pair that counts is {O, L, tmax = PT_FAR_PLANE, 0}: the render's shadow
+ *     ray, which has no far end (Part 15 says why and what follows), traced as PT_QUERY_ANY_HIT by Part 3's rules.
+ *  8. Sum.  direct[ch] starts at +0.0f; in ascending pair index direct[ch] = direct[ch] + c[ch] for every pair that counts (at
+ *     least one c > 0) and whose PTRayHit.prim == 0xFFFFFFFF.  The result is {direct.rgb, 1.0f}.
+ *
+ * PTDirectLight equals PTShadeSurfaces, PTDirectRays, PTTraceRays(PT_QUERY_ANY_HIT) and PTDirectAccumulate bit for bit, with the
+ * walks inside the kernel and nothing per pair stored; it adds nothing to PTStats at any stats level.  PTShadeMixed equals
+ * PTShadeLightmapped plus PTDirectLight, one add per channel (w is PTShadeLightmapped's).  PTShadeMixedFrame equals
+ * PTShadeLightmappedFrame's rays and query followed by PTShadeMixed; entry i = y * W + x (the same scratch).  A scene without
+ * HAS_LIGHTS has pairsPerEntry == 0: PTDirectLight writes {0, 0, 0, 1} for hits and PTShadeMixed equals PTShadeLightmapped.
+ * The light arrays seen are the current generation's (Part 5's ordering).
+ *
+ * Device pointers are 16-byte aligned; the calls are stream-ordered on the context's stream and nothing past `count` is
+ * written; count == 0 returns PT_OK and launches nothing.  count * pairsPerEntry is at most 2^31 per PTDirectRays /
+ * PTDirectAccumulate call.  Errors are Part 21's and 22's (NULL or misaligned pointers, PT_ERR_NO_SCENE before PTSetScene, the
+ * refusals of `inputs`), plus PT_ERR_INVALID_ARG for strata outside 1 ... PT_DIRECT_MAX_STRATA, an unknown flag, a nonzero
+ * reserved word, a minAlpha that is not finite or is negative, a zero structSize (or one below this header's).
+ * PTDirectAccumulate reads no scene: pairsPerEntry is the caller's, PTDirectPairCount's for the rays it accumulates.  No CPU
+ * fallback.
+ * The host twins take no context and no GPU; lights: lightCount PTLight records; they return 1, or 0 with
+ * PTGetBVHBuildError() set.
+ * ===================================================================================================================== */
+#define PT_DIRECT_CENTERED   1u     /* PTDirectParams.flags: no jitter, every stratum sampled at its centre; no RNG draw */
+#define PT_DIRECT_MAX_STRATA 4u     /* per axis: up to 16 shadow rays per rectangle light */
+
+typedef struct PTDirectParams {
+    uint32_t structSize;            /* sizeof(PTDirectParams) of the caller's header; members are only appended */
+    uint32_t strata;                /* S: a rectangle light is sampled on an S x S grid, 1 ... PT_DIRECT_MAX_STRATA */
+    uint32_t seed;
+    uint32_t flags;
+    float    minAlpha;              /* the specular lobe's alpha is max(alpha, minAlpha); 0 leaves it alone; finite, >= 0 */
+    uint32_t reserved[3];           /* must be 0 */
+} PTDirectParams;
+
+#ifdef __cplusplus
+static_assert(sizeof(PTDirectParams) == 32, "PTDirectParams is 32 bytes");
+#else
+_Static_assert(sizeof(PTDirectParams) == 32, "PTDirectParams is 32 bytes");
+#endif
+
+PT_API int PTDirectPairCount(PTContext* ctx, uint32_t strata, uint32_t* outPairsPerEntry);
+/* steps 2-7: dOutRays and dOutContrib have count * pairsPerEntry entries (PTRay; float4 with w = 0) */
+PT_API int PTDirectRays(PTContext* ctx, const PTDirectParams* params, const PTRay* dRays, const PTShadeTerms* dTerms, const PTReceiver* dRecv,
+                        uint64_t count, PTRay* dOutRays, float* dOutContrib);
+/* step 8 over what PTTraceRays(PT_QUERY_ANY_HIT) wrote for dOutRays; dOut: count float4 entries */
+PT_API int PTDirectAccumulate(PTContext* ctx, const PTShadeTerms* dTerms, const float* dContrib, const PTRayHit* dPairHits, uint64_t count,
+                              uint32_t pairsPerEntry, float* dOut);
+/* the hot path: material fetch, terms, steps 2-8 with the walks inside the kernel; nothing per pair is stored */
+PT_API int PTDirectLight(PTContext* ctx, const PTDirectParams* params, const PTRay* dRays, const PTRayHit* dHits, const PTRaySurface* dSurface,
+                         uint64_t count, float* dOut);
+/* PTShadeLightmapped's result with direct.rgb added per channel (one add each); w is PTShadeLightmapped's */
+PT_API int PTShadeMixed(PTContext* ctx, const PTShadeInputs* inputs, const PTDirectParams* params, const PTRay* dRays, const PTRayHit* dHits,
+                        const PTRaySurface* dSurface, uint64_t count, float* dOut);
+PT_API int PTShadeMixedFrame(PTContext* ctx, const PTFrameParams* params, const PTShadeInputs* inputs, const PTDirectParams* direct, float* dOut,
+                             PTRay* dOutRays);
+/* host twins, no GPU */
+PT_API int PTDirectPairCountHost(const void* lights, uint32_t lightCount, uint32_t strata, uint32_t* outPairsPerEntry);
+PT_API int PTDirectRaysHost(const PTDirectParams* params, const void* lights, uint32_t lightCount, const PTRay* rays, const PTShadeTerms* terms,
+                            const PTReceiver* receivers, uint64_t count, PTRay* outRays, float* outContrib);
+PT_API int PTDirectAccumulateHost(const PTShadeTerms* terms, const float* contrib, const PTRayHit* pairHits, uint64_t count,
+                                  uint32_t pairsPerEntry, float* out);
+
 /* Text of the last error on the calling thread ("" if none). */
 PT_API const char* PTGetLastError(void);
 /* Library/ABI version: (major << 16) | minor. */

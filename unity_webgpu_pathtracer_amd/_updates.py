@@ -34,6 +34,7 @@ class Updates(HostCalls):
         """PTUpdateLights: (k, 16) float32 PTLight records, 1 <= k <= the scene's light count."""
         L = np.ascontiguousarray(lights, dtype=np.float32).reshape(-1, 16)
         plugin.check(self.lib.PTUpdateLights(self.ctx, L.ctypes.data, L.shape[0]))
+        self._lightRecords = L.copy()           # what light_records() and muted_lights() (Part 24) start from
 
     def update_materials(self, materials: np.ndarray):
         """PTUpdateMaterials: (materialCount, 32) float32 PTMaterialData records."""

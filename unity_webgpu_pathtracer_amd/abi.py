@@ -422,6 +422,27 @@ class PTLightmapBinding(C.Structure):
 assert C.sizeof(PTLightmapBinding) == 48
 
 
+# ---- direct light at first hits (include/ptmi_plugin.h Part 24)
+PT_DIRECT_CENTERED = 1
+PT_DIRECT_MAX_STRATA = 4
+
+
+class PTDirectParams(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("strata", C.c_uint32), ("seed", C.c_uint32), ("flags", C.c_uint32), ("minAlpha", C.c_float),
+                ("reserved", C.c_uint32 * 3)]
+
+
+assert C.sizeof(PTDirectParams) == 32
+
+
+def direct_params(strata: int = 1, seed: int = 0, centered: bool = False, min_alpha: float = 0.0) -> PTDirectParams:
+    """A PTDirectParams with structSize set"""
+    p = PTDirectParams()
+    p.structSize = C.sizeof(PTDirectParams)
+    p.strata, p.seed, p.flags, p.minAlpha = int(strata), int(seed) & 0xFFFFFFFF, PT_DIRECT_CENTERED if centered else 0, float(min_alpha)
+    return p
+
+
 # ---- lightmap charts (include/ptmi_plugin.h Part 14)
 PT_CHART_MAX_SIZE = 8192
 PT_CHART_MAX_DILATE = 16

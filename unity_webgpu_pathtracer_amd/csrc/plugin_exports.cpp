@@ -26,6 +26,7 @@
 #include "lightmap_lookup_rule.h"
 #include "repack_rule.h"
 #include "unwrap_rule.h"
+#include "direct_rule.h"
 #include "ptmi_plugin.h"
 
 namespace {
@@ -384,6 +385,27 @@ PT_API int PTEmitChartUVsHost(const PTUnwrapDesc* desc, const PTFloat4* tris, co
     if (!unwrap_desc_ok(desc, "PTEmitChartUVsHost")) return 0;
     if (!ptunwrap::emit_uvs_host(tris, verticesOrNull, (uint32_t)desc->triangleCount, chartOfPrim, charts, origins, chartCount, width, height, padding,
                                  texelsPerUnit, uvs, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+// Direct light at first hits on the host (direct_host.cpp; Part 24 has the rule).  No GPU involved.
+PT_API int PTDirectPairCountHost(const void* lights, uint32_t lightCount, uint32_t strata, uint32_t* outPairsPerEntry)
+{
+    if (!ptdirect::pair_count_host(lights, lightCount, strata, outPairsPerEntry, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+PT_API int PTDirectRaysHost(const PTDirectParams* params, const void* lights, uint32_t lightCount, const PTRay* rays, const PTShadeTerms* terms,
+                            const PTReceiver* receivers, uint64_t count, PTRay* outRays, float* outContrib)
+{
+    if (!ptdirect::rays_host(params, lights, lightCount, rays, terms, receivers, count, outRays, outContrib, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+PT_API int PTDirectAccumulateHost(const PTShadeTerms* terms, const float* contrib, const PTRayHit* pairHits, uint64_t count, uint32_t pairsPerEntry,
+                                  float* out)
+{
+    if (!ptdirect::accumulate_host(terms, contrib, pairHits, count, pairsPerEntry, out, g_buildError)) return 0;
     g_buildError.clear();
     return 1;
 }

@@ -6,7 +6,7 @@
 namespace {
 
 int shade_lightmapped(PTContext* c, const PTShadeInputs& in, const PTRay* dRays, const PTRayHit* dHits, const PTRaySurface* dSurface, uint64_t count,
-                      float4* dOut)
+                      float4* dOut, const void* = nullptr)
 {
     return for_each_launch(count, 1ull << 30, [&](uint64_t first, uint32_t n) {
         HIP_TRY(pt_launch_shade_lightmapped(c->scene, in, c->lightmaps.device(), c->lightmaps.count, dRays + first, dHits + first, dSurface + first, n,

@@ -33,8 +33,11 @@ int query_prepare(PTContext* c)
     PTContext::Query& q = c->query;
     if (q.slab.ptr) return PT_OK;
     HIP_TRY(pt_query_grid_caps(c->device, q.caps));
+    HIP_TRY(pt_direct_grid_caps(c->device, q.directCaps));
     for (uint32_t cap : q.caps) q.capMax = cap > q.capMax ? cap : q.capMax;
-    return q.slab.reserve((size_t)q.capMax * pt_query_slab_bytes_per_wave());
+    for (uint32_t cap : q.directCaps) q.capMax = cap > q.capMax ? cap : q.capMax;
+    const size_t perWave = pt_query_slab_bytes_per_wave() > pt_direct_slab_bytes_per_wave() ? pt_query_slab_bytes_per_wave() : pt_direct_slab_bytes_per_wave();
+    return q.slab.reserve((size_t)q.capMax * perWave);
 }
 
 extern "C" {

@@ -32,7 +32,8 @@ int check_shade_inputs(const PTShadeInputs* in, const char* who)
 
 namespace {
 
-int shade_baked(PTContext* c, const PTShadeInputs& in, const PTRay* dRays, const PTRayHit* dHits, const PTRaySurface* dSurface, uint64_t count, float4* dOut)
+int shade_baked(PTContext* c, const PTShadeInputs& in, const PTRay* dRays, const PTRayHit* dHits, const PTRaySurface* dSurface, uint64_t count, float4* dOut,
+                const void* = nullptr)
 {
     return for_each_launch(count, 1ull << 30, [&](uint64_t first, uint32_t n) {
         HIP_TRY(pt_launch_shade_baked(c->scene, in, dRays + first, dHits + first, dSurface + first, n, dOut + first, c->stream));
@@ -42,7 +43,8 @@ int shade_baked(PTContext* c, const PTShadeInputs& in, const PTRay* dRays, const
 
 } // namespace
 
-int shade_frame(PTContext* c, const PTFrameParams* hostParams, const PTShadeInputs* inputs, float* dOut, PTRay* dOutRays, const char* who, ShadeList shade)
+int shade_frame(PTContext* c, const PTFrameParams* hostParams, const PTShadeInputs* inputs, float* dOut, PTRay* dOutRays, const char* who, ShadeList shade,
+                const void* user)
 {
     if (!c) return fail(PT_ERR_INVALID_ARG, std::string(who) + ": ctx == NULL");
     PTFrameParams p;
@@ -70,7 +72,7 @@ int shade_frame(PTContext* c, const PTFrameParams* hostParams, const PTShadeInpu
         return PT_OK;
     });
     if (rc) return rc;
-    return shade(c, *inputs, rays, (const PTRayHit*)W.hits.ptr, (const PTRaySurface*)W.surfaces.ptr, pixels, (float4*)dOut);
+    return shade(c, *inputs, rays, (const PTRayHit*)W.hits.ptr, (const PTRaySurface*)W.surfaces.ptr, pixels, (float4*)dOut, user);
 }
 
 extern "C" {

@@ -11,6 +11,7 @@
 #include "pt_lmfilter.h"
 #include "pt_adaptive_gather.h"
 #include "pt_unwrap.h"
+#include "pt_direct.h"
 #include "bvh_refit.h"
 #include "bvh_builder_gpu.h"
 
@@ -190,6 +191,7 @@ struct PTContext {
     // ray queries (PTTraceRays): grid caps per query kernel (read once), the CWBVH stack slab sized for the largest, host staging
     struct Query {
         uint32_t caps[PT_QUERY_KERNELS] = {};
+        uint32_t directCaps[2] = {};            // pt_direct_light, pt_direct_light_tlas (Part 24): they share the slab
         uint32_t capMax = 0;
         DeviceBuffer slab;
         DeviceBuffer rays, hits, surface;       // PTTraceRaysHost staging, grown on demand
@@ -362,6 +364,7 @@ struct PTContext {
         PTTlasWork tlasW = {};
         uint32_t instanceCount = 0, sceneLightCount = 0, origTlasNodes = 0;
         std::vector<uint32_t> validTextures;            // texture indices PTSetScene validated (sorted)
+        std::vector<uint32_t> lightTypes;               // the current lights' types (PTSetScene, PTUpdateLights): Part 24 counts pairs on the host
     } update;
 };
 
@@ -490,9 +493,11 @@ int trace_radiance(PTContext* c, const PTFrameParams& p, const PTRadianceRay* dR
 // pt_api_shade.hip: what PTShadeBaked and PTShadeBakedFrame check of the struct before the context is used, and PTShadeBakedFrame's
 // body -- the frame's rays, the closest-hit walk with surface records into the context's scratch, then shade(...) over them
 int check_shade_inputs(const PTShadeInputs* in, const char* who);
+// user: what the frame's entry point hands its own list call besides the inputs (Part 24: the direct parameters); may be null
 using ShadeList = int (*)(PTContext* c, const PTShadeInputs& in, const PTRay* dRays, const PTRayHit* dHits, const PTRaySurface* dSurface, uint64_t count,
-                          float4* dOut);
-int shade_frame(PTContext* c, const PTFrameParams* hostParams, const PTShadeInputs* inputs, float* dOut, PTRay* dOutRays, const char* who, ShadeList shade);
+                          float4* dOut, const void* user);
+int shade_frame(PTContext* c, const PTFrameParams* hostParams, const PTShadeInputs* inputs, float* dOut, PTRay* dOutRays, const char* who, ShadeList shade,
+                const void* user = nullptr);
 int query_prepare(PTContext* c);                                                // pt_api_query.hip: the grid caps and the stack slab of the query kernels, on first use
 int set_scene(PTContext* c, const PTSceneDesc* hostScene, bool validate);      // pt_api_context.hip; PTGroupSetScene validates once
 int drain_events(PTContext* c);                                                 // pt_api_context.hip

@@ -14,9 +14,6 @@
 #include "pt_device.h"
 #include "pt_launch.h"
 
-#ifndef PT_Q_LDS_STACK
-#define PT_Q_LDS_STACK 8        // CWBVH stack entries per lane in LDS (4 KB per one-wave workgroup); the stress build uses 1
-#endif
 #define PT_G_SLAB_ENTRIES (PT_BVH_STACK_SIZE - PT_Q_LDS_STACK)
 
 namespace {

@@ -125,6 +125,12 @@ PT_DEV float rnd(uint32_t& s) { return pt_random_float(&s); }
 #define PT_LDS_STACK 12
 #endif
 #define PT_SPILL_STACK (PT_BVH_STACK_SIZE - PT_LDS_STACK)
+// The one-wave-per-workgroup kernels that walk with a slab behind the LDS part (pt_query.hip, pt_denoise.hip, pt_direct.hip): CWBVH
+// stack entries per lane in LDS (4 KB per workgroup); a slab row holds the other PT_BVH_STACK_SIZE - PT_Q_LDS_STACK.  The stress
+// build uses 1.  One definition: the context sizes ONE slab for all of them.
+#ifndef PT_Q_LDS_STACK
+#define PT_Q_LDS_STACK 8
+#endif
 
 // GSPILL = true: entries beyond the LDS part go to a slab in HBM (gbase + gidx * (32 - LDSN)) instead of a private
 // array.  A private array that is indexed dynamically lives in scratch memory, and a kernel that declares ANY scratch
@@ -536,7 +542,9 @@ PT_DEV TlasStep tlas_node_step(float4 a, float4 b, float4 c, float4 e, v3 O, v3 
     return s;
 }
 
-// tlas.hlsl:236-332
+// tlas.hlsl:236-332.  pt_direct.hip's anyhit_tlas is this loop for an any-hit ray with the TLAS stack in LDS instead of the private
+// array (steps, instance walks and the pop rule are the functions above): a change to the walk's order here is made there too;
+// tests/test_gpu_direct.py compares the two on the instanced scene bit for bit.
 template <bool STATS, class ST>
 PT_DEV bool traverse_tlas(const DScene& S, v3 O, v3 dir, bool isShadow, HitRecord& rec, ST& st, Counters& cn)
 {

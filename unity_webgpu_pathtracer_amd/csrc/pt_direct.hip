@@ -1,0 +1,363 @@
+// pt_direct.hip — direct light at first hits (include/ptmi_plugin.h Part 24).
+//
+//     pt_direct_rays        one lane per entry: three 16-byte loads of terms, two each of the ray and the receiver; the lights
+//                           walked through wave-uniform scalar loads; per pair two 16-byte stores of the ray and one of the
+//                           contribution
+//     pt_direct_accumulate  one lane per entry: row 1 of the terms, per pair a 16-byte load of the hit and one of the contribution
+//     pt_direct_light[_tlas]  the hot path, shaped as pt_query.hip's kernels: one entry per lane, one 64-lane wave per workgroup,
+//                           the grid capped at the resident waves and walking the list grid-stride.  pt_shade_hit.h's front
+//                           (records, material fetch, terms), then a wave-uniform loop over (light, stratum): the light's record
+//                           and derived rows arrive through scalar loads, every lane evaluates its pair, the wave walks towards
+//                           that light together when any lane's pair counts (the others sit the walk out), the contribution is
+//                           added when nothing was hit.  Terms, O, N, Vd and the running sum stay in registers; nothing per pair
+//                           is stored.  What only a chunk's front reads of the kernel's arguments is read from the argument
+//                           segment again per chunk, so neither kernel spills a scalar register.  The CWBVH stack is pt_query.hip's (PT_Q_LDS_STACK entries per lane in LDS, the rest in the
+//                           context's slab); the HAS_TLAS kernel keeps its 32 TLAS stack entries per lane in LDS too, so neither
+//                           kernel has scratch.
+//
+// The arithmetic is direct_rule.h's, which the host twins evaluate too; the walks are the render's (pt_device.h).
+#include "pt_device.h"
+#include "pt_launch.h"
+#include "pt_shade_hit.h"
+#include "direct_rule.h"
+#include "pt_direct.h"
+
+#define PT_D_SLAB_ENTRIES (PT_BVH_STACK_SIZE - PT_Q_LDS_STACK)
+
+namespace {
+
+typedef __attribute__((address_space(3))) uint32_t* pt_lds_u32;
+
+// light l of the scene as the rule reads it; l is the same in every lane of the wave: six scalar loads
+PT_DEV ptdirect::Light uniform_light(const DScene& S, uint32_t l)
+{
+    const float4 a = pt_uniform_load(S.lights, (size_t)l * 4), b = pt_uniform_load(S.lights, (size_t)l * 4 + 1), c = pt_uniform_load(S.lights, (size_t)l * 4 + 2),
+                 d = pt_uniform_load(S.lights, (size_t)l * 4 + 3);
+    const float4 n = pt_uniform_load(S.lightConst, (size_t)l * 4), nn = pt_uniform_load(S.lightConst, (size_t)l * 4 + 3);
+    ptdirect::Light L;
+    L.position[0] = a.x; L.position[1] = a.y; L.position[2] = a.z; L.type = pt_asuint(a.w);
+    L.emission[0] = b.x; L.emission[1] = b.y; L.emission[2] = b.z; L.range = b.w;
+    L.u[0] = c.x; L.u[1] = c.y; L.u[2] = c.z; L.area = c.w;
+    L.v[0] = d.x; L.v[1] = d.y; L.v[2] = d.z;
+    L.N[0] = n.x; L.N[1] = n.y; L.N[2] = n.z;
+    L.NN[0] = nn.x; L.NN[1] = nn.y; L.NN[2] = nn.z;
+    return L;
+}
+
+PT_DEV uint32_t scene_lights(const DScene& S) { return S.hasLights && S.lightCount > 0 ? (uint32_t)S.lightCount : 0u; }
+
+__global__ __launch_bounds__(256) void pt_direct_rays(DScene S, PTDirectParams P, uint32_t pairsPerEntry, const PTRay* __restrict__ rays,
+                                                      const PTShadeTerms* __restrict__ terms, const PTReceiver* __restrict__ receivers, uint32_t count,
+                                                      uint32_t first, float4* __restrict__ outRays, float4* __restrict__ outContrib)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= count) return;
+    const float4* tp = (const float4*)terms + (size_t)i * 3;
+    const float4 t0 = tp[0], t1 = tp[1], t2 = tp[2];
+    const PTShadeTerms T = {{t0.x, t0.y, t0.z}, t0.w, {t1.x, t1.y, t1.z}, t1.w, {t2.x, t2.y, t2.z}, t2.w};
+    const bool miss = ptshade::is_miss(T);
+    ptdirect::Entry e = {};
+    if (!miss) {
+        const float4 r0 = ((const float4*)rays)[(size_t)i * 2], r1 = ((const float4*)rays)[(size_t)i * 2 + 1];
+        const float4 c0 = ((const float4*)receivers)[(size_t)i * 2], c1 = ((const float4*)receivers)[(size_t)i * 2 + 1];
+        const float D[3] = {r0.w, r1.x, r1.y}, Pp[3] = {c0.x, c0.y, c0.z}, N[3] = {c1.x, c1.y, c1.z};
+        ptdirect::entry_begin(T, D, Pp, N, P.minAlpha, e);
+    }
+    const bool centred = (P.flags & PT_DIRECT_CENTERED) != 0u;
+    uint32_t s = ptdirect::entry_state(P.seed, (uint64_t)first + i);
+    size_t pair = (size_t)i * pairsPerEntry;
+    const uint32_t lightCount = scene_lights(S);
+    for (uint32_t l = 0; l < lightCount; ++l) {
+        const ptdirect::Light Lt = uniform_light(S, l);
+        const uint32_t n = ptdirect::pairs_of(Lt.type, P.strata);
+        for (uint32_t k = 0; k < n; ++k, ++pair) {
+            float x1 = 0.5f, x2 = 0.5f;
+            if (!centred && Lt.type == PT_LIGHT_TYPE_RECTANGLE) {
+                x1 = pt_random_float(&s);
+                x2 = pt_random_float(&s);
+            }
+            float dir[3] = {0.0f, 0.0f, 0.0f}, c[3] = {0.0f, 0.0f, 0.0f};
+            const bool counts = !miss && ptdirect::pair_eval(e, Lt, P.strata, k, x1, x2, dir, c);
+            outRays[2u * pair] = make_float4(counts ? e.O[0] : 0.0f, counts ? e.O[1] : 0.0f, counts ? e.O[2] : 0.0f, dir[0]);
+            outRays[2u * pair + 1u] = make_float4(dir[1], dir[2], counts ? PT_FAR_PLANE : 0.0f, pt_asfloat(0u));
+            outContrib[pair] = make_float4(c[0], c[1], c[2], 0.0f);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void pt_direct_accumulate(const PTShadeTerms* __restrict__ terms, const float4* __restrict__ contrib,
+                                                            const PTRayHit* __restrict__ pairHits, uint32_t count, uint32_t pairsPerEntry,
+                                                            float4* __restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= count) return;
+    const float4 t1 = ((const float4*)terms)[(size_t)i * 3 + 1];
+    if (!(t1.w > 0.0f)) {                                               // ptshade::is_miss
+        out[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
+    float d[3] = {0.0f, 0.0f, 0.0f};
+    for (uint32_t k = 0; k < pairsPerEntry; ++k) {
+        const size_t pair = (size_t)i * pairsPerEntry + k;
+        const float4 h = ((const float4*)pairHits)[pair], c = contrib[pair];
+        if (pt_asuint(h.w) != 0xFFFFFFFFu || !(c.x > 0.0f || c.y > 0.0f || c.z > 0.0f)) continue;
+        d[0] = d[0] + c.x; d[1] = d[1] + c.y; d[2] = d[2] + c.z;
+    }
+    out[i] = make_float4(d[0], d[1], d[2], 1.0f);
+}
+
+// A COPY of traverse_tlas's loop (pt_device.h) for an any-hit ray with the TLAS stack in LDS ([entry][lane], 32 entries): the
+// same nodes in the same order, the same overflow rule (a push at index >= 32 stores nothing, a pop from there yields nothing).
+// tlas_node_step and traverse_instance are called; the push, the pop and the leaf iteration are written out again and follow that
+// function by hand (tests/test_gpu_direct.py holds the two together on the instanced scene, bit for bit)
+template <class ST>
+PT_DEV void anyhit_tlas(const DScene& S, v3 O, v3 dir, HitRecord& rec, ST& st, pt_lds_u32 tstack)
+{
+    if (ray_has_nan(O, dir)) return;
+    Counters cn = {};
+    const v3 D = normalize3(dir);
+    const v3 rD = mk3(1.0f / D.x, 1.0f / D.y, 1.0f / D.z);
+    uint32_t nodeIndex = 0u, sp = 0u;
+    const float* T = S.tlas;
+    while (true) {
+        const float4* np = (const float4*)(T + (size_t)nodeIndex * 16u);
+        const float4 a = np[0], b = np[1], c = np[2], e = np[3];
+        const TlasStep step = tlas_node_step(a, b, c, e, O, rD, rec.h.t);
+        bool pop = false;
+        if (!step.leaf) {
+            if (step.nothingHit) pop = true;
+            else {
+                nodeIndex = step.near;
+                if (step.pushFar) {
+                    if (sp < PT_BVH_STACK_SIZE) tstack[sp * 64u] = step.far;
+                    sp++;
+                }
+            }
+        } else {
+            for (uint32_t i = 0; i < step.count; ++i) {
+                const uint32_t instanceIndex = pt_asuint(T[S.tlasIndexOffset + step.first + i]);
+                bool stopNow = false;
+                traverse_instance<false>(S, O, dir, instanceIndex, true, rec, st, cn, stopNow);
+                if (stopNow) return;
+            }
+            pop = true;
+        }
+        if (pop) {
+            sp = sp < PT_BVH_STACK_SIZE ? sp : PT_BVH_STACK_SIZE;
+            if (sp == 0u) break;
+            nodeIndex = tstack[--sp * 64u];
+        }
+    }
+}
+
+// what the fused kernels read of PTDirectParams, in four scalar registers; add: PTShadeMixed's second launch
+struct DirectArgs {
+    uint32_t strata, seed, flags;       // flags: PTDirectParams.flags | kAddBit
+    float minAlpha;
+};
+constexpr uint32_t kAddBit = 0x80000000u;
+
+// The fused kernels' ONE argument.  What only a chunk's front reads -- the lists and the material fetch's tables -- is read from
+// the kernel-argument segment again at the head of every chunk (front_args) and is dead once the front is done: held across the
+// pair loop next to what the walks read, those 17 words do not fit the scalar register file (18 spilled in the HAS_TLAS kernel).
+struct LightArgs {
+    DScene S;
+    DirectArgs P;
+    const PTRay* rays;
+    const PTRayHit* hits;
+    const PTRaySurface* surfaces;
+    float4* out;
+    uint2* slab;
+    uint32_t count, first;
+};
+typedef const __attribute__((address_space(4))) LightArgs* pt_light_kernargs;
+
+struct FrontArgs {
+    const float4* materials;
+    const uint32_t* tex;
+    const float4* attrs;
+    uint32_t materialCount, hasTextures;
+    const PTRay* rays;
+    const PTRayHit* hits;
+    const PTRaySurface* surfaces;
+    uint32_t seed, first;
+    float minAlpha;
+};
+
+// scalar loads of the kernel's own arguments (the struct is the kernel's only argument: it starts the segment).  The empty asm
+// makes the pointer a new value at every call, so the loads stay in the chunk they are written in
+PT_DEV FrontArgs front_args()
+{
+    pt_light_kernargs K = (pt_light_kernargs)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(K));
+    FrontArgs f;
+    f.materials = K->S.materials; f.tex = K->S.tex; f.attrs = K->S.attrs;
+    f.materialCount = K->S.materialCount; f.hasTextures = K->S.hasTextures;
+    f.rays = K->rays; f.hits = K->hits; f.surfaces = K->surfaces;
+    f.seed = K->P.seed; f.first = K->first; f.minAlpha = K->P.minAlpha;
+    return f;
+}
+
+// likewise what a pair reads between two walks (the light arrays) and what a chunk's end reads (the output)
+PT_DEV void light_arrays(const float4*& lights, const float4*& lightConst)
+{
+    pt_light_kernargs K = (pt_light_kernargs)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(K));
+    lights = K->S.lights;
+    lightConst = K->S.lightConst;
+}
+PT_DEV float4* output_array()
+{
+    pt_light_kernargs K = (pt_light_kernargs)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(K));
+    return K->out;
+}
+
+template <bool TLAS>
+PT_DEV void direct_light_body(const LightArgs& A)
+{
+    const DScene& S = A.S;                                              // the walks' fields: live throughout
+    const DirectArgs& P = A.P;
+    const uint32_t count = A.count;
+    __shared__ uint2 s_stack[PT_Q_LDS_STACK][64];
+    __shared__ uint32_t s_tstack[TLAS ? PT_BVH_STACK_SIZE : 1][64];
+    __shared__ uint32_t s_gw;
+    const uint32_t lane = threadIdx.x;
+    if (lane == 0u) s_gw = blockIdx.x;                                  // slab row = wave * 64 + lane (grid <= slab waves)
+    __builtin_amdgcn_wave_barrier();
+
+    Counters cn = {};
+    TravStackT<PT_Q_LDS_STACK, true> st;
+    st.lds = PT_LDS_U2(&s_stack[0][lane]);
+    st.stride = 64u;
+    st.gbase = A.slab;
+    st.gwave = PT_LDS_WORD(s_gw);
+
+    const bool centred = (P.flags & PT_DIRECT_CENTERED) != 0u;
+    const uint32_t lightCount = scene_lights(S);
+    for (uint32_t base = blockIdx.x * 64u; base < count; base += gridDim.x * 64u) {     // base is wave-uniform: no lane leaves early
+        const uint32_t i = base + lane;
+        const bool active = i < count;
+        bool hit = false;
+        ptdirect::Entry e = {};
+        uint32_t s;
+        {
+            const FrontArgs f = front_args();
+            DScene Sf = {};                                             // the scene as the material fetch reads it
+            Sf.materials = f.materials; Sf.tex = f.tex; Sf.attrs = f.attrs;
+            Sf.materialCount = f.materialCount; Sf.hasTextures = f.hasTextures;
+            if (active) {
+                HitRecords h;
+                hit_records(Sf, f.rays, f.hits, f.surfaces, i, nullptr, nullptr, 0u, h);
+                hit = !ptshade::is_miss(h.T);
+                if (hit) {
+                    const float4 r0 = ((const float4*)f.rays)[(size_t)i * 2], r1 = ((const float4*)f.rays)[(size_t)i * 2 + 1];
+                    const float D[3] = {r0.w, r1.x, r1.y};
+                    ptdirect::entry_begin(h.T, D, h.P, h.N, f.minAlpha, e);
+                }
+            }
+            s = ptdirect::entry_state(f.seed, (uint64_t)f.first + i);
+        }
+        float d0 = 0.0f, d1 = 0.0f, d2 = 0.0f;
+        const v3 o = mk3(e.O[0], e.O[1], e.O[2]);
+        // one loop over the pairs (l, k), both wave-uniform.  The light's 24 words are loaded again for every pair (scalar-cache
+        // hits) instead of being held in scalar registers across the walk, where the scene's pointers already fill the file
+        for (uint32_t l = 0, k = 0; l < lightCount;) {
+            DScene Sl = {};
+            light_arrays(Sl.lights, Sl.lightConst);
+            const ptdirect::Light Lt = uniform_light(Sl, l);
+            if (k >= ptdirect::pairs_of(Lt.type, P.strata)) {
+                ++l;
+                k = 0;
+                continue;
+            }
+            float x1 = 0.5f, x2 = 0.5f;
+            if (!centred && Lt.type == PT_LIGHT_TYPE_RECTANGLE) {
+                x1 = pt_random_float(&s);
+                x2 = pt_random_float(&s);
+            }
+            float dir[3], c[3];
+            const bool counts = hit && ptdirect::pair_eval(e, Lt, P.strata, k, x1, x2, dir, c);
+            ++k;
+            if (!__any(counts)) continue;                               // no lane's pair counts: no walk
+            if (counts) {
+                HitRecord rec;
+                rec.h.t = PT_FAR_PLANE; rec.h.u = 0.0f; rec.h.v = 0.0f; rec.h.triIndex = 0xFFFFFFFFu;
+                rec.pos = mk3(0.0f); rec.inst = 0xFFFFFFFFu;
+                const v3 d = mk3(dir[0], dir[1], dir[2]);
+                if (TLAS) anyhit_tlas(S, o, d, rec, st, (pt_lds_u32)&s_tstack[0][lane]);
+                else traverse_cwbvh<false>(S, o, d, true, rec.h, st, cn, PT_FAR_PLANE);
+                if (rec.h.triIndex == 0xFFFFFFFFu) { d0 = d0 + c[0]; d1 = d1 + c[1]; d2 = d2 + c[2]; }
+            }
+        }
+        if (active) {
+            float4* out = output_array();
+            if ((P.flags & kAddBit) != 0u) {
+                if (hit) {
+                    const float4 v = out[i];
+                    out[i] = make_float4(v.x + d0, v.y + d1, v.z + d2, v.w);
+                }
+            } else {
+                out[i] = hit ? make_float4(d0, d1, d2, 1.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            }
+        }
+    }
+}
+
+} // namespace
+
+// Stable, unmangled kernel names (rocprofv3 --kernel-trace lists them as they are written here).
+extern "C" __global__ __launch_bounds__(64) void pt_direct_light(LightArgs A) { direct_light_body<false>(A); }
+extern "C" __global__ __launch_bounds__(64) void pt_direct_light_tlas(LightArgs A) { direct_light_body<true>(A); }
+
+size_t pt_direct_slab_bytes_per_wave() { return (size_t)64 * PT_D_SLAB_ENTRIES * sizeof(uint2); }
+
+hipError_t pt_direct_grid_caps(int device, uint32_t caps[2])
+{
+    hipDeviceProp_t prop;
+    hipError_t e = hipGetDeviceProperties(&prop, device);
+    if (e != hipSuccess) return e;
+    const void* kernels[2] = {reinterpret_cast<const void*>(pt_direct_light), reinterpret_cast<const void*>(pt_direct_light_tlas)};
+    for (int k = 0; k < 2; ++k) {
+        int blocks = 0;
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernels[k], 64, 0);
+        if (e != hipSuccess) return e;
+        caps[k] = (uint32_t)(blocks > 0 ? blocks : 1) * (uint32_t)prop.multiProcessorCount;
+    }
+    return hipSuccess;
+}
+
+hipError_t pt_launch_direct_rays(const DScene& S, const PTDirectParams& P, uint32_t pairsPerEntry, const PTRay* rays, const PTShadeTerms* terms,
+                                 const PTReceiver* receivers, uint32_t count, uint32_t first, PTRay* outRays, float4* outContrib, hipStream_t stream)
+{
+    if (count == 0u || pairsPerEntry == 0u) return hipSuccess;
+    if (!ptdirect::strata_ok(P.strata) || (uint64_t)count * pairsPerEntry > (1ull << 31)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pt_direct_rays, dim3((count + 255u) / 256u), dim3(256), 0, stream, S, P, pairsPerEntry, rays, terms, receivers, count, first,
+                       (float4*)outRays, outContrib);
+    return hipGetLastError();
+}
+
+hipError_t pt_launch_direct_accumulate(const PTShadeTerms* terms, const float4* contrib, const PTRayHit* pairHits, uint32_t count, uint32_t pairsPerEntry,
+                                       float4* out, hipStream_t stream)
+{
+    if (count == 0u) return hipSuccess;
+    if ((uint64_t)count * pairsPerEntry > (1ull << 31)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pt_direct_accumulate, dim3((count + 255u) / 256u), dim3(256), 0, stream, terms, contrib, pairHits, count, pairsPerEntry, out);
+    return hipGetLastError();
+}
+
+hipError_t pt_launch_direct_light(const DScene& S, const PTDirectParams& P, const PTRay* rays, const PTRayHit* hits, const PTRaySurface* surfaces,
+                                  uint32_t count, uint32_t first, float4* out, bool add, uint2* slab, uint32_t gridCap, hipStream_t stream)
+{
+    if (count == 0u) return hipSuccess;
+    if (!ptdirect::strata_ok(P.strata) || !slab || gridCap == 0u) return hipErrorInvalidValue;
+#ifdef PT_D_GRID_CAP
+    gridCap = gridCap < PT_D_GRID_CAP ? gridCap : PT_D_GRID_CAP;         // the stress build: every wave takes several chunks of a short list
+#endif
+    const uint32_t chunks = (count + 63u) / 64u;
+    const uint32_t grid = chunks < gridCap ? chunks : gridCap;
+    const LightArgs A = {S, {P.strata, P.seed, P.flags | (add ? kAddBit : 0u), P.minAlpha}, rays, hits, surfaces, out, slab, count, first};
+    if (S.hasTlas) hipLaunchKernelGGL(pt_direct_light_tlas, dim3(grid), dim3(64), 0, stream, A);
+    else hipLaunchKernelGGL(pt_direct_light, dim3(grid), dim3(64), 0, stream, A);
+    return hipGetLastError();
+}

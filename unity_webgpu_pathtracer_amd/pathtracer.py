@@ -11,8 +11,8 @@ here renders, traverses or shades on the host.
 
 This module keeps the scene, the construction, the render passes, the presentation, the statistics and the schedule.  The
 other parts of the header are mixins of `PathTracer`, one module each: _queries.py (Parts 3 and 8, camera, pick, focus),
-_denoise.py (Parts 4, 6 and 7), _updates.py (Parts 5 and 9 to 12) and _bakes.py (Parts 13 to 23, with `ProbeVolume` and
-`ReflectionProbes`); what they share -- the two call forms among it -- is _hostcalls.py.
+_denoise.py (Parts 4, 6 and 7), _updates.py (Parts 5 and 9 to 12), _bakes.py (Parts 13 to 23, with `ProbeVolume` and
+`ReflectionProbes`) and _direct.py (Part 24); what they share -- the two call forms among it -- is _hostcalls.py.
 """
 import ctypes as C
 
@@ -20,6 +20,7 @@ import numpy as np
 
 from . import abi, plugin
 from ._bakes import Bakes, LightmapUnwrap, ProbeVolume, ReflectionProbes, probe_grid        # noqa: F401 (re-exported)
+from ._direct import Direct
 from ._denoise import Denoise, list_slot_to_pixel, select_blocks           # noqa: F401 (re-exported)
 from ._queries import Queries
 from ._updates import Updates
@@ -162,7 +163,7 @@ class BVHScene:
         plugin.check(plugin.load_library().PTSetScene(ctx, C.byref(self.desc())))
 
 
-class PathTracer(Queries, Denoise, Updates, Bakes):
+class PathTracer(Queries, Denoise, Updates, Bakes, Direct):
     """One render context on one GPU, driven exactly as PathTracer.cs drives the compute shader."""
 
     def __init__(self, scene: Scene, device: int = 0, width: int = 256, height: int = 256,

@@ -191,6 +191,16 @@ sig = {
     "PTUnwrapChartsHost": (i32, [C.POINTER(abi.PTUnwrapDesc), vp, vp, vp, vp, C.c_uint32, u32p, C.POINTER(abi.PTUnwrapStats)]),
     "PTPackChartsHost": (i32, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, vp, u32p]),
     "PTEmitChartUVsHost": (i32, [C.POINTER(abi.PTUnwrapDesc), vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, vp]),
+    # Part 24 (direct light at first hits)
+    "PTDirectPairCount": (i32, [vp, C.c_uint32, u32p]),
+    "PTDirectRays": (i32, [vp, C.POINTER(abi.PTDirectParams), vp, vp, vp, C.c_uint64, vp, vp]),
+    "PTDirectAccumulate": (i32, [vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp]),
+    "PTDirectLight": (i32, [vp, C.POINTER(abi.PTDirectParams), vp, vp, vp, C.c_uint64, vp]),
+    "PTShadeMixed": (i32, [vp, C.POINTER(abi.PTShadeInputs), C.POINTER(abi.PTDirectParams), vp, vp, vp, C.c_uint64, vp]),
+    "PTShadeMixedFrame": (i32, [vp, C.POINTER(abi.PTFrameParams), C.POINTER(abi.PTShadeInputs), C.POINTER(abi.PTDirectParams), vp, vp]),
+    "PTDirectPairCountHost": (i32, [vp, C.c_uint32, C.c_uint32, u32p]),
+    "PTDirectRaysHost": (i32, [C.POINTER(abi.PTDirectParams), vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, vp]),
+    "PTDirectAccumulateHost": (i32, [vp, vp, vp, C.c_uint64, C.c_uint32, vp]),
     "PTGetLastError": (C.c_char_p, []), "PTGetVersion": (i32, []),
 }
 EXPORTED_SYMBOLS = list(sig)
@@ -1007,6 +1017,61 @@ def lightmap_lookup(bindings, tri_attrs, material_count: int, rays, hits, surfac
         raise PluginError(abi.PT_ERR_INVALID_ARG, "PTLightmapLookupHost failed: " + lib.PTGetBVHBuildError().decode())
     del keep
     return out, which
+
+
+# ---- direct light at first hits on the host (include/ptmi_plugin.h Part 24)
+def _light_rows(lights):
+    return np.ascontiguousarray(lights, dtype=np.float32).reshape(-1, 16)
+
+
+def direct_pair_count(lights, strata: int = 1) -> int:
+    """PTDirectPairCountHost: the pairs one entry has with these lights -- (k, 16) float32 PTLight records --: 1 per point or spot
+    light, strata * strata per rectangle light, none for any other type."""
+    L = _light_rows(lights)
+    n = C.c_uint32()
+    lib = load_library()
+    if not lib.PTDirectPairCountHost(L.ctypes.data if L.shape[0] else None, L.shape[0], int(strata), C.byref(n)):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTDirectPairCountHost failed: " + lib.PTGetBVHBuildError().decode())
+    return n.value
+
+
+def direct_rays(lights, rays, terms, receivers, strata: int = 1, seed: int = 0, centered: bool = False, min_alpha: float = 0.0, params=None):
+    """The pairs' shadow rays and contributions on the host (PTDirectRaysHost): lights (k, 16) PTLight records, rays (n, 8) PTRay
+    rows, terms (n, 12) and receivers (n, 8) as PathTracer.shade_surfaces returns them.  params: a ready PTDirectParams instead of
+    the keywords.  Returns (pair rays (n * pairs, 8), contributions (n * pairs, 4)), float32; a pair that does not count has
+    tmax = 0 and zero contribution."""
+    L = _light_rows(lights)
+    r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+    t = np.ascontiguousarray(terms, dtype=np.float32).reshape(-1, 12)
+    rc = np.ascontiguousarray(receivers, dtype=np.float32).reshape(-1, 8)
+    n = r.shape[0]
+    assert t.shape[0] == n and rc.shape[0] == n, (r.shape, t.shape, rc.shape)
+    p = params if params is not None else abi.direct_params(strata, seed, centered, min_alpha)
+    lib = load_library()
+    lights_ptr = L.ctypes.data if L.shape[0] else None
+    pairs = C.c_uint32()
+    ok = lib.PTDirectPairCountHost(lights_ptr, L.shape[0], p.strata, C.byref(pairs))
+    out_rays, contrib = np.empty((n * pairs.value, 8), np.float32), np.empty((n * pairs.value, 4), np.float32)
+    if not ok or not lib.PTDirectRaysHost(C.byref(p), lights_ptr, L.shape[0], r.ctypes.data, t.ctypes.data, rc.ctypes.data, n, out_rays.ctypes.data,
+                                          contrib.ctypes.data):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTDirectRaysHost failed: " + lib.PTGetBVHBuildError().decode())
+    return out_rays, contrib
+
+
+def direct_accumulate(terms, contrib, pair_hits, pairs_per_entry: int) -> np.ndarray:
+    """The sum over the visible pairs on the host (PTDirectAccumulateHost): terms (n, 12), contrib (n * pairs, 4) as direct_rays
+    returns it, pair_hits (n * pairs, 4) PTRayHit rows of an any-hit query over the pair rays.  Returns (n, 4) float32: the direct
+    light and 1, zeros for a miss."""
+    t = np.ascontiguousarray(terms, dtype=np.float32).reshape(-1, 12)
+    c = np.ascontiguousarray(contrib, dtype=np.float32).reshape(-1, 4)
+    h = np.ascontiguousarray(pair_hits, dtype=np.float32).reshape(-1, 4)
+    n = t.shape[0]
+    assert c.shape[0] == n * pairs_per_entry and h.shape[0] == n * pairs_per_entry, (t.shape, c.shape, h.shape, pairs_per_entry)
+    out = np.empty((n, 4), np.float32)
+    lib = load_library()
+    if not lib.PTDirectAccumulateHost(t.ctypes.data, c.ctypes.data, h.ctypes.data, n, int(pairs_per_entry), out.ctypes.data):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTDirectAccumulateHost failed: " + lib.PTGetBVHBuildError().decode())
+    return out
 
 
 def build_tlas(instances: np.ndarray):
