@@ -2234,6 +2234,100 @@ PT_API int PTDirectRaysHost(const PTDirectParams* params, const void* lights, ui
 PT_API int PTDirectAccumulateHost(const PTShadeTerms* terms, const float* contrib, const PTRayHit* pairHits, uint64_t count,
                                   uint32_t pairsPerEntry, float* out);
 
+/* =====================================================================================================================
+ * Part 25: direct light over many lights.  Part 24's fused calls walk every light of the scene for every entry; with a few
+ * hundred local lights almost every pair falls to lsDistance > range.  This part adds a uniform grid over the lights and three
+ * calls that offer each wave only the lights the grid lists for its lanes' cells.  Step 7 of Part 24 says that a pair which
+ * does not count contributes nothing and gets no walk, so leaving it out changes no bit: PTDirectLightCulled,
+ * PTShadeMixedCulled and PTShadeMixedFrameCulled give PTDirectLight's, PTShadeMixed's and PTShadeMixedFrame's bits.  An addition
+ * detected by symbol; PTGetVersion, PTDirectParams, its flags and its refusals are unchanged.
+ *
+ * Left out: a spot's cone beyond its half-space; a hierarchical or screen-space structure; culling inside PTDirectRays /
+ * PTDirectAccumulate; PTGroup wrappers.
+ *
+ * The rule (csrc/light_grid_rule.h is its one definition, written out operator by operator there; the kernels, the host twin
+ * and tests/light_grid_ref.py evaluate it).  The grid is dims[0] x dims[1] x dims[2] cubes of cellSize from origin.
+ *  1. The cell of a point X: per axis t = (X[a] - origin[a]) / cellSize; inside iff t >= 0 and t < (float)dims[a]; i[a] =
+ *     (uint32_t)t; cell = (i.z * dims.y + i.y) * dims.x + i.x.  A point outside on any axis (a NaN is outside) gets cell index
+ *     `cells`, the overflow cell, whose list is every light 0 ... L-1: such points are correct, merely not culled.
+ *  2. A cell lists light l unless a test proves that no pair of l counts at any point step 1 maps to the cell: the type has no
+ *     pairs (directional, unknown); every emission channel is 0; the squared distance from the light's centre C to the cell's
+ *     box, inflated by `pad`, exceeds (R * (1 + 2^-10))^2 -- C = position and R = range, for a rectangle C = position + u / 2 + v
+ *     / 2 and R = range + (|u| + |v|) / 2 --; or, for a rectangle and for a spot whose outer cosine v.x >= 0, the inflated box
+ *     lies behind the plane through position with the light's derived normal by more than R * (1 + 2^-10) * 2^-16 (the margin
+ *     covers the rounding of the cosine the pair rule decides by).  Every comparison culls only when it is
+ *     TRUE, so a NaN or an infinity anywhere keeps the light listed.  pad = cellSize * 2^-10 + (|origin[a]| + cellSize *
+ *     dims[a]) * 2^-20 per axis covers the rounding of step 1 and of the box corners (DESIGN.md 5.30 derives it).
+ *     Nothing is assumed of the materials: a light with a negative emission channel stays listed.
+ *  3. Storage: offsets, cells + 2 words -- the list of cell c is indices[offsets[c] ... offsets[c + 1]), the overflow cell's comes
+ *     last and offsets[cells + 1] is the total --; indices, the lights of each list in ascending index; rectBefore, L + 1 words,
+ *     the number of rectangle lights with a smaller index.
+ *
+ * PTBuildLightGrid builds the grid for the CURRENT generation of the light arrays on the context's stream, into memory the
+ * context owns: one lane per cell, three launches (count, scan, emit), no atomics -- the same input gives the same bytes.  It
+ * reads the 4-byte total back once between scan and emit (one stream synchronisation) to size the index buffer; a call that has to
+ * grow one of the context's grid buffers (the first build, more cells, more lights) drains the stream once more before it frees
+ * the smaller one; everything else is stream-ordered.  PTUpdateLights and PTSetScene make the grid stale: the culled calls refuse a stale or absent grid with
+ * PT_ERR_INVALID_ARG ("no light grid" / "the light grid is stale") and never read a grid built for other lights.  A scene without
+ * HAS_LIGHTS builds a grid whose lists are all empty.
+ *
+ * The culled calls.  After Part 24's steps 1-3 a lane takes the cell of its O (step 3's, the point the light sample uses); a
+ * miss and a lane past `count` hold an empty list.  The wave visits the union of its lanes' lists in ascending light index and
+ * every lane evaluates its pair with every visited light, exactly as PTDirectLight does: a lane whose cell does not list the
+ * light gets a pair that does not count.  Without PT_DIRECT_CENTERED, when the loop goes from light a to light b every lane
+ * advances its state by 2 * S * S * (rectBefore[b] - rectBefore[a + 1]) calls of pt_rng_next, the draws PTDirectLight makes for the
+ * rectangle lights in between; the draws past the last visited light are dropped, nothing reads the state afterwards.
+ *
+ * Errors: Part 24's, plus PT_ERR_INVALID_ARG for a grid whose structSize is 0 (or below this header's), a dim outside 1 ... 256,
+ * more than 2^20 cells, a cellSize that is not finite and > 0, a nonzero reserved word; PT_ERR_NO_SCENE before PTSetScene.
+ * PTReadLightGrid and PTLightGridInfo synchronise the context's stream.  PTBuildLightGridHost takes no context and no GPU;
+ * lights: lightCount PTLight records; it returns 1, or 0 with PTGetBVHBuildError() set.
+ * ===================================================================================================================== */
+#define PT_LIGHT_GRID_MAX_DIM   256u
+#define PT_LIGHT_GRID_MAX_CELLS (1u << 20)
+
+typedef struct PTLightGridParams {
+    uint32_t structSize;            /* sizeof(PTLightGridParams) of the caller's header; members are only appended */
+    float    origin[3];             /* the corner of cell (0, 0, 0) */
+    float    cellSize;              /* finite, > 0 */
+    uint32_t dims[3];               /* 1 ... PT_LIGHT_GRID_MAX_DIM each; their product at most PT_LIGHT_GRID_MAX_CELLS */
+    uint32_t reserved;              /* must be 0 */
+} PTLightGridParams;
+
+typedef struct PTLightGridStats {
+    uint32_t structSize;
+    uint32_t built;                 /* 1: a grid exists (it may be stale) */
+    uint32_t cells;                 /* without the overflow cell */
+    uint32_t lightCount;            /* L of the lights it was built for */
+    uint32_t longest;               /* the longest list among cells 0 ... cells - 1 */
+    uint32_t stale;                 /* 1: the lights changed since the build */
+    uint64_t entries;               /* offsets[cells + 1]: all lists, the overflow cell's included */
+    uint64_t generation;            /* the light generation the grid was built for: PTSetScene and PTUpdateLights each start one */
+} PTLightGridStats;
+
+#ifdef __cplusplus
+static_assert(sizeof(PTLightGridParams) == 36 && sizeof(PTLightGridStats) == 40, "PTLightGridParams is 36 bytes, PTLightGridStats 40");
+#else
+_Static_assert(sizeof(PTLightGridParams) == 36 && sizeof(PTLightGridStats) == 40, "PTLightGridParams is 36 bytes, PTLightGridStats 40");
+#endif
+
+PT_API int PTBuildLightGrid(PTContext* ctx, const PTLightGridParams* params);
+/* host pointers: offsets cells + 2 words, rectBefore L + 1 words, indices indexCapacity words (NULL with 0: none are copied);
+ * any of the three may be NULL.  PT_ERR_INVALID_ARG when indices is given and indexCapacity is below the total */
+PT_API int PTReadLightGrid(PTContext* ctx, uint32_t* offsets, uint32_t* indices, uint64_t indexCapacity, uint32_t* rectBefore);
+PT_API int PTLightGridInfo(PTContext* ctx, PTLightGridStats* out);
+/* PTDirectLight, PTShadeMixed and PTShadeMixedFrame through the grid: the same arguments, the same bits */
+PT_API int PTDirectLightCulled(PTContext* ctx, const PTDirectParams* params, const PTRay* dRays, const PTRayHit* dHits, const PTRaySurface* dSurface,
+                               uint64_t count, float* dOut);
+PT_API int PTShadeMixedCulled(PTContext* ctx, const PTShadeInputs* inputs, const PTDirectParams* params, const PTRay* dRays, const PTRayHit* dHits,
+                              const PTRaySurface* dSurface, uint64_t count, float* dOut);
+PT_API int PTShadeMixedFrameCulled(PTContext* ctx, const PTFrameParams* params, const PTShadeInputs* inputs, const PTDirectParams* direct, float* dOut,
+                                   PTRay* dOutRays);
+/* host twin, no GPU.  offsets: cells + 2 words; rectBefore: lightCount + 1 words; indices: indexCapacity words, written only when
+ * the total fits (NULL with 0: count only); *outTotal (may be NULL): the total */
+PT_API int PTBuildLightGridHost(const PTLightGridParams* params, const void* lights, uint32_t lightCount, uint32_t* offsets, uint32_t* indices,
+                                uint64_t indexCapacity, uint32_t* rectBefore, uint64_t* outTotal);
+
 /* Text of the last error on the calling thread ("" if none). */
 PT_API const char* PTGetLastError(void);
 /* Library/ABI version: (major << 16) | minor. */

@@ -443,6 +443,36 @@ def direct_params(strata: int = 1, seed: int = 0, centered: bool = False, min_al
     return p
 
 
+# ---- direct light over many lights: the light grid (include/ptmi_plugin.h Part 25)
+PT_LIGHT_GRID_MAX_DIM = 256
+PT_LIGHT_GRID_MAX_CELLS = 1 << 20
+
+
+class PTLightGridParams(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("origin", C.c_float * 3), ("cellSize", C.c_float), ("dims", C.c_uint32 * 3), ("reserved", C.c_uint32)]
+
+
+class PTLightGridStats(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("built", C.c_uint32), ("cells", C.c_uint32), ("lightCount", C.c_uint32), ("longest", C.c_uint32),
+                ("stale", C.c_uint32), ("entries", C.c_uint64), ("generation", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "structSize"}
+
+
+assert C.sizeof(PTLightGridParams) == 36 and C.sizeof(PTLightGridStats) == 40
+
+
+def light_grid_params(origin, cell_size: float, dims) -> PTLightGridParams:
+    """A PTLightGridParams with structSize set: dims[0] x dims[1] x dims[2] cubes of cell_size from origin"""
+    p = PTLightGridParams()
+    p.structSize = C.sizeof(PTLightGridParams)
+    p.origin[:] = [float(x) for x in origin]
+    p.cellSize = float(cell_size)
+    p.dims[:] = [int(d) for d in dims]
+    return p
+
+
 # ---- lightmap charts (include/ptmi_plugin.h Part 14)
 PT_CHART_MAX_SIZE = 8192
 PT_CHART_MAX_DILATE = 16

@@ -27,6 +27,7 @@
 #include "repack_rule.h"
 #include "unwrap_rule.h"
 #include "direct_rule.h"
+#include "light_grid_rule.h"
 #include "ptmi_plugin.h"
 
 namespace {
@@ -406,6 +407,14 @@ PT_API int PTDirectAccumulateHost(const PTShadeTerms* terms, const float* contri
                                   float* out)
 {
     if (!ptdirect::accumulate_host(terms, contrib, pairHits, count, pairsPerEntry, out, g_buildError)) return 0;
+    g_buildError.clear();
+    return 1;
+}
+// The light grid of the culled direct-light calls on the host (light_grid_host.cpp; Part 25 has the rule).  No GPU involved.
+PT_API int PTBuildLightGridHost(const PTLightGridParams* params, const void* lights, uint32_t lightCount, uint32_t* offsets, uint32_t* indices,
+                                uint64_t indexCapacity, uint32_t* rectBefore, uint64_t* outTotal)
+{
+    if (!ptlgrid::build_host(params, lights, lightCount, offsets, indices, indexCapacity, rectBefore, outTotal, g_buildError)) return 0;
     g_buildError.clear();
     return 1;
 }

@@ -392,6 +392,7 @@ int set_scene(PTContext* c, const PTSceneDesc* hostScene, bool validate)
     c->update.instanceCount = tlasOn ? s->instanceCount : 0u;
     c->update.sceneLightCount = lights ? s->lightCount : 0u;
     c->update.origTlasNodes = tlasOn ? s->tlasIndexOffset / 16u : 0u;
+    ++c->update.lightGeneration;
     c->update.lightTypes.clear();
     for (uint32_t l = 0; lights && l < s->lightCount; ++l) c->update.lightTypes.push_back(((const PTLight*)s->lights)[l].type);
     std::vector<uint32_t>& valid = c->update.validTextures;

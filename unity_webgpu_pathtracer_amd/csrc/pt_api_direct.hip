@@ -1,5 +1,6 @@
 // pt_api_direct.hip — direct light at first hits: the pair count, the pairs' rays, the sum, the fused call, the mixed list call
-// and a whole mixed frame (include/ptmi_plugin.h Part 24).
+// and a whole mixed frame (include/ptmi_plugin.h Part 24), and the same three through the context's light grid
+// (Part 25).
 #include "pt_context.h"
 #include "direct_rule.h"
 
@@ -23,23 +24,38 @@ uint64_t pairs_per_entry(const PTContext* c, uint32_t strata)
     return pairs;
 }
 
+// grid: the context's light grid, which the entry point has found current (current_light_grid): the culled kernels (Part 25);
+// null: the kernels that walk every light
 int direct_light(PTContext* c, const PTDirectParams& p, const PTRay* dRays, const PTRayHit* dHits, const PTRaySurface* dSurface, uint64_t count, float4* dOut,
-                 bool add)
+                 bool add, const PTLightGridDevice* grid = nullptr)
 {
     if (int rc = query_prepare(c)) return rc;
-    const uint32_t cap = c->query.directCaps[c->scene.hasTlas ? 1 : 0];
+    const int k = c->scene.hasTlas ? 1 : 0;
+    uint32_t cap = c->query.directCaps[k];
+    if (grid) {
+        if (!c->query.culledCaps[0]) HIP_TRY(pt_direct_culled_grid_caps(c->device, c->query.culledCaps));
+        cap = c->query.culledCaps[k] < c->query.capMax ? c->query.culledCaps[k] : c->query.capMax;      // the slab holds capMax waves
+    }
     return for_each_launch(count, 1ull << 28, [&](uint64_t first, uint32_t n) {
         HIP_TRY(pt_launch_direct_light(c->scene, p, dRays + first, dHits + first, dSurface + first, n, (uint32_t)first, dOut + first, add,
-                                       (uint2*)c->query.slab.ptr, cap, c->stream));
+                                       (uint2*)c->query.slab.ptr, cap, c->stream, grid));
         return PT_OK;
     });
 }
 
-// PTShadeLightmapped's launches, then pt_direct_light adding into dOut (a ShadeList; user: the checked PTDirectParams)
+// what the mixed calls hand their list call: the checked PTDirectParams and, for a culled call, the grid its entry point checked
+struct MixedUser {
+    PTDirectParams direct;
+    bool culled;
+    PTLightGridDevice grid;
+};
+
+// PTShadeLightmapped's launches, then pt_direct_light adding into dOut (a ShadeList; user: a MixedUser)
 int shade_mixed(PTContext* c, const PTShadeInputs& in, const PTRay* dRays, const PTRayHit* dHits, const PTRaySurface* dSurface, uint64_t count, float4* dOut,
                 const void* user)
 {
-    const PTDirectParams& direct = *(const PTDirectParams*)user;
+    const PTDirectParams& direct = ((const MixedUser*)user)->direct;
+    const PTLightGridDevice* grid = ((const MixedUser*)user)->culled ? &((const MixedUser*)user)->grid : nullptr;
     int rc = for_each_launch(count, 1ull << 30, [&](uint64_t first, uint32_t n) {
         HIP_TRY(pt_launch_shade_lightmapped(c->scene, in, c->lightmaps.device(), c->lightmaps.count, dRays + first, dHits + first, dSurface + first, n,
                                             dOut + first, c->stream));
@@ -47,7 +63,58 @@ int shade_mixed(PTContext* c, const PTShadeInputs& in, const PTRay* dRays, const
     });
     if (rc) return rc;
     if (pairs_per_entry(c, direct.strata) == 0u) return PT_OK;               // nothing to add: PTShadeLightmapped's bits
-    return direct_light(c, direct, dRays, dHits, dSurface, count, dOut, true);
+    return direct_light(c, direct, dRays, dHits, dSurface, count, dOut, true, grid);
+}
+
+// the bodies of the fused call, the mixed list call and the mixed frame; culled: through the context's light grid, checked here, once
+int direct_light_call(PTContext* c, const PTDirectParams* params, const PTRay* dRays, const PTRayHit* dHits, const PTRaySurface* dSurface, uint64_t count,
+                      float* dOut, const char* who, bool culled)
+{
+    const std::string w(who);
+    if (!c) return fail(PT_ERR_INVALID_ARG, w + ": ctx == NULL");
+    PTDirectParams p;
+    if (int rc = import_direct_params(params, p, who)) return rc;
+    if (!dRays || !dHits || !dSurface || !dOut) return fail(PT_ERR_INVALID_ARG, w + ": rays/hits/surface/out == NULL");
+    if (misaligned(dRays) || misaligned(dHits) || misaligned(dSurface) || misaligned(dOut))
+        return fail(PT_ERR_INVALID_ARG, w + ": rays/hits/surface/out is not 16-byte aligned");
+    if (!c->hasScene) return fail(PT_ERR_NO_SCENE, "PTSetScene has not been called");
+    PTLightGridDevice grid;
+    if (culled)                                                         // also with count == 0: a stale grid is the caller's mistake
+        if (int rc = current_light_grid(c, who, grid)) return rc;
+    if (count == 0) return PT_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    RoctxRange range("PT direct light (enqueue)");
+    return direct_light(c, p, dRays, dHits, dSurface, count, (float4*)dOut, false, culled ? &grid : nullptr);
+}
+
+int shade_mixed_call(PTContext* c, const PTShadeInputs* inputs, const PTDirectParams* params, const PTRay* dRays, const PTRayHit* dHits,
+                     const PTRaySurface* dSurface, uint64_t count, float* dOut, const char* who, bool culled)
+{
+    const std::string w(who);
+    if (!c) return fail(PT_ERR_INVALID_ARG, w + ": ctx == NULL");
+    if (int rc = check_shade_inputs(inputs, who)) return rc;
+    MixedUser u = {{}, culled, {}};
+    if (int rc = import_direct_params(params, u.direct, who)) return rc;
+    if (!dRays || !dHits || !dSurface || !dOut) return fail(PT_ERR_INVALID_ARG, w + ": rays/hits/surface/out == NULL");
+    if (misaligned(dRays) || misaligned(dHits) || misaligned(dSurface) || misaligned(dOut))
+        return fail(PT_ERR_INVALID_ARG, w + ": rays/hits/surface/out is not 16-byte aligned");
+    if (!c->hasScene) return fail(PT_ERR_NO_SCENE, "PTSetScene has not been called");
+    if (culled)
+        if (int rc = current_light_grid(c, who, u.grid)) return rc;
+    if (count == 0) return PT_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    return shade_mixed(c, *inputs, dRays, dHits, dSurface, count, (float4*)dOut, &u);
+}
+
+int shade_mixed_frame_call(PTContext* c, const PTFrameParams* hostParams, const PTShadeInputs* inputs, const PTDirectParams* direct, float* dOut,
+                           PTRay* dOutRays, const char* who, bool culled)
+{
+    if (!c) return fail(PT_ERR_INVALID_ARG, std::string(who) + ": ctx == NULL");
+    MixedUser u = {{}, culled, {}};
+    if (int rc = import_direct_params(direct, u.direct, who)) return rc;
+    if (culled && c->hasScene)                                          // before the frame's rays are made; without a scene shade_frame refuses
+        if (int rc = current_light_grid(c, who, u.grid)) return rc;
+    return shade_frame(c, hostParams, inputs, dOut, dOutRays, who, shade_mixed, &u);
 }
 
 } // namespace
@@ -101,42 +168,38 @@ PT_API int PTDirectAccumulate(PTContext* c, const PTShadeTerms* dTerms, const fl
 PT_API int PTDirectLight(PTContext* c, const PTDirectParams* params, const PTRay* dRays, const PTRayHit* dHits, const PTRaySurface* dSurface, uint64_t count,
                          float* dOut)
 {
-    if (!c) return fail(PT_ERR_INVALID_ARG, "PTDirectLight: ctx == NULL");
-    PTDirectParams p;
-    if (int rc = import_direct_params(params, p, "PTDirectLight")) return rc;
-    if (!dRays || !dHits || !dSurface || !dOut) return fail(PT_ERR_INVALID_ARG, "PTDirectLight: rays/hits/surface/out == NULL");
-    if (misaligned(dRays) || misaligned(dHits) || misaligned(dSurface) || misaligned(dOut))
-        return fail(PT_ERR_INVALID_ARG, "PTDirectLight: rays/hits/surface/out is not 16-byte aligned");
-    if (!c->hasScene) return fail(PT_ERR_NO_SCENE, "PTSetScene has not been called");
-    if (count == 0) return PT_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    RoctxRange range("PT direct light (enqueue)");
-    return direct_light(c, p, dRays, dHits, dSurface, count, (float4*)dOut, false);
+    return direct_light_call(c, params, dRays, dHits, dSurface, count, dOut, "PTDirectLight", false);
 }
 
 PT_API int PTShadeMixed(PTContext* c, const PTShadeInputs* inputs, const PTDirectParams* params, const PTRay* dRays, const PTRayHit* dHits,
                         const PTRaySurface* dSurface, uint64_t count, float* dOut)
 {
-    if (!c) return fail(PT_ERR_INVALID_ARG, "PTShadeMixed: ctx == NULL");
-    if (int rc = check_shade_inputs(inputs, "PTShadeMixed")) return rc;
-    PTDirectParams p;
-    if (int rc = import_direct_params(params, p, "PTShadeMixed")) return rc;
-    if (!dRays || !dHits || !dSurface || !dOut) return fail(PT_ERR_INVALID_ARG, "PTShadeMixed: rays/hits/surface/out == NULL");
-    if (misaligned(dRays) || misaligned(dHits) || misaligned(dSurface) || misaligned(dOut))
-        return fail(PT_ERR_INVALID_ARG, "PTShadeMixed: rays/hits/surface/out is not 16-byte aligned");
-    if (!c->hasScene) return fail(PT_ERR_NO_SCENE, "PTSetScene has not been called");
-    if (count == 0) return PT_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    return shade_mixed(c, *inputs, dRays, dHits, dSurface, count, (float4*)dOut, &p);
+    return shade_mixed_call(c, inputs, params, dRays, dHits, dSurface, count, dOut, "PTShadeMixed", false);
 }
 
 PT_API int PTShadeMixedFrame(PTContext* c, const PTFrameParams* hostParams, const PTShadeInputs* inputs, const PTDirectParams* direct, float* dOut,
                              PTRay* dOutRays)
 {
-    if (!c) return fail(PT_ERR_INVALID_ARG, "PTShadeMixedFrame: ctx == NULL");
-    PTDirectParams p;
-    if (int rc = import_direct_params(direct, p, "PTShadeMixedFrame")) return rc;
-    return shade_frame(c, hostParams, inputs, dOut, dOutRays, "PTShadeMixedFrame", shade_mixed, &p);
+    return shade_mixed_frame_call(c, hostParams, inputs, direct, dOut, dOutRays, "PTShadeMixedFrame", false);
+}
+
+// ---- Part 25: the same calls through the context's light grid ----
+PT_API int PTDirectLightCulled(PTContext* c, const PTDirectParams* params, const PTRay* dRays, const PTRayHit* dHits, const PTRaySurface* dSurface,
+                               uint64_t count, float* dOut)
+{
+    return direct_light_call(c, params, dRays, dHits, dSurface, count, dOut, "PTDirectLightCulled", true);
+}
+
+PT_API int PTShadeMixedCulled(PTContext* c, const PTShadeInputs* inputs, const PTDirectParams* params, const PTRay* dRays, const PTRayHit* dHits,
+                              const PTRaySurface* dSurface, uint64_t count, float* dOut)
+{
+    return shade_mixed_call(c, inputs, params, dRays, dHits, dSurface, count, dOut, "PTShadeMixedCulled", true);
+}
+
+PT_API int PTShadeMixedFrameCulled(PTContext* c, const PTFrameParams* hostParams, const PTShadeInputs* inputs, const PTDirectParams* direct, float* dOut,
+                                   PTRay* dOutRays)
+{
+    return shade_mixed_frame_call(c, hostParams, inputs, direct, dOut, dOutRays, "PTShadeMixedFrameCulled", true);
 }
 
 } // extern "C"

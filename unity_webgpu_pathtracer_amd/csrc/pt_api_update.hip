@@ -160,6 +160,7 @@ PT_API int PTUpdateLights(PTContext* c, const void* lights, uint32_t count)
     c->scene.lights = dl;
     c->scene.lightConst = dc;
     c->scene.lightCount = (int32_t)count;
+    ++c->update.lightGeneration;
     c->update.lightTypes.clear();
     for (uint32_t l = 0; l < count; ++l) c->update.lightTypes.push_back(((const PTLight*)lights)[l].type);
     return PT_OK;

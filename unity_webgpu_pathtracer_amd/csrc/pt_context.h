@@ -12,6 +12,7 @@
 #include "pt_adaptive_gather.h"
 #include "pt_unwrap.h"
 #include "pt_direct.h"
+#include "pt_light_grid.h"
 #include "bvh_refit.h"
 #include "bvh_builder_gpu.h"
 
@@ -192,6 +193,7 @@ struct PTContext {
     struct Query {
         uint32_t caps[PT_QUERY_KERNELS] = {};
         uint32_t directCaps[2] = {};            // pt_direct_light, pt_direct_light_tlas (Part 24): they share the slab
+        uint32_t culledCaps[2] = {};            // pt_direct_light_grid, pt_direct_light_grid_tlas (Part 25), on first use: likewise
         uint32_t capMax = 0;
         DeviceBuffer slab;
         DeviceBuffer rays, hits, surface;       // PTTraceRaysHost staging, grown on demand
@@ -365,7 +367,20 @@ struct PTContext {
         uint32_t instanceCount = 0, sceneLightCount = 0, origTlasNodes = 0;
         std::vector<uint32_t> validTextures;            // texture indices PTSetScene validated (sorted)
         std::vector<uint32_t> lightTypes;               // the current lights' types (PTSetScene, PTUpdateLights): Part 24 counts pairs on the host
+        uint64_t lightGeneration = 0;                   // PTSetScene and PTUpdateLights each start one (Part 25: what a light grid was built for)
     } update;
+    // the light grid of the culled direct-light calls (PTBuildLightGrid, Part 25): grown on demand, kept across PTSetScene, written
+    // and read in stream order on the context stream; current only while generation == update.lightGeneration
+    struct LightGrid {
+        DeviceBuffer offsets, indices, rectBefore;      // light_grid_rule.h's storage
+        DeviceBuffer blockCounts;                       // 4 B per block of 1024 cells, then the 4-byte total
+        PinnedBuffer total;                             // the total, read back
+        ptlgrid::Grid g = {};
+        bool built = false;
+        uint64_t generation = 0;
+        uint32_t cells = 0, lightCount = 0, entries = 0;
+        int64_t longest = -1;                           // PTLightGridInfo computes it on first use (-1: not yet)
+    } lightGrid;
 };
 
 struct PTGroup {
@@ -498,6 +513,8 @@ using ShadeList = int (*)(PTContext* c, const PTShadeInputs& in, const PTRay* dR
                           float4* dOut, const void* user);
 int shade_frame(PTContext* c, const PTFrameParams* hostParams, const PTShadeInputs* inputs, float* dOut, PTRay* dOutRays, const char* who, ShadeList shade,
                 const void* user = nullptr);
+// pt_api_light_grid.hip: the context's grid for a culled call, or the refusal of an absent or stale one
+int current_light_grid(PTContext* c, const char* who, PTLightGridDevice& out);
 int query_prepare(PTContext* c);                                                // pt_api_query.hip: the grid caps and the stack slab of the query kernels, on first use
 int set_scene(PTContext* c, const PTSceneDesc* hostScene, bool validate);      // pt_api_context.hip; PTGroupSetScene validates once
 int drain_events(PTContext* c);                                                 // pt_api_context.hip

@@ -14,6 +14,10 @@
 //                           segment again per chunk, so neither kernel spills a scalar register.  The CWBVH stack is pt_query.hip's (PT_Q_LDS_STACK entries per lane in LDS, the rest in the
 //                           context's slab); the HAS_TLAS kernel keeps its 32 TLAS stack entries per lane in LDS too, so neither
 //                           kernel has scratch.
+//     pt_direct_light_grid[_tlas]  the same kernels over a light grid (Part 25): after the front a lane takes the
+//                           list of its O's cell; the wave visits the union of its lanes' lists in ascending light index -- a
+//                           cross-lane minimum of the list heads per visited light -- and makes up the draws of the rectangle
+//                           lights it jumps over.  The pair, the walk and the sum are the kernels' above, so are the bits.
 //
 // The arithmetic is direct_rule.h's, which the host twins evaluate too; the walks are the render's (pt_device.h).
 #include "pt_device.h"
@@ -21,6 +25,7 @@
 #include "pt_shade_hit.h"
 #include "direct_rule.h"
 #include "pt_direct.h"
+#include "pt_light_grid.h"
 
 #define PT_D_SLAB_ENTRIES (PT_BVH_STACK_SIZE - PT_Q_LDS_STACK)
 
@@ -304,20 +309,201 @@ PT_DEV void direct_light_body(const LightArgs& A)
     }
 }
 
+// ---- the culled kernels (Part 25): direct_light_body with the pair loop over the union of the lanes' cell lists ----
+// The culled kernels' ONE argument: LightArgs first, so that front_args, light_arrays and output_array read it as they are
+struct GridLightArgs {
+    LightArgs A;
+    PTLightGridDevice G;
+};
+typedef const __attribute__((address_space(4))) GridLightArgs* pt_grid_kernargs;
+
+// what a chunk's front reads of the grid, and what a step to the next light reads: from the argument segment again, as front_args
+PT_DEV PTLightGridDevice grid_args()
+{
+    pt_grid_kernargs K = (pt_grid_kernargs)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(K));
+    PTLightGridDevice g;
+    for (uint32_t a = 0; a < 3u; ++a) { g.g.origin[a] = K->G.g.origin[a]; g.g.dims[a] = K->G.g.dims[a]; }
+    g.g.cellSize = K->G.g.cellSize;
+    g.offsets = K->G.offsets;
+    g.indices = K->G.indices;
+    g.rectBefore = K->G.rectBefore;
+    return g;
+}
+PT_DEV void grid_lists(const uint32_t*& indices, const uint32_t*& rectBefore)
+{
+    pt_grid_kernargs K = (pt_grid_kernargs)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(K));
+    indices = K->G.indices;
+    rectBefore = K->G.rectBefore;
+}
+
+// ... and whether the chunk's end adds to the output (kAddBit): held across the pair loop, the flag spills in the HAS_TLAS kernel
+PT_DEV bool add_to_output()
+{
+    pt_light_kernargs K = (pt_light_kernargs)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(K));
+    return (K->P.flags & kAddBit) != 0u;
+}
+
+// word `index` of p through a scalar load; p + index must be the same address in every lane of the wave
+PT_DEV uint32_t uniform_word(const uint32_t* p, size_t index)
+{
+    const __attribute__((address_space(4))) uint32_t* q = (const __attribute__((address_space(4))) uint32_t*)(uintptr_t)p;
+    return q[index];
+}
+
+// the smallest v of the wave's 64 lanes, in a scalar register; every lane is active where this is called
+PT_DEV uint32_t wave_min(uint32_t v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)v, m, 64);
+        v = o < v ? o : v;
+    }
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+
+// The next light of the union of the lanes' lists: the wave-wide minimum of the heads (kNoLight: every list is used up).  The
+// lanes whose head it is advance their cursor.  Without `centred` every lane makes the draws PTDirectLight makes for the rectangle
+// lights jumped over, drawn ... l - 1: two per pair, S * S pairs each -- integer-only, the trip count is the wave's
+PT_DEV uint32_t next_light(uint32_t& head, uint32_t& cur, uint32_t end, uint32_t& s, uint32_t& drawn, bool centred, uint32_t strata)
+{
+    const uint32_t l = wave_min(head);
+    if (l == ptlgrid::kNoLight) return l;
+    const uint32_t *indices, *rectBefore;
+    grid_lists(indices, rectBefore);
+    if (head == l) {
+        ++cur;
+        head = cur < end ? indices[cur] : ptlgrid::kNoLight;
+    }
+    if (!centred) {
+        const uint32_t* rb = (const uint32_t*)__builtin_assume_aligned(rectBefore, 4);
+        const uint32_t skipped = uniform_word(rb, l) - uniform_word(rb, (uint32_t)__builtin_amdgcn_readfirstlane((int)drawn));
+        for (uint32_t n = 2u * strata * strata * skipped; n != 0u; --n) pt_rng_next(&s);
+    }
+    drawn = l + 1u;
+    asm volatile("" : "+v"(drawn));                                     // held in a vector register across the walk: the scalar file is full there
+    return l;
+}
+
+template <bool TLAS>
+PT_DEV void direct_light_grid_body(const LightArgs& A)
+{
+    const DScene& S = A.S;                                              // the walks' fields: live throughout
+    const DirectArgs& P = A.P;
+    const uint32_t count = A.count;
+    __shared__ uint2 s_stack[PT_Q_LDS_STACK][64];
+    __shared__ uint32_t s_tstack[TLAS ? PT_BVH_STACK_SIZE : 1][64];
+    __shared__ uint32_t s_gw;
+    const uint32_t lane = threadIdx.x;
+    if (lane == 0u) s_gw = blockIdx.x;                                  // slab row = wave * 64 + lane (grid <= slab waves)
+    __builtin_amdgcn_wave_barrier();
+
+    Counters cn = {};
+    TravStackT<PT_Q_LDS_STACK, true> st;
+    st.lds = PT_LDS_U2(&s_stack[0][lane]);
+    st.stride = 64u;
+    st.gbase = A.slab;
+    st.gwave = PT_LDS_WORD(s_gw);
+
+    const bool centred = (P.flags & PT_DIRECT_CENTERED) != 0u;
+    for (uint32_t base = blockIdx.x * 64u; base < count; base += gridDim.x * 64u) {     // base is wave-uniform: no lane leaves early
+        const uint32_t i = base + lane;
+        const bool active = i < count;
+        bool hit = false;
+        ptdirect::Entry e = {};
+        uint32_t s;
+        uint32_t cur = 0u, end = 0u;                                    // the lane's cursor into its cell's list; a miss holds an empty one
+        {
+            const FrontArgs f = front_args();
+            DScene Sf = {};                                             // the scene as the material fetch reads it
+            Sf.materials = f.materials; Sf.tex = f.tex; Sf.attrs = f.attrs;
+            Sf.materialCount = f.materialCount; Sf.hasTextures = f.hasTextures;
+            if (active) {
+                HitRecords h;
+                hit_records(Sf, f.rays, f.hits, f.surfaces, i, nullptr, nullptr, 0u, h);
+                hit = !ptshade::is_miss(h.T);
+                if (hit) {
+                    const float4 r0 = ((const float4*)f.rays)[(size_t)i * 2], r1 = ((const float4*)f.rays)[(size_t)i * 2 + 1];
+                    const float D[3] = {r0.w, r1.x, r1.y};
+                    ptdirect::entry_begin(h.T, D, h.P, h.N, f.minAlpha, e);
+                }
+            }
+            s = ptdirect::entry_state(f.seed, (uint64_t)f.first + i);
+        }
+        float d0 = 0.0f, d1 = 0.0f, d2 = 0.0f;
+        const v3 o = mk3(e.O[0], e.O[1], e.O[2]);
+        uint32_t head = ptlgrid::kNoLight;                              // the light at the lane's cursor
+        if (hit) {                                                      // the front's arguments are dead: the grid's fit the scalar file now
+            const PTLightGridDevice G = grid_args();
+            const uint32_t cell = ptlgrid::cell_of(G.g, e.O);
+            cur = G.offsets[cell];
+            end = G.offsets[cell + 1u];
+            if (cur < end) head = G.indices[cur];
+        }
+        // One loop over the pairs (l, k), both wave-uniform, as direct_light_body's; l steps through the union of the lanes' lists
+        // (next_light).  drawn: the lights below it have had their draws
+        uint32_t drawn = 0u;
+        for (uint32_t l = next_light(head, cur, end, s, drawn, centred, P.strata), k = 0; l != ptlgrid::kNoLight;) {
+            DScene Sl = {};
+            light_arrays(Sl.lights, Sl.lightConst);
+            const ptdirect::Light Lt = uniform_light(Sl, l);
+            if (k >= ptdirect::pairs_of(Lt.type, P.strata)) {
+                l = next_light(head, cur, end, s, drawn, centred, P.strata);
+                k = 0;
+                continue;
+            }
+            float x1 = 0.5f, x2 = 0.5f;
+            if (!centred && Lt.type == PT_LIGHT_TYPE_RECTANGLE) {
+                x1 = pt_random_float(&s);
+                x2 = pt_random_float(&s);
+            }
+            float dir[3], c[3];
+            const bool counts = hit && ptdirect::pair_eval(e, Lt, P.strata, k, x1, x2, dir, c);
+            ++k;
+            if (!__any(counts)) continue;                               // no lane's pair counts: no walk
+            if (counts) {
+                HitRecord rec;
+                rec.h.t = PT_FAR_PLANE; rec.h.u = 0.0f; rec.h.v = 0.0f; rec.h.triIndex = 0xFFFFFFFFu;
+                rec.pos = mk3(0.0f); rec.inst = 0xFFFFFFFFu;
+                const v3 d = mk3(dir[0], dir[1], dir[2]);
+                if (TLAS) anyhit_tlas(S, o, d, rec, st, (pt_lds_u32)&s_tstack[0][lane]);
+                else traverse_cwbvh<false>(S, o, d, true, rec.h, st, cn, PT_FAR_PLANE);
+                if (rec.h.triIndex == 0xFFFFFFFFu) { d0 = d0 + c[0]; d1 = d1 + c[1]; d2 = d2 + c[2]; }
+            }
+        }
+        if (active) {
+            float4* out = output_array();
+            if (add_to_output()) {
+                if (hit) {
+                    const float4 v = out[i];
+                    out[i] = make_float4(v.x + d0, v.y + d1, v.z + d2, v.w);
+                }
+            } else {
+                out[i] = hit ? make_float4(d0, d1, d2, 1.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            }
+        }
+    }
+}
+
 } // namespace
 
 // Stable, unmangled kernel names (rocprofv3 --kernel-trace lists them as they are written here).
 extern "C" __global__ __launch_bounds__(64) void pt_direct_light(LightArgs A) { direct_light_body<false>(A); }
 extern "C" __global__ __launch_bounds__(64) void pt_direct_light_tlas(LightArgs A) { direct_light_body<true>(A); }
+extern "C" __global__ __launch_bounds__(64) void pt_direct_light_grid(GridLightArgs A) { direct_light_grid_body<false>(A.A); }
+extern "C" __global__ __launch_bounds__(64) void pt_direct_light_grid_tlas(GridLightArgs A) { direct_light_grid_body<true>(A.A); }
 
 size_t pt_direct_slab_bytes_per_wave() { return (size_t)64 * PT_D_SLAB_ENTRIES * sizeof(uint2); }
 
-hipError_t pt_direct_grid_caps(int device, uint32_t caps[2])
+namespace {
+
+hipError_t grid_caps_of(int device, const void* const kernels[2], uint32_t caps[2])
 {
     hipDeviceProp_t prop;
     hipError_t e = hipGetDeviceProperties(&prop, device);
     if (e != hipSuccess) return e;
-    const void* kernels[2] = {reinterpret_cast<const void*>(pt_direct_light), reinterpret_cast<const void*>(pt_direct_light_tlas)};
     for (int k = 0; k < 2; ++k) {
         int blocks = 0;
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernels[k], 64, 0);
@@ -325,6 +511,20 @@ hipError_t pt_direct_grid_caps(int device, uint32_t caps[2])
         caps[k] = (uint32_t)(blocks > 0 ? blocks : 1) * (uint32_t)prop.multiProcessorCount;
     }
     return hipSuccess;
+}
+
+} // namespace
+
+hipError_t pt_direct_grid_caps(int device, uint32_t caps[2])
+{
+    const void* kernels[2] = {reinterpret_cast<const void*>(pt_direct_light), reinterpret_cast<const void*>(pt_direct_light_tlas)};
+    return grid_caps_of(device, kernels, caps);
+}
+
+hipError_t pt_direct_culled_grid_caps(int device, uint32_t caps[2])
+{
+    const void* kernels[2] = {reinterpret_cast<const void*>(pt_direct_light_grid), reinterpret_cast<const void*>(pt_direct_light_grid_tlas)};
+    return grid_caps_of(device, kernels, caps);
 }
 
 hipError_t pt_launch_direct_rays(const DScene& S, const PTDirectParams& P, uint32_t pairsPerEntry, const PTRay* rays, const PTShadeTerms* terms,
@@ -347,7 +547,8 @@ hipError_t pt_launch_direct_accumulate(const PTShadeTerms* terms, const float4* 
 }
 
 hipError_t pt_launch_direct_light(const DScene& S, const PTDirectParams& P, const PTRay* rays, const PTRayHit* hits, const PTRaySurface* surfaces,
-                                  uint32_t count, uint32_t first, float4* out, bool add, uint2* slab, uint32_t gridCap, hipStream_t stream)
+                                  uint32_t count, uint32_t first, float4* out, bool add, uint2* slab, uint32_t gridCap, hipStream_t stream,
+                                  const PTLightGridDevice* lightGrid)
 {
     if (count == 0u) return hipSuccess;
     if (!ptdirect::strata_ok(P.strata) || !slab || gridCap == 0u) return hipErrorInvalidValue;
@@ -357,6 +558,13 @@ hipError_t pt_launch_direct_light(const DScene& S, const PTDirectParams& P, cons
     const uint32_t chunks = (count + 63u) / 64u;
     const uint32_t grid = chunks < gridCap ? chunks : gridCap;
     const LightArgs A = {S, {P.strata, P.seed, P.flags | (add ? kAddBit : 0u), P.minAlpha}, rays, hits, surfaces, out, slab, count, first};
+    if (lightGrid) {
+        if (!lightGrid->offsets || !lightGrid->indices || !lightGrid->rectBefore) return hipErrorInvalidValue;
+        const GridLightArgs GA = {A, *lightGrid};
+        if (S.hasTlas) hipLaunchKernelGGL(pt_direct_light_grid_tlas, dim3(grid), dim3(64), 0, stream, GA);
+        else hipLaunchKernelGGL(pt_direct_light_grid, dim3(grid), dim3(64), 0, stream, GA);
+        return hipGetLastError();
+    }
     if (S.hasTlas) hipLaunchKernelGGL(pt_direct_light_tlas, dim3(grid), dim3(64), 0, stream, A);
     else hipLaunchKernelGGL(pt_direct_light, dim3(grid), dim3(64), 0, stream, A);
     return hipGetLastError();

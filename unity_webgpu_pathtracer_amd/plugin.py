@@ -201,6 +201,14 @@ sig = {
     "PTDirectPairCountHost": (i32, [vp, C.c_uint32, C.c_uint32, u32p]),
     "PTDirectRaysHost": (i32, [C.POINTER(abi.PTDirectParams), vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, vp]),
     "PTDirectAccumulateHost": (i32, [vp, vp, vp, C.c_uint64, C.c_uint32, vp]),
+    # Part 25 (direct light over many lights: the light grid)
+    "PTBuildLightGrid": (i32, [vp, C.POINTER(abi.PTLightGridParams)]),
+    "PTReadLightGrid": (i32, [vp, vp, vp, C.c_uint64, vp]),
+    "PTLightGridInfo": (i32, [vp, C.POINTER(abi.PTLightGridStats)]),
+    "PTDirectLightCulled": (i32, [vp, C.POINTER(abi.PTDirectParams), vp, vp, vp, C.c_uint64, vp]),
+    "PTShadeMixedCulled": (i32, [vp, C.POINTER(abi.PTShadeInputs), C.POINTER(abi.PTDirectParams), vp, vp, vp, C.c_uint64, vp]),
+    "PTShadeMixedFrameCulled": (i32, [vp, C.POINTER(abi.PTFrameParams), C.POINTER(abi.PTShadeInputs), C.POINTER(abi.PTDirectParams), vp, vp]),
+    "PTBuildLightGridHost": (i32, [C.POINTER(abi.PTLightGridParams), vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]),
     "PTGetLastError": (C.c_char_p, []), "PTGetVersion": (i32, []),
 }
 EXPORTED_SYMBOLS = list(sig)
@@ -1072,6 +1080,29 @@ def direct_accumulate(terms, contrib, pair_hits, pairs_per_entry: int) -> np.nda
     if not lib.PTDirectAccumulateHost(t.ctypes.data, c.ctypes.data, h.ctypes.data, n, int(pairs_per_entry), out.ctypes.data):
         raise PluginError(abi.PT_ERR_INVALID_ARG, "PTDirectAccumulateHost failed: " + lib.PTGetBVHBuildError().decode())
     return out
+
+
+# ---- the light grid on the host (include/ptmi_plugin.h Part 25)
+def build_light_grid(lights, origin=None, cell_size=None, dims=None, params=None):
+    """PTBuildLightGridHost: the grid PathTracer.build_light_grid builds on the GPU, byte for byte.  lights: (k, 16) float32 PTLight
+    records; the grid is dims[0] x dims[1] x dims[2] cubes of cell_size from origin (or a ready PTLightGridParams).  Returns
+    (offsets (cells + 2,), indices (total,), rect_before (k + 1,)), uint32: the list of cell c is indices[offsets[c]:offsets[c + 1]],
+    the overflow cell's -- every light -- comes last."""
+    L = _light_rows(lights)
+    p = params if params is not None else abi.light_grid_params(origin, cell_size, dims)
+    lib = load_library()
+    lights_ptr = L.ctypes.data if L.shape[0] else None
+    cells = int(p.dims[0]) * int(p.dims[1]) * int(p.dims[2])
+    ok = 0 < cells <= abi.PT_LIGHT_GRID_MAX_CELLS                       # else the call below refuses, with nothing written
+    offsets, rect_before = np.zeros((cells if ok else 0) + 2, np.uint32), np.zeros(L.shape[0] + 1, np.uint32)
+    total = C.c_uint64()
+    if not lib.PTBuildLightGridHost(C.byref(p), lights_ptr, L.shape[0], offsets.ctypes.data, None, 0, rect_before.ctypes.data, C.byref(total)):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTBuildLightGridHost failed: " + lib.PTGetBVHBuildError().decode())
+    indices = np.zeros(total.value, np.uint32)
+    if not lib.PTBuildLightGridHost(C.byref(p), lights_ptr, L.shape[0], offsets.ctypes.data, indices.ctypes.data if total.value else None, total.value,
+                                    rect_before.ctypes.data, None):
+        raise PluginError(abi.PT_ERR_INVALID_ARG, "PTBuildLightGridHost failed: " + lib.PTGetBVHBuildError().decode())
+    return offsets, indices, rect_before
 
 
 def build_tlas(instances: np.ndarray):
