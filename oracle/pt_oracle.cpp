@@ -1626,6 +1626,9 @@ float oracle_env_probe(const PTSceneDesc* scene, const PTFrameParams* params, in
             f4 r = SampleEnvMap(c, col, rng);
             float* o = out + 8 * k;
             o[0] = r.x; o[1] = r.y; o[2] = r.z; o[3] = r.w; o[4] = col.x; o[5] = col.y; o[6] = col.z; o[7] = 0.0f;
+        } else if (what == 4) {
+            f3 col = EnvSampleLevel(S, f2{in[2 * k], in[2 * k + 1]});
+            out[3 * k] = col.x; out[3 * k + 1] = col.y; out[3 * k + 2] = col.z;
         }
     }
     return S.EnvironmentCdfSum;

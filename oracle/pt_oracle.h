@@ -96,6 +96,7 @@ void     oracle_sample_brdf_batch(const float* material, const float* V, const f
  *   what 1: BinarySearch(in[k])                                         -> out[2k..2k+1]     (uv)
  *   what 2: EvalEnvMap(in[3k..3k+2], intensity 1)                       -> out[4k..4k+3]     (rgb, pdf)
  *   what 3: SampleEnvMap with rngState = (uint)in[k] bits               -> out[8k..8k+7]     (dir xyz, pdf, colour rgb, 0)
+ *   what 4: EnvironmentTexture.SampleLevel(uv = in[2k..2k+1], 0)        -> out[3k..3k+2]     (rgb)
  * Returns EnvironmentCdfSum. */
 float    oracle_env_probe(const PTSceneDesc* scene, const PTFrameParams* params, int what, const float* in, uint64_t n, float* out);
 

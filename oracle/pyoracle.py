@@ -347,11 +347,11 @@ def trace_rays(buffers: SceneBuffers, rays: np.ndarray):
 
 
 def env_probe(buffers: SceneBuffers, params, what: int, values: np.ndarray):
-    """oracle_env_probe: what 0 CDF[i], 1 BinarySearch(value), 2 EvalEnvMap(dir), 3 SampleEnvMap(rng state bits).
-    Returns (array, EnvironmentCdfSum)."""
+    """oracle_env_probe: what 0 CDF[i], 1 BinarySearch(value), 2 EvalEnvMap(dir), 3 SampleEnvMap(rng state bits),
+    4 EnvironmentTexture.SampleLevel(uv).  Returns (array, EnvironmentCdfSum)."""
     lib = load_oracle()
-    per_in = {0: 1, 1: 1, 2: 3, 3: 1}[what]
-    per_out = {0: 1, 1: 2, 2: 4, 3: 8}[what]
+    per_in = {0: 1, 1: 1, 2: 3, 3: 1, 4: 2}[what]
+    per_out = {0: 1, 1: 2, 2: 4, 3: 8, 4: 3}[what]
     if what == 3:
         vin = np.ascontiguousarray(values, dtype=np.uint32).view(np.float32)
     else:

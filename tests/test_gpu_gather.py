@@ -26,7 +26,7 @@ def _bits(a):
 # ---------------------------------------------------------------------------------------------------------------------------
 # scenes
 # ---------------------------------------------------------------------------------------------------------------------------
-def _box(emission=(0.0, 0.0, 0.0), lights=(), occluder=None, ceiling=True):
+def _box(emission=(0.0, 0.0, 0.0), lights=(), occluder=None, ceiling=True, sky="basic"):
     """A CLOSED Cornell shell (scenes._cornell_shell plus ceiling and front wall), every material of roughness 1.  emission: a
     1.2 x 1.2 ceiling patch with an emissive MATERIAL (no analytic light).  Basic sky of intensity 0: no environment NEE, and
     nothing to see anyway (an escaping ray adds exactly 0).  ceiling=False leaves the ceiling and its patch off: the render's
@@ -43,9 +43,18 @@ def _box(emission=(0.0, 0.0, 0.0), lights=(), occluder=None, ceiling=True):
         sb.quad(*occluder, 1, 1, 0)
     verts, attrs = sb.finish()
     L = np.stack(lights).astype(F) if len(lights) else np.zeros((0, 16), dtype=F)
-    return scenes.Scene("gather_box", verts, attrs, np.stack(mats), L, np.zeros(0, dtype=np.uint32),
-                        scenes.Camera(eye=(0.0, 1.0, -0.9), target=(0.0, 1.0, 0.0), vfov_deg=40.0),
-                        environment_mode=1, environment_color=(0.0, 0.0, 0.0, 1.0), environment_intensity=0.0)
+    s = scenes.Scene("gather_box", verts, attrs, np.stack(mats), L, np.zeros(0, dtype=np.uint32),
+                     scenes.Camera(eye=(0.0, 1.0, -0.9), target=(0.0, 1.0, 0.0), vfov_deg=40.0),
+                     environment_mode=1, environment_color=(0.0, 0.0, 0.0, 1.0), environment_intensity=0.0)
+    if sky == "black map":
+        # mode 0 with an all-black 8 x 4 map at intensity 1: as dark as the basic sky of intensity 0, but every surface hit now draws
+        # and traces an environment shadow ray, which adds nothing (envCdfSum == 0: its pdf is 0 / 0, valid == 2)
+        texels = np.zeros((4, 8, 4), dtype=F)
+        texels[..., 3] = 1.0
+        s.environment_mode, s.environment_intensity, s.environment_texture = 0, 1.0, texels
+    else:
+        assert sky == "basic"
+    return s
 
 
 def _box_receivers(n, seed=3):
@@ -134,8 +143,14 @@ _LIGHTS = {
 }
 
 
-@pytest.mark.parametrize("kind", ["point", "spot"])
-def test_direct_light_closed_form(kind):
+# the sky: the box's own basic sky of intensity 0, and an all-black environment map -- an extra draw and an extra traced ray per
+# receiver that add nothing; every sample of a point or spot light has the same value, so the shifted draws cannot move the result
+_SKIES = [pytest.param("point", "basic", id="point"), pytest.param("spot", "basic", id="spot"),
+          pytest.param("point", "black map", id="point-black-map"), pytest.param("spot", "black map", id="spot-black-map")]
+
+
+@pytest.mark.parametrize("kind,sky", _SKIES)
+def test_direct_light_closed_form(kind, sky):
     light = _LIGHTS[kind]
     lp = np.asarray(_LIGHT_POS, dtype=np.float64)
     pos = np.array([(-0.3, 0.6, -0.2), (0.5, 0.5, -0.3), (0.4, 0.7, 0.3), (0.6, 0.4, 0.5)], dtype=np.float64)
@@ -150,13 +165,13 @@ def test_direct_light_closed_form(kind):
     pos, nrm = pos.astype(F), nrm.astype(F)
     samples, seeds = 8, np.arange(4, dtype=np.uint32) + 11
     # Under the ceiling every shadow ray ends on it behind the light, exactly as in a render of that box: E is 0 everywhere.
-    pt = _tracer(_box(lights=[light], occluder=occluder), 1, bounces=1)
+    pt = _tracer(_box(lights=[light], occluder=occluder, sky=sky), 1, bounces=1)
     try:
         assert (pt.irradiance(pos, nrm, spp=samples, seeds=seeds, params=_with_bounces(pt, 1)) == 0).all()
     finally:
         pt.close()
     # The dark box with its top open (all four lines to the light leave through it): the closed form.
-    pt = _tracer(_box(lights=[light], occluder=occluder, ceiling=False), 1, bounces=1)
+    pt = _tracer(_box(lights=[light], occluder=occluder, ceiling=False, sky=sky), 1, bounces=1)
     try:
         out = pt.irradiance(pos, nrm, spp=samples, seeds=seeds, params=_with_bounces(pt, 1))
         want = np.stack([gather_ref.direct_irradiance(light, pos[i], nrm[i]) for i in range(4)])

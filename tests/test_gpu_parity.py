@@ -768,7 +768,8 @@ def test_analytic_scenes_bit_exact(oracle, schedule):
 
 def _fuzz_scene(seed):
     """A random small scene: every material parameter drawn over its whole range (extremes included), random lights of all three
-    types, random textures in random slots, random camera with or without a lens, one of the three sky settings."""
+    types, random textures in random slots, random camera with or without a lens, one of two sky settings: mode 0 with a constant colour (no map) or mode 1, the basic sky
+    (tests/test_gpu_env.py redraws the sky over environment maps and mode 2)."""
     rng = np.random.RandomState(seed)
     pick = lambda lo, hi: float(rng.choice([lo, hi, rng.uniform(lo, hi), rng.uniform(lo, hi)]))
     n_tex = int(rng.randint(0, 4))

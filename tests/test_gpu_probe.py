@@ -27,7 +27,7 @@ def _bits(a):
 # ---------------------------------------------------------------------------------------------------------------------------
 # scenes
 # ---------------------------------------------------------------------------------------------------------------------------
-def _box(emission=(0.0, 0.0, 0.0), lights=(), occluder=None, ceiling=True):
+def _box(emission=(0.0, 0.0, 0.0), lights=(), occluder=None, ceiling=True, sky="basic"):
     """tests/test_gpu_gather.py's box: a CLOSED Cornell shell, every material of roughness 1.  emission: a 1.2 x 1.2 ceiling patch
     with an emissive MATERIAL (no analytic light).  Basic sky of intensity 0.  ceiling=False leaves the ceiling and its patch off:
     the render's shadow rays have no far end, so a light that geometry encloses lights nothing."""
@@ -42,9 +42,18 @@ def _box(emission=(0.0, 0.0, 0.0), lights=(), occluder=None, ceiling=True):
         sb.quad(*occluder, 1, 1, 0)
     verts, attrs = sb.finish()
     L = np.stack(lights).astype(F) if len(lights) else np.zeros((0, 16), dtype=F)
-    return scenes.Scene("probe_box", verts, attrs, np.stack(mats), L, np.zeros(0, dtype=np.uint32),
-                        scenes.Camera(eye=(0.0, 1.0, -0.9), target=(0.0, 1.0, 0.0), vfov_deg=40.0),
-                        environment_mode=1, environment_color=(0.0, 0.0, 0.0, 1.0), environment_intensity=0.0)
+    s = scenes.Scene("probe_box", verts, attrs, np.stack(mats), L, np.zeros(0, dtype=np.uint32),
+                     scenes.Camera(eye=(0.0, 1.0, -0.9), target=(0.0, 1.0, 0.0), vfov_deg=40.0),
+                     environment_mode=1, environment_color=(0.0, 0.0, 0.0, 1.0), environment_intensity=0.0)
+    if sky == "black map":
+        # mode 0 with an all-black 8 x 4 map at intensity 1: as dark as the basic sky of intensity 0, but every surface hit now draws
+        # and traces an environment shadow ray, which adds nothing (envCdfSum == 0: its pdf is 0 / 0, valid == 2)
+        texels = np.zeros((4, 8, 4), dtype=F)
+        texels[..., 3] = 1.0
+        s.environment_mode, s.environment_intensity, s.environment_texture = 0, 1.0, texels
+    else:
+        assert sky == "basic"
+    return s
 
 
 _EMISSION = (6.0, 5.0, 3.0)
@@ -136,8 +145,14 @@ def _direct(light, P, w):
     return probe_ref.direct_irradiance(light, np.asarray(P, F) - np.asarray(w, F) * F(1.0e-4), w)
 
 
-@pytest.mark.parametrize("kind", ["point", "spot"])
-def test_delta_light_closed_form(kind):
+# the sky: the box's own basic sky of intensity 0, and an all-black environment map -- the walls a probe sees now draw and trace an
+# environment shadow ray that adds nothing; the delta term is the difference of two results with the same paths, so it cannot move
+_SKIES = [pytest.param("point", "basic", id="point"), pytest.param("spot", "basic", id="spot"),
+          pytest.param("point", "black map", id="point-black-map"), pytest.param("spot", "black map", id="spot-black-map")]
+
+
+@pytest.mark.parametrize("kind,sky", _SKIES)
+def test_delta_light_closed_form(kind, sky):
     light = _LIGHTS[kind]
     lp = np.asarray(_LIGHT_POS, dtype=np.float64)
     # probes 0, 1: in the open; 2: behind the occluder; 3: beside the light, behind the spot's cone.  All four lie below the light, so
@@ -152,7 +167,7 @@ def test_delta_light_closed_form(kind):
     pos32, samples, seeds = pos.astype(F), 70, np.arange(4, dtype=np.uint32) + 11
     # The dark box with its top open.  Without the flag a probe still sees the walls the light shines on (their own NEE), so the
     # difference of the two results carries one rounding of the sum: half an ulp of a coefficient of order 1, a hundredth of 1e-5
-    pt = _tracer(_box(lights=[light], occluder=occluder, ceiling=False), 1, bounces=2)
+    pt = _tracer(_box(lights=[light], occluder=occluder, ceiling=False, sky=sky), 1, bounces=2)
     try:
         p = _with_bounces(pt, 2)
         off, m2_off = pt.probe_sh(pos32, spp=samples, seeds=seeds, delta_lights=False, params=p)
@@ -184,7 +199,7 @@ def test_delta_light_closed_form(kind):
     finally:
         pt.close()
     # under the ceiling every shadow ray ends on it behind the light, exactly as in a render of that box: the bits stay
-    pt = _tracer(_box(emission=_EMISSION, lights=[light], occluder=occluder), 1, bounces=2)
+    pt = _tracer(_box(emission=_EMISSION, lights=[light], occluder=occluder, sky=sky), 1, bounces=2)
     try:
         p = _with_bounces(pt, 2)
         off, m2_off = pt.probe_sh(pos32, spp=samples, seeds=seeds, delta_lights=False, params=p)

@@ -4,6 +4,7 @@
 // (PathTracer.cs:226-252) and the ping-pong frame bookkeeping (PathTracer.cs:246-247, 268-272).
 // There is NO CPU fallback: without a HIP device PTCreate fails with PT_ERR_NO_DEVICE.
 #include "pt_context.h"
+#include "pt_env_cdf.h"
 
 #include <dlfcn.h>
 
@@ -353,11 +354,7 @@ int set_scene(PTContext* c, const PTSceneDesc* hostScene, bool validate)
         // OnEnvTexReadback (PathTracer.cs:297-306): running fp32 sum of Color.grayscale = 0.299 r + 0.587 g + 0.114 b
         const size_t n = (size_t)s->envWidth * s->envHeight;
         cdf.resize(n);
-        for (size_t i = 0; i < n; ++i) {
-            const float* px = s->envTexture + 4 * i;
-            cdfSum += 0.299f * px[0] + 0.587f * px[1] + 0.114f * px[2];
-            cdf[i] = cdfSum;
-        }
+        cdfSum = pt_env_build_cdf(s->envTexture, n, cdf.data());
         if ((rc = upload(c, c->envTex, s->envTexture, n * 16))) return rc;
         if ((rc = upload(c, c->envCdf, cdf.data(), n * 4))) return rc;
     }
