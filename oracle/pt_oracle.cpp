@@ -1634,6 +1634,111 @@ float oracle_env_probe(const PTSceneDesc* scene, const PTFrameParams* params, in
     return S.EnvironmentCdfSum;
 }
 
+namespace {
+inline void StoreMaterial(float* o, const Material& m)
+{
+    o[0] = m.baseColor.x; o[1] = m.baseColor.y; o[2] = m.baseColor.z; o[3] = m.opacity;
+    o[4] = m.emission.x; o[5] = m.emission.y; o[6] = m.emission.z; o[7] = m.alphaMode;
+    o[8] = m.alphaCutoff; o[9] = m.anisotropic; o[10] = m.metallic; o[11] = m.roughness;
+    o[12] = m.subsurface; o[13] = m.specularTint; o[14] = m.sheen; o[15] = m.sheenTint;
+    o[16] = m.clearcoat; o[17] = m.clearcoatRoughness; o[18] = m.specTrans; o[19] = m.ior;
+    o[20] = m.ax; o[21] = m.ay; o[22] = m.eta; o[23] = m.occlusion;
+}
+const size_t kBsdfProbeIn[6] = {9, 3, 8, 10, 14, 11}, kBsdfProbeOut[6] = {51, 20, 9, 15, 4, 8};
+} // namespace
+
+int oracle_bsdf_probe(const PTSceneDesc* scene, int what, const float* in, uint64_t n, float* out)
+{
+    if (!scene || what < 0 || what > 5 || !in || !out) return -1;
+    SceneView S = MakeView(scene);
+    PTFrameParams P;
+    memset(&P, 0, sizeof(P));
+    Ctx c;
+    c.S = &S; c.P = &P; memset(&c.st, 0, sizeof(PTStats)); c.shadowAnyHit = false; c.nanRayEarlyOut = false; c.opt = nullptr;
+    for (uint64_t k = 0; k < n; k++) {
+        const float* a = in + kBsdfProbeIn[what] * k;
+        float* o = out + kBsdfProbeOut[what] * k;
+        if (what == 0) {
+            if (!(a[0] >= 0.0f && a[0] < (float)S.materialCount)) return -1;
+            Ray ray = {V3(0.0f), V3(a[3], a[4], a[5])};
+            RayHit hit;
+            memset(&hit, 0, sizeof(hit));
+            hit.uv = {a[1], a[2]};
+            hit.normal = V3(a[6], a[7], a[8]);
+            memset(&c.st, 0, sizeof(PTStats));
+            c.st.materialFetches++;                                                    // as PathTrace counts it
+            Material m = GetMaterial(c, S.materials[(size_t)a[0]], ray, hit);
+            StoreMaterial(o, m);
+            StoreMaterial(o + 24, m);                                                  // the kernel's two forms are one function here
+            o[48] = (float)c.st.materialFetches; o[49] = (float)c.st.texDescriptorFetches; o[50] = (float)c.st.texelFetches;
+        } else if (what == 1) {
+            if (!S.hasTextures || !(a[0] >= 0.0f && a[0] < (float)(S.tex[2] / 4u))) return -1;     // the first texel follows the descriptors
+            f4 r = SampleTexture(c, (int32_t)a[0], f2{a[1], a[2]}, true);
+            for (int q = 0; q < 5; q++) { o[4 * q] = r.x; o[4 * q + 1] = r.y; o[4 * q + 2] = r.z; o[4 * q + 3] = r.w; }
+        } else if (what == 2) {
+            for (int q = 0; q < 9; q++) o[q] = 0.0f;
+            const float a0 = a[1], a1 = a[2], a2 = a[3], a3 = a[4], a4 = a[5], a5 = a[6], a6 = a[7];
+            f3 t = V3(0.0f);
+            switch ((int)a[0]) {
+            case 0: o[0] = GTR1(a0, a1); break;
+            case 1: t = SampleGTR1(a0, a1, a2); o[0] = t.x; o[1] = t.y; o[2] = t.z; break;
+            case 2: t = SampleGGXVNDF(V3(a0, a1, a2), a3, a4, a5, a6); o[0] = t.x; o[1] = t.y; o[2] = t.z; break;
+            case 3: o[0] = GTR2Aniso(a0, a1, a2, a3, a4); break;
+            case 4: o[0] = SmithG(a0, a1); break;
+            case 5: o[0] = SmithGAniso(a0, a1, a2, a3, a4); break;
+            case 6: o[0] = SchlickWeight(a0); break;
+            case 7: o[0] = DielectricFresnel(a0, a1); break;
+            case 8: t = CosineSampleHemisphere(a0, a1); o[0] = t.x; o[1] = t.y; o[2] = t.z; break;
+            case 9: o[0] = PowerHeuristic(a0, a1); break;
+            case 10: t = reflect(V3(a0, a1, a2), V3(a3, a4, a5)); o[0] = t.x; o[1] = t.y; o[2] = t.z; break;
+            case 11: t = refract(V3(a0, a1, a2), V3(a3, a4, a5), a6); o[0] = t.x; o[1] = t.y; o[2] = t.z; break;
+            case 12: {
+                Mat3 b = GetONB(V3(a0, a1, a2));
+                o[0] = b.r0.x; o[1] = b.r0.y; o[2] = b.r0.z; o[3] = b.r1.x; o[4] = b.r1.y; o[5] = b.r1.z; o[6] = b.r2.x; o[7] = b.r2.y; o[8] = b.r2.z;
+                break;
+            }
+            case 13: o[0] = Luminance(V3(a0, a1, a2)); break;
+            default: break;
+            }
+        } else {
+            if (!(a[0] >= 0.0f && a[0] < (float)S.materialCount)) return -1;
+            const f3 V = V3(a[3], a[4], a[5]);
+            Ray ray = {V3(0.0f), -V};
+            RayHit hit;
+            memset(&hit, 0, sizeof(hit));
+            hit.uv = {a[1], a[2]};
+            hit.normal = V3(a[6], a[7], a[8]);
+            hit.ffnormal = dot(hit.normal, ray.direction) <= 0.0f ? hit.normal : -hit.normal;      // util/bvh.hlsl:209
+            Material material = GetMaterial(c, S.materials[(size_t)a[0]], ray, hit);
+            float maxRoughness = a[9];                                                 // PathTrace
+            maxRoughness = pt_max(maxRoughness, material.roughness);
+            material.roughness = maxRoughness;
+            if (what == 3) {
+                Mat3 onb = GetONB(hit.ffnormal);
+                f3 Vl = ToLocal(onb, -ray.direction);
+                f3 Csheen, Cspec0;
+                float F0;
+                TintColors(material, material.eta, F0, Csheen, Cspec0);
+                LobeWeights w = ComputeLobes(material, Cspec0, Vl.z);
+                o[0] = F0; o[1] = Csheen.x; o[2] = Csheen.y; o[3] = Csheen.z; o[4] = Cspec0.x; o[5] = Cspec0.y; o[6] = Cspec0.z;
+                o[7] = w.dielectricWt; o[8] = w.metalWt; o[9] = w.glassWt; o[10] = w.diffPr; o[11] = w.dielectricPr; o[12] = w.metalPr;
+                o[13] = w.glassPr; o[14] = w.clearCtPr;
+            } else if (what == 4) {
+                float pdf = 0.0f;
+                f3 f = EvalBRDF(material, -ray.direction, a[13] == 0.0f ? hit.ffnormal : hit.normal, V3(a[10], a[11], a[12]), pdf);   // DirectLight / EvalLight
+                o[0] = f.x; o[1] = f.y; o[2] = f.z; o[3] = pdf;
+            } else {
+                uint32_t rng = pt_asuint(a[10]);
+                f3 L = V3(0.0f);
+                float pdf = 0.0f;
+                f3 f = SampleBRDF(material, -ray.direction, hit.ffnormal, L, pdf, rng);
+                o[0] = L.x; o[1] = L.y; o[2] = L.z; o[3] = f.x; o[4] = f.y; o[5] = f.z; o[6] = pdf; o[7] = pt_asfloat(rng);
+            }
+        }
+    }
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------
 // MeshProcessing.compute / CopyTextureData.compute
 // ------------------------------------------------------------------------------------------

@@ -100,6 +100,22 @@ void     oracle_sample_brdf_batch(const float* material, const float* V, const f
  * Returns EnvironmentCdfSum. */
 float    oracle_env_probe(const PTSceneDesc* scene, const PTFrameParams* params, int what, const float* in, uint64_t n, float* out);
 
+/* The material fetch and the BSDF in isolation (util/material.hlsl, util/texture.hlsl, util/sampling.hlsl, util/brdf.hlsl), over `scene`'s
+ * materials and textures; the element layouts are those of csrc/bsdf_probe.hip (floats in, floats out, an RNG state as its bits):
+ *   what 0: GetMaterial(material in[0], uv in[1..2], ray direction in[3..5], normal in[6..8])   -> 24 floats of Material, the same 24 again,
+ *           materialFetches, texDescriptorFetches, texelFetches of that one fetch              (9 in, 51 out)
+ *   what 1: SampleTexture(texture in[0], uv in[1..2], linear)                                   -> rgba, five times   (3 in, 20 out)
+ *   what 2: one helper of util/sampling.hlsl / util/common.hlsl, in[0] = 0 GTR1 1 SampleGTR1 2 SampleGGXVNDF 3 GTR2Aniso 4 SmithG
+ *           5 SmithGAniso 6 SchlickWeight 7 DielectricFresnel 8 CosineSampleHemisphere 9 PowerHeuristic 10 reflect 11 refract 12 GetONB
+ *           13 Luminance, operands in[1..7]                                                     -> 9 floats, the unused ones 0   (8 in, 9 out)
+ *   what 3: material in[0], uv, V in[3..5], hit normal in[6..8], roughness floor in[9]; ray direction -V, ffnormal by util/bvh.hlsl:209,
+ *           GetMaterial, roughness = max(floor, roughness) as PathTrace does, TintColors, ComputeLobes at V.z in GetONB(ffnormal)
+ *                                                                                               -> F0, Csheen, Cspec0, the 8 LobeWeights   (10 in, 15 out)
+ *   what 4: as 3, then L in[10..12] and a flag in[13]: EvalBRDF(mat, V, flag == 0 ? ffnormal : normal, L)  -> f, pdf   (14 in, 4 out)
+ *   what 5: as 3, then an RNG state in[10]: SampleBRDF(mat, V, ffnormal)                         -> L, f, pdf, the state after   (11 in, 8 out)
+ * Returns 0, or -1 for a bad argument or an index outside the scene. */
+int      oracle_bsdf_probe(const PTSceneDesc* scene, int what, const float* in, uint64_t n, float* out);
+
 /* Scene ingestion: one Dispatch of MeshProcessing.compute:59-139 (writes triangles [OutputTriangleStart, +TriangleCount) of both
  * output buffers) and the texture loop of BVHScene.cs:386-417 over CopyTextureData.compute:13-36. */
 int      oracle_process_mesh(const PTMeshDesc* mesh, float* vertexPositionBuffer, void* triangleAttributesBuffer);

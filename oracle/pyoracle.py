@@ -90,6 +90,8 @@ def load_oracle():
         lib.oracle_present.argtypes = [C.POINTER(abi.PTPresentParams), C.c_void_p, C.c_void_p]
         lib.oracle_env_probe.restype = C.c_float
         lib.oracle_env_probe.argtypes = [C.POINTER(abi.PTSceneDesc), C.POINTER(abi.PTFrameParams), C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
+        lib.oracle_bsdf_probe.restype = C.c_int
+        lib.oracle_bsdf_probe.argtypes = [C.POINTER(abi.PTSceneDesc), C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
         _oracle = lib
     return _oracle
 
@@ -360,6 +362,23 @@ def env_probe(buffers: SceneBuffers, params, what: int, values: np.ndarray):
     out = np.zeros((n, per_out), dtype=np.float32)
     total = lib.oracle_env_probe(C.byref(buffers.desc), C.byref(params), what, vin.ctypes.data, n, out.ctypes.data)
     return out, float(total)
+
+
+BSDF_PROBE_IN = {0: 9, 1: 3, 2: 8, 3: 10, 4: 14, 5: 11}
+BSDF_PROBE_OUT = {0: 51, 1: 20, 2: 9, 3: 15, 4: 4, 5: 8}
+
+
+def bsdf_probe(buffers: SceneBuffers, what: int, values: np.ndarray) -> np.ndarray:
+    """oracle_bsdf_probe over `values` (n, BSDF_PROBE_IN[what]) float32 -> (n, BSDF_PROBE_OUT[what]) float32: what 0 GetMaterial,
+    1 SampleTexture, 2 a sampling helper, 3 TintColors + ComputeLobes, 4 EvalBRDF, 5 SampleBRDF (layouts: oracle/pt_oracle.h)."""
+    lib = load_oracle()
+    vin = np.ascontiguousarray(values, dtype=np.float32)
+    assert vin.size % BSDF_PROBE_IN[what] == 0
+    n = vin.size // BSDF_PROBE_IN[what]
+    out = np.zeros((n, BSDF_PROBE_OUT[what]), dtype=np.float32)
+    rc = lib.oracle_bsdf_probe(C.byref(buffers.desc), what, vin.ctypes.data, n, out.ctypes.data)
+    assert rc == 0, rc
+    return out
 
 
 def present(params, frame: np.ndarray) -> np.ndarray:
