@@ -31,14 +31,15 @@ def device_flags(unit=None):
 
 
 def parse_report(stderr):
-    """kernel name -> {vgprs, scratch, occupancy, vgpr_spill, lds} from the compiler's remarks"""
+    """kernel name -> {vgprs, scratch, occupancy, vgpr_spill, sgpr_spill, lds} from the compiler's remarks"""
     res, cur = {}, None
     for line in stderr.splitlines():
         m = re.search(r"Function Name: (\S+)", line)
         if m:
             cur = res.setdefault(m.group(1), {})
             continue
-        for key, name in (("VGPRs:", "vgprs"), ("ScratchSize", "scratch"), ("Occupancy", "occupancy"), ("VGPRs Spill", "vgpr_spill"), ("LDS Size", "lds")):
+        for key, name in (("VGPRs:", "vgprs"), ("ScratchSize", "scratch"), ("Occupancy", "occupancy"), ("VGPRs Spill", "vgpr_spill"), ("SGPRs Spill", "sgpr_spill"),
+                          ("LDS Size", "lds")):
             m = re.search(re.escape(key) + r"[^0-9]*(\d+)", line)
             if m and cur is not None and key in line:
                 cur[name] = int(m.group(1))

@@ -250,16 +250,17 @@ def _translate(x, y, z):
     return m
 
 
-def deep_tlas(count=48, floor=False):
+def deep_tlas(count=48, floor=False, lights=None):
     """count instances of a one-quad mesh (the unit square of the plane x = 0), instance k moved to (k, k, 0): strip y in [k, k + 1]
     of the plane x = k.  TLAS inner node I_k = node 2k has the leaf L_k = node 2k + 1 (box x in [k - 0.5, k + 0.5]) on the left and
     I_{k+1} (box x in [k + 0.5, count - 0.5]) on the right; the last inner node has the last two leaves.  Every box spans
     [-64, 128] in y and in z.  floor: a floor instance and a rect light for frames (the floor's leaf takes the place of the last
-    quad's, which moves one level down), not used by the ray families."""
+    quad's, which moves one level down), not used by the ray families.  lights: (k, 16) PTLight records for the scene without the
+    floor, which has none of its own (the direct-light test brings its point lights)."""
     quad = [((0.0, 0.0, 0.0), (0, 1, 0), (0, 0, 1)), ((0.0, 1.0, 1.0), (0, -1, 0), (0, 0, -1))]
     tris, mats, ranges = list(quad), [0, 0], [(0, 2)]
     inst = [(0, _translate(k, k, 0), 0) for k in range(count)]
-    lights = np.zeros((0, 16), np.float32)
+    lights = np.zeros((0, 16), np.float32) if lights is None else np.ascontiguousarray(lights, np.float32).reshape(-1, 16)
     boxes = [((k - 0.5, -64.0, -64.0), (k + 0.5, 128.0, 128.0)) for k in range(count)]
     if floor:
         ftris, light = _floor_and_light((-8.0, -8.0), (56.0, 8.0), -1.0, 70.0)

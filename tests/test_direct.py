@@ -12,7 +12,7 @@ import pytest
 
 from unity_webgpu_pathtracer_amd import abi, plugin
 
-from kernel_resources import device_flags, resources
+from kernel_resources import resources
 import direct_cases as cases
 import direct_ref as ref
 
@@ -300,28 +300,11 @@ def test_direct_refusals():
 # ---------------------------------------------------------------------------------------------------------------------------
 # the kernels' resources and the sanitizer program
 # ---------------------------------------------------------------------------------------------------------------------------
-def _scalar_spills(src):
-    """kernel name -> scalar registers spilled, from hipcc's report of csrc/<src> (the shared helper reads the vector spills only)"""
-    import re
-    out = subprocess.run(["hipcc", "--offload-arch=gfx950", "--cuda-device-only", "-c", src, "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"] + device_flags(),
-                         cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    res, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-        m = re.search(r"SGPRs Spill: (\d+)", line)
-        if m and cur is not None:
-            res[cur] = int(m.group(1))
-    return res
-
-
 def test_direct_kernel_resources():
     """no scratch and no spill, of vector or of scalar registers, in any of the four kernels; the fused kernels' waves per SIMD as
     DESIGN.md 5.29 records them (pt_query's any-hit kernels: 8 flat, 4 with a TLAS)"""
     rep = resources("pt_direct.hip")
-    sgpr = _scalar_spills("pt_direct.hip")
+    sgpr = {k: r["sgpr_spill"] for k, r in rep.items()}
     names = {"rays": [k for k in rep if "pt_direct_rays" in k], "accumulate": [k for k in rep if "pt_direct_accumulate" in k],
              "light": ["pt_direct_light"], "tlas": ["pt_direct_light_tlas"]}
     for what, ks in names.items():

@@ -240,6 +240,54 @@ def test_all_blocks_active_is_the_batch(oracle, name):
     assert stats[0] == stats[1] and stats[0][4] > 0, (name, stats)
 
 
+def test_direct_light_follows_the_rule_on_the_deep_tlas(oracle):
+    """Direct light at the first hits of deep_tlas(48)'s rays, whose shadow rays push more than 32 TLAS entries: PTDirectLight must
+    equal, bit for bit, PTDirectRays -> any-hit PTTraceRays -> PTDirectAccumulate, and PTDirectLightCulled over a one-cell grid.
+
+    Which shadow rays can overflow follows from the construction.  A pair counts only when its light lies in front of the surface
+    (N . L > 0, N turned towards the first ray).  The chain_first rays come from +x, so their hits face +x and their shadow rays
+    run towards +x: the leaves below the hit lie behind such a ray and every leaf above it is nearer than the rest of the chain, so
+    the stack never holds more than one entry.  The hits that face -x are the leaf_first rays': a shadow ray towards -x from the
+    hit on instance j finds the rest of the chain first at every level below j and pushes leaf 0 ... j - 1: entries 32 ... j - 1
+    are lost for j > 32.  So the list is the chain_first rays' first hits AND the leaf_first rays', 128 entries each, with one point
+    light on either side; the light at -x stands where the quads j - 1, j - 2, ... shade the hit on quad j -- instances the
+    overflowing walks lose, so the rule decides which of these entries are lit."""
+    lights = np.stack([sc.scenes.pack_point_light((100.0, 24.0, 12.0), (1.0, 1.0, 1.0), 400.0, rng=1000.0),
+                       sc.scenes.pack_point_light((-40.0, -28.0, 0.3), (1.0, 0.9, 0.8), 400.0, rng=1000.0)])
+    case = sc.deep_tlas(48, lights=lights)
+    pt = case.tracer()
+    try:
+        rays = np.concatenate([sc.pad128(case.families["chain_first"]["rays"]), sc.pad128(case.families["leaf_first"]["rays"])])
+        hits, surf = pt.trace_rays(rays, surface=True)
+        found = _bits(hits[:, 3]) != MISS
+        assert found[128:].all() and found[:128].any() and not found[:128].all()     # chain first: entries 32 ... 46 are lost
+        kw = dict(strata=1, centered=True)
+        _, terms, recv, _ = pt.shade_surfaces(rays, hits, surf)
+        pair_rays, contrib = pt.direct_rays(rays, terms, recv, **kw)
+        pairs = pt.direct_pair_count(1)
+        assert pairs == 2 and pair_rays.shape[0] == 2 * len(rays)
+        counting = pair_rays[:, 6] > 0
+        assert (counting.reshape(-1, 2) == np.stack([found & (np.arange(256) < 128), np.arange(256) >= 128], axis=1)).all()
+        # the condition, on the CPU first: the oracle's any-hit walk of the pair rays overflows
+        ref, ref_st = oracle.trace_rays(case.buffers(oracle), _oracle_rays(oracle, pair_rays, any_hit=True))
+        assert ref_st.stackOverflows > 0
+        pair_hits, st = _query(pt, pair_rays, any_hit=True)
+        print(f"[stack] direct light on deep_tlas48: {int(counting.sum())} counting pairs, stackOverflows {st.stackOverflows} (oracle {ref_st.stackOverflows})")
+        assert st.stackOverflows == ref_st.stackOverflows > 0
+        occluded = _bits(pair_hits[:, 3]) != MISS
+        assert (occluded == (_bits(ref[:, 3]) != MISS)).all()
+        want = pt.direct_accumulate(terms, contrib, pair_hits, pairs)
+        got = pt.direct_light(rays, hits, surf, **kw)
+        assert (_bits(got) == _bits(want)).all()
+        pt.build_light_grid((-64.0, -64.0, -64.0), 256.0, (1, 1, 1))
+        assert (_bits(pt.direct_light(rays, hits, surf, culled=True, **kw)) == _bits(want)).all()
+        # not vacuous: lit and shadowed entries on the side that overflows, light on the other side too
+        lit = (want[:, 0:3] > 0).any(axis=1)
+        assert lit[:128].any() and lit[128:].any() and (~lit[128:]).any() and occluded[counting].any() and not occluded[~counting].any()
+    finally:
+        pt.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # slab neighbours
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -14,7 +14,7 @@ import pytest
 
 from unity_webgpu_pathtracer_amd import abi, plugin
 
-from kernel_resources import device_flags, resources
+from kernel_resources import resources
 import direct_cases
 import light_grid_cases as cases
 import light_grid_ref as ref
@@ -337,29 +337,12 @@ def test_light_grid_refusals():
 # ---------------------------------------------------------------------------------------------------------------------------
 # the culled kernels' resources and the sanitizer program
 # ---------------------------------------------------------------------------------------------------------------------------
-def _scalar_spills(src):
-    """kernel name -> scalar registers spilled, from hipcc's report of csrc/<src> (the shared helper reads the vector spills only)"""
-    import re
-    out = subprocess.run(["hipcc", "--offload-arch=gfx950", "--cuda-device-only", "-c", src, "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"] + device_flags(),
-                         cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    res, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-        m = re.search(r"SGPRs Spill: (\d+)", line)
-        if m and cur is not None:
-            res[cur] = int(m.group(1))
-    return res
-
-
 def test_light_grid_kernel_resources():
     """no scratch and no spill, of vector or of scalar registers, in the culled kernels and the build kernels; the culled kernels'
     LDS is the unculled ones' and their waves per SIMD as DESIGN.md 5.30 records them (5 flat, 4 with a TLAS); the unculled kernels
     keep DESIGN.md 5.29's figures with the culled ones beside them in the file"""
     rep = resources("pt_direct.hip")
-    sgpr = _scalar_spills("pt_direct.hip")
+    sgpr = {k: r["sgpr_spill"] for k, r in rep.items()}
     for k in ("pt_direct_light", "pt_direct_light_tlas", "pt_direct_light_grid", "pt_direct_light_grid_tlas"):
         r = rep[k]
         print(f"[light grid] {k}: {r}, scalar spill {sgpr[k]}")
@@ -370,7 +353,7 @@ def test_light_grid_kernel_resources():
     assert rep["pt_direct_light"]["occupancy"] >= 6 and rep["pt_direct_light_tlas"]["occupancy"] >= 4
     assert (rep["pt_direct_light"]["vgprs"], rep["pt_direct_light_tlas"]["vgprs"]) == (75, 110)         # as before the culled kernels stood beside them
     build = resources("pt_light_grid.hip")
-    spills = _scalar_spills("pt_light_grid.hip")
+    spills = {k: r["sgpr_spill"] for k, r in build.items()}
     for k in ("pt_lgrid_count", "pt_lgrid_scan", "pt_lgrid_emit"):
         r = build[k]
         print(f"[light grid] {k}: {r}, scalar spill {spills[k]}")

@@ -1,4 +1,5 @@
-"""Direct light over many lights at the first hits of the 1920x1080 frame on the Sponza-class scene: PTDirectLight against
+"""Direct light over many lights at the first hits of the 1920x1080 frame on the Sponza-class scene (or, with --scene instanced, on
+the HAS_TLAS scene of direct_light_bench.py: pt_direct_light_tlas against pt_direct_light_grid_tlas): PTDirectLight against
 PTDirectLightCulled (include/ptmi_plugin.h Part 25).  One JSON line.
 
 The scene's two lights are replaced, through scene construction, by lattices of 64, 256 and 1,024 local lights -- a third point,
@@ -69,20 +70,29 @@ def main():
     ap.add_argument("--legs", type=int, default=3, help="legs of each kind, alternating")
     ap.add_argument("--short", action="store_true", help="profiling runs: one leg of each kind, two calls")
     ap.add_argument("--detail", type=float, default=1.0, help="the scene's tessellation (1: the benchmark's 250,752 triangles)")
+    ap.add_argument("--scene", default="sponza", choices=["sponza", "instanced"], help="instanced: the HAS_TLAS scene (200 instances): the _tlas kernels")
     args = ap.parse_args()
     if args.short:
         args.legs, args.steps = 1, 2
 
-    base = scenes.sponza_atrium(detail=args.detail)
-    v = base.vertices[:, :3]
-    lo, hi = v.min(0).astype(np.float64), v.max(0).astype(np.float64)
+    def make_scene():
+        return scenes.sponza_atrium(detail=args.detail) if args.scene == "sponza" else scenes.instanced_scene(count=200, detail=24)
+
+    base = make_scene()
+    if args.scene == "sponza":
+        v = base.vertices[:, :3]
+        lo, hi = v.min(0).astype(np.float64), v.max(0).astype(np.float64)
+    else:                                                        # the instances' world boxes: the context knows them
+        probe = PathTracer(base, width=W, height=H, samplesPerPass=8)
+        lo, hi = (np.asarray(b, np.float64) for b in probe._scene_bounds())
+        probe.close()
     result = {"scene": base.name, "image": f"{W}x{H}", "entries": W * H, "triangles": base.vertices.shape[0] // 3, "steps": args.steps, "warmup": args.warmup,
               "configs": {}}
     configs = [("own", None, ((1, False),)), ("64", (4, 4, 4), ((1, False), (1, True))), ("256", (8, 4, 8), ((1, False), (1, True), (4, False))),
                ("1024", (16, 4, 16), ((1, False), (1, True)))]
     rays = hits = surf = None
     for name, dims, modes in configs:
-        s = scenes.sponza_atrium(detail=args.detail)
+        s = make_scene()
         if dims is None:
             cell = float((hi - lo).max() / 16)
         else:

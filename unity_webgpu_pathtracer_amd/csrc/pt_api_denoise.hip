@@ -10,7 +10,7 @@ int ensure_guides(PTContext* c, uint32_t w, uint32_t h)
     if (!g.slab.ptr) {
         HIP_TRY(pt_guide_grid_caps(c->device, g.caps));
         const uint32_t cap = g.caps[0] > g.caps[1] ? g.caps[0] : g.caps[1];
-        if (int rc = g.slab.reserve((size_t)cap * pt_guide_slab_bytes_per_wave())) return rc;
+        if (int rc = g.slab.reserve((size_t)cap * pt_resident_wave_slab_bytes())) return rc;
     }
     return g.frames.resize(w, h, {sizeof(float4), sizeof(float4)}, c->stream);
 }

@@ -36,8 +36,7 @@ int query_prepare(PTContext* c)
     HIP_TRY(pt_direct_grid_caps(c->device, q.directCaps));
     for (uint32_t cap : q.caps) q.capMax = cap > q.capMax ? cap : q.capMax;
     for (uint32_t cap : q.directCaps) q.capMax = cap > q.capMax ? cap : q.capMax;
-    const size_t perWave = pt_query_slab_bytes_per_wave() > pt_direct_slab_bytes_per_wave() ? pt_query_slab_bytes_per_wave() : pt_direct_slab_bytes_per_wave();
-    return q.slab.reserve((size_t)q.capMax * perWave);
+    return q.slab.reserve((size_t)q.capMax * pt_resident_wave_slab_bytes());
 }
 
 extern "C" {

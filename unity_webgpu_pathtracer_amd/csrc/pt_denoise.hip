@@ -14,8 +14,6 @@
 #include "pt_device.h"
 #include "pt_launch.h"
 
-#define PT_G_SLAB_ENTRIES (PT_BVH_STACK_SIZE - PT_Q_LDS_STACK)
-
 namespace {
 
 // GetBaseColorOpacity (util/material.hlsl:56-69) as get_material computes it: the material's base colour, times the bilinear
@@ -36,18 +34,10 @@ template <bool TLAS>
 PT_DEV void guide_body(const DScene& S, const PTFrameParams& P, uint32_t n, float4* __restrict__ albedo,
                        float4* __restrict__ normalDepth, uint2* __restrict__ slab)
 {
-    __shared__ uint2 s_stack[PT_Q_LDS_STACK][64];
-    __shared__ uint32_t s_gw;
     const uint32_t lane = threadIdx.x;
-    if (lane == 0u) s_gw = blockIdx.x;                                  // slab row = wave * 64 + lane (grid <= slab waves)
-    __builtin_amdgcn_wave_barrier();
-
     Counters cn = {};
     TravStackT<PT_Q_LDS_STACK, true> st;
-    st.lds = PT_LDS_U2(&s_stack[0][lane]);
-    st.stride = 64u;
-    st.gbase = slab;
-    st.gwave = PT_LDS_WORD(s_gw);
+    resident_wave_stack(st, slab);
 
     const uint32_t W = P.OutputWidth, H = P.OutputHeight;
     const uint32_t bw = (W + 7u) / 8u, blocks = bw * ((H + 7u) / 8u);
@@ -70,9 +60,7 @@ PT_DEV void guide_body(const DScene& S, const PTFrameParams& P, uint32_t n, floa
                 const v4 d4 = mul44(P.CamInvProj, v4{uvx, uvy, 0.0f, 1.0f});
                 const v4 w4 = mul44(P.CamToWorld, v4{d4.x, d4.y, d4.z, 0.0f});
                 const v3 d = normalize3(mk3(w4.x, w4.y, w4.z));
-                HitRecord rec;
-                rec.h.t = PT_FAR_PLANE; rec.h.u = 0.0f; rec.h.v = 0.0f; rec.h.triIndex = 0xFFFFFFFFu;
-                rec.pos = mk3(0.0f); rec.inst = 0xFFFFFFFFu;
+                HitRecord rec = miss_record(PT_FAR_PLANE);
                 bool found;
                 if (TLAS) {
                     traverse_tlas<false>(S, o, d, false, rec, st, cn);
@@ -381,20 +369,9 @@ typedef void (*GuideKernel)(DScene, PTFrameParams, uint32_t, float4*, float4*, u
 const GuideKernel kGuideKernels[2] = {pt_guides, pt_guides_tlas};
 } // namespace
 
-size_t pt_guide_slab_bytes_per_wave() { return (size_t)64 * PT_G_SLAB_ENTRIES * sizeof(uint2); }
-
 hipError_t pt_guide_grid_caps(int device, uint32_t caps[2])
 {
-    hipDeviceProp_t prop;
-    hipError_t e = hipGetDeviceProperties(&prop, device);
-    if (e != hipSuccess) return e;
-    for (int k = 0; k < 2; ++k) {
-        int blocks = 0;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, reinterpret_cast<const void*>(kGuideKernels[k]), 64, 0);
-        if (e != hipSuccess) return e;
-        caps[k] = (uint32_t)(blocks > 0 ? blocks : 1) * (uint32_t)prop.multiProcessorCount;
-    }
-    return hipSuccess;
+    return pt_resident_wave_caps(device, kGuideKernels, 2, caps);
 }
 
 hipError_t pt_launch_guides(const DScene& S, const PTFrameParams& P, uint32_t n, float4* albedo, float4* normalDepth, uint2* slab,

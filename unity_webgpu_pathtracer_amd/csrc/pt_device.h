@@ -189,6 +189,23 @@ PT_DEV uint2 stack_pop(ST& st, uint32_t sp)
     return make_uint2(0u, 0u);
 }
 
+// The frame of a resident-wave walk (pt_query.hip, pt_denoise.hip, pt_direct.hip: one 64-lane wave per workgroup, the grid no
+// larger than the slab's waves): the LDS part of the CWBVH stack and the word that holds the wave's slab row, declared here once.
+PT_DEV void resident_wave_stack(TravStackT<PT_Q_LDS_STACK, true>& st, uint2* slab)
+{
+    __shared__ uint2 s_stack[PT_Q_LDS_STACK][64];
+    __shared__ uint32_t s_gw;
+    const uint32_t lane = threadIdx.x;
+    if (lane == 0u) s_gw = blockIdx.x;                                  // slab row = wave * 64 + lane (grid <= slab waves)
+    __builtin_amdgcn_wave_barrier();
+    st.lds = PT_LDS_U2(&s_stack[0][lane]);
+    st.stride = 64u;
+    st.gbase = slab;
+    st.gwave = PT_LDS_WORD(s_gw);
+}
+// host side: entries of a slab row of those kernels (pt_resident_wave_slab_bytes, pt_launch.h)
+#define PT_Q_SLAB_ENTRIES (PT_BVH_STACK_SIZE - PT_Q_LDS_STACK)
+
 PT_DEV uint32_t byte_of(uint32_t v, int i) { return (v >> (i * 8)) & 0xFFu; }
 
 // util/bvh.hlsl:77-124.  n0..n4 are the five 16-byte rows of the node.
@@ -440,6 +457,14 @@ struct HitRecord {
     v3 pos;              // HAS_TLAS: world-space hit position (tlas.hlsl:216)
     uint32_t inst;       // HAS_TLAS: instance that owns the hit
 };
+// the record a walk starts from: nothing hit below tmax
+PT_DEV HitRecord miss_record(float tmax)
+{
+    HitRecord rec;
+    rec.h.t = tmax; rec.h.u = 0.0f; rec.h.v = 0.0f; rec.h.triIndex = 0xFFFFFFFFu;
+    rec.pos = mk3(0.0f); rec.inst = 0xFFFFFFFFu;
+    return rec;
+}
 
 PT_DEV v4 mul44c(float4 c0, float4 c1, float4 c2, float4 c3, v4 v)   // Matrix4x4 given as its four columns
 {
@@ -495,14 +520,32 @@ PT_DEV bool traverse_instance(const DScene& S, v3 wo, v3 wd, uint32_t instIndex,
     return rec.h.t < PT_FAR_PLANE;
 }
 
+// Where traverse_tlas keeps its PT_BVH_STACK_SIZE node indices.  Private: the reference's per-thread array (scratch once it is
+// indexed dynamically).  Lds: a column of a [PT_BVH_STACK_SIZE][64] LDS array, entry stride 64 -- for the one-wave kernels that
+// must not have scratch (pt_direct.hip).  Both are only ever indexed below PT_BVH_STACK_SIZE: the rule is the walk's, not theirs.
+// The private one is a bare array that the walk itself declares, where it always has: wrapped in a struct, or declared by the
+// caller, it is placed differently in scratch and every HAS_TLAS kernel of the render moves (profiles/direct_shared_ab.md).
+typedef uint32_t TlasStackPrivate[PT_BVH_STACK_SIZE];
+typedef __attribute__((address_space(3))) uint32_t* pt_lds_column;     // &smem[0][lane], an LDS address (32 bits, no flat pointer)
+struct TlasStackLds {
+    pt_lds_column col;
+};
+PT_DEV void tlas_stack_begin(TlasStackPrivate&, pt_lds_column) {}
+PT_DEV void tlas_stack_begin(TlasStackLds& s, pt_lds_column col) { s.col = col; }
+PT_DEV void tlas_stack_store(TlasStackPrivate& s, uint32_t i, uint32_t v) { s[i] = v; }
+PT_DEV uint32_t tlas_stack_load(const TlasStackPrivate& s, uint32_t i) { return s[i]; }
+PT_DEV void tlas_stack_store(TlasStackLds& s, uint32_t i, uint32_t v) { s.col[i * 64u] = v; }
+PT_DEV uint32_t tlas_stack_load(const TlasStackLds& s, uint32_t i) { return s.col[i * 64u]; }
+
 // The pop of the overflow rule (ptmi_plugin.h, Part 3) for the TLAS stack: entries at index >= 32 were never stored, yield nothing
 // and popping goes on -- so the next entry that can be yielded is the one below min(sp, 32).  false: nothing left, the walk is over.
 // No index >= PT_BVH_STACK_SIZE is formed.
-PT_DEV bool tlas_stack_pop(const uint32_t (&stack)[PT_BVH_STACK_SIZE], uint32_t& sp, uint32_t& nodeIndex)
+template <class TS>
+PT_DEV bool tlas_stack_pop(const TS& stack, uint32_t& sp, uint32_t& nodeIndex)
 {
     sp = sp < PT_BVH_STACK_SIZE ? sp : PT_BVH_STACK_SIZE;
     if (sp == 0u) return false;
-    nodeIndex = stack[--sp];
+    nodeIndex = tlas_stack_load(stack, --sp);
     return true;
 }
 
@@ -542,17 +585,17 @@ PT_DEV TlasStep tlas_node_step(float4 a, float4 b, float4 c, float4 e, v3 O, v3 
     return s;
 }
 
-// tlas.hlsl:236-332.  pt_direct.hip's anyhit_tlas is this loop for an any-hit ray with the TLAS stack in LDS instead of the private
-// array (steps, instance walks and the pop rule are the functions above): a change to the walk's order here is made there too;
-// tests/test_gpu_direct.py compares the two on the instanced scene bit for bit.
-template <bool STATS, class ST>
-PT_DEV bool traverse_tlas(const DScene& S, v3 O, v3 dir, bool isShadow, HitRecord& rec, ST& st, Counters& cn)
+// tlas.hlsl:236-332.  TS is the walk's TLAS stack: the private array, as in the reference, unless the caller names TlasStackLds
+// and hands over its lane's column.
+template <bool STATS, class TS = TlasStackPrivate, class ST>
+PT_DEV bool traverse_tlas(const DScene& S, v3 O, v3 dir, bool isShadow, HitRecord& rec, ST& st, Counters& cn, pt_lds_column ldsColumn = nullptr)
 {
     if (ray_has_nan(O, dir)) return false;
     const v3 D = normalize3(dir);
     const v3 rD = mk3(1.0f / D.x, 1.0f / D.y, 1.0f / D.z);
     bool hitFound = false, overflow = false;
-    uint32_t stack[PT_BVH_STACK_SIZE];
+    TS stack;
+    tlas_stack_begin(stack, ldsColumn);
     uint32_t nodeIndex = 0u, sp = 0u;
     const float* T = S.tlas;
     while (true) {
@@ -566,7 +609,7 @@ PT_DEV bool traverse_tlas(const DScene& S, v3 O, v3 dir, bool isShadow, HitRecor
             } else {
                 nodeIndex = step.near;
                 if (step.pushFar) {
-                    if (sp < PT_BVH_STACK_SIZE) stack[sp] = step.far;
+                    if (sp < PT_BVH_STACK_SIZE) tlas_stack_store(stack, sp, step.far);
                     else if (STATS) overflow = true;
                     sp++;
                 }

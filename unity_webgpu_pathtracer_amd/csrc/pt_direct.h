@@ -4,11 +4,10 @@
 
 struct PTLightGridDevice;           // pt_light_grid.h
 
-// resident one-wave workgroups per device of pt_direct_light (caps[0]) and pt_direct_light_tlas (caps[1]): the grid cap, and the
-// slab waves it needs
+// pt_launch.h's pt_resident_wave_caps of pt_direct_light (caps[0]) and pt_direct_light_tlas (caps[1]); a slab row is the ray
+// queries' (pt_resident_wave_slab_bytes)
 hipError_t pt_direct_grid_caps(int device, uint32_t caps[2]);
 hipError_t pt_direct_culled_grid_caps(int device, uint32_t caps[2]);      // likewise pt_direct_light_grid and pt_direct_light_grid_tlas (Part 25)
-size_t pt_direct_slab_bytes_per_wave();
 // first: the list index of entry 0 of this launch (the entry's RNG state is made from the list index)
 hipError_t pt_launch_direct_rays(const DScene& S, const PTDirectParams& P, uint32_t pairsPerEntry, const PTRay* rays, const PTShadeTerms* terms,
                                  const PTReceiver* receivers, uint32_t count, uint32_t first, PTRay* outRays, float4* outContrib, hipStream_t stream);

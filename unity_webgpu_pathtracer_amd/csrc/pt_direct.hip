@@ -11,15 +11,17 @@
 //                           that light together when any lane's pair counts (the others sit the walk out), the contribution is
 //                           added when nothing was hit.  Terms, O, N, Vd and the running sum stay in registers; nothing per pair
 //                           is stored.  What only a chunk's front reads of the kernel's arguments is read from the argument
-//                           segment again per chunk, so neither kernel spills a scalar register.  The CWBVH stack is pt_query.hip's (PT_Q_LDS_STACK entries per lane in LDS, the rest in the
-//                           context's slab); the HAS_TLAS kernel keeps its 32 TLAS stack entries per lane in LDS too, so neither
-//                           kernel has scratch.
-//     pt_direct_light_grid[_tlas]  the same kernels over a light grid (Part 25): after the front a lane takes the
+//                           segment again per chunk, so neither kernel spills a scalar register.  The CWBVH stack is the ray
+//                           queries' (pt_device.h's resident_wave_stack: PT_Q_LDS_STACK entries per lane in LDS, the rest in the
+//                           context's slab); the HAS_TLAS kernel hands traverse_tlas a TLAS stack in LDS too (TlasStackLds, 32
+//                           entries per lane), so neither kernel has scratch.
+//     pt_direct_light_grid[_tlas]  the same body over a light grid (Part 25): after the front a lane takes the
 //                           list of its O's cell; the wave visits the union of its lanes' lists in ascending light index -- a
 //                           cross-lane minimum of the list heads per visited light -- and makes up the draws of the rectangle
-//                           lights it jumps over.  The pair, the walk and the sum are the kernels' above, so are the bits.
+//                           lights it jumps over.  The front, the pair, the walk, the sum and the output are written once
+//                           (direct_light_body<TLAS, CULLED>), so are the bits.
 //
-// The arithmetic is direct_rule.h's, which the host twins evaluate too; the walks are the render's (pt_device.h).
+// The arithmetic is direct_rule.h's, which the host twins evaluate too; the walks are the render's (pt_device.h), called, not copied.
 #include "pt_device.h"
 #include "pt_launch.h"
 #include "pt_shade_hit.h"
@@ -27,11 +29,7 @@
 #include "pt_direct.h"
 #include "pt_light_grid.h"
 
-#define PT_D_SLAB_ENTRIES (PT_BVH_STACK_SIZE - PT_Q_LDS_STACK)
-
 namespace {
-
-typedef __attribute__((address_space(3))) uint32_t* pt_lds_u32;
 
 // light l of the scene as the rule reads it; l is the same in every lane of the wave: six scalar loads
 PT_DEV ptdirect::Light uniform_light(const DScene& S, uint32_t l)
@@ -111,50 +109,6 @@ __global__ __launch_bounds__(256) void pt_direct_accumulate(const PTShadeTerms* 
     out[i] = make_float4(d[0], d[1], d[2], 1.0f);
 }
 
-// A COPY of traverse_tlas's loop (pt_device.h) for an any-hit ray with the TLAS stack in LDS ([entry][lane], 32 entries): the
-// same nodes in the same order, the same overflow rule (a push at index >= 32 stores nothing, a pop from there yields nothing).
-// tlas_node_step and traverse_instance are called; the push, the pop and the leaf iteration are written out again and follow that
-// function by hand (tests/test_gpu_direct.py holds the two together on the instanced scene, bit for bit)
-template <class ST>
-PT_DEV void anyhit_tlas(const DScene& S, v3 O, v3 dir, HitRecord& rec, ST& st, pt_lds_u32 tstack)
-{
-    if (ray_has_nan(O, dir)) return;
-    Counters cn = {};
-    const v3 D = normalize3(dir);
-    const v3 rD = mk3(1.0f / D.x, 1.0f / D.y, 1.0f / D.z);
-    uint32_t nodeIndex = 0u, sp = 0u;
-    const float* T = S.tlas;
-    while (true) {
-        const float4* np = (const float4*)(T + (size_t)nodeIndex * 16u);
-        const float4 a = np[0], b = np[1], c = np[2], e = np[3];
-        const TlasStep step = tlas_node_step(a, b, c, e, O, rD, rec.h.t);
-        bool pop = false;
-        if (!step.leaf) {
-            if (step.nothingHit) pop = true;
-            else {
-                nodeIndex = step.near;
-                if (step.pushFar) {
-                    if (sp < PT_BVH_STACK_SIZE) tstack[sp * 64u] = step.far;
-                    sp++;
-                }
-            }
-        } else {
-            for (uint32_t i = 0; i < step.count; ++i) {
-                const uint32_t instanceIndex = pt_asuint(T[S.tlasIndexOffset + step.first + i]);
-                bool stopNow = false;
-                traverse_instance<false>(S, O, dir, instanceIndex, true, rec, st, cn, stopNow);
-                if (stopNow) return;
-            }
-            pop = true;
-        }
-        if (pop) {
-            sp = sp < PT_BVH_STACK_SIZE ? sp : PT_BVH_STACK_SIZE;
-            if (sp == 0u) break;
-            nodeIndex = tstack[--sp * 64u];
-        }
-    }
-}
-
 // what the fused kernels read of PTDirectParams, in four scalar registers; add: PTShadeMixed's second launch
 struct DirectArgs {
     uint32_t strata, seed, flags;       // flags: PTDirectParams.flags | kAddBit
@@ -218,98 +172,7 @@ PT_DEV float4* output_array()
     return K->out;
 }
 
-template <bool TLAS>
-PT_DEV void direct_light_body(const LightArgs& A)
-{
-    const DScene& S = A.S;                                              // the walks' fields: live throughout
-    const DirectArgs& P = A.P;
-    const uint32_t count = A.count;
-    __shared__ uint2 s_stack[PT_Q_LDS_STACK][64];
-    __shared__ uint32_t s_tstack[TLAS ? PT_BVH_STACK_SIZE : 1][64];
-    __shared__ uint32_t s_gw;
-    const uint32_t lane = threadIdx.x;
-    if (lane == 0u) s_gw = blockIdx.x;                                  // slab row = wave * 64 + lane (grid <= slab waves)
-    __builtin_amdgcn_wave_barrier();
-
-    Counters cn = {};
-    TravStackT<PT_Q_LDS_STACK, true> st;
-    st.lds = PT_LDS_U2(&s_stack[0][lane]);
-    st.stride = 64u;
-    st.gbase = A.slab;
-    st.gwave = PT_LDS_WORD(s_gw);
-
-    const bool centred = (P.flags & PT_DIRECT_CENTERED) != 0u;
-    const uint32_t lightCount = scene_lights(S);
-    for (uint32_t base = blockIdx.x * 64u; base < count; base += gridDim.x * 64u) {     // base is wave-uniform: no lane leaves early
-        const uint32_t i = base + lane;
-        const bool active = i < count;
-        bool hit = false;
-        ptdirect::Entry e = {};
-        uint32_t s;
-        {
-            const FrontArgs f = front_args();
-            DScene Sf = {};                                             // the scene as the material fetch reads it
-            Sf.materials = f.materials; Sf.tex = f.tex; Sf.attrs = f.attrs;
-            Sf.materialCount = f.materialCount; Sf.hasTextures = f.hasTextures;
-            if (active) {
-                HitRecords h;
-                hit_records(Sf, f.rays, f.hits, f.surfaces, i, nullptr, nullptr, 0u, h);
-                hit = !ptshade::is_miss(h.T);
-                if (hit) {
-                    const float4 r0 = ((const float4*)f.rays)[(size_t)i * 2], r1 = ((const float4*)f.rays)[(size_t)i * 2 + 1];
-                    const float D[3] = {r0.w, r1.x, r1.y};
-                    ptdirect::entry_begin(h.T, D, h.P, h.N, f.minAlpha, e);
-                }
-            }
-            s = ptdirect::entry_state(f.seed, (uint64_t)f.first + i);
-        }
-        float d0 = 0.0f, d1 = 0.0f, d2 = 0.0f;
-        const v3 o = mk3(e.O[0], e.O[1], e.O[2]);
-        // one loop over the pairs (l, k), both wave-uniform.  The light's 24 words are loaded again for every pair (scalar-cache
-        // hits) instead of being held in scalar registers across the walk, where the scene's pointers already fill the file
-        for (uint32_t l = 0, k = 0; l < lightCount;) {
-            DScene Sl = {};
-            light_arrays(Sl.lights, Sl.lightConst);
-            const ptdirect::Light Lt = uniform_light(Sl, l);
-            if (k >= ptdirect::pairs_of(Lt.type, P.strata)) {
-                ++l;
-                k = 0;
-                continue;
-            }
-            float x1 = 0.5f, x2 = 0.5f;
-            if (!centred && Lt.type == PT_LIGHT_TYPE_RECTANGLE) {
-                x1 = pt_random_float(&s);
-                x2 = pt_random_float(&s);
-            }
-            float dir[3], c[3];
-            const bool counts = hit && ptdirect::pair_eval(e, Lt, P.strata, k, x1, x2, dir, c);
-            ++k;
-            if (!__any(counts)) continue;                               // no lane's pair counts: no walk
-            if (counts) {
-                HitRecord rec;
-                rec.h.t = PT_FAR_PLANE; rec.h.u = 0.0f; rec.h.v = 0.0f; rec.h.triIndex = 0xFFFFFFFFu;
-                rec.pos = mk3(0.0f); rec.inst = 0xFFFFFFFFu;
-                const v3 d = mk3(dir[0], dir[1], dir[2]);
-                if (TLAS) anyhit_tlas(S, o, d, rec, st, (pt_lds_u32)&s_tstack[0][lane]);
-                else traverse_cwbvh<false>(S, o, d, true, rec.h, st, cn, PT_FAR_PLANE);
-                if (rec.h.triIndex == 0xFFFFFFFFu) { d0 = d0 + c[0]; d1 = d1 + c[1]; d2 = d2 + c[2]; }
-            }
-        }
-        if (active) {
-            float4* out = output_array();
-            if ((P.flags & kAddBit) != 0u) {
-                if (hit) {
-                    const float4 v = out[i];
-                    out[i] = make_float4(v.x + d0, v.y + d1, v.z + d2, v.w);
-                }
-            } else {
-                out[i] = hit ? make_float4(d0, d1, d2, 1.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            }
-        }
-    }
-}
-
-// ---- the culled kernels (Part 25): direct_light_body with the pair loop over the union of the lanes' cell lists ----
+// ---- what only the culled kernels read (Part 25): the pair loop over the union of the lanes' cell lists ----
 // The culled kernels' ONE argument: LightArgs first, so that front_args, light_arrays and output_array read it as they are
 struct GridLightArgs {
     LightArgs A;
@@ -387,34 +250,37 @@ PT_DEV uint32_t next_light(uint32_t& head, uint32_t& cur, uint32_t end, uint32_t
     return l;
 }
 
-template <bool TLAS>
-PT_DEV void direct_light_grid_body(const LightArgs& A)
+// The four kernels' body.  CULLED: the pair loop steps through the union of the lanes' cell lists (next_light) where the others
+// step through every light of the scene; a lane takes its list after the front.  Nothing else differs but two switches for
+// scalar-register pressure, marked where they stand: the chunk loop's step (CULLED && TLAS) and the add flag (CULLED || TLAS).
+template <bool TLAS, bool CULLED>
+PT_DEV void direct_light_body(const LightArgs& A)
 {
     const DScene& S = A.S;                                              // the walks' fields: live throughout
     const DirectArgs& P = A.P;
     const uint32_t count = A.count;
-    __shared__ uint2 s_stack[PT_Q_LDS_STACK][64];
     __shared__ uint32_t s_tstack[TLAS ? PT_BVH_STACK_SIZE : 1][64];
-    __shared__ uint32_t s_gw;
     const uint32_t lane = threadIdx.x;
-    if (lane == 0u) s_gw = blockIdx.x;                                  // slab row = wave * 64 + lane (grid <= slab waves)
-    __builtin_amdgcn_wave_barrier();
-
     Counters cn = {};
     TravStackT<PT_Q_LDS_STACK, true> st;
-    st.lds = PT_LDS_U2(&s_stack[0][lane]);
-    st.stride = 64u;
-    st.gbase = A.slab;
-    st.gwave = PT_LDS_WORD(s_gw);
+    resident_wave_stack(st, A.slab);
+    const pt_lds_column tstack = (pt_lds_column)&s_tstack[0][lane];
 
     const bool centred = (P.flags & PT_DIRECT_CENTERED) != 0u;
-    for (uint32_t base = blockIdx.x * 64u; base < count; base += gridDim.x * 64u) {     // base is wave-uniform: no lane leaves early
+    const uint32_t lightCount = scene_lights(S);
+    // The chunk loop's step.  Left to the compiler, the pointer it is loaded through at every chunk's end is held in two scalar
+    // registers across the pair loop; the culled HAS_TLAS kernel has none to spare (they spill) and holds the step itself, in one
+    uint32_t step = 0u;
+    if (CULLED && TLAS) {
+        step = gridDim.x * 64u;
+        asm volatile("" : "+s"(step));
+    }
+    for (uint32_t base = blockIdx.x * 64u; base < count; base += CULLED && TLAS ? step : gridDim.x * 64u) {     // base is wave-uniform: no lane leaves early
         const uint32_t i = base + lane;
         const bool active = i < count;
         bool hit = false;
         ptdirect::Entry e = {};
         uint32_t s;
-        uint32_t cur = 0u, end = 0u;                                    // the lane's cursor into its cell's list; a miss holds an empty one
         {
             const FrontArgs f = front_args();
             DScene Sf = {};                                             // the scene as the material fetch reads it
@@ -434,23 +300,25 @@ PT_DEV void direct_light_grid_body(const LightArgs& A)
         }
         float d0 = 0.0f, d1 = 0.0f, d2 = 0.0f;
         const v3 o = mk3(e.O[0], e.O[1], e.O[2]);
-        uint32_t head = ptlgrid::kNoLight;                              // the light at the lane's cursor
-        if (hit) {                                                      // the front's arguments are dead: the grid's fit the scalar file now
+        // CULLED: the lane's cursor into its cell's list and the light at it; a miss holds an empty list.  drawn: the lights below
+        // it have had their draws
+        uint32_t cur = 0u, end = 0u, head = ptlgrid::kNoLight, drawn = 0u;
+        if (CULLED && hit) {                                            // the front's arguments are dead: the grid's fit the scalar file now
             const PTLightGridDevice G = grid_args();
             const uint32_t cell = ptlgrid::cell_of(G.g, e.O);
             cur = G.offsets[cell];
             end = G.offsets[cell + 1u];
             if (cur < end) head = G.indices[cur];
         }
-        // One loop over the pairs (l, k), both wave-uniform, as direct_light_body's; l steps through the union of the lanes' lists
-        // (next_light).  drawn: the lights below it have had their draws
-        uint32_t drawn = 0u;
-        for (uint32_t l = next_light(head, cur, end, s, drawn, centred, P.strata), k = 0; l != ptlgrid::kNoLight;) {
+        // one loop over the pairs (l, k), both wave-uniform.  The light's 24 words are loaded again for every pair (scalar-cache
+        // hits) instead of being held in scalar registers across the walk, where the scene's pointers already fill the file
+        for (uint32_t l = CULLED ? next_light(head, cur, end, s, drawn, centred, P.strata) : 0u, k = 0;
+             CULLED ? l != ptlgrid::kNoLight : l < lightCount;) {
             DScene Sl = {};
             light_arrays(Sl.lights, Sl.lightConst);
             const ptdirect::Light Lt = uniform_light(Sl, l);
             if (k >= ptdirect::pairs_of(Lt.type, P.strata)) {
-                l = next_light(head, cur, end, s, drawn, centred, P.strata);
+                l = CULLED ? next_light(head, cur, end, s, drawn, centred, P.strata) : l + 1u;
                 k = 0;
                 continue;
             }
@@ -464,18 +332,19 @@ PT_DEV void direct_light_grid_body(const LightArgs& A)
             ++k;
             if (!__any(counts)) continue;                               // no lane's pair counts: no walk
             if (counts) {
-                HitRecord rec;
-                rec.h.t = PT_FAR_PLANE; rec.h.u = 0.0f; rec.h.v = 0.0f; rec.h.triIndex = 0xFFFFFFFFu;
-                rec.pos = mk3(0.0f); rec.inst = 0xFFFFFFFFu;
+                HitRecord rec = miss_record(PT_FAR_PLANE);
                 const v3 d = mk3(dir[0], dir[1], dir[2]);
-                if (TLAS) anyhit_tlas(S, o, d, rec, st, (pt_lds_u32)&s_tstack[0][lane]);
+                if (TLAS) traverse_tlas<false, TlasStackLds>(S, o, d, /*isShadow*/ true, rec, st, cn, tstack);
                 else traverse_cwbvh<false>(S, o, d, true, rec.h, st, cn, PT_FAR_PLANE);
                 if (rec.h.triIndex == 0xFFFFFFFFu) { d0 = d0 + c[0]; d1 = d1 + c[1]; d2 = d2 + c[2]; }
             }
         }
         if (active) {
             float4* out = output_array();
-            if (add_to_output()) {
+            // held across the pair loop, the flag spills in the HAS_TLAS kernels and costs the flat culled one registers: only the
+            // flat kernel over every light holds it, the others read it again (add_to_output)
+            const bool add = CULLED || TLAS ? add_to_output() : (P.flags & kAddBit) != 0u;
+            if (add) {
                 if (hit) {
                     const float4 v = out[i];
                     out[i] = make_float4(v.x + d0, v.y + d1, v.z + d2, v.w);
@@ -490,41 +359,21 @@ PT_DEV void direct_light_grid_body(const LightArgs& A)
 } // namespace
 
 // Stable, unmangled kernel names (rocprofv3 --kernel-trace lists them as they are written here).
-extern "C" __global__ __launch_bounds__(64) void pt_direct_light(LightArgs A) { direct_light_body<false>(A); }
-extern "C" __global__ __launch_bounds__(64) void pt_direct_light_tlas(LightArgs A) { direct_light_body<true>(A); }
-extern "C" __global__ __launch_bounds__(64) void pt_direct_light_grid(GridLightArgs A) { direct_light_grid_body<false>(A.A); }
-extern "C" __global__ __launch_bounds__(64) void pt_direct_light_grid_tlas(GridLightArgs A) { direct_light_grid_body<true>(A.A); }
-
-size_t pt_direct_slab_bytes_per_wave() { return (size_t)64 * PT_D_SLAB_ENTRIES * sizeof(uint2); }
-
-namespace {
-
-hipError_t grid_caps_of(int device, const void* const kernels[2], uint32_t caps[2])
-{
-    hipDeviceProp_t prop;
-    hipError_t e = hipGetDeviceProperties(&prop, device);
-    if (e != hipSuccess) return e;
-    for (int k = 0; k < 2; ++k) {
-        int blocks = 0;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernels[k], 64, 0);
-        if (e != hipSuccess) return e;
-        caps[k] = (uint32_t)(blocks > 0 ? blocks : 1) * (uint32_t)prop.multiProcessorCount;
-    }
-    return hipSuccess;
-}
-
-} // namespace
+extern "C" __global__ __launch_bounds__(64) void pt_direct_light(LightArgs A) { direct_light_body<false, false>(A); }
+extern "C" __global__ __launch_bounds__(64) void pt_direct_light_tlas(LightArgs A) { direct_light_body<true, false>(A); }
+extern "C" __global__ __launch_bounds__(64) void pt_direct_light_grid(GridLightArgs A) { direct_light_body<false, true>(A.A); }
+extern "C" __global__ __launch_bounds__(64) void pt_direct_light_grid_tlas(GridLightArgs A) { direct_light_body<true, true>(A.A); }
 
 hipError_t pt_direct_grid_caps(int device, uint32_t caps[2])
 {
-    const void* kernels[2] = {reinterpret_cast<const void*>(pt_direct_light), reinterpret_cast<const void*>(pt_direct_light_tlas)};
-    return grid_caps_of(device, kernels, caps);
+    void (*const kernels[2])(LightArgs) = {pt_direct_light, pt_direct_light_tlas};
+    return pt_resident_wave_caps(device, kernels, 2, caps);
 }
 
 hipError_t pt_direct_culled_grid_caps(int device, uint32_t caps[2])
 {
-    const void* kernels[2] = {reinterpret_cast<const void*>(pt_direct_light_grid), reinterpret_cast<const void*>(pt_direct_light_grid_tlas)};
-    return grid_caps_of(device, kernels, caps);
+    void (*const kernels[2])(GridLightArgs) = {pt_direct_light_grid, pt_direct_light_grid_tlas};
+    return pt_resident_wave_caps(device, kernels, 2, caps);
 }
 
 hipError_t pt_launch_direct_rays(const DScene& S, const PTDirectParams& P, uint32_t pairsPerEntry, const PTRay* rays, const PTShadeTerms* terms,

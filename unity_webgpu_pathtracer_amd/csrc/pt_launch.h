@@ -60,20 +60,37 @@ hipError_t pt_launch_copy_texture(const float4* dTexture, uint32_t width, uint32
                                   int hasAlpha, uint32_t* dTextureData, hipStream_t stream);
 hipError_t pt_launch_present(const PTPresentParams& Q, const float4* src, float4* dst, hipStream_t stream);
 
+// ---- the resident-wave kernels (pt_query.hip, pt_denoise.hip's guides, pt_direct.hip): one 64-lane wave per workgroup, walking
+// with pt_device.h's resident_wave_stack ----
+// caps[k] = resident workgroups per device of kernels[k] (occupancy x CUs): its grid cap, and the slab waves it needs
+template <class Kernel>
+inline hipError_t pt_resident_wave_caps(int device, const Kernel* kernels, int n, uint32_t* caps)
+{
+    hipDeviceProp_t prop;
+    hipError_t e = hipGetDeviceProperties(&prop, device);
+    if (e != hipSuccess) return e;
+    for (int k = 0; k < n; ++k) {
+        int blocks = 0;
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, reinterpret_cast<const void*>(kernels[k]), 64, 0);
+        if (e != hipSuccess) return e;
+        caps[k] = (uint32_t)(blocks > 0 ? blocks : 1) * (uint32_t)prop.multiProcessorCount;
+    }
+    return hipSuccess;
+}
+// bytes of one wave's slab rows (64 lanes x PT_Q_SLAB_ENTRIES); defined in pt_query.hip, so the stress build's value is its kernels'
+size_t pt_resident_wave_slab_bytes();
+
 // ---- ray queries (pt_query.hip): mode PT_QUERY_CLOSEST / PT_QUERY_ANY_HIT / 2 = closest + surface ----
 #define PT_QUERY_KERNELS 12
 inline int pt_query_kernel_index(bool tlas, uint32_t mode, bool stats) { return ((tlas ? 3 : 0) + (int)mode) * 2 + (stats ? 1 : 0); }
-// resident one-wave workgroups per device of every query kernel (occupancy x CUs): the grid cap, and the slab waves it needs
 hipError_t pt_query_grid_caps(int device, uint32_t caps[PT_QUERY_KERNELS]);
-size_t pt_query_slab_bytes_per_wave();
 // count <= 2^31; rays: 2 float4 per ray, hits: 1 float4 per ray, surface (mode 2): 3 float4 per ray; slab holds >= gridCap waves
 hipError_t pt_launch_query(const DScene& S, const float4* rays, uint32_t count, uint32_t mode, bool stats, float4* hits,
                            float4* surface, uint2* slab, uint32_t gridCap, unsigned long long* gstats, hipStream_t stream);
 
 // ---- guides and denoising (pt_denoise.hip) ----
-// resident one-wave workgroups per device of the two guide kernels (flat, HAS_TLAS): the grid cap, and the slab waves it needs
+// the two guide kernels (flat, HAS_TLAS)
 hipError_t pt_guide_grid_caps(int device, uint32_t caps[2]);
-size_t pt_guide_slab_bytes_per_wave();
 // n x n sub-pixel samples per pixel of P's OutputWidth x OutputHeight; albedo / normalDepth: one float4 per pixel each
 hipError_t pt_launch_guides(const DScene& S, const PTFrameParams& P, uint32_t n, float4* albedo, float4* normalDepth, uint2* slab,
                             uint32_t gridCap, hipStream_t stream);

@@ -14,8 +14,6 @@
 #include "pt_device.h"
 #include "pt_launch.h"
 
-#define PT_Q_SLAB_ENTRIES (PT_BVH_STACK_SIZE - PT_Q_LDS_STACK)
-
 namespace {
 
 enum : uint32_t { Q_CLOSEST = 0u, Q_ANY_HIT = 1u, Q_SURFACE = 2u };
@@ -24,18 +22,10 @@ template <uint32_t MODE, bool STATS, bool TLAS>
 PT_DEV void query_body(const DScene& S, const float4* __restrict__ rays, uint32_t count, float4* __restrict__ hits,
                        float4* __restrict__ surface, uint2* __restrict__ slab, unsigned long long* __restrict__ gstats)
 {
-    __shared__ uint2 s_stack[PT_Q_LDS_STACK][64];
-    __shared__ uint32_t s_gw;
     const uint32_t lane = threadIdx.x;
-    if (lane == 0u) s_gw = blockIdx.x;                                  // slab row = wave * 64 + lane (grid <= slab waves)
-    __builtin_amdgcn_wave_barrier();
-
     Counters cn = {};
     TravStackT<PT_Q_LDS_STACK, true> st;
-    st.lds = PT_LDS_U2(&s_stack[0][lane]);
-    st.stride = 64u;
-    st.gbase = slab;
-    st.gwave = PT_LDS_WORD(s_gw);
+    resident_wave_stack(st, slab);
 
     for (uint32_t base = blockIdx.x * 64u; base < count; base += gridDim.x * 64u) {
         const uint32_t i = base + lane;
@@ -46,9 +36,7 @@ PT_DEV void query_body(const DScene& S, const float4* __restrict__ rays, uint32_
         if (STATS) { if (MODE == Q_ANY_HIT) cn.shadowRays++; else cn.closestRays++; }
         // tmax NaN or <= 0: a miss by definition, no walk (the comparison is false for NaN)
         const bool walk = tmax > 0.0f;
-        HitRecord rec;
-        rec.h.t = tmax; rec.h.u = 0.0f; rec.h.v = 0.0f; rec.h.triIndex = 0xFFFFFFFFu;
-        rec.pos = mk3(0.0f); rec.inst = 0xFFFFFFFFu;
+        HitRecord rec = miss_record(tmax);
         bool found = false;
         if (walk) {
             if (TLAS) {
@@ -123,20 +111,11 @@ const QueryKernel kQueryKernels[PT_QUERY_KERNELS] = {
 };
 } // namespace
 
-size_t pt_query_slab_bytes_per_wave() { return (size_t)64 * PT_Q_SLAB_ENTRIES * sizeof(uint2); }
+size_t pt_resident_wave_slab_bytes() { return (size_t)64 * PT_Q_SLAB_ENTRIES * sizeof(uint2); }
 
 hipError_t pt_query_grid_caps(int device, uint32_t caps[PT_QUERY_KERNELS])
 {
-    hipDeviceProp_t prop;
-    hipError_t e = hipGetDeviceProperties(&prop, device);
-    if (e != hipSuccess) return e;
-    for (int k = 0; k < PT_QUERY_KERNELS; ++k) {
-        int blocks = 0;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, reinterpret_cast<const void*>(kQueryKernels[k]), 64, 0);
-        if (e != hipSuccess) return e;
-        caps[k] = (uint32_t)(blocks > 0 ? blocks : 1) * (uint32_t)prop.multiProcessorCount;
-    }
-    return hipSuccess;
+    return pt_resident_wave_caps(device, kQueryKernels, PT_QUERY_KERNELS, caps);
 }
 
 hipError_t pt_launch_query(const DScene& S, const float4* rays, uint32_t count, uint32_t mode, bool stats, float4* hits,
